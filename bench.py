@@ -3,13 +3,17 @@
 Chamfer regulariser, on N GPUs of one node (BASELINE.json configs[1]; one rank per GPU, independent attack
 instances per rank, one RCCL broadcast of the frozen weights, no per-iteration collective).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-sweep] [--no-cpu-baseline]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" = one pass of the hot-loop body for the whole batch: victim forward, adversarial + Chamfer loss,
 backward to the input points, Adam step, per-point clip, best-attack bookkeeping — inputs already resident in HBM.
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` (dominant kernel, measured live
-with HIP events) and `cpu_baseline` (the oracle's torch-CPU restatement of the same loop, timed on the host cores).
+Prints ONE JSON line on rank 0 (contract in the task description). A plain run sets up, warms up, times the K steps
+and prints the headline (`value`, `ms_per_step`). `--full` adds everything else, in the order of DESIGN.md §5:
+`roofline` (dominant kernel, measured live with HIP events) and `chamfer` before the headline loop, then `sweep` (the
+other sizes and BASELINE configs) and `cpu_baseline` (the oracle's torch-CPU restatement of the same loop, timed on the
+host cores); without `--full` those fields are null. `--dump-outputs DIR` writes the attack state the last timed step
+left (rank 0) as DIR/<name>.npy; the inputs are seeded, so runs with the same arguments compare array for array.
 """
 import argparse
 import importlib
@@ -234,14 +238,33 @@ def cpu_baseline(pcs, labels, seconds_budget=20.0):
             "sample": f"{n - 1} iterations of the same CW/PointNet/Chamfer step (B={B}, N={NPTS}) via oracle/ref_torch.py on torch-CPU"}
 
 
+# what one CW step leaves for its caller: the iterate it produced, the one it started from and that one's prediction and
+# L2 distance to the clean cloud, this binary step's and the overall best results ([B,3,N] layout as on the device)
+DUMPED_STATE = ("adv", "input_val", "pred", "dist_val", "bestdist", "bestscore", "o_bestdist", "o_bestscore", "o_bestattack")
+
+
+def dump_outputs(out_dir, st):
+    """DUMPED_STATE as out_dir/<name>.npy: float32 as computed, integer arrays as float64 (exact)."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    for name in DUMPED_STATE:
+        a = st[name].detach().cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.astype(np.float32 if a.dtype == np.float32 else np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sweep", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the kernel rooflines, Chamfer points, sweep and CPU baselines (tens of seconds more)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-sweep", action="store_true", help="with --full: skip the sweep")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the state of the last timed step as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -309,7 +332,7 @@ def main():
     # headline (the sweep below runs several seconds of other work), and the GPU enters the W warm-up steps at its
     # working clocks instead of from idle (a 20-step timed region is 6 ms long: a clock ramp is 5 % of it)
     roofline = chamfer = None
-    if rank == 0:
+    if args.full and rank == 0:
         # ---- the Chamfer kernel at N=4096 (north_star's second figure): VALU-bound, HBM share reported too.
         # Three timings per size: `values` = what Chamfer / Hausdorff VALUES need (utils/dis_utils_*.py, the metric's
         # kernel: scan + fold launches, no arg-min), `with_idx` = values + both arg-min index arrays (what the
@@ -395,6 +418,18 @@ def main():
         roofline = {"kernel": "pointmlp3_max_fwd_kernel", "bound": "mfma", "achieved": ach,
                     "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": ach / MFMA_F32_PEAK_TFLOPS,
                     "traffic": traffic, "traffic_source": pmc_src, "launch_us": k_ms * 1e3, "launches_per_step": 2}
+    elif not args.full:
+        # Without the measurements above the W warm-up steps would start on an idle GPU that raises its clocks over tens of
+        # ms of load (--steps 20 --warmup 5: 3294-3304 iters/s from idle, 3475-3486 after this; 2000 steps: equal, DESIGN.md
+        # §5). So CLOCK_WARM_MS of the step's dominant kernel first; it reads the iterate and writes only its own outputs.
+        x = st["adv"].detach()
+        tower = model.feat.folded()
+        tw = time.perf_counter()
+        while time.perf_counter() - tw < CLOCK_WARM_MS * 1e-3:
+            for _ in range(20):
+                ops.pointmlp3_max_fwd_raw(x, tower, False, fold=False)
+            torch.cuda.synchronize()
+        del x
 
     it = 0
     for _ in range(args.warmup):
@@ -429,12 +464,14 @@ def main():
     elapsed, per_rank_elapsed = across_ranks(elapsed)
     ms_per_step = elapsed * 1e3 / args.steps
     iters_per_s = world * args.steps / elapsed     # whole job: every rank advances its own batch each step
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, st)
 
     # ---- the other shapes of the same path, on EVERY rank (the collectives inside line up): north_star's N = 2048 /
     # 4096 clouds, the reference's default L2 regulariser, and one GPU's share of BASELINE configs[4] (CW on CurveNet,
     # 32 of the 256 clouds, N=4096). Reported as whole-job rates over the slowest rank, with the per-rank times.
     sweep = None
-    if not args.no_sweep:
+    if args.full and not args.no_sweep:
         sweep = {}
 
         def time_cw(victim, trans, npts, dname, warm, iters, seed):
@@ -664,7 +701,7 @@ def main():
         out["sweep"] = sweep
         out["per_rank_ms_per_step"] = [e * 1e3 / args.steps for e in per_rank_elapsed]
         out["gather_results"] = gather
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(pcs, labels)
             out["chamfer"]["cpu_baseline"] = chamfer_cpu_baseline()
             out["chamfer"]["cpu_baseline"]["gpu_us_per_pair"] = {

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 for ctr in FETCH_SIZE WRITE_SIZE; do
   out=$root/gpurun_out/pmc_${tag}_$ctr
   mkdir -p $out
-  rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $out -- python3 $root/bench.py --steps 40 --warmup 5 --no-sweep --no-cpu-baseline > $out/bench.log 2>&1
+  rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $out -- python3 $root/bench.py --full --steps 40 --warmup 5 --no-sweep --no-cpu-baseline > $out/bench.log 2>&1
 done
 python3 - "$root" "$tag" <<'PY'
 import csv, glob, json, sys, collections
