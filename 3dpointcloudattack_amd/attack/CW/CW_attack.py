@@ -480,16 +480,9 @@ class CW:
         with ops.deterministic(self.deterministic):
             return self._attack(data, target)
 
-    def _attack(self, data, target):
-        """Attack on given data to target.
-        Args:
-            data (torch.FloatTensor): victim data, [B, num_points, 3]
-            target (torch.LongTensor): target output, [B]
-        Returns (o_bestdist [B] float64, o_bestattack [B,K,3] float64, success_num) like the reference (:260).
-        """
-        dev = self.device
-        st = self._begin(data, target)
-        target = st["target"]
+    def _search(self, st):
+        """The binary search (reference :93-200): every step restarts from a fresh start point, runs num_iter iterations
+        (captured into hipGraphs when the body allows) and adjusts the weights once on the host."""
         run = None
         self.weight_history = []          # [binary_step][B]: the distance weight every binary step ran with (reference :93-200)
         for binary_step in range(self.binary_step):
@@ -520,12 +513,26 @@ class CW:
                 run.flush()
             self._end_binary_step(st)
 
+    def _outcome(self, st):
+        """(success_num, o_bestattack [B,3,K]) after the search: success counted on the last prediction; samples that
+        never succeeded take the last iterate (reference :205-209)."""
         pred = st["pred"] if self.num_iter > 0 and self.binary_step > 0 else None
         success_num = int(self._success(pred, st["label"]).sum().item()) if pred is not None else 0
+        fail_idx = torch.from_numpy(st["lower_bound"] == 0.).to(self.device)
+        return success_num, torch.where(fail_idx[:, None, None], st["input_val"], st["o_bestattack"])
 
-        # fail to attack some examples: assign them the last iterate (reference :205-209)
-        fail_idx = torch.from_numpy(st["lower_bound"] == 0.).to(dev)
-        o_bestattack = torch.where(fail_idx[:, None, None], st["input_val"], st["o_bestattack"])
+    def _attack(self, data, target):
+        """Attack on given data to target.
+        Args:
+            data (torch.FloatTensor): victim data, [B, num_points, 3]
+            target (torch.LongTensor): target output, [B]
+        Returns (o_bestdist [B] float64, o_bestattack [B,K,3] float64, success_num) like the reference (:260).
+        """
+        dev = self.device
+        st = self._begin(data, target)
+        target = st["target"]
+        self._search(st)
+        success_num, o_bestattack = self._outcome(st)
         o_bestdist = st["o_bestdist"]
 
         with torch.no_grad():

@@ -1,0 +1,3 @@
+"""attack/Gen3DAdv/utils/distance.py mirror. The reference's file is a copy of attack/CW/CW_utils/distance.py (whitespace
+aside), so this re-exports that mirror: the same classes, which the attacks' fast-path type checks recognise."""
+from ...CW.CW_utils.distance import *  # noqa: F401,F403

@@ -30,6 +30,21 @@ def _logits_of(out):
     return out[0] if isinstance(out, tuple) else out
 
 
+TRANSFER_MODELS = (("pt_fail", "pt_model"), ("ptm_fail", "ptm_model"), ("pts_fail", "pts_model"),
+                   ("dgcnn_fail", "dgcnn_model"), ("cur_fail", "cur_model"))
+
+
+def count_transfer_fails(attack, result, target):
+    """The five transfer checks (reference :160-240): every transfer model the attack holds (None: skipped) classifies
+    `result` [B,3,K]; its counter grows by the samples on which the attack does not succeed there."""
+    for name, attr in TRANSFER_MODELS:
+        m = getattr(attack, attr)
+        if m is None:
+            continue
+        p = torch.argmax(_logits_of(m(result)), dim=1)
+        setattr(attack, name, getattr(attack, name) + int((~attack._success(p, target)).sum().item()))
+
+
 class CWKNN:
     """Class for CW attack."""
 
@@ -234,12 +249,7 @@ class CWKNN:
             result = adv_data.detach().float()
             # Test attack + transfer models (:160-240)
             self.attack_fail += int((~self._success(torch.argmax(_logits_of(self.model(result)), dim=1), target)).sum().item())
-            for name, m in (("pt_fail", self.pt_model), ("ptm_fail", self.ptm_model), ("pts_fail", self.pts_model),
-                            ("dgcnn_fail", self.dgcnn_model), ("cur_fail", self.cur_model)):
-                if m is None:
-                    continue
-                p = torch.argmax(_logits_of(m(result)), dim=1)
-                setattr(self, name, getattr(self, name) + int((~self._success(p, target)).sum().item()))
+            count_transfer_fails(self, result, target)
 
         adv_np = adv_data.detach().transpose(1, 2).contiguous().cpu().numpy()  # [B, K, 3]
         return adv_np, success_num

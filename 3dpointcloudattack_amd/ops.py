@@ -801,6 +801,60 @@ def cw_update(adv, ori, pred, label, untarget, bestdist, bestscore, o_bestdist, 
     return adv
 
 
+ADD_UPDATE_MAX_POINTS = 2048   # pc3d_add_update_f32 keeps a sample's added points in registers (4 per thread x 512)
+ADD_UPDATE_MAX_CLUSTER = 64    # ... and gives every cluster of the farthest-pair term one wavefront
+ADD_KINDS = {"chamfer": 1, "hausdorff": 2, "far_chamfer": 3}
+
+
+def add_update(adv, ori, nn_d, nn_idx, pred, label, untarget, bestdist, bestscore, o_bestdist, o_bestscore, o_bestattack,
+               g, m, v, step, lr, kind, w, input_val=None, dist_val=None, cd_w=1.0, P=0, betas=(0.9, 0.999), eps=1e-8):
+    """The point-adding attacks' iteration in one launch (see pc3d_add_update_f32): set distance adv -> ori from the
+    search output (nn_d / nn_idx of nn_raw(adv, ori)), bookkeeping on it, total gradient g + w[b] * d dist / d adv and
+    Adam without clip, in place on `adv` ([B,3,A], any strides). o_bestattack / input_val / m / v: contiguous [B,3,A].
+    kind: a key of ADD_KINDS; far_chamfer takes clusters of P consecutive added points and the Chamfer weight cd_w."""
+    _, _, _, _, B, A = _pts(adv, True, "adv")
+    _, _, _, _, B2, K = _pts(ori, True, "ori")
+    if B2 != B:
+        raise ValueError("add_update: adv and ori must have the same batch dimension")
+    if A > ADD_UPDATE_MAX_POINTS:
+        raise ValueError(f"add_update: {A} added points; the update launch holds at most {ADD_UPDATE_MAX_POINTS} per sample")
+    k = ADD_KINDS[kind]
+    if k == 3 and not (1 <= P <= ADD_UPDATE_MAX_CLUSTER and A % P == 0):
+        raise ValueError(f"add_update: clusters of {P} points must tile {A} added points (1 <= P <= {ADD_UPDATE_MAX_CLUSTER})")
+    for nm, t in (("o_bestattack", o_bestattack), ("m", m), ("v", v), ("input_val", input_val)):
+        if t is not None:
+            _check(t, nm)
+            if tuple(t.shape) != (B, 3, A) or not t.is_contiguous():
+                raise ValueError(f"add_update: {nm} must be a contiguous [B,3,A] tensor")
+    _pts(g, True, "g")
+    if tuple(g.shape) != (B, 3, A):
+        raise ValueError(f"add_update: g must be [B,3,A] = {(B, 3, A)} (any strides), got {tuple(g.shape)}")
+    for nm, t, dt in (("nn_d", nn_d, torch.float32), ("nn_idx", nn_idx, torch.int32)):
+        if t.dtype != dt or tuple(t.shape) != (B, A) or not t.is_contiguous():
+            raise ValueError(f"add_update: {nm} must be a contiguous [B,A] {dt} tensor")
+    for nm, t, dt in (("pred", pred, torch.int64), ("label", label, torch.int64), ("bestdist", bestdist, torch.float32),
+                      ("bestscore", bestscore, torch.int64), ("o_bestdist", o_bestdist, torch.float32),
+                      ("o_bestscore", o_bestscore, torch.int64), ("w", w, torch.float32),
+                      ("dist_val", dist_val, torch.float32)):
+        if t is None and nm == "dist_val":
+            continue
+        if not isinstance(t, torch.Tensor) or t.device != adv.device or t.dtype != dt or tuple(t.shape) != (B,) \
+                or not t.is_contiguous():
+            raise ValueError(f"add_update: {nm} must be a contiguous [B] {dt} tensor on {adv.device}")
+    if isinstance(step, torch.Tensor):
+        step_dev, step_host = step.data_ptr(), 0
+    else:
+        step_dev, step_host = 0, int(step)
+    with torch.cuda.device(adv.device):
+        _lib.call("pc3d_add_update_f32", *_pv(adv, True, "adv"), *_pv(ori, True, "ori"), B, A, K, nn_d.data_ptr(),
+                  nn_idx.data_ptr(), pred.data_ptr(), label.data_ptr(), 1 if untarget else 0, bestdist.data_ptr(),
+                  bestscore.data_ptr(), o_bestdist.data_ptr(), o_bestscore.data_ptr(), o_bestattack.data_ptr(),
+                  _ptr(input_val), _ptr(dist_val), *_pv(g, True, "g"), m.data_ptr(), v.data_ptr(), float(lr),
+                  float(betas[0]), float(betas[1]), float(eps), step_dev, step_host, k, w.data_ptr(), float(cd_w),
+                  int(P), _stream())
+    return adv
+
+
 def cw_bookkeep(adv, ori, pred, label, untarget, bestdist, bestscore, o_bestdist, o_bestscore, o_bestattack,
                 input_val=None, dist_val=None, step=None, cf=True):
     """In-place update of the best-attack state for one iteration (see pc3d_cw_bookkeep_f32)."""

@@ -830,6 +830,22 @@ int pc3d_cw_update_f32(float* adv, int64_t a_bs, int64_t a_ps, int64_t a_cs,
                        const int32_t* step_dev, int step_host, int dist_kind, const float* w,
                        const int32_t* nn_idx, void* stream);
 
+/* The point-adding attacks' iteration (attack/Gen3DAdv CWAdd / CWAddClusters) as ONE launch, one workgroup per sample:
+ * the set distance adv -> ori from the search output (nn_d / nn_idx [B,A], pc3d_nn_f32), bookkeeping on it, total
+ * gradient (g, the victim's gradient on the A added columns, + w[b] * d distance / d adv) and Adam without clip, written
+ * back through adv's strides. kind: 1 Chamfer adv2ori (mean), 2 Hausdorff adv2ori (max), 3 FarChamfer (farthest
+ * intra-cluster pair over A/P clusters of P points + cd_w * Chamfer). o_bestattack / input_val / m / v are contiguous
+ * [B,3,A]; input_val / dist_val may be NULL. 1 <= A <= 2048, 1 <= P <= 64 with A % P == 0. The step number is READ
+ * from *step_dev (or step_host). */
+int pc3d_add_update_f32(float* adv, int64_t a_bs, int64_t a_ps, int64_t a_cs,
+                        const float* ori, int64_t o_bs, int64_t o_ps, int64_t o_cs, int B, int A, int K,
+                        const float* nn_d, const int32_t* nn_idx, const int64_t* pred, const int64_t* label,
+                        int untarget, float* bestdist, int64_t* bestscore, float* o_bestdist, int64_t* o_bestscore,
+                        float* o_bestattack, float* input_val, float* dist_val,
+                        const float* g, int64_t g_bs, int64_t g_ps, int64_t g_cs, float* m, float* v,
+                        double lr, double beta1, double beta2, double eps, const int32_t* step_dev, int step_host,
+                        int kind, const float* w, float cd_w, int P, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
