@@ -141,6 +141,11 @@ SIGNATURES = {
     "pc3d_pointmlp3_bwd_tile_points": [],
     "pc3d_linear_f32": [_P, _I, _I, _I, _I, _P, _P, _I, _I, _F, _P, _I, _F, _P, _I, _P],
     "pc3d_cls_loss_f32": [_P, _I, _I, _I, _P, _I, _F, _F, _P, _P, _P, _P, _P],
+    "pc3d_sor_select_f32": [_P] + _PTS + [_I, _I, _I, _D, _I, _P, _P, _P, _P, _P] + _PTS + [_P],
+    "pc3d_sor_fused_f32": _PTS + [_I, _I, _I, _D, _I, _P, _P, _P, _P, _P, _P] + _PTS + [_P],
+    "pc3d_sor_bwd_f32": _PTS + [_P, _P, _I, _I, _I] + _PTS + [_P],
+    "pc3d_srs_select_i32": [_L, _P, _I, _I, _I, _I, _P, _P],
+    "pc3d_gather_points_f32": _PTS + [_P, _I, _I, _I] + _PTS + [_P],
 }
 
 # entry points that do not return a status code

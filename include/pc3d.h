@@ -846,6 +846,41 @@ int pc3d_add_update_f32(float* adv, int64_t a_bs, int64_t a_ps, int64_t a_cs,
                         double lr, double beta1, double beta2, double eps, const int32_t* step_dev, int step_host,
                         int kind, const float* w, float cd_w, int P, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Point-dropping defences in front of a victim (attack/SIadv/baselines/defense/drop_points/SOR.py, SRS.py).
+ * ------------------------------------------------------------------------------------------------------- */
+/* Statistical outlier removal (SOR.py:24-76) after the search, ONE launch, one workgroup per cloud. dists [B,K,k1]: the
+ * k1 = k + 1 ascending squared distances of the self-kNN search (pc3d_knn_f32 on q == r: column 0 is the point itself).
+ * v[b,i] = mean of columns 1 .. k; thr[b] = mean_i v + alpha * std_i v (unbiased), both in fp64 with a fixed summation
+ * order; the points with v <= thr are kept in ascending index order, count[b] = n_b of them; rank [B,K] = position among
+ * the kept or -1; src [B,npoint] = kept_b[j mod n_b] (the reference's repeat-then-top-up padding); out [B,npoint]
+ * (element strides) = the points of x at src. v [B,K] / thr [B] (fp32 copies) may be NULL. 2 <= k1 <= K <= npoint,
+ * K <= 8192. A cloud whose v are all NaN keeps nothing: count 0, src -1, out NaN. */
+int pc3d_sor_select_f32(const float* dists, const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int K, int k1,
+                        double alpha, int npoint, float* v, float* thr, int32_t* count, int32_t* rank, int32_t* src,
+                        float* out, int64_t o_bs, int64_t o_ps, int64_t o_cs, void* stream);
+/* Search and selection in one launch: the cloud in LDS, every point scans it with the search's arithmetic (the same
+ * distance bits as pc3d_knn_f32). dists [B,K,k1] is written (and must be given). k1 <= 9, K <= 4096. One workgroup per
+ * cloud: B of the chip's 256 compute units work, where the two-launch form's search fills all of them. */
+int pc3d_sor_fused_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int K, int k1, double alpha, int npoint,
+                       float* dists, float* v, float* thr, int32_t* count, int32_t* rank, int32_t* src,
+                       float* out, int64_t o_bs, int64_t o_ps, int64_t o_cs, void* stream);
+/* Backward of the copies: grad[b,i,:] = sum over j = rank[b,i], rank + n_b, ... < npoint of g[b,j,:] in ascending j, zero
+ * for dropped points. One thread per input point, no atomics: the same bits in every run and for every batch size. */
+int pc3d_sor_bwd_f32(const float* g, int64_t g_bs, int64_t g_ps, int64_t g_cs, const int32_t* count, const int32_t* rank,
+                     int B, int K, int npoint, float* grad, int64_t gr_bs, int64_t gr_ps, int64_t gr_cs, void* stream);
+/* Simple random sampling drawn on the device (SRS.py:23-32 draws on the host with numpy): idx [B,M] = M distinct indices
+ * of [0,K) per cloud, uniformly chosen and in random order — every point gets the key hash(seed, call, b, i), the M
+ * smallest keys win (bitonic network in LDS), indices are emitted in key order. `call` is read from *counter (a device
+ * word the caller advances with pc3d_i32_add, so replays of a captured graph draw new subsets) or, with counter NULL,
+ * is counter_host. 1 <= M <= K <= 4096. */
+int pc3d_srs_select_i32(int64_t seed, const int32_t* counter, int counter_host, int B, int K, int M, int32_t* idx,
+                        void* stream);
+/* out[b,j,:] = x[b,idx[b,j],:] for an index table idx [B,M] int32 (element strides on both sides); an index outside
+ * [0,K) reads nothing and writes NaN. */
+int pc3d_gather_points_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, const int32_t* idx, int B, int K, int M,
+                           float* out, int64_t o_bs, int64_t o_ps, int64_t o_cs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
