@@ -10,6 +10,9 @@ tensors. Here SOR is the self-kNN search plus ONE launch (pc3d_sor_select_f32: s
 padding, gather) with a gather-form backward (pc3d_sor_bwd_f32), has a fixed output shape and never touches the host, so
 a defended victim runs inside an attack loop and inside ``torch.cuda.graph``.
 
+``DUPNet`` (SOR followed by the PU-Net upsampler, attack/SIadv/baselines/defense/DUP_Net) is exported from here too; it lives
+under the reference's import path.
+
 ``Defended(model, head)`` is the composition as an ``nn.Module``; ``evaluate_defended`` is the after-the-attack table
 row. There is no CPU fallback: tensors must live on the GPU.
 
@@ -257,3 +260,12 @@ def evaluate_defended(model, head, clouds, labels, batch=32):
             res[1, s:s + pred.shape[0]] = (pred == labels[s:s + pred.shape[0]]).long()
     host = res.cpu().numpy()
     return dict(pred=host[0], correct=host[1].astype(bool), count=int(host[1].sum()))
+
+
+def __getattr__(name):
+    """``DUPNet`` / ``PUNet`` (the third head: SOR + the PU-Net upsampler) live under the reference's import path,
+    attack/SIadv/baselines/defense/DUP_Net, which imports SORDefense from here: resolved on first use."""
+    if name in ("DUPNet", "PUNet", "load_punet_weights"):
+        from .attack.SIadv.baselines.defense.DUP_Net import DUP_Net as _dup
+        return getattr(_dup, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

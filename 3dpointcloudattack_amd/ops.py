@@ -2690,3 +2690,159 @@ def linear_relu_max(x, w, b):
         raise ValueError(f"linear_relu_max: group size {ns} exceeds {GROUP_MAX_NS}")
     out = _LinearReLUMaxFn.apply(x.reshape(-1, ns, C2).contiguous(), w.contiguous(), b.contiguous())
     return out.view(*lead, w.shape[0])
+
+
+# ------------------------------------------------------------------------------------------------------
+# PU-Net (the DUP-Net defence): 3-NN interpolation of a feature-propagation level, the coordinate head
+# ------------------------------------------------------------------------------------------------------
+def _interp_shapes(unknown, known, feats, u_cf, k_cf):
+    """(B, N, M, C) of a three_interp call from the shapes alone (ValueError before any tensor reaches the device)."""
+    for t, nm in ((unknown, "unknown"), (known, "known"), (feats, "feats")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3:
+            raise ValueError(f"three_interp: {nm} must be a 3-d tensor, got {tuple(getattr(t, 'shape', ()))}")
+    B, N = unknown.shape[0], unknown.shape[2 if u_cf else 1]
+    M = known.shape[2 if k_cf else 1]
+    if unknown.shape[1 if u_cf else 2] != 3 or known.shape[1 if k_cf else 2] != 3:
+        raise ValueError("three_interp: unknown / known must hold 3 coordinates per point")
+    if known.shape[0] != B or feats.shape[0] != B or feats.shape[1] != M:
+        raise ValueError(f"three_interp: feats {tuple(feats.shape)} does not fit known points [B={B}, M={M}]")
+    C = feats.shape[2]
+    if M < 3 or C % 4 or C < 4:
+        raise ValueError(f"three_interp: M={M} >= 3 known points and C={C} a multiple of 4 expected")
+    return B, N, M, C
+
+
+def three_interp_raw(d, idx, feats, out, col, C, bias=None, relu=False):
+    """The forward launch: columns [col, col + C) of out [B,N,ld] from the search's lists d / idx [B,N,3]."""
+    B, N, _ = d.shape
+    M = feats.shape[1]
+    with torch.cuda.device(d.device):
+        _lib.call("pc3d_three_interp_f32", d.data_ptr(), idx.data_ptr(), feats.data_ptr(), feats.stride(1), B, N, M, C,
+                  _ptr(bias), 1 if relu else 0, out.data_ptr() + 4 * col, out.stride(1), _stream())
+    return out
+
+
+class _ThreeInterpFn(torch.autograd.Function):
+    """out[..., col:col+C] = act(interp(feats) + bias); with a caller's buffer the buffer is returned (modified in place, so
+    several levels chain through it and autograd orders them); backward: gradients to unknown, known (through the
+    distances, pu_modules.py:161-168) and feats, the scatter to the known rows as a gather through the reverse index."""
+
+    @staticmethod
+    def forward(ctx, unknown, known, feats, out, col, bias, relu, u_cf, k_cf):
+        B, N, M, C = _interp_shapes(unknown, known, feats, u_cf, k_cf)
+        d, idx = knn_raw(unknown, known, 3, u_cf, k_cf)
+        own = out is None
+        if own:
+            out = torch.empty((B, N, C), dtype=torch.float32, device=feats.device)
+        else:
+            ctx.mark_dirty(out)
+        three_interp_raw(d, idx, feats, out, col, C, bias, relu)
+        # (the caller's buffer is written again by the next level — other columns — so its version counter moves on: the
+        # ReLU mask is read through an alias that does not carry it)
+        ctx.save_for_backward(unknown, known, feats, d, idx, out.data if relu else None)
+        ctx.cfg = (B, N, M, C, col, u_cf, k_cf, own)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        unknown, known, feats, d, idx, y = ctx.saved_tensors
+        B, N, M, C, col, u_cf, k_cf, own = ctx.cfg
+        if g.stride(2) != 1 or g.stride(0) != N * g.stride(1):
+            g = g.contiguous()
+        dev = g.device
+        off, lst = rev_index(idx, M)
+        wrec = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
+        krec = torch.empty((B, N, 3, 3), dtype=torch.float32, device=dev)
+        gu = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
+        gF = torch.empty((B, M, C), dtype=torch.float32, device=dev)
+        gk = torch.empty((B, M, 3), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.call("pc3d_three_interp_bwd_f32", *_pv(unknown, u_cf, "unknown"), *_pv(known, k_cf, "known"), d.data_ptr(),
+                      idx.data_ptr(), feats.data_ptr(), feats.stride(1), g.data_ptr() + 4 * col, g.stride(1),
+                      (y.data_ptr() + 4 * col) if y is not None else 0, y.stride(1) if y is not None else 0,
+                      off.data_ptr(), lst.data_ptr(), B, N, M, C, wrec.data_ptr(), krec.data_ptr(), gu.data_ptr(),
+                      gF.data_ptr(), gk.data_ptr(), _stream())
+        return (gu.permute(0, 2, 1) if u_cf else gu) if ctx.needs_input_grad[0] else None, \
+            (gk.permute(0, 2, 1) if k_cf else gk) if ctx.needs_input_grad[1] else None, \
+            gF if ctx.needs_input_grad[2] else None, (None if own else g), None, None, None, None, None
+
+
+def three_interp(unknown, known, feats, out=None, col=0, bias=None, relu=False, u_cf=False, k_cf=False):
+    """3-NN inverse-distance interpolation (pu_modules.py:158-168) of feats [B,M,C] (channels-last, at the known points
+    [B,M,3]) at the unknown points [B,N,3] ([B,3,*] with u_cf / k_cf): act(sum_j w_j feats[idx_j] + bias), w_j ~ 1 /
+    (d_j + 1e-8) normalised. out=None: a new [B,N,C] tensor; else the columns [col, col + C) of the caller's contiguous
+    [B,N,ld] buffer are written and the buffer is returned. Differentiable in unknown, known and feats."""
+    B, N, M, C = _interp_shapes(unknown, known, feats, u_cf, k_cf)
+    _check(unknown, "unknown"), _check(known, "known"), _check(feats, "feats")
+    if feats.stride(2) != 1 or feats.stride(1) % 4 or feats.stride(0) != M * feats.stride(1):
+        feats = feats.contiguous()
+    if bias is not None:
+        _check(bias, "bias")
+        bias = bias.detach().contiguous()
+        if bias.shape != (C,):
+            raise ValueError(f"three_interp: bias must be [C={C}]")
+    if out is not None:
+        _check(out, "out")
+        if out.dim() != 3 or out.shape[0] != B or out.shape[1] != N or not out.is_contiguous() or not (0 <= col <= out.shape[2] - C):
+            raise ValueError(f"three_interp: out must be a contiguous [B={B},N={N},ld] buffer with ld >= col + C")
+    elif col:
+        raise ValueError("three_interp: a column offset needs an output buffer")
+    return _ThreeInterpFn.apply(unknown, known, feats, out, int(col), bias, bool(relu), bool(u_cf), bool(k_cf))
+
+
+PCD_TAIL_WIDTHS = (128, 64, 3)
+
+
+def _tail_shapes(h, w3, b3, w4, b4, B, N, r):
+    C2, C3, C4 = PCD_TAIL_WIDTHS
+    if not isinstance(h, torch.Tensor) or h.dim() != 2 or tuple(h.shape) != (r * B * N, C2):
+        raise ValueError(f"pcd_tail: h must be [r*B*N={r * B * N}, {C2}], got {tuple(getattr(h, 'shape', ()))}")
+    if tuple(w3.shape) != (C3, C2) or tuple(b3.shape) != (C3,) or tuple(w4.shape) != (C4, C3) or tuple(b4.shape) != (C4,):
+        raise ValueError(f"pcd_tail: weights of a {C2} -> {C3} -> {C4} head expected")
+
+
+def pcd_tail_raw(h, w3, b3, w4, b4, B, N, r):
+    """(out [B, r*N, 3], mask [r*B*N, 2] int32: the hidden layer's sign bits)."""
+    out = torch.empty((B, r * N, 3), dtype=torch.float32, device=h.device)
+    mask = torch.empty((r * B * N, 2), dtype=torch.int32, device=h.device)
+    with torch.cuda.device(h.device):
+        _lib.call("pc3d_pcd_tail_f32", h.data_ptr(), h.stride(0), w3.data_ptr(), b3.data_ptr(), w4.data_ptr(), b4.data_ptr(),
+                  B, N, r, w3.shape[1], w3.shape[0], mask.data_ptr(), out.data_ptr(), _stream())
+    return out, mask
+
+
+def pcd_tail_bwd_raw(g, mask, w3, w4, B, N, r):
+    gh = torch.empty((r * B * N, w3.shape[1]), dtype=torch.float32, device=g.device)
+    g = g.contiguous()
+    with torch.cuda.device(g.device):
+        _lib.call("pc3d_pcd_tail_bwd_f32", g.data_ptr(), mask.data_ptr(), w4.data_ptr(), _w_transposed(w3).data_ptr(), B, N, r,
+                  w3.shape[1], w3.shape[0], gh.data_ptr(), gh.stride(0), _stream())
+    return gh
+
+
+class _PcdTailFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, w3, b3, w4, b4, B, N, r):
+        out, mask = pcd_tail_raw(h, w3, b3, w4, b4, B, N, r)
+        ctx.save_for_backward(mask, w3, w4)
+        ctx.dims = (B, N, r)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        mask, w3, w4 = ctx.saved_tensors
+        return (pcd_tail_bwd_raw(g, mask, w3, w4, *ctx.dims),) + (None,) * 7
+
+
+def pcd_tail(h, w3, b3, w4, b4, B, N, r):
+    """PU-Net's coordinate head (pu_net.py:83-86,131): W4 relu(W3 h + b3) + b4 for h [r*B*N, 128] (the r expansion
+    branches one after the other) -> [B, r*N, 3], branch k at the points k*N .. (k+1)*N - 1. Frozen weights;
+    differentiable in h. One launch each way."""
+    B, N, r = int(B), int(N), int(r)
+    _tail_shapes(h, w3, b3, w4, b4, B, N, r)
+    for t, nm in ((h, "h"), (w3, "w3"), (b3, "b3"), (w4, "w4"), (b4, "b4")):
+        _check(t, nm)
+    if h.stride(1) != 1 or h.stride(0) % 4:
+        h = h.contiguous()
+    return _PcdTailFn.apply(h, w3.detach().contiguous(), b3.detach().contiguous(), w4.detach().contiguous(),
+                            b4.detach().contiguous(), B, N, r)

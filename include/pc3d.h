@@ -881,6 +881,37 @@ int pc3d_srs_select_i32(int64_t seed, const int32_t* counter, int counter_host, 
 int pc3d_gather_points_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, const int32_t* idx, int B, int K, int M,
                            float* out, int64_t o_bs, int64_t o_ps, int64_t o_cs, void* stream);
 
+/* -------------------------------------------------------------------------------------------------------
+ * PU-Net, the upsampler of the DUP-Net defence (attack/SIadv/baselines/defense/DUP_Net/).
+ * ------------------------------------------------------------------------------------------------------- */
+/* 3-NN inverse-distance interpolation of a feature-propagation level (pu_modules.py:161-168) from the search's lists:
+ * dists / idx [B,N,3] (pc3d_knn_f32 of the N unknown points among the M known ones), feats [B,M,ldf] channels-last.
+ * out[b,n,c] = act(sum_j w_j feats[b,idx_j,c] + bias[c]), w_j = r_j / (r_0 + r_1 + r_2), r_j = 1 / (d_j + 1e-8); out is
+ * [B,N,ldo] and points at the first of the C columns written (a column offset of a wider row buffer; any alignment).
+ * bias [C] may be NULL; relu != 0 applies max(., 0). C % 4 == 0, ldf % 4 == 0, M >= 3. */
+int pc3d_three_interp_f32(const float* dists, const int32_t* idx, const float* feats, int64_t ldf, int B, int N, int M, int C,
+                          const float* bias, int relu, float* out, int64_t ldo, void* stream);
+/* Backward to the known features AND to both coordinate sets (the reference differentiates through the distances):
+ * g [B,N,ldg] upstream gradient (at the column offset), y [B,N,ldy] the forward's output there (its sign is the ReLU mask)
+ * or NULL; u [B,N] / k [B,M] the unknown / known points (element strides). gu [B,N,3], gF [B,M,C], gk [B,M,3] are
+ * contiguous and fully written. rev_off [B,M+1] / rev_lst [B,3N]: the sorted reverse index of idx (pc3d_rev_index_i32):
+ * the scatter to the known rows is a gather through it in ascending order — no atomics, the same bits in every run and
+ * for every batch size. wrec [B,N,3] and krec [B,N,3,3] are scratch. */
+int pc3d_three_interp_bwd_f32(const float* u, int64_t u_bs, int64_t u_ps, int64_t u_cs, const float* k, int64_t k_bs,
+                              int64_t k_ps, int64_t k_cs, const float* dists, const int32_t* idx, const float* feats, int64_t ldf,
+                              const float* g, int64_t ldg, const float* y, int64_t ldy, const int32_t* rev_off,
+                              const int32_t* rev_lst, int B, int N, int M, int C, float* wrec, float* krec, float* gu, float* gF,
+                              float* gk, void* stream);
+/* The coordinate head (pu_net.py:83-86,131) in one launch: out = W4 relu(W3 h + b3) + b4 with widths C2 = 128 -> C3 = 64
+ * -> 3 on the fp32 MFMA. h [R*B*N, ldh] holds the R expansion branches one after the other (row (r*B + b)*N + n); out is
+ * [B, R*N, 3] with branch r at rows r*N .. (the reference concatenates the branches along the point axis). mask
+ * [R*B*N, 2] receives the sign bits of the 64 hidden channels of every row for the backward. */
+int pc3d_pcd_tail_f32(const float* h, int64_t ldh, const float* w3, const float* b3, const float* w4, const float* b4, int B,
+                      int N, int R, int C2, int C3, uint32_t* mask, float* out, void* stream);
+/* gh [R*B*N, ldgh] = (mask * (g W4)) W3 for the upstream gradient g [B, R*N, 3]; w3t [128,64] is W3 transposed. */
+int pc3d_pcd_tail_bwd_f32(const float* g, const uint32_t* mask, const float* w4, const float* w3t, int B, int N, int R, int C2,
+                          int C3, float* gh, int64_t ldgh, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
