@@ -323,6 +323,8 @@ struct PMBwdArgs {
   int accumulate;         // gx += instead of gx =
 };
 
+// The two-list form of the backward (kept for parity tests and tools/bench_pointmlp.py; pc3d_pointmlp3_max_bwd_f32
+// launches pointmlp3_max_bwd_kernel below, which computes the same bits).
 // Workgroup = (batch b, 32 points), 4 waves; <= 36 KiB LDS so four workgroups share a CU (the kernel is a chain of
 // dependent latencies, residency is what hides them).
 //  A. channels whose arg-max lies in the tile are compacted IN CHANNEL ORDER (block prefix sum) into two lists
@@ -331,7 +333,7 @@ struct PMBwdArgs {
 //     forward kernel hands over its decisions as bit masks: nothing is recomputed, and no decision can differ);
 //  C. g1 = (g2 masked) . W2 on MFMA with K = 128 split over wave pairs, masked by the forward's layer-1 bits;
 //  D. g' = g1 . W1 on the VALU, then the x' = x @ T chain (dL/dx, per-tile partial of dL/dT).
-__global__ __launch_bounds__(256) void pointmlp3_max_bwd_kernel(PMBwdArgs a) {
+__global__ __launch_bounds__(256) void pointmlp3_max_bwd_twolist_kernel(PMBwdArgs a) {
   __shared__ __attribute__((aligned(16))) float lds[PM_BTP * PM_LD2 + PM_BTP * PM_LD1 + 4 * PM_BTP + PM_MAXC3 + (3 * PM_MAXC3) / 2];  // 36.4 KB
   float* g2s = lds;                                   // [32][132]
   float* h1s = g2s + PM_BTP * PM_LD2;                 // [32][68]   g1
@@ -563,6 +565,366 @@ __global__ __launch_bounds__(256) void pointmlp3_max_bwd_kernel(PMBwdArgs a) {
   }
 }
 
+
+// The balanced form. Same grid, tile, LDS budget and arithmetic as the two-list kernel above; what differs is how the
+// layer-3 gather (phase A) is scheduled:
+//  A1. the tile's hits are compacted in channel order into ONE list of (local point, channel) pairs, then a stable
+//      counting sort over the 32 points orders them by point and, within a point, by ascending channel;
+//  A2. the four waves share out WHOLE points: point p goes to wave floor(4 * start[p] / L) (start = its offset in the
+//      sorted list, L = hits in the tile), so a wave gets at most ceil(L / 4) hits plus the rest of its last point.
+//      A lane holds a float2 of k (a W3 row is one 512-B request of the wave) and a point's row is the register chain
+//      acc = fma(g[c], W3[c,k], acc) from +0 in ascending channel order — the chain the two-list kernel forms through
+//      LDS read-modify-writes, so every bit of g2 is the same whichever wave runs it — written once with the layer-2
+//      mask applied. The walk is wave-uniform: one LDS read fetches up to 64 list entries (and one their gradients),
+//      v_readlane hands them out as scalars, so point changes are scalar branches and 32 independent row loads are in
+//      flight per wave with nothing but the FMAs behind them.
+// Everything that depends on nothing (T[b], the tile's raw x, the old gx of an accumulating launch, W1) is fetched at
+// entry, in front of the W2 operand prefetch, and parked in LDS. That prefetch reads W2 itself ([128][64]: 32 lanes =
+// 32 consecutive j of one k2 row, two 128-B lines per instruction) instead of W2T, where every lane of a float4 load
+// sits in a row of its own (64 lines per instruction; measured 2.5 us of the launch's first 5.8).
+constexpr int PM_BSEG = 8;           // list segments (of 32 lanes = 32 bins each) of the counting sort
+constexpr int PM_BFLY = 32;          // W3 rows in flight per wave
+
+// phase C of both backward kernels: g1 = (g2 masked) . W2 on MFMA, K split over wave pairs, layer-1 mask applied
+__device__ __forceinline__ void pm_bwd_phase_c(const float4 (&w2tr)[PM_C2 / 16], float* g2s, float* h1s,
+                                               const uint64_t* s_m1, int wave, int r, int h) {
+  f32x16 acc;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+  const int jb = wave & 1, kh = wave >> 1;
+#pragma unroll
+  for (int t = 0; t < PM_C2 / 16; ++t) {
+    const float4 bw = w2tr[t];
+    const float4 av = *reinterpret_cast<const float4*>(g2s + r * PM_LD2 + 64 * kh + 8 * t + 4 * h);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bw.x, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bw.y, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bw.z, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bw.w, acc, 0, 0, 0);
+  }
+  __syncthreads();   // g2s is dead once every wave has read its A operands: it doubles as the exchange buffer
+  float* cr = g2s + jb * (32 * 33);
+  if (kh == 1) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) cr[((e & 3) + 8 * (e >> 2) + 4 * h) * 33 + r] = acc[e];
+  }
+  __syncthreads();
+  if (kh == 0) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const int pt = (e & 3) + 8 * (e >> 2) + 4 * h;
+      const bool on = (s_m1[pt] >> (32 * jb + r)) & 1ull;          // layer-1 ReLU of the forward pass
+      h1s[pt * PM_LD1 + 32 * jb + r] = on ? (acc[e] + cr[pt * 33 + r]) : 0.f;
+    }
+  }
+}
+
+// a finished point's row: layer-2 ReLU of the forward pass, one store (lane = k 2*lane, 2*lane + 1)
+__device__ __forceinline__ void pm_bwd_put_row(const uint32_t (*s_m2)[4], float* g2s, int pt, int lane, float2 acc) {
+  const uint32_t m = s_m2[pt][lane >> 4] >> ((2 * lane) & 31);
+  float2 o;
+  o.x = (m & 1u) ? acc.x : 0.f, o.y = (m & 2u) ? acc.y : 0.f;
+  *reinterpret_cast<float2*>(g2s + pt * PM_LD2 + 2 * lane) = o;
+}
+
+// NB entries of the wave's current chunk, from entry u on: lane s of my_e / my_g holds entry s (point << 10 | channel)
+// and its gradient; nb = entries in the chunk. TAIL: the batch may reach past nb (entries at or past nb repeat the
+// last one and are not accumulated). Everything but the row loads and the FMAs is scalar.
+template <int NB, bool TAIL>
+__device__ __forceinline__ void pm_bwd_rows(const float* W3, int my_e, int my_g, const uint32_t (*s_m2)[4], float* g2s,
+                                            int u, int nb, int lane, float2& acc, int& cur) {
+  int e[NB];
+  float2 w[NB];
+#pragma unroll
+  for (int t = 0; t < NB; ++t) {
+    const int s = (!TAIL || u + t < nb) ? u + t : nb - 1;
+    e[t] = __builtin_amdgcn_readlane(my_e, s);
+    w[t] = *reinterpret_cast<const float2*>(W3 + (size_t)(uint32_t)((e[t] & (PM_MAXC3 - 1)) * PM_C2 + 2 * lane));
+  }
+#pragma unroll
+  for (int t = 0; t < NB; ++t) {
+    if (!TAIL || u + t < nb) {
+      const float gv = __builtin_bit_cast(float, __builtin_amdgcn_readlane(my_g, u + t));
+      const int n = e[t] >> 10;
+      if (__builtin_expect(n != cur, 0)) {
+        if (cur >= 0) pm_bwd_put_row(s_m2, g2s, cur, lane, acc);
+        acc = make_float2(0.f, 0.f);
+        cur = n;
+      }
+      acc.x = __builtin_fmaf(gv, w[t].x, acc.x);
+      acc.y = __builtin_fmaf(gv, w[t].y, acc.y);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void pointmlp3_max_bwd_kernel(PMBwdArgs a) {
+  __shared__ __attribute__((aligned(16))) float lds[PM_BTP * PM_LD2 + PM_BTP * PM_LD1 + 4 * PM_BTP + PM_MAXC3 + PM_MAXC3];  // 34.3 KB
+  float* g2s = lds;                                   // [32][132]
+  float* h1s = g2s + PM_BTP * PM_LD2;                 // [32][68]   g1 (phase C on); before that the sort's counters
+  float* xs = h1s + PM_BTP * PM_LD1;                  // [3][32]    scratch of phase D
+  int* s_scan = reinterpret_cast<int*>(xs + 3 * PM_BTP);   // [32] wave totals
+  float* s_g = xs + 4 * PM_BTP;                       // [C3]
+  unsigned short* s_hit = reinterpret_cast<unsigned short*>(s_g + PM_MAXC3);   // [C3] (point << 10 | channel), channel order
+  unsigned short* s_sorted = s_hit + PM_MAXC3;        // [C3] the same, ordered by (point, channel)
+  int* s_cnt = reinterpret_cast<int*>(h1s);           // [8][32] hits of point p in list segment q
+  int* s_start = s_cnt + PM_BSEG * PM_BTP;            // [33]    offset of point p in the sorted list
+  __shared__ uint32_t s_m2[PM_BTP][4];
+  __shared__ uint64_t s_m1[PM_BTP];
+  __shared__ float s_W1[PM_C1 * 3];
+  __shared__ float s_x[3 * PM_BTP], s_gxo[3 * PM_BTP], s_T[12];
+  static_assert(PM_MAXC3 <= 1024 && PM_BTP <= 32, "a hit is packed as point << 10 | channel in 16 bits");
+  const int tile = blockIdx.x, b = blockIdx.y;
+  const int n0 = tile * PM_BTP;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 31, h = lane >> 5;
+
+  // ---- entry: every load that depends on nothing, smallest first (vector-memory results return in issue order, so
+  // anything issued behind the 32 KiB weight prefetch below would wait for all of it)
+  int ld_n[PM_MAXC3 / 256];
+  float ld_g[PM_MAXC3 / 256];
+#pragma unroll
+  for (int e = 0; e < PM_MAXC3 / 256; ++e) {
+    const int c = tid * (PM_MAXC3 / 256) + e;
+    ld_n[e] = (c < a.C3) ? a.argidx[(int64_t)b * a.C3 + c] : -1;
+    ld_g[e] = (c < a.C3) ? a.g[(int64_t)b * a.C3 + c] : 0.f;
+  }
+  uint32_t ld_m2 = 0u;
+  uint64_t ld_m1 = 0ull;
+  if (tid < PM_BTP * 4 && n0 + (tid >> 2) < a.N) ld_m2 = a.mask2[((int64_t)b * a.N + n0) * 4 + tid];
+  if (tid < PM_BTP && n0 + tid < a.N) ld_m1 = a.mask1[(int64_t)b * a.N + n0 + tid];
+  const bool want_gT = a.T != nullptr && a.part_gT != nullptr;
+  float ld_w1 = 0.f, ld_px = 0.f, ld_t = 0.f;
+  if (tid < PM_C1 * 3) ld_w1 = a.W1[tid];
+  if (tid < 3 * PM_BTP) {   // (coordinate tid >> 5, point tid & 31): the tile's raw x and the gradient already in gx
+    const int p = tid & (PM_BTP - 1), c = tid >> 5;
+    if (n0 + p < a.N) {
+      if (want_gT) ld_px = a.x.p[(int64_t)b * a.x.bs + (int64_t)(n0 + p) * a.x.ps + c * a.x.cs];
+      if (a.accumulate) ld_t = a.gx.p[(int64_t)b * a.gx.bs + (int64_t)(n0 + p) * a.gx.ps + c * a.gx.cs];
+    }
+  } else if (tid >= 128 && tid < 137 && a.T) {
+    ld_t = a.T[(int64_t)b * 9 + tid - 128];
+  }
+  // MFMA B operand of phase C depends on nothing either: its L2 latency hides under phase A
+  float4 w2tr[PM_C2 / 16];
+  {
+    // phase C: wave = (j block wave&1, K half wave>>1): k2 in [64*(wave>>1), +64); lane (r, h) holds, for step t,
+    // W2[64*(wave>>1) + 8t + 4h + {0..3}][32*(wave&1) + r]  (= the float4 of W2T the two-list kernel loads)
+    const float* wcol = a.W2 + (64 * (wave >> 1) + 4 * h) * PM_C1 + 32 * (wave & 1) + r;
+#pragma unroll
+    for (int t = 0; t < PM_C2 / 16; ++t) {
+      w2tr[t].x = wcol[(8 * t + 0) * PM_C1];
+      w2tr[t].y = wcol[(8 * t + 1) * PM_C1];
+      w2tr[t].z = wcol[(8 * t + 2) * PM_C1];
+      w2tr[t].w = wcol[(8 * t + 3) * PM_C1];
+    }
+  }
+
+  // ---- A1. classify 4 consecutive channels per thread; block-wide ordered compaction of the hits
+  int cnt = 0;
+  int myn[PM_MAXC3 / 256];
+#pragma unroll
+  for (int e = 0; e < PM_MAXC3 / 256; ++e) {
+    const int c = tid * (PM_MAXC3 / 256) + e;
+    int n = -1;
+    if (c < a.C3) {
+      n = ld_n[e] - n0;
+      const float gv = ld_g[e];
+      if (n < 0 || n >= PM_BTP || gv == 0.f) n = -1;
+      s_g[c] = gv;
+    }
+    myn[e] = n;
+    cnt += (n >= 0) ? 1 : 0;
+  }
+  if (tid < PM_BTP * 4) s_m2[tid >> 2][tid & 3] = ld_m2;
+  if (tid < PM_BTP) s_m1[tid] = ld_m1;
+  if (tid < PM_C1 * 3) s_W1[tid] = ld_w1;
+  if (tid < 3 * PM_BTP) {
+    s_x[tid] = ld_px;
+    s_gxo[tid] = ld_t;
+  } else if (tid >= 128 && tid < 137) {
+    s_T[tid - 128] = ld_t;
+  }
+  for (int i = tid; i < PM_BTP * PM_LD2; i += 256) g2s[i] = 0.f;   // a point without a hit keeps a zero row
+  int incl = cnt;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int v = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += v;
+  }
+  if (lane == 63) s_scan[wave] = incl;
+  __syncthreads();
+  int base = 0, L = 0;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const int v = s_scan[w];
+    if (w < wave) base += v;
+    L += v;
+  }
+  if (L == 0) {  // no critical point in this tile: gradient is exactly zero
+    if (tid < 3 * PM_BTP && !a.accumulate) {
+      const int p = tid & (PM_BTP - 1), c = tid >> 5;
+      if (n0 + p < a.N) a.gx.p[(int64_t)b * a.gx.bs + (int64_t)(n0 + p) * a.gx.ps + c * a.gx.cs] = 0.f;
+    }
+    if (a.part_gT && tid < 16) a.part_gT[((int64_t)b * gridDim.x + tile) * 16 + tid] = 0.f;
+    return;
+  }
+  {
+    int o = base + incl - cnt;
+#pragma unroll
+    for (int e = 0; e < PM_MAXC3 / 256; ++e) {
+      const int n = myn[e];
+      if (n >= 0) s_hit[o++] = (unsigned short)((n << 10) | (tid * (PM_MAXC3 / 256) + e));
+    }
+  }
+  __syncthreads();
+
+  // ---- stable counting sort by point: the list is cut into 8 segments (multiples of 4 entries, read 4 at a time);
+  // group q of 32 lanes owns segment q, its lane p counts, then places, the hits of point p
+  const int grp = tid >> 5, gl = tid & 31;
+  const int seg = 4 * ((L + 4 * PM_BSEG - 1) / (4 * PM_BSEG));
+  const int s0 = grp * seg < L ? grp * seg : L;
+  const int s1 = s0 + seg < L ? s0 + seg : L;
+  {
+    int k = 0;
+    for (int j = s0; j < s1; j += 4) {
+      const uint2 v = *reinterpret_cast<const uint2*>(s_hit + j);
+      const int e[4] = {(int)(v.x & 0xffffu), (int)(v.x >> 16), (int)(v.y & 0xffffu), (int)(v.y >> 16)};
+#pragma unroll
+      for (int t = 0; t < 4; ++t) k += (j + t < s1 && (e[t] >> 10) == gl) ? 1 : 0;
+    }
+    s_cnt[grp * PM_BTP + gl] = k;
+  }
+  __syncthreads();
+  int p_tot = 0, p_start;   // of point gl: its hits in the tile, its offset in the sorted list
+  {
+    int before = 0;         // hits of point gl in the segments in front of this group's
+#pragma unroll
+    for (int q = 0; q < PM_BSEG; ++q) {
+      const int v = s_cnt[q * PM_BTP + gl];
+      if (q < grp) before += v;
+      p_tot += v;
+    }
+    int inc = p_tot;
+#pragma unroll
+    for (int o = 1; o < 32; o <<= 1) {
+      const int v = __shfl_up(inc, o, 32);
+      if (gl >= o) inc += v;
+    }
+    p_start = inc - p_tot;
+    if (grp == 0) {
+      s_start[gl] = p_start;
+      if (gl == 31) s_start[32] = inc;
+    }
+    int o = p_start + before;
+    for (int j = s0; j < s1; j += 4) {
+      const uint2 v = *reinterpret_cast<const uint2*>(s_hit + j);
+      const int e[4] = {(int)(v.x & 0xffffu), (int)(v.x >> 16), (int)(v.y & 0xffffu), (int)(v.y >> 16)};
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+        if (j + t < s1 && (e[t] >> 10) == gl) s_sorted[o++] = (unsigned short)e[t];
+    }
+  }
+  __syncthreads();
+
+  // ---- A2. point p belongs to wave floor(4 * start[p] / L); a wave's points are consecutive in the sorted list
+  {
+    int owner = 0;
+#pragma unroll
+    for (int q = 1; q < 4; ++q) owner += (p_start * 4 >= q * L) ? 1 : 0;
+    // (both halves of a wave hold the same per-point values: the low word is the mask of this wave's points)
+    const uint32_t mine = (uint32_t)__builtin_amdgcn_ballot_w64(p_tot > 0 && owner == wave);
+    if (mine != 0u) {
+      int i = __builtin_amdgcn_readfirstlane(s_start[__builtin_ctz(mine)]);
+      const int end = __builtin_amdgcn_readfirstlane(s_start[32 - __builtin_clz(mine)]);
+      float2 acc = make_float2(0.f, 0.f);
+      int cur = -1;
+      while (i < end) {   // chunks of up to 64 entries: lane s fetches entry i + s and its gradient
+        const int nb = end - i < 64 ? end - i : 64;
+        const int my_e = s_sorted[i + (lane < nb ? lane : nb - 1)];
+        const int my_g = __builtin_bit_cast(int, s_g[my_e & (PM_MAXC3 - 1)]);
+        int u = 0;
+        for (; u + PM_BFLY <= nb; u += PM_BFLY) pm_bwd_rows<PM_BFLY, false>(a.W3, my_e, my_g, s_m2, g2s, u, nb, lane, acc, cur);
+        if (u + 16 <= nb) {
+          pm_bwd_rows<16, false>(a.W3, my_e, my_g, s_m2, g2s, u, nb, lane, acc, cur);
+          u += 16;
+        }
+        if (u + 8 <= nb) {
+          pm_bwd_rows<8, false>(a.W3, my_e, my_g, s_m2, g2s, u, nb, lane, acc, cur);
+          u += 8;
+        }
+        for (; u < nb; u += 4) pm_bwd_rows<4, true>(a.W3, my_e, my_g, s_m2, g2s, u, nb, lane, acc, cur);
+        i += nb;
+      }
+      pm_bwd_put_row(s_m2, g2s, cur, lane, acc);
+    }
+  }
+  __syncthreads();   // also: the sort's counters in h1s are dead
+
+  // ---- C. g1[pt][j] = sum_k2 g2[pt][k2] W2[k2][j] on MFMA: wave = (j block wave&1, K half wave>>1)
+  pm_bwd_phase_c(w2tr, g2s, h1s, s_m1, wave, r, h);
+  __syncthreads();
+
+  // ---- D. g'[p][c] = sum_j W1[j][c] g1[p][j]  (gradient wrt the tower input x' = x @ T)
+  float* gp = xs;  // [3][32] scratch
+  if (wave < 3 && lane < PM_BTP) {   // wave = coordinate c, lane = point
+    const int p = lane, c = wave;
+    float sa = 0.f, sb = 0.f;
+#pragma unroll
+    for (int j = 0; j < PM_C1; j += 4) {
+      const float4 hv = *reinterpret_cast<const float4*>(h1s + p * PM_LD1 + j);
+      sa = __builtin_fmaf(s_W1[j * 3 + c], hv.x, sa);
+      sb = __builtin_fmaf(s_W1[(j + 1) * 3 + c], hv.y, sb);
+      sa = __builtin_fmaf(s_W1[(j + 2) * 3 + c], hv.z, sa);
+      sb = __builtin_fmaf(s_W1[(j + 3) * 3 + c], hv.w, sb);
+    }
+    gp[c * PM_BTP + p] = sa + sb;
+  }
+  __syncthreads();
+  if (wave == 0) {  // lanes 0..31 = the tile's points; lanes 32..63 contribute zeros to the reductions
+    const int p = lane & (PM_BTP - 1);
+    const bool live = lane < PM_BTP;
+    const float g0 = live ? gp[p] : 0.f, g1v = live ? gp[PM_BTP + p] : 0.f, g2v = live ? gp[2 * PM_BTP + p] : 0.f;
+    float o0 = g0, o1 = g1v, o2 = g2v;
+    if (a.T) {
+      // x' = x @ T  =>  dL/dx[c] = sum_c' g'[c'] T[c][c'] ;  dL/dT[c][c'] = sum_p x[p][c] g'[p][c']
+      const float* t = s_T;
+      o0 = __builtin_fmaf(g2v, t[2], __builtin_fmaf(g1v, t[1], g0 * t[0]));
+      o1 = __builtin_fmaf(g2v, t[5], __builtin_fmaf(g1v, t[4], g0 * t[3]));
+      o2 = __builtin_fmaf(g2v, t[8], __builtin_fmaf(g1v, t[7], g0 * t[6]));
+      if (a.part_gT) {
+        float xr[3] = {0.f, 0.f, 0.f};
+        if (live) xr[0] = s_x[p], xr[1] = s_x[PM_BTP + p], xr[2] = s_x[2 * PM_BTP + p];   // zeros past N
+        const float gv[3] = {g0, g1v, g2v};
+        // nine wave_sum butterflies (the same additions, in the same order, each), stepped together so that their
+        // cross-lane round trips overlap; lane j keeps sum j and lanes 0..15 store the tile's 16 words at once
+        float sum[9];
+#pragma unroll
+        for (int j = 0; j < 9; ++j) sum[j] = xr[j / 3] * gv[j % 3];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+          float other[9];
+#pragma unroll
+          for (int j = 0; j < 9; ++j) other[j] = __shfl_xor(sum[j], o, 64);
+#pragma unroll
+          for (int j = 0; j < 9; ++j) sum[j] += other[j];
+        }
+        float mine = 0.f;
+#pragma unroll
+        for (int j = 0; j < 9; ++j) mine = (lane == j) ? sum[j] : mine;
+        if (lane < 16) a.part_gT[((int64_t)b * gridDim.x + tile) * 16 + lane] = mine;
+      }
+    }
+    if (live && n0 + p < a.N) {
+      float* q = a.gx.p + (int64_t)b * a.gx.bs + (int64_t)(n0 + p) * a.gx.ps;
+      if (a.accumulate) {
+        q[0] = s_gxo[p] + o0, q[a.gx.cs] = s_gxo[PM_BTP + p] + o1, q[2 * a.gx.cs] = s_gxo[2 * PM_BTP + p] + o2;
+      } else {
+        q[0] = o0, q[a.gx.cs] = o1, q[2 * a.gx.cs] = o2;
+      }
+    }
+  }
+}
+
 }  // namespace pc3d
 
 using namespace pc3d;
@@ -622,6 +984,28 @@ extern "C" int pc3d_pointmlp3_max_fwd_th_f32(const float* x, int64_t x_bs, int64
                        C3, relu_last, part_val, part_idx, pooled, argidx, mask1, mask2, stream);
 }
 
+static int pm_bwd_launch(const char* who, bool twolist, const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B,
+                         int N, const float* T, const float* W1, const float* b1, const float* W2, const float* b2,
+                         const float* W3, const float* W2T, int C1, int C2, int C3, const int32_t* argidx,
+                         const uint64_t* mask1, const uint32_t* mask2, const float* g_pooled, float* grad_x,
+                         int64_t gx_bs, int64_t gx_ps, int64_t gx_cs, float* part_gT, int accumulate, void* stream) {
+  PC3D_REQUIRE(B >= 0 && N >= 1, "%s: bad sizes B=%d N=%d", who, B, N);
+  PC3D_REQUIRE(C1 == PM_C1 && C2 == PM_C2 && C3 >= 32 && C3 % 32 == 0 && C3 <= PM_MAXC3,
+               "%s: unsupported widths %d/%d/%d", who, C1, C2, C3);
+  PC3D_REQUIRE(B <= 65535, "%s: B=%d exceeds grid.y limit", who, B);
+  if (B == 0) return PC3D_OK;
+  PC3D_REQUIRE(x && W1 && b1 && W2 && b2 && W3 && W2T && argidx && mask1 && mask2 && g_pooled && grad_x,
+               "%s: null pointer", who);
+  PMBwdArgs a{{x, x_bs, x_ps, x_cs}, N, C3, T, W1, b1, W2, b2, W3, W2T, argidx, mask1, mask2, g_pooled, {grad_x, gx_bs, gx_ps, gx_cs},
+              part_gT, accumulate};
+  if (twolist)
+    hipLaunchKernelGGL(pointmlp3_max_bwd_twolist_kernel, dim3(cdiv(N, PM_BTP), B), dim3(256), 0, as_stream(stream), a);
+  else
+    hipLaunchKernelGGL(pointmlp3_max_bwd_kernel, dim3(cdiv(N, PM_BTP), B), dim3(256), 0, as_stream(stream), a);
+  PC3D_LAUNCH_CHECK(who);
+  return PC3D_OK;
+}
+
 extern "C" int pc3d_pointmlp3_max_bwd_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
                                           const float* T, const float* W1, const float* b1, const float* W2,
                                           const float* b2, const float* W3, const float* W2T, int C1, int C2,
@@ -629,16 +1013,18 @@ extern "C" int pc3d_pointmlp3_max_bwd_f32(const float* x, int64_t x_bs, int64_t 
                                           const uint32_t* mask2, const float* g_pooled, float* grad_x,
                                           int64_t gx_bs, int64_t gx_ps, int64_t gx_cs, float* part_gT,
                                           int accumulate, void* stream) {
-  PC3D_REQUIRE(B >= 0 && N >= 1, "pc3d_pointmlp3_max_bwd_f32: bad sizes B=%d N=%d", B, N);
-  PC3D_REQUIRE(C1 == PM_C1 && C2 == PM_C2 && C3 >= 32 && C3 % 32 == 0 && C3 <= PM_MAXC3,
-               "pc3d_pointmlp3_max_bwd_f32: unsupported widths %d/%d/%d", C1, C2, C3);
-  PC3D_REQUIRE(B <= 65535, "pc3d_pointmlp3_max_bwd_f32: B=%d exceeds grid.y limit", B);
-  if (B == 0) return PC3D_OK;
-  PC3D_REQUIRE(x && W1 && b1 && W2 && b2 && W3 && W2T && argidx && mask1 && mask2 && g_pooled && grad_x,
-               "pc3d_pointmlp3_max_bwd_f32: null pointer");
-  PMBwdArgs a{{x, x_bs, x_ps, x_cs}, N, C3, T, W1, b1, W2, b2, W3, W2T, argidx, mask1, mask2, g_pooled, {grad_x, gx_bs, gx_ps, gx_cs},
-              part_gT, accumulate};
-  hipLaunchKernelGGL(pointmlp3_max_bwd_kernel, dim3(cdiv(N, PM_BTP), B), dim3(256), 0, as_stream(stream), a);
-  PC3D_LAUNCH_CHECK("pc3d_pointmlp3_max_bwd_f32");
-  return PC3D_OK;
+  return pm_bwd_launch("pc3d_pointmlp3_max_bwd_f32", false, x, x_bs, x_ps, x_cs, B, N, T, W1, b1, W2, b2, W3, W2T, C1,
+                       C2, C3, argidx, mask1, mask2, g_pooled, grad_x, gx_bs, gx_ps, gx_cs, part_gT, accumulate, stream);
+}
+
+extern "C" int pc3d_pointmlp3_max_bwd_twolist_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B,
+                                                  int N, const float* T, const float* W1, const float* b1,
+                                                  const float* W2, const float* b2, const float* W3, const float* W2T,
+                                                  int C1, int C2, int C3, const int32_t* argidx,
+                                                  const uint64_t* mask1, const uint32_t* mask2, const float* g_pooled,
+                                                  float* grad_x, int64_t gx_bs, int64_t gx_ps, int64_t gx_cs,
+                                                  float* part_gT, int accumulate, void* stream) {
+  return pm_bwd_launch("pc3d_pointmlp3_max_bwd_twolist_f32", true, x, x_bs, x_ps, x_cs, B, N, T, W1, b1, W2, b2, W3, W2T,
+                       C1, C2, C3, argidx, mask1, mask2, g_pooled, grad_x, gx_bs, gx_ps, gx_cs, part_gT, accumulate,
+                       stream);
 }

@@ -422,10 +422,11 @@ def pointmlp3_max_fwd_raw(x, weights, relu_last, T=None, x_cf=True, fold=True, w
 
 
 def pointmlp3_max_bwd_raw(x, weights, argidx, g_pooled, masks, T=None, x_cf=True, out=None, accumulate=False,
-                          want_gT=False):
+                          want_gT=False, twolist=False):
     """Gradient w.r.t. the tower input (T None) or w.r.t. the raw points through x' = x @ T (T given); same layout
     as x. masks: the (mask1, mask2) pair of the forward launch on the same x/T (want_masks=True).
-    want_gT: also return the per-tile partials [B, ntiles, 16] of dL/dT. out/accumulate: add into `out`."""
+    want_gT: also return the per-tile partials [B, ntiles, 16] of dL/dT. out/accumulate: add into `out`.
+    twolist: run the earlier two-list kernel (same bits; parity tests and tools/bench_pointmlp.py only)."""
     xp, xbs, xps, xcs, B, N = _pts(x, x_cf, "x")
     W1, b1, W2, b2, W3, b3 = weights[:6]
     W2T = weights[6] if len(weights) > 6 else W2.t().contiguous()
@@ -444,7 +445,8 @@ def pointmlp3_max_bwd_raw(x, weights, argidx, g_pooled, masks, T=None, x_cf=True
         bt = _lib.load().pc3d_pointmlp3_bwd_tile_points()
         part_gT = torch.empty((B, (N + bt - 1) // bt, 16), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        _lib.call("pc3d_pointmlp3_max_bwd_f32", xp, xbs, xps, xcs, B, N, _ptr(T),
+        _lib.call("pc3d_pointmlp3_max_bwd_twolist_f32" if twolist else "pc3d_pointmlp3_max_bwd_f32",
+                  xp, xbs, xps, xcs, B, N, _ptr(T),
                   W1.data_ptr(), b1.data_ptr(), W2.data_ptr(), b2.data_ptr(), W3.data_ptr(), W2T.data_ptr(),
                   C1, C2, C3, argidx.data_ptr(), m1.data_ptr(), m2.data_ptr(), g_pooled.data_ptr(), gp, gbs, gps, gcs,
                   _ptr(part_gT),

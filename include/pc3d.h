@@ -384,9 +384,12 @@ int pc3d_pointmlp3_max_fwd_th_f32(const float* x, int64_t x_bs, int64_t x_ps, in
  * [B, ceil(N / pc3d_pointmlp3_bwd_tile_points()), 16], 9 used) the per-tile partial sums of dL/dT (row-major 3x3);
  * their sum over tiles is the gradient that flows on into the STN head. accumulate != 0: grad_x += (used to add the
  * STN tower's contribution on top of the trunk's).
- * W2T is W2 transposed ([64,128] row-major; lets the W2^T product read its operand rows contiguously).
+ * W2T is W2 transposed ([64,128] row-major); required, but the balanced kernel behind this entry fetches its MFMA
+ * operand from W2 itself (coalesced in that operand's lane order) and only the two-list entry below reads W2T.
  * mask1 / mask2 are the forward launch's outputs of those names (required).
- * The max-pool routes each channel to one point, so the layer-3 dgrad is a sparse ordered gather: deterministic. */
+ * The max-pool routes each channel to one point, so the layer-3 dgrad is a sparse ordered gather: the tile's hits are
+ * sorted by point and each point's row is one fma chain in ascending channel order, whole points shared out over the
+ * workgroup's waves: deterministic, and independent of which wave runs a point. */
 int pc3d_pointmlp3_max_bwd_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
                                const float* T, const float* W1, const float* b1, const float* W2,
                                const float* b2, const float* W3, const float* W2T, int C1, int C2, int C3,
@@ -394,6 +397,16 @@ int pc3d_pointmlp3_max_bwd_f32(const float* x, int64_t x_bs, int64_t x_ps, int64
                                const float* g_pooled,
                                float* grad_x, int64_t gx_bs, int64_t gx_ps, int64_t gx_cs,
                                float* part_gT, int accumulate, void* stream);
+/* The same computation, bit for bit, by the earlier two-list kernel (hits split at points 0-15 / 16-31, rows
+ * accumulated through LDS). Kept as the parity reference of the balanced kernel above and for tools/bench_pointmlp.py;
+ * nothing on a hot path calls it. */
+int pc3d_pointmlp3_max_bwd_twolist_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                       const float* T, const float* W1, const float* b1, const float* W2,
+                                       const float* b2, const float* W3, const float* W2T, int C1, int C2, int C3,
+                                       const int32_t* argidx, const uint64_t* mask1, const uint32_t* mask2,
+                                       const float* g_pooled,
+                                       float* grad_x, int64_t gx_bs, int64_t gx_ps, int64_t gx_cs,
+                                       float* part_gT, int accumulate, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Classifier heads. Y[b,o] = epi(sum_k X[b,k] W[o,k] + bias[o]) for small row counts (the B samples of a batch),
