@@ -71,14 +71,16 @@ class CW:
     def __init__(self, model, trans_model, adv_func, clip_func, dist_func, attack_lr=1e-2,
                  init_weight=10., max_weight=80., binary_step=10, num_iter=500, attack_method="untarget",
                  device=None, verbose=False, fused=True, graph=True, sample_seeds=None, global_batch=None,
-                 deterministic=None):
+                 deterministic=None, riders=True):
         """Arguments as attack/CW/CW_attack.py:26-38. Extra keyword-only style options (defaults keep the
         reference behaviour): device (default: current CUDA device), verbose (reference prints), fused (use the
         fused Adam+clip launch when clip_func is recognised). For sharded runs: `sample_seeds` (one int
         per sample of the batch handed to attack()) draws each sample's 1e-7 start noise (:94) from its own CPU
         generator instead of the shared global stream, and `global_batch` is the size of the unsharded batch whose
         `.mean()` (:160-165) this shard's losses belong to — with both, a sample's trajectory does not depend on the
-        rank / batch it is attacked in."""
+        rank / batch it is attacked in. `riders`: the fused PointNet iteration in 15 launches (the search and the bookkeeping
+        ride head launches, the update is the last backward's epilogue; True, the default) or in the 17 launches it replaced
+        (False: the parity yardstick, bit-identical); a collection out of {"search", "update"} takes only those pieces."""
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.model = model.to(self.device)
         self.model.eval()
@@ -106,6 +108,9 @@ class CW:
         self.overlap_search = os.environ.get("PC3D_OVERLAP_SEARCH", "0") == "1"
         self.fused = fused
         self.graph = graph
+        self.riders = {"search", "update"} if riders is True else (set() if not riders else set(riders))
+        if self.riders - {"search", "update"}:
+            raise ValueError(f"riders: unknown piece(s) {sorted(self.riders - {'search', 'update'})}")
         self.sample_seeds = sample_seeds
         self.global_batch = global_batch
         # None: the process-wide setting (ops.DETERMINISTIC, default on: ordered backward sums, bit-reproducible runs);
@@ -216,7 +221,9 @@ class CW:
             o_bestattack=torch.zeros((B, 3, K), dtype=torch.float32, device=dev),
             input_val=ori_data.clone(), pred=torch.zeros((B,), dtype=torch.long, device=dev),
             step=torch.zeros((1,), dtype=torch.int32, device=dev), graph=None,
-            dist_val=torch.zeros((B,), dtype=torch.float32, device=dev))
+            dist_val=torch.zeros((B,), dtype=torch.float32, device=dev),
+            # Adam's two bias-correction factors of the current step, written on the device by the bookkeeping rider
+            adam=torch.zeros((2,), dtype=torch.float32, device=dev))
 
     def _begin_binary_step(self, st):
         """Fresh start point, Adam state and per-step bests (reference :94-100)."""
@@ -267,6 +274,18 @@ class CW:
             # launch-minimal pass: victim fwd/bwd (fused heads), bookkeeping, [NN search], one update launch
             with torch.no_grad():
                 cur = adv_data.detach()
+                if (self.riders and "adam" in st and hasattr(self.model, "fused_attack_update") and st["K"] <= ops.CW_UPDATE_MAX_POINTS
+                        and not (dk == 2 and getattr(self, "overlap_search", False))):
+                    # 15 launches: the search, the bookkeeping and the update ride the victim's own launches
+                    self.model.fused_attack_update(
+                        cur, st["target"], *fml, pred_out=st["pred"], step=st["step"], scale=st["ratio"] / st["B"],
+                        cw=dict(ori=ori_data, label=label, untarget=self.attack_method == 'untarget',
+                                bestdist=st["bestdist"], bestscore=st["bestscore"], o_bestdist=st["o_bestdist"],
+                                o_bestscore=st["o_bestscore"], o_bestattack=st["o_bestattack"], input_val=st["input_val"],
+                                dist_val=st["dist_val"], m=st["exp_avg"], v=st["exp_avg_sq"], w=st["weights"],
+                                adam=st["adam"], lr=self.attack_lr, budget=st["budget"], dist_kind=dk),
+                        ride_search="search" in self.riders, epilogue="update" in self.riders)
+                    return
                 if hasattr(self.model, "fused_attack_grad") and st["K"] <= ops.CW_UPDATE_MAX_POINTS:
                     # 17 launches: the classifier tail writes pred + advances the step word, one update launch
                     nn_box = []

@@ -4,24 +4,11 @@
 // optimiser update (loss.backward() of the distance term + Adam + clip, :160-174) as TWO launches
 // (cw_bookkeep_kernel + cw_step_kernel) or as ONE (cw_update_kernel, what the captured CW iteration uses).
 #include "pc3d_common.h"
+#include "cw_update_body.h"
 
 namespace pc3d {
 
-struct BookArgs {
-  PtsView adv, ori;          // [B,K] points
-  int K;
-  const int64_t* pred;       // [B]
-  const int64_t* label;      // [B]
-  int untarget;              // success = pred != label (1) or pred == label (0)
-  float* bestdist;           // [B] per-binary-step best
-  int64_t* bestscore;        // [B]
-  float* o_bestdist;         // [B] overall best
-  int64_t* o_bestscore;      // [B]
-  PtsViewMut o_bestattack;   // [B,K] points: copy of adv where the overall best improved
-  PtsViewMut input_val;      // [B,K] points: always the iterate this pass started from (may be null)
-  float* dist_val;           // [B] out: ||adv-ori||_F (feeds the L2 distance gradient)
-  int32_t* step;             // Adam step word, incremented once per launch (may be null)
-};
+// BookArgs, the bookkeeping decisions (cw_book_decide) and the per-point update (cw_point_update) live in cw_update_body.h
 
 // one workgroup per sample
 __global__ __launch_bounds__(256) void cw_bookkeep_kernel(BookArgs a) {
@@ -40,20 +27,7 @@ __global__ __launch_bounds__(256) void cw_bookkeep_kernel(BookArgs a) {
   __syncthreads();
   if (threadIdx.x == 0) {
     const float dist = __builtin_sqrtf(part[0] + part[1] + part[2] + part[3]);
-    if (a.dist_val) a.dist_val[b] = dist;
-    const int64_t pr = a.pred[b], lb = a.label[b];
-    const bool succ = a.untarget ? (pr != lb) : (pr == lb);
-    if (succ && dist < a.bestdist[b]) {
-      a.bestdist[b] = dist;
-      a.bestscore[b] = pr;
-    }
-    int copy = 0;
-    if (succ && dist < a.o_bestdist[b]) {
-      a.o_bestdist[b] = dist;
-      a.o_bestscore[b] = pr;
-      copy = 1;
-    }
-    s_copy = copy;
+    s_copy = cw_book_decide(a, b, dist, a.pred[b], a.label[b], a.bestdist[b], a.o_bestdist[b]);
     if (b == 0 && a.step) a.step[0] += 1;
   }
   __syncthreads();
@@ -102,8 +76,7 @@ __global__ __launch_bounds__(256) void cw_step_kernel(StepArgs a) {
   if (k >= a.K) return;
   const int t = a.step_dev ? a.step_dev[0] : a.step_host;
   const float omb1 = (float)(1.0 - a.b1), omb2 = (float)(1.0 - a.b2), fb2 = (float)a.b2;
-  const float step_size = (float)(a.lr / (1.0 - pow(a.b1, (double)t)));
-  const float bc2s = (float)sqrt(1.0 - pow(a.b2, (double)t));
+  const float step_size = cw_adam_step_size(a.lr, a.b1, t), bc2s = cw_adam_bc2s(a.b2, t);
   float* pp = a.p.p + (int64_t)b * a.p.bs + (int64_t)k * a.p.ps;
   const float* gp = a.g.p + (int64_t)b * a.g.bs + (int64_t)k * a.g.ps;
   float* mp = a.m.p + (int64_t)b * a.m.bs + (int64_t)k * a.m.ps;
@@ -112,42 +85,21 @@ __global__ __launch_bounds__(256) void cw_step_kernel(StepArgs a) {
   const float ox = o[0], oy = o[a.ori.cs], oz = o[2 * a.ori.cs];
   const float px = pp[0], py = pp[a.p.cs], pz = pp[2 * a.p.cs];
   float g[3] = {gp[0], gp[a.g.cs], gp[2 * a.g.cs]};
-  if (a.dist_kind == 1) {
-    const float nrm = a.l2norm[b];
-    // torch: d sqrt(s)/ds = 1/(2 sqrt(s)), ds/dp = 2 (p - o)  ->  (p-o)/norm ; weight/B from the batch mean
-    const float c = a.w[b] / (float)a.B;
-    g[0] += c * ((px - ox) / nrm);
-    g[1] += c * ((py - oy) / nrm);
-    g[2] += c * ((pz - oz) / nrm);
-  } else if (a.dist_kind == 2) {
+  float q[3] = {0.f, 0.f, 0.f};
+  if (a.dist_kind == 2) {
     const int j = a.nn_idx[(int64_t)b * a.K + k];
-    const float* q = a.ori.p + (int64_t)b * a.ori.bs + (int64_t)j * a.ori.ps;
-    const float c = 2.f * (a.w[b] / (float)a.B) / (float)a.K;
-    g[0] += c * (px - q[0]);
-    g[1] += c * (py - q[a.ori.cs]);
-    g[2] += c * (pz - q[2 * a.ori.cs]);
+    const float* qp = a.ori.p + (int64_t)b * a.ori.bs + (int64_t)j * a.ori.ps;
+    q[0] = qp[0], q[1] = qp[a.ori.cs], q[2] = qp[2 * a.ori.cs];
   }
-  float np_[3];
-  const float pin[3] = {px, py, pz};
+  const CwPointConsts c{a.dist_kind, a.B, a.K, omb1, omb2, fb2, step_size, bc2s, a.eps, a.budget};
+  const float pin[3] = {px, py, pz}, oin[3] = {ox, oy, oz};
+  float m[3] = {mp[0], mp[a.m.cs], mp[2 * a.m.cs]}, v[3] = {vp[0], vp[a.v.cs], vp[2 * a.v.cs]}, np_[3];
+  cw_point_update(c, pin, oin, g, q, a.dist_kind ? a.w[b] : 0.f, a.dist_kind == 1 ? a.l2norm[b] : 0.f, m, v, np_);
 #pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    float m = mp[c * a.m.cs], v = vp[c * a.v.cs];
-    m = m + (g[c] - m) * omb1;
-    v = v * fb2 + omb2 * g[c] * g[c];
-    mp[c * a.m.cs] = m;
-    vp[c * a.v.cs] = v;
-    const float denom = __builtin_sqrtf(v) / bc2s + a.eps;
-    np_[c] = pin[c] - step_size * (m / denom);
-  }
-  float dx = np_[0] - ox, dy = np_[1] - oy, dz = np_[2] - oz;
-  if (a.budget > 0.f) {  // ClipPointsLinf (clip_utils.py:43-56)
-    const float norm = __builtin_sqrtf(dx * dx + dy * dy + dz * dz);
-    const float s = fminf(a.budget / (norm + 1e-9f), 1.f);
-    dx *= s, dy *= s, dz *= s;
-  }
-  pp[0] = ox + dx;
-  pp[a.p.cs] = oy + dy;
-  pp[2 * a.p.cs] = oz + dz;
+  for (int e = 0; e < 3; ++e) mp[e * a.m.cs] = m[e], vp[e * a.v.cs] = v[e];
+  pp[0] = np_[0];
+  pp[a.p.cs] = np_[1];
+  pp[2 * a.p.cs] = np_[2];
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -226,22 +178,10 @@ __global__ __launch_bounds__(1024) void cw_update_kernel(UpdateArgs u) {
     for (int w = 0; w < 16; ++w) tot += part[w];
     const float dist = __builtin_sqrtf(tot);
     s_dist = dist;
-    if (a.dist_val) a.dist_val[b] = dist;
-    const bool succ = a.untarget ? (pr != lb) : (pr == lb);
-    if (succ && dist < bd) {
-      a.bestdist[b] = dist;
-      a.bestscore[b] = pr;
-    }
-    int copy = 0;
-    if (succ && dist < obd) {
-      a.o_bestdist[b] = dist;
-      a.o_bestscore[b] = pr;
-      copy = 1;
-    }
-    s_copy = copy;
+    s_copy = cw_book_decide(a, b, dist, pr, lb, bd, obd);
     // Adam bias corrections in double (as torch): evaluated once per workgroup, not by all 1024 threads
-    s_step_size = (float)(s.lr / (1.0 - pow(s.b1, (double)t)));
-    s_bc2s = (float)sqrt(1.0 - pow(s.b2, (double)t));
+    s_step_size = cw_adam_step_size(s.lr, s.b1, t);
+    s_bc2s = cw_adam_bc2s(s.b2, t);
   }
   __syncthreads();
   const bool copy = s_copy != 0;
@@ -261,41 +201,18 @@ __global__ __launch_bounds__(1024) void cw_update_kernel(UpdateArgs u) {
       q[0] = px[i], q[a.o_bestattack.cs] = py[i], q[2 * a.o_bestattack.cs] = pz[i];
     }
     float g[3] = {gx[i], gy[i], gz[i]};
-    if (s.dist_kind == 1) {
-      const float c = wb / (float)s.B;
-      g[0] += c * ((px[i] - ox[i]) / l2n);
-      g[1] += c * ((py[i] - oy[i]) / l2n);
-      g[2] += c * ((pz[i] - oz[i]) / l2n);
-    } else if (s.dist_kind == 2) {
-      const float c = 2.f * (wb / (float)s.B) / (float)s.K;
-      g[0] += c * (px[i] - qx[i]);
-      g[1] += c * (py[i] - qy[i]);
-      g[2] += c * (pz[i] - qz[i]);
-    }
     float* pp = s.p.p + (int64_t)b * s.p.bs + (int64_t)k * s.p.ps;
     float* mp = s.m.p + (int64_t)b * s.m.bs + (int64_t)k * s.m.ps;
     float* vp = s.v.p + (int64_t)b * s.v.bs + (int64_t)k * s.v.ps;
+    const CwPointConsts c{s.dist_kind, s.B, s.K, omb1, omb2, fb2, step_size, bc2s, s.eps, s.budget};
+    const float pin[3] = {px[i], py[i], pz[i]}, oin[3] = {ox[i], oy[i], oz[i]}, q[3] = {qx[i], qy[i], qz[i]};
     float np_[3];
-    const float pin[3] = {px[i], py[i], pz[i]};
+    cw_point_update(c, pin, oin, g, q, wb, l2n, m_[i], v_[i], np_);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      float m = m_[i][c], v = v_[i][c];
-      m = m + (g[c] - m) * omb1;
-      v = v * fb2 + omb2 * g[c] * g[c];
-      mp[c * s.m.cs] = m;
-      vp[c * s.v.cs] = v;
-      const float denom = __builtin_sqrtf(v) / bc2s + s.eps;
-      np_[c] = pin[c] - step_size * (m / denom);
-    }
-    float dx = np_[0] - ox[i], dy = np_[1] - oy[i], dz = np_[2] - oz[i];
-    if (s.budget > 0.f) {
-      const float norm = __builtin_sqrtf(dx * dx + dy * dy + dz * dz);
-      const float sc = fminf(s.budget / (norm + 1e-9f), 1.f);
-      dx *= sc, dy *= sc, dz *= sc;
-    }
-    pp[0] = ox[i] + dx;
-    pp[s.p.cs] = oy[i] + dy;
-    pp[2 * s.p.cs] = oz[i] + dz;
+    for (int e = 0; e < 3; ++e) mp[e * s.m.cs] = m_[i][e], vp[e * s.v.cs] = v_[i][e];
+    pp[0] = np_[0];
+    pp[s.p.cs] = np_[1];
+    pp[2 * s.p.cs] = np_[2];
   }
 }
 

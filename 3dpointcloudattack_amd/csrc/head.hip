@@ -8,28 +8,13 @@
 //   summed through LDS in fixed wave order (deterministic). Backward of a linear layer is the same kernel on the
 //   transposed weight (the host keeps W^T next to W: weights are frozen).
 #include "pc3d_common.h"
+#include "linear16_body.h"
 
 namespace pc3d {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
-constexpr int LN_T = 512;  // threads: 8 waves split K
-constexpr int LN_W = LN_T / 64;
-
-struct LinArgs {
-  const float* X;     // [B, P, K] (P partial slabs summed on load; P = 1 for a plain matrix)
-  int ldx;            // row stride of X in floats (>= P*K)
-  int P;
-  const float* W;     // [O, K] row-major
-  const float* bias;  // [O] or null
-  const float* gate;  // [B, O] or null: Y = gate > 0 ? Y : gslope * Y  (the (Leaky)ReLU mask of a saved forward activation)
-  int ldg;
-  float* Y;           // [B, O]
-  int ldy;
-  int B, K, O;
-  int relu;           // 1: Y = Y > 0 ? Y : slope * Y  (slope 0 = ReLU)
-  float slope, gslope;
-};
+// LinArgs, LN_T / LN_W and the 32 x 16 tiling (linear16_body) live in linear16_body.h
 
 __global__ __launch_bounds__(LN_T) void linear_kernel(LinArgs a) {
   __shared__ float red[LN_W][32][33];
@@ -131,71 +116,8 @@ __global__ __launch_bounds__(LN_T) void linear_kernel(LinArgs a) {
   }
 }
 
-// 32 rows x 16 outputs per workgroup on v_mfma_f32_16x16x4_f32: twice the workgroups (CUs) of the 32 x 32 tiling for
-// the same layer, half the MFMA time and half the weight bytes per workgroup — these launches are latency-bound and
-// use at most O/32 of the 256 CUs. Operand mapping: lane (r = lane & 15, q = lane >> 4) holds the float4 at
-// k = 16c + 4q of row r; MFMA call e consumes element e of every lane's float4, so its four k-slices are
-// k = 16c + 4q + e — the same permutation on both operands, i.e. an exact fp32 sum in a permuted k order.
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-__global__ __launch_bounds__(LN_T) void linear16_kernel(LinArgs a) {
-  __shared__ float red[LN_W][32][17];
-  const int o0 = blockIdx.x * 16, b0 = blockIdx.y * 32;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int r = lane & 15, q = lane >> 4;
-  const int xb0 = (b0 + r < a.B) ? b0 + r : a.B - 1;
-  const int xb1 = (b0 + 16 + r < a.B) ? b0 + 16 + r : a.B - 1;
-  const int wo = (o0 + r < a.O) ? o0 + r : a.O - 1;
-  const float* x0 = a.X + (int64_t)xb0 * a.ldx + 4 * q;
-  const float* x1 = a.X + (int64_t)xb1 * a.ldx + 4 * q;
-  const float* wr = a.W + (int64_t)wo * a.K + 4 * q;
-  const int nchunk = a.K / 16;          // chunks of 16 k; wave w takes chunks w, w+8, ... (<= 8 per wave)
-  float4 xv0[8], xv1[8], wv[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int c = wave + i * LN_W;
-    if (c < nchunk) {
-      xv0[i] = *reinterpret_cast<const float4*>(x0 + 16 * c);
-      xv1[i] = *reinterpret_cast<const float4*>(x1 + 16 * c);
-      wv[i] = *reinterpret_cast<const float4*>(wr + 16 * c);
-    }
-  }
-  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int c = wave + i * LN_W;
-    if (c < nchunk) {   // D[row = sample][col = output]; two independent accumulators cover the 40-cycle MFMA latency
-      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(xv0[i].x, wv[i].x, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(xv1[i].x, wv[i].x, acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(xv0[i].y, wv[i].y, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(xv1[i].y, wv[i].y, acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(xv0[i].z, wv[i].z, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(xv1[i].z, wv[i].z, acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(xv0[i].w, wv[i].w, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(xv1[i].w, wv[i].w, acc1, 0, 0, 0);
-    }
-  }
-  // 16x16x4 result layout: lane holds column r, rows 4*q + e
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    red[wave][4 * q + e][r] = acc0[e];
-    red[wave][16 + 4 * q + e][r] = acc1[e];
-  }
-  __syncthreads();
-  {
-    const int row = threadIdx.x >> 4, col = threadIdx.x & 15;   // 512 threads = 32 x 16 outputs
-    float s = red[0][row][col];
-#pragma unroll
-    for (int w = 1; w < LN_W; ++w) s += red[w][row][col];
-    const int b = b0 + row, o = o0 + col;
-    if (b < a.B && o < a.O) {
-      if (a.bias) s += a.bias[o];
-      if (a.relu) s = s > 0.f ? s : s * a.slope;
-      if (a.gate && !(a.gate[(int64_t)b * a.ldg + o] > 0.f)) s *= a.gslope;
-      a.Y[(int64_t)b * a.ldy + o] = s;
-    }
-  }
-}
+// 32 rows x 16 outputs per workgroup on v_mfma_f32_16x16x4_f32 (linear16_body.h)
+__global__ __launch_bounds__(LN_T) void linear16_kernel(LinArgs a) { linear16_body(a, blockIdx.x, blockIdx.y); }
 
 // The same 32 x 16 tiling with the X operand produced on the fly by a tiny PRE-layer:
 //     X[b,k] = gate_pre[b,k] > 0 ? sum_{j<J} S[b,j] Wp[j,k] : 0,      S[b,j] = sum_p parts[b,p,j]
@@ -524,7 +446,7 @@ extern "C" int pc3d_linear_f32(const float* X, int ldx, int P, int B, int K, con
   PC3D_REQUIRE(X && W && Y, "pc3d_linear_f32: null pointer");
   PC3D_REQUIRE(gate == nullptr || ldg >= O, "pc3d_linear_f32: ldg=%d too small", ldg);
   LinArgs a{X, ldx, P, W, bias, gate, ldg, Y, ldy, B, K, O, relu, slope, gate_slope};
-  if ((K & 15) == 0 && P == 1 && K / 16 <= 8 * LN_W && O >= 64)
+  if (linear16_applies(K, P, O))
     hipLaunchKernelGGL(linear16_kernel, dim3(cdiv(O, 16), cdiv(B, 32)), dim3(LN_T), 0, as_stream(stream), a);
   else
     hipLaunchKernelGGL(linear_kernel, dim3(cdiv(O, 32), cdiv(B, 32)), dim3(LN_T), 0, as_stream(stream), a);

@@ -17,6 +17,7 @@
 // bit masks (24 B per point — nothing is recomputed) and chains W2^T on MFMA and W1^T on the VALU.
 #include <stdlib.h>
 #include "pc3d_common.h"
+#include "cw_update_body.h"
 
 namespace pc3d {
 
@@ -656,7 +657,51 @@ __device__ __forceinline__ void pm_bwd_rows(const float* W3, int my_e, int my_g,
   }
 }
 
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void pointmlp3_max_bwd_kernel(PMBwdArgs a) {
+// The CW update as the epilogue of the LAST backward launch of an iteration (the STN tower's, in accumulate form): the
+// three values lane p of wave 0 holds at the end — the gradient already in gx plus this tower's — are the whole input
+// gradient of point p, so Adam + clip + the distance gradient (cw_point_update) run right there instead of in a launch
+// of their own. A workgroup reads and writes only its own 32 points: updating adv in place is safe.
+struct PMUpdArgs {
+  PtsViewMut adv;            // the iterate (the tower's x), updated in place; m / v share its layout
+  float *m, *v;
+  PtsView ori;
+  const int32_t* nn_idx;     // [B,N] (kind 2)
+  const float* w;            // [B] (kind 1, 2)
+  const float* dist_val;     // [B] ||adv - ori||_F (kind 1)
+  const float* adam;         // [2] {step_size, bc2s}
+  int B;
+  int dist_kind;
+  float omb1, omb2, fb2, eps, budget;
+};
+constexpr int PM_UPD_LD = 3 * PM_BTP;   // parked operands: [p, ori, m, v, ori[nn]][coordinate][point] + 4 per-sample words
+
+// lane p of wave 0: point n = n0 + p with its whole input gradient (g0, g1, g2)
+__device__ __forceinline__ void pm_bwd_update_point(const PMUpdArgs& u, const float* s_u, int N, int b, int n, int p,
+                                                    float g0, float g1, float g2) {
+  const float* s_uc = s_u + 5 * PM_UPD_LD;
+  const CwPointConsts c{u.dist_kind, u.B, N, u.omb1, u.omb2, u.fb2, s_uc[2], s_uc[3], u.eps, u.budget};
+  float pin[3], oin[3], m[3], v[3], q[3], np_[3], g[3] = {g0, g1, g2};
+#pragma unroll
+  for (int e = 0; e < 3; ++e) {
+    pin[e] = s_u[0 * PM_UPD_LD + e * PM_BTP + p];
+    oin[e] = s_u[1 * PM_UPD_LD + e * PM_BTP + p];
+    m[e] = s_u[2 * PM_UPD_LD + e * PM_BTP + p];
+    v[e] = s_u[3 * PM_UPD_LD + e * PM_BTP + p];
+    q[e] = s_u[4 * PM_UPD_LD + e * PM_BTP + p];
+  }
+  cw_point_update(c, pin, oin, g, q, s_uc[0], s_uc[1], m, v, np_);
+  const int64_t off = (int64_t)b * u.adv.bs + (int64_t)n * u.adv.ps;
+#pragma unroll
+  for (int e = 0; e < 3; ++e) {
+    u.m[off + e * u.adv.cs] = m[e];
+    u.v[off + e * u.adv.cs] = v[e];
+    u.adv.p[off + e * u.adv.cs] = np_[e];
+  }
+}
+
+// UPD: the accumulate form whose epilogue applies the CW update instead of storing gx (pointmlp3_max_bwd_update_kernel)
+template <bool UPD>
+__device__ __forceinline__ void pm_bwd_body(const PMBwdArgs& a, const PMUpdArgs& u) {
   __shared__ __attribute__((aligned(16))) float lds[PM_BTP * PM_LD2 + PM_BTP * PM_LD1 + 4 * PM_BTP + PM_MAXC3 + PM_MAXC3];  // 34.3 KB
   float* g2s = lds;                                   // [32][132]
   float* h1s = g2s + PM_BTP * PM_LD2;                 // [32][68]   g1 (phase C on); before that the sort's counters
@@ -671,6 +716,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   __shared__ uint64_t s_m1[PM_BTP];
   __shared__ float s_W1[PM_C1 * 3];
   __shared__ float s_x[3 * PM_BTP], s_gxo[3 * PM_BTP], s_T[12];
+  __shared__ float s_u[UPD ? 5 * PM_UPD_LD + 4 : 1];
   static_assert(PM_MAXC3 <= 1024 && PM_BTP <= 32, "a hit is packed as point << 10 | channel in 16 bits");
   const int tile = blockIdx.x, b = blockIdx.y;
   const int n0 = tile * PM_BTP;
@@ -680,6 +726,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 
   // ---- entry: every load that depends on nothing, smallest first (vector-memory results return in issue order, so
   // anything issued behind the 32 KiB weight prefetch below would wait for all of it)
+  float ld_u[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  if (UPD) {   // the update's operands first: ori[nn_idx] is the one dependent load of the launch
+    if (tid < 3 * PM_BTP) {
+      const int p = tid & (PM_BTP - 1), c = tid >> 5;
+      if (n0 + p < a.N) {
+        const int64_t off = (int64_t)b * u.adv.bs + (int64_t)(n0 + p) * u.adv.ps + c * u.adv.cs;
+        const float* ob = u.ori.p + (int64_t)b * u.ori.bs + c * u.ori.cs;
+        const int j = (u.dist_kind == 2) ? u.nn_idx[(int64_t)b * a.N + n0 + p] : 0;
+        ld_u[0] = u.adv.p[off];
+        ld_u[1] = ob[(int64_t)(n0 + p) * u.ori.ps];
+        ld_u[2] = u.m[off];
+        ld_u[3] = u.v[off];
+        if (u.dist_kind == 2) ld_u[4] = ob[(int64_t)j * u.ori.ps];
+      }
+    } else if (tid < 3 * PM_BTP + 4) {
+      const int e = tid - 3 * PM_BTP;
+      if (e == 0) ld_u[0] = u.w ? u.w[b] : 0.f;
+      else if (e == 1) ld_u[0] = u.dist_val ? u.dist_val[b] : 0.f;
+      else ld_u[0] = u.adam[e - 2];
+    }
+  }
   int ld_n[PM_MAXC3 / 256];
   float ld_g[PM_MAXC3 / 256];
 #pragma unroll
@@ -744,6 +811,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   } else if (tid >= 128 && tid < 137) {
     s_T[tid - 128] = ld_t;
   }
+  if (UPD) {
+    if (tid < 3 * PM_BTP) {
+#pragma unroll
+      for (int e = 0; e < 5; ++e) s_u[e * PM_UPD_LD + tid] = ld_u[e];
+    } else if (tid < 3 * PM_BTP + 4) {
+      s_u[5 * PM_UPD_LD + tid - 3 * PM_BTP] = ld_u[0];
+    }
+  }
   for (int i = tid; i < PM_BTP * PM_LD2; i += 256) g2s[i] = 0.f;   // a point without a hit keeps a zero row
   int incl = cnt;
 #pragma unroll
@@ -761,6 +836,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     L += v;
   }
   if (L == 0) {  // no critical point in this tile: gradient is exactly zero
+    if (UPD && wave == 0 && lane < PM_BTP && n0 + lane < a.N)   // the gradient already in gx is the whole gradient
+      pm_bwd_update_point(u, s_u, a.N, b, n0 + lane, lane, s_gxo[lane], s_gxo[PM_BTP + lane], s_gxo[2 * PM_BTP + lane]);
     if (tid < 3 * PM_BTP && !a.accumulate) {
       const int p = tid & (PM_BTP - 1), c = tid >> 5;
       if (n0 + p < a.N) a.gx.p[(int64_t)b * a.gx.bs + (int64_t)(n0 + p) * a.gx.ps + c * a.gx.cs] = 0.f;
@@ -914,7 +991,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         if (lane < 16) a.part_gT[((int64_t)b * gridDim.x + tile) * 16 + lane] = mine;
       }
     }
-    if (live && n0 + p < a.N) {
+    if (UPD) {
+      if (live && n0 + p < a.N)
+        pm_bwd_update_point(u, s_u, a.N, b, n0 + p, p, s_gxo[p] + o0, s_gxo[PM_BTP + p] + o1, s_gxo[2 * PM_BTP + p] + o2);
+    } else if (live && n0 + p < a.N) {
       float* q = a.gx.p + (int64_t)b * a.gx.bs + (int64_t)(n0 + p) * a.gx.ps;
       if (a.accumulate) {
         q[0] = s_gxo[p] + o0, q[a.gx.cs] = s_gxo[PM_BTP + p] + o1, q[2 * a.gx.cs] = s_gxo[2 * PM_BTP + p] + o2;
@@ -923,6 +1003,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
       }
     }
   }
+}
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void pointmlp3_max_bwd_kernel(PMBwdArgs a) {
+  pm_bwd_body<false>(a, PMUpdArgs{});
+}
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void pointmlp3_max_bwd_update_kernel(PMBwdArgs a,
+                                                                                                                   PMUpdArgs u) {
+  pm_bwd_body<true>(a, u);
 }
 
 }  // namespace pc3d
@@ -1027,4 +1115,35 @@ extern "C" int pc3d_pointmlp3_max_bwd_twolist_f32(const float* x, int64_t x_bs, 
   return pm_bwd_launch("pc3d_pointmlp3_max_bwd_twolist_f32", true, x, x_bs, x_ps, x_cs, B, N, T, W1, b1, W2, b2, W3, W2T,
                        C1, C2, C3, argidx, mask1, mask2, g_pooled, grad_x, gx_bs, gx_ps, gx_cs, part_gT, accumulate,
                        stream);
+}
+
+extern "C" int pc3d_pointmlp3_max_bwd_update_f32(float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                                 const float* W1, const float* b1, const float* W2, const float* b2,
+                                                 const float* W3, const float* W2T, int C1, int C2, int C3,
+                                                 const int32_t* argidx, const uint64_t* mask1, const uint32_t* mask2,
+                                                 const float* g_pooled, const float* grad_x, int64_t gx_bs, int64_t gx_ps,
+                                                 int64_t gx_cs, const float* ori, int64_t o_bs, int64_t o_ps, int64_t o_cs,
+                                                 float* m, float* v, double beta1, double beta2, double eps, float budget,
+                                                 const float* adam, int dist_kind, const float* w, const float* dist_val,
+                                                 const int32_t* nn_idx, void* stream) {
+  const char* who = "pc3d_pointmlp3_max_bwd_update_f32";
+  PC3D_REQUIRE(B >= 0 && N >= 1, "%s: bad sizes B=%d N=%d", who, B, N);
+  PC3D_REQUIRE(C1 == PM_C1 && C2 == PM_C2 && C3 >= 32 && C3 % 32 == 0 && C3 <= PM_MAXC3,
+               "%s: unsupported widths %d/%d/%d", who, C1, C2, C3);
+  PC3D_REQUIRE(B <= 65535, "%s: B=%d exceeds grid.y limit", who, B);
+  PC3D_REQUIRE(dist_kind >= 0 && dist_kind <= 2, "%s: dist_kind=%d not in {0,1,2}", who, dist_kind);
+  if (B == 0) return PC3D_OK;
+  PC3D_REQUIRE(x && W1 && b1 && W2 && b2 && W3 && W2T && argidx && mask1 && mask2 && g_pooled && grad_x && ori && m && v && adam,
+               "%s: null pointer", who);
+  PC3D_REQUIRE(dist_kind == 0 || w != nullptr, "%s: distance term needs the weights w", who);
+  PC3D_REQUIRE(dist_kind != 1 || dist_val != nullptr, "%s: L2 term needs dist_val", who);
+  PC3D_REQUIRE(dist_kind != 2 || nn_idx != nullptr, "%s: Chamfer term needs nn_idx", who);
+  // gx is only read here (the sum goes into the update, not back to memory)
+  PMBwdArgs a{{x, x_bs, x_ps, x_cs}, N, C3, nullptr, W1, b1, W2, b2, W3, W2T, argidx, mask1, mask2, g_pooled,
+              {const_cast<float*>(grad_x), gx_bs, gx_ps, gx_cs}, nullptr, 1};
+  PMUpdArgs u{{x, x_bs, x_ps, x_cs}, m, v, {ori, o_bs, o_ps, o_cs}, nn_idx, w, dist_val, adam, B, dist_kind,
+              (float)(1.0 - beta1), (float)(1.0 - beta2), (float)beta2, (float)eps, budget};
+  hipLaunchKernelGGL(pointmlp3_max_bwd_update_kernel, dim3(cdiv(N, PM_BTP), B), dim3(256), 0, as_stream(stream), a, u);
+  PC3D_LAUNCH_CHECK(who);
+  return PC3D_OK;
 }

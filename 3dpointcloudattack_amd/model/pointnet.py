@@ -192,6 +192,56 @@ class PointNetCls(_FrozenFusedMixin, nn.Module):
                                            pred_out=pred_out, step=step, want_logp=False)
         return pred, loss, fused_input_grad(ctx, None, g_c2=g_c2)
 
+    def fused_attack_update(self, x, target, kind, kappa=0.0, pred_out=None, step=None, scale=None, cw=None,
+                            ride_search=True, epilogue=True):
+        """A whole CW iteration on the iterate x ([B,3,N], updated IN PLACE) in 15 launches, one chain: fused_attack_grad's
+        victim passes with the attack's independent pieces carried by launches that exist anyway —
+          * the adv -> ori search (Chamfer) rides the STN head's first linear launch (ops.linear_nn);
+          * the bookkeeping (||adv-ori||, best-distance decisions, input_val / o_bestattack copies) and Adam's two
+            bias-correction factors ride the first launch after the classifier tail (ops.linear_book);
+          * distance gradient + Adam + clip are the epilogue of the last backward launch (ops.pointmlp3_max_bwd_update).
+        The same bits as fused_attack_grad + ops.nn_raw + ops.cw_update. cw: the loop's state — ori, label, untarget,
+        bestdist, bestscore, o_bestdist, o_bestscore, o_bestattack, input_val, dist_val, m, v, w, adam (float32 [2]), lr,
+        budget, dist_kind. ride_search / epilogue = False give that piece its own launch again (A/B switches). Returns pred."""
+        self._require_fused(x)
+        pk = fused_pack(self)
+        w1s, b1s, w2s, b2s, w3s, b3s = pk["s"]
+        w1c, b1c, w2c, b2c, w3c, b3c = pk["c"]
+        w1c_t, w2c_t, w3c_t = pk["c_t"]
+        w1s_t, w2s_t, w3s_t = pk["s_t"]
+        dk, ori = cw["dist_kind"], cw["ori"]
+        pooled_s, idx_s, masks_s = ops.pointmlp3_max_fwd_raw(x, pk["tower_s"], True, want_masks=True)
+        nn_idx = None
+        if dk == 2:
+            a1, _, nn_idx = ops.linear_nn(pooled_s, w1s, b1s, relu=True, q=x, r=ori, q_cf=True, r_cf=True, ride=ride_search)
+        else:
+            a1 = ops.linear(pooled_s, w1s, b1s, relu=True)
+        a2 = ops.linear(a1, w2s, b2s, relu=True)
+        pooled, idx, masks, trans = ops.pointmlp3_max_fwd_raw(x, pk["tower_c"], False, want_masks=True, T_head=(a2, w3s, b3s))
+        c1 = ops.linear(pooled, w1c, b1c, relu=True)
+        c2 = ops.linear(c1, w2c, b2c, relu=True)
+        _, pred, _, g_c2 = ops.cls_tail(c2, w3c, b3c, target, kind, kappa, scale=1.0 / x.shape[0] if scale is None else scale,
+                                        pred_out=pred_out, step=step, want_logp=False)
+        if epilogue:
+            g_c1 = ops.linear_book(g_c2, w2c_t, x, ori, pred, cw["label"], cw["untarget"], cw["bestdist"], cw["bestscore"],
+                                   cw["o_bestdist"], cw["o_bestscore"], cw["o_bestattack"], gate=c1,
+                                   input_val=cw["input_val"], dist_val=cw["dist_val"], step=step, lr=cw["lr"], adam=cw["adam"])
+        else:
+            g_c1 = ops.linear(g_c2, w2c_t, gate=c1)
+        g_pooled = ops.linear(g_c1, w1c_t)
+        gx, part_gT = ops.pointmlp3_max_bwd_raw(x, pk["tower_c"], idx, g_pooled, masks, T=trans, want_gT=True)
+        g_a1 = ops.linear_pre(part_gT, 9, pk["s"][4], a2, w2s_t, gate=a1)
+        g_pooled_s = ops.linear(g_a1, w1s_t, gate=pooled_s)
+        if epilogue:
+            ops.pointmlp3_max_bwd_update(x, pk["tower_s"], idx_s, g_pooled_s, masks_s, gx, ori, cw["m"], cw["v"], cw["adam"],
+                                         cw["budget"], dist_kind=dk, w=cw["w"], dist_val=cw["dist_val"], nn_idx=nn_idx)
+        else:
+            ops.pointmlp3_max_bwd_raw(x, pk["tower_s"], idx_s, g_pooled_s, masks_s, out=gx, accumulate=True)
+            ops.cw_update(x, ori, pred, cw["label"], cw["untarget"], cw["bestdist"], cw["bestscore"], cw["o_bestdist"],
+                          cw["o_bestscore"], cw["o_bestattack"], gx, cw["m"], cw["v"], step, cw["lr"], cw["budget"],
+                          input_val=cw["input_val"], dist_val=cw["dist_val"], dist_kind=dk, w=cw["w"], nn_idx=nn_idx)
+        return pred
+
     def forward(self, x):
         self._require_fused(x)
         head = self.folded()

@@ -803,6 +803,101 @@ def cw_update(adv, ori, pred, label, untarget, bestdist, bestscore, o_bestdist, 
     return adv
 
 
+# ------------------------------------------------------------------------------------------------------
+# CW-family loop: independent pieces carried by launches that exist anyway (csrc/linear_riders.hip, pointmlp.hip)
+# ------------------------------------------------------------------------------------------------------
+def _linear_args(who, X, W, bias, relu, gate, out, slope, gate_slope):
+    """pc3d_linear_f32's first 15 arguments for a plain [B,K] X (+ the output tensor)."""
+    _check(X, "X")
+    _check(W, "W")
+    B, K = X.shape
+    if X.stride(1) != 1:
+        raise ValueError(f"{who}: X rows must be contiguous")
+    O = W.shape[0]
+    if W.shape[1] != K or not W.is_contiguous():
+        raise ValueError(f"{who}: W must be contiguous [O,{K}], got {tuple(W.shape)}")
+    Y = out if out is not None else torch.empty((B, O), dtype=torch.float32, device=X.device)
+    return [X.data_ptr(), X.stride(0), 1, B, K, W.data_ptr(), _ptr(bias), O, 1 if relu else 0, float(slope), _ptr(gate),
+            gate.stride(0) if gate is not None else 0, float(gate_slope), Y.data_ptr(), Y.stride(0)], Y
+
+
+def linear_nn(X, W, bias=None, relu=False, gate=None, q=None, r=None, q_cf=False, r_cf=False, want_idx=True, ride=True,
+              out=None, slope=0.0, gate_slope=0.0):
+    """linear(X, W, ...) and nn_raw(q, r, ...) as ONE launch (pc3d_linear_nn_f32): the search's workgroups ride behind
+    the layer's. Returns (Y, min_d2, idx), the same bits as the two calls. Shapes outside the rider's range, or
+    ride=False, run the two launches — the entry decides."""
+    args, Y = _linear_args("linear_nn", X, W, bias, relu, gate, out, slope, gate_slope)
+    qp, qbs, qps, qcs, B, N = _pts(q, q_cf, "q")
+    rp, rbs, rps, rcs, B2, M = _pts(r, r_cf, "r")
+    if B != B2:
+        raise ValueError("q and r must have the same batch dimension")
+    if M < 1:
+        raise ValueError("reference set is empty")
+    d = torch.empty((B, N), dtype=torch.float32, device=q.device)
+    i = torch.empty((B, N), dtype=torch.int32, device=q.device) if want_idx else None
+    with torch.cuda.device(X.device):
+        _lib.call("pc3d_linear_nn_f32", *args, qp, qbs, qps, qcs, rp, rbs, rps, rcs, B, N, M, d.data_ptr(), _ptr(i),
+                  1 if ride else 0, _stream())
+    return Y, d, i
+
+
+def linear_book(X, W, adv, ori, pred, label, untarget, bestdist, bestscore, o_bestdist, o_bestscore, o_bestattack,
+                bias=None, relu=False, gate=None, input_val=None, dist_val=None, step=None, lr=0.0, adam=None,
+                betas=(0.9, 0.999), cf=True, ride=True, out=None, slope=0.0, gate_slope=0.0):
+    """linear(X, W, ...) and the bookkeeping half of cw_update (||adv-ori|| into dist_val, best-distance decisions, the
+    input_val / o_bestattack copies; the same bits) as ONE launch (pc3d_linear_book_f32). adam: float32 [2] to receive
+    Adam's {step size, sqrt of the second bias correction} for the value of the device step word `step`. Returns Y."""
+    args, Y = _linear_args("linear_book", X, W, bias, relu, gate, out, slope, gate_slope)
+    _, _, _, _, B, K = _pts(adv, cf, "adv")
+    if K > CW_UPDATE_MAX_POINTS:
+        raise ValueError(f"linear_book: {K} points; the bookkeeping holds at most {CW_UPDATE_MAX_POINTS} per sample")
+    for nm, t in (("o_bestattack", o_bestattack), ("input_val", input_val)):
+        if t is not None and (t.shape != adv.shape or t.stride() != adv.stride()):
+            raise ValueError(f"linear_book: {nm} must share adv's shape and strides")
+    if adam is not None and (adam.dtype != torch.float32 or adam.numel() < 2 or not adam.is_contiguous() or step is None):
+        raise ValueError("linear_book: adam must be a contiguous float32 [2] tensor and needs the device step word")
+    with torch.cuda.device(X.device):
+        _lib.call("pc3d_linear_book_f32", *args, *_pv(adv, cf, "adv"), *_pv(ori, cf, "ori"), B, K, pred.data_ptr(),
+                  label.data_ptr(), 1 if untarget else 0, bestdist.data_ptr(), bestscore.data_ptr(),
+                  o_bestdist.data_ptr(), o_bestscore.data_ptr(), o_bestattack.data_ptr(), _ptr(input_val),
+                  _ptr(dist_val), float(lr), float(betas[0]), float(betas[1]), _ptr(step), _ptr(adam),
+                  1 if ride else 0, _stream())
+    return Y
+
+
+def pointmlp3_max_bwd_update(x, weights, argidx, g_pooled, masks, gx, ori, m, v, adam, budget, dist_kind=0, w=None,
+                             dist_val=None, nn_idx=None, betas=(0.9, 0.999), eps=1e-8, x_cf=True):
+    """pointmlp3_max_bwd_raw(..., out=gx, accumulate=True) followed by the update half of cw_update, as ONE launch
+    (pc3d_pointmlp3_max_bwd_update_f32): x — the iterate — and the Adam moments m / v are updated in place, gx is only
+    read. adam: the [2] factors written by linear_book; dist_val: ||adv-ori|| per sample (dist_kind 1)."""
+    xp, xbs, xps, xcs, B, N = _pts(x, x_cf, "x")
+    W1, b1, W2, b2, W3, b3 = weights[:6]
+    W2T = weights[6] if len(weights) > 6 else W2.t().contiguous()
+    C1, C2, C3 = W1.shape[0], W2.shape[0], W3.shape[0]
+    _check(g_pooled, "g_pooled")
+    g_pooled = g_pooled.contiguous()
+    m1, m2 = masks
+    if m1.shape != (B, N) or m1.dtype != torch.int64 or m2.shape != (B, N, 4) or m2.dtype != torch.int32 \
+            or not (m1.is_contiguous() and m2.is_contiguous()):
+        raise ValueError("pointmlp3_max_bwd_update: masks must be the (int64 [B,N], int32 [B,N,4]) pair of the forward launch")
+    for nm, t in (("m", m), ("v", v)):
+        _check(t, nm)
+        if t.shape != x.shape or t.stride() != x.stride():
+            raise ValueError(f"pointmlp3_max_bwd_update: {nm} must share x's shape and strides")
+    if tuple(gx.shape) != tuple(x.shape):
+        raise ValueError("pointmlp3_max_bwd_update: gx must have x's shape")
+    if nn_idx is not None and (nn_idx.dtype != torch.int32 or tuple(nn_idx.shape) != (B, N) or not nn_idx.is_contiguous()):
+        raise ValueError("pointmlp3_max_bwd_update: nn_idx must be a contiguous int32 [B,N] tensor")
+    with torch.cuda.device(x.device):
+        _lib.call("pc3d_pointmlp3_max_bwd_update_f32", xp, xbs, xps, xcs, B, N,
+                  W1.data_ptr(), b1.data_ptr(), W2.data_ptr(), b2.data_ptr(), W3.data_ptr(), W2T.data_ptr(),
+                  C1, C2, C3, argidx.data_ptr(), m1.data_ptr(), m2.data_ptr(), g_pooled.data_ptr(),
+                  *_pv(gx, x_cf, "gx"), *_pv(ori, x_cf, "ori"), m.data_ptr(), v.data_ptr(), float(betas[0]), float(betas[1]),
+                  float(eps), float(budget), adam.data_ptr(), int(dist_kind), _ptr(w), _ptr(dist_val), _ptr(nn_idx),
+                  _stream())
+    return x
+
+
 ADD_UPDATE_MAX_POINTS = 2048   # pc3d_add_update_f32 keeps a sample's added points in registers (4 per thread x 512)
 ADD_UPDATE_MAX_CLUSTER = 64    # ... and gives every cluster of the farthest-pair term one wavefront
 ADD_KINDS = {"chamfer": 1, "hausdorff": 2, "far_chamfer": 3}

@@ -925,6 +925,48 @@ int pc3d_pcd_tail_f32(const float* h, int64_t ldh, const float* w3, const float*
 int pc3d_pcd_tail_bwd_f32(const float* g, const uint32_t* mask, const float* w4, const float* w3t, int B, int N, int R, int C2,
                           int C3, float* gh, int64_t ldgh, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * The CW iteration (attack/CW/CW_attack.py:111-174) with its independent pieces carried by launches that exist anyway:
+ * 15 launches per iteration instead of 17, still one chain. Every entry computes the bits of the launches it replaces.
+ *
+ * pc3d_linear_nn_f32: pc3d_linear_f32 (first 15 arguments) + pc3d_nn_f32 (q, r, NB clouds, N queries, M reference
+ * points, min_d2 / idx) as ONE launch: the search's workgroups ride behind the layer's. ride = 0, or a shape outside
+ * the rider's range (the layer not on the 32 x 16 tiling, the search not on its 512-thread form or M > 2048), runs the
+ * two existing launches instead: callers always make one call.
+ * ------------------------------------------------------------------------------------------------------- */
+int pc3d_linear_nn_f32(const float* X, int ldx, int P, int B, int K, const float* W, const float* bias, int O,
+                       int relu, float slope, const float* gate, int ldg, float gate_slope, float* Y, int ldy,
+                       const float* q, int64_t q_bs, int64_t q_ps, int64_t q_cs,
+                       const float* r, int64_t r_bs, int64_t r_ps, int64_t r_cs,
+                       int NB, int N, int M, float* min_d2, int32_t* idx, int ride, void* stream);
+/* pc3d_linear_f32 + the bookkeeping half of pc3d_cw_update_f32 (||adv-ori|| into dist_val, best-distance decisions,
+ * the input_val / o_bestattack copies; same reduction tree, same bits) for NB samples of NK <= 8192 points, as NB extra
+ * workgroups of the layer's launch. adam [2] (may be NULL) receives Adam's {lr / (1 - beta1^t), sqrt(1 - beta2^t)} for
+ * the value t of the device step word step_dev. ride = 0 or a layer outside the 32 x 16 tiling: two launches. */
+int pc3d_linear_book_f32(const float* X, int ldx, int P, int B, int K, const float* W, const float* bias, int O,
+                         int relu, float slope, const float* gate, int ldg, float gate_slope, float* Y, int ldy,
+                         const float* adv, int64_t a_bs, int64_t a_ps, int64_t a_cs,
+                         const float* ori, int64_t o_bs, int64_t o_ps, int64_t o_cs, int NB, int NK,
+                         const int64_t* pred, const int64_t* label, int untarget,
+                         float* bestdist, int64_t* bestscore, float* o_bestdist, int64_t* o_bestscore,
+                         float* o_bestattack, float* input_val, float* dist_val,
+                         double lr, double beta1, double beta2, const int32_t* step_dev, float* adam,
+                         int ride, void* stream);
+/* pc3d_pointmlp3_max_bwd_f32 in accumulate form (T = NULL, no dL/dT) whose epilogue applies the update half of
+ * pc3d_cw_update_f32 to the tower's input x (= the iterate adv, updated IN PLACE together with m / v, which share its
+ * strides) instead of storing grad_x + this tower's gradient: distance gradient (dist_kind 0 / 1 / 2 as
+ * pc3d_cw_step_f32; dist_val = ||adv-ori|| per sample for kind 1, nn_idx for kind 2), Adam with the factors adam [2] of
+ * pc3d_linear_book_f32, ClipPointsLinf (budget > 0). grad_x is only read. */
+int pc3d_pointmlp3_max_bwd_update_f32(float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                      const float* W1, const float* b1, const float* W2, const float* b2,
+                                      const float* W3, const float* W2T, int C1, int C2, int C3,
+                                      const int32_t* argidx, const uint64_t* mask1, const uint32_t* mask2,
+                                      const float* g_pooled, const float* grad_x, int64_t gx_bs, int64_t gx_ps,
+                                      int64_t gx_cs, const float* ori, int64_t o_bs, int64_t o_ps, int64_t o_cs,
+                                      float* m, float* v, double beta1, double beta2, double eps, float budget,
+                                      const float* adam, int dist_kind, const float* w, const float* dist_val,
+                                      const int32_t* nn_idx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
