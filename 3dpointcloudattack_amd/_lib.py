@@ -157,6 +157,10 @@ SIGNATURES = {
     "pc3d_three_interp_bwd_f32": _PTS + _PTS + [_P, _P, _P, _L, _P, _L, _P, _L, _P, _P, _I, _I, _I, _I] + [_P] * 5 + [_P],
     "pc3d_pcd_tail_f32": [_P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
     "pc3d_pcd_tail_bwd_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P],
+    "pc3d_iso_apply_f32": _PTS + [_P, _I, _I, _I, _I] + _PTS + [_P],
+    "pc3d_iso_wgrad_f32": _PTS + _PTS + [_I, _I, _I, _P, _P],
+    "pc3d_iso_update_f32": _PTS + _PTS + [_P, _I, _I, _P, _P, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _D, _D, _D, _D]
+    + _PTS + [_P],
 }
 
 # entry points that do not return a status code

@@ -2943,3 +2943,112 @@ def pcd_tail(h, w3, b3, w4, b4, B, N, r):
         h = h.contiguous()
     return _PcdTailFn.apply(h, w3.detach().contiguous(), b3.detach().contiguous(), w4.detach().contiguous(),
                             b4.detach().contiguous(), B, N, r)
+
+
+# ------------------------------------------------------------------------------------------------------
+# The isometry attack (attack/ISO): x' = W x with one 3x3 matrix per cloud (csrc/iso.hip)
+# ------------------------------------------------------------------------------------------------------
+def _iso_w(W, n, name="W"):
+    """W as a contiguous [n, 9] view (n matrices, row-major)."""
+    _check(W, name)
+    if W.numel() != n * 9:
+        raise ValueError(f"{name}: expected {n} 3x3 matrices, got shape {tuple(W.shape)}")
+    return W.reshape(n, 9) if W.is_contiguous() else W.contiguous().view(n, 9)
+
+
+def iso_apply(x, W, R=1, transpose=False, cf=True, out=None):
+    """out[b R + r] = W[b R + r] x[b] (W^T with transpose) for the R matrices of every cloud: x [B,3,N] (cf) or [B,N,3],
+    W [B*R,3,3], out [B*R,3,N] / [B*R,N,3]. x is read in place through its strides, once for its R matrices."""
+    xp, xbs, xps, xcs, B, N = _pts(x, cf, "x")
+    R = int(R)
+    W9 = _iso_w(W, B * R)
+    if out is None:
+        out = torch.empty((B * R, 3, N) if cf else (B * R, N, 3), dtype=torch.float32, device=x.device)
+    op, obs, ops_, ocs, Bo, No = _pts(out, cf, "out")
+    if (Bo, No) != (B * R, N):
+        raise ValueError(f"iso_apply: out has shape {tuple(out.shape)}, expected {B * R} clouds of {N} points")
+    with torch.cuda.device(x.device):
+        _lib.call("pc3d_iso_apply_f32", xp, xbs, xps, xcs, W9.data_ptr(), B, R, N, 1 if transpose else 0, op, obs, ops_, ocs,
+                  _stream())
+    return out
+
+
+def iso_wgrad(g, x, R=1, cf=True):
+    """gW [B*R,3,3] with gW[i, a, c] = sum_n g[i, a, n] x[i // R, c, n]: g [B*R,3,N], x [B,3,N] (cf) or channels-last.
+    One fixed summation order, whatever B and R."""
+    xp, xbs, xps, xcs, B, N = _pts(x, cf, "x")
+    gp, gbs, gps, gcs, BR, Ng = _pts(g, cf, "g")
+    R = int(R)
+    if BR != B * R or Ng != N:
+        raise ValueError(f"iso_wgrad: g {tuple(g.shape)} does not match x {tuple(x.shape)} with R={R}")
+    gW = torch.empty((BR, 3, 3), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.call("pc3d_iso_wgrad_f32", gp, gbs, gps, gcs, xp, xbs, xps, xcs, B, R, N, gW.data_ptr(), _stream())
+    return gW
+
+
+def iso_update(x, xo, W, m, v, pred, label, row, done, steps, kept_out, kept_pred, lr, g=None, gW=None,
+               betas=(0.9, 0.999), eps=1e-8, cf=True):
+    """The non-victim part of one CTRI step in one launch (see pc3d_iso_update_f32): latch `done` on pred != label, record
+    this evaluation (steps, kept_out = row, kept_pred) for the clouds not done on entry, Adam on W (m, v [B,3,3]) for the
+    clouds still running — gradient g x^T from the point gradient g, or gW as given — and xo = W x for all. In place."""
+    xp, xbs, xps, xcs, B, N = _pts(x, cf, "x")
+    op, obs, ops_, ocs, Bo, No = _pts(xo, cf, "xo")
+    if (Bo, No) != (B, N):
+        raise ValueError("iso_update: xo must have x's shape")
+    if (g is None) == (gW is None):
+        raise ValueError("iso_update: give exactly one of g (point gradient) and gW (weight gradient)")
+    for t, nm in ((W, "W"), (m, "m"), (v, "v")):
+        _check(t, nm)
+        if t.numel() != B * 9 or not t.is_contiguous():
+            raise ValueError(f"iso_update: {nm} must be a contiguous [B,3,3] tensor")
+    _check(row, "row"), _check(kept_out, "kept_out")
+    if row.dim() != 2:
+        raise ValueError("iso_update: row must be [B,ncls]")
+    ncls = row.shape[1]
+    if row.shape[0] != B or row.stride(1) != 1 or kept_out.shape != (B, ncls) or not kept_out.is_contiguous():
+        raise ValueError("iso_update: row [B,ncls] (unit column stride) and a contiguous kept_out [B,ncls] are required")
+    for t, nm, dt in ((pred, "pred", torch.int64), (label, "label", torch.int64), (kept_pred, "kept_pred", torch.int64),
+                      (done, "done", torch.int32), (steps, "steps", torch.int32)):
+        if t.dtype != dt or t.shape != (B,) or not t.is_contiguous() or not t.is_cuda:
+            raise TypeError(f"iso_update: {nm} must be a contiguous {dt} [B] GPU tensor")
+    gv = _pv(g, cf, "g")
+    if g is not None and tuple(g.shape) != tuple(x.shape):
+        raise ValueError("iso_update: g must have x's shape")
+    if gW is not None:
+        gW = _iso_w(gW, B, "gW")
+    with torch.cuda.device(x.device):
+        _lib.call("pc3d_iso_update_f32", xp, xbs, xps, xcs, *gv, _ptr(gW), B, N, pred.data_ptr(), label.data_ptr(),
+                  row.data_ptr(), row.stride(0), ncls, done.data_ptr(), steps.data_ptr(), kept_out.data_ptr(),
+                  kept_pred.data_ptr(), W.data_ptr(), m.data_ptr(), v.data_ptr(), float(lr), float(betas[0]), float(betas[1]),
+                  float(eps), op, obs, ops_, ocs, _stream())
+    return xo
+
+
+class IsoTransform(torch.autograd.Function):
+    """x' = W x in front of any victim: x [B,3,N], W [B*R,3,3] -> [B*R,3,N]. Backward: gW by iso_wgrad, gx by the
+    transposed apply (summed over a cloud's R matrices)."""
+
+    @staticmethod
+    def forward(ctx, x, W):
+        B = x.shape[0]
+        if B < 1 or W.numel() % (9 * B):
+            raise ValueError(f"IsoTransform: W {tuple(W.shape)} does not hold a whole number of 3x3 matrices per cloud of x {tuple(x.shape)}")
+        R = W.numel() // (9 * B)
+        Wc = W.detach().reshape(B * R, 3, 3).contiguous()
+        ctx.save_for_backward(x.detach(), Wc)
+        ctx.R, ctx.wshape = R, W.shape
+        return iso_apply(x.detach(), Wc, R=R)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, Wc = ctx.saved_tensors
+        R = ctx.R
+        gW = gx = None
+        if ctx.needs_input_grad[1]:
+            gW = iso_wgrad(g, x, R=R).reshape(ctx.wshape)
+        if ctx.needs_input_grad[0]:
+            gx = iso_apply(g, Wc, R=1, transpose=True)           # W_i^T g_i, one matrix per gradient cloud
+            if R > 1:
+                gx = gx.view(x.shape[0], R, 3, -1).sum(1)
+        return gx, gW

@@ -967,6 +967,37 @@ int pc3d_pointmlp3_max_bwd_update_f32(float* x, int64_t x_bs, int64_t x_ps, int6
                                       const float* adam, int dist_kind, const float* w, const float* dist_val,
                                       const int32_t* nn_idx, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * The isometry attack (attack/ISO/iso_attack.py): x' = W x with one 3x3 matrix per cloud, in front of a frozen victim.
+ * W is row-major [., 9]; point tensors are B clouds (or B * R for the per-matrix ones) of N points with element strides.
+ * ------------------------------------------------------------------------------------------------------- */
+/* out[b R + r, :, n] = W[b R + r] x[b, :, n] for R >= 1 matrices per cloud (ISOnet's nn.Linear(3, 3, bias=False),
+ * iso_attack.py:96-100); transpose != 0 applies W^T instead, the input-gradient direction of the same op. x [B clouds] is
+ * read once for its R matrices; out [B * R clouds] must not alias it. B <= 65535. */
+int pc3d_iso_apply_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, const float* W, int B, int R, int N,
+                       int transpose, float* out, int64_t o_bs, int64_t o_ps, int64_t o_cs, void* stream);
+/* gW[i, a, c] = sum_n g[i, a, n] * x[i / R, c, n] for the B * R matrices (g: B * R clouds, x: B clouds, gW [B * R, 9]).
+ * One workgroup per matrix and one summation order that depends on neither B nor R; no float atomics. */
+int pc3d_iso_wgrad_f32(const float* g, int64_t g_bs, int64_t g_ps, int64_t g_cs,
+                       const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int R, int N, float* gW,
+                       void* stream);
+/* Everything of one CTRI step (gradient_attack, iso_attack.py:127-153) that is not the victim, per cloud, one launch:
+ *   latch   a cloud that is not done and has pred[b] != label[b] becomes done (the reference's `break`);
+ *   record  while the cloud was not done ON ENTRY: steps[b] += 1, kept_out[b] = row[b] (this evaluation's [ncls] output
+ *           row, row stride row_ld), kept_pred[b] = pred[b];
+ *   update  a cloud that is still not done takes one torch.optim.Adam step (weight_decay 0, amsgrad off) on W[b] with
+ *           the gradient gW[b] = g[b] x[b]^T — pc3d_iso_wgrad_f32's reduction, the same bits — or with gW_in[b] when
+ *           g is NULL (exactly one of g, gW_in is given). m, v [B,9]. The step number t of the Adam step is the
+ *           cloud's own device word: the value steps[b] has just taken, so a replayed launch needs no host counter;
+ *   next    xo[b] = W[b] x[b] for every cloud (a done cloud rewrites the same values). xo aliases neither x nor g.
+ * done, steps: int32 [B], zero before the first step. A done cloud's W, m, v, steps and kept_* never change again. */
+int pc3d_iso_update_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs,
+                        const float* g, int64_t g_bs, int64_t g_ps, int64_t g_cs, const float* gW_in,
+                        int B, int N, const int64_t* pred, const int64_t* label, const float* row, int64_t row_ld,
+                        int ncls, int32_t* done, int32_t* steps, float* kept_out, int64_t* kept_pred,
+                        float* W, float* m, float* v, double lr, double beta1, double beta2, double eps,
+                        float* xo, int64_t xo_bs, int64_t xo_ps, int64_t xo_cs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
