@@ -126,6 +126,7 @@ SIGNATURES = {
     "pc3d_edge_max_bwd_slice_f32": [_P, _L, _P, _P, _I, _I, _I, _F, _P, _I, _P],
     "pc3d_group_max_linear_bwd_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
     "pc3d_cls_tail_f32": [_P, _I, _I, _P, _P, _I, _P, _I, _F, _F, _P, _P, _P, _P, _P, _P],
+    "pc3d_cls_tail_serial_f32": [_P, _I, _I, _P, _P, _I, _P, _I, _F, _F, _P, _P, _P, _P, _P, _P],
     "pc3d_cw_update_f32": _PTS + _PTS + [_I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P] + _PTS + [_P, _P]
     + [_D, _D, _D, _D, _F, _P, _I, _I, _P, _P, _P],
     "pc3d_add_update_f32": _PTS + _PTS + [_I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P] + _PTS + [_P, _P]
@@ -136,6 +137,7 @@ SIGNATURES = {
     "pc3d_pointmlp3_tile_points": [],
     "pc3d_pointmlp3_max_fwd_f32": _PTS + [_I, _I] + [_P] * 7 + [_I, _I, _I, _I] + [_P] * 6 + [_P],
     "pc3d_pointmlp3_max_fwd_th_f32": _PTS + [_I, _I] + [_P, _P, _P, _I, _P] + [_P] * 6 + [_I, _I, _I, _I] + [_P] * 6 + [_P],
+    "pc3d_pointmlp3_fold_f32": [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P],
     "pc3d_linear_pre_f32": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P],
     "pc3d_pointmlp3_max_bwd_f32": _PTS + [_I, _I] + [_P] * 7 + [_I, _I, _I] + [_P, _P, _P, _P] + _PTS + [_P, _I, _P],
     "pc3d_pointmlp3_max_bwd_twolist_f32": _PTS + [_I, _I] + [_P] * 7 + [_I, _I, _I] + [_P, _P, _P, _P] + _PTS + [_P, _I, _P],

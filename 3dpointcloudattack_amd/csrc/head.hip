@@ -317,6 +317,11 @@ struct ClsTailArgs {
   int32_t* step;        // incremented by block 0 (may be null)
 };
 
+// All global loads are issued at entry, before the first wait (see the staging block). SERIAL keeps the earlier form: one
+// load -> wait -> LDS write per trip of the staging loops, b3, target and the step word one behind the other
+// (pc3d_cls_tail_serial_f32: parity test and tools/bench_small_launches.py).
+constexpr int CT_WPT = CT_MAXCLS * (CT_K / 4) / CT_T;   // float4 of W3 per thread at K2 = CT_K: 16
+template <bool SERIAL>
 __global__ __launch_bounds__(CT_T) void cls_tail_kernel(ClsTailArgs a) {
   __shared__ __attribute__((aligned(16))) float s_w[CT_MAXCLS * CT_LD];   // W3 (zero rows above ncls)
   __shared__ __attribute__((aligned(16))) float s_c[CT_S * CT_LD];        // this block's rows of c2
@@ -324,21 +329,59 @@ __global__ __launch_bounds__(CT_T) void cls_tail_kernel(ClsTailArgs a) {
   const int b0 = blockIdx.x * CT_S;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int kq = a.K2 >> 2;   // float4 per row
-  for (int i = tid; i < CT_MAXCLS * kq; i += CT_T) {
-    const int r = i / kq, k4 = i - r * kq;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r < a.ncls) v = *reinterpret_cast<const float4*>(a.W3 + (int64_t)r * a.K2 + 4 * k4);
-    *reinterpret_cast<float4*>(&s_w[r * CT_LD + 4 * k4]) = v;
-  }
-  for (int i = tid; i < CT_S * kq; i += CT_T) {
-    const int r = i / kq, k4 = i - r * kq;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (b0 + r < a.B) v = *reinterpret_cast<const float4*>(a.c2 + (int64_t)(b0 + r) * a.K2 + 4 * k4);
-    *reinterpret_cast<float4*>(&s_c[r * CT_LD + 4 * k4]) = v;
-  }
   const int b = b0 + wave;
-  const float bias = (lane < a.ncls) ? a.b3[lane] : 0.f;
-  const int t = (b < a.B) ? (int)a.target[b] : 0;
+  float bias;
+  int t;
+  int32_t stepv = 0;
+  const bool steps = a.step && blockIdx.x == 0 && tid == 0;
+  if (SERIAL) {
+    for (int i = tid; i < CT_MAXCLS * kq; i += CT_T) {
+      const int r = i / kq, k4 = i - r * kq;
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (r < a.ncls) v = *reinterpret_cast<const float4*>(a.W3 + (int64_t)r * a.K2 + 4 * k4);
+      *reinterpret_cast<float4*>(&s_w[r * CT_LD + 4 * k4]) = v;
+    }
+    for (int i = tid; i < CT_S * kq; i += CT_T) {
+      const int r = i / kq, k4 = i - r * kq;
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (b0 + r < a.B) v = *reinterpret_cast<const float4*>(a.c2 + (int64_t)(b0 + r) * a.K2 + 4 * k4);
+      *reinterpret_cast<float4*>(&s_c[r * CT_LD + 4 * k4]) = v;
+    }
+    bias = (lane < a.ncls) ? a.b3[lane] : 0.f;
+    t = (b < a.B) ? (int)a.target[b] : 0;
+  } else {
+    // every global load of the kernel before the first wait: the small ones first (results return in issue order), then
+    // this thread's share of the c2 rows (CT_S * kq <= CT_T: at most one float4) and of W3 (at most CT_WPT float4)
+    // (a workgroup-scope relaxed atomic load is a plain vector load; as an ordinary load of a uniform address it becomes
+    // a scalar load that is waited for on the spot)
+    if (steps) stepv = __hip_atomic_load(a.step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    bias = (lane < a.ncls) ? a.b3[lane] : 0.f;
+    t = 0;   // the low word of the little-endian int64 is (int)target[b]
+    if (b < a.B) t = reinterpret_cast<const int32_t*>(a.target)[2 * (int64_t)b];
+    const int cr = tid / kq, ck4 = tid - cr * kq;
+    float4 cv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (cr < CT_S && b0 + cr < a.B) cv = *reinterpret_cast<const float4*>(a.c2 + (int64_t)(b0 + cr) * a.K2 + 4 * ck4);
+    float4 wv[CT_WPT];   // loaded where wlive says so (no zero to merge with at the load: the merge would wait for it)
+    int wofs[CT_WPT];    // LDS offset of element u, or -1 past the staged area
+    unsigned wlive = 0;
+    const int dq = CT_T / kq, dr = CT_T - dq * kq;   // element tid + u * CT_T is (r, k4): stepped, not divided, per u
+    int r = cr, k4 = ck4;
+#pragma unroll
+    for (int u = 0; u < CT_WPT; ++u) {
+      wofs[u] = (r < CT_MAXCLS) ? r * CT_LD + 4 * k4 : -1;
+      if (r < a.ncls) {
+        wv[u] = *reinterpret_cast<const float4*>(a.W3 + (int64_t)r * a.K2 + 4 * k4);
+        wlive |= 1u << u;
+      }
+      r += dq, k4 += dr;
+      if (k4 >= kq) k4 -= kq, r += 1;
+    }
+    if (cr < CT_S) *reinterpret_cast<float4*>(&s_c[cr * CT_LD + 4 * ck4]) = cv;
+#pragma unroll
+    for (int u = 0; u < CT_WPT; ++u)
+      if (wofs[u] >= 0)
+        *reinterpret_cast<float4*>(&s_w[wofs[u]]) = ((wlive >> u) & 1u) ? wv[u] : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
   __syncthreads();
   // logits of sample `wave`: lane = class, four interleaved fma chains over k (a re-association of the fp32 sum
   // pc3d_linear_f32 forms; the tests bound the difference)
@@ -415,25 +458,49 @@ __global__ __launch_bounds__(CT_T) void cls_tail_kernel(ClsTailArgs a) {
     for (int j = 0; j < CT_S; ++j)
       if (b0 + j < a.B) a.g_c2[(int64_t)(b0 + j) * a.K2 + tid] = (s_c[j * CT_LD + tid] > 0.f) ? acc[j] : 0.f;
   }
-  if (a.step && blockIdx.x == 0 && tid == 0) a.step[0] += 1;
+  if (steps) {
+    if (SERIAL) {
+      a.step[0] += 1;
+    } else {
+      asm volatile("" : "+v"(stepv));   // the increment stays here: formed at the load, it would wait for it at entry
+      a.step[0] = stepv + 1;
+    }
+  }
 }
 
 }  // namespace pc3d
 
 using namespace pc3d;
 
+static int cls_tail_launch(const char* who, bool serial, const float* c2, int B, int K2, const float* W3, const float* b3,
+                           int ncls, const int64_t* target, int kind, float kappa, float scale, float* logp, int64_t* pred,
+                           float* loss, float* g_c2, int32_t* step, void* stream) {
+  PC3D_REQUIRE(B >= 0 && K2 >= 4 && K2 <= CT_K && (K2 % 4) == 0 && ncls >= 2 && ncls <= CT_MAXCLS,
+               "%s: unsupported sizes B=%d K2=%d ncls=%d (K2 <= 256, K2 %% 4 == 0, ncls <= 64)", who, B, K2, ncls);
+  PC3D_REQUIRE(kind >= 0 && kind <= 2, "%s: kind=%d not in {0,1,2}", who, kind);
+  if (B == 0) return PC3D_OK;
+  PC3D_REQUIRE(c2 && W3 && b3 && target && pred && g_c2, "%s: null pointer", who);
+  ClsTailArgs a{c2, W3, b3, target, B, K2, ncls, kind, kappa, scale, logp, pred, loss, g_c2, step};
+  if (serial)
+    hipLaunchKernelGGL(cls_tail_kernel<true>, dim3(cdiv(B, CT_S)), dim3(CT_T), 0, as_stream(stream), a);
+  else
+    hipLaunchKernelGGL(cls_tail_kernel<false>, dim3(cdiv(B, CT_S)), dim3(CT_T), 0, as_stream(stream), a);
+  PC3D_LAUNCH_CHECK(who);
+  return PC3D_OK;
+}
+
 extern "C" int pc3d_cls_tail_f32(const float* c2, int B, int K2, const float* W3, const float* b3, int ncls,
                                  const int64_t* target, int kind, float kappa, float scale, float* logp,
                                  int64_t* pred, float* loss, float* g_c2, int32_t* step, void* stream) {
-  PC3D_REQUIRE(B >= 0 && K2 >= 4 && K2 <= CT_K && (K2 % 4) == 0 && ncls >= 2 && ncls <= CT_MAXCLS,
-               "pc3d_cls_tail_f32: unsupported sizes B=%d K2=%d ncls=%d (K2 <= 256, K2 %% 4 == 0, ncls <= 64)", B, K2, ncls);
-  PC3D_REQUIRE(kind >= 0 && kind <= 2, "pc3d_cls_tail_f32: kind=%d not in {0,1,2}", kind);
-  if (B == 0) return PC3D_OK;
-  PC3D_REQUIRE(c2 && W3 && b3 && target && pred && g_c2, "pc3d_cls_tail_f32: null pointer");
-  ClsTailArgs a{c2, W3, b3, target, B, K2, ncls, kind, kappa, scale, logp, pred, loss, g_c2, step};
-  hipLaunchKernelGGL(cls_tail_kernel, dim3(cdiv(B, CT_S)), dim3(CT_T), 0, as_stream(stream), a);
-  PC3D_LAUNCH_CHECK("pc3d_cls_tail_f32");
-  return PC3D_OK;
+  return cls_tail_launch("pc3d_cls_tail_f32", false, c2, B, K2, W3, b3, ncls, target, kind, kappa, scale, logp, pred, loss,
+                         g_c2, step, stream);
+}
+
+extern "C" int pc3d_cls_tail_serial_f32(const float* c2, int B, int K2, const float* W3, const float* b3, int ncls,
+                                        const int64_t* target, int kind, float kappa, float scale, float* logp,
+                                        int64_t* pred, float* loss, float* g_c2, int32_t* step, void* stream) {
+  return cls_tail_launch("pc3d_cls_tail_serial_f32", true, c2, B, K2, W3, b3, ncls, target, kind, kappa, scale, logp, pred,
+                         loss, g_c2, step, stream);
 }
 
 extern "C" int pc3d_linear_f32(const float* X, int ldx, int P, int B, int K, const float* W, const float* bias,

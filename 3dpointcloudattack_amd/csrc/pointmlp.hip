@@ -287,7 +287,13 @@ __global__ __launch_bounds__(PM_FT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
   }
 }
 
-// fold tiles: pooled[b,c] = max_t part[b,t,c] (first tile wins ties => lowest point index), optional ReLU
+// fold tiles: pooled[b,c] = max_t part[b,t,c] (first tile wins ties => lowest point index), optional ReLU.
+// The values AND the indices of PM_FOLD_U tiles are loaded together, unconditionally (tiles past ntiles are predicated
+// off), and the winner is selected in registers in ascending tile order with the same strict `>`: one load round trip
+// per PM_FOLD_U tiles, where loading a value, comparing and then fetching the winner's index is one (or two) per tile.
+// SERIAL keeps that earlier form (pc3d_pointmlp3_fold_f32 with serial = 1: parity test and tools/bench_small_launches.py).
+constexpr int PM_FOLD_U = 8;
+template <bool SERIAL>
 __global__ __launch_bounds__(256) void pointmlp3_fold_kernel(const float* part_val, const int32_t* part_idx,
                                                              int ntiles, int C3, int relu_last, float* pooled,
                                                              int32_t* argidx) {
@@ -295,13 +301,38 @@ __global__ __launch_bounds__(256) void pointmlp3_fold_kernel(const float* part_v
   const int b = blockIdx.y;
   if (c >= C3) return;
   const int64_t base = (int64_t)b * ntiles * C3 + c;
-  float best = part_val[base];
-  int bi = part_idx[base];
-  for (int t = 1; t < ntiles; ++t) {
-    const float v = part_val[base + (int64_t)t * C3];
-    if (v > best) {
-      best = v;
-      bi = part_idx[base + (int64_t)t * C3];
+  float best;
+  int bi;
+  if (SERIAL) {
+    best = part_val[base];
+    bi = part_idx[base];
+    for (int t = 1; t < ntiles; ++t) {
+      const float v = part_val[base + (int64_t)t * C3];
+      if (v > best) {
+        best = v;
+        bi = part_idx[base + (int64_t)t * C3];
+      }
+    }
+  } else {
+    best = 0.f, bi = 0;
+    for (int t0 = 0; t0 < ntiles; t0 += PM_FOLD_U) {
+      float v[PM_FOLD_U];
+      int ix[PM_FOLD_U];
+#pragma unroll
+      for (int u = 0; u < PM_FOLD_U; ++u) {
+        if (t0 + u < ntiles) {
+          v[u] = part_val[base + (int64_t)(t0 + u) * C3];
+          ix[u] = part_idx[base + (int64_t)(t0 + u) * C3];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < PM_FOLD_U; ++u) {
+        if (t0 + u < ntiles) {
+          const bool take = (t0 + u == 0) || (v[u] > best);   // tile 0 starts the running best, whatever it holds
+          best = take ? v[u] : best;
+          bi = take ? ix[u] : bi;
+        }
+      }
     }
   }
   if (relu_last) best = fmaxf(best, 0.f);
@@ -1043,10 +1074,27 @@ static int pm_fwd_launch(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_c
   hipLaunchKernelGGL(pointmlp3_max_fwd_kernel, dim3(ntiles, B), dim3(PM_FT), 0, st, a);
   PC3D_LAUNCH_CHECK("pc3d_pointmlp3_max_fwd_f32");
   if (pooled) {  // NULL: leave the per-tile partials unfolded (a fused consumer, or kernel-only timing)
-    hipLaunchKernelGGL(pointmlp3_fold_kernel, dim3(cdiv(C3, 256), B), dim3(256), 0, st, part_val, part_idx, ntiles,
+    hipLaunchKernelGGL(pointmlp3_fold_kernel<false>, dim3(cdiv(C3, 256), B), dim3(256), 0, st, part_val, part_idx, ntiles,
                        C3, relu_last, pooled, argidx);
     PC3D_LAUNCH_CHECK("pc3d_pointmlp3_max_fwd_f32/fold");
   }
+  return PC3D_OK;
+}
+
+extern "C" int pc3d_pointmlp3_fold_f32(const float* part_val, const int32_t* part_idx, int B, int ntiles, int C3,
+                                       int relu_last, float* pooled, int32_t* argidx, int serial, void* stream) {
+  PC3D_REQUIRE(B >= 0 && B <= 65535 && ntiles >= 1 && C3 >= 1, "pc3d_pointmlp3_fold_f32: bad sizes B=%d ntiles=%d C3=%d", B,
+               ntiles, C3);
+  if (B == 0) return PC3D_OK;
+  PC3D_REQUIRE(part_val && part_idx && pooled && argidx, "pc3d_pointmlp3_fold_f32: null pointer");
+  const dim3 grid(cdiv(C3, 256), B);
+  if (serial)
+    hipLaunchKernelGGL(pointmlp3_fold_kernel<true>, grid, dim3(256), 0, as_stream(stream), part_val, part_idx, ntiles, C3,
+                       relu_last, pooled, argidx);
+  else
+    hipLaunchKernelGGL(pointmlp3_fold_kernel<false>, grid, dim3(256), 0, as_stream(stream), part_val, part_idx, ntiles, C3,
+                       relu_last, pooled, argidx);
+  PC3D_LAUNCH_CHECK("pc3d_pointmlp3_fold_f32");
   return PC3D_OK;
 }
 

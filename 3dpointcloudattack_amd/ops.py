@@ -373,12 +373,28 @@ def _pm_tile():
     return _PM_TILE
 
 
-def pointmlp3_max_fwd_raw(x, weights, relu_last, T=None, x_cf=True, fold=True, want_masks=False, T_head=None):
+def pointmlp3_fold_raw(part_val, part_idx, relu_last, serial=False):
+    """The tower's fold launch on its own: (pooled [B,C3], argidx [B,C3]) of the per-tile partials [B,ntiles,C3] (f32 /
+    i32, contiguous). serial: the earlier kernel (same bits; parity tests and tools/bench_small_launches.py only)."""
+    _check(part_val, "part_val")
+    B, ntiles, C3 = part_val.shape
+    if part_idx.shape != part_val.shape or part_idx.dtype != torch.int32 or not (part_val.is_contiguous() and part_idx.is_contiguous()):
+        raise ValueError("pointmlp3_fold_raw: part_val f32 / part_idx i32, both contiguous [B,ntiles,C3], expected")
+    pooled = torch.empty((B, C3), dtype=torch.float32, device=part_val.device)
+    argidx = torch.empty((B, C3), dtype=torch.int32, device=part_val.device)
+    with torch.cuda.device(part_val.device):
+        _lib.call("pc3d_pointmlp3_fold_f32", part_val.data_ptr(), part_idx.data_ptr(), B, ntiles, C3, 1 if relu_last else 0,
+                  pooled.data_ptr(), argidx.data_ptr(), 1 if serial else 0, _stream())
+    return pooled, argidx
+
+
+def pointmlp3_max_fwd_raw(x, weights, relu_last, T=None, x_cf=True, fold=True, want_masks=False, T_head=None, serial=False):
     """x [B,3,N] (x_cf) or [B,N,3]; weights = (W1[64,3], b1, W2[128,64], b2, W3[C3,128], b3) with eval-BN folded.
     Returns (pooled [B,C3] f32, argidx [B,C3] i32) and, with want_masks, a third item (mask1 [B,N] i64, mask2 [B,N,4]
     i32): the per-point ReLU decisions of layers 1 and 2 as bit masks, which pointmlp3_max_bwd_raw consumes.
     T_head = (h [B,K], W [9,K], b [9]): the input transform T = h @ W.T + b is computed in the launch's prologue
-    (no launch of its own) and returned as a last extra item [B,9]."""
+    (no launch of its own) and returned as a last extra item [B,9].
+    serial: fold with the earlier fold kernel (same bits; parity tests and tools/bench_small_launches.py only)."""
     xp, xbs, xps, xcs, B, N = _pts(x, x_cf, "x")
     W1, b1, W2, b2, W3, b3 = weights[:6]
     for w in weights:
@@ -400,7 +416,7 @@ def pointmlp3_max_fwd_raw(x, weights, relu_last, T=None, x_cf=True, fold=True, w
         masks = (torch.empty((B, N), dtype=torch.int64, device=dev), torch.empty((B, N, 4), dtype=torch.int32, device=dev))
     tail = (W1.data_ptr(), b1.data_ptr(), W2.data_ptr(), b2.data_ptr(), W3.data_ptr(), b3.data_ptr(),
             C1, C2, C3, 1 if relu_last else 0, part_val.data_ptr(), part_idx.data_ptr(),
-            pooled.data_ptr() if fold else 0, argidx.data_ptr() if fold else 0,
+            pooled.data_ptr() if fold and not serial else 0, argidx.data_ptr() if fold and not serial else 0,
             masks[0].data_ptr() if masks else 0, masks[1].data_ptr() if masks else 0, _stream())
     T_out = None
     with torch.cuda.device(dev):
@@ -415,6 +431,9 @@ def pointmlp3_max_fwd_raw(x, weights, relu_last, T=None, x_cf=True, fold=True, w
                       h.shape[1], T_out.data_ptr(), *tail)
         else:
             _lib.call("pc3d_pointmlp3_max_fwd_f32", xp, xbs, xps, xcs, B, N, _ptr(T), *tail)
+        if fold and serial:
+            _lib.call("pc3d_pointmlp3_fold_f32", part_val.data_ptr(), part_idx.data_ptr(), B, ntiles, C3,
+                      1 if relu_last else 0, pooled.data_ptr(), argidx.data_ptr(), 1, _stream())
     if not fold:
         return (part_val, part_idx) if T_out is None else (part_val, part_idx, T_out)
     res = (pooled, argidx, masks) if want_masks else (pooled, argidx)
@@ -755,9 +774,10 @@ def cls_loss(logits, target, kind, kappa=0.0, scale=1.0, want_grad=True, pred_ou
     return logp, pred, loss, g
 
 
-def cls_tail(c2, w3, b3, target, kind, kappa=0.0, scale=1.0, pred_out=None, step=None, want_logp=True):
+def cls_tail(c2, w3, b3, target, kind, kappa=0.0, scale=1.0, pred_out=None, step=None, want_logp=True, serial=False):
     """fc3 + cls_loss + fc3-backward in one launch (see pc3d_cls_tail_f32): (logp or None, pred, loss, g_c2).
-    pred_out: persistent int64 [B] to write the prediction into; step: int32 [1] device word to advance."""
+    pred_out: persistent int64 [B] to write the prediction into; step: int32 [1] device word to advance.
+    serial: the earlier kernel (same bits; parity tests and tools/bench_small_launches.py only)."""
     _check(c2, "c2"), _check(w3, "w3"), _check(b3, "b3")
     B, K2 = c2.shape
     ncls = w3.shape[0]
@@ -769,7 +789,7 @@ def cls_tail(c2, w3, b3, target, kind, kappa=0.0, scale=1.0, pred_out=None, step
     loss = torch.empty((B,), dtype=torch.float32, device=dev)
     g_c2 = torch.empty((B, K2), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        _lib.call("pc3d_cls_tail_f32", c2.data_ptr(), B, K2, w3.data_ptr(), b3.data_ptr(), ncls, target.data_ptr(),
+        _lib.call("pc3d_cls_tail_serial_f32" if serial else "pc3d_cls_tail_f32", c2.data_ptr(), B, K2, w3.data_ptr(), b3.data_ptr(), ncls, target.data_ptr(),
                   LOSS_KINDS[kind] if isinstance(kind, str) else int(kind), float(kappa), float(scale), _ptr(logp),
                   pred.data_ptr(), loss.data_ptr(), g_c2.data_ptr(), _ptr(step), _stream())
     return logp, pred, loss, g_c2

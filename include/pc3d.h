@@ -367,6 +367,12 @@ int pc3d_pointmlp3_max_fwd_f32(const float* x, int64_t x_bs, int64_t x_ps, int64
                                const float* b2, const float* W3, const float* b3, int C1, int C2, int C3,
                                int relu_last, float* part_val, int32_t* part_idx,
                                float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2, void* stream);
+/* The fold launch of the entry above on its own: pooled[b,c] = max_t part_val[b,t,c] (the first tile wins ties),
+ * argidx the winner's part_idx, optional ReLU; part_* are [B,ntiles,C3]. serial = 1 runs the earlier kernel, which
+ * loads one tile's value, compares, and then fetches the winner's index: the same bits. Parity tests and
+ * tools/bench_small_launches.py only; nothing on a hot path calls it. */
+int pc3d_pointmlp3_fold_f32(const float* part_val, const int32_t* part_idx, int B, int ntiles, int C3, int relu_last,
+                            float* pooled, int32_t* argidx, int serial, void* stream);
 /* The same launch with the input transform computed in its prologue: T[b] = th_W [9,th_K] . th_in[b] + th_b — the
  * last layer of STN3d (model/pointnet.py:45-47: fc3, with the flattened identity added into th_b) — instead of a
  * launch of its own between the two towers; T_out [B,9] receives it (the backward launch reads it as its T). */
@@ -829,6 +835,11 @@ int pc3d_rowdot3_f32(const float* mat, const float* vec, int B, int R, int K, in
 int pc3d_cls_tail_f32(const float* c2, int B, int K2, const float* W3, const float* b3, int ncls,
                       const int64_t* target, int kind, float kappa, float scale, float* logp,
                       int64_t* pred, float* loss, float* g_c2, int32_t* step, void* stream);
+/* The same by the earlier kernel, which stages W3 and c2 one load -> wait -> LDS write at a time: the same bits. Parity
+ * tests and tools/bench_small_launches.py only. */
+int pc3d_cls_tail_serial_f32(const float* c2, int B, int K2, const float* W3, const float* b3, int ncls,
+                             const int64_t* target, int kind, float kappa, float scale, float* logp,
+                             int64_t* pred, float* loss, float* g_c2, int32_t* step, void* stream);
 
 /* pc3d_cw_bookkeep_f32 + pc3d_cw_step_f32 as ONE launch (one workgroup per sample): bookkeeping on the current
  * iterate, then total gradient + Adam + clip on that sample's points. o_bestattack / input_val / m / v share adv's
