@@ -163,6 +163,9 @@ SIGNATURES = {
     "pc3d_iso_wgrad_f32": _PTS + _PTS + [_I, _I, _I, _P, _P],
     "pc3d_iso_update_f32": _PTS + _PTS + [_P, _I, _I, _P, _P, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _D, _D, _D, _D]
     + _PTS + [_P],
+    "pc3d_pca_normal_f32": _PTS + [_P, _I, _I, _I] + _PTS + [_P],
+    "pc3d_si_frame_f32": _PTS + _PTS + [_P, _I, _I, _I] + _PTS + _PTS + [_P],
+    "pc3d_si_step_f32": _PTS + _PTS + _PTS + _PTS + [_P, _I, _I, _I] + _PTS + [_D, _D, _P],
 }
 
 # entry points that do not return a status code

@@ -1,0 +1,294 @@
+"""The shape-invariant white-box attack (SI-Adv, I-FGM) — MI355X mirror of the reference's ``attack/SIadv/SIadv_attack.py``.
+
+Every point moves only inside its tangent plane: with the normal n the point is taken to the frame P' = U (P + (P.n) n),
+the surrogate's gradient is taken there, its component along the normal is dropped, P' makes an L2-normalised step and
+goes back, P = U^T P' - (P.n) n, followed by the clamp to the eps box; then the normals are estimated again.
+
+The reference runs one cloud at a time and re-estimates the normals with open3d on the host in every step.
+``PointCloudAttack`` runs a batch and stays on the device: per step one self-kNN search (K = 20, hinted by the previous
+step's lists), ``pc3d_si_frame_f32`` (the PCA normals from the lists and the cloud U^T (U (P + t)) - t the reference
+shows the victim), the surrogate's passes, and ``pc3d_si_step_f32`` (the step). The loop has no data-dependent exit,
+so with a PointNet surrogate (fused passes, no autograd) the step is captured into a hipGraph and replayed. Any other
+surrogate, a defence head or the top-5 loss take autograd for the gradient and the same two kernels.
+
+Kept on purpose: the spin-axis matrix as written, including its rows for |n_z^2 - 1| < 1e-4, which are
+not the frame of n — so the victim sees those points displaced by up to 1e-4, which a PointNet's max-pool can amplify;
+sqrt(3 * 1024) in the step whatever N is; the loss summed over the batch. Not kept: the checkpoint loading of
+``build_models`` (the models are handed in), ``assert abs(normal_vec).max() <= 1`` (a host round trip), the normal
+estimation after the last step (never used), and the three query attacks (``simba``, ``simbapp``, ``ours``), which
+``run`` refuses by name.
+"""
+import numpy as np
+import torch
+
+from ... import graphed as _graphed
+from ... import ops
+from ... import streams as _streams
+from .baselines import ClipPointsLinf, DUPNet, SORDefense, SRSDefense
+
+KNN = 20                                  # open3d.geometry.KDTreeSearchParamKNN(knn=20), SIadv_attack.py:212
+QUERY_METHODS = ("simba", "simbapp", "ours")
+_MAX_LOOPS = 4
+
+
+def _first(out):
+    return out[0] if isinstance(out, (tuple, list)) else out
+
+
+class _Loop:
+    """The fast path's state for one batch shape: static buffers, one step as a function, and its hipGraph."""
+
+    def __init__(self, victim, B, N, dev, step_size, eps):
+        self.victim, self.step_size, self.eps = victim, float(step_size), float(eps)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.x, self.ori, self.xe, self.nrm = (torch.zeros((B, 3, N), **f32) for _ in range(4))
+        self.label = torch.zeros((B,), dtype=torch.int64, device=dev)
+        self.graph, self.keep = None, None
+
+    def load(self, x, ori, label):
+        self.x.copy_(x), self.ori.copy_(ori), self.label.copy_(label)
+
+    def _move(self, nrm):
+        # the victim is shown xe (si_frame), as in the reference; its loss is summed over the batch, not averaged: scale 1
+        g = self.victim.fused_attack_grad(self.xe, self.label, "untargeted_logits", 0.0, scale=1.0)[2]
+        ops.si_step(self.x, self.ori, g, self.step_size, self.eps, nrm=nrm)
+
+    def first(self, nrm):
+        """Step 0: the normals that came with the cloud."""
+        ops.si_frame(self.x, nrm=nrm, out=self.xe)
+        self._move(nrm)
+
+    def step(self):
+        _, idx = ops.knn_raw(self.x, self.x, KNN, q_cf=True, r_cf=True)
+        ops.si_frame(self.x, idx=idx, out=self.xe, nrm_out=self.nrm)
+        self._move(self.nrm)
+
+    def capture(self, warmup=2):
+        """Capture one step (after `warmup` eager ones on the side stream; they advance the state: load() again)."""
+        dev = self.x.device
+        side = _streams.side_stream(dev, _streams.TERMS)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                self.step()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        with _graphed.capture_guard() as keep:
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self.step()
+        # the graph bakes in the addresses of the folded weights: hold what it points at
+        self.graph, self.keep = g, keep + _graphed._cached_tensors(self.victim)
+
+    def run(self, steps):
+        for _ in range(steps):
+            if self.graph is not None:
+                self.graph.replay()
+            else:
+                self.step()
+
+
+class PointCloudAttack(object):
+    """``PointCloudAttack(args, wb_classifier=None, classifier=None)``: the surrogate and the target are handed in (or
+    taken from ``args.wb_classifier`` / ``args.classifier``); args carries eps, step_size, max_steps, num_class,
+    top5_attack, defense_method and the attack method (``transfer_attack_method`` or ``query_attack_method``).
+    ``run(points [B,N,6], target [B])`` returns (adv_points [B,N,3], adv_target [B], number of misclassified clouds).
+    fused / graph: use the surrogate's fused passes when it has them, and replay the step from a hipGraph."""
+
+    def __init__(self, args, wb_classifier=None, classifier=None, fused=True, graph=True):
+        self.args = args
+        self.device = getattr(args, "device", None)
+        self.eps = args.eps
+        self.normal = getattr(args, "normal", False)
+        self.step_size = args.step_size
+        self.num_class = args.num_class
+        self.max_steps = args.max_steps
+        self.top5_attack = args.top5_attack
+        query = getattr(args, "query_attack_method", None)
+        self.attack_method = getattr(args, "transfer_attack_method", None) if query is None else query
+        wb_classifier = wb_classifier if wb_classifier is not None else getattr(args, "wb_classifier", None)
+        classifier = classifier if classifier is not None else getattr(args, "classifier", None)
+        if wb_classifier is None or classifier is None:
+            raise ValueError("PointCloudAttack: pass the surrogate (wb_classifier) and the target (classifier) models")
+        self.wb_classifier = wb_classifier.eval()
+        self.classifier = classifier.eval()
+        self.defense_method = args.defense_method
+        self.pre_head = None
+        if self.defense_method is not None:
+            self.pre_head = self.get_defense_head(self.defense_method)
+        self.fused, self.graph = fused, graph
+        self._loops = {}
+
+    def CWLoss(self, logits, target, kappa=0, tar=False, num_classes=40):
+        """Carlini & Wagner loss, summed over the batch (SIadv_attack.py:142-164). logits [B,num_classes], target [B]."""
+        target = torch.ones(logits.size(0), dtype=logits.dtype, device=logits.device).mul(target.to(logits.dtype))
+        target_one_hot = torch.eye(num_classes, dtype=logits.dtype, device=logits.device)[target.long()]
+        real = torch.sum(target_one_hot * logits, 1)
+        if not self.top5_attack:
+            other = torch.max((1 - target_one_hot) * logits - (target_one_hot * 10000), 1)[0]
+        else:
+            other = torch.topk((1 - target_one_hot) * logits - (target_one_hot * 10000), 5)[0][:, 4]
+        kappa = torch.zeros_like(other).fill_(kappa)
+        if tar:
+            return torch.sum(torch.max(other - real, kappa))
+        return torch.sum(torch.max(real - other, kappa))
+
+    def run(self, points, target):
+        """points [B,N,6] (coordinates and normals), target [B]."""
+        if self.attack_method == 'ifgm_ours':
+            return self.shape_invariant_ifgm(points, target)
+        if self.attack_method in QUERY_METHODS:
+            raise NotImplementedError(f"PointCloudAttack: the query attack '{self.attack_method}' is not mirrored "
+                                      "(only the transfer attack 'ifgm_ours' is)")
+        raise NotImplementedError(f"PointCloudAttack: unknown attack method {self.attack_method!r}")
+
+    def get_defense_head(self, method):
+        """The pre-processing defence in front of both models (SIadv_attack.py:189-202)."""
+        if method == 'sor':
+            pre_head = SORDefense(k=2, alpha=1.1)
+        elif method == 'srs':
+            pre_head = SRSDefense(drop_num=500)
+        elif method == 'dupnet':
+            pre_head = DUPNet(sor_k=2, sor_alpha=1.1, npoint=1024, up_ratio=4)
+        else:
+            raise NotImplementedError
+        return pre_head
+
+    def get_normal_vector(self, points):
+        """Normals [B,N,3] of points [B,N,3] on the GPU: the self-kNN search (K = 20, the point included) and the PCA
+        normal of every list (pc3d_pca_normal_f32) — the definition open3d documents for
+        estimate_normals(KDTreeSearchParamKNN(knn=20)); the sign is this library's."""
+        if points.shape[1] < KNN:
+            raise ValueError(f"get_normal_vector: N = {points.shape[1]} points, the {KNN}-neighbour normals need N >= {KNN}")
+        points = points.detach().float()
+        _, idx = ops.knn_raw(points, points, KNN)
+        return ops.pca_normal(points, idx)
+
+    def get_spin_axis_matrix(self, normal_vec):
+        """U [B,N,3,3] of normals [B,N,3] (SIadv_attack.py:217-247), the rows for |z^2 - 1| < 1e-4 included."""
+        x, y, z = normal_vec[:, :, 0], normal_vec[:, :, 1], normal_vec[:, :, 2]
+        u = torch.zeros(normal_vec.shape[:2] + (3, 3), dtype=normal_vec.dtype, device=normal_vec.device)
+        denominator = torch.sqrt(1 - z ** 2)
+        u[:, :, 0, 0] = y / denominator
+        u[:, :, 0, 1] = - x / denominator
+        u[:, :, 0, 2] = 0.
+        u[:, :, 1, 0] = x * z / denominator
+        u[:, :, 1, 1] = y * z / denominator
+        u[:, :, 1, 2] = - denominator
+        u[:, :, 2] = normal_vec
+        # revision for |z| = 1, boundary case
+        pos = abs(z ** 2 - 1) < 1e-4
+        r = 1 / np.sqrt(2)
+        zero = torch.zeros_like(z)
+        bound = torch.stack([torch.stack([zero + r, zero - r, zero], -1),
+                             torch.stack([z / np.sqrt(2), z / np.sqrt(2), zero], -1),
+                             torch.stack([zero, zero, z], -1)], -2)
+        return torch.where(pos[:, :, None, None], bound, u).data
+
+    def get_transformed_point_cloud(self, points, normal_vec):
+        """(P' = U (P + (P.N) N), U, (P.N) N) for points, normals [B,N,3] (SIadv_attack.py:250-263)."""
+        intercept = torch.mul(points, normal_vec).sum(-1, keepdim=True)
+        spin_axis_matrix = self.get_spin_axis_matrix(normal_vec)
+        translation_matrix = torch.mul(intercept, normal_vec).data
+        new_points = (points + translation_matrix).unsqueeze(-1)
+        new_points = torch.matmul(spin_axis_matrix, new_points).squeeze(-1).data
+        return new_points, spin_axis_matrix, translation_matrix
+
+    def get_original_point_cloud(self, new_points, spin_axis_matrix, translation_matrix):
+        """P = U^T P' - (P.N) N (SIadv_attack.py:266-276)."""
+        inputs = torch.matmul(spin_axis_matrix.transpose(-1, -2), new_points.unsqueeze(-1))
+        inputs = inputs - translation_matrix.unsqueeze(-1)
+        return inputs.squeeze(-1)
+
+    # ------------------------------------------------------------------------------------------------------
+    def _fast(self):
+        return bool(self.fused and self.pre_head is None and not self.top5_attack
+                    and hasattr(self.wb_classifier, "fused_attack_grad"))
+
+    def _loop(self, x, ori, target):
+        """A loaded _Loop for x [B,3,N]; with graph=True captured once per (shape, settings, weights)."""
+        B, _, N = x.shape
+        v = self.wb_classifier
+        if not self.graph:
+            c = _Loop(v, B, N, x.device, self.step_size, self.eps)
+        else:
+            wkey = tuple((t.data_ptr(), t._version) for t in list(v.parameters()) + list(v.buffers()))
+            key = (B, N, x.device, float(self.step_size), float(self.eps), wkey)
+            c = self._loops.get(key)
+            if c is None:
+                while len(self._loops) >= _MAX_LOOPS:
+                    self._loops.pop(next(iter(self._loops)))
+                c = _Loop(v, B, N, x.device, self.step_size, self.eps)
+                c.load(x, ori, target)
+                c.capture()
+                self._loops[key] = c
+        c.load(x, ori, target)
+        return c
+
+    def _generic_grad(self, xe, target):
+        """dL/dxe [B,3,N] by autograd through the defence head and the surrogate, at the cloud xe = U^T P' - t that
+        si_frame hands over. The reference takes the gradient at P'; the chain rule gives dL/dP' = U dL/dxe, which the
+        step kernel forms."""
+        P = xe.detach().clone().requires_grad_()
+        with torch.enable_grad():
+            inp = self.pre_head(P) if self.pre_head is not None else P
+            logits = _first(self.wb_classifier(inp))
+            loss = self.CWLoss(logits, target, kappa=0., tar=False, num_classes=self.num_class)
+            if not loss.requires_grad:           # nothing of the loss depends on the points
+                return torch.zeros_like(xe), loss.detach()
+            (g,) = torch.autograd.grad(loss, P)
+        return g.contiguous(), loss.detach()
+
+    def iterate(self, points, target, steps=None, ori=None):
+        """The loop alone: the coordinates [B,3,N] after `steps` (default max_steps) steps from points [B,N,6]. With
+        points [B,N,3] (no normals) the first step estimates them like the later ones do. ori [B,N,3]: the clean cloud the
+        clamp refers to when the run continues from an iterate (default: the coordinates given)."""
+        steps = self.max_steps if steps is None else steps
+        points = points.detach().float()
+        B, N, C = points.shape
+        if C not in (3, 6):
+            raise ValueError(f"shape_invariant_ifgm: points must be [B,N,6] (or [B,N,3]), got {tuple(points.shape)}")
+        if N < KNN and (steps > 1 or C == 3):
+            raise ValueError(f"shape_invariant_ifgm: N = {N} points, the {KNN}-neighbour normals need N >= {KNN}")
+        target = target.detach().reshape(-1).long().to(points.device)
+        nrm = None
+        if C == 6:
+            normal_vec = points[:, :, -3:]
+            normal_vec = normal_vec / torch.sqrt(torch.sum(normal_vec ** 2, dim=-1, keepdim=True))
+            nrm = normal_vec.transpose(1, 2).contiguous()
+        x = points[:, :, :3].transpose(1, 2).contiguous()
+        ori = x.clone() if ori is None else ori.detach().float().transpose(1, 2).contiguous()
+        if steps < 1:
+            return x
+        with torch.cuda.device(x.device), torch.no_grad():
+            if self._fast():
+                c = self._loop(x, ori, target)
+                if nrm is not None:
+                    c.first(nrm)
+                c.run(steps - (nrm is not None))
+                return c.x.clone()
+            xe = torch.empty_like(x)
+            for i in range(steps):
+                if i > 0 or nrm is None:
+                    _, idx = ops.knn_raw(x, x, KNN, q_cf=True, r_cf=True)
+                    nrm = torch.empty_like(x)
+                    ops.si_frame(x, idx=idx, out=xe, nrm_out=nrm)
+                else:
+                    ops.si_frame(x, nrm=nrm, out=xe)
+                g, _ = self._generic_grad(xe, target)
+                ops.si_step(x, ori, g, self.step_size, self.eps, nrm=nrm)
+        return x
+
+    def shape_invariant_ifgm(self, points, target):
+        """White-box I-FGM on shape-invariant sensitivity maps, transferred to the target model.
+        points [B,N,6], target [B] -> (adv_points [B,N,3], adv_target [B], number of clouds the target misclassifies)."""
+        x = self.iterate(points, target)
+        target = target.detach().reshape(-1).long().to(x.device)
+        with torch.no_grad():
+            inp = self.pre_head(x) if self.pre_head is not None else x
+            adv_logits = _first(self.classifier(inp))
+            pred = adv_logits.max(1)[1]
+            adv_target = pred
+            if self.top5_attack:
+                in_top5 = (adv_logits.topk(5)[1] == target[:, None]).any(1)
+                adv_target = torch.where(in_top5, target, torch.full_like(target, -1))
+        return x.transpose(1, 2).contiguous(), adv_target, (pred != target).sum().item()

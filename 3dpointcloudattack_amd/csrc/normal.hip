@@ -7,7 +7,7 @@
 // symmetric 3 x 3 problem has a closed form: eigenvalues from the trigonometric solution of the characteristic cubic,
 // the eigenvector as the largest cross product of two rows of (A - lambda I). One thread per point, arithmetic in
 // double (the covariance of 3 neighbours has rank 2: lambda_min / lambda_max ~ 1e-7 in fp32), microseconds per call.
-#include "pc3d_common.h"
+#include "eig3_body.h"
 
 namespace pc3d {
 
@@ -43,35 +43,9 @@ __global__ __launch_bounds__(256) void estimate_normal_kernel(NormalArgs a) {
   }
   const double f = 1.0 / (double)(k > 1 ? k - 1 : 1);
   c00 *= f, c01 *= f, c02 *= f, c11 *= f, c12 *= f, c22 *= f;
-  // smallest eigenvalue (Smith 1961)
-  const double q = (c00 + c11 + c22) / 3.0;
-  const double p1 = c01 * c01 + c02 * c02 + c12 * c12;
-  const double d0 = c00 - q, d1 = c11 - q, d2 = c22 - q;
-  const double p2 = d0 * d0 + d1 * d1 + d2 * d2 + 2.0 * p1;
-  double nx = 0.0, ny = 0.0, nz = 1.0;
-  if (p2 > 0.0) {
-    const double p = sqrt(p2 / 6.0), ip = 1.0 / p;
-    const double b00 = d0 * ip, b11 = d1 * ip, b22 = d2 * ip, b01 = c01 * ip, b02 = c02 * ip, b12 = c12 * ip;
-    double r = 0.5 * (b00 * (b11 * b22 - b12 * b12) - b01 * (b01 * b22 - b12 * b02) + b02 * (b01 * b12 - b11 * b02));
-    r = r < -1.0 ? -1.0 : (r > 1.0 ? 1.0 : r);
-    const double phi = acos(r) / 3.0;
-    const double lmin = q + 2.0 * p * cos(phi + 2.0943951023931953);   // + 2 pi / 3
-    // eigenvector: the largest cross product of two rows of A - lmin I
-    const double r0x = c00 - lmin, r0y = c01, r0z = c02;
-    const double r1x = c01, r1y = c11 - lmin, r1z = c12;
-    const double r2x = c02, r2y = c12, r2z = c22 - lmin;
-    const double ax = r0y * r1z - r0z * r1y, ay = r0z * r1x - r0x * r1z, az = r0x * r1y - r0y * r1x;
-    const double bx = r0y * r2z - r0z * r2y, by = r0z * r2x - r0x * r2z, bz = r0x * r2y - r0y * r2x;
-    const double cx = r1y * r2z - r1z * r2y, cy = r1z * r2x - r1x * r2z, cz = r1x * r2y - r1y * r2x;
-    const double na = ax * ax + ay * ay + az * az, nbn = bx * bx + by * by + bz * bz, nc = cx * cx + cy * cy + cz * cz;
-    double vx = ax, vy = ay, vz = az, nn = na;
-    if (nbn > nn) vx = bx, vy = by, vz = bz, nn = nbn;
-    if (nc > nn) vx = cx, vy = cy, vz = cz, nn = nc;
-    if (nn > 0.0) {
-      const double inv = 1.0 / sqrt(nn);
-      nx = vx * inv, ny = vy * inv, nz = vz * inv;
-    }
-  }
+  // smallest eigenvalue's eigenvector, closed form (eig3_body.h)
+  double nx, ny, nz;
+  eig3_smallest_vec(c00, c01, c02, c11, c12, c22, nx, ny, nz);
   // sign = -sign(<n, sum of the centred neighbours>) (sign(0) = 0, as torch.sign)
   const double dotp = nx * (double)sx + ny * (double)sy + nz * (double)sz;
   const double sg = dotp > 0.0 ? -1.0 : (dotp < 0.0 ? 1.0 : 0.0);

@@ -3072,3 +3072,74 @@ class IsoTransform(torch.autograd.Function):
             if R > 1:
                 gx = gx.view(x.shape[0], R, 3, -1).sum(1)
         return gx, gW
+
+
+
+# ------------------------------------------------------------------------------------------------------
+# The shape-invariant attack (attack/SIadv): PCA normals and the I-FGM step in the tangent frame (csrc/siadv.hip)
+# ------------------------------------------------------------------------------------------------------
+def _knn_lists(idx, B, N, who):
+    if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int32 or not idx.is_cuda or not idx.is_contiguous() \
+            or idx.dim() != 3 or tuple(idx.shape[:2]) != (B, N) or idx.shape[2] < 1:
+        raise ValueError(f"{who}: idx must be a contiguous int32 [B,N,K] GPU tensor")
+    return idx.shape[2]
+
+
+def pca_normal(pts, idx, cf=False):
+    """Normals of pts [B,N,3] ([B,3,N] with cf), in pts' layout, from neighbour lists idx [B,N,K] int32 that include
+    the point itself: the smallest eigenvector of the covariance of the K listed points about their mean (see
+    pc3d_pca_normal_f32: sign rule, (0,0,1) for degenerate lists, NaN for an index outside [0,N))."""
+    p, bs, ps, cs, B, N = _pts(pts, cf, "pts")
+    K = _knn_lists(idx, B, N, "pca_normal")
+    out = torch.empty((B, 3, N) if cf else (B, N, 3), dtype=torch.float32, device=pts.device)
+    with torch.cuda.device(pts.device):
+        _lib.call("pc3d_pca_normal_f32", p, bs, ps, cs, idx.data_ptr(), B, N, K, *_pts(out, cf, "out")[:4], _stream())
+    return out
+
+
+def si_frame(x, nrm=None, idx=None, nrm_out=None, cf=True, out=None):
+    """The cloud the shape-invariant attack shows its victim: U^T (U (x + t)) - t per point (pc3d_si_frame_f32), a new
+    tensor (or `out`) in x's layout [B,3,N] ([B,N,3] with cf=False). Exactly one of nrm (normals) and idx (int32 [B,N,K]
+    neighbour lists, self included) is given; nrm_out receives the normals used."""
+    xp, xbs, xps, xcs, B, N = _pts(x, cf, "x")
+    if (nrm is None) == (idx is None):
+        raise ValueError("si_frame: give exactly one of nrm (normals) and idx (neighbour lists)")
+    if out is None:
+        out = torch.empty(tuple(x.shape), dtype=torch.float32, device=x.device)
+    views = []
+    for t, nm in ((nrm, "nrm"), (out, "out"), (nrm_out, "nrm_out")):
+        if t is None:
+            views.append((0, 0, 0, 0))
+            continue
+        v = _pts(t, cf, nm)
+        if v[4:] != (B, N):
+            raise ValueError(f"si_frame: {nm} {tuple(t.shape)} must have x's shape {tuple(x.shape)}")
+        views.append(v[:4])
+    K = _knn_lists(idx, B, N, "si_frame") if idx is not None else 0
+    with torch.cuda.device(x.device):
+        _lib.call("pc3d_si_frame_f32", xp, xbs, xps, xcs, *views[0], _ptr(idx), K, B, N, *views[1], *views[2], _stream())
+    return out
+
+
+def si_step(x, ori, g, step_size, eps, nrm=None, idx=None, nrm_out=None, cf=True):
+    """One shape-invariant I-FGM step, IN PLACE on x [B,3,N] ([B,N,3] with cf=False; ori, g, nrm, nrm_out share the
+    layout), one launch (see pc3d_si_step_f32). g = the victim's gradient at si_frame(x). Exactly one of nrm (the normals) and idx (int32 [B,N,K]
+    neighbour lists, self included: the normals are computed as pca_normal does) is given; nrm_out receives the
+    normals used. Returns x."""
+    xp, xbs, xps, xcs, B, N = _pts(x, cf, "x")
+    if (nrm is None) == (idx is None):
+        raise ValueError("si_step: give exactly one of nrm (normals) and idx (neighbour lists)")
+    views = []
+    for t, nm in ((ori, "ori"), (g, "g"), (nrm, "nrm"), (nrm_out, "nrm_out")):
+        if t is None:
+            views.append((0, 0, 0, 0))
+            continue
+        v = _pts(t, cf, nm)
+        if v[4:] != (B, N):
+            raise ValueError(f"si_step: {nm} {tuple(t.shape)} must have x's shape {tuple(x.shape)}")
+        views.append(v[:4])
+    K = _knn_lists(idx, B, N, "si_step") if idx is not None else 0
+    with torch.cuda.device(x.device):
+        _lib.call("pc3d_si_step_f32", xp, xbs, xps, xcs, *views[0], *views[1], *views[2], _ptr(idx), K, B, N, *views[3],
+                  float(step_size), float(eps), _stream())
+    return x

@@ -1009,6 +1009,50 @@ int pc3d_iso_update_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs
                         float* W, float* m, float* v, double lr, double beta1, double beta2, double eps,
                         float* xo, int64_t xo_bs, int64_t xo_ps, int64_t xo_cs, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * The shape-invariant white-box attack (attack/SIadv/SIadv_attack.py, shape_invariant_ifgm): I-FGM in every point's
+ * tangent frame, with the normals re-estimated on the device every step (csrc/siadv.hip).
+ * ------------------------------------------------------------------------------------------------------- */
+/* out[b, i] = the unit eigenvector of the smallest eigenvalue of the covariance of the K points idx[b, i, :] of cloud b
+ * about their own mean (the point itself is among them: idx comes from a self-kNN search, self first). This is what
+ * the reference asks of open3d's estimate_normals(KDTreeSearchParamKNN(knn=K)). Mean, covariance and the closed-form
+ * 3 x 3 solve (shared with pc3d_estimate_normal_f32) in double.
+ *   sign         free in the method; here the last non-zero of (x, y, z) is positive. No sign fix against the
+ *                neighbours as in pc3d_estimate_normal_f32: the attack step does not depend on the sign.
+ *   degenerate   K < 3, a zero covariance deviator or a zero cross product give (0, 0, 1).
+ *   bad index    an entry outside [0, N) is never dereferenced; that point's normal is NaN.
+ * out must not alias x. B <= 65535. */
+int pc3d_pca_normal_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, const int32_t* idx, int B, int N,
+                        int K, float* out, int64_t o_bs, int64_t o_ps, int64_t o_cs, void* stream);
+/* xe = U^T (U (x + t)) - t per point, with U = get_spin_axis_matrix(n) and t = (x . n) n: the cloud the reference hands to
+ * the victim in every step (SIadv_attack.py:293-298). It is x up to rounding except at the rows of U that are rewritten
+ * for |n_z^2 - 1| < 1e-4, where U is not the frame of n and the point moves by up to ~1e-4 |x|; the gradient of
+ * pc3d_si_step_f32 is the victim's at xe. Normals given (nrm) or from idx as pc3d_pca_normal_f32 computes them (exactly one
+ * of the two); nrm_out (may be NULL) receives them. xe and nrm_out alias nothing else. B <= 65535. */
+int pc3d_si_frame_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs,
+                      const float* nrm, int64_t n_bs, int64_t n_ps, int64_t n_cs,
+                      const int32_t* idx, int K, int B, int N,
+                      float* xe, int64_t e_bs, int64_t e_ps, int64_t e_cs,
+                      float* nrm_out, int64_t no_bs, int64_t no_ps, int64_t no_cs, void* stream);
+/* One I-FGM step of shape_invariant_ifgm (SIadv_attack.py:293-320) for B clouds of N points, IN PLACE on x, one launch,
+ * one workgroup per cloud. g = dL/dxe of the victim at pc3d_si_frame_f32's xe. The normals are either given (nrm, idx NULL) or computed in
+ * the prologue from the neighbour lists idx [B,N,K] exactly as pc3d_pca_normal_f32 computes them (nrm NULL). Per point,
+ * the reference's arithmetic as written:
+ *   U        get_spin_axis_matrix(n), the rows for |n_z^2 - 1| < 1e-4 chosen before anything divides by sqrt(1 - n_z^2);
+ *   t        (P . n) n;         P' = U (P + t);         g' = U g with g'_z = 0;
+ *   P'      -= step_size * sqrt(3 * 1024) * g' / (sqrt(sum over the cloud of g'^2) + 1e-9);
+ *   P        = U^T P' - t, then P - ori clamped to [-eps, eps] per coordinate (NaN stays NaN).
+ * The cloud's sum runs in one fixed order that depends on neither B nor N's split over a grid; no float atomics.
+ * nrm_out (may be NULL) receives the normals used; in idx mode with N > 5120 it is required (the normals pass through
+ * it instead of LDS). x must not alias any other argument. A NaN normal (bad index) makes its whole cloud NaN. */
+int pc3d_si_step_f32(float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs,
+                     const float* ori, int64_t o_bs, int64_t o_ps, int64_t o_cs,
+                     const float* g, int64_t g_bs, int64_t g_ps, int64_t g_cs,
+                     const float* nrm, int64_t n_bs, int64_t n_ps, int64_t n_cs,
+                     const int32_t* idx, int K, int B, int N,
+                     float* nrm_out, int64_t no_bs, int64_t no_ps, int64_t no_cs,
+                     double step_size, double eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
