@@ -17,7 +17,6 @@ import torch.optim as optim
 
 from ... import graphed as _graphed
 from ... import ops
-from ... import streams as _streams
 from ..CW.CW_utils import adv_utils as _adv_utils
 
 
@@ -217,18 +216,8 @@ class CWTAOF:
             begin_step(adv0)
             if binary_step == 0 and self._capturable() and self.num_iter > 0:
                 # capture once (after eager warm-up passes on a side stream, as torch requires), then rewind the state
-                side = _streams.side_stream(dev, _streams.TERMS)     # ONE per process (streams.py)
-                side.wait_stream(torch.cuda.current_stream(dev))
-                with torch.cuda.stream(side):
-                    for _ in range(2):
-                        iterate()
-                torch.cuda.current_stream(dev).wait_stream(side)
-                with _graphed.capture_guard() as keep:
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
-                        iterate()
-                run = g.replay
-                st["graph_keep"] = (g, _graphed._cached_tensors(self.model), keep)   # the graph points into the weight caches
+                st["graph_keep"] = loop = _graphed.LoopGraph(iterate, dev, 2, owners=(self.model,))
+                run = loop.replay
                 st["o_bestdist"].fill_(1e10), st["o_bestscore"].fill_(-1), st["o_bestattack"].zero_()
                 begin_step(adv0, reuse_basis=True)
             for _ in range(self.num_iter):

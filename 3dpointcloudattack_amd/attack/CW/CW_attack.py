@@ -13,8 +13,6 @@ Same constructor / ``attack(data, target)`` signature and return values as the r
   user callables still work through the generic path (same protocol as the reference:
   ``adv_func(logits, target)``, ``dist_func(adv[B,3,K], ori[B,3,K], weights[B])``, ``clip_func(pc, ori)``).
 """
-import os
-
 import numpy as np
 import torch
 import torch.optim as optim
@@ -42,14 +40,15 @@ def _logits_of(out):
 class _GraphRunner:
     """Replays captured iterations; batches calls into unrolled graphs. The captured launches hold raw pointers
     into the state dict's tensors AND into the victim's folded / transposed weight caches, so the runner keeps both
-    alive for as long as it lives (a later re-fold of the victim — other weights loaded, a device move — then leaves
-    this runner replaying the weights it was captured with instead of reading freed memory).
+    alive for as long as it lives — the former itself, the latter with the graphed.LoopGraph it holds (a later re-fold
+    of the victim — other weights loaded, a device move — then leaves this runner replaying the weights it was captured
+    with instead of reading freed memory).
     graphs: {iterations per launch: CUDAGraph}, always including 1. Calls accumulate until the largest graph is full;
     flush() runs what is pending with the largest graphs that fit. (A graph boundary costs ~17 us on this stack —
     single-iteration graphs replay at 308.7 us per iteration against 291.7 in a four-iteration graph — hence 16.)"""
 
-    def __init__(self, st, graphs, weights=()):
-        self._keep, self.graphs, self.pending = (st, weights), dict(graphs), 0
+    def __init__(self, st, loop):
+        self._keep, self.loop, self.graphs, self.pending = st, loop, loop.graphs, 0
         self.sizes = sorted(self.graphs, reverse=True)
         self.g1, self.unroll = self.graphs[1], self.sizes[0]
 
@@ -102,10 +101,10 @@ class CW:
         self.trans_fail = 0
         self.attack_fail = 0
         self.verbose = verbose
-        # the fused PointNet iteration's adv -> ori search forked beside the head launches: measured SLOWER in round 4 (headline
-        # 0.310-0.315 ms per iteration forked after the STN tower, 0.309-0.313 after the trunk tower, 0.288 in line: a second
-        # branch in the replayed graph costs ~25 us of cross-queue hand-off for the 12 us it hides), so off unless asked for
-        self.overlap_search = os.environ.get("PC3D_OVERLAP_SEARCH", "0") == "1"
+        # A/B switches of the autograd passes (on: the shipped behaviour): differentiate the functors' per-sample terms
+        # directly (_direct_terms); run the distance term on the TERMS stream beside a sampling-chain victim (_dist_fork)
+        self.direct_terms = True
+        self.dist_stream = True
         self.fused = fused
         self.graph = graph
         self.riders = {"search", "update"} if riders is True else (set() if not riders else set(riders))
@@ -147,14 +146,7 @@ class CW:
         one of this package's own (their gradients are built into pc3d_cls_loss_f32); else None (autograd path)."""
         if not self.fused or not hasattr(self.model, "fused_loss_and_grad"):
             return None
-        af = self.adv_func
-        if type(af) is _adv_utils.UntargetedLogitsAdvLoss:
-            return "untargeted_logits", float(af.kappa)
-        if type(af) is _adv_utils.LogitsAdvLoss:
-            return "logits", float(af.kappa)
-        if type(af) is _adv_utils.CrossEntropyAdvLoss:
-            return "cross_entropy", 0.0
-        return None
+        return self._own_adv_kind()
 
     def _own_adv_kind(self):
         """(kind, kappa) of this package's own adversarial functors (their gradients are built into pc3d_cls_loss_f32)."""
@@ -172,7 +164,7 @@ class CW:
         autograd. The iteration then differentiates the functors' per-sample terms (d loss / d term built in) and the logits
         (gradient from the loss kernel) directly — no mean / weight / sum / accumulate launches, see attack/KNN."""
         own_dist = (_dist_utils.ChamferDist, _dist_utils.HausdorffDist, _dist_utils.ChamferkNNDist)
-        return (self.fused and getattr(self, "direct_terms", True) and st["budget"] is not None and st["adv"].is_cuda
+        return (self.fused and self.direct_terms and st["budget"] is not None and st["adv"].is_cuda
                 and type(self.dist_func) in own_dist and self._own_adv_kind() is not None
                 and st["adv"].shape[1] == 3 and st["input_val"] is not None)
 
@@ -264,120 +256,139 @@ class CW:
 
     def _iterate(self, st, iteration=None, last=False):
         """One pass of the hot-loop body (reference :111-174), entirely on the device. The Adam step number lives
-        in st["step"] on the device, so the body is identical every pass (hipGraph-replayable)."""
-        adv_data, ori_data, label = st["adv"], st["ori"], st["label"]
+        in st["step"] on the device, so the body is identical every pass (hipGraph-replayable). Picks the pass."""
         fml = self._fused_model_loss() if st["budget"] is not None else None
-        gx_model = None
-        side = None
         dk = self._fused_dist_kind() if fml is not None else 0
         if dk:
-            # launch-minimal pass: victim fwd/bwd (fused heads), bookkeeping, [NN search], one update launch
-            with torch.no_grad():
-                cur = adv_data.detach()
-                if (self.riders and "adam" in st and hasattr(self.model, "fused_attack_update") and st["K"] <= ops.CW_UPDATE_MAX_POINTS
-                        and not (dk == 2 and getattr(self, "overlap_search", False))):
-                    # 15 launches: the search, the bookkeeping and the update ride the victim's own launches
-                    self.model.fused_attack_update(
-                        cur, st["target"], *fml, pred_out=st["pred"], step=st["step"], scale=st["ratio"] / st["B"],
-                        cw=dict(ori=ori_data, label=label, untarget=self.attack_method == 'untarget',
-                                bestdist=st["bestdist"], bestscore=st["bestscore"], o_bestdist=st["o_bestdist"],
-                                o_bestscore=st["o_bestscore"], o_bestattack=st["o_bestattack"], input_val=st["input_val"],
-                                dist_val=st["dist_val"], m=st["exp_avg"], v=st["exp_avg_sq"], w=st["weights"],
-                                adam=st["adam"], lr=self.attack_lr, budget=st["budget"], dist_kind=dk),
-                        ride_search="search" in self.riders, epilogue="update" in self.riders)
-                    return
-                if hasattr(self.model, "fused_attack_grad") and st["K"] <= ops.CW_UPDATE_MAX_POINTS:
-                    # 17 launches: the classifier tail writes pred + advances the step word, one update launch
-                    nn_box = []
-                    fork = None
-                    if dk == 2 and getattr(self, "overlap_search", False):
-                        # the adv -> ori search depends on the iterate only: forked onto the TERMS stream right after the
-                        # first tower launch, it runs beside the STN head's fold + two linear launches (a few CUs each)
-                        # instead of behind the whole victim; joined before the update launch. Inside a captured iteration
-                        # the fork and the join become graph edges.
-                        main = torch.cuda.current_stream(cur.device)
-                        side_s = _streams.side_stream(cur.device, _streams.TERMS)
-
-                        def fork():
-                            side_s.wait_stream(main)
-                            with torch.cuda.stream(side_s):
-                                nn_box.append(ops.nn_raw(cur, ori_data, True, True)[1])
-                    _, _, gx_model = self.model.fused_attack_grad(cur, st["target"], *fml, pred_out=st["pred"],
-                                                                  step=st["step"], scale=st["ratio"] / st["B"],
-                                                                  after_stn_tower=fork)
-                    nn_idx = None
-                    if fork is not None:
-                        main.wait_stream(side_s)
-                        nn_idx = nn_box[0]
-                    elif dk == 2:
-                        _, nn_idx = ops.nn_raw(cur, ori_data, True, True)
-                    ops.cw_update(cur, ori_data, st["pred"], label, self.attack_method == 'untarget', st["bestdist"],
-                                  st["bestscore"], st["o_bestdist"], st["o_bestscore"], st["o_bestattack"], gx_model,
-                                  st["exp_avg"], st["exp_avg_sq"], st["step"], self.attack_lr, st["budget"],
-                                  input_val=st["input_val"], dist_val=st["dist_val"], dist_kind=dk, w=st["weights"],
-                                  nn_idx=nn_idx)
-                    return
-                _, pred, _, gx_model = self.model.fused_loss_and_grad(cur, st["target"], *fml,
-                                                                      scale=st["ratio"] / st["B"])
-                ops.cw_bookkeep(cur, ori_data, pred, label, self.attack_method == 'untarget', st["bestdist"],
-                                st["bestscore"], st["o_bestdist"], st["o_bestscore"], st["o_bestattack"],
-                                input_val=st["input_val"], dist_val=st["dist_val"], step=st["step"])
-                st["pred"].copy_(pred)
-                nn_idx = None
-                if dk == 2:
-                    _, nn_idx = ops.nn_raw(cur, ori_data, True, True)
-                ops.cw_step(cur, gx_model, st["exp_avg"], st["exp_avg_sq"], st["step"], self.attack_lr, ori_data,
-                            st["budget"], dist_kind=dk, w=st["weights"], l2norm=st["dist_val"], nn_idx=nn_idx)
-            return
+            # launch-minimal passes: victim fwd/bwd (fused heads), bookkeeping, [NN search], one update launch
+            if (self.riders and "adam" in st and hasattr(self.model, "fused_attack_update")
+                    and st["K"] <= ops.CW_UPDATE_MAX_POINTS):
+                return self._pass_riders(st, fml, dk)
+            if hasattr(self.model, "fused_attack_grad") and st["K"] <= ops.CW_UPDATE_MAX_POINTS:
+                return self._pass_fused_update(st, fml, dk)
+            return self._pass_fused_steps(st, fml, dk)
         if fml is None and self._direct_terms(st):
-            B = st["B"]
-            alias = st.get("adv_alias")
-            if alias is None or alias.data_ptr() != adv_data.data_ptr():
-                alias = st["adv_alias"] = adv_data.detach().requires_grad_()      # same storage, its own .grad
-            capturing = torch.cuda.is_current_stream_capturing()
-            if (getattr(self, "dist_stream", True) and getattr(self.model, "sampling_chain_front", False) and not capturing):
-                main = torch.cuda.current_stream(adv_data.device)
-                side = _streams.side_stream(adv_data.device, _streams.TERMS)
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    terms = self.dist_func.per_sample_terms(alias, ori_data, st["gdist"], mean=False)
-            logits = _logits_of(self.model(adv_data))
-            kind, kappa = self._own_adv_kind()
-            lg = logits if (logits.dtype == torch.float32 and logits.stride(1) == 1) else logits.float().contiguous()
-            # the loss kernel in raw mode (+4: the functor's value on the logits as given): prediction into st["pred"],
-            # gradient already scaled by ratio / B (the batch mean)
-            _, pred, _, g_logits = ops.cls_loss(lg.detach(), st["target"], ops.LOSS_KINDS[kind] + 4, kappa,
-                                                float(np.float32(st["ratio"]) / np.float32(B)), pred_out=st["pred"])
-            with torch.no_grad():
-                ops.cw_bookkeep(adv_data.detach(), ori_data, pred, label, self.attack_method == 'untarget', st["bestdist"],
-                                st["bestscore"], st["o_bestdist"], st["o_bestscore"], st["o_bestattack"],
-                                input_val=st["input_val"], dist_val=st["dist_val"], step=st["step"])
-            if side is not None:
-                main.wait_stream(side)
-            else:
+            return self._pass_direct_terms(st)
+        return self._pass_autograd(st, fml)
+
+    def _pass_riders(self, st, fml, dk):
+        """15 launches: the search, the bookkeeping and the update ride the victim's own launches."""
+        with torch.no_grad():
+            self.model.fused_attack_update(
+                st["adv"].detach(), st["target"], *fml, pred_out=st["pred"], step=st["step"], scale=st["ratio"] / st["B"],
+                cw=dict(ori=st["ori"], label=st["label"], untarget=self.attack_method == 'untarget',
+                        bestdist=st["bestdist"], bestscore=st["bestscore"], o_bestdist=st["o_bestdist"],
+                        o_bestscore=st["o_bestscore"], o_bestattack=st["o_bestattack"], input_val=st["input_val"],
+                        dist_val=st["dist_val"], m=st["exp_avg"], v=st["exp_avg_sq"], w=st["weights"],
+                        adam=st["adam"], lr=self.attack_lr, budget=st["budget"], dist_kind=dk),
+                ride_search="search" in self.riders, epilogue="update" in self.riders)
+
+    def _pass_fused_update(self, st, fml, dk):
+        """17 launches: the classifier tail writes pred + advances the step word, [the search], one update launch."""
+        ori_data = st["ori"]
+        with torch.no_grad():
+            cur = st["adv"].detach()
+            _, _, gx_model = self.model.fused_attack_grad(cur, st["target"], *fml, pred_out=st["pred"],
+                                                          step=st["step"], scale=st["ratio"] / st["B"])
+            nn_idx = None
+            if dk == 2:
+                _, nn_idx = ops.nn_raw(cur, ori_data, True, True)
+            ops.cw_update(cur, ori_data, st["pred"], st["label"], self.attack_method == 'untarget', st["bestdist"],
+                          st["bestscore"], st["o_bestdist"], st["o_bestscore"], st["o_bestattack"], gx_model,
+                          st["exp_avg"], st["exp_avg_sq"], st["step"], self.attack_lr, st["budget"],
+                          input_val=st["input_val"], dist_val=st["dist_val"], dist_kind=dk, w=st["weights"],
+                          nn_idx=nn_idx)
+
+    def _pass_fused_steps(self, st, fml, dk):
+        """A victim with fused_loss_and_grad only (or a cloud too large for the update launch): bookkeeping, [the
+        search] and the step are a launch each."""
+        ori_data = st["ori"]
+        with torch.no_grad():
+            cur = st["adv"].detach()
+            _, pred, _, gx_model = self.model.fused_loss_and_grad(cur, st["target"], *fml,
+                                                                  scale=st["ratio"] / st["B"])
+            ops.cw_bookkeep(cur, ori_data, pred, st["label"], self.attack_method == 'untarget', st["bestdist"],
+                            st["bestscore"], st["o_bestdist"], st["o_bestscore"], st["o_bestattack"],
+                            input_val=st["input_val"], dist_val=st["dist_val"], step=st["step"])
+            st["pred"].copy_(pred)
+            nn_idx = None
+            if dk == 2:
+                _, nn_idx = ops.nn_raw(cur, ori_data, True, True)
+            ops.cw_step(cur, gx_model, st["exp_avg"], st["exp_avg_sq"], st["step"], self.attack_lr, ori_data,
+                        st["budget"], dist_kind=dk, w=st["weights"], l2norm=st["dist_val"], nn_idx=nn_idx)
+
+    def _dist_fork(self, adv_data):
+        """(main, side) when the distance term is to run beside the victim, side already waiting on main; else None.
+        The term depends on the iterate only: beside a victim whose forward starts with a sampling chain (most of the
+        chip idle: CurveNet, PointNet++) it runs on the process-wide TERMS stream, and autograd runs its backward there
+        too (as in attack/KNN/KNN_attack.py). Beside DGCNN the same move cost GeoA3 2 %, hence the victim's flag."""
+        if not (adv_data.is_cuda and self.dist_stream and getattr(self.model, "sampling_chain_front", False)
+                and not torch.cuda.is_current_stream_capturing()):
+            return None
+        main = torch.cuda.current_stream(adv_data.device)
+        side = _streams.side_stream(adv_data.device, _streams.TERMS)
+        side.wait_stream(main)
+        return main, side
+
+    def _pass_direct_terms(self, st):
+        """The autograd pass without the loss (see _direct_terms)."""
+        adv_data, ori_data, B = st["adv"], st["ori"], st["B"]
+        alias = st.get("adv_alias")
+        if alias is None or alias.data_ptr() != adv_data.data_ptr():
+            alias = st["adv_alias"] = adv_data.detach().requires_grad_()      # same storage, its own .grad
+        fork = self._dist_fork(adv_data)
+        if fork:
+            with torch.cuda.stream(fork[1]):
                 terms = self.dist_func.per_sample_terms(alias, ori_data, st["gdist"], mean=False)
-            adv_data.grad = None
-            alias.grad = None
-            ones = ops.const_vec(adv_data.device, B, 1.0)
-            torch.autograd.backward([lg] + terms, [g_logits] + [ones] * len(terms))
-            ops.adam_clip_step(adv_data.data, adv_data.grad, st["exp_avg"], st["exp_avg_sq"], st["step"],
-                               self.attack_lr, ori=ori_data, budget=st["budget"], g2=alias.grad)
-            return
+        logits = _logits_of(self.model(adv_data))
+        kind, kappa = self._own_adv_kind()
+        lg = logits if (logits.dtype == torch.float32 and logits.stride(1) == 1) else logits.float().contiguous()
+        # the loss kernel in raw mode (+4: the functor's value on the logits as given): prediction into st["pred"],
+        # gradient already scaled by ratio / B (the batch mean)
+        _, pred, _, g_logits = ops.cls_loss(lg.detach(), st["target"], ops.LOSS_KINDS[kind] + 4, kappa,
+                                            float(np.float32(st["ratio"]) / np.float32(B)), pred_out=st["pred"])
+        with torch.no_grad():
+            ops.cw_bookkeep(adv_data.detach(), ori_data, pred, st["label"], self.attack_method == 'untarget', st["bestdist"],
+                            st["bestscore"], st["o_bestdist"], st["o_bestscore"], st["o_bestattack"],
+                            input_val=st["input_val"], dist_val=st["dist_val"], step=st["step"])
+        if fork:
+            fork[0].wait_stream(fork[1])
+        else:
+            terms = self.dist_func.per_sample_terms(alias, ori_data, st["gdist"], mean=False)
+        adv_data.grad = None
+        alias.grad = None
+        ones = ops.const_vec(adv_data.device, B, 1.0)
+        torch.autograd.backward([lg] + terms, [g_logits] + [ones] * len(terms))
+        ops.adam_clip_step(adv_data.data, adv_data.grad, st["exp_avg"], st["exp_avg_sq"], st["step"],
+                           self.attack_lr, ori=ori_data, budget=st["budget"], g2=alias.grad)
+
+    def _bookkeep_torch(self, st, cur, pred, dist_val):
+        """The record of one pass (reference :129-153) in torch ops, for what pc3d_cw_bookkeep_f32 does not take."""
+        with torch.no_grad():
+            succ = self._success(pred, st["label"])
+            upd = succ & (dist_val < st["bestdist"])
+            st["bestdist"].copy_(torch.where(upd, dist_val, st["bestdist"]))
+            st["bestscore"].copy_(torch.where(upd, pred, st["bestscore"]))
+            upd_o = succ & (dist_val < st["o_bestdist"])
+            st["o_bestdist"].copy_(torch.where(upd_o, dist_val, st["o_bestdist"]))
+            st["o_bestscore"].copy_(torch.where(upd_o, pred, st["o_bestscore"]))
+            st["o_bestattack"].copy_(torch.where(upd_o[:, None, None], cur, st["o_bestattack"]))
+            st["input_val"].copy_(cur)     # the iterate the LAST pass started from (reference :133, :208-209)
+            st["pred"].copy_(pred)
+
+    def _pass_autograd(self, st, fml):
+        """The generic protocol: the functors as given, gradients from autograd. With fml the victim's side (forward,
+        adversarial loss, backward to the input) is its fused_loss_and_grad and autograd differentiates the distance only."""
+        adv_data, ori_data, label = st["adv"], st["ori"], st["label"]
+        gx_model = fork = None
         if fml is not None:
             with torch.no_grad():  # victim forward + adversarial loss + backward-to-input without autograd
                 logits, pred, _, gx_model = self.model.fused_loss_and_grad(adv_data.detach(), st["target"], *fml,
                                                                            scale=st["ratio"] / st["B"])
         else:
-            if (adv_data.is_cuda and getattr(self, "dist_stream", True) and getattr(self.model, "sampling_chain_front", False)
-                    and not torch.cuda.is_current_stream_capturing()):
-                # the distance term depends on the iterate only: beside a victim whose forward starts with a sampling
-                # chain (most of the chip idle: CurveNet, PointNet++) it runs on the process-wide TERMS stream, and
-                # autograd runs its backward there too (as in attack/KNN/KNN_attack.py). Beside DGCNN the same move cost
-                # GeoA3 2 %, hence the victim's flag.
-                main = torch.cuda.current_stream(adv_data.device)
-                side = _streams.side_stream(adv_data.device, _streams.TERMS)
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
+            fork = self._dist_fork(adv_data)
+            if fork:
+                with torch.cuda.stream(fork[1]):
                     dist_loss = self.dist_func(adv_data, ori_data, st["weights"]).mean()
             logits = _logits_of(self.model(adv_data))
             pred = torch.argmax(logits, dim=1)  # [B]
@@ -395,19 +406,10 @@ class CW:
         else:
             with torch.no_grad():
                 dist_val = torch.sqrt(torch.sum((cur - ori_data) ** 2, dim=[1, 2]))  # [B]
-                succ = self._success(pred, label)
-                upd = succ & (dist_val < st["bestdist"])
-                st["bestdist"].copy_(torch.where(upd, dist_val, st["bestdist"]))
-                st["bestscore"].copy_(torch.where(upd, pred, st["bestscore"]))
-                upd_o = succ & (dist_val < st["o_bestdist"])
-                st["o_bestdist"].copy_(torch.where(upd_o, dist_val, st["o_bestdist"]))
-                st["o_bestscore"].copy_(torch.where(upd_o, pred, st["o_bestscore"]))
-                st["o_bestattack"].copy_(torch.where(upd_o[:, None, None], cur, st["o_bestattack"]))
-                st["input_val"].copy_(cur)     # the iterate the LAST pass started from (reference :133, :208-209)
-                st["pred"].copy_(pred)
+            self._bookkeep_torch(st, cur, pred, dist_val)
         # compute loss and backward
-        if side is not None:
-            main.wait_stream(side)
+        if fork:
+            fork[0].wait_stream(fork[1])
         else:
             dist_loss = self.dist_func(adv_data, ori_data, st["weights"]).mean()
         if gx_model is not None:
@@ -449,29 +451,15 @@ class CW:
             return run
         if st["graph"] is not None:
             return st["graph_run"]
-        side = _streams.side_stream(self.device, _streams.TERMS)     # ONE per process (streams.py)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._iterate(st)
-        torch.cuda.current_stream(self.device).wait_stream(side)
+        victim = self.model.model if isinstance(self.model, _graphed.GraphedVictim) else self.model
         # warm-up passes are real iterations; account for them by NOT rolling anything back: callers start counting
         # after _make_runner (bench) or use _begin_binary_step to reset the state (attack()).
-        st["adv"].grad = None
-        graphs = {}
-        with _graphed.capture_guard() as cap_keep:   # no cyclic-GC destruction of older graphs while a stream captures
-            for n in sorted({1, min(4, max(1, unroll)), max(1, unroll)}):
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    for _ in range(n):
-                        self._iterate(st)
-                graphs[n] = g
-        st["graph"] = graphs[1]
-        victim = self.model.model if isinstance(self.model, _graphed.GraphedVictim) else self.model
+        loop = _graphed.LoopGraph(lambda: self._iterate(st), self.device, warmup,
+                                  counts={1, min(4, max(1, unroll)), max(1, unroll)}, owners=(victim,))
+        st["graph"] = loop.graphs[1]
         # the runner keeps the state's tensors alive, not the dict itself (st -> runner -> st would be a cycle that only
         # the cycle collector frees, at an arbitrary later time)
-        keep = [v for v in st.values() if torch.is_tensor(v)] + cap_keep
-        st["graph_run"] = _GraphRunner(keep, graphs, weights=_graphed._cached_tensors(victim))
+        st["graph_run"] = _GraphRunner([v for v in st.values() if torch.is_tensor(v)], loop)
         return st["graph_run"]
 
     def _end_binary_step(self, st):

@@ -171,7 +171,7 @@ class CWAdd(_CW):
 
     def _iterate(self, st, iteration=None, last=False):
         """One pass of the hot-loop body (reference :138-187)."""
-        ori, label, B = st["ori"], st["label"], st["B"]
+        ori, B = st["ori"], st["B"]
         scale = float(np.float32(st["ratio"]) / np.float32(B))
         if st["path"] == "fast":
             # the classifier tail writes pred and advances the step word; then search + update
@@ -203,16 +203,7 @@ class CWAdd(_CW):
         with torch.no_grad():
             cur = adv.detach()
             dist_val = self.dist_func(cur.transpose(1, 2).contiguous(), ori_t, batch_avg=False).detach().float().view(-1)
-            succ = self._success(pred, label)
-            upd = succ & (dist_val < st["bestdist"])
-            st["bestdist"].copy_(torch.where(upd, dist_val, st["bestdist"]))
-            st["bestscore"].copy_(torch.where(upd, pred, st["bestscore"]))
-            upd_o = succ & (dist_val < st["o_bestdist"])
-            st["o_bestdist"].copy_(torch.where(upd_o, dist_val, st["o_bestdist"]))
-            st["o_bestscore"].copy_(torch.where(upd_o, pred, st["o_bestscore"]))
-            st["o_bestattack"].copy_(torch.where(upd_o[:, None, None], cur, st["o_bestattack"]))
-            st["input_val"].copy_(cur)
-            st["pred"].copy_(pred)
+            self._bookkeep_torch(st, cur, pred, dist_val)
             st["dist_val"].copy_(dist_val)
         adv_loss = self.adv_func(logits, st["target"]).mean()
         if st["ratio"] != 1.0:

@@ -22,7 +22,6 @@ import torch.nn.functional as F
 
 from ... import graphed as _graphed
 from ... import ops
-from ... import streams as _streams
 from . import isometry_init  # noqa: F401  (reference-style drivers reach it through this module)
 from . import thompson_sample as ts
 from .thompson_sample import logits_info
@@ -138,7 +137,7 @@ class _Ctri:
         self.done = torch.zeros((B,), dtype=torch.int32, device=dev)
         self.steps = torch.zeros((B,), dtype=torch.int32, device=dev)
         self.kept_out = None                   # [B, ncls], allocated by the first step from the victim's output
-        self.graph, self.keep = None, None
+        self.graph = None
 
     def load(self, x, label, W, active=None):
         """active: bool [B], the clouds that run (default: all)."""
@@ -175,19 +174,8 @@ class _Ctri:
 
     def capture(self, warmup=2):
         """Capture one step (after `warmup` eager ones on the side stream; they advance the state: load() again)."""
-        dev = self.x.device
-        side = _streams.side_stream(dev, _streams.TERMS)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self.step()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        with _graphed.capture_guard() as keep:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self.step()
-        # the graph bakes in the addresses of the folded weights: hold what it points at
-        self.graph, self.keep = g, keep + _graphed._cached_tensors(self.victim)
+        # the graph bakes in the addresses of the folded weights: it holds what it points at (LoopGraph.keep)
+        self.graph = _graphed.LoopGraph(self.step, self.x.device, warmup, owners=(self.victim,))
 
     def run(self, num_steps):
         for _ in range(num_steps):

@@ -23,7 +23,6 @@ import torch
 
 from ... import graphed as _graphed
 from ... import ops
-from ... import streams as _streams
 from .baselines import ClipPointsLinf, DUPNet, SORDefense, SRSDefense
 
 KNN = 20                                  # open3d.geometry.KDTreeSearchParamKNN(knn=20), SIadv_attack.py:212
@@ -43,7 +42,7 @@ class _Loop:
         f32 = dict(dtype=torch.float32, device=dev)
         self.x, self.ori, self.xe, self.nrm = (torch.zeros((B, 3, N), **f32) for _ in range(4))
         self.label = torch.zeros((B,), dtype=torch.int64, device=dev)
-        self.graph, self.keep = None, None
+        self.graph = None
 
     def load(self, x, ori, label):
         self.x.copy_(x), self.ori.copy_(ori), self.label.copy_(label)
@@ -65,19 +64,8 @@ class _Loop:
 
     def capture(self, warmup=2):
         """Capture one step (after `warmup` eager ones on the side stream; they advance the state: load() again)."""
-        dev = self.x.device
-        side = _streams.side_stream(dev, _streams.TERMS)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self.step()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        with _graphed.capture_guard() as keep:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self.step()
-        # the graph bakes in the addresses of the folded weights: hold what it points at
-        self.graph, self.keep = g, keep + _graphed._cached_tensors(self.victim)
+        # the graph bakes in the addresses of the folded weights: it holds what it points at (LoopGraph.keep)
+        self.graph = _graphed.LoopGraph(self.step, self.x.device, warmup, owners=(self.victim,))
 
     def run(self, steps):
         for _ in range(steps):

@@ -62,6 +62,38 @@ def capture_guard():
         if was:
             gc.enable()
 
+
+class LoopGraph:
+    """``body()`` captured into hipGraphs: the one place where the package's loops (the attacks' iterations, the
+    victim's no-grad forward) are captured. `warmup` eager passes run on the process-wide TERMS side stream, as torch
+    requires before a capture (ONE side stream per process, see streams.py); then, under one capture_guard(), every n
+    in `counts` gets a graph of n passes back to back. The warm-up passes are real passes and nothing is rolled back
+    here: the caller rewinds its own state.
+    graphs: {n: CUDAGraph}; replay(n) launches one. keep: what the graphs point at besides the caller's own buffers —
+    the guard's list and every tensor cached on the `owners` (the victims' folded / transposed weights) — and it lives
+    exactly as long as this object, so whoever holds the object to replay it holds the memory too."""
+
+    def __init__(self, body, device, warmup, counts=(1,), owners=()):
+        main = torch.cuda.current_stream(device)
+        side = _streams.side_stream(device, _streams.TERMS)
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                body()
+        main.wait_stream(side)
+        self.graphs = {}
+        with capture_guard() as keep:
+            for n in sorted(set(counts)):
+                g = self.graphs[n] = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    for _ in range(n):
+                        body()
+        self.keep = keep + [t for owner in owners for t in _cached_tensors(owner)]
+
+    def replay(self, n=1):
+        self.graphs[n].replay()
+
+
 MAX_CAPTURES = 4     # distinct (shape, mode, weights) keys per wrapper; the oldest is dropped beyond this
 MAX_REPLICAS = 4     # captures of ONE key that may wait for their backward at the same time (EOT-style loops that
                      # run several forwards before one backward); further forwards run eagerly
@@ -235,32 +267,32 @@ class GraphedVictim(nn.Module):
             o = o if isinstance(o, (tuple, list)) else (o,)
             return tuple(o[i] for i in picks)
 
+        # The graphs hold raw pointers to every tensor the forward read, including the victims' folded-weight caches
+        # (created lazily, re-folded when weights change): keep those alive with the capture.
         if with_grad:
             g = torch.cuda.make_graphed_callables(fn, (x.detach().clone().requires_grad_(True),),
                                                   num_warmup_iters=self._warmup)
+            keepalive = _cached_tensors(model)
         else:
             static_in = x.detach().clone()
-            side = _streams.side_stream(x.device, _streams.TERMS)     # warm-up passes; ONE per process (streams.py)
-            side.wait_stream(torch.cuda.current_stream(x.device))
-            with torch.cuda.stream(side), torch.no_grad():
-                for _ in range(self._warmup):
-                    fn(static_in)
-            torch.cuda.current_stream(x.device).wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.no_grad(), torch.cuda.graph(graph):
-                static_out = fn(static_in)
+            static_out = []                              # the last pass's outputs: in the end, the captured pass's
+
+            def body():
+                static_out.clear()                       # a warm-up pass's outputs go before the next pass runs
+                with torch.no_grad():
+                    static_out.extend(fn(static_in))
+            loop = LoopGraph(body, x.device, self._warmup, owners=(model,))
+            keepalive = loop.keep
 
             def g(inp):
                 static_in.copy_(inp)
-                graph.replay()
+                loop.replay()
                 return static_out
         slot = _Slot(g)
         slot.where, slot.is_seq = where, is_seq
         rec = model.__dict__.get("_input_knn")           # the capture pass's neighbour graph: static memory of this capture,
         slot.input_knn = rec[3] if rec else None         # rewritten by every replay (see note_input_knn)
-        # The graphs hold raw pointers to every tensor the forward read, including the victims' folded-weight caches
-        # (created lazily, re-folded when weights change): keep those alive with the capture.
-        slot.keepalive = _cached_tensors(model)
+        slot.keepalive = keepalive
         self.stats["captures"] += 1
         return slot
 
