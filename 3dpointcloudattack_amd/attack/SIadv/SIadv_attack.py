@@ -1,33 +1,48 @@
-"""The shape-invariant white-box attack (SI-Adv, I-FGM) — MI355X mirror of the reference's ``attack/SIadv/SIadv_attack.py``.
+"""SI-Adv: the shape-invariant white-box attack (I-FGM) and the three query attacks — MI355X mirror of the reference's
+``attack/SIadv/SIadv_attack.py``.
 
-Every point moves only inside its tangent plane: with the normal n the point is taken to the frame P' = U (P + (P.n) n),
-the surrogate's gradient is taken there, its component along the normal is dropped, P' makes an L2-normalised step and
-goes back, P = U^T P' - (P.n) n, followed by the clamp to the eps box; then the normals are estimated again.
+White box (``ifgm_ours``). Every point moves only inside its tangent plane: with the normal n the point is taken to the
+frame P' = U (P + (P.n) n), the surrogate's gradient is taken there, its component along the normal is dropped, P' makes
+an L2-normalised step and goes back, P = U^T P' - (P.n) n, followed by the clamp to the eps box; then the normals are
+estimated again. The reference runs one cloud at a time and re-estimates the normals with open3d on the host in every
+step. ``PointCloudAttack`` runs a batch and stays on the device: per step one self-kNN search (K = 20, hinted by the
+previous step's lists), ``pc3d_si_frame_f32`` (the PCA normals from the lists and the cloud U^T (U (P + t)) - t the
+reference shows the victim), the surrogate's passes, and ``pc3d_si_step_f32`` (the step). The loop has no data-dependent
+exit, so with a PointNet surrogate (fused passes, no autograd) the step is captured into a hipGraph and replayed. Any
+other surrogate, a defence head or the top-5 loss take autograd for the gradient and the same two kernels.
 
-The reference runs one cloud at a time and re-estimates the normals with open3d on the host in every step.
-``PointCloudAttack`` runs a batch and stays on the device: per step one self-kNN search (K = 20, hinted by the previous
-step's lists), ``pc3d_si_frame_f32`` (the PCA normals from the lists and the cloud U^T (U (P + t)) - t the reference
-shows the victim), the surrogate's passes, and ``pc3d_si_step_f32`` (the step). The loop has no data-dependent exit,
-so with a PointNet surrogate (fused passes, no autograd) the step is captured into a hipGraph and replayed. Any other
-surrogate, a defence head or the top-5 loss take autograd for the gradient and the same two kernels.
+Black box (``simba``, ``simbapp``, ``ours``: ``simba_attack``, ``simbapp_attack``, ``shape_invariant_query_attack``). The
+reference queries the target once per signed try of one table entry of one cloud and reads the loss back each time. Here
+all clouds of a batch advance together: a step is ONE forward of the 2B candidate clouds (both signed tries of every
+cloud) and one launch of ``pc3d_query_step_f32``, which takes the reference's decision per cloud (try 0, and only if it
+was rejected try 1; strict >; query_costs + 1 or + 2), puts the accepted change into the state, latches the clouds whose
+loop has ended and writes the candidates of the next entry. With a PointNet target and no defence head the step is
+captured into a hipGraph; the host reads the latches back every 16 steps. The tables come first: ``simba``'s shuffled
+basis lists are drawn on the host exactly as the reference draws them (``draw_simba_tables``); ``simbapp``'s choices and
+amounts are drawn once per batch on the device from the caller's generator (parity unpinned: the reference's body cannot
+run); ``ours`` ranks the points by the surrogate's gradient in the tangent frame (``pc3d_si_rank_f32``).
 
-Kept on purpose: the spin-axis matrix as written, including its rows for |n_z^2 - 1| < 1e-4, which are
-not the frame of n — so the victim sees those points displaced by up to 1e-4, which a PointNet's max-pool can amplify;
-sqrt(3 * 1024) in the step whatever N is; the loss summed over the batch. Not kept: the checkpoint loading of
-``build_models`` (the models are handed in), ``assert abs(normal_vec).max() <= 1`` (a host round trip), the normal
-estimation after the last step (never used), and the three query attacks (``simba``, ``simbapp``, ``ours``), which
-``run`` refuses by name.
+Kept on purpose: the spin-axis matrix as written, including its rows for |n_z^2 - 1| < 1e-4, which
+are not the frame of n — so the victim sees those points displaced by up to 1e-4, which a PointNet's max-pool can
+amplify; sqrt(3 * 1024) in the step whatever N is; the loss summed over the batch; in the query attacks the returned
+cloud of ``ours`` (the last candidate evaluated, accepted or not), the top-5 rule on the last logits evaluated, strict >
+and kappa = -999. Not kept: the checkpoint loading of ``build_models`` (the models are handed in), ``assert
+abs(normal_vec).max() <= 1`` (a host round trip), the normal estimation after the last step (never used), and the two
+shuffled re-evaluations with their prints at the end of ``shape_invariant_query_attack`` (they change no result).
 """
 import numpy as np
 import torch
 
 from ... import graphed as _graphed
 from ... import ops
+from ...model import pointnet as _pointnet
 from .baselines import ClipPointsLinf, DUPNet, SORDefense, SRSDefense
 
 KNN = 20                                  # open3d.geometry.KDTreeSearchParamKNN(knn=20), SIadv_attack.py:212
 QUERY_METHODS = ("simba", "simbapp", "ours")
 _MAX_LOOPS = 4
+POLL = 16                                 # query loops: steps per graph replay, and between two reads of the latches
+_QUERY_NAMES = {"simba": "simba_attack", "simbapp": "simbapp_attack", "ours": "shape_invariant_query_attack"}
 
 
 def _first(out):
@@ -75,12 +90,107 @@ class _Loop:
                 self.step()
 
 
+def simba_basis(N):
+    """basis_list of simba_attack before its shuffle (SIadv_attack.py:371-375): [3N,2] rows (channel, idx), in the
+    reference's loop order (the point index outermost)."""
+    basis_list = []
+    for j in range(N):
+        for i in range(3):
+            basis_list.append((i, j))
+    return np.array(basis_list)
+
+
+def draw_simba_tables(N, active):
+    """The tables of simba_attack for a batch, drawn as the reference draws them: one np.random.shuffle of the [3N,2]
+    basis list per cloud, in cloud order, and only for the clouds that did not return early (active[b] true).
+    Returns int32 [B,3N]: entry 3 * idx + channel (zeros for a cloud that returned early)."""
+    tab = np.zeros((len(active), 3 * N), np.int32)
+    for b, on in enumerate(active):
+        if on:
+            basis_list = simba_basis(N)
+            np.random.shuffle(basis_list)
+            tab[b] = 3 * basis_list[:, 1] + basis_list[:, 0]
+    return tab
+
+
+def sign_order(step_size):
+    """The two signs in the order the reference's ``for eps in {step_size, -step_size}`` visits them."""
+    return tuple({step_size, -step_size})
+
+
+class _QueryLoop:
+    """The query loops' state for one batch shape: static buffers, one step as a function, and its hipGraph of POLL steps.
+    frame: the shape-invariant mode (the state is P', a candidate is the whole cloud U^T (P' + pert) - t)."""
+
+    def __init__(self, attack, B, N, L, k, dev, frame, table_eps, fast):
+        self.attack, self.fast, self.L = attack, fast, L
+        f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+        s = self.s = dict(top=5 if attack.top5_attack else 1)
+        s["st"], s["last"] = torch.zeros((B, 3, N), **f32), torch.zeros((B, 3, N), **f32)
+        s["cand"] = torch.zeros((2 * B, 3, N), **f32)
+        s["ori"], s["nrm"], s["dir"] = ((torch.zeros((B, 3, N), **f32), torch.zeros((B, 3, N), **f32),
+                                         torch.zeros((B, N, 3), **f32)) if frame else (None, None, None))
+        s["tab"] = torch.zeros((B, L), **i32)
+        s["eps"] = torch.zeros((B, L, 2) if table_eps else (2,), **f32)
+        for nm in ("pos", "done", "queries", "adv_target", "last_try"):
+            s[nm] = torch.zeros((B,), **i32)
+        s["best"] = torch.zeros((B,), **f32)
+        s["label"] = torch.zeros((B,), dtype=torch.int64, device=dev)
+        s["last_logp"] = torch.zeros((B, k), **f32)
+        s["acc_trace"], s["loss_trace"] = torch.zeros((B, L), **i32), torch.zeros((B, L, 2), **f32)
+        self.graph = None
+
+    def load(self, x, label, tab, eps, active, adv_target0, logp0, nrm=None, dirs=None):
+        """The clean clouds x [B,3,N], the tables, the clouds whose loop runs, and the initial query's outcome; then the
+        first candidates."""
+        s = self.s
+        s["tab"].copy_(tab), s["eps"].copy_(eps), s["label"].copy_(label)
+        s["pos"].zero_(), s["queries"].fill_(1), s["last_try"].zero_(), s["best"].fill_(-999.)
+        s["done"].copy_(~active), s["adv_target"].copy_(adv_target0), s["last_logp"].copy_(logp0)
+        s["acc_trace"].fill_(-2), s["loss_trace"].fill_(float("nan"))
+        s["last"].copy_(x)
+        if s["nrm"] is not None:
+            s["ori"].copy_(x), s["nrm"].copy_(nrm), s["dir"].copy_(dirs)
+        else:
+            s["st"].copy_(x)
+        ops.query_step(s, init=True)
+
+    def step(self):
+        a, cand = self.attack, self.s["cand"]
+        if self.fast:
+            logp = torch.log_softmax(_pointnet.fused_forward(a.classifier, cand)[0], dim=1)
+        else:
+            logp = _first(a.classifier(a.pre_head(cand) if a.pre_head is not None else cand)).float().contiguous()
+        ops.query_step(self.s, logp)
+
+    def _steps(self):
+        for _ in range(POLL):
+            self.step()
+
+    def capture(self, warmup=1):
+        """Capture POLL steps (after `warmup` eager rounds on the side stream; they advance the state: load() again)."""
+        self.graph = _graphed.LoopGraph(self._steps, self.s["cand"].device, warmup, owners=(self.attack.classifier,))
+
+    def run(self):
+        """Steps until every cloud is latched; the latches come back to the host once per POLL steps. A latched cloud is
+        left alone by the kernel, so a round may run past the end of the tables."""
+        for _ in range((self.L + POLL - 1) // POLL):
+            if self.graph is not None:
+                self.graph.replay()
+            else:
+                self._steps()
+            if bool(self.s["done"].all()):
+                break
+
+
 class PointCloudAttack(object):
     """``PointCloudAttack(args, wb_classifier=None, classifier=None)``: the surrogate and the target are handed in (or
     taken from ``args.wb_classifier`` / ``args.classifier``); args carries eps, step_size, max_steps, num_class,
     top5_attack, defense_method and the attack method (``transfer_attack_method`` or ``query_attack_method``).
     ``run(points [B,N,6], target [B])`` returns (adv_points [B,N,3], adv_target [B], number of misclassified clouds).
-    fused / graph: use the surrogate's fused passes when it has them, and replay the step from a hipGraph."""
+    With a query method, ``run(points [B,N,3 or 6], target [B])`` returns (adv_points [B,N,3], adv_target [B] int64,
+    query_costs [B] int64).
+    fused / graph: use the models' fused passes when they have them, and replay the step from a hipGraph."""
 
     def __init__(self, args, wb_classifier=None, classifier=None, fused=True, graph=True):
         self.args = args
@@ -105,6 +215,9 @@ class PointCloudAttack(object):
             self.pre_head = self.get_defense_head(self.defense_method)
         self.fused, self.graph = fused, graph
         self._loops = {}
+        self._query_loops = {}
+        self.generator = getattr(args, "generator", None)      # simbapp's draws (a torch.Generator on the clouds' device)
+        self.last_query = None                                  # the last query loop's traces (see _query)
 
     def CWLoss(self, logits, target, kappa=0, tar=False, num_classes=40):
         """Carlini & Wagner loss, summed over the batch (SIadv_attack.py:142-164). logits [B,num_classes], target [B]."""
@@ -121,12 +234,15 @@ class PointCloudAttack(object):
         return torch.sum(torch.max(real - other, kappa))
 
     def run(self, points, target):
-        """points [B,N,6] (coordinates and normals), target [B]."""
+        """points [B,N,6] (coordinates and normals; the query attacks use the coordinates only), target [B]."""
         if self.attack_method == 'ifgm_ours':
             return self.shape_invariant_ifgm(points, target)
-        if self.attack_method in QUERY_METHODS:
-            raise NotImplementedError(f"PointCloudAttack: the query attack '{self.attack_method}' is not mirrored "
-                                      "(only the transfer attack 'ifgm_ours' is)")
+        if self.attack_method == 'simba':
+            return self.simba_attack(points, target)
+        if self.attack_method == 'simbapp':
+            return self.simbapp_attack(points, target)
+        if self.attack_method == 'ours':
+            return self.shape_invariant_query_attack(points, target)
         raise NotImplementedError(f"PointCloudAttack: unknown attack method {self.attack_method!r}")
 
     def get_defense_head(self, method):
@@ -280,3 +396,158 @@ class PointCloudAttack(object):
                 in_top5 = (adv_logits.topk(5)[1] == target[:, None]).any(1)
                 adv_target = torch.where(in_top5, target, torch.full_like(target, -1))
         return x.transpose(1, 2).contiguous(), adv_target, (pred != target).sum().item()
+
+    # ------------------------------------------------------------------------------------------------------
+    # the query attacks
+    def _query_prepare(self, points, target, method):
+        """Checks, the coordinates x [B,3,N], the labels, and the initial query: (x, target, logp0, adv_target0)."""
+        if not isinstance(points, torch.Tensor) or not points.is_cuda:
+            raise NotImplementedError(f"PointCloudAttack.{_QUERY_NAMES[method]}: the query attack '{method}' runs on the GPU "
+                                      "only (no CPU fallback)")
+        points = points.detach().float()
+        if points.dim() != 3 or points.shape[2] not in (3, 6):
+            raise ValueError(f"{_QUERY_NAMES[method]}: points must be [B,N,3] or [B,N,6], got {tuple(points.shape)}")
+        if method == "ours" and points.shape[1] < KNN:
+            raise ValueError(f"{_QUERY_NAMES[method]}: N = {points.shape[1]} points, the {KNN}-neighbour normals need N >= {KNN}")
+        x = points[:, :, :3].transpose(1, 2).contiguous()
+        target = target.detach().reshape(-1).long().to(x.device)
+        with torch.no_grad():
+            logp0 = _first(self.classifier(self.pre_head(x) if self.pre_head is not None else x)).float()
+        adv_target0 = logp0.max(1)[1]
+        if self.top5_attack:
+            adv_target0 = self._top5_rule(logp0, target)
+        return x, target, logp0, adv_target0
+
+    @staticmethod
+    def _top5_rule(logits, target):
+        in_top5 = (logits.topk(5)[1] == target[:, None]).any(1)
+        return torch.where(in_top5, target, torch.full_like(target, -1))
+
+    def _wb_grad(self, x, target):
+        """d CWLoss(kappa=-999, tar=True) / dx [B,3,N] of the surrogate at x [B,3,N] (no defence head: the reference hands
+        the surrogate the cloud itself). The loss is max(other - real, -999) per cloud, so its gradient on the
+        log-probabilities is +1 at `other` and -1 at the label — a row that sums to zero, which the log-softmax's backward
+        passes on unchanged: with a fused surrogate the row goes straight into its backward-to-input."""
+        sur = self.wb_classifier
+        if self.fused and isinstance(sur, _pointnet.PointNetCls):
+            with torch.no_grad():
+                logits, ctx = _pointnet.fused_forward(sur, x)
+                masked = torch.log_softmax(logits, dim=1)
+                real = masked.gather(1, target[:, None])[:, 0]
+                masked.scatter_(1, target[:, None], -10000.)
+                if self.top5_attack:
+                    ov, oi = masked.topk(5)
+                    ov, oi = ov[:, 4], oi[:, 4]
+                else:
+                    ov, oi = masked.max(1)
+                g = torch.zeros_like(logits)
+                g.scatter_(1, oi[:, None], 1.0)
+                g.scatter_add_(1, target[:, None], torch.full_like(real, -1.0)[:, None])
+                g = (g * ((ov - real) > -999.)[:, None]).contiguous()
+                return _pointnet.fused_input_grad(ctx, g)
+        P = x.detach().clone().requires_grad_()
+        with torch.enable_grad():
+            loss = self.CWLoss(_first(sur(P)), target, kappa=-999., tar=True, num_classes=self.num_class)
+            if not loss.requires_grad:
+                return torch.zeros_like(x)
+            (g,) = torch.autograd.grad(loss, P)
+        return g.contiguous()
+
+    def _query_fast(self):
+        return bool(self.fused and self.pre_head is None and isinstance(self.classifier, _pointnet.PointNetCls))
+
+    def _query_loop(self, B, N, L, k, dev, frame, table_eps):
+        fast = self._query_fast()
+        if not (fast and self.graph):
+            return _QueryLoop(self, B, N, L, k, dev, frame, table_eps, fast)
+        v = self.classifier
+        wkey = tuple((t.data_ptr(), t._version) for t in list(v.parameters()) + list(v.buffers()))
+        key = (B, N, L, k, dev, frame, table_eps, bool(self.top5_attack), wkey)
+        c = self._query_loops.get(key)
+        if c is None:
+            while len(self._query_loops) >= _MAX_LOOPS:
+                self._query_loops.pop(next(iter(self._query_loops)))
+            c = _QueryLoop(self, B, N, L, k, dev, frame, table_eps, fast)
+            c.capture()                     # on the zeroed buffers (every table entry 0 is in range); load() follows
+            self._query_loops[key] = c
+        return c
+
+    def _query(self, method, x, target, logp0, adv_target0, active, tab, eps, nrm=None, dirs=None):
+        """The loop for prepared tables. tab int32 [B,L], eps float32 [2] or [B,L,2]; active [B] bool: the clouds whose
+        loop runs. self.last_query keeps the traces: accepted [B,L] (0 / 1, -1 neither, -2 not reached), losses [B,L,2],
+        best [B]."""
+        B, _, N = x.shape
+        dev = x.device
+        tab = torch.as_tensor(tab).to(device=dev, dtype=torch.int32).contiguous()
+        eps = torch.as_tensor(eps).to(device=dev, dtype=torch.float32).contiguous()
+        L, frame = tab.shape[1], nrm is not None
+        if tab.shape[0] != B or L < 1:
+            raise ValueError(f"{_QUERY_NAMES[method]}: the table must be [B,L], got {tuple(tab.shape)}")
+        with torch.cuda.device(dev), torch.no_grad():
+            c = self._query_loop(B, N, L, logp0.shape[1], dev, frame, eps.dim() == 3)
+            c.load(x, target, tab, eps, active, adv_target0.to(torch.int32), logp0, nrm, dirs)
+            c.run()
+            s = c.s
+            adv_target = s["adv_target"].long()
+            if bool((adv_target == -2).any()):
+                raise ValueError(f"{_QUERY_NAMES[method]}: a table entry or a label is out of range")
+            if self.top5_attack:                  # on the logits of the last candidate evaluated (:406-411, :599-604)
+                adv_target = torch.where(active, self._top5_rule(s["last_logp"], target), adv_target)
+            out = (s["last"] if frame else s["st"]).transpose(1, 2).contiguous()
+            self.last_query = dict(accepted=s["acc_trace"].clone(), losses=s["loss_trace"].clone(), best=s["best"].clone(),
+                                   table=tab, eps=eps)
+            return out, adv_target, s["queries"].long()
+
+    def simba_attack(self, points, target, table=None):
+        """Black-box query-based SimBA attack, batched. points [B,N,3 or 6], target [B] -> (adv_points [B,N,3],
+        adv_target [B] int64, query_costs [B] int64). table: int32 [B,3N] of 3 * idx + channel in place of the draw."""
+        x, target, logp0, adv_target0 = self._query_prepare(points, target, "simba")
+        active = adv_target0 == target                          # the others return the clean cloud at once
+        if table is None:
+            table = draw_simba_tables(x.shape[2], active.cpu().numpy())
+        eps = torch.tensor(sign_order(self.step_size), dtype=torch.float32)
+        return self._query("simba", x, target, logp0, adv_target0, active, table, eps)
+
+    def simbapp_attack(self, points, target, table=None, generator=None):
+        """Black-box query-based SimBA++ attack, batched (mirrored against its restatement only: the reference's body
+        cannot run). The choices Categorical(|g|).sample() and the amounts eps + 0.1 randn are drawn up front, once per
+        batch, on the device from `generator` (default: self.generator). table: (choices int32 [B,3N], amounts
+        float32 [B,3N,2]) in place of the draw."""
+        x, target, logp0, adv_target0 = self._query_prepare(points, target, "simbapp")
+        active = adv_target0 == target
+        if table is None:
+            B, _, N = x.shape
+            gen = generator if generator is not None else self.generator
+            w = self._wb_grad(x, target).abs().reshape(B, -1)
+            w = torch.where(active[:, None], w, torch.ones_like(w))        # a cloud that returned early draws nothing it uses
+            choice = torch.multinomial(w, 3 * N, replacement=True, generator=gen).to(torch.int32)
+            signs = torch.tensor(sign_order(self.step_size), dtype=torch.float32, device=x.device)
+            table = (choice, signs[None, None, :] + 0.1 * torch.randn((B, 3 * N, 2), generator=gen, dtype=torch.float32,
+                                                                      device=x.device))
+        return self._query("simbapp", x, target, logp0, adv_target0, active, table[0], table[1])
+
+    def query_sensitivity(self, x, target):
+        """The sensitivity map of the shape-invariant query attack for clouds x [B,3,N]: (nrm [B,3,N], order int32 [B,N],
+        dir [B,N,3], key [B,N]). The normals come from the coordinates (get_normal_vector), the gradient is the surrogate's
+        at the clamped cloud U^T P' - t, taken to the frame and ranked by pc3d_si_rank_f32."""
+        normal_vec = self.get_normal_vector(x.transpose(1, 2))
+        normal_vec = normal_vec / torch.sqrt(torch.sum(normal_vec ** 2, dim=-1, keepdim=True))
+        nrm = normal_vec.transpose(1, 2).contiguous()
+        xe = ops.si_frame(x, nrm=nrm)
+        lo, hi = x - self.eps, x + self.eps
+        inside = (xe >= lo) & (xe <= hi)               # the clamp passes the gradient on where it does not bind
+        g = self._wb_grad(torch.min(torch.max(xe, lo), hi), target) * inside
+        key, dirs, order, _ = ops.si_rank(g.contiguous(), nrm)
+        return nrm, order, dirs, key
+
+    def shape_invariant_query_attack(self, points, target, table=None):
+        """Black-box query-based attack on point-cloud sensitivity maps, batched. Returns, as the reference does, the LAST
+        CANDIDATE EVALUATED, accepted or not. table: (nrm [B,3,N], order int32 [B,N], dir [B,N,3]) in place of the
+        sensitivity map."""
+        x, target, logp0, adv_target0 = self._query_prepare(points, target, "ours")
+        active = torch.ones_like(target, dtype=torch.bool)      # no early return (:533-534 is commented out)
+        with torch.no_grad():
+            nrm, order, dirs = table if table is not None else self.query_sensitivity(x, target)[:3]
+        eps = torch.tensor(sign_order(self.step_size), dtype=torch.float32)
+        return self._query("ours", x, target, logp0, adv_target0, active, order,
+                           eps, nrm.float().contiguous(), dirs.float().contiguous())

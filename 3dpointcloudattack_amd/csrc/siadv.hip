@@ -1,5 +1,5 @@
 // The shape-invariant white-box attack (attack/SIadv/SIadv_attack.py of the reference, shape_invariant_ifgm): I-FGM in
-// the tangent frame of every point. Three kernels:
+// the tangent frame of every point. Three kernels (the two of the query attacks, query_step and si_rank, follow them below):
 //   pca_normal  per point, the unit eigenvector of the smallest eigenvalue of the covariance of its K listed neighbours
 //               (the point itself among them) about their own mean — what the reference asks of open3d's
 //               estimate_normals(KDTreeSearchParamKNN(knn=20)) on the host, one cloud at a time, every step;
@@ -221,6 +221,271 @@ __global__ __launch_bounds__(SI_T) void si_step_kernel(SiStepArgs a) {
   }
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The query attacks (simba_attack, simbapp_attack, shape_invariant_query_attack, SIadv_attack.py:343-624): one victim
+// forward of the 2B candidate clouds per step, then query_step — the accept / reject decision of step i for every cloud
+// and the two candidate clouds of step i + 1, one workgroup per cloud. Nothing is reduced across threads except inside a
+// wave: EVERY wave computes both losses of its cloud from the 2 k log-probabilities itself (the same shuffles on the same
+// values: the same bits), so the decision needs no LDS and the one barrier only separates the entry loads of the state
+// words from thread 0's stores to them.
+constexpr int QS_KPL = 4;              // log-probabilities per lane: k <= 256
+
+// CWLoss(kappa = -999, tar = True) of one row held lane-strided in v[] (entry j of lane l: class l + 64 j; beyond k:
+// -inf), as written in the reference: the target's entry is replaced by -10000, `other` is the largest (top = 1) or the
+// fifth largest (top = 5) of the row, the loss max(other - real, -999). pred: the row's arg-max, the lowest index on a tie.
+__device__ __forceinline__ void qs_row_loss(const float* v, int k, int lane, int label, int top, float& loss, int& pred) {
+  float m[QS_KPL];
+  float real = 0.f;
+#pragma unroll
+  for (int j = 0; j < QS_KPL; ++j) {
+    m[j] = v[j];
+    if (lane + 64 * j == label) real = v[j], m[j] = -10000.f;
+  }
+  real = wave_sum(real);               // one lane holds it, the others 0 (x + 0 is x; -0 becomes +0, the same number)
+  float ov = 0.f;
+  for (int r = 0; r <= top; ++r) {     // round 0: the raw row's arg-max (the prediction); rounds 1 .. top: the masked row
+    float bv = -__builtin_inff();
+    int bi = 0x7fffffff;
+#pragma unroll
+    for (int j = 0; j < QS_KPL; ++j) {
+      const float c = r == 0 ? v[j] : m[j];
+      const int ci = lane + 64 * j;
+      if (ci < k && (c > bv || (c == bv && ci < bi))) bv = c, bi = ci;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float c = __shfl_xor(bv, o, 64);
+      const int ci = __shfl_xor(bi, o, 64);
+      if (c > bv || (c == bv && ci < bi)) bv = c, bi = ci;
+    }
+    if (r == 0) {
+      pred = bi == 0x7fffffff ? 0 : bi;
+    } else {
+      ov = bv;
+#pragma unroll
+      for (int j = 0; j < QS_KPL; ++j)
+        if (lane + 64 * j == bi) m[j] = -__builtin_inff();
+    }
+  }
+  const float d = ov - real;
+  loss = d > -999.f ? d : (d == d ? -999.f : d);      // torch.max(d, kappa): NaN stays NaN
+}
+
+struct QueryStepArgs {
+  const float* logp;       // [2B,k]: the victim's output for cand, try 0 then try 1 of every cloud (null with init)
+  const int64_t* label;
+  int k, top;
+  PtsViewMut st;           // the accepted state: the cloud (coordinate mode) or P' (frame mode)
+  PtsView ori, nrm;        // frame mode (nrm.p != null): the clean cloud (t = (P . n) n is taken from it) and the normals
+  const int32_t* tab;      // [B,L]: 3 * point + channel (coordinate mode) or the point (frame mode)
+  int L;
+  const float* dir;        // [B,N,3] (frame mode)
+  const float* eps;        // the amount of try t at entry l of cloud b: eps[b * eps_bs + l * eps_ls + t]
+  int64_t eps_bs, eps_ls;
+  int32_t *pos, *done, *queries, *adv_target, *last_try;
+  float* best;
+  float* last_logp;        // [B,k]: the row of the last try evaluated
+  PtsViewMut cand, last;   // [2B,.]; [B,.] the last candidate evaluated, written when the cloud latches (p may be null)
+  int32_t* acc_trace;      // [B,L] or null: the accepted try of every entry handled (-1: neither)
+  float* loss_trace;       // [B,L,2] or null
+  int N, init;
+};
+
+__global__ __launch_bounds__(1024) void query_step_kernel(QueryStepArgs a) {
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (kWave - 1), T = blockDim.x;
+  const bool frame = a.nrm.p != nullptr;
+  const int E = frame ? a.N : 3 * a.N;                       // table entries are in [0, E)
+  // entry loads, all issued before anything waits: the state words, the label, both rows
+  int pos = a.pos[b];
+  int done = a.done[b];
+  float best = a.best[b];
+  const int label = a.init ? 0 : (int)a.label[b];
+  float v0[QS_KPL], v1[QS_KPL];
+#pragma unroll
+  for (int j = 0; j < QS_KPL; ++j) {
+    const int c = lane + 64 * j;
+    const bool in = !a.init && c < a.k;
+    v0[j] = in ? a.logp[(int64_t)(2 * b) * a.k + c] : -__builtin_inff();
+    v1[j] = in ? a.logp[(int64_t)(2 * b + 1) * a.k + c] : -__builtin_inff();
+  }
+  const bool live = !a.init && !done;
+  const bool pos_ok = (unsigned)pos < (unsigned)a.L;
+  // the entry this step decides and the one after it, with their amounts: one more round trip, together
+  int e_cur = -1, e_nxt = -1;
+  float ec0 = 0.f, ec1 = 0.f, en0 = 0.f, en1 = 0.f;
+  const int pn = a.init ? pos : pos + 1;
+  if (live && pos_ok) {
+    e_cur = a.tab[(int64_t)b * a.L + pos];
+    const float* ep = a.eps + (int64_t)b * a.eps_bs + (int64_t)pos * a.eps_ls;
+    ec0 = ep[0], ec1 = ep[1];
+  }
+  if (!done && (unsigned)pn < (unsigned)a.L) {
+    e_nxt = a.tab[(int64_t)b * a.L + pn];
+    const float* ep = a.eps + (int64_t)b * a.eps_bs + (int64_t)pn * a.eps_ls;
+    en0 = ep[0], en1 = ep[1];
+  }
+  __syncthreads();                                           // every thread has read the state words: thread 0 may store
+  int acc = -1, bad = 0, latched = 0, ltry = 0;
+  if (live) {
+    if (!pos_ok || (unsigned)e_cur >= (unsigned)E || (unsigned)label >= (unsigned)a.k) {
+      bad = 1;
+    } else {
+      float l0, l1;
+      int p0, p1;
+      qs_row_loss(v0, a.k, lane, label, a.top, l0, p0);
+      qs_row_loss(v1, a.k, lane, label, a.top, l1, p1);
+      acc = l0 > best ? 0 : (l1 > best ? 1 : -1);            // strict >; try 1 is only evaluated when try 0 was rejected
+      ltry = acc == 0 ? 0 : 1;
+      if (acc >= 0) best = acc == 0 ? l0 : l1;
+      pos += 1;
+      if (tid == 0) {
+        a.queries[b] += acc == 0 ? 1 : 2;
+        a.last_try[b] = ltry;
+        if (acc >= 0) a.best[b] = best, a.adv_target[b] = acc == 0 ? p0 : p1;
+        a.pos[b] = pos;
+        if (a.acc_trace) a.acc_trace[(int64_t)b * a.L + pos - 1] = acc;
+        if (a.loss_trace) {
+          float* lt = a.loss_trace + ((int64_t)b * a.L + pos - 1) * 2;
+          lt[0] = l0, lt[1] = l1;
+        }
+      }
+      if (tid < kWave) {
+#pragma unroll
+        for (int j = 0; j < QS_KPL; ++j)
+          if (lane + 64 * j < a.k) a.last_logp[(int64_t)b * a.k + lane + 64 * j] = ltry ? v1[j] : v0[j];
+      }
+      if (!(best < 0.f && pos < a.L)) latched = 1;
+    }
+  }
+  // the next entry is checked before any candidate is built from it
+  if (!done && !bad && !latched && (unsigned)e_nxt >= (unsigned)E) bad = 1;
+  if (bad) {
+    latched = 1;
+    if (tid == 0) a.adv_target[b] = -2;
+  }
+  if (latched && tid == 0) a.done[b] = 1;
+  const bool perturb = !done && !latched;
+  const int np_ = perturb ? (frame ? e_nxt : e_nxt / 3) : -1, nc_ = perturb && !frame ? e_nxt % 3 : -1;   // next entry
+  const int ap_ = acc >= 0 ? (frame ? e_cur : e_cur / 3) : -1, ac_ = acc >= 0 && !frame ? e_cur % 3 : -1;  // accepted entry
+  const float ea = acc == 0 ? ec0 : ec1;
+  float* sb = a.st.p + (int64_t)b * a.st.bs;
+  float* c0 = a.cand.p + (int64_t)(2 * b) * a.cand.bs;
+  float* c1 = c0 + a.cand.bs;
+  const bool keep_last = a.last.p && live && !bad && latched;
+  for (int n = tid; n < a.N; n += T) {
+    if (keep_last) {                                         // before this point's candidates are overwritten
+      const float* lc = (ltry ? c1 : c0) + (int64_t)n * a.cand.ps;
+      float* lo = a.last.p + (int64_t)b * a.last.bs + (int64_t)n * a.last.ps;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) lo[c * a.last.cs] = lc[c * a.cand.cs];
+    }
+    float* sp = sb + (int64_t)n * a.st.ps;
+    float o0[3], o1[3];
+    if (!frame) {
+      float s[3];
+      if (a.init || !live) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) s[c] = sp[c * a.st.cs];
+      } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          s[c] = sp[c * a.st.cs];
+          if (n == ap_ && c == ac_) s[c] = s[c] + ea, sp[c * a.st.cs] = s[c];      // points = points + pert
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const bool hit = n == np_ && c == nc_;
+        o0[c] = hit ? s[c] + en0 : s[c];
+        o1[c] = hit ? s[c] + en1 : s[c];
+      }
+    } else {
+      const float* np3 = a.nrm.p + (int64_t)b * a.nrm.bs + (int64_t)n * a.nrm.ps;
+      const float* op = a.ori.p + (int64_t)b * a.ori.bs + (int64_t)n * a.ori.ps;
+      const float nx = np3[0], ny = np3[a.nrm.cs], nz = np3[2 * a.nrm.cs];
+      float u[9], t3[3], r3[3];
+      si_frame(nx, ny, nz, u);
+      si_to_frame(u, op[0], op[a.ori.cs], op[2 * a.ori.cs], nx, ny, nz, t3, r3);
+      if (a.init) {                                          // P' of the clean cloud
+#pragma unroll
+        for (int c = 0; c < 3; ++c) sp[c * a.st.cs] = r3[c];
+      } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) r3[c] = sp[c * a.st.cs];
+        if (n == ap_) {                                      // new_points = new_points + pert, pert = eps * direction
+          const float* dp = a.dir + ((int64_t)b * a.N + n) * 3;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) r3[c] = r3[c] + ea * dp[c], sp[c * a.st.cs] = r3[c];
+        }
+      }
+      float q0[3] = {r3[0], r3[1], r3[2]}, q1[3] = {r3[0], r3[1], r3[2]};
+      if (n == np_) {
+        const float* dp = a.dir + ((int64_t)b * a.N + n) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) q0[c] = r3[c] + en0 * dp[c], q1[c] = r3[c] + en1 * dp[c];
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) o0[c] = si_from_frame(u, q0, t3, c), o1[c] = si_from_frame(u, q1, t3, c);
+    }
+    float* w0 = c0 + (int64_t)n * a.cand.ps;
+    float* w1 = c1 + (int64_t)n * a.cand.ps;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) w0[c * a.cand.cs] = o0[c], w1[c * a.cand.cs] = o1[c];
+  }
+}
+
+// The sensitivity map of shape_invariant_query_attack (:553-563) for one cloud per workgroup: g' = U g with g'_z = 0, the
+// ranking sqrt(g'_x^2 + g'_y^2), the directions g' / (ranking + 1e-16), and the points ordered by (ranking descending,
+// index ascending) — Python's stable sorted(..., reverse=True) — by an ascending bitonic network over P = 2^p >= N
+// 64-bit keys in LDS: the complement of the ranking's bits (a non-negative float orders as its bits do) above the index.
+// All keys are distinct, so the result does not depend on how the network is scheduled. Pads sort to the end.
+constexpr int kRankMaxPoints = 8192;   // 64 KB of keys
+
+struct SiRankArgs {
+  PtsView g, nrm;
+  int N, P;
+  float *gp, *key, *dir;   // [B,N,3] (may be null), [B,N], [B,N,3]
+  int32_t* order;          // [B,N]
+};
+
+__global__ __launch_bounds__(1024) void si_rank_kernel(SiRankArgs a) {
+  extern __shared__ uint64_t rk_keys[];
+  const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
+  for (int n = tid; n < a.P; n += T) {
+    uint64_t kk = ~0ull;
+    if (n < a.N) {
+      const float* gq = a.g.p + (int64_t)b * a.g.bs + (int64_t)n * a.g.ps;
+      const float* nq = a.nrm.p + (int64_t)b * a.nrm.bs + (int64_t)n * a.nrm.ps;
+      const float gx = gq[0], gy = gq[a.g.cs], gz = gq[2 * a.g.cs];           // six independent loads
+      const float nx = nq[0], ny = nq[a.nrm.cs], nz = nq[2 * a.nrm.cs];
+      float u[9], hx, hy;
+      si_frame(nx, ny, nz, u);
+      si_grad(u, gx, gy, gz, hx, hy);
+      const float r = __builtin_sqrtf(hx * hx + hy * hy);
+      const float den = r + 1e-16f;
+      const int64_t o = (int64_t)b * a.N + n;
+      a.key[o] = r;
+      a.dir[o * 3] = hx / den, a.dir[o * 3 + 1] = hy / den, a.dir[o * 3 + 2] = 0.f / den;
+      if (a.gp) a.gp[o * 3] = hx, a.gp[o * 3 + 1] = hy, a.gp[o * 3 + 2] = 0.f;
+      kk = ((uint64_t)(~__builtin_bit_cast(uint32_t, r)) << 32) | (uint32_t)n;
+    }
+    rk_keys[n] = kk;
+  }
+  __syncthreads();
+  for (int k = 2; k <= a.P; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = tid; t < (a.P >> 1); t += T) {
+        const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
+        const uint64_t x = rk_keys[lo], y = rk_keys[hi];
+        const bool up = (lo & k) == 0;
+        if ((x > y) == up) rk_keys[lo] = y, rk_keys[hi] = x;
+      }
+      __syncthreads();
+    }
+  for (int i = tid; i < a.N; i += T) a.order[(int64_t)b * a.N + i] = (int32_t)(rk_keys[i] & 0xffffffffull);
+}
+
 }  // namespace pc3d
 
 using namespace pc3d;
@@ -280,5 +545,52 @@ extern "C" int pc3d_si_step_f32(float* x, int64_t x_bs, int64_t x_ps, int64_t x_
   const size_t lds = lds_stage ? (size_t)3 * N * sizeof(float) : 0;
   hipLaunchKernelGGL(si_step_kernel, dim3((unsigned)B), dim3(SI_T), lds, as_stream(stream), a);
   PC3D_LAUNCH_CHECK("pc3d_si_step_f32");
+  return PC3D_OK;
+}
+
+extern "C" int pc3d_query_step_f32(const float* logp, int k, const int64_t* label, int top,
+                                   float* st, int64_t s_bs, int64_t s_ps, int64_t s_cs,
+                                   const float* ori, int64_t o_bs, int64_t o_ps, int64_t o_cs,
+                                   const float* nrm, int64_t n_bs, int64_t n_ps, int64_t n_cs,
+                                   const int32_t* tab, int L, const float* dir, const float* eps, int64_t eps_bs, int64_t eps_ls,
+                                   int32_t* pos, float* best, int32_t* done, int32_t* queries, int32_t* adv_target,
+                                   int32_t* last_try, float* last_logp,
+                                   float* cand, int64_t c_bs, int64_t c_ps, int64_t c_cs,
+                                   float* last, int64_t l_bs, int64_t l_ps, int64_t l_cs,
+                                   int32_t* acc_trace, float* loss_trace, int B, int N, int init, void* stream) {
+  PC3D_REQUIRE(B >= 0 && N >= 1 && L >= 1, "pc3d_query_step_f32: bad sizes B=%d N=%d L=%d", B, N, L);
+  PC3D_REQUIRE(N <= 0x7fffffff / 3, "pc3d_query_step_f32: N=%d too large for the 3 N table entries", N);
+  PC3D_REQUIRE(top == 1 || top == 5, "pc3d_query_step_f32: top must be 1 or 5, got %d", top);
+  PC3D_REQUIRE(init || (k > top && k <= 64 * QS_KPL), "pc3d_query_step_f32: k=%d classes, need top < k <= %d", k, 64 * QS_KPL);
+  PC3D_REQUIRE((ori != nullptr) == (nrm != nullptr) && (dir != nullptr) == (nrm != nullptr),
+               "pc3d_query_step_f32: the frame mode takes ori, nrm and dir together, the coordinate mode none of them");
+  if (B == 0) return PC3D_OK;
+  PC3D_REQUIRE(st && tab && eps && pos && best && done && cand, "pc3d_query_step_f32: null pointer");
+  PC3D_REQUIRE(init || (logp && label && queries && adv_target && last_try && last_logp), "pc3d_query_step_f32: null pointer");
+  PC3D_REQUIRE(cand != st && cand != ori && cand != nrm && cand != last && st != ori && st != nrm && last != st,
+               "pc3d_query_step_f32: st, cand and last must not alias each other or the inputs");
+  QueryStepArgs a{logp, label, k, top, {st, s_bs, s_ps, s_cs}, {ori, o_bs, o_ps, o_cs}, {nrm, n_bs, n_ps, n_cs}, tab, L, dir,
+                  eps, eps_bs, eps_ls, pos, done, queries, adv_target, last_try, best, last_logp,
+                  {cand, c_bs, c_ps, c_cs}, {last, l_bs, l_ps, l_cs}, acc_trace, loss_trace, N, init ? 1 : 0};
+  const int T = N >= 1024 ? 1024 : cdiv(N, kWave) * kWave;
+  hipLaunchKernelGGL(query_step_kernel, dim3((unsigned)B), dim3(T), 0, as_stream(stream), a);
+  PC3D_LAUNCH_CHECK("pc3d_query_step_f32");
+  return PC3D_OK;
+}
+
+extern "C" int pc3d_si_rank_f32(const float* g, int64_t g_bs, int64_t g_ps, int64_t g_cs,
+                                const float* nrm, int64_t n_bs, int64_t n_ps, int64_t n_cs, int B, int N,
+                                float* gp, float* key, float* dir, int32_t* order, void* stream) {
+  PC3D_REQUIRE(B >= 0 && N >= 1, "pc3d_si_rank_f32: bad sizes B=%d N=%d", B, N);
+  PC3D_REQUIRE(N <= kRankMaxPoints, "pc3d_si_rank_f32: N=%d exceeds the limit of %d points (the keys are sorted in LDS)", N,
+               kRankMaxPoints);
+  if (B == 0) return PC3D_OK;
+  PC3D_REQUIRE(g && nrm && key && dir && order, "pc3d_si_rank_f32: null pointer");
+  int P = 2;
+  while (P < N) P <<= 1;
+  SiRankArgs a{{g, g_bs, g_ps, g_cs}, {nrm, n_bs, n_ps, n_cs}, N, P, gp, key, dir, order};
+  const int T = P / 2 >= 1024 ? 1024 : (P / 2 < kWave ? kWave : P / 2);
+  hipLaunchKernelGGL(si_rank_kernel, dim3((unsigned)B), dim3(T), (size_t)P * sizeof(uint64_t), as_stream(stream), a);
+  PC3D_LAUNCH_CHECK("pc3d_si_rank_f32");
   return PC3D_OK;
 }

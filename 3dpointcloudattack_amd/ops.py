@@ -3143,3 +3143,84 @@ def si_step(x, ori, g, step_size, eps, nrm=None, idx=None, nrm_out=None, cf=True
         _lib.call("pc3d_si_step_f32", xp, xbs, xps, xcs, *views[0], *views[1], *views[2], _ptr(idx), K, B, N, *views[3],
                   float(step_size), float(eps), _stream())
     return x
+
+
+QUERY_STEP_MAX_CLASSES = 256    # pc3d_query_step_f32 keeps a row of log-probabilities in one wave's registers
+SI_RANK_MAX_POINTS = 8192       # pc3d_si_rank_f32 sorts a cloud's keys in LDS
+
+
+def query_step(s, logp=None, init=False):
+    """One step of the SI-Adv query loops for all clouds, one launch (see pc3d_query_step_f32). s: the loop's buffers —
+    st / cand / last [B | 2B | B, 3, N] float32, ori / nrm [B,3,N] and dir [B,N,3] (frame mode) or None, tab int32 [B,L],
+    eps float32 [2] or [B,L,2], label int64 [B], pos / done / queries / adv_target / last_try int32 [B], best float32 [B],
+    last_logp float32 [B,k], acc_trace int32 [B,L] / loss_trace float32 [B,L,2] or None, top (1 or 5). logp [2B,k]: the
+    victim's output for s["cand"]. init: write the first candidates only."""
+    st, cand = s["st"], s["cand"]
+    sp, sbs, sps, scs, B, N = _pts(st, True, "st")
+    cv = _pts(cand, True, "cand")
+    if cv[4:] != (2 * B, N):
+        raise ValueError(f"query_step: cand {tuple(cand.shape)} must be [2B,3,N] = [{2 * B},3,{N}]")
+    views = []
+    for nm in ("ori", "nrm", "last"):
+        t = s.get(nm)
+        if t is None:
+            views.append((0, 0, 0, 0))
+            continue
+        v = _pts(t, True, nm)
+        if v[4:] != (B, N):
+            raise ValueError(f"query_step: {nm} {tuple(t.shape)} must have st's shape {tuple(st.shape)}")
+        views.append(v[:4])
+    tab, eps, dirs = s["tab"], s["eps"], s.get("dir")
+    if tab.dtype != torch.int32 or not tab.is_cuda or not tab.is_contiguous() or tab.dim() != 2 or tab.shape[0] != B:
+        raise ValueError("query_step: tab must be a contiguous int32 [B,L] GPU tensor")
+    L = tab.shape[1]
+    _check(eps, "eps")
+    if not eps.is_contiguous() or tuple(eps.shape) not in ((2,), (B, L, 2)):
+        raise ValueError(f"query_step: eps must be float32 [2] or [B,L,2], got {tuple(eps.shape)}")
+    ebs, els = (0, 0) if eps.dim() == 1 else (L * 2, 2)
+    if dirs is not None:
+        _check(dirs, "dir")
+        if tuple(dirs.shape) != (B, N, 3) or not dirs.is_contiguous():
+            raise ValueError(f"query_step: dir must be a contiguous [B,N,3] tensor, got {tuple(dirs.shape)}")
+    k = s["last_logp"].shape[1]
+    if not init:
+        _check(logp, "logp")
+        if tuple(logp.shape) != (2 * B, k) or not logp.is_contiguous():
+            raise ValueError(f"query_step: logp must be a contiguous [{2 * B},{k}] tensor, got {tuple(logp.shape)}")
+    words = {"pos": torch.int32, "best": torch.float32, "done": torch.int32, "queries": torch.int32, "adv_target": torch.int32,
+             "last_try": torch.int32, "label": torch.int64}
+    for nm, dt in words.items():
+        t = s[nm]
+        if t.dtype != dt or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (B,):
+            raise ValueError(f"query_step: {nm} must be a contiguous {dt} [B] GPU tensor")
+    _check(s["last_logp"], "last_logp")
+    acc, los = s.get("acc_trace"), s.get("loss_trace")
+    if acc is not None and (acc.dtype != torch.int32 or tuple(acc.shape) != (B, L) or not acc.is_contiguous() or not acc.is_cuda):
+        raise ValueError("query_step: acc_trace must be a contiguous int32 [B,L] GPU tensor")
+    if los is not None and (los.dtype != torch.float32 or tuple(los.shape) != (B, L, 2) or not los.is_contiguous() or not los.is_cuda):
+        raise ValueError("query_step: loss_trace must be a contiguous float32 [B,L,2] GPU tensor")
+    with torch.cuda.device(st.device):
+        _lib.call("pc3d_query_step_f32", _ptr(None if init else logp), k, s["label"].data_ptr(), int(s["top"]),
+                  sp, sbs, sps, scs, *views[0], *views[1], tab.data_ptr(), L, _ptr(dirs), eps.data_ptr(), ebs, els,
+                  s["pos"].data_ptr(), s["best"].data_ptr(), s["done"].data_ptr(), s["queries"].data_ptr(),
+                  s["adv_target"].data_ptr(), s["last_try"].data_ptr(), s["last_logp"].data_ptr(), *cv[:4], *views[2],
+                  _ptr(acc), _ptr(los), B, N, 1 if init else 0, _stream())
+
+
+def si_rank(g, nrm, cf=True, want_gp=False):
+    """The sensitivity map of the shape-invariant query attack, one launch (pc3d_si_rank_f32): from the surrogate's
+    gradient g and the normals nrm ([B,3,N]; [B,N,3] with cf=False) -> (key [B,N], dir [B,N,3], order int32 [B,N] by key
+    descending and index ascending, gp [B,N,3] or None)."""
+    gp_, gbs, gps, gcs, B, N = _pts(g, cf, "g")
+    nv = _pts(nrm, cf, "nrm")
+    if nv[4:] != (B, N):
+        raise ValueError(f"si_rank: nrm {tuple(nrm.shape)} must have g's shape {tuple(g.shape)}")
+    dev = g.device
+    key = torch.empty((B, N), dtype=torch.float32, device=dev)
+    dirs = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
+    order = torch.empty((B, N), dtype=torch.int32, device=dev)
+    gp = torch.empty((B, N, 3), dtype=torch.float32, device=dev) if want_gp else None
+    with torch.cuda.device(dev):
+        _lib.call("pc3d_si_rank_f32", gp_, gbs, gps, gcs, *nv[:4], B, N, _ptr(gp), key.data_ptr(), dirs.data_ptr(),
+                  order.data_ptr(), _stream())
+    return key, dirs, order, gp

@@ -1053,6 +1053,47 @@ int pc3d_si_step_f32(float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs,
                      float* nrm_out, int64_t no_bs, int64_t no_ps, int64_t no_cs,
                      double step_size, double eps, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * SI-Adv's query attacks (simba_attack, simbapp_attack, shape_invariant_query_attack, SIadv_attack.py:343-624) as one
+ * batched loop: per step one victim forward of the 2B candidate clouds and one launch of pc3d_query_step_f32.
+ * ------------------------------------------------------------------------------------------------------- */
+/* Decides entry pos[b] of every cloud's table from logp [2B,k] (the victim's log-probabilities for cand: rows 2b and
+ * 2b + 1 are the two tries of cloud b) and writes the two candidate clouds of the next entry into cand [2B,.]. One
+ * workgroup per cloud, fixed order, no atomics. Per cloud that is not done:
+ *   loss_t  = max(other - real, -999) with real = logp[label] and other the largest (top = 1) or fifth largest (top = 5)
+ *             entry of the row after the label's entry is replaced by -10000 (CWLoss, kappa = -999, tar = True);
+ *   try 0 is accepted when loss_0 > best (strict), otherwise try 1 when loss_1 > best; queries += 1 or 2;
+ *   accepted: the one-entry change goes into the state st, best = the loss, adv_target = the row's arg-max (lowest index
+ *             on a tie); last_try / last_logp = the last try evaluated and its row;
+ *   pos += 1; done = !(best < 0 && pos < L).
+ * Coordinate mode (ori, nrm, dir NULL): st is the cloud, table entry e in [0, 3N) stands for coordinate e % 3 of point
+ * e / 3, candidate t = st with eps_t added there. Frame mode: st is P' = U (ori + t), entry e in [0, N) is a point,
+ * candidate t = U^T (P' + eps_t * dir[b, e] at that point) - t for the WHOLE cloud, U and t = (ori . n) n from nrm as
+ * pc3d_si_step_f32 forms them. eps_t of entry l of cloud b is eps[b * eps_bs + l * eps_ls + t] (strides 0: two constants).
+ * A cloud that is done changes nothing and gets unperturbed candidates. init != 0: nothing is decided (logp may be NULL);
+ * the candidates of entry pos[b] are written, and in frame mode st = P' of ori first. last (may be NULL) receives, when
+ * the cloud latches, the last candidate cloud evaluated. acc_trace [B,L] / loss_trace [B,L,2] (may be NULL) receive the
+ * accepted try (-1: neither) and both losses of every entry decided. A table entry, a position or a label out of range
+ * is never used as an index: the cloud is latched done with adv_target = -2. k <= 256. */
+int pc3d_query_step_f32(const float* logp, int k, const int64_t* label, int top,
+                        float* st, int64_t s_bs, int64_t s_ps, int64_t s_cs,
+                        const float* ori, int64_t o_bs, int64_t o_ps, int64_t o_cs,
+                        const float* nrm, int64_t n_bs, int64_t n_ps, int64_t n_cs,
+                        const int32_t* tab, int L, const float* dir, const float* eps, int64_t eps_bs, int64_t eps_ls,
+                        int32_t* pos, float* best, int32_t* done, int32_t* queries, int32_t* adv_target,
+                        int32_t* last_try, float* last_logp,
+                        float* cand, int64_t c_bs, int64_t c_ps, int64_t c_cs,
+                        float* last, int64_t l_bs, int64_t l_ps, int64_t l_cs,
+                        int32_t* acc_trace, float* loss_trace, int B, int N, int init, void* stream);
+/* The sensitivity map of shape_invariant_query_attack (:553-563), one launch: per point g' = U g (g = the surrogate's
+ * gradient at the cloud pc3d_si_frame_f32 shows it, U from nrm) with g'_z = 0 -> gp [B,N,3] (may be NULL), the ranking
+ * key = sqrt(g'_x^2 + g'_y^2) [B,N], dir = g' / (key + 1e-16) [B,N,3] (a zero gradient gives zeros), and order [B,N]: the
+ * points by (key descending, index ascending), which is Python's stable sorted(..., reverse=True). In-LDS bitonic
+ * network over the next power of two; N <= 8192. */
+int pc3d_si_rank_f32(const float* g, int64_t g_bs, int64_t g_ps, int64_t g_cs,
+                     const float* nrm, int64_t n_bs, int64_t n_ps, int64_t n_cs, int B, int N,
+                     float* gp, float* key, float* dir, int32_t* order, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
