@@ -262,7 +262,7 @@ class CW:
         if dk:
             # launch-minimal passes: victim fwd/bwd (fused heads), bookkeeping, [NN search], one update launch
             if (self.riders and "adam" in st and hasattr(self.model, "fused_attack_update")
-                    and st["K"] <= ops.CW_UPDATE_MAX_POINTS):
+                    and getattr(self.model, "has_fused_attack_update", True) and st["K"] <= ops.CW_UPDATE_MAX_POINTS):
                 return self._pass_riders(st, fml, dk)
             if hasattr(self.model, "fused_attack_grad") and st["K"] <= ops.CW_UPDATE_MAX_POINTS:
                 return self._pass_fused_update(st, fml, dk)

@@ -6,7 +6,11 @@ The attack path runs the victim in eval mode with frozen weights (attack/CW/CW_a
 weights once, and each tower (3 -> 64 -> 128 -> 1024 + max over points) is ONE fused HIP launch pair
 (``pc3d_pointmlp3_max_{fwd,bwd}_f32``, fp32 MFMA) that never writes the [B,C,N] activations.
 
-Reference: STN3d model/pointnet.py:14-48, PointNetfeat :89-128, PointNetCls :130-148.
+``feature_transform=True`` adds STNkd (the 64 x 64 feature transform). Its tower and the trunk then run on the
+``pc3d_pointnet_ft_*`` kernels: the transform is folded into the trunk's layer-2 weight per cloud instead of being
+applied to every point. The ``feature_transform=False`` path launches exactly what it did before.
+
+Reference: STN3d model/pointnet.py:14-48, STNkd :51-87, PointNetfeat :89-128, PointNetCls :130-148.
 """
 
 import torch
@@ -105,18 +109,62 @@ class STN3d(_FrozenFusedMixin, nn.Module):
         iden = torch.eye(3, dtype=torch.float32, device=self.fc3.weight.device).reshape(1, 9)
         return tower, head, iden
 
-    def forward(self, x):
+    def forward(self, x, blocked_bwd=False):
         self._require_fused(x)
         tower, head, iden = self.folded()
-        g = ops.pointmlp3_max(x, tower, True)                 # relu(bn3(conv3)) then max == max then relu
+        g = ops.pointmlp3_max(x, tower, True, blocked_bwd)    # relu(bn3(conv3)) then max == max then relu
         g = ops.linear_act(g, *head[0], "relu")
         g = ops.linear_act(g, *head[1], "relu")
         g = ops.linear_act(g, *head[2]) + iden
         return g.view(-1, 3, 3)
 
 
+class STNkd(_FrozenFusedMixin, nn.Module):
+    """Feature transform net (model/pointnet.py:51-87). It has no forward of its own here: its tower recomputes the
+    trunk's first layer from the points, so it only runs inside PointNetfeat (ops.pointnet_ft_feat_fwd)."""
+
+    def __init__(self, k=64):
+        super(STNkd, self).__init__()
+        if k != 64:
+            raise NotImplementedError("STNkd: only k=64 (the PointNetfeat feature transform) is implemented on MI355X")
+        self.conv1 = torch.nn.Conv1d(k, 64, 1)
+        self.conv2 = torch.nn.Conv1d(64, 128, 1)
+        self.conv3 = torch.nn.Conv1d(128, 1024, 1)
+        self.fc1 = nn.Linear(1024, 512)
+        self.fc2 = nn.Linear(512, 256)
+        self.fc3 = nn.Linear(256, k * k)
+        self.relu = nn.ReLU()
+
+        self.bn1 = nn.BatchNorm1d(64)
+        self.bn2 = nn.BatchNorm1d(128)
+        self.bn3 = nn.BatchNorm1d(1024)
+        self.bn4 = nn.BatchNorm1d(512)
+        self.bn5 = nn.BatchNorm1d(256)
+
+        self.k = k
+        self._folded_cache = None
+
+    def _fold(self):
+        WA, bA = _fold_bn(self.conv1.weight, self.conv1.bias, self.bn1)
+        W2, b2 = _fold_bn(self.conv2.weight, self.conv2.bias, self.bn2)
+        W3, b3 = _fold_bn(self.conv3.weight, self.conv3.bias, self.bn3)
+        w1, b1 = _fold_bn(self.fc1.weight, self.fc1.bias, self.bn4)
+        w2, b2h = _fold_bn(self.fc2.weight, self.fc2.bias, self.bn5)
+        w3, b3h = _plain(self.fc3.weight, self.fc3.bias)
+        iden = torch.eye(self.k, dtype=torch.float32, device=w3.device).reshape(-1)
+        return dict(WA=WA, bA=bA, W2=W2, b2=b2, W3=W3, b3=b3,
+                    head=((w1, b1), (w2, b2h), (w3, (b3h + iden).contiguous())),    # + identity (:82-86)
+                    head_t=(_t(w1), _t(w2), _t(w3)))
+
+    def forward(self, x):
+        raise NotImplementedError("STNkd runs inside PointNetfeat(feature_transform=True) only: its fused tower starts "
+                                  "from the points, not from a [B,64,N] activation")
+
+
 class PointNetfeat(_FrozenFusedMixin, nn.Module):
-    """Global feature trunk (model/pointnet.py:89-128), global_feat=True / feature_transform=False path."""
+    """Global feature trunk (model/pointnet.py:89-128), global_feat=True. With feature_transform=True, forward returns
+    trans_feat [B,64,64] DETACHED: the gradient that reaches x through the transform's use inside the trunk is
+    complete, but a loss term on the returned trans_feat itself (the training regulariser) gets no gradient."""
 
     def __init__(self, global_feat=True, feature_transform=False):
         super(PointNetfeat, self).__init__()
@@ -129,10 +177,12 @@ class PointNetfeat(_FrozenFusedMixin, nn.Module):
         self.bn3 = nn.BatchNorm1d(1024)
         self.global_feat = global_feat
         self.feature_transform = feature_transform
-        if self.feature_transform or not self.global_feat:
+        if not self.global_feat:
             raise NotImplementedError(
-                "PointNetfeat: feature_transform=True / global_feat=False are not on the attack path "
-                "(every attack driver builds PointNetCls(k, feature_transform=False): attack/CW/Eval_CW.py:97)")
+                "PointNetfeat: global_feat=False (the PointNetDenseCls segmentation trunk) is not on the attack path "
+                "(every attack driver builds PointNetCls: attack/CW/Eval_CW.py:97)")
+        if self.feature_transform:
+            self.fstn = STNkd(k=64)
         self._folded_cache = None
 
     def _fold(self):
@@ -143,19 +193,25 @@ class PointNetfeat(_FrozenFusedMixin, nn.Module):
 
     def forward(self, x):
         self._require_fused(x)
-        trans = self.stn(x)
+        trans = self.stn(x, blocked_bwd=self.feature_transform)
+        if self.feature_transform:
+            g, trans_feat = ops.pointnet_ft_feat(x, trans, self.folded(), self.fstn.folded())
+            return g, trans, trans_feat
         xt = torch.bmm(x.transpose(2, 1), trans).transpose(2, 1)   # [B,3,N] strided view; kernel takes strides
         g = ops.pointmlp3_max(xt, self.folded(), False)            # bn3(conv3) has no ReLU (:121)
         return g, trans, None
 
 
 class PointNetCls(_FrozenFusedMixin, nn.Module):
-    """model/pointnet.py:130-148 — returns (log_softmax logits [B,k], trans [B,3,3], trans_feat None)."""
+    """model/pointnet.py:130-148 — returns (log_softmax logits [B,k], trans [B,3,3], trans_feat): None, or with
+    feature_transform=True the [B,64,64] feature transform, detached (see PointNetfeat)."""
     deterministic_forward = True   # forward is a pure function of its input (no RNG): attack loops may share it
 
     def __init__(self, k=2, feature_transform=False):
         super(PointNetCls, self).__init__()
         self.feature_transform = feature_transform
+        # the 15-launch riders iteration exists for the two-tower victim only; attack loops ask the instance
+        self.has_fused_attack_update = not feature_transform
         self.feat = PointNetfeat(global_feat=True, feature_transform=feature_transform)
         self.fc1 = nn.Linear(1024, 512)
         self.fc2 = nn.Linear(512, 256)
@@ -201,6 +257,9 @@ class PointNetCls(_FrozenFusedMixin, nn.Module):
         bestdist, bestscore, o_bestdist, o_bestscore, o_bestattack, input_val, dist_val, m, v, w, adam (float32 [2]), lr,
         budget, dist_kind. ride_search / epilogue = False give that piece its own launch again (A/B switches). Returns pred."""
         self._require_fused(x)
+        if self.feature_transform:
+            raise NotImplementedError("PointNetCls.fused_attack_update: the riders iteration is not built for a "
+                                      "feature-transform victim (has_fused_attack_update is False); use fused_attack_grad")
         pk = fused_pack(self)
         w1s, b1s, w2s, b2s, w3s, b3s = pk["s"]
         w1c, b1c, w2c, b2c, w3c, b3c = pk["c"]
@@ -254,7 +313,8 @@ def _t(w):
 
 
 def _fused_sources(model):
-    return model.feat.stn.folded(), model.feat.folded(), model.folded()
+    src = model.feat.stn.folded(), model.feat.folded(), model.folded()
+    return src + (model.feat.fstn.folded(),) if model.feature_transform else src
 
 
 def fused_pack(model):
@@ -271,12 +331,12 @@ def _fused_pack(model):
     """Everything the launch-minimal path needs, built once from the folded weights: heads as (W, b) plus the
     transposed copies the backward launches read (weights are frozen, so W^T is a constant)."""
     src = _fused_sources(model)
-    (tower_s, head_s, iden), tower_c, head_c = src
+    (tower_s, head_s, iden), tower_c, head_c = src[:3]
     (w1s, b1s), (w2s, b2s), (w3s, b3s) = head_s
     (w1c, b1c), (w2c, b2c), (w3c, b3c) = head_c
     w3s_t = torch.zeros((w3s.shape[1], 16), dtype=torch.float32, device=w3s.device)   # [256,16], 9 used
     w3s_t[:, :9] = w3s.t()
-    return dict(src=src, tower_s=tower_s, tower_c=tower_c,
+    return dict(src=src, tower_s=tower_s, tower_c=tower_c, fstn=src[3] if len(src) > 3 else None,
                 s=(w1s, b1s, w2s, b2s, w3s, (b3s + iden.view(-1)).contiguous()),
                 c=(w1c, b1c, w2c, b2c, w3c, b3c),
                 s_t=(_t(w1s), _t(w2s), w3s_t.contiguous()), c_t=(_t(w1c), _t(w2c), _t(w3c)))
@@ -284,7 +344,8 @@ def _fused_pack(model):
 
 def fused_forward(model, x, tail=True):
     """Launch-minimal forward of PointNetCls: 2 tower launches (+2 folds) + 5 head launches, no autograd graph.
-    Returns (logits [B,k] PRE-softmax, ctx) — ctx feeds fused_input_grad."""
+    Returns (logits [B,k] PRE-softmax, ctx) — ctx feeds fused_input_grad.
+    A feature-transform victim: 3 tower launches (+3 folds), the W2 fold, 9 head launches; ctx has a 13th item."""
     model._require_fused(x)
     pk = fused_pack(model)
     w1s, b1s, w2s, b2s, w3s, b3s = pk["s"]
@@ -292,28 +353,42 @@ def fused_forward(model, x, tail=True):
     pooled_s, idx_s, masks_s = ops.pointmlp3_max_fwd_raw(x, pk["tower_s"], True, want_masks=True)
     a1 = ops.linear(pooled_s, w1s, b1s, relu=True)
     a2 = ops.linear(a1, w2s, b2s, relu=True)
-    # the transform (STN fc3 + identity, [B,9]) is computed in the trunk tower's prologue: no launch of its own
-    pooled, idx, masks, trans = ops.pointmlp3_max_fwd_raw(x, pk["tower_c"], False, want_masks=True, T_head=(a2, w3s, b3s))
+    ft = None
+    if pk["fstn"] is not None:
+        trans = ops.linear(a2, w3s, b3s)             # two towers read the transform: it gets a launch of its own
+        pooled, _, ft = ops.pointnet_ft_feat_fwd(x, trans, pk["tower_c"], pk["fstn"])
+        idx = masks = None
+    else:
+        # the transform (STN fc3 + identity, [B,9]) is computed in the trunk tower's prologue: no launch of its own
+        pooled, idx, masks, trans = ops.pointmlp3_max_fwd_raw(x, pk["tower_c"], False, want_masks=True, T_head=(a2, w3s, b3s))
     c1 = ops.linear(pooled, w1c, b1c, relu=True)
     c2 = ops.linear(c1, w2c, b2c, relu=True)
     logits = ops.linear(c2, w3c, b3c) if tail else None
-    return logits, (x, pk, pooled_s, idx_s, a1, a2, trans, idx, c1, c2, masks_s, masks)
+    ctx = (x, pk, pooled_s, idx_s, a1, a2, trans, idx, c1, c2, masks_s, masks)
+    return logits, ctx if ft is None else ctx + (ft,)
 
 
 def fused_input_grad(ctx, g_logits, out=None, g_c2=None):
     """Backward-to-input of fused_forward for an upstream gradient on the logits: 5 head launches + 2 tower launches."""
-    x, pk, pooled_s, idx_s, a1, a2, trans, idx, c1, c2, masks_s, masks = ctx
+    x, pk, pooled_s, idx_s, a1, a2, trans, idx, c1, c2, masks_s, masks = ctx[:12]
     w1c_t, w2c_t, w3c_t = pk["c_t"]
     w1s_t, w2s_t, w3s_t = pk["s_t"]
     if g_c2 is None:
         g_c2 = ops.linear(g_logits, w3c_t, gate=c2)
     g_c1 = ops.linear(g_c2, w2c_t, gate=c1)
     g_pooled = ops.linear(g_c1, w1c_t)
-    gx, part_gT = ops.pointmlp3_max_bwd_raw(x, pk["tower_c"], idx, g_pooled, masks, T=trans, want_gT=True, out=out)
+    if len(ctx) > 12:   # feature transform: trunk, dL/dTf, STNkd head and tower; both towers' dL/dT partials in part_gT
+        gx, part_gT = ops.pointnet_ft_feat_bwd(ctx[12], g_pooled, out=out)
+    else:
+        gx, part_gT = ops.pointmlp3_max_bwd_raw(x, pk["tower_c"], idx, g_pooled, masks, T=trans, want_gT=True, out=out)
     # fc3's backward (dL/dT partials summed, 9 -> 256, ReLU mask of a2) runs inside the launch of fc2's backward
     g_a1 = ops.linear_pre(part_gT, 9, pk["s"][4], a2, w2s_t, gate=a1)
     g_pooled_s = ops.linear(g_a1, w1s_t, gate=pooled_s)                 # ReLU after the STN max-pool
-    ops.pointmlp3_max_bwd_raw(x, pk["tower_s"], idx_s, g_pooled_s, masks_s, out=gx, accumulate=True)
+    if len(ctx) > 12:   # all three towers of this victim sum a point's channels in blocks (DESIGN §8.7)
+        ts = pk["tower_s"]
+        ops.pointnet_ft_tower_bwd_raw(x, None, ts[0], ts[2], ts[4], idx_s, g_pooled_s, masks_s, None, 0, out=gx, accumulate=True)
+    else:
+        ops.pointmlp3_max_bwd_raw(x, pk["tower_s"], idx_s, g_pooled_s, masks_s, out=gx, accumulate=True)
     return gx
 
 

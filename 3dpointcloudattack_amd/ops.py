@@ -477,11 +477,11 @@ class _PointMLP3MaxFn(torch.autograd.Function):
     """x [B,3,N] -> pooled [B,C3] through the fused tower; differentiable in x only (frozen weights)."""
 
     @staticmethod
-    def forward(ctx, x, relu_last, W1, b1, W2, b2, W3, b3, W2T):
+    def forward(ctx, x, relu_last, W1, b1, W2, b2, W3, b3, W2T, blocked_bwd=False):
         weights = (W1, b1, W2, b2, W3, b3, W2T)
         pooled, argidx, masks = pointmlp3_max_fwd_raw(x, weights, relu_last, want_masks=True)
         ctx.save_for_backward(x, argidx, pooled, masks[0], masks[1], *weights)
-        ctx.relu_last = relu_last
+        ctx.relu_last, ctx.blocked_bwd = relu_last, blocked_bwd
         return pooled
 
     @staticmethod
@@ -489,15 +489,188 @@ class _PointMLP3MaxFn(torch.autograd.Function):
         x, argidx, pooled, m1, m2, *weights = ctx.saved_tensors
         if ctx.relu_last:
             g = g * (pooled > 0)
-        gx = pointmlp3_max_bwd_raw(x, tuple(weights), argidx, g, (m1, m2))
-        return (gx,) + (None,) * 8
+        if ctx.blocked_bwd:
+            gx = pointnet_ft_tower_bwd_raw(x, None, weights[0], weights[2], weights[4], argidx, g, (m1, m2), None, 0)[0]
+        else:
+            gx = pointmlp3_max_bwd_raw(x, tuple(weights), argidx, g, (m1, m2))
+        return (gx,) + (None,) * 9
 
 
-def pointmlp3_max(x, weights, relu_last):
-    """weights: (W1,b1,W2,b2,W3,b3[,W2T]) with eval-BN folded; W2T is derived when absent."""
+def pointmlp3_max(x, weights, relu_last, blocked_bwd=False):
+    """weights: (W1,b1,W2,b2,W3,b3[,W2T]) with eval-BN folded; W2T is derived when absent. blocked_bwd: the backward
+    runs on pointnet_ft_tower_bwd_raw's plain form (a point's channels summed in blocks: the feature-transform victim)."""
     if len(weights) == 6:
         weights = tuple(weights) + (weights[2].t().contiguous(),)
-    return _PointMLP3MaxFn.apply(x, relu_last, *weights)
+    return _PointMLP3MaxFn.apply(x, relu_last, *weights, blocked_bwd)
+
+
+# ------------------------------------------------------------------------------------------------------
+# K8-FT: the towers of a PointNet with the feature transform (csrc/pointmlp_ft.hip)
+# ------------------------------------------------------------------------------------------------------
+def _ft_T(T, B):
+    _check(T, "T")
+    if T.numel() != B * 9 or not T.is_contiguous():
+        raise ValueError("pointnet_ft: T must be a contiguous [B,3,3] (or [B,9]) tensor")
+    return T
+
+
+def pointnet_ft_fold_w2(W2, Tf):
+    """W2_b = W2 @ Tf_b^T per cloud: W2 [128,64], Tf [B,64,64] (or [B,4096]) -> [B,128,64]. With it the trunk's layer 2
+    consumes h directly: W2 (Tf^T h) = (W2 Tf^T) h."""
+    _check(W2, "W2"), _check(Tf, "Tf")
+    B = Tf.shape[0]
+    if W2.shape != (128, 64) or Tf.numel() != B * 4096 or not (W2.is_contiguous() and Tf.is_contiguous()):
+        raise ValueError("pointnet_ft_fold_w2: W2 [128,64] and Tf [B,64,64], both contiguous, expected")
+    out = torch.empty((B, 128, 64), dtype=torch.float32, device=Tf.device)
+    with torch.cuda.device(Tf.device):
+        _lib.call("pc3d_pointnet_ft_fold_w2_f32", W2.data_ptr(), Tf.data_ptr(), B, out.data_ptr(), _stream())
+    return out
+
+
+def pointnet_ft_tower_fwd_raw(x, T, W1, b1, W2, b2, W3, b3, relu_last, extra=None, x_cf=True):
+    """One tower of a feature-transform PointNet on x' = x @ T: (pooled [B,C3], argidx [B,C3], masks).
+    extra = (WA [64,64], bA): STNkd's tower 3 -> 64 -> 64 -> 128 -> C3 (W1, b1 are the trunk's layer 1);
+    extra None: the trunk 3 -> 64 -> 128 -> C3. W2 is [128,64] or per cloud [B,128,64] (pointnet_ft_fold_w2).
+    masks = (mask1 [B,N] i64, mask2 [B,N,4] i32, maskA [B,N] i64 or None) feeds pointnet_ft_tower_bwd_raw."""
+    xp, xbs, xps, xcs, B, N = _pts(x, x_cf, "x")
+    T = _ft_T(T, B)
+    ws = (W1, b1, W2, b2, W3, b3) + (tuple(extra) if extra is not None else ())
+    for w in ws:
+        _check(w, "weight")
+        if not w.is_contiguous():
+            raise ValueError("pointnet_ft weights must be contiguous")
+    C3 = W3.shape[0]
+    if W1.shape != (64, 3) or W2.shape[-2:] != (128, 64) or W3.shape[1] != 128 or (W2.dim() == 3 and W2.shape[0] != B) \
+            or (extra is not None and extra[0].shape != (64, 64)):
+        raise ValueError("pointnet_ft_tower_fwd_raw: widths 3 -> 64 [-> 64] -> 128 -> C3 expected")
+    ntiles = (N + _pm_tile() - 1) // _pm_tile()
+    dev = x.device
+    part_val = torch.empty((B, ntiles, C3), dtype=torch.float32, device=dev)
+    part_idx = torch.empty((B, ntiles, C3), dtype=torch.int32, device=dev)
+    m1 = torch.empty((B, N), dtype=torch.int64, device=dev)
+    m2 = torch.empty((B, N, 4), dtype=torch.int32, device=dev)
+    mA = torch.empty((B, N), dtype=torch.int64, device=dev) if extra is not None else None
+    with torch.cuda.device(dev):
+        _lib.call("pc3d_pointnet_ft_tower_fwd_f32", xp, xbs, xps, xcs, B, N, T.data_ptr(), W1.data_ptr(), b1.data_ptr(),
+                  _ptr(extra[0]) if extra is not None else 0, _ptr(extra[1]) if extra is not None else 0,
+                  W2.data_ptr(), 128 * 64 if W2.dim() == 3 else 0, b2.data_ptr(), W3.data_ptr(), b3.data_ptr(), C3,
+                  part_val.data_ptr(), part_idx.data_ptr(), m1.data_ptr(), _ptr(mA), m2.data_ptr(), _stream())
+    pooled, argidx = pointmlp3_fold_raw(part_val, part_idx, relu_last)
+    return pooled, argidx, (m1, m2, mA)
+
+
+def pointnet_ft_gT_workspace(B, N, device, towers=2):
+    """The dL/dT partials of `towers` backward launches side by side: [B, towers * ntiles, 16]; tower t writes its rows
+    at gT_off = t * ntiles, and linear_pre sums them all."""
+    bt = _lib.load().pc3d_pointmlp3_bwd_tile_points()
+    nt = (N + bt - 1) // bt
+    return torch.empty((B, towers * nt, 16), dtype=torch.float32, device=device), nt
+
+
+def pointnet_ft_tower_bwd_raw(x, T, W1, W2, W3, argidx, g_pooled, masks, part_gT, gT_off, WA=None, W2q=None, out=None,
+                              accumulate=False, x_cf=True):
+    """Gradient w.r.t. the raw points of pointnet_ft_tower_fwd_raw (same x, T, masks). WA given: the STNkd tower.
+    W2q given: the trunk, W2 = the folded per-cloud weight, W2q = the unfolded W2; also returns q [B,N,64]
+    (q[b,n] = g_z2[b,n] @ W2), the operand of pointnet_ft_dtf_raw. Neither: a plain 3 -> 64 -> 128 -> C3 tower.
+    The per-tile dL/dT partials go to rows [gT_off, gT_off + ntiles) of part_gT (pointnet_ft_gT_workspace).
+    T None (then part_gT None too): a tower on the raw points, e.g. STN3d's with the (mask1, mask2) of
+    pointmlp3_max_fwd_raw — the same gradient as pointmlp3_max_bwd_raw, with a point's channels summed in blocks of 32
+    instead of one chain. Returns (gx, q or None)."""
+    xp, xbs, xps, xcs, B, N = _pts(x, x_cf, "x")
+    if T is not None:
+        T = _ft_T(T, B)
+    _check(g_pooled, "g_pooled")
+    g_pooled = g_pooled.contiguous()
+    m1, m2 = masks[:2]
+    mA = masks[2] if len(masks) > 2 else None
+    if (WA is not None and W2q is not None) or (WA is not None and mA is None) or ((T is None) != (part_gT is None)):
+        raise ValueError("pointnet_ft_tower_bwd_raw: WA (with the forward's maskA) or W2q, not both; T and part_gT go together")
+    if m1.shape != (B, N) or m2.shape != (B, N, 4) or W2.shape[-2:] != (128, 64) or (W2.dim() == 3 and W2.shape[0] != B) \
+            or (part_gT is not None and (part_gT.dim() != 3 or part_gT.shape[0] != B or part_gT.shape[2] != 16
+                                         or not part_gT.is_contiguous())):
+        raise ValueError("pointnet_ft_tower_bwd_raw: masks / W2 / part_gT do not match x")
+    C3 = W3.shape[0]
+    gx = out if out is not None else torch.empty((B, 3, N) if x_cf else (B, N, 3), dtype=torch.float32, device=x.device)
+    gp, gbs, gps, gcs, _, _ = _pts(gx, x_cf, "grad_x")
+    q = torch.empty((B, N, 64), dtype=torch.float32, device=x.device) if W2q is not None else None
+    with torch.cuda.device(x.device):
+        _lib.call("pc3d_pointnet_ft_tower_bwd_f32", xp, xbs, xps, xcs, B, N, _ptr(T), W1.data_ptr(), _ptr(WA),
+                  W2.data_ptr(), 128 * 64 if W2.dim() == 3 else 0, _ptr(W2q), W3.data_ptr(), C3, argidx.data_ptr(),
+                  m1.data_ptr(), _ptr(mA) if WA is not None else 0, m2.data_ptr(), g_pooled.data_ptr(), gp, gbs, gps, gcs,
+                  _ptr(part_gT), part_gT.shape[1] if part_gT is not None else 0, int(gT_off), _ptr(q),
+                  1 if accumulate else 0, _stream())
+    return gx, q
+
+
+def pointnet_ft_dtf_raw(x, T, W1, b1, q, x_cf=True):
+    """dL/dTf [B,4096] (row-major 64 x 64): g_Tf[b,i,j] = sum_n relu(W1 (x @ T) + b1)[i,n] q[b,n,j], n ascending."""
+    xp, xbs, xps, xcs, B, N = _pts(x, x_cf, "x")
+    T = _ft_T(T, B)
+    _check(q, "q")
+    if q.shape != (B, N, 64) or not q.is_contiguous():
+        raise ValueError("pointnet_ft_dtf_raw: q must be a contiguous [B,N,64] tensor")
+    g = torch.empty((B, 4096), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.call("pc3d_pointnet_ft_dtf_f32", xp, xbs, xps, xcs, B, N, T.data_ptr(), W1.data_ptr(), b1.data_ptr(),
+                  q.data_ptr(), g.data_ptr(), _stream())
+    return g
+
+
+def pointnet_ft_feat_fwd(x, T, trunk, fstn):
+    """Everything between the input transform and the pooled feature of a feature-transform PointNet, 9 launches.
+    trunk = (W1,b1,W2,b2,W3,b3,...) folded; fstn = STNkd's folded dict (model/pointnet.py). Returns
+    (pooled [B,1024], Tf [B,4096] = trans_feat row-major, saved) — saved feeds pointnet_ft_feat_bwd."""
+    W1, b1, W2, b2, W3, b3 = trunk[:6]
+    (w1f, b1f), (w2f, b2f), (w3f, b3f) = fstn["head"]
+    pooled_f, idx_f, masks_f = pointnet_ft_tower_fwd_raw(x, T, W1, b1, fstn["W2"], fstn["b2"], fstn["W3"], fstn["b3"], True,
+                                                         extra=(fstn["WA"], fstn["bA"]))
+    f1 = linear(pooled_f, w1f, b1f, relu=True)
+    f2 = linear(f1, w2f, b2f, relu=True)
+    Tf = linear(f2, w3f, b3f)                       # b3f carries the flattened identity
+    W2b = pointnet_ft_fold_w2(W2, Tf)
+    pooled, idx, masks = pointnet_ft_tower_fwd_raw(x, T, W1, b1, W2b, b2, W3, b3, False)
+    return pooled, Tf, (x, T, trunk, fstn, pooled_f, idx_f, masks_f, f1, f2, W2b, idx, masks)
+
+
+def pointnet_ft_feat_bwd(saved, g_pooled, out=None):
+    """Backward-to-input of pointnet_ft_feat_fwd for a gradient on `pooled`: (gx, part_gT). gx holds both towers'
+    contributions (trunk first, then the STNkd tower on top); part_gT [B, 2*ntiles, 16] both towers' dL/dT partials.
+    No gradient is taken from a use of the returned Tf other than the trunk's own."""
+    x, T, trunk, fstn, pooled_f, idx_f, masks_f, f1, f2, W2b, idx, masks = saved
+    W1, b1, W2, b2, W3, b3 = trunk[:6]
+    w1f_t, w2f_t, w3f_t = fstn["head_t"]
+    B, N = x.shape[0], x.shape[2]
+    part_gT, nt = pointnet_ft_gT_workspace(B, N, x.device)
+    gx, q = pointnet_ft_tower_bwd_raw(x, T, W1, W2b, W3, idx, g_pooled, masks, part_gT, 0, W2q=W2, out=out)
+    g_Tf = pointnet_ft_dtf_raw(x, T, W1, b1, q)
+    g_f2 = linear(g_Tf, w3f_t, gate=f2)
+    g_f1 = linear(g_f2, w2f_t, gate=f1)
+    g_pf = linear(g_f1, w1f_t, gate=pooled_f)       # ReLU after the STNkd max-pool
+    pointnet_ft_tower_bwd_raw(x, T, W1, fstn["W2"], fstn["W3"], idx_f, g_pf, masks_f, part_gT, nt, WA=fstn["WA"], out=gx,
+                              accumulate=True)
+    return gx, part_gT
+
+
+class _PointNetFTFeatFn(torch.autograd.Function):
+    """(x [B,3,N], trans [B,3,3]) -> (pooled [B,1024], trans_feat [B,64,64]) of a feature-transform PointNet;
+    differentiable in x and trans through `pooled`. trans_feat is returned non-differentiable (detached)."""
+
+    @staticmethod
+    def forward(ctx, x, trans, trunk, fstn):
+        pooled, Tf, saved = pointnet_ft_feat_fwd(x.detach(), trans.detach().contiguous(), trunk, fstn)
+        ctx.ft_saved = saved
+        Tf = Tf.view(-1, 64, 64)
+        ctx.mark_non_differentiable(Tf)
+        return pooled, Tf
+
+    @staticmethod
+    def backward(ctx, g, _g_tf):
+        gx, part_gT = pointnet_ft_feat_bwd(ctx.ft_saved, g)
+        return gx, part_gT.sum(1)[:, :9].reshape(-1, 3, 3), None, None
+
+
+def pointnet_ft_feat(x, trans, trunk, fstn):
+    return _PointNetFTFeatFn.apply(x, trans, trunk, fstn)
 
 
 # ------------------------------------------------------------------------------------------------------

@@ -415,6 +415,50 @@ int pc3d_pointmlp3_max_bwd_twolist_f32(const float* x, int64_t x_bs, int64_t x_p
                                        float* part_gT, int accumulate, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * PointNet with the feature transform (model/pointnet.py:51-87 STNkd, :101-117), eval mode, BatchNorm folded:
+ *   x' = x @ T,  h = relu(W1 x' + b1),  Tf = I + head(max_n tower_{64->64->128->1024}(h)),
+ *   pooled = max_n (W3 relu(W2 Tf^T h + b2) + b3).
+ * The towers are the pc3d_pointmlp3_* design (one launch, no per-point activation leaves the CU, ReLU decisions as
+ * per-point bit masks, (max, argmax) per tile of pc3d_pointmlp3_tile_points() points in part_val / part_idx
+ * [B, ntiles, C3], folded by pc3d_pointmlp3_fold_f32) with two extensions; T [B,3,3] is required.
+ *
+ * pc3d_pointnet_ft_tower_fwd_f32:
+ *   WA, bA, maskA given: STNkd's tower 3 -> 64 -> [64 -> 64] -> 128 -> C3. h is recomputed from x (W1, b1 are the
+ *     TRUNK's layer 1); WA [64,64] / bA is the extra layer, whose decisions go to maskA [B,N] (bit c = channel c).
+ *   WA, bA, maskA NULL: the trunk 3 -> 64 -> 128 -> C3.
+ *   W2 [128,64] is read at W2 + b * w2_bs floats for cloud b (w2_bs = 0: one weight for all clouds). The trunk takes
+ *   the folded W2_b = W2 Tf_b^T of pc3d_pointnet_ft_fold_w2_f32 (w2_bs = 8192), which replaces the per-point
+ *   64 x 64 product Tf^T h. mask1 [B,N] / mask2 [B,N,4] as pc3d_pointmlp3_max_fwd_f32. */
+int pc3d_pointnet_ft_tower_fwd_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                   const float* T, const float* W1, const float* b1, const float* WA, const float* bA,
+                                   const float* W2, int64_t w2_bs, const float* b2, const float* W3, const float* b3,
+                                   int C3, float* part_val, int32_t* part_idx, uint64_t* mask1, uint64_t* maskA,
+                                   uint32_t* mask2, void* stream);
+/* W2b[b][c][i] = sum_j W2[c][j] Tf[b][i][j] (W2 [128,64], Tf [B,64,64], W2b [B,128,64]); ascending j. */
+int pc3d_pointnet_ft_fold_w2_f32(const float* W2, const float* Tf, int B, float* W2b, void* stream);
+/* Backward-to-input of pc3d_pointnet_ft_tower_fwd_f32 (winners only: the ordered gather of
+ * pc3d_pointmlp3_max_bwd_twolist_f32, then the masked layers on MFMA). grad_x receives (accumulate != 0: is added) the
+ * gradient w.r.t. the RAW points; rows [gT_off, gT_off + ceil(N / pc3d_pointmlp3_bwd_tile_points())) of part_gT
+ * [B, gT_tiles, 16] the per-tile partials of dL/dT, so that both towers' partials sit in ONE workspace the STN head's
+ * backward sums. WA / maskA given: the 64 -> 64 form (W2q, q NULL). W2q / q given: the trunk; W2 is the folded
+ * per-cloud weight, W2q the UNfolded W2, and q [B,N,64] receives q[b,n,:] = g_z2[b,n,:] . W2 (zero rows for points
+ * that won no channel) for pc3d_pointnet_ft_dtf_f32. Neither: a plain 3 -> 64 -> 128 -> C3 tower. T == NULL (part_gT
+ * is then not written): a tower on the raw points, i.e. what pc3d_pointmlp3_max_bwd_f32 computes for STN3d's tower.
+ * Unlike that entry, the gather sums a run of channels that hit the same point in a register and cuts runs at 32
+ * entries, so a point that wins hundreds of channels is summed in blocks, not as one chain: all three towers of a
+ * feature-transform victim go through this entry. */
+int pc3d_pointnet_ft_tower_bwd_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                   const float* T, const float* W1, const float* WA, const float* W2, int64_t w2_bs,
+                                   const float* W2q, const float* W3, int C3, const int32_t* argidx,
+                                   const uint64_t* mask1, const uint64_t* maskA, const uint32_t* mask2,
+                                   const float* g_pooled, float* grad_x, int64_t gx_bs, int64_t gx_ps, int64_t gx_cs,
+                                   float* part_gT, int gT_tiles, int gT_off, float* q, int accumulate, void* stream);
+/* g_Tf[b][i][j] = sum_n h[b][i][n] q[b][n][j] with h = relu(W1 (x @ T) + b1) recomputed by the forward's FMA chain;
+ * one thread owns an (i, j) and walks n in ascending order: no atomics, the same bits every run. */
+int pc3d_pointnet_ft_dtf_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N, const float* T,
+                             const float* W1, const float* b1, const float* q, float* g_Tf, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Classifier heads. Y[b,o] = epi(sum_k X[b,k] W[o,k] + bias[o]) for small row counts (the B samples of a batch),
  * fp32 MFMA. X may be given as P partial slabs per row ([B,P,K], summed on load; P=1 = plain matrix; ldx = row
  * stride in floats). epi: optional (Leaky)ReLU (relu = 1: Y = Y > 0 ? Y : slope * Y; slope 0 = ReLU), then optional
