@@ -360,6 +360,14 @@ def _geoA3_attack(net, pt_model, ptm_model, pts_model, dgcnn_model, cur_model, p
                         output_label = torch.argmax(_logits_of(net(input_curr_iter)), dim=1)
                         attack_success = _compare(output_label, target, gt_target, targeted)
                     record(output_label, attack_success, constrain_loss.detach())
+            else:
+                # the forward that is saved here is one the reference runs (:317), and a victim whose forward draws from
+                # torch's CPU generator (CurveNet's discarded FPS starts) draws in it too: make those draws, so that what
+                # is drawn from that generator afterwards — the next binary step's start offsets under cfg.host_rng, the
+                # FPS starts of a PointNet++ transfer model — is what the reference draws under the same seed
+                consume = getattr(net, "consume_forward_rng", None)
+                if consume is not None:
+                    consume(input_curr_iter)
 
             if cfg.is_pre_jitter_input:
                 if step % cfg.calculate_project_jitter_noise_iter == 0:

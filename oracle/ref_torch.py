@@ -655,15 +655,25 @@ class DGCNN(nn.Module):
 class GeoA3Oracle:
     """Restatement of the GeoA3 loop. ``as_written=True`` reproduces knn_utils.py:12-15 literally (squared norms
     broadcast on the wrong axes, SURVEY App. A-2) — used to pin this oracle against the real reference;
-    ``as_written=False`` uses true squared distances — what the build implements and is compared against."""
+    ``as_written=False`` uses true squared distances — what the build implements and is compared against.
+    ``dtype`` runs the neighbour search in that type and hands fp32 values on; ``keep_dtype=True`` hands the values on
+    in ``dtype`` and keeps every later step there (a float64 run end to end, given float64 inputs and a double model).
+    ``direct=True`` forms the squared distances as sum((a - b)^2) instead of |a|^2 - 2ab + |b|^2: in fp32 the expansion
+    loses |a|^2 * eps per distance, which is all of a distance of 1e-6 (adv ~ ori at the start of a binary step); in
+    float64 the two forms pick the same neighbours."""
 
-    def __init__(self, as_written=True, dtype=None):
-        self.as_written, self.dtype = as_written, dtype
+    def __init__(self, as_written=True, dtype=None, keep_dtype=False, direct=False):
+        assert not (as_written and direct), "the as-written broadcast exists in the expansion form only"
+        self.as_written, self.dtype, self.keep_dtype, self.direct = as_written, dtype, keep_dtype, direct
 
     # -- knn_utils.py
     def knn_points(self, p1, p2, K=1):
         if self.dtype is not None:
             p1, p2 = p1.to(self.dtype), p2.to(self.dtype)
+        if self.direct:
+            dist = ((p1[:, :, None, :] - p2[:, None, :, :]) ** 2).sum(-1)    # [B,N,M]
+            value, pos = (-dist).topk(k=K, dim=-1)
+            return (-value if self.keep_dtype else (-value).float()), pos
         inner = -2. * torch.matmul(p1, p2.transpose(2, 1))
         p1_2 = torch.sum((p1.transpose(2, 1)) ** 2, dim=1, keepdim=True)      # [B,1,N]
         p2_2 = torch.sum((p2.transpose(2, 1)) ** 2, dim=1, keepdim=True)      # [B,1,M]
@@ -672,7 +682,7 @@ class GeoA3Oracle:
         else:
             dist = p1_2.transpose(2, 1) + inner + p2_2
         value, pos = (-dist).topk(k=K, dim=-1)
-        return (-value).float(), pos
+        return (-value if self.keep_dtype else (-value).float()), pos
 
     @staticmethod
     def knn_gather(x, idx):
@@ -732,7 +742,7 @@ class GeoA3Oracle:
     def forward_step(self, net, pc_ori, x, normal_ori, ori_kappa, target, scale_const, cfg, targeted):
         out = net(x)[0]
         if cfg.cls_loss_type == 'Margin':
-            oh = torch.zeros(target.size() + (cfg.classes,)).scatter_(1, target.unsqueeze(1), 1.)
+            oh = torch.zeros(target.size() + (cfg.classes,), dtype=out.dtype).scatter_(1, target.unsqueeze(1), 1.)
             fake = (oh * out).sum(1)
             other = ((1. - oh) * out - oh * 10000.).max(1)[0]
             cls_loss = torch.clamp((other - fake if targeted else fake - other) + cfg.confidence, min=0.)
@@ -740,7 +750,7 @@ class GeoA3Oracle:
             ce = nn.CrossEntropyLoss(reduction='none')(out, target.long())
             cls_loss = ce if targeted else -ce
         else:
-            cls_loss = torch.zeros(x.shape[0])
+            cls_loss = torch.zeros(x.shape[0], dtype=x.dtype)
         if cfg.dis_loss_type == 'CD':
             dis = self.pseudo_chamfer_loss(x, pc_ori) if cfg.is_cd_single_side else self.chamfer_loss(x, pc_ori)
             constrain = cfg.dis_loss_weight * dis
@@ -758,7 +768,7 @@ class GeoA3Oracle:
             ak, _ = self.kappa_adv(x, pc_ori, normal_ori, cfg.curv_loss_knn)
             curv = self.curvature_loss(x, pc_ori, ak, ori_kappa)
             constrain = constrain + cfg.curv_loss_weight * curv
-        loss_n = cls_loss + scale_const.float() * constrain
+        loss_n = cls_loss + (scale_const.to(x.dtype) if self.keep_dtype else scale_const.float()) * constrain
         return out, loss_n.mean(), loss_n, cls_loss, dis, hd, curv, constrain
 
     # -- GeoA3_attack.py:185-473 (default mode: full offset variable, Adam, no jitter / projection / clip)

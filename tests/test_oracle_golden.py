@@ -298,6 +298,49 @@ def test_oracle_geoa3_on_dgcnn_at_config_size_matches_reference():
         torch.set_num_threads(was)
 
 
+def test_oracle_geoa3_gradients_on_dgcnn_iterates_match_fixture():
+    """tests/golden/geoa3_grads.npz recomputed where that needs no reference: the oracle's DGCNN (seeded weights, sha256
+    checked) and the oracle's forward_step in fp32 (direct-difference distances, the form the fixture's bands are measured
+    with) on the 6 stored DGCNN iterates of each case. g_total lies within b_total[i] — the deviation the reference's own
+    fp32 run has there — of the stored float64 gradient, and the as-written oracle's distance from the reference's own
+    gradient (`*_aw_gdev`) lies within the same band. One thread, like the generator."""
+    import types
+    fx = np.load(os.path.join(GOLDEN, "geoa3_grads.npz"))
+    cs = np.load(os.path.join(GOLDEN, "config_sizes.npz"))
+    net = ort.DGCNN(types.SimpleNamespace(k=20, emb_dims=1024, dropout=0.5), output_channels=40)
+    sd = ort.seeded_state_dict(net, 5)
+    net.load_state_dict(sd)
+    net.eval()
+    assert ort.state_sha256(sd) == str(fx["dgcnn_sha256"]) == str(cs["dgcnn_sha256"])
+    was = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        for nm in ("margin_l2", "ce_cd_hd_curv"):
+            key = f"dgcnn_n1024_{nm}"
+            cfg = _geo_cfg(npoint=1024, **GEO_CASES[nm])
+            orc_g = ort.GeoA3Oracle(as_written=False, direct=True)
+            ori = torch.from_numpy(cs[f"{key}_pc"]).transpose(2, 1).contiguous()
+            normal = torch.from_numpy(fx[f"{key}_normal_ori"])
+            kappa = torch.from_numpy(fx[f"{key}_ori_kappa"]) if f"{key}_ori_kappa" in fx.files else None
+            assert fx[f"{key}_iter_index"].tolist() == [0, 4, 8, 12, 16, 20]
+            for i in range(6):
+                x = torch.from_numpy(fx[f"{key}_iter_inputs"][i:i + 1]).requires_grad_()
+                _, loss, loss_n, _, _, _, _, _ = orc_g.forward_step(net, ori, x, normal, kappa, torch.from_numpy(fx[f"{key}_target"]),
+                                                                  torch.from_numpy(fx[f"{key}_scale_const"][i]), cfg,
+                                                                  bool(fx[f"{key}_targeted"][i]))
+                loss.backward()
+                ref = fx[f"{key}_g_total"][i:i + 1].astype(np.float64)
+                dev = np.linalg.norm(x.grad.numpy() - ref) / np.linalg.norm(ref)
+                band = float(fx[f"{key}_b_total"][i])
+                # (+ 2^-24: this DGCNN and the reference's are two fp32 programs; where they differ in one last bit the
+                # deviation moves by a fraction of the gradient's own half-ulp — the fixture's bands are floored there too)
+                assert dev <= band + 2.0 ** -24, (key, i, dev, band)
+                assert float(fx[f"{key}_aw_gdev"][i]) <= band, (key, i)
+                np.testing.assert_allclose(float(loss_n), float(fx[f"{key}_loss_n"][i]), rtol=1e-4)
+    finally:
+        torch.set_num_threads(was)
+
+
 def test_oracle_f4_functors_match_reference():
     """FarthestDist / FarChamferDist / L2ChamferDist of the real reference (tests/golden/f4.npz)."""
     fx = np.load(os.path.join(GOLDEN, "f4.npz"))
