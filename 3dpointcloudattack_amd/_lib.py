@@ -174,6 +174,11 @@ SIGNATURES = {
     "pc3d_query_step_f32": [_P, _I, _P, _I] + _PTS + _PTS + _PTS + [_P, _I, _P, _P, _L, _L] + [_P] * 7 + _PTS + _PTS
     + [_P, _P, _I, _I, _I, _P],
     "pc3d_si_rank_f32": _PTS + _PTS + [_I, _I, _P, _P, _P, _P, _P],
+    "pc3d_ig_steps_f32": _PTS + [_I, _I, _I, _P, _I, _P, _P, _P],
+    "pc3d_ig_cotangent_f32": [_P, _I, _I, _I, _I, _I, _P, _P],
+    "pc3d_ig_reduce_f64": [_P, _I, _I, _I] + _PTS + [_P, _P, _P, _P, _P],
+    "pc3d_cta_cotangent_f32": [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P],
+    "pc3d_cta_update_f32": [_P] * 6 + [_I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _D, _D, _D, _P],
 }
 
 # entry points that do not return a status code

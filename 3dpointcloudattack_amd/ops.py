@@ -3397,3 +3397,128 @@ def si_rank(g, nrm, cf=True, want_gp=False):
         _lib.call("pc3d_si_rank_f32", gp_, gbs, gps, gcs, *nv[:4], B, N, _ptr(gp), key.data_ptr(), dirs.data_ptr(),
                   order.data_ptr(), _stream())
     return key, dirs, order, gp
+
+
+# ------------------------------------------------------------------------------------------------------
+# the critical-point attack (csrc/cta.hip; attack/CTA)
+# ------------------------------------------------------------------------------------------------------
+CTA_MAX_CLASSES = 256           # the cotangent kernels keep a row of logits in one wave's registers
+CTA_POLL_WORDS = 64             # int32 words of per-set state (pc3d_cta_cotangent_f32)
+CTA_HISTORY = 1500              # records per pass: the reference breaks a pass at cur_step >= 1500
+_IG_KINDS = {"black": 0, "white": 1}
+
+
+def _cta_buf(t, dtype, shape, name):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected a contiguous {dtype} GPU tensor of shape {tuple(shape)}")
+    return t
+
+
+def ig_steps(x, alphas, baseline="black"):
+    """IntegratedGradients.get_mask's step clouds, one launch (pc3d_ig_steps_f32): x [B,3,N], alphas = the S doubles of
+    np.linspace -> (clouds [S*B,3,N], base [1]): baseline + alpha * (x - baseline) with baseline the minimum ('black') or
+    maximum ('white') over the whole of x, or zero (anything else, as the reference)."""
+    xp, xbs, xps, xcs, B, N = _pts(x, True, "x")
+    if torch.is_tensor(alphas) and alphas.is_cuda and alphas.dtype == torch.float64 and alphas.is_contiguous():
+        al = alphas                                    # already on the device (a caller that captures the launch)
+    else:
+        al = torch.as_tensor(np.asarray(alphas, dtype=np.float64)).to(x.device)
+    S = al.numel()
+    out = torch.empty((S * B, 3, N), dtype=torch.float32, device=x.device)
+    base = torch.empty((1,), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.call("pc3d_ig_steps_f32", xp, xbs, xps, xcs, B, N, _IG_KINDS.get(baseline, 2), al.data_ptr(), S, out.data_ptr(),
+                  base.data_ptr(), _stream())
+    return out, base
+
+
+def ig_cotangent(logits, B, set_size, target, out=None):
+    """VanillaGradient.get_mask's cotangent on the logits [R,k] of R / B steps of B clouds (pc3d_ig_cotangent_f32).
+    target: a class, or None for the multi-hot of every row's top-1 class."""
+    _check(logits, "logits")
+    R, k = logits.shape
+    if not logits.is_contiguous():
+        raise ValueError("ig_cotangent: logits must be contiguous")
+    g = _cta_buf(out, torch.float32, (R, k), "out") if out is not None else torch.empty_like(logits)
+    with torch.cuda.device(logits.device):
+        _lib.call("pc3d_ig_cotangent_f32", logits.data_ptr(), R, B, k, int(set_size), -1 if target is None else int(target),
+                  g.data_ptr(), _stream())
+    return g
+
+
+def ig_reduce(grads, x, base):
+    """(mask float64 [3,N,B], contri [3,B], contri [B,N]) of the step gradients grads [S*B,3,N] (pc3d_ig_reduce_f64)."""
+    xp, xbs, xps, xcs, B, N = _pts(x, True, "x")
+    _check(grads, "grads")
+    if grads.dim() != 3 or grads.shape[0] % B or tuple(grads.shape[1:]) != (3, N) or not grads.is_contiguous():
+        raise ValueError(f"ig_reduce: grads must be a contiguous [S*{B},3,{N}] tensor, got {tuple(grads.shape)}")
+    S = grads.shape[0] // B
+    f64 = dict(dtype=torch.float64, device=x.device)
+    mask, c_cn, c_bn = torch.empty((3, N, B), **f64), torch.empty((3, B), **f64), torch.empty((B, N), **f64)
+    with torch.cuda.device(x.device):
+        _lib.call("pc3d_ig_reduce_f64", grads.data_ptr(), S, B, N, xp, xbs, xps, xcs, base.data_ptr(), mask.data_ptr(),
+                  c_cn.data_ptr(), c_bn.data_ptr(), _stream())
+    return mask, c_cn, c_bn
+
+
+CTA_MODES = {"ori_minus_tar": 0, "ori_minus_second": 1, "ori": 2, "log_softmax": 3}
+
+
+def cta_cotangent(logits, s, out=None):
+    """The CTA loop's cotangent on logits [G*S,k] plus sample 0's records, windows and success flag, one launch
+    (pc3d_cta_cotangent_f32). s: the loop's buffers — mode, targeted, ori / tar int32 [G] (tar may be None), w float32
+    [S], poll int32 [G,64], hist_ori / hist_max float32 [G,H], zlast float32 [G*S,k] or None (the logits of the last
+    forward of every set that is not latched)."""
+    _check(logits, "logits")
+    poll = s["poll"]
+    G, S = poll.shape[0], s["w"].numel()
+    if logits.dim() != 2 or logits.shape[0] != G * S or not logits.is_contiguous():
+        raise ValueError(f"cta_cotangent: logits must be a contiguous [{G * S},k] tensor, got {tuple(logits.shape)}")
+    k = logits.shape[1]
+    H = s["hist_ori"].shape[1]
+    _cta_buf(poll, torch.int32, (G, CTA_POLL_WORDS), "poll")
+    _cta_buf(s["ori"], torch.int32, (G,), "ori")
+    if s.get("tar") is not None:
+        _cta_buf(s["tar"], torch.int32, (G,), "tar")
+    _cta_buf(s["w"], torch.float32, (S,), "w")
+    _cta_buf(s["hist_ori"], torch.float32, (G, H), "hist_ori")
+    _cta_buf(s["hist_max"], torch.float32, (G, H), "hist_max")
+    if s.get("zlast") is not None:
+        _cta_buf(s["zlast"], torch.float32, (G * S, k), "zlast")
+    g = _cta_buf(out, torch.float32, (G * S, k), "out") if out is not None else torch.empty_like(logits)
+    with torch.cuda.device(logits.device):
+        _lib.call("pc3d_cta_cotangent_f32", logits.data_ptr(), G, S, k, CTA_MODES[s["mode"]], 1 if s["targeted"] else 0,
+                  s["ori"].data_ptr(), _ptr(s.get("tar")), s["w"].data_ptr(), poll.data_ptr(), s["hist_ori"].data_ptr(),
+                  s["hist_max"].data_ptr(), H, g.data_ptr(), _ptr(s.get("zlast")), _stream())
+    return g
+
+
+def cta_update(s, g=None, control=False):
+    """One optimiser step of every live set, in place on s["x"] [G*S,3,N] (pc3d_cta_update_f32), or with control=True
+    the host's control words s["ctrl"] (1: next level and iterate reset, 2: latch). s: x, proto, v, s_adam (None for
+    Momentum), sel int32 [G,P,W], cap, poll, ctrl int32 [G], S, optimizer ('Adam' | 'Momentum')."""
+    x, poll = s["x"], s["poll"]
+    G, S = poll.shape[0], int(s["S"])
+    _check(x, "x")
+    if x.dim() != 3 or x.shape[0] != G * S or x.shape[1] != 3 or not x.is_contiguous():
+        raise ValueError(f"cta_update: x must be a contiguous [{G * S},3,N] tensor, got {tuple(x.shape)}")
+    N = x.shape[2]
+    shp = tuple(x.shape)
+    _cta_buf(s["proto"], torch.float32, shp, "proto")
+    _cta_buf(poll, torch.int32, (G, CTA_POLL_WORDS), "poll")
+    _cta_buf(s["ctrl"], torch.int32, (G,), "ctrl")
+    opt = {"Adam": 0, "Momentum": 1}[s["optimizer"]]
+    sel = s["sel"]
+    if sel.dtype != torch.int32 or not sel.is_cuda or not sel.is_contiguous() or sel.dim() != 3 or sel.shape[0] != G:
+        raise ValueError("cta_update: sel must be a contiguous int32 [G,P,W] GPU tensor")
+    if not control:
+        _cta_buf(g, torch.float32, shp, "g")
+        _cta_buf(s["v"], torch.float32, shp, "v")
+        if opt == 0:
+            _cta_buf(s["s_adam"], torch.float32, shp, "s_adam")
+    with torch.cuda.device(x.device):
+        _lib.call("pc3d_cta_update_f32", x.data_ptr(), _ptr(g), s["proto"].data_ptr(), _ptr(s.get("v")),
+                  _ptr(s.get("s_adam")) if opt == 0 else 0, sel.data_ptr(), sel.shape[1], sel.shape[2],
+                  min(int(s["cap"]), 0x7fffffff), poll.data_ptr(), s["ctrl"].data_ptr(), G, S, N, opt, 1 if control else 0,
+                  0.9, 0.999, 1e-8, _stream())
+    return x

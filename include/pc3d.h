@@ -1138,6 +1138,51 @@ int pc3d_si_rank_f32(const float* g, int64_t g_bs, int64_t g_ps, int64_t g_cs,
                      const float* nrm, int64_t n_bs, int64_t n_ps, int64_t n_cs, int B, int N,
                      float* gp, float* key, float* dir, int32_t* order, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * The critical-point attack (attack/CTA/CTA.py, CTA_sumloss.py): integrated-gradients saliency of a set of clouds and
+ * the optimiser loop on its most salient points (csrc/cta.hip). No atomics; every sum has one order.
+ * ------------------------------------------------------------------------------------------------------- */
+/* IntegratedGradients.get_mask's step clouds, one launch: base = the minimum (kind 0, 'black') or maximum (kind 1,
+ * 'white') over ALL B*3*N coordinates of x, or 0 (kind 2); out[s*B + b] = base + (float)alpha[s] * (x[b] - base), the
+ * product rounded to float once and then added, as torch evaluates baseline + alpha * image_diff for a double scalar
+ * alpha. alpha: S doubles in device memory (np.linspace(0, 1, S)). out [S*B,3,N] contiguous; base [1] receives base. */
+int pc3d_ig_steps_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N, int kind,
+                      const double* alpha, int S, float* out, float* base, void* stream);
+/* The cotangent of VanillaGradient.get_mask taken back from the log-softmax output to the logits z [R,k] (row r = step *
+ * B + sample, R a multiple of B): g = t - softmax(z) * sum(t) with t one-hot at `target` (target >= 0) or, target < 0,
+ * the multi-hot of the top-1 classes (lowest class on a tie) of ALL B rows of the step; rows of samples >= set_size are
+ * zero. k <= 256. */
+int pc3d_ig_cotangent_f32(const float* z, int R, int B, int k, int set_size, int target, float* g, void* stream);
+/* mask[c,n,b] = (sum over s = 0..S-1, in that order, of (double)g[s*B + b, c, n]) * (double)(x[b,c,n] - base) / S, the
+ * float64 [3,N,B] array IntegratedGradients.get_mask returns (g [S*B,3,N] contiguous: the victim's input gradients of
+ * pc3d_ig_steps_f32's clouds; base: its base word). Also both contribution tables: contri_cn [3,B] = the mask summed over
+ * the points in ascending order (CTA.py), contri_bn [B,N] = (m[0] + m[1]) + m[2] per point (CTA_sumloss.py). */
+int pc3d_ig_reduce_f64(const float* g, int S, int B, int N, const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs,
+                       const float* base, double* mask, double* contri_cn, double* contri_bn, void* stream);
+/* The loop's loss as a cotangent on the logits z [G*S,k] of G sets of S clouds: row (g, j) gets w[j] times
+ *   mode 0: e[ori] - e[tar]     mode 1: e[ori] - e[second], second = torch.topk(z, 2).indices[-1] (value descending,
+ *   class ascending)            mode 2: e[ori]     mode 3: e[ori] - softmax(z)   (the gradient of log_softmax(z)[ori]).
+ * In the same launch, for sample 0 of every set that is not latched, at position cur_step of the set: hist_ori = z[ori],
+ * hist_max = the row's maximum with z[ori] NEGATED ([G,H] each; nothing is stored beyond H), the 25-entry windows of
+ * z[ori] and z[tar] in poll, and the success flag (targeted: arg-max == tar, else arg-max != ori; lowest class on a
+ * tie). poll [G,64] int32: 0..24 / 25..49 the windows (float bits), 50 latch, 51 cur_step, 52 step, 53 num_p_per,
+ * 54 success flag. A latched set gets a zero cotangent. zlast [G*S,k] (may be NULL) receives the
+ * rows of every set that is not latched: the logits of its last forward. k <= 256. */
+int pc3d_cta_cotangent_f32(const float* z, int G, int S, int k, int mode, int targeted, const int32_t* ori,
+                           const int32_t* tar, const float* w, int32_t* poll, float* hist_ori, float* hist_max, int H,
+                           float* g, float* zlast, void* stream);
+/* One optimiser step of every live set, in place on x [G*S,3,N] (contiguous, as g, proto, v, s): the gradient is kept at
+ * the slots (sample * N + point) listed in levels 0 .. min(num_p_per, cap, P) - 1 of the set's table sel [G,P,W] and
+ * zeroed elsewhere (entries outside [0, S*N) are padding), then for ALL coordinates of the set
+ *   opt 0:  v = b1 v + (1 - b1) g;  s = b2 s + (1 - b2) g^2;  x += -v / sqrt(s + xi)   (no bias correction, step 1)
+ *   opt 1:  v = b1 v - g;           x += v
+ * cur_step += 1, step += 1, and latch = 1 when the step's success flag is set. control != 0: no step; a set with
+ * ctrl[g] == 1 gets x = proto, num_p_per += 1, cur_step = 0 (the optimiser state stays), with ctrl[g] == 2 latch = 2;
+ * ctrl[g] is cleared. Latched sets are untouched in both modes. S*N <= 49152. */
+int pc3d_cta_update_f32(float* x, const float* g, const float* proto, float* v, float* s, const int32_t* sel, int P,
+                        int W, int cap, int32_t* poll, int32_t* ctrl, int G, int S, int N, int opt, int control,
+                        double b1, double b2, double xi, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
