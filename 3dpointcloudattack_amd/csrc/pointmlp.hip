@@ -22,126 +22,14 @@
 
 namespace pc3d {
 
-struct PMFwdArgs {
-  PtsView x;
-  int N, C3, ntiles;
-  const float* T;  // [B,3,3] or null: x'[n,:] = x[n,:] @ T  (model/pointnet.py:106-109)
-  const float *W1, *b1, *W2, *b2, *W3, *b3;
-  float* part_val;    // [B, ntiles, C3]
-  int32_t* part_idx;  // [B, ntiles, C3]
-  uint64_t* mask1;    // [B,N]    bit c  = (layer-1 output c of the point > 0), or null
-  uint32_t* mask2;    // [B,N,4]  word j bit r = (layer-2 output 32j+r of the point > 0), or null
-  // optional "transform head" (T == null): T[b] = th_W [9,th_K] . th_in[b] + th_b — STN3d's fc3 (+ identity folded
-  // into th_b, model/pointnet.py:45-47) evaluated in this kernel's prologue instead of a launch of its own; tile 0 of
-  // every cloud also writes it to th_out [B,9] for the backward
-  const float *th_in, *th_W, *th_b;
-  int th_K;
-  float* th_out;
-};
-
-
 __global__ __launch_bounds__(PM_FT) __attribute__((amdgpu_waves_per_eu(2, 2))) void pointmlp3_max_fwd_kernel(PMFwdArgs a) {
-  __shared__ __attribute__((aligned(16))) float lds[PM_TP * PM_LD2 + 3 * PM_TP];  // 69,120 B static
-  float* h1 = lds;                       // [128][68]   (dead after layer 2)
-  float* h2 = lds;                       // [128][132]  (overwrites h1 behind a barrier)
-  float* xs = lds + PM_TP * PM_LD2;      // [3][128]
+  __shared__ __attribute__((aligned(16))) float lds[PM_FWD_LDS_FLOATS];  // 69,120 B static
+  pm_fwd_prologue(a, lds);   // layers 1-2, masks, transform head: h2 [128][132] at lds, behind a barrier
+  float* h2 = lds;
   const int tile = blockIdx.x, b = blockIdx.y;
   const int n0 = tile * PM_TP;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r = lane & 31, h = lane >> 5;
-
-  const float* Tb = a.T ? a.T + (int64_t)b * 9 : nullptr;
-  // raw coordinates first (their load latency overlaps the transform head's), the transform is applied afterwards
-  float px = 0.f, py = 0.f, pz = 0.f;
-  if (threadIdx.x < PM_TP) load_point(a.x, nullptr, b, n0 + threadIdx.x, a.N, px, py, pz);
-  if (a.th_in) {   // 9 outputs x th_K: 32 lanes per output, strided partial sums + a half-wave reduction
-    __shared__ float Ts[9];
-    if (threadIdx.x < 9 * 32) {
-      const int j = threadIdx.x >> 5, l = threadIdx.x & 31;
-      const float* in = a.th_in + (int64_t)b * a.th_K;
-      const float* w = a.th_W + (int64_t)j * a.th_K;
-      float sacc = 0.f;
-      if (a.th_K == 256) {      // STN3d: all eight operand pairs in flight at once
-        float iv[8], wv[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) iv[u] = in[l + 32 * u], wv[u] = w[l + 32 * u];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) sacc = __builtin_fmaf(iv[u], wv[u], sacc);
-      } else {
-        for (int k = l; k < a.th_K; k += 32) sacc = __builtin_fmaf(in[k], w[k], sacc);
-      }
-#pragma unroll
-      for (int o = 16; o > 0; o >>= 1) sacc += __shfl_xor(sacc, o, 32);
-      if (l == 0) {
-        const float t = sacc + a.th_b[j];
-        Ts[j] = t;
-        if (tile == 0) a.th_out[(int64_t)b * 9 + j] = t;
-      }
-    }
-    __syncthreads();
-    Tb = Ts;
-  }
-  if (threadIdx.x < PM_TP) {
-    if (Tb) {   // x' = x @ T (model/pointnet.py:106-109)
-      const float x0 = px, x1 = py, x2 = pz;
-      px = __builtin_fmaf(x2, Tb[6], __builtin_fmaf(x1, Tb[3], x0 * Tb[0]));
-      py = __builtin_fmaf(x2, Tb[7], __builtin_fmaf(x1, Tb[4], x0 * Tb[1]));
-      pz = __builtin_fmaf(x2, Tb[8], __builtin_fmaf(x1, Tb[5], x0 * Tb[2]));
-    }
-    xs[threadIdx.x] = px;
-    xs[PM_TP + threadIdx.x] = py;
-    xs[2 * PM_TP + threadIdx.x] = pz;
-  }
-  __syncthreads();
-  layer1_to_lds<PM_TP, PM_FT>(xs, h1, a.W1, a.b1, a.mask1 ? a.mask1 + (int64_t)b * a.N + n0 : nullptr, a.N - n0);
-  __syncthreads();
-
-  // ---- layer 2 on MFMA: D[pt][c2] = sum_k h1[pt][k] W2[c2][k]; wave owns c2 block (wave&3) and 2 of the 4 point tiles
-  {
-    const int c2b = wave & 3, tl0 = (wave >> 2) * 2;
-    f32x16 acc[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
-    const float* wrow = a.W2 + (32 * c2b + r) * PM_C1 + 4 * h;
-#pragma unroll
-    for (int t = 0; t < PM_C1 / 8; ++t) {
-      const float4 bw = *reinterpret_cast<const float4*>(wrow + 8 * t);
-      float4 av[2];
-#pragma unroll
-      for (int tl = 0; tl < 2; ++tl)
-        av[tl] = *reinterpret_cast<const float4*>(h1 + ((tl0 + tl) * 32 + r) * PM_LD1 + 8 * t + 4 * h);
-#pragma unroll
-      for (int tl = 0; tl < 2; ++tl) {
-        acc[tl] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[tl].x, bw.x, acc[tl], 0, 0, 0);
-        acc[tl] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[tl].y, bw.y, acc[tl], 0, 0, 0);
-        acc[tl] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[tl].z, bw.z, acc[tl], 0, 0, 0);
-        acc[tl] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[tl].w, bw.w, acc[tl], 0, 0, 0);
-      }
-    }
-    __syncthreads();  // every wave is done reading h1
-    const float bias = a.b2[32 * c2b + r];
-    unsigned long long mine = 0ull;   // lane 16*tl + e keeps the ballot of (tl, e): points pt(e,0) [low word], pt(e,1) [high]
-#pragma unroll
-    for (int tl = 0; tl < 2; ++tl)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int pt = (tl0 + tl) * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-        const float v = acc[tl][e] + bias;
-        h2[pt * PM_LD2 + 32 * c2b + r] = fmaxf(v, 0.f);
-        const unsigned long long bal = __builtin_amdgcn_ballot_w64(v > 0.f);
-        if (lane == 16 * tl + e) mine = bal;
-      }
-    if (a.mask2 != nullptr && lane < 32) {   // the backward's layer-2 ReLU mask: exactly the decisions taken here
-      const int tl = lane >> 4, e = lane & 15;
-      const int pt0 = n0 + (tl0 + tl) * 32 + (e & 3) + 8 * (e >> 2);
-      uint32_t* m2 = a.mask2 + ((int64_t)b * a.N) * 4 + c2b;
-      if (pt0 < a.N) m2[(int64_t)pt0 * 4] = (uint32_t)mine;
-      if (pt0 + 4 < a.N) m2[(int64_t)(pt0 + 4) * 4] = (uint32_t)(mine >> 32);
-    }
-  }
-  __syncthreads();
 
   // ---- layer 3 + max over the tile's points.
   // Wave w owns point tile (w & 3) = 32 points and half of the channel blocks ((w >> 2) selects blocks
@@ -1002,7 +890,9 @@ static int pm_fwd_launch(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_c
                          const float* th_in, const float* th_W, const float* th_b, int th_K, float* th_out,
                          const float* W1, const float* b1, const float* W2, const float* b2, const float* W3,
                          const float* b3, int C1, int C2, int C3, int relu_last, float* part_val, int32_t* part_idx,
-                         float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2, void* stream) {
+                         float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2, void* stream,
+                         bool exact = false, int32_t* stats = nullptr, float* dbg_S = nullptr, float* dbg_E = nullptr,
+                         int stop_after = 0) {
   PC3D_REQUIRE(B >= 0 && N >= 1, "pc3d_pointmlp3_max_fwd_f32: bad sizes B=%d N=%d", B, N);
   PC3D_REQUIRE(C1 == PM_C1 && C2 == PM_C2 && C3 >= 32 && C3 % 32 == 0 && C3 <= PM_MAXC3F,
                "pc3d_pointmlp3_max_fwd_f32: unsupported widths %d/%d/%d (need 64/128/multiple of 32 <= 1024)", C1, C2, C3);
@@ -1018,7 +908,14 @@ static int pm_fwd_launch(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_c
   PMFwdArgs a{{x, x_bs, x_ps, x_cs}, N, C3, ntiles, T, W1, b1, W2, b2, W3, b3, part_val, part_idx, mask1, mask2,
               th_in, th_W, th_b, th_K, th_out};
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(pointmlp3_max_fwd_kernel, dim3(ntiles, B), dim3(PM_FT), 0, st, a);
+  // Layer 3 screened on bf16 MFMA and rechecked exactly (pointmlp_screen.hip: the same bits) at every shape this entry
+  // accepts; the exact kernel on request, and when the screened one cannot be launched yet (see pm_fwd_screen_launch).
+  int rc = 1;
+  if (!exact) {
+    rc = pm_fwd_screen_launch(a, B, stream, stats, dbg_S, dbg_E, stop_after);
+    if (rc < 0) return rc;
+  }
+  if (rc != 0) hipLaunchKernelGGL(pointmlp3_max_fwd_kernel, dim3(ntiles, B), dim3(PM_FT), 0, st, a);
   PC3D_LAUNCH_CHECK("pc3d_pointmlp3_max_fwd_f32");
   if (pooled) {  // NULL: leave the per-tile partials unfolded (a fused consumer, or kernel-only timing)
     hipLaunchKernelGGL(pointmlp3_fold_kernel<false>, dim3(cdiv(C3, 256), B), dim3(256), 0, st, part_val, part_idx, ntiles,
@@ -1065,6 +962,47 @@ extern "C" int pc3d_pointmlp3_max_fwd_th_f32(const float* x, int64_t x_bs, int64
                "pc3d_pointmlp3_max_fwd_th_f32: the transform head needs its input, weights [9,K], bias [9] and T_out");
   return pm_fwd_launch(x, x_bs, x_ps, x_cs, B, N, nullptr, th_in, th_W, th_b, th_K, T_out, W1, b1, W2, b2, W3, b3, C1, C2,
                        C3, relu_last, part_val, part_idx, pooled, argidx, mask1, mask2, stream);
+}
+
+extern "C" int pc3d_pointmlp3_max_fwd_exact_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                                const float* T, const float* W1, const float* b1, const float* W2,
+                                                const float* b2, const float* W3, const float* b3, int C1, int C2,
+                                                int C3, int relu_last, float* part_val, int32_t* part_idx,
+                                                float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2,
+                                                void* stream) {
+  return pm_fwd_launch(x, x_bs, x_ps, x_cs, B, N, T, nullptr, nullptr, nullptr, 0, nullptr, W1, b1, W2, b2, W3, b3, C1, C2,
+                       C3, relu_last, part_val, part_idx, pooled, argidx, mask1, mask2, stream, true);
+}
+
+extern "C" int pc3d_pointmlp3_max_fwd_exact_th_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                                   const float* th_in, const float* th_W, const float* th_b, int th_K,
+                                                   float* T_out, const float* W1, const float* b1, const float* W2,
+                                                   const float* b2, const float* W3, const float* b3, int C1, int C2,
+                                                   int C3, int relu_last, float* part_val, int32_t* part_idx,
+                                                   float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2,
+                                                   void* stream) {
+  PC3D_REQUIRE(th_in && th_W && th_b && T_out && th_K >= 1,
+               "pc3d_pointmlp3_max_fwd_exact_th_f32: the transform head needs its input, weights [9,K], bias [9] and T_out");
+  return pm_fwd_launch(x, x_bs, x_ps, x_cs, B, N, nullptr, th_in, th_W, th_b, th_K, T_out, W1, b1, W2, b2, W3, b3, C1, C2,
+                       C3, relu_last, part_val, part_idx, pooled, argidx, mask1, mask2, stream, true);
+}
+
+extern "C" int pc3d_pointmlp3_max_fwd_screen_dbg_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B,
+                                                     int N, const float* T, const float* th_in, const float* th_W,
+                                                     const float* th_b, int th_K, float* T_out, const float* W1,
+                                                     const float* b1, const float* W2, const float* b2, const float* W3,
+                                                     const float* b3, int C1, int C2, int C3, int relu_last,
+                                                     float* part_val, int32_t* part_idx, float* pooled, int32_t* argidx,
+                                                     uint64_t* mask1, uint32_t* mask2, int32_t* stats, float* dbg_S,
+                                                     float* dbg_E, int stop_after, void* stream) {
+  PC3D_REQUIRE(stats != nullptr, "pc3d_pointmlp3_max_fwd_screen_dbg_f32: stats [B, ntiles, 2] is required");
+  PC3D_REQUIRE((dbg_S == nullptr) == (dbg_E == nullptr), "pc3d_pointmlp3_max_fwd_screen_dbg_f32: dbg_S and dbg_E go together");
+  PC3D_REQUIRE(stop_after >= 0 && stop_after <= 3, "pc3d_pointmlp3_max_fwd_screen_dbg_f32: stop_after = %d", stop_after);
+  PC3D_REQUIRE(th_in == nullptr || (T == nullptr && th_W && th_b && T_out && th_K >= 1),
+               "pc3d_pointmlp3_max_fwd_screen_dbg_f32: T or a complete transform head, not both");
+  return pm_fwd_launch(x, x_bs, x_ps, x_cs, B, N, T, th_in, th_W, th_b, th_K, T_out, W1, b1, W2, b2, W3, b3, C1, C2, C3,
+                       relu_last, part_val, part_idx, pooled, argidx, mask1, mask2, stream, false, stats, dbg_S, dbg_E,
+                       stop_after);
 }
 
 static int pm_bwd_launch(const char* who, bool twolist, const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B,

@@ -60,4 +60,138 @@ constexpr int PM_MAXC3F = 1024;      // forward: widest layer 3 (cross-wave max 
 constexpr int PM_FT = 512;           // forward: threads per workgroup (8 waves = 2 per SIMD: one wave's epilogue /
                                      // operand waits overlap the other's MFMAs)
 
+
+// ---- the tower forward's arguments and prologue, shared by the exact kernel (pointmlp.hip) and the screened one
+// (pointmlp_screen.hip): the same statements, so h2 and the two masks are the same bits by construction
+struct PMFwdArgs {
+  PtsView x;
+  int N, C3, ntiles;
+  const float* T;  // [B,3,3] or null: x'[n,:] = x[n,:] @ T  (model/pointnet.py:106-109)
+  const float *W1, *b1, *W2, *b2, *W3, *b3;
+  float* part_val;    // [B, ntiles, C3]
+  int32_t* part_idx;  // [B, ntiles, C3]
+  uint64_t* mask1;    // [B,N]    bit c  = (layer-1 output c of the point > 0), or null
+  uint32_t* mask2;    // [B,N,4]  word j bit r = (layer-2 output 32j+r of the point > 0), or null
+  // optional "transform head" (T == null): T[b] = th_W [9,th_K] . th_in[b] + th_b — STN3d's fc3 (+ identity folded
+  // into th_b, model/pointnet.py:45-47) evaluated in this kernel's prologue instead of a launch of its own; tile 0 of
+  // every cloud also writes it to th_out [B,9] for the backward
+  const float *th_in, *th_W, *th_b;
+  int th_K;
+  float* th_out;
+};
+
+constexpr int PM_FWD_LDS_FLOATS = PM_TP * PM_LD2 + 3 * PM_TP;   // h2 tile [128][132] (h1 aliases it) + xs [3][128]
+
+// Transform head, x . T, layer 1 (VALU) and layer 2 (fp32 MFMA) of the workgroup's 128 points; mask1 / mask2 / th_out
+// leave here. On return h2 [128][PM_LD2] sits at lds and every wave has passed the barrier behind its last write.
+__device__ __forceinline__ void pm_fwd_prologue(const PMFwdArgs& a, float* lds) {
+  float* h1 = lds;                       // [128][68]   (dead after layer 2)
+  float* h2 = lds;                       // [128][132]  (overwrites h1 behind a barrier)
+  float* xs = lds + PM_TP * PM_LD2;      // [3][128]
+  const int tile = blockIdx.x, b = blockIdx.y;
+  const int n0 = tile * PM_TP;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = lane & 31, h = lane >> 5;
+
+  const float* Tb = a.T ? a.T + (int64_t)b * 9 : nullptr;
+  // raw coordinates first (their load latency overlaps the transform head's), the transform is applied afterwards
+  float px = 0.f, py = 0.f, pz = 0.f;
+  if (threadIdx.x < PM_TP) load_point(a.x, nullptr, b, n0 + threadIdx.x, a.N, px, py, pz);
+  if (a.th_in) {   // 9 outputs x th_K: 32 lanes per output, strided partial sums + a half-wave reduction
+    __shared__ float Ts[9];
+    if (threadIdx.x < 9 * 32) {
+      const int j = threadIdx.x >> 5, l = threadIdx.x & 31;
+      const float* in = a.th_in + (int64_t)b * a.th_K;
+      const float* w = a.th_W + (int64_t)j * a.th_K;
+      float sacc = 0.f;
+      if (a.th_K == 256) {      // STN3d: all eight operand pairs in flight at once
+        float iv[8], wv[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) iv[u] = in[l + 32 * u], wv[u] = w[l + 32 * u];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) sacc = __builtin_fmaf(iv[u], wv[u], sacc);
+      } else {
+        for (int k = l; k < a.th_K; k += 32) sacc = __builtin_fmaf(in[k], w[k], sacc);
+      }
+#pragma unroll
+      for (int o = 16; o > 0; o >>= 1) sacc += __shfl_xor(sacc, o, 32);
+      if (l == 0) {
+        const float t = sacc + a.th_b[j];
+        Ts[j] = t;
+        if (tile == 0) a.th_out[(int64_t)b * 9 + j] = t;
+      }
+    }
+    __syncthreads();
+    Tb = Ts;
+  }
+  if (threadIdx.x < PM_TP) {
+    if (Tb) {   // x' = x @ T (model/pointnet.py:106-109)
+      const float x0 = px, x1 = py, x2 = pz;
+      px = __builtin_fmaf(x2, Tb[6], __builtin_fmaf(x1, Tb[3], x0 * Tb[0]));
+      py = __builtin_fmaf(x2, Tb[7], __builtin_fmaf(x1, Tb[4], x0 * Tb[1]));
+      pz = __builtin_fmaf(x2, Tb[8], __builtin_fmaf(x1, Tb[5], x0 * Tb[2]));
+    }
+    xs[threadIdx.x] = px;
+    xs[PM_TP + threadIdx.x] = py;
+    xs[2 * PM_TP + threadIdx.x] = pz;
+  }
+  __syncthreads();
+  layer1_to_lds<PM_TP, PM_FT>(xs, h1, a.W1, a.b1, a.mask1 ? a.mask1 + (int64_t)b * a.N + n0 : nullptr, a.N - n0);
+  __syncthreads();
+
+  // ---- layer 2 on MFMA: D[pt][c2] = sum_k h1[pt][k] W2[c2][k]; wave owns c2 block (wave&3) and 2 of the 4 point tiles
+  {
+    const int c2b = wave & 3, tl0 = (wave >> 2) * 2;
+    f32x16 acc[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
+    const float* wrow = a.W2 + (32 * c2b + r) * PM_C1 + 4 * h;
+#pragma unroll
+    for (int t = 0; t < PM_C1 / 8; ++t) {
+      const float4 bw = *reinterpret_cast<const float4*>(wrow + 8 * t);
+      float4 av[2];
+#pragma unroll
+      for (int tl = 0; tl < 2; ++tl)
+        av[tl] = *reinterpret_cast<const float4*>(h1 + ((tl0 + tl) * 32 + r) * PM_LD1 + 8 * t + 4 * h);
+#pragma unroll
+      for (int tl = 0; tl < 2; ++tl) {
+        acc[tl] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[tl].x, bw.x, acc[tl], 0, 0, 0);
+        acc[tl] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[tl].y, bw.y, acc[tl], 0, 0, 0);
+        acc[tl] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[tl].z, bw.z, acc[tl], 0, 0, 0);
+        acc[tl] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[tl].w, bw.w, acc[tl], 0, 0, 0);
+      }
+    }
+    __syncthreads();  // every wave is done reading h1
+    const float bias = a.b2[32 * c2b + r];
+    unsigned long long mine = 0ull;   // lane 16*tl + e keeps the ballot of (tl, e): points pt(e,0) [low word], pt(e,1) [high]
+#pragma unroll
+    for (int tl = 0; tl < 2; ++tl)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int pt = (tl0 + tl) * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+        const float v = acc[tl][e] + bias;
+        h2[pt * PM_LD2 + 32 * c2b + r] = fmaxf(v, 0.f);
+        const unsigned long long bal = __builtin_amdgcn_ballot_w64(v > 0.f);
+        if (lane == 16 * tl + e) mine = bal;
+      }
+    if (a.mask2 != nullptr && lane < 32) {   // the backward's layer-2 ReLU mask: exactly the decisions taken here
+      const int tl = lane >> 4, e = lane & 15;
+      const int pt0 = n0 + (tl0 + tl) * 32 + (e & 3) + 8 * (e >> 2);
+      uint32_t* m2 = a.mask2 + ((int64_t)b * a.N) * 4 + c2b;
+      if (pt0 < a.N) m2[(int64_t)pt0 * 4] = (uint32_t)mine;
+      if (pt0 + 4 < a.N) m2[(int64_t)(pt0 + 4) * 4] = (uint32_t)(mine >> 32);
+    }
+  }
+  __syncthreads();
+}
+
+
+// pointmlp_screen.hip: the same launch with layer 3 screened on bf16 MFMA and rechecked exactly (the same bits).
+// Returns 0 when launched, 1 when it could not be (first use on a device while the stream is capturing: the caller
+// launches the exact kernel), < 0 on an error. stats / dbg_S / dbg_E / stop_after: pc3d_pointmlp3_max_fwd_screen_dbg_f32.
+int pm_fwd_screen_launch(const PMFwdArgs& a, int B, void* stream, int32_t* stats, float* dbg_S, float* dbg_E,
+                         int stop_after);
+
 }  // namespace pc3d

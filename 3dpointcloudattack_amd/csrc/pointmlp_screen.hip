@@ -1,0 +1,384 @@
+// K8s — the PointNet tower forward (pointmlp.hip) with layer 3 SCREENED on bf16 MFMA and the survivors rechecked
+// exactly. Same grid, tile, arguments and outputs as pointmlp3_max_fwd_kernel, and the same bits in every output.
+//
+// Layer 3 (128 -> C3) feeds a max over points: of a tile's 128 values per channel only the winner leaves the kernel.
+//  screen  S[p][c] = sum_k (ah aw + ah wl + al wh) on v_mfma_f32_32x32x16_bf16 (16x the fp32 MFMA rate), where
+//          xh = bf16(x), xl = bf16(x - xh): both operands split in two bf16 terms, the lo x lo product dropped. Three
+//          MFMAs per k-step instead of one buy a bound 65x tighter than the single product's 2^-7: 1.0x candidates per
+//          (tile, channel) instead of 4.3 (measured), and the recheck, not the screen, is what costs. A wave
+//          owns WHOLE channel blocks (block = 32 channels; blocks wave, wave + 8, ...) and all 128 points: its A
+//          operands come from two bf16 images of h2 in LDS (hi, lo), W3 rows are read in fp32 once
+//          per workgroup and converted in registers, so the cross-point max never leaves the wave.
+//  bound   |v - S| <= E = PMS_C na[p] nw[c]  (pointmlp_screen_bound.h; Cauchy-Schwarz form: one norm per point, made
+//          once per tile, one per channel, made from the fp32 row the lane holds anyway).
+//  select  L = max_p (S - E) over the tile's valid points; candidates are the points with S + E >= L. They contain
+//          the exact arg-max and every exact tie with it.
+//  recheck one lane per candidate runs the exact kernel's fmaf chain (h2 from LDS, the fp32 W3 row from L2) and
+//          enters (value, lowest point) into the channel's 64-bit key with an LDS max: order-free, so deterministic.
+//  fallback (wave-uniform) the exact fp32 MFMA block on the same h2: a tile with a non-finite or huge h2, a channel
+//          block with a non-finite or huge W3 row, a block with more than PMS_CAP candidates.
+#include "pc3d_common.h"
+#include "pointmlp_body.h"
+#include "pointmlp_screen_bound.h"
+
+namespace pc3d {
+
+using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+
+constexpr int PMS_CAP = 128;                               // candidates per (tile, channel block) before it falls back
+constexpr int PMS_SLOTS = PM_MAXC3F / 32 / (PM_FT / 64);   // channel blocks per wave (4)
+constexpr int PMS_WLIST = PMS_SLOTS * PMS_CAP;             // list entries per wave
+constexpr int PMS_LDA = PM_C2 + 8;                         // bf16 row stride: +16 B keeps ds_read_b128 conflict-free
+// dynamic LDS: h2 + xs (69,120 B) | na [128] f32 | key [1024] u64 | lists [8][512] u16 | bf16 h2 hi, lo [2][128][136]
+// = 155,648 B
+constexpr size_t PMS_LDS_BYTES = (size_t)PM_FWD_LDS_FLOATS * 4 + PM_TP * 4 + (size_t)PM_MAXC3F * 8 +
+                                 (PM_FT / 64) * PMS_WLIST * 2 + 2 * (size_t)PM_TP * PMS_LDA * 2;
+static_assert(PMS_LDS_BYTES + 1024 <= 160 * 1024, "one workgroup's LDS on gfx950");
+static_assert((PM_FWD_LDS_FLOATS * 4 + PM_TP * 4) % 8 == 0, "the keys are 8-byte aligned");
+static_assert(PM_TP == 128 && PMS_SLOTS <= 4, "a list entry is slot << 12 | channel-in-block << 7 | point");
+
+struct PMScreenDbg {
+  int32_t* stats;    // [B, ntiles, 2]: candidates rechecked, channel blocks that fell back (added to)
+  float* dbg_S;      // [B, N, C3] or null (screened blocks only)
+  float* dbg_E;
+  int stop_after;    // timing only (outputs are then garbage): 1 prologue + norms, 2 + screen, 3 + select, 0 everything
+};
+
+// eight fp32 values as two bf16 terms each: xh = bf16(x), xl = bf16(x - xh) (the difference is exact in fp32)
+__device__ __forceinline__ void pms_split8(const float4& lo, const float4& hi, bf16x8& oh, bf16x8& ol) {
+  const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    oh[i] = (__bf16)v[i];
+    ol[i] = (__bf16)(v[i] - (float)oh[i]);
+  }
+}
+
+// accumulator register e of point sub-tile pt, lane half h  ->  point of the tile
+__device__ __forceinline__ constexpr int pms_point(int pt, int e, int h) { return pt * 32 + (e & 3) + 8 * (e >> 2) + 4 * h; }
+
+// L = max over the lane's points of S - E; then, given the channel's L, the 64 candidate flags (bit 16 * (pt & 1) + e of
+// word pt >> 1). s_na holds +inf for the points past the end of a ragged last tile: their S - E is -inf, so they never
+// raise L, and the caller clears their flags.
+__device__ __forceinline__ float pms_lower(const f32x16 (&acc)[4], const float* s_na, float cw, int h) {
+  float L = -__builtin_inff();
+#pragma unroll
+  for (int pt = 0; pt < 4; ++pt)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float4 na = *reinterpret_cast<const float4*>(s_na + pt * 32 + 8 * q + 4 * h);
+      L = fmaxf(L, pms_lo(acc[pt][4 * q + 0], na.x, cw));
+      L = fmaxf(L, pms_lo(acc[pt][4 * q + 1], na.y, cw));
+      L = fmaxf(L, pms_lo(acc[pt][4 * q + 2], na.z, cw));
+      L = fmaxf(L, pms_lo(acc[pt][4 * q + 3], na.w, cw));
+    }
+  return L;
+}
+__device__ __forceinline__ void pms_flags(const f32x16 (&acc)[4], const float* s_na, float cw, int h, float L,
+                                          unsigned (&flags)[2]) {
+#pragma unroll
+  for (int wd = 0; wd < 2; ++wd) {
+    unsigned f = 0u;                      // shifted in from the top bit down: no 32 mask constants held in registers
+#pragma unroll
+    for (int pq = 7; pq >= 0; --pq) {
+      const int pt = 2 * wd + (pq >> 2), q = pq & 3;
+      const float4 na = *reinterpret_cast<const float4*>(s_na + pt * 32 + 8 * q + 4 * h);
+      f = (f << 1) | (pms_hi(acc[pt][4 * q + 3], na.w, cw) >= L ? 1u : 0u);
+      f = (f << 1) | (pms_hi(acc[pt][4 * q + 2], na.z, cw) >= L ? 1u : 0u);
+      f = (f << 1) | (pms_hi(acc[pt][4 * q + 1], na.y, cw) >= L ? 1u : 0u);
+      f = (f << 1) | (pms_hi(acc[pt][4 * q + 0], na.x, cw) >= L ? 1u : 0u);
+    }
+    flags[wd] = f;
+  }
+}
+
+// The exact kernel's layer 3 + max for ONE channel block and all four point sub-tiles, by one wave, A operands from the
+// fp32 h2 in LDS: the same MFMA chain per (point, channel), the same selects in the same order, so the same bits.
+__device__ __forceinline__ void pms_exact_block(const float* h2, const float* W3, const float* b3, int cb, int n0, int N,
+                                             float* out_val, int32_t* out_idx) {
+  const int lane = threadIdx.x & 63;
+  const int r = lane & 31, h = lane >> 5;
+  float4 bw[PM_C2 / 8];
+  const float* wrow = W3 + (int64_t)(cb * 32 + r) * PM_C2 + 4 * h;
+#pragma unroll
+  for (int t = 0; t < PM_C2 / 8; ++t) bw[t] = *reinterpret_cast<const float4*>(wrow + 8 * t);
+  float tbest = 0.f;
+  int tbi = 0;
+#pragma unroll 1
+  for (int pt = 0; pt < 4; ++pt) {
+    f32x16 acc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+#pragma unroll
+    for (int t = 0; t < PM_C2 / 8; ++t) {
+      const float4 av = *reinterpret_cast<const float4*>(h2 + (pt * 32 + r) * PM_LD2 + 8 * t + 4 * h);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bw[t].x, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bw[t].y, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bw[t].z, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bw[t].w, acc, 0, 0, 0);
+    }
+    float best = -__builtin_inff();
+    int be = 0;
+    const int base = n0 + pt * 32;
+#pragma unroll
+    for (int e = 0; e < 16; ++e)      // ascending point index in e for fixed h: strict > keeps the lowest
+      if (base + (e & 3) + 8 * (e >> 2) + 4 * h < N && acc[e] > best) best = acc[e], be = (e & 3) + 8 * (e >> 2);
+    int bi = best == -__builtin_inff() ? base : base + be + 4 * h;
+    argmax_xor32(best, bi);
+    if (pt == 0 || best > tbest) tbest = best, tbi = bi;   // ascending sub-tile, strict >: the exact kernel's cross-wave max
+  }
+  if (h == 0) {
+    out_val[cb * 32 + r] = tbest + b3[cb * 32 + r];
+    out_idx[cb * 32 + r] = tbi;
+  }
+}
+
+// DBG: stats and the truncated forms for phase timing; DUMP: dbg_S / dbg_E as well (tests of tiny shapes: it spills).
+// The production kernel is <false, false> and carries none of it.
+template <bool DBG, bool DUMP>
+__global__ __launch_bounds__(PM_FT) __attribute__((amdgpu_waves_per_eu(2, 2))) void pointmlp3_max_fwd_screen_kernel(
+    PMFwdArgs a, PMScreenDbg d) {
+  extern __shared__ __attribute__((aligned(16))) float pms_lds[];
+  float* h2 = pms_lds;                                                              // [128][132] fp32, kept to the end
+  float* s_na = pms_lds + PM_FWD_LDS_FLOATS;                                        // [128] upper bounds of ||h2[p]||
+  unsigned long long* s_key = reinterpret_cast<unsigned long long*>(s_na + PM_TP);  // [C3] (value, lowest point) keys
+  unsigned short* s_list = reinterpret_cast<unsigned short*>(s_key + PM_MAXC3F);    // [8 waves][PMS_WLIST]
+  __bf16* s_a16 = reinterpret_cast<__bf16*>(s_list + (PM_FT / 64) * PMS_WLIST);     // [128][PMS_LDA] bf16 image of h2: hi
+  __bf16* s_a16l = s_a16 + PM_TP * PMS_LDA;                                         // and lo terms
+  pm_fwd_prologue(a, pms_lds);
+  const int tile = blockIdx.x, b = blockIdx.y;
+  const int n0 = tile * PM_TP;
+  const int nvalid = a.N - n0;            // >= 1
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = lane & 31, h = lane >> 5;
+  const int64_t obase = ((int64_t)b * a.ntiles + tile) * a.C3;
+
+  // ---- one norm per point (4 threads per point, 32 k each, fixed order), h2's bf16 image and the keys' start value
+  bool bad;
+  {
+    const int p = threadIdx.x >> 2, q = threadIdx.x & 3;
+    const float* row = h2 + p * PM_LD2 + 32 * q;
+    float ss = 0.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const float4 v = *reinterpret_cast<const float4*>(row + 8 * t), u = *reinterpret_cast<const float4*>(row + 8 * t + 4);
+      ss = __builtin_fmaf(v.x, v.x, ss), ss = __builtin_fmaf(v.y, v.y, ss);
+      ss = __builtin_fmaf(v.z, v.z, ss), ss = __builtin_fmaf(v.w, v.w, ss);
+      ss = __builtin_fmaf(u.x, u.x, ss), ss = __builtin_fmaf(u.y, u.y, ss);
+      ss = __builtin_fmaf(u.z, u.z, ss), ss = __builtin_fmaf(u.w, u.w, ss);
+      bf16x8 vh, vl;
+      pms_split8(v, u, vh, vl);
+      *reinterpret_cast<bf16x8*>(s_a16 + p * PMS_LDA + 32 * q + 8 * t) = vh;
+      *reinterpret_cast<bf16x8*>(s_a16l + p * PMS_LDA + 32 * q + 8 * t) = vl;
+    }
+    ss += __shfl_xor(ss, 1, 64);
+    ss += __shfl_xor(ss, 2, 64);
+    const float na = pms_norm_up(ss);
+    bad = !pms_norm_ok(na);               // NaN, inf or huge h2 anywhere in the tile: no screen for this tile
+    if (q == 0) s_na[p] = p < nvalid ? na : __builtin_inff();   // past the end of a ragged tile: see pms_lower
+    for (int c = threadIdx.x; c < a.C3; c += PM_FT) s_key[c] = 0ull;
+  }
+  const bool tile_bad = __syncthreads_or(bad ? 1 : 0) != 0;
+  if (DBG && d.stop_after == 1) return;
+
+  unsigned vmask[2] = {0u, 0u};           // the lane's 64 points that exist (all of them but in a ragged last tile)
+#pragma unroll
+  for (int pt = 0; pt < 4; ++pt)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) vmask[pt >> 1] |= (pms_point(pt, e, h) < nvalid) ? (1u << (16 * (pt & 1) + e)) : 0u;
+  const int nblk = a.C3 / 32;
+  unsigned short* my_list = s_list + wave * PMS_WLIST;
+  int wave_cnt = 0, nfall = 0;
+  unsigned screened = 0u;                 // bit slot: that block of the wave went through the screen
+  float sink = 0.f;
+#pragma unroll 1
+  for (int slot = 0; slot < PMS_SLOTS; ++slot) {
+    const int cb = wave + (PM_FT / 64) * slot;
+    if (cb >= nblk) break;                // (uniform)
+    bool fall = tile_bad;
+    float4 w[PM_C2 / 8];
+    float cw = 0.f;
+    if (!fall) {                          // the block's fp32 rows: lane (r, h) holds W3[32 cb + r][16 t + 8 h + 0..7]
+      const float* wrow = a.W3 + (int64_t)(cb * 32 + r) * PM_C2 + 8 * h;
+      float ss = 0.f;
+#pragma unroll
+      for (int t = 0; t < PM_C2 / 16; ++t) {
+        w[2 * t] = *reinterpret_cast<const float4*>(wrow + 16 * t);
+        w[2 * t + 1] = *reinterpret_cast<const float4*>(wrow + 16 * t + 4);
+      }
+#pragma unroll
+      for (int t = 0; t < PM_C2 / 8; ++t) {
+        ss = __builtin_fmaf(w[t].x, w[t].x, ss), ss = __builtin_fmaf(w[t].y, w[t].y, ss);
+        ss = __builtin_fmaf(w[t].z, w[t].z, ss), ss = __builtin_fmaf(w[t].w, w[t].w, ss);
+      }
+      ss = sum_xor32(ss);
+      const float nw = pms_norm_up(ss);
+      cw = pms_cw(nw);
+      fall = __builtin_amdgcn_ballot_w64(!pms_norm_ok(nw)) != 0ull;   // a non-finite or huge W3 row in the block
+    }
+    if (!fall) {
+      f32x16 acc[4];
+#pragma unroll
+      for (int pt = 0; pt < 4; ++pt)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[pt][e] = 0.f;
+#pragma unroll
+      for (int t = 0; t < PM_C2 / 16; ++t) {
+        bf16x8 bh, bl;
+        pms_split8(w[2 * t], w[2 * t + 1], bh, bl);
+#pragma unroll
+        for (int pt = 0; pt < 4; ++pt) {   // A: lane (r, h) holds the terms of h2[32 pt + r][16 t + 8 h + 0..7]
+          const bf16x8 ah = *reinterpret_cast<const bf16x8*>(s_a16 + (pt * 32 + r) * PMS_LDA + 16 * t + 8 * h);
+          const bf16x8 al = *reinterpret_cast<const bf16x8*>(s_a16l + (pt * 32 + r) * PMS_LDA + 16 * t + 8 * h);
+          acc[pt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[pt], 0, 0, 0);
+          acc[pt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[pt], 0, 0, 0);
+          acc[pt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[pt], 0, 0, 0);
+        }
+      }
+      if (DBG && d.stop_after == 2) {
+#pragma unroll
+        for (int pt = 0; pt < 4; ++pt)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) sink += acc[pt][e];
+        continue;
+      }
+      if (DUMP && d.dbg_S != nullptr) {
+        int c3v = a.C3;
+        unsigned vm[2] = {vmask[0], vmask[1]};
+        asm volatile("" : "+v"(c3v), "+v"(vm[0]), "+v"(vm[1]));   // opaque: nothing of the 64 stores is hoisted out of the block loop
+        const int64_t o0 = ((int64_t)b * a.N + n0) * a.C3 + cb * 32 + r;
+#pragma unroll
+        for (int pt = 0; pt < 4; ++pt)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) {
+            const int p = pms_point(pt, e, h);
+            if ((vm[pt >> 1] >> (16 * (pt & 1) + e)) & 1u) {
+              d.dbg_S[o0 + (int64_t)p * c3v] = acc[pt][e];
+              d.dbg_E[o0 + (int64_t)p * c3v] = pms_E(s_na[p], cw);
+            }
+          }
+      }
+      unsigned flags[2];
+      float L = pms_lower(acc, s_na, cw, h);
+      L = fmaxf(L, __shfl_xor(L, 32, 64));
+      pms_flags(acc, s_na, cw, h, L, flags);
+      flags[0] &= vmask[0], flags[1] &= vmask[1];
+      const int cnt = __builtin_popcount(flags[0]) + __builtin_popcount(flags[1]);
+      int incl = cnt;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += v;
+      }
+      const int total = __builtin_amdgcn_readlane(incl, 63);
+      if (total > PMS_CAP) {
+        fall = true;                      // (uniform) more candidates than the list holds: the exact block instead
+      } else {
+        int off = wave_cnt + incl - cnt;  // wave_cnt + total <= PMS_WLIST: every slot adds at most PMS_CAP
+#pragma unroll
+        for (int wd = 0; wd < 2; ++wd) {
+          unsigned f = flags[wd];
+          while (f) {
+            const int bit = __builtin_ctz(f);
+            f &= f - 1;
+            const int p = pms_point(2 * wd + (bit >> 4), bit & 15, h);
+            my_list[off++] = (unsigned short)((slot << 12) | (r << 7) | p);
+          }
+        }
+        wave_cnt += total;
+        screened |= 1u << slot;
+      }
+    }
+    if (fall) {
+      pms_exact_block(h2, a.W3, a.b3, cb, n0, a.N, a.part_val + obase, a.part_idx + obase);
+      ++nfall;
+    }
+  }
+  if (DBG && d.stop_after == 2) {
+    if (sink == 12345.678f) a.part_val[obase] = sink;   // keeps the products alive
+    return;
+  }
+  if (DBG && d.stats != nullptr && lane == 0) {
+    int32_t* st = d.stats + ((int64_t)b * a.ntiles + tile) * 2;
+    if (wave_cnt) atomicAdd(st, wave_cnt);
+    if (nfall) atomicAdd(st + 1, nfall);
+  }
+  if (DBG && d.stop_after == 3) {
+    if (wave_cnt == 123456789) a.part_val[obase] = 0.f;
+    return;
+  }
+
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the wave's list entries, written by other lanes
+  // ---- recheck: one lane per candidate, the exact kernel's chain (t ascending; x, y, z, w; k = 8t + c, then 8t + 4 + c)
+  for (int i = lane; i < wave_cnt; i += 64) {
+    const int e = my_list[i];
+    const int p = e & 127, c = (wave + (PM_FT / 64) * (e >> 12)) * 32 + ((e >> 7) & 31);
+    const float4* wr = reinterpret_cast<const float4*>(a.W3 + (int64_t)c * PM_C2);
+    const float4* ar = reinterpret_cast<const float4*>(h2 + p * PM_LD2);
+    float4 wv[PM_C2 / 4];                 // the whole row in flight at once: one round trip per pass
+#pragma unroll
+    for (int t = 0; t < PM_C2 / 4; ++t) wv[t] = wr[t];
+    float v = 0.f;
+#pragma unroll
+    for (int t = 0; t < PM_C2 / 8; ++t) {
+      const float4 a0 = ar[2 * t], a1 = ar[2 * t + 1];
+      const float4 w0 = wv[2 * t], w1 = wv[2 * t + 1];
+      v = __builtin_fmaf(a0.x, w0.x, v), v = __builtin_fmaf(a1.x, w1.x, v);
+      v = __builtin_fmaf(a0.y, w0.y, v), v = __builtin_fmaf(a1.y, w1.y, v);
+      v = __builtin_fmaf(a0.z, w0.z, v), v = __builtin_fmaf(a1.z, w1.z, v);
+      v = __builtin_fmaf(a0.w, w0.w, v), v = __builtin_fmaf(a1.w, w1.w, v);
+    }
+    // key: the value as an ordered integer (both zeros as one value), then the LOWEST point, then whether it was -0:
+    // the largest key is the exact kernel's winner (v is finite here: the norms' range check rules out overflow)
+    const unsigned vb = __builtin_bit_cast(unsigned, v);
+    const unsigned zb = (v == 0.f) ? 0u : vb;
+    const unsigned ord = (zb & 0x80000000u) ? ~zb : (zb | 0x80000000u);
+    const unsigned low = ((unsigned)(127 - p) << 1) | ((vb == 0x80000000u) ? 1u : 0u);
+    atomicMax(&s_key[c], ((unsigned long long)ord << 32) | low);
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // only this wave touches its channels' keys
+  for (int i = lane; i < 32 * PMS_SLOTS; i += 64) {
+    const int slot = i >> 5;
+    if (!((screened >> slot) & 1u)) continue;
+    const int c = (wave + (PM_FT / 64) * slot) * 32 + (i & 31);
+    const unsigned long long key = s_key[c];
+    const unsigned ord = (unsigned)(key >> 32), low = (unsigned)key;
+    unsigned vb = (ord & 0x80000000u) ? (ord & 0x7fffffffu) : ~ord;
+    if (low & 1u) vb = 0x80000000u;
+    a.part_val[obase + c] = __builtin_bit_cast(float, vb) + a.b3[c];
+    a.part_idx[obase + c] = n0 + 127 - (int)((low >> 1) & 127u);
+  }
+}
+
+// 0: launched. 1: not launched — the kernel needs its dynamic-LDS attribute, which is set at first use on a device and
+// never while the stream is capturing; the caller then launches the exact kernel.
+template <bool DBG, bool DUMP>
+static int pms_launch_t(const PMFwdArgs& a, int B, hipStream_t st, const PMScreenDbg& d) {
+  static bool done[64] = {};
+  int dev = 0;
+  PC3D_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "pointmlp3 screen: no current device");
+  auto kernel = pointmlp3_max_fwd_screen_kernel<DBG, DUMP>;
+  if (!done[dev]) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
+      (void)hipGetLastError();
+      return 1;
+    }
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)PMS_LDS_BYTES);
+    PC3D_REQUIRE(e == hipSuccess, "pointmlp3 screen: hipFuncSetAttribute(MaxDynamicSharedMemorySize): %s", hipGetErrorString(e));
+    done[dev] = true;
+  }
+  hipLaunchKernelGGL(kernel, dim3(a.ntiles, B), dim3(PM_FT), PMS_LDS_BYTES, st, a, d);
+  return 0;
+}
+
+int pm_fwd_screen_launch(const PMFwdArgs& a, int B, void* stream, int32_t* stats, float* dbg_S, float* dbg_E,
+                         int stop_after) {
+  const PMScreenDbg d{stats, dbg_S, dbg_E, stop_after};
+  if (dbg_S || dbg_E) return pms_launch_t<true, true>(a, B, as_stream(stream), d);
+  if (stats || stop_after) return pms_launch_t<true, false>(a, B, as_stream(stream), d);
+  return pms_launch_t<false, false>(a, B, as_stream(stream), d);
+}
+
+}  // namespace pc3d

@@ -388,13 +388,19 @@ def pointmlp3_fold_raw(part_val, part_idx, relu_last, serial=False):
     return pooled, argidx
 
 
-def pointmlp3_max_fwd_raw(x, weights, relu_last, T=None, x_cf=True, fold=True, want_masks=False, T_head=None, serial=False):
+def pointmlp3_max_fwd_raw(x, weights, relu_last, T=None, x_cf=True, fold=True, want_masks=False, T_head=None, serial=False,
+                          exact=False, screen_dbg=None):
     """x [B,3,N] (x_cf) or [B,N,3]; weights = (W1[64,3], b1, W2[128,64], b2, W3[C3,128], b3) with eval-BN folded.
     Returns (pooled [B,C3] f32, argidx [B,C3] i32) and, with want_masks, a third item (mask1 [B,N] i64, mask2 [B,N,4]
     i32): the per-point ReLU decisions of layers 1 and 2 as bit masks, which pointmlp3_max_bwd_raw consumes.
     T_head = (h [B,K], W [9,K], b [9]): the input transform T = h @ W.T + b is computed in the launch's prologue
     (no launch of its own) and returned as a last extra item [B,9].
-    serial: fold with the earlier fold kernel (same bits; parity tests and tools/bench_small_launches.py only)."""
+    serial: fold with the earlier fold kernel (same bits; parity tests and tools/bench_small_launches.py only).
+    exact: launch the exact fp32 kernel; the default screens layer 3 on bf16 MFMA and rechecks the survivors exactly
+    (the same bits). screen_dbg: a dict, for tests and tools — the screened launch's debug instantiation runs and the
+    dict receives "stats" [B,ntiles,2] i32 (candidates rechecked, channel blocks that fell back to the exact block);
+    with screen_dbg["dump"] set also "S" and "E" [B,N,C3] (tiny shapes), with screen_dbg["stop_after"] = 1 / 2 / 3
+    the launch ends after that phase (timing only: the outputs are undefined)."""
     xp, xbs, xps, xcs, B, N = _pts(x, x_cf, "x")
     W1, b1, W2, b2, W3, b3 = weights[:6]
     for w in weights:
@@ -419,6 +425,9 @@ def pointmlp3_max_fwd_raw(x, weights, relu_last, T=None, x_cf=True, fold=True, w
             pooled.data_ptr() if fold and not serial else 0, argidx.data_ptr() if fold and not serial else 0,
             masks[0].data_ptr() if masks else 0, masks[1].data_ptr() if masks else 0, _stream())
     T_out = None
+    if screen_dbg is not None and exact:
+        raise ValueError("pointmlp3_max_fwd_raw: screen_dbg belongs to the screened launch, not to exact=True")
+    sfx = "exact_" if exact else ""
     with torch.cuda.device(dev):
         if T_head is not None:
             if T is not None:
@@ -427,10 +436,21 @@ def pointmlp3_max_fwd_raw(x, weights, relu_last, T=None, x_cf=True, fold=True, w
             if h.shape[0] != B or Wt.shape != (9, h.shape[1]) or bt.numel() != 9 or not (h.is_contiguous() and Wt.is_contiguous()):
                 raise ValueError("pointmlp3_max_fwd_raw: T_head = (h [B,K], W [9,K], b [9]) contiguous expected")
             T_out = torch.empty((B, 9), dtype=torch.float32, device=dev)
-            _lib.call("pc3d_pointmlp3_max_fwd_th_f32", xp, xbs, xps, xcs, B, N, h.data_ptr(), Wt.data_ptr(), bt.data_ptr(),
+        if screen_dbg is not None:
+            screen_dbg["stats"] = torch.zeros((B, ntiles, 2), dtype=torch.int32, device=dev)
+            dS = dE = None
+            if screen_dbg.get("dump"):
+                dS = torch.full((B, N, C3), float("nan"), dtype=torch.float32, device=dev)
+                dE = torch.full((B, N, C3), float("nan"), dtype=torch.float32, device=dev)
+                screen_dbg["S"], screen_dbg["E"] = dS, dE
+            th = (h.data_ptr(), Wt.data_ptr(), bt.data_ptr(), h.shape[1], T_out.data_ptr()) if T_head is not None else (0, 0, 0, 0, 0)
+            _lib.call("pc3d_pointmlp3_max_fwd_screen_dbg_f32", xp, xbs, xps, xcs, B, N, _ptr(T), *th, *tail[:-1],
+                      screen_dbg["stats"].data_ptr(), _ptr(dS), _ptr(dE), int(screen_dbg.get("stop_after", 0)), tail[-1])
+        elif T_head is not None:
+            _lib.call("pc3d_pointmlp3_max_fwd_%sth_f32" % sfx, xp, xbs, xps, xcs, B, N, h.data_ptr(), Wt.data_ptr(), bt.data_ptr(),
                       h.shape[1], T_out.data_ptr(), *tail)
         else:
-            _lib.call("pc3d_pointmlp3_max_fwd_f32", xp, xbs, xps, xcs, B, N, _ptr(T), *tail)
+            _lib.call("pc3d_pointmlp3_max_fwd_%sf32" % sfx, xp, xbs, xps, xcs, B, N, _ptr(T), *tail)
         if fold and serial:
             _lib.call("pc3d_pointmlp3_fold_f32", part_val.data_ptr(), part_idx.data_ptr(), B, ntiles, C3,
                       1 if relu_last else 0, pooled.data_ptr(), argidx.data_ptr(), 1, _stream())

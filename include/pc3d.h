@@ -358,7 +358,7 @@ int pc3d_nn_bwd_f32(const float* a, int64_t a_bs, int64_t a_ps, int64_t a_cs,
  *   mask1 [B,N] u64, mask2 [B,N,4] u32 (both or neither)  the ReLU decisions of layers 1 and 2 per point (bit c of
  *          mask1 = channel c of layer 1 is positive; word j bit r of mask2 = channel 32j+r of layer 2 is positive),
  *          which the backward launch consumes instead of recomputing the two layers
- * fp32 throughout: layer 2/3 run on v_mfma_f32_32x32x2_f32 (exact fp32 FMA chains).
+ * fp32 throughout: layer 2/3 are exact fp32 FMA chains (v_mfma_f32_32x32x2_f32; layer 3 screened, see below).
  * ------------------------------------------------------------------------------------------------------- */
 int pc3d_pointmlp3_tile_points(void);
 int pc3d_pointmlp3_bwd_tile_points(void);
@@ -382,6 +382,35 @@ int pc3d_pointmlp3_max_fwd_th_f32(const float* x, int64_t x_bs, int64_t x_ps, in
                                   const float* b3, int C1, int C2, int C3, int relu_last, float* part_val,
                                   int32_t* part_idx, float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2,
                                   void* stream);
+
+/* Layer 3 of the two entries above is SCREENED: S = h2 . W3 with both operands split in two bf16 terms (three products
+ * on v_mfma_f32_32x32x16_bf16) with a rigorous bound E (csrc/pointmlp_screen_bound.h), and only the points whose S + E reaches the tile's best S - E are recomputed
+ * as the exact fp32 fmaf chain; tiles / channel blocks with non-finite or huge operands, or with more candidates than
+ * their list holds, run the exact fp32 MFMA block. Every output is the same bits as the exact kernel's, which these two
+ * entries (same arguments) always launch: */
+int pc3d_pointmlp3_max_fwd_exact_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                     const float* T, const float* W1, const float* b1, const float* W2,
+                                     const float* b2, const float* W3, const float* b3, int C1, int C2, int C3,
+                                     int relu_last, float* part_val, int32_t* part_idx,
+                                     float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2, void* stream);
+int pc3d_pointmlp3_max_fwd_exact_th_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                        const float* th_in, const float* th_W, const float* th_b, int th_K, float* T_out,
+                                        const float* W1, const float* b1, const float* W2, const float* b2,
+                                        const float* W3, const float* b3, int C1, int C2, int C3, int relu_last,
+                                        float* part_val, int32_t* part_idx, float* pooled, int32_t* argidx,
+                                        uint64_t* mask1, uint32_t* mask2, void* stream);
+/* The screened launch with its optional outputs (a separate kernel instantiation: tests and tools/bench_pointmlp_screen.py).
+ * T or (th_in, th_W, th_b, th_K, T_out) or neither. stats [B, ntiles, 2] i32 (required, ADDED to: zero it first):
+ * candidates rechecked, channel blocks that ran the exact block. dbg_S / dbg_E [B, N, C3] f32 (both or neither; tiny
+ * shapes): the screen's value and bound of every (point, channel) of a screened block. stop_after 1 / 2 / 3: return
+ * after the prologue and norms / the screen / the selection (timing only: the outputs are then undefined); 0: all. */
+int pc3d_pointmlp3_max_fwd_screen_dbg_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                          const float* T, const float* th_in, const float* th_W, const float* th_b,
+                                          int th_K, float* T_out, const float* W1, const float* b1, const float* W2,
+                                          const float* b2, const float* W3, const float* b3, int C1, int C2, int C3,
+                                          int relu_last, float* part_val, int32_t* part_idx, float* pooled,
+                                          int32_t* argidx, uint64_t* mask1, uint32_t* mask2, int32_t* stats,
+                                          float* dbg_S, float* dbg_E, int stop_after, void* stream);
 
 /* Backward-to-input of the above (weights are frozen during an attack: no weight gradients, SURVEY A-14).
  * g_pooled [B,C3] is the upstream gradient on `pooled`; with relu_last the caller zeroes it where pooled <= 0.
