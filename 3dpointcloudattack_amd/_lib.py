@@ -101,6 +101,9 @@ SIGNATURES = {
     "pc3d_gather_max_bwd_f32": [_P, _P, _I, _I, _I, _P, _I, _P],
     "pc3d_graph_laplacian_f32": _PTS + [_P, _I, _I, _I, _P, _P],
     "pc3d_spectral_reproject_f32": [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
+    "pc3d_spectral_reproject_sum_f32": [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
+    "pc3d_aof_record_f32": [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "pc3d_aof_update_f32": [_P] * 8 + [_I, _I, _D, _D, _D, _D, _F, _P, _I, _P],
     "pc3d_rowdot3_f32": [_P, _P, _I, _I, _I, _I, _P, _P, _P],
     "pc3d_clip_f32": _PTS + _PTS + _PTS + [_I, _I, _I, _F] + _PTS + [_P],
     "pc3d_adam_clip_step_f32": _PTS + _PTS + _PTS + [_P, _P] + _PTS + _PTS + [_I, _I, _D, _D, _D, _D, _F, _P, _I, _P],

@@ -90,6 +90,7 @@ struct RowdotArgs {
   int R, K, split;    // columns k < split go to out_lo, the others to out_hi (out_hi null: one output, all columns)
   float* out_lo;      // [B, 3, R]
   float* out_hi;      // [B, 3, R] or null
+  float* out_sum;     // [B, 3, R] or null: out_lo + out_hi, added by the thread that holds both (out_hi given)
 };
 
 // sum over the 64 lanes, the same value (and the same summation tree) in every lane; VALU only
@@ -202,7 +203,10 @@ __global__ __launch_bounds__(64 * kRdWaves, 2) void rowdot3_kernel(RowdotArgs a)
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       a.out_lo[o + (int64_t)c * a.R] = keep[c];
-      if (SPLIT) a.out_hi[o + (int64_t)c * a.R] = keep[3 + c];
+      if (SPLIT) {
+        a.out_hi[o + (int64_t)c * a.R] = keep[3 + c];
+        if (a.out_sum) a.out_sum[o + (int64_t)c * a.R] = keep[c] + keep[3 + c];
+      }
     }
   }
 }
@@ -236,18 +240,22 @@ __global__ __launch_bounds__(256) void rowdot3_generic_kernel(RowdotArgs a) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       a.out_lo[o + (int64_t)c * a.R] = lo[c];
-      if (a.out_hi) a.out_hi[o + (int64_t)c * a.R] = hi[c];
+      if (a.out_hi) {
+        a.out_hi[o + (int64_t)c * a.R] = hi[c];
+        if (a.out_sum) a.out_sum[o + (int64_t)c * a.R] = lo[c] + hi[c];
+      }
     }
   }
 }
 
 static int rowdot3(const char* nm, const float* mat, const float* vec, int B, int R, int K, int split, float* out_lo, float* out_hi,
-                   void* stream) {
+                   void* stream, float* out_sum = nullptr) {
   PC3D_REQUIRE(B >= 0 && R >= 1 && K >= 1 && split >= 0 && split <= K, "%s: bad sizes B=%d R=%d K=%d split=%d", nm, B, R, K, split);
   PC3D_REQUIRE(B <= 65535, "%s: B=%d exceeds grid.y limit", nm, B);
   if (B == 0) return PC3D_OK;
   PC3D_REQUIRE(mat && vec && out_lo, "%s: null pointer", nm);
-  RowdotArgs a{mat, vec, R, K, split, out_lo, out_hi};
+  PC3D_REQUIRE(out_hi || !out_sum, "%s: a sum output needs both bands", nm);
+  RowdotArgs a{mat, vec, R, K, split, out_lo, out_hi, out_sum};
   hipStream_t st = as_stream(stream);
   const bool fast = K % 4 == 0 && ((reinterpret_cast<uintptr_t>(mat) | reinterpret_cast<uintptr_t>(vec)) & 15) == 0;
   if (fast) {
@@ -276,11 +284,25 @@ extern "C" int pc3d_rowdot3_f32(const float* mat, const float* vec, int B, int R
   return rowdot3("pc3d_rowdot3_f32", mat, vec, B, R, K, split, out_lo, out_hi, stream);
 }
 
+// sum (may be null): lfc + hfc, one fp32 add by the thread of the bands launch that holds both values
+static int spectral_reproject(const char* nm, const char* nm_coeff, const char* nm_bands, const float* adv, const float* V,
+                              const float* Vt, int B, int N, int lp, float* coeff, float* lfc, float* hfc, float* sum, void* stream) {
+  PC3D_REQUIRE(lp >= 0 && lp <= N, "%s: low_pass=%d outside [0, N=%d]", nm, lp, N);
+  PC3D_REQUIRE(coeff && lfc && hfc, "%s: null output", nm);
+  int rc = pc3d::rowdot3(nm_coeff, Vt, adv, B, N, N, N, coeff, nullptr, stream);
+  if (rc != PC3D_OK) return rc;
+  return pc3d::rowdot3(nm_bands, V, coeff, B, N, N, lp, lfc, hfc, stream, sum);
+}
+
 extern "C" int pc3d_spectral_reproject_f32(const float* adv, const float* V, const float* Vt, int B, int N, int lp, float* coeff,
                                            float* lfc, float* hfc, void* stream) {
-  PC3D_REQUIRE(lp >= 0 && lp <= N, "pc3d_spectral_reproject_f32: low_pass=%d outside [0, N=%d]", lp, N);
-  PC3D_REQUIRE(coeff && lfc && hfc, "pc3d_spectral_reproject_f32: null output");
-  int rc = rowdot3("pc3d_spectral_reproject_f32/coeff", Vt, adv, B, N, N, N, coeff, nullptr, stream);
-  if (rc != PC3D_OK) return rc;
-  return rowdot3("pc3d_spectral_reproject_f32/bands", V, coeff, B, N, N, lp, lfc, hfc, stream);
+  return spectral_reproject("pc3d_spectral_reproject_f32", "pc3d_spectral_reproject_f32/coeff", "pc3d_spectral_reproject_f32/bands",
+                            adv, V, Vt, B, N, lp, coeff, lfc, hfc, nullptr, stream);
+}
+
+extern "C" int pc3d_spectral_reproject_sum_f32(const float* adv, const float* V, const float* Vt, int B, int N, int lp, float* coeff,
+                                               float* lfc, float* hfc, float* sum, void* stream) {
+  PC3D_REQUIRE(sum != nullptr, "pc3d_spectral_reproject_sum_f32: null output");
+  return spectral_reproject("pc3d_spectral_reproject_sum_f32", "pc3d_spectral_reproject_sum_f32/coeff",
+                            "pc3d_spectral_reproject_sum_f32/bands", adv, V, Vt, B, N, lp, coeff, lfc, hfc, sum, stream);
 }

@@ -2500,10 +2500,12 @@ def graph_laplacian(xyz, k=30, cf=True):
     return L
 
 
-def spectral_reproject(adv, V, Vt, low_pass, lfc=None, hfc=None, coeff=None):
+def spectral_reproject(adv, V, Vt, low_pass, lfc=None, hfc=None, coeff=None, sum=None):
     """AOF's re-projection of adv [B,3,N] onto the graph-frequency bands of the basis V [B,N,N] (Vt = its transpose, kept
     beside it): returns (lfc, hfc) = (adv V)[..., :lp] V[..., :lp]^T, (adv V)[..., lp:] V[..., lp:]^T, written into the
-    given buffers when passed (TAOF_attack.py:114-126,164-170). No gradient (the reference runs it under no_grad)."""
+    given buffers when passed (TAOF_attack.py:114-126,164-170). No gradient (the reference runs it under no_grad).
+    sum: a [B,3,N] buffer that receives lfc + hfc from the same launches (pc3d_spectral_reproject_sum_f32); lfc, hfc keep
+    their bits. The outputs may be slices along dim 0 of larger buffers."""
     for nm, t in (("adv", adv), ("V", V), ("Vt", Vt)):
         _check(t, nm)
         if not t.is_contiguous():
@@ -2513,13 +2515,70 @@ def spectral_reproject(adv, V, Vt, low_pass, lfc=None, hfc=None, coeff=None):
         raise ValueError("spectral_reproject: adv [B,3,N], V and Vt [B,N,N] expected")
     mk = lambda t: torch.empty((B, 3, N), dtype=torch.float32, device=adv.device) if t is None else t
     lfc, hfc, coeff = mk(lfc), mk(hfc), mk(coeff)
-    for nm, t in (("lfc", lfc), ("hfc", hfc), ("coeff", coeff)):
+    for nm, t in (("lfc", lfc), ("hfc", hfc), ("coeff", coeff)) + ((("sum", sum),) if sum is not None else ()):
         if t.shape != (B, 3, N) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != adv.device:
             raise ValueError(f"spectral_reproject: {nm} must be a contiguous fp32 [B,3,N] tensor on adv's device")
     with torch.cuda.device(adv.device):
-        _lib.call("pc3d_spectral_reproject_f32", adv.data_ptr(), V.data_ptr(), Vt.data_ptr(), B, N, int(low_pass),
-                  coeff.data_ptr(), lfc.data_ptr(), hfc.data_ptr(), _stream())
+        if sum is None:
+            _lib.call("pc3d_spectral_reproject_f32", adv.data_ptr(), V.data_ptr(), Vt.data_ptr(), B, N, int(low_pass),
+                      coeff.data_ptr(), lfc.data_ptr(), hfc.data_ptr(), _stream())
+        else:
+            _lib.call("pc3d_spectral_reproject_sum_f32", adv.data_ptr(), V.data_ptr(), Vt.data_ptr(), B, N, int(low_pass),
+                      coeff.data_ptr(), lfc.data_ptr(), hfc.data_ptr(), sum.data_ptr(), _stream())
     return lfc, hfc
+
+
+def _aof_blocks(fn, B, N, dev, **tensors):
+    for nm, t in tensors.items():
+        if t is None:
+            continue
+        _check(t, f"{fn}: {nm}")
+        if t.shape != (B, 3, N) or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{fn}: {nm} must be a contiguous fp32 [B,3,N] tensor on one device, got {tuple(t.shape)}")
+
+
+def _aof_words(fn, B, dev, dtype, **tensors):
+    for nm, t in tensors.items():
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.shape != (B,) or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{fn}: {nm} must be a contiguous {dtype} [B] tensor on the clouds' device")
+
+
+def aof_record(adv, data, pred, lfc_pred, label, o_bestdist, o_bestscore, o_bestattack, dist_val=None, step=None):
+    """The untargeted AOF loop's bookkeeping (Eval_AOF.py:168-185) in one launch: dist = amax |adv - data| per cloud; where
+    pred != label and dist < o_bestdist and lfc_pred != label the three bests are updated IN PLACE (o_bestattack[b] =
+    adv[b]). adv, data, o_bestattack [B,3,N]; pred, lfc_pred, label, o_bestscore int64 [B]; o_bestdist, dist_val fp32 [B].
+    A NaN in a cloud gives dist NaN and no update. step: a 1-element int32 GPU tensor, advanced by one (the Adam step word)."""
+    B, _, N = adv.shape
+    _aof_blocks("aof_record", B, N, adv.device, adv=adv, data=data, o_bestattack=o_bestattack)
+    _aof_words("aof_record", B, adv.device, torch.int64, pred=pred, lfc_pred=lfc_pred, label=label, o_bestscore=o_bestscore)
+    _aof_words("aof_record", B, adv.device, torch.float32, o_bestdist=o_bestdist, dist_val=dist_val)
+    with torch.cuda.device(adv.device):
+        _lib.call("pc3d_aof_record_f32", adv.data_ptr(), data.data_ptr(), B, N, pred.data_ptr(), lfc_pred.data_ptr(),
+                  label.data_ptr(), o_bestdist.data_ptr(), o_bestscore.data_ptr(), o_bestattack.data_ptr(), _ptr(dist_val),
+                  _ptr(step), _stream())
+
+
+def aof_update(lfc, g1, g2, m, v, hfc, data, step, lr, budget, betas=(0.9, 0.999), eps=1e-8, out=None):
+    """The untargeted AOF loop between the backward and the re-projection (Eval_AOF.py:187-195) in one launch: Adam on lfc
+    (IN PLACE, with m and v) for the gradient g1 + g2, then out = ClipPointsLinf(budget)(lfc + hfc, data). The bits of
+    adam_clip_step(lfc, g1, ..., g2=g2) + torch.add + clip. `step`: an int or a 1-element int32 GPU tensor holding t."""
+    B, _, N = lfc.shape
+    if out is None:
+        out = torch.empty((B, 3, N), dtype=torch.float32, device=lfc.device)
+    _aof_blocks("aof_update", B, N, lfc.device, lfc=lfc, g1=g1, g2=g2, m=m, v=v, hfc=hfc, data=data, out=out)
+    if any(out.data_ptr() == t.data_ptr() for t in (lfc, g1, g2, m, v, hfc, data)):
+        raise ValueError("aof_update: out must not alias an input")
+    if isinstance(step, torch.Tensor):
+        step_dev, step_host = step.data_ptr(), 0
+    else:
+        step_dev, step_host = 0, int(step)
+    with torch.cuda.device(lfc.device):
+        _lib.call("pc3d_aof_update_f32", lfc.data_ptr(), g1.data_ptr(), g2.data_ptr(), m.data_ptr(), v.data_ptr(), hfc.data_ptr(),
+                  data.data_ptr(), out.data_ptr(), B, N, float(lr), float(betas[0]), float(betas[1]), float(eps), float(budget),
+                  step_dev, step_host, _stream())
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------

@@ -897,10 +897,36 @@ int pc3d_graph_laplacian_f32(const float* xyz, int64_t x_bs, int64_t x_ps, int64
  * torch.symeig / torch.linalg.eigh return it) and Vt = V^T [B,N,N], both contiguous. Sums in a fixed order. */
 int pc3d_spectral_reproject_f32(const float* adv, const float* V, const float* Vt, int B, int N, int lp, float* coeff,
                                 float* lfc, float* hfc, void* stream);
+/* The same two launches with a fourth output sum = lfc + hfc [B,3,N]: one fp32 add by the thread of the second launch
+ * that already holds both values (the bits of torch.add(lfc, hfc)), so the next iteration's adv_pc = lfc + hfc
+ * (attack/AOF/Eval_AOF.py:163) costs no launch. lfc, hfc keep the bits of pc3d_spectral_reproject_f32. Every output is
+ * its own pointer: lfc and sum may be the two halves of one [2B,3,N] buffer (the victim's stacked pass). */
+int pc3d_spectral_reproject_sum_f32(const float* adv, const float* V, const float* Vt, int B, int N, int lp, float* coeff,
+                                    float* lfc, float* hfc, float* sum, void* stream);
 /* The building block: out[b,c,r] = sum_k vec[b,c,k] * mat[b,r,k] for the 3 rows of vec [B,3,K] against every row of
  * mat [B,R,K]; with out_hi != NULL the columns k < split go to out_lo and the others to out_hi (both [B,3,R]). */
 int pc3d_rowdot3_f32(const float* mat, const float* vec, int B, int R, int K, int split, float* out_lo, float* out_hi,
                      void* stream);
+
+/* K12c  bookkeeping of the untargeted AOF loop on the device (attack/AOF/Eval_AOF.py:168-185), one workgroup per
+ * cloud: dist = max |adv - data| over the whole [3,N] cloud (an exact maximum: the bits of torch.amax); where
+ * pred != label && dist < o_bestdist && lfc_pred != label (strict <) update (o_bestdist, o_bestscore) and copy adv[b]
+ * into o_bestattack[b]. A NaN anywhere in the cloud makes dist NaN and, as numpy's `nan < x` is False, leaves the bests
+ * alone. adv, data, o_bestattack [B,3,N] contiguous; pred, lfc_pred, label int64 [B], each its own pointer (the two
+ * predictions may be the halves of one [2B] tensor); dist_val [B] (may be NULL) receives dist; *step (may be NULL) is
+ * incremented by one (the Adam step word that pc3d_aof_update_f32 reads next). */
+int pc3d_aof_record_f32(const float* adv, const float* data, int B, int N, const int64_t* pred, const int64_t* lfc_pred,
+                        const int64_t* label, float* o_bestdist, int64_t* o_bestscore, float* o_bestattack,
+                        float* dist_val, int32_t* step, void* stream);
+/* K12c  the untargeted AOF loop between the backward and the re-projection (attack/AOF/Eval_AOF.py:187-195), one thread
+ * per point: g = g1 + g2 (the two terms of the loss, already scaled); torch.optim.Adam on lfc with m, v in place and the
+ * step number t (>= 1) from *step_dev when non-NULL, else step_host, in the arithmetic of pc3d_adam_clip_step_f32;
+ * out = ClipPointsLinf(lfc + hfc, data): per-point L2 norm, budget / (norm + 1e-9) capped at 1, budget <= 0: none. The
+ * bits of pc3d_adam_clip_step_f32 (g2 given, no clip) + torch.add + pc3d_clip_f32 (mode 0). All tensors [B,3,N]
+ * contiguous, each its own pointer; out must not alias an input. */
+int pc3d_aof_update_f32(float* lfc, const float* g1, const float* g2, float* m, float* v, const float* hfc,
+                        const float* data, float* out, int B, int N, double lr, double beta1, double beta2, double eps,
+                        float budget, const int32_t* step_dev, int step_host, void* stream);
 
 /* Classifier tail in one launch: logits = c2 W3^T + b3 (fc3), log_softmax / pred / adversarial loss as
  * pc3d_cls_loss_f32, and g_c2 = (g_logits W3) * (c2 > 0) (fc3 backward + ReLU mask of fc2's activation). K2 <= 256,
