@@ -145,6 +145,12 @@ SIGNATURES = {
     "pc3d_pointmlp3_max_fwd_exact_th_f32": _PTS + [_I, _I] + [_P, _P, _P, _I, _P] + [_P] * 6 + [_I, _I, _I, _I] + [_P] * 6 + [_P],
     "pc3d_pointmlp3_max_fwd_screen_dbg_f32": _PTS + [_I, _I] + [_P, _P, _P, _P, _I, _P] + [_P] * 6 + [_I, _I, _I, _I]
     + [_P] * 6 + [_P, _P, _P, _I, _P],
+    "pc3d_pointmlp3_w3_prepare_f32": [_P, _I, _P, _P, _P, _P],
+    "pc3d_pointmlp3_max_fwd_prep_f32": _PTS + [_I, _I] + [_P] * 7 + [_I, _I, _I, _I] + [_P] * 6 + [_P, _P, _P] + [_P],
+    "pc3d_pointmlp3_max_fwd_prep_th_f32": _PTS + [_I, _I] + [_P, _P, _P, _I, _P] + [_P] * 6 + [_I, _I, _I, _I] + [_P] * 6
+    + [_P, _P, _P] + [_P],
+    "pc3d_pointmlp3_max_fwd_screen_dbg_prep_f32": _PTS + [_I, _I] + [_P, _P, _P, _P, _I, _P] + [_P] * 6 + [_I, _I, _I, _I]
+    + [_P] * 6 + [_P, _P, _P, _I] + [_P, _P, _P] + [_P],
     "pc3d_linear_pre_f32": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P],
     "pc3d_pointmlp3_max_bwd_f32": _PTS + [_I, _I] + [_P] * 7 + [_I, _I, _I] + [_P, _P, _P, _P] + _PTS + [_P, _I, _P],
     "pc3d_pointmlp3_max_bwd_twolist_f32": _PTS + [_I, _I] + [_P] * 7 + [_I, _I, _I] + [_P, _P, _P, _P] + _PTS + [_P, _I, _P],

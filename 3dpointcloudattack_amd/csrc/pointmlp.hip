@@ -892,7 +892,7 @@ static int pm_fwd_launch(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_c
                          const float* b3, int C1, int C2, int C3, int relu_last, float* part_val, int32_t* part_idx,
                          float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2, void* stream,
                          bool exact = false, int32_t* stats = nullptr, float* dbg_S = nullptr, float* dbg_E = nullptr,
-                         int stop_after = 0) {
+                         int stop_after = 0, const PMScreenPrep* prep = nullptr) {
   PC3D_REQUIRE(B >= 0 && N >= 1, "pc3d_pointmlp3_max_fwd_f32: bad sizes B=%d N=%d", B, N);
   PC3D_REQUIRE(C1 == PM_C1 && C2 == PM_C2 && C3 >= 32 && C3 % 32 == 0 && C3 <= PM_MAXC3F,
                "pc3d_pointmlp3_max_fwd_f32: unsupported widths %d/%d/%d (need 64/128/multiple of 32 <= 1024)", C1, C2, C3);
@@ -909,10 +909,11 @@ static int pm_fwd_launch(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_c
               th_in, th_W, th_b, th_K, th_out};
   hipStream_t st = as_stream(stream);
   // Layer 3 screened on bf16 MFMA and rechecked exactly (pointmlp_screen.hip: the same bits) at every shape this entry
-  // accepts; the exact kernel on request, and when the screened one cannot be launched yet (see pm_fwd_screen_launch).
+  // accepts, from the prepared image of W3 when the caller passes one; the exact kernel on request, and when the screened
+  // one cannot be launched yet (see pm_fwd_screen_launch).
   int rc = 1;
   if (!exact) {
-    rc = pm_fwd_screen_launch(a, B, stream, stats, dbg_S, dbg_E, stop_after);
+    rc = pm_fwd_screen_launch(a, B, stream, stats, dbg_S, dbg_E, stop_after, prep);
     if (rc < 0) return rc;
   }
   if (rc != 0) hipLaunchKernelGGL(pointmlp3_max_fwd_kernel, dim3(ntiles, B), dim3(PM_FT), 0, st, a);
@@ -1003,6 +1004,69 @@ extern "C" int pc3d_pointmlp3_max_fwd_screen_dbg_f32(const float* x, int64_t x_b
   return pm_fwd_launch(x, x_bs, x_ps, x_cs, B, N, T, th_in, th_W, th_b, th_K, T_out, W1, b1, W2, b2, W3, b3, C1, C2, C3,
                        relu_last, part_val, part_idx, pooled, argidx, mask1, mask2, stream, false, stats, dbg_S, dbg_E,
                        stop_after);
+}
+
+// ---- the launches above fed from a prepared image of W3 (pc3d_pointmlp3_w3_prepare_f32 made it from the same W3)
+static PMScreenPrep pm_prep(const void* w3_bf, const float* w3_nw, const float* w3_q) {
+  return PMScreenPrep{reinterpret_cast<decltype(PMScreenPrep::w3_bf)>(w3_bf), w3_nw, reinterpret_cast<const float4*>(w3_q)};
+}
+
+extern "C" int pc3d_pointmlp3_w3_prepare_f32(const float* W3, int C3, void* w3_bf, float* w3_nw, float* w3_q, void* stream) {
+  PC3D_REQUIRE(C3 >= 32 && C3 % 32 == 0 && C3 <= PM_MAXC3F, "pc3d_pointmlp3_w3_prepare_f32: C3 = %d (need a multiple of 32 <= 1024)", C3);
+  PC3D_REQUIRE(W3 && w3_bf && w3_nw && w3_q, "pc3d_pointmlp3_w3_prepare_f32: null pointer");
+  pm_w3_prepare_launch(W3, C3, w3_bf, w3_nw, w3_q, stream);
+  PC3D_LAUNCH_CHECK("pc3d_pointmlp3_w3_prepare_f32");
+  return PC3D_OK;
+}
+
+extern "C" int pc3d_pointmlp3_max_fwd_prep_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                               const float* T, const float* W1, const float* b1, const float* W2,
+                                               const float* b2, const float* W3, const float* b3, int C1, int C2, int C3,
+                                               int relu_last, float* part_val, int32_t* part_idx, float* pooled,
+                                               int32_t* argidx, uint64_t* mask1, uint32_t* mask2, const void* w3_bf,
+                                               const float* w3_nw, const float* w3_q, void* stream) {
+  PC3D_REQUIRE(w3_bf && w3_nw && w3_q, "pc3d_pointmlp3_max_fwd_prep_f32: the prepared image needs w3_bf, w3_nw and w3_q");
+  const PMScreenPrep q = pm_prep(w3_bf, w3_nw, w3_q);
+  return pm_fwd_launch(x, x_bs, x_ps, x_cs, B, N, T, nullptr, nullptr, nullptr, 0, nullptr, W1, b1, W2, b2, W3, b3, C1, C2,
+                       C3, relu_last, part_val, part_idx, pooled, argidx, mask1, mask2, stream, false, nullptr, nullptr,
+                       nullptr, 0, &q);
+}
+
+extern "C" int pc3d_pointmlp3_max_fwd_prep_th_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                                  const float* th_in, const float* th_W, const float* th_b, int th_K,
+                                                  float* T_out, const float* W1, const float* b1, const float* W2,
+                                                  const float* b2, const float* W3, const float* b3, int C1, int C2,
+                                                  int C3, int relu_last, float* part_val, int32_t* part_idx,
+                                                  float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2,
+                                                  const void* w3_bf, const float* w3_nw, const float* w3_q, void* stream) {
+  PC3D_REQUIRE(th_in && th_W && th_b && T_out && th_K >= 1,
+               "pc3d_pointmlp3_max_fwd_prep_th_f32: the transform head needs its input, weights [9,K], bias [9] and T_out");
+  PC3D_REQUIRE(w3_bf && w3_nw && w3_q, "pc3d_pointmlp3_max_fwd_prep_th_f32: the prepared image needs w3_bf, w3_nw and w3_q");
+  const PMScreenPrep q = pm_prep(w3_bf, w3_nw, w3_q);
+  return pm_fwd_launch(x, x_bs, x_ps, x_cs, B, N, nullptr, th_in, th_W, th_b, th_K, T_out, W1, b1, W2, b2, W3, b3, C1, C2,
+                       C3, relu_last, part_val, part_idx, pooled, argidx, mask1, mask2, stream, false, nullptr, nullptr,
+                       nullptr, 0, &q);
+}
+
+extern "C" int pc3d_pointmlp3_max_fwd_screen_dbg_prep_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B,
+                                                          int N, const float* T, const float* th_in, const float* th_W,
+                                                          const float* th_b, int th_K, float* T_out, const float* W1,
+                                                          const float* b1, const float* W2, const float* b2,
+                                                          const float* W3, const float* b3, int C1, int C2, int C3,
+                                                          int relu_last, float* part_val, int32_t* part_idx, float* pooled,
+                                                          int32_t* argidx, uint64_t* mask1, uint32_t* mask2, int32_t* stats,
+                                                          float* dbg_S, float* dbg_E, int stop_after, const void* w3_bf,
+                                                          const float* w3_nw, const float* w3_q, void* stream) {
+  PC3D_REQUIRE(stats != nullptr, "pc3d_pointmlp3_max_fwd_screen_dbg_prep_f32: stats [B, ntiles, 2] is required");
+  PC3D_REQUIRE((dbg_S == nullptr) == (dbg_E == nullptr), "pc3d_pointmlp3_max_fwd_screen_dbg_prep_f32: dbg_S and dbg_E go together");
+  PC3D_REQUIRE(stop_after >= 0 && stop_after <= 3, "pc3d_pointmlp3_max_fwd_screen_dbg_prep_f32: stop_after = %d", stop_after);
+  PC3D_REQUIRE(th_in == nullptr || (T == nullptr && th_W && th_b && T_out && th_K >= 1),
+               "pc3d_pointmlp3_max_fwd_screen_dbg_prep_f32: T or a complete transform head, not both");
+  PC3D_REQUIRE(w3_bf && w3_nw && w3_q, "pc3d_pointmlp3_max_fwd_screen_dbg_prep_f32: the prepared image needs w3_bf, w3_nw and w3_q");
+  const PMScreenPrep q = pm_prep(w3_bf, w3_nw, w3_q);
+  return pm_fwd_launch(x, x_bs, x_ps, x_cs, B, N, T, th_in, th_W, th_b, th_K, T_out, W1, b1, W2, b2, W3, b3, C1, C2, C3,
+                       relu_last, part_val, part_idx, pooled, argidx, mask1, mask2, stream, false, stats, dbg_S, dbg_E,
+                       stop_after, &q);
 }
 
 static int pm_bwd_launch(const char* who, bool twolist, const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B,

@@ -191,7 +191,16 @@ __device__ __forceinline__ void pm_fwd_prologue(const PMFwdArgs& a, float* lds) 
 // pointmlp_screen.hip: the same launch with layer 3 screened on bf16 MFMA and rechecked exactly (the same bits).
 // Returns 0 when launched, 1 when it could not be (first use on a device while the stream is capturing: the caller
 // launches the exact kernel), < 0 on an error. stats / dbg_S / dbg_E / stop_after: pc3d_pointmlp3_max_fwd_screen_dbg_f32.
+// prep: the prepared image of W3 (pm_w3_prepare_launch wrote it from THIS W3), or null: the operands are then made from
+// the fp32 rows inside the launch.
+struct PMScreenPrep {
+  const __attribute__((ext_vector_type(8))) __bf16* w3_bf;   // [C3/32][8][2][64] x 8 bf16
+  const float* w3_nw;                                        // [C3]
+  const float4* w3_q;                                        // [32][C3]
+};
 int pm_fwd_screen_launch(const PMFwdArgs& a, int B, void* stream, int32_t* stats, float* dbg_S, float* dbg_E,
-                         int stop_after);
+                         int stop_after, const PMScreenPrep* prep);
+// w3_bf (C3 * 512 B), w3_nw (C3 floats), w3_q (C3 * 128 floats) from the folded fp32 W3 [C3,128]
+int pm_w3_prepare_launch(const float* W3, int C3, void* w3_bf, float* w3_nw, float* w3_q, void* stream);
 
 }  // namespace pc3d

@@ -17,6 +17,19 @@
 //          enters (value, lowest point) into the channel's 64-bit key with an LDS max: order-free, so deterministic.
 //  fallback (wave-uniform) the exact fp32 MFMA block on the same h2: a tile with a non-finite or huge h2, a channel
 //          block with a non-finite or huge W3 row, a block with more than PMS_CAP candidates.
+//
+// PREP: the same launch fed from a PREPARED image of W3 (pms_w3_prepare_kernel, made once per fold: W3 is a frozen victim
+// weight). Same S, E, candidates and outputs in every bit; what differs is where the operands come from and how the
+// recheck is laid out:
+//  w3_bf [C3/32][8][2][64] x 16 B  the screen's B operands as the MFMA reads them: for channel block cb, k-step t, lane
+//          (r, h) = r + 32 h, the 8 hi terms ([..][0][lane]) and the 8 lo terms ([..][1][lane]) of
+//          W3[32 cb + r][16 t + 8 h + 0..7]; one wave load of 16 B per lane reads 1 KB contiguous. The screen loop streams
+//          them through a ring of four k-steps that runs on across the block boundary: no fp32 row buffer, no split.
+//  w3_nw [C3]  pms_norm_up of the row's sum of squares, accumulated in the in-launch order (so cw and E keep their bits).
+//  w3_q  [32][C3] float4  w3_q[t][c] = W3[c][4t .. 4t+3]: the recheck goes BY CHANNEL (lane <-> channel, its fp32 row in
+//          registers from two contiguous 512-B runs per load), over the channel's candidates in s_pts[c][PMS_PCAP]; the
+//          winner's key stays in registers: no list, no scan, no LDS atomics, no decode pass. A block in which a channel
+//          has more than PMS_PCAP candidates runs the exact block.
 #include "pc3d_common.h"
 #include "pointmlp_body.h"
 #include "pointmlp_screen_bound.h"
@@ -36,6 +49,14 @@ constexpr size_t PMS_LDS_BYTES = (size_t)PM_FWD_LDS_FLOATS * 4 + PM_TP * 4 + (si
 static_assert(PMS_LDS_BYTES + 1024 <= 160 * 1024, "one workgroup's LDS on gfx950");
 static_assert((PM_FWD_LDS_FLOATS * 4 + PM_TP * 4) % 8 == 0, "the keys are 8-byte aligned");
 static_assert(PM_TP == 128 && PMS_SLOTS <= 4, "a list entry is slot << 12 | channel-in-block << 7 | point");
+
+constexpr int PMS_PCAP = 8;                                // PREP: candidates per (tile, channel) before the block falls back
+// PREP's dynamic LDS: h2 + xs | na [128] f32 | pts [1024][PMS_PCAP] u8 | bf16 h2 hi, lo = 147,968 B
+constexpr size_t PMS_A16_OFF = (size_t)PM_FWD_LDS_FLOATS * 4 + PM_TP * 4 + (size_t)PM_MAXC3F * 8 + (PM_FT / 64) * PMS_WLIST * 2;
+constexpr size_t PMS_A16_OFF_PREP = (size_t)PM_FWD_LDS_FLOATS * 4 + PM_TP * 4 + (size_t)PM_MAXC3F * PMS_PCAP;
+constexpr size_t PMS_LDS_BYTES_PREP = PMS_A16_OFF_PREP + 2 * (size_t)PM_TP * PMS_LDA * 2;
+static_assert(PMS_LDS_BYTES_PREP <= PMS_LDS_BYTES && PMS_A16_OFF_PREP % 16 == 0 && PMS_A16_OFF % 16 == 0, "PREP's LDS map");
+static_assert(PMS_PCAP >= 4 && PMS_PCAP <= 15, "a channel's candidate count is kept in 4 bits");
 
 struct PMScreenDbg {
   int32_t* stats;    // [B, ntiles, 2]: candidates rechecked, channel blocks that fell back (added to)
@@ -133,17 +154,53 @@ __device__ __forceinline__ void pms_exact_block(const float* h2, const float* W3
   }
 }
 
+// The prepared image of W3 (see the head of the file): one wave per channel block. Lane (r, h) holds what the in-launch
+// screen's lane holds and forms the norm in the same order, so w3_nw is that launch's nw in every bit.
+__global__ __launch_bounds__(64) void pms_w3_prepare_kernel(const float* __restrict__ W3, bf16x8* __restrict__ w3_bf,
+                                                            float* __restrict__ w3_nw, float4* __restrict__ w3_q, int C3) {
+  const int cb = blockIdx.x, lane = threadIdx.x;
+  const int r = lane & 31, h = lane >> 5;
+  float4 w[PM_C2 / 8];
+  const float* wrow = W3 + (int64_t)(cb * 32 + r) * PM_C2 + 8 * h;
+  float ss = 0.f;
+#pragma unroll
+  for (int t = 0; t < PM_C2 / 16; ++t) {
+    w[2 * t] = *reinterpret_cast<const float4*>(wrow + 16 * t);
+    w[2 * t + 1] = *reinterpret_cast<const float4*>(wrow + 16 * t + 4);
+  }
+#pragma unroll
+  for (int t = 0; t < PM_C2 / 8; ++t) {
+    ss = __builtin_fmaf(w[t].x, w[t].x, ss), ss = __builtin_fmaf(w[t].y, w[t].y, ss);
+    ss = __builtin_fmaf(w[t].z, w[t].z, ss), ss = __builtin_fmaf(w[t].w, w[t].w, ss);
+  }
+  ss = sum_xor32(ss);
+  if (h == 0) w3_nw[cb * 32 + r] = pms_norm_up(ss);
+#pragma unroll
+  for (int t = 0; t < PM_C2 / 16; ++t) {
+    bf16x8 bh, bl;
+    pms_split8(w[2 * t], w[2 * t + 1], bh, bl);
+    w3_bf[((cb * (PM_C2 / 16) + t) * 2 + 0) * 64 + lane] = bh;
+    w3_bf[((cb * (PM_C2 / 16) + t) * 2 + 1) * 64 + lane] = bl;
+  }
+  for (int i = lane; i < 32 * (PM_C2 / 4); i += 64) {
+    const int c = cb * 32 + (i & 31), t = i >> 5;
+    w3_q[(int64_t)t * C3 + c] = *reinterpret_cast<const float4*>(W3 + (int64_t)c * PM_C2 + 4 * t);
+  }
+}
+
 // DBG: stats and the truncated forms for phase timing; DUMP: dbg_S / dbg_E as well (tests of tiny shapes: it spills).
 // The production kernel is <false, false> and carries none of it.
-template <bool DBG, bool DUMP>
+// PREP: the operands come from the prepared image w3 (the head of the file), which is not read otherwise.
+template <bool DBG, bool DUMP, bool PREP>
 __global__ __launch_bounds__(PM_FT) __attribute__((amdgpu_waves_per_eu(2, 2))) void pointmlp3_max_fwd_screen_kernel(
-    PMFwdArgs a, PMScreenDbg d) {
+    PMFwdArgs a, PMScreenDbg d, PMScreenPrep w3) {
   extern __shared__ __attribute__((aligned(16))) float pms_lds[];
   float* h2 = pms_lds;                                                              // [128][132] fp32, kept to the end
   float* s_na = pms_lds + PM_FWD_LDS_FLOATS;                                        // [128] upper bounds of ||h2[p]||
   unsigned long long* s_key = reinterpret_cast<unsigned long long*>(s_na + PM_TP);  // [C3] (value, lowest point) keys
   unsigned short* s_list = reinterpret_cast<unsigned short*>(s_key + PM_MAXC3F);    // [8 waves][PMS_WLIST]
-  __bf16* s_a16 = reinterpret_cast<__bf16*>(s_list + (PM_FT / 64) * PMS_WLIST);     // [128][PMS_LDA] bf16 image of h2: hi
+  __bf16* s_a16 = reinterpret_cast<__bf16*>(reinterpret_cast<char*>(pms_lds) +
+                                            (PREP ? PMS_A16_OFF_PREP : PMS_A16_OFF));   // [128][PMS_LDA] bf16 image of h2: hi
   __bf16* s_a16l = s_a16 + PM_TP * PMS_LDA;                                         // and lo terms
   pm_fwd_prologue(a, pms_lds);
   const int tile = blockIdx.x, b = blockIdx.y;
@@ -176,7 +233,8 @@ __global__ __launch_bounds__(PM_FT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
     const float na = pms_norm_up(ss);
     bad = !pms_norm_ok(na);               // NaN, inf or huge h2 anywhere in the tile: no screen for this tile
     if (q == 0) s_na[p] = p < nvalid ? na : __builtin_inff();   // past the end of a ragged tile: see pms_lower
-    for (int c = threadIdx.x; c < a.C3; c += PM_FT) s_key[c] = 0ull;
+    if (!PREP)
+      for (int c = threadIdx.x; c < a.C3; c += PM_FT) s_key[c] = 0ull;
   }
   const bool tile_bad = __syncthreads_or(bad ? 1 : 0) != 0;
   if (DBG && d.stop_after == 1) return;
@@ -187,6 +245,189 @@ __global__ __launch_bounds__(PM_FT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
 #pragma unroll
     for (int e = 0; e < 16; ++e) vmask[pt >> 1] |= (pms_point(pt, e, h) < nvalid) ? (1u << (16 * (pt & 1) + e)) : 0u;
   const int nblk = a.C3 / 32;
+  if constexpr (PREP) {
+    unsigned char* s_pts = reinterpret_cast<unsigned char*>(s_na + PM_TP);   // [C3][PMS_PCAP] a channel's candidate points
+    const int nslots = wave < nblk ? (nblk - wave + PM_FT / 64 - 1) / (PM_FT / 64) : 0;   // <= PMS_SLOTS
+    unsigned screened = 0u, cnts = 0u;    // bit slot: screened; bits 4 slot .. + 3: candidates of the lane's channel r
+    int ncand = 0, nfall = 0;
+    float sink = 0.f;
+    // the B operands' ring: four k-steps ahead in the wave's stream of blocks, across the block boundary
+    const bf16x8* wb = w3.w3_bf + lane;
+    bf16x8 qh[4], ql[4];
+    float nw_next = 0.f;
+    if (nslots > 0) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        qh[i] = wb[((wave * (PM_C2 / 16) + i) * 2 + 0) * 64];
+        ql[i] = wb[((wave * (PM_C2 / 16) + i) * 2 + 1) * 64];
+      }
+      nw_next = w3.w3_nw[wave * 32 + r];
+    }
+#pragma unroll 1
+    for (int slot = 0; slot < nslots; ++slot) {
+      const int cb = wave + (PM_FT / 64) * slot;
+      const int nxt = slot + 1 < nslots ? cb + PM_FT / 64 : cb;   // past the wave's last block: a valid address, unused
+      const float nw = nw_next;
+      nw_next = w3.w3_nw[nxt * 32 + r];
+      const float cw = pms_cw(nw);
+      // (uniform) a non-finite or huge h2 in the tile, or such a W3 row in the block (its prepared norm fails too)
+      bool fall = tile_bad || __builtin_amdgcn_ballot_w64(!pms_norm_ok(nw)) != 0ull;
+      if (!fall) {
+        f32x16 acc[4];
+#pragma unroll
+        for (int pt = 0; pt < 4; ++pt)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) acc[pt][e] = 0.f;
+#pragma unroll
+        for (int t = 0; t < PM_C2 / 16; ++t) {
+          const bf16x8 bh = qh[t & 3], bl = ql[t & 3];
+          {
+            const int cs = t < 4 ? cb : nxt, ts = (t + 4) & 7;
+            qh[t & 3] = wb[((cs * (PM_C2 / 16) + ts) * 2 + 0) * 64];
+            ql[t & 3] = wb[((cs * (PM_C2 / 16) + ts) * 2 + 1) * 64];
+          }
+#pragma unroll
+          for (int pt = 0; pt < 4; ++pt) {   // A: lane (r, h) holds the terms of h2[32 pt + r][16 t + 8 h + 0..7]
+            const bf16x8 ah = *reinterpret_cast<const bf16x8*>(s_a16 + (pt * 32 + r) * PMS_LDA + 16 * t + 8 * h);
+            const bf16x8 al = *reinterpret_cast<const bf16x8*>(s_a16l + (pt * 32 + r) * PMS_LDA + 16 * t + 8 * h);
+            acc[pt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[pt], 0, 0, 0);
+            acc[pt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[pt], 0, 0, 0);
+            acc[pt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[pt], 0, 0, 0);
+          }
+        }
+        // the order of the 16 loads, 64 LDS reads and 96 MFMAs above, pinned (hipcc otherwise sinks the loads to just in
+        // time): a k-step's two loads lead it and land four k-steps later; the A operands are read two (pt) groups ahead
+        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);        // 4 DS read
+#pragma unroll
+        for (int g = 0; g < 4 * (PM_C2 / 16); ++g) {
+          if (g % 4 == 0) __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);   // 2 VMEM read
+          __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);      // 3 MFMA
+          if (g + 2 < 4 * (PM_C2 / 16)) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+        }
+        if (DBG && d.stop_after == 2) {
+#pragma unroll
+          for (int pt = 0; pt < 4; ++pt)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) sink += acc[pt][e];
+          continue;
+        }
+        if (DUMP && d.dbg_S != nullptr) {
+          int c3v = a.C3;
+          unsigned vm[2] = {vmask[0], vmask[1]};
+          asm volatile("" : "+v"(c3v), "+v"(vm[0]), "+v"(vm[1]));   // opaque: nothing of the 64 stores is hoisted out of the block loop
+          const int64_t o0 = ((int64_t)b * a.N + n0) * a.C3 + cb * 32 + r;
+#pragma unroll
+          for (int pt = 0; pt < 4; ++pt)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+              const int p = pms_point(pt, e, h);
+              if ((vm[pt >> 1] >> (16 * (pt & 1) + e)) & 1u) {
+                d.dbg_S[o0 + (int64_t)p * c3v] = acc[pt][e];
+                d.dbg_E[o0 + (int64_t)p * c3v] = pms_E(s_na[p], cw);
+              }
+            }
+        }
+        unsigned flags[2];
+        float L = pms_lower(acc, s_na, cw, h);
+        L = fmaxf(L, __shfl_xor(L, 32, 64));
+        pms_flags(acc, s_na, cw, h, L, flags);
+        flags[0] &= vmask[0], flags[1] &= vmask[1];
+        const int cnt = __builtin_popcount(flags[0]) + __builtin_popcount(flags[1]);
+        const int other = __shfl_xor(cnt, 32, 64);   // the channel's other half of the points
+        if (__builtin_amdgcn_ballot_w64(cnt + other > PMS_PCAP) != 0ull) {
+          fall = true;                    // (uniform) a channel with more candidates than its slots: the exact block instead
+        } else {
+          unsigned char* mine = s_pts + (cb * 32 + r) * PMS_PCAP + (h ? other : 0);   // h = 1 writes behind h = 0's
+#pragma unroll
+          for (int wd = 0; wd < 2; ++wd) {
+            unsigned f = flags[wd];
+            while (f) {
+              const int bit = __builtin_ctz(f);
+              f &= f - 1;
+              *mine++ = (unsigned char)pms_point(2 * wd + (bit >> 4), bit & 15, h);
+            }
+          }
+          cnts |= (unsigned)(cnt + other) << (4 * slot);
+          screened |= 1u << slot;
+          if (DBG) ncand += h ? 0 : cnt + other;
+        }
+      } else {                            // not screened: the ring moves on to the next block's first k-steps
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          qh[i] = wb[((nxt * (PM_C2 / 16) + i) * 2 + 0) * 64];
+          ql[i] = wb[((nxt * (PM_C2 / 16) + i) * 2 + 1) * 64];
+        }
+      }
+      if (fall) {
+        pms_exact_block(h2, a.W3, a.b3, cb, n0, a.N, a.part_val + obase, a.part_idx + obase);
+        ++nfall;
+      }
+    }
+    if (DBG && d.stop_after == 2) {
+      if (sink == 12345.678f) a.part_val[obase] = sink;   // keeps the products alive
+      return;
+    }
+    if (DBG && d.stats != nullptr) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) ncand += __shfl_xor(ncand, o, 64);
+      if (lane == 0) {
+        int32_t* st = d.stats + ((int64_t)b * a.ntiles + tile) * 2;
+        if (ncand) atomicAdd(st, ncand);
+        if (nfall) atomicAdd(st + 1, nfall);
+      }
+    }
+    if (DBG && d.stop_after == 3) {
+      if (cnts == 0xffffffffu) a.part_val[obase] = 0.f;
+      return;
+    }
+
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the channels' candidate points, written by other lanes
+    // ---- recheck by channel: lanes 0..31 the channels of slot 2j, lanes 32..63 those of slot 2j + 1; the lane holds its
+    // channel's fp32 row and runs the exact kernel's chain (t ascending; x, y, z, w; k = 8t + c, then 8t + 4 + c) for each
+    // of the channel's candidates; the largest key (see the in-launch form) is the exact kernel's winner
+#pragma unroll 1
+    for (int j = 0; 2 * j < nslots; ++j) {
+      const int sl = 2 * j + h;
+      const bool live = sl < nslots && ((screened >> sl) & 1u);
+      const int n = live ? (int)((cnts >> (4 * sl)) & 15u) : 0;
+      if (__builtin_amdgcn_ballot_w64(n > 0) == 0ull) continue;   // (uniform)
+      const int c = (wave + (PM_FT / 64) * (live ? sl : 0)) * 32 + r;   // an idle lane: a valid row, unused
+      float4 wv[PM_C2 / 4];               // the whole row in flight at once: one round trip per trip
+#pragma unroll
+      for (int t = 0; t < PM_C2 / 4; ++t) wv[t] = w3.w3_q[(int64_t)t * a.C3 + c];
+      unsigned long long key = 0ull;
+#pragma unroll 1
+      for (int i = 0; i < PMS_PCAP; ++i) {
+        if (__builtin_amdgcn_ballot_w64(i < n) == 0ull) break;    // (uniform)
+        const int p = i < n ? s_pts[c * PMS_PCAP + i] : 0;
+        const float4* ar = reinterpret_cast<const float4*>(h2 + p * PM_LD2);
+        float v = 0.f;
+#pragma unroll
+        for (int t = 0; t < PM_C2 / 8; ++t) {
+          const float4 a0 = ar[2 * t], a1 = ar[2 * t + 1];
+          const float4 w0 = wv[2 * t], w1 = wv[2 * t + 1];
+          v = __builtin_fmaf(a0.x, w0.x, v), v = __builtin_fmaf(a1.x, w1.x, v);
+          v = __builtin_fmaf(a0.y, w0.y, v), v = __builtin_fmaf(a1.y, w1.y, v);
+          v = __builtin_fmaf(a0.z, w0.z, v), v = __builtin_fmaf(a1.z, w1.z, v);
+          v = __builtin_fmaf(a0.w, w0.w, v), v = __builtin_fmaf(a1.w, w1.w, v);
+        }
+        const unsigned vb = __builtin_bit_cast(unsigned, v);
+        const unsigned zb = (v == 0.f) ? 0u : vb;
+        const unsigned ord = (zb & 0x80000000u) ? ~zb : (zb | 0x80000000u);
+        const unsigned low = ((unsigned)(127 - p) << 1) | ((vb == 0x80000000u) ? 1u : 0u);
+        const unsigned long long k = ((unsigned long long)ord << 32) | low;
+        if (i < n && k > key) key = k;
+      }
+      if (live) {
+        const unsigned ord = (unsigned)(key >> 32), low = (unsigned)key;
+        unsigned vb = (ord & 0x80000000u) ? (ord & 0x7fffffffu) : ~ord;
+        if (low & 1u) vb = 0x80000000u;
+        a.part_val[obase + c] = __builtin_bit_cast(float, vb) + a.b3[c];
+        a.part_idx[obase + c] = n0 + 127 - (int)((low >> 1) & 127u);
+      }
+    }
+    return;
+  }
   unsigned short* my_list = s_list + wave * PMS_WLIST;
   int wave_cnt = 0, nfall = 0;
   unsigned screened = 0u;                 // bit slot: that block of the wave went through the screen
@@ -352,12 +593,13 @@ __global__ __launch_bounds__(PM_FT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
 
 // 0: launched. 1: not launched — the kernel needs its dynamic-LDS attribute, which is set at first use on a device and
 // never while the stream is capturing; the caller then launches the exact kernel.
-template <bool DBG, bool DUMP>
-static int pms_launch_t(const PMFwdArgs& a, int B, hipStream_t st, const PMScreenDbg& d) {
+template <bool DBG, bool DUMP, bool PREP>
+static int pms_launch_t(const PMFwdArgs& a, int B, hipStream_t st, const PMScreenDbg& d, const PMScreenPrep& q) {
   static bool done[64] = {};
   int dev = 0;
   PC3D_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "pointmlp3 screen: no current device");
-  auto kernel = pointmlp3_max_fwd_screen_kernel<DBG, DUMP>;
+  auto kernel = pointmlp3_max_fwd_screen_kernel<DBG, DUMP, PREP>;
+  constexpr size_t lds = PREP ? PMS_LDS_BYTES_PREP : PMS_LDS_BYTES;
   if (!done[dev]) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
@@ -365,20 +607,34 @@ static int pms_launch_t(const PMFwdArgs& a, int B, hipStream_t st, const PMScree
       return 1;
     }
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)PMS_LDS_BYTES);
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     PC3D_REQUIRE(e == hipSuccess, "pointmlp3 screen: hipFuncSetAttribute(MaxDynamicSharedMemorySize): %s", hipGetErrorString(e));
     done[dev] = true;
   }
-  hipLaunchKernelGGL(kernel, dim3(a.ntiles, B), dim3(PM_FT), PMS_LDS_BYTES, st, a, d);
+  hipLaunchKernelGGL(kernel, dim3(a.ntiles, B), dim3(PM_FT), lds, st, a, d, q);
   return 0;
 }
 
+template <bool PREP>
+static int pms_launch_form(const PMFwdArgs& a, int B, hipStream_t st, const PMScreenDbg& d, const PMScreenPrep& q) {
+  if (d.dbg_S || d.dbg_E) return pms_launch_t<true, true, PREP>(a, B, st, d, q);
+  if (d.stats || d.stop_after) return pms_launch_t<true, false, PREP>(a, B, st, d, q);
+  return pms_launch_t<false, false, PREP>(a, B, st, d, q);
+}
+
 int pm_fwd_screen_launch(const PMFwdArgs& a, int B, void* stream, int32_t* stats, float* dbg_S, float* dbg_E,
-                         int stop_after) {
+                         int stop_after, const PMScreenPrep* prep) {
   const PMScreenDbg d{stats, dbg_S, dbg_E, stop_after};
-  if (dbg_S || dbg_E) return pms_launch_t<true, true>(a, B, as_stream(stream), d);
-  if (stats || stop_after) return pms_launch_t<true, false>(a, B, as_stream(stream), d);
-  return pms_launch_t<false, false>(a, B, as_stream(stream), d);
+  // the prepared form when the caller has the image; the in-launch form without one, and when the prepared
+  // instantiation cannot be launched yet (its first use on the device falls into a capture)
+  if (prep != nullptr && pms_launch_form<true>(a, B, as_stream(stream), d, *prep) == 0) return 0;
+  return pms_launch_form<false>(a, B, as_stream(stream), d, PMScreenPrep{nullptr, nullptr, nullptr});
+}
+
+int pm_w3_prepare_launch(const float* W3, int C3, void* w3_bf, float* w3_nw, float* w3_q, void* stream) {
+  hipLaunchKernelGGL(pms_w3_prepare_kernel, dim3(C3 / 32), dim3(64), 0, as_stream(stream), W3,
+                     reinterpret_cast<bf16x8*>(w3_bf), w3_nw, reinterpret_cast<float4*>(w3_q), C3);
+  return 0;
 }
 
 }  // namespace pc3d

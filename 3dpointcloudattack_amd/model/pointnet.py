@@ -102,7 +102,7 @@ class STN3d(_FrozenFusedMixin, nn.Module):
         tower = _fold_bn(self.conv1.weight, self.conv1.bias, self.bn1) + \
             _fold_bn(self.conv2.weight, self.conv2.bias, self.bn2) + \
             _fold_bn(self.conv3.weight, self.conv3.bias, self.bn3)
-        tower = tower + (tower[2].t().contiguous(),)      # W2^T for the backward kernel
+        tower = tower + (tower[2].t().contiguous(), [])  # W2^T for the backward kernel; the holder of W3's prepared image (PointNetfeat._fold)
         head = (_fold_bn(self.fc1.weight, self.fc1.bias, self.bn4),
                 _fold_bn(self.fc2.weight, self.fc2.bias, self.bn5),
                 _plain(self.fc3.weight, self.fc3.bias))
@@ -189,7 +189,10 @@ class PointNetfeat(_FrozenFusedMixin, nn.Module):
         tower = _fold_bn(self.conv1.weight, self.conv1.bias, self.bn1) + \
             _fold_bn(self.conv2.weight, self.conv2.bias, self.bn2) + \
             _fold_bn(self.conv3.weight, self.conv3.bias, self.bn3)
-        return tower + (tower[2].t().contiguous(),)       # W2^T for the backward kernel
+        # W2^T for the backward kernel, and an empty list that ops.pointmlp3_max_fwd_raw fills once, on its first launch,
+        # with the prepared image of this W3 (nothing is launched here). A plain list on purpose: graphed._cached_tensors
+        # walks tuples, lists and dicts, which is what keeps the image alive next to a captured graph after a re-fold.
+        return tower + (tower[2].t().contiguous(), [])
 
     def forward(self, x):
         self._require_fused(x)

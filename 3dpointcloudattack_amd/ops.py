@@ -388,8 +388,38 @@ def pointmlp3_fold_raw(part_val, part_idx, relu_last, serial=False):
     return pooled, argidx
 
 
+def pointmlp3_w3_prepare(W3):
+    """The prepared image of a folded W3 [C3,128] for the screened tower forward (csrc/pointmlp_screen.hip), one small
+    launch: (w3_bf [C3/32,8,2,64,8] bf16 — block, k-step, hi / lo terms, lane r + 32 h, W3[32 cb + r][16 t + 8 h + 0..7];
+    w3_nw [C3] f32 — the screen's upper bound of the row norm; w3_q [32,C3,4] f32 — w3_q[t][c] = W3[c][4t..4t+3])."""
+    _check(W3, "W3")
+    C3 = W3.shape[0]
+    if W3.dim() != 2 or W3.shape[1] != 128 or not W3.is_contiguous():
+        raise ValueError("pointmlp3_w3_prepare: W3 must be a contiguous [C3,128] tensor")
+    bf = torch.empty((C3 // 32, 8, 2, 64, 8), dtype=torch.bfloat16, device=W3.device)
+    nw = torch.empty((C3,), dtype=torch.float32, device=W3.device)
+    q = torch.empty((32, C3, 4), dtype=torch.float32, device=W3.device)
+    with torch.cuda.device(W3.device):
+        _lib.call("pc3d_pointmlp3_w3_prepare_f32", W3.data_ptr(), C3, bf.data_ptr(), nw.data_ptr(), q.data_ptr(), _stream())
+    return bf, nw, q
+
+
+def _pm_w3_pack(weights, W3):
+    """The prepared image in the tower tuple's 8th item (a plain list: empty after the fold, filled here ONCE, on the
+    first call outside a capture, never cleared or refilled — a graph may point at its tensors), or None: no list, a
+    capture before the first fill, or a W3 that is not the tensor (storage, version) the image was made from."""
+    pack = weights[7] if len(weights) > 7 else None
+    if not isinstance(pack, list):
+        return None
+    if not pack:
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        pack.extend(pointmlp3_w3_prepare(W3) + ((W3.data_ptr(), W3._version),))
+    return pack[:3] if pack[3] == (W3.data_ptr(), W3._version) else None
+
+
 def pointmlp3_max_fwd_raw(x, weights, relu_last, T=None, x_cf=True, fold=True, want_masks=False, T_head=None, serial=False,
-                          exact=False, screen_dbg=None):
+                          exact=False, screen_dbg=None, in_launch=False):
     """x [B,3,N] (x_cf) or [B,N,3]; weights = (W1[64,3], b1, W2[128,64], b2, W3[C3,128], b3) with eval-BN folded.
     Returns (pooled [B,C3] f32, argidx [B,C3] i32) and, with want_masks, a third item (mask1 [B,N] i64, mask2 [B,N,4]
     i32): the per-point ReLU decisions of layers 1 and 2 as bit masks, which pointmlp3_max_bwd_raw consumes.
@@ -400,10 +430,13 @@ def pointmlp3_max_fwd_raw(x, weights, relu_last, T=None, x_cf=True, fold=True, w
     (the same bits). screen_dbg: a dict, for tests and tools — the screened launch's debug instantiation runs and the
     dict receives "stats" [B,ntiles,2] i32 (candidates rechecked, channel blocks that fell back to the exact block);
     with screen_dbg["dump"] set also "S" and "E" [B,N,C3] (tiny shapes), with screen_dbg["stop_after"] = 1 / 2 / 3
-    the launch ends after that phase (timing only: the outputs are undefined)."""
+    the launch ends after that phase (timing only: the outputs are undefined).
+    weights[7], when present: a plain list that holds the prepared image of W3 (see _pm_w3_pack; model/pointnet.py puts an
+    empty one into every folded tower). With it the screened launch reads its bf16 operands, norms and recheck rows from
+    the image instead of making them from W3 in every workgroup (the same bits). in_launch: do not use the image."""
     xp, xbs, xps, xcs, B, N = _pts(x, x_cf, "x")
     W1, b1, W2, b2, W3, b3 = weights[:6]
-    for w in weights:
+    for w in weights[:7]:
         _check(w, "weight")
         if not w.is_contiguous():
             raise ValueError("pointmlp3 weights must be contiguous")
@@ -429,6 +462,9 @@ def pointmlp3_max_fwd_raw(x, weights, relu_last, T=None, x_cf=True, fold=True, w
         raise ValueError("pointmlp3_max_fwd_raw: screen_dbg belongs to the screened launch, not to exact=True")
     sfx = "exact_" if exact else ""
     with torch.cuda.device(dev):
+        prep = None if exact or in_launch else _pm_w3_pack(weights, W3)
+        if prep is not None:
+            sfx, prep = "prep_", tuple(t.data_ptr() for t in prep)
         if T_head is not None:
             if T is not None:
                 raise ValueError("pointmlp3_max_fwd_raw: give T or T_head, not both")
@@ -444,13 +480,14 @@ def pointmlp3_max_fwd_raw(x, weights, relu_last, T=None, x_cf=True, fold=True, w
                 dE = torch.full((B, N, C3), float("nan"), dtype=torch.float32, device=dev)
                 screen_dbg["S"], screen_dbg["E"] = dS, dE
             th = (h.data_ptr(), Wt.data_ptr(), bt.data_ptr(), h.shape[1], T_out.data_ptr()) if T_head is not None else (0, 0, 0, 0, 0)
-            _lib.call("pc3d_pointmlp3_max_fwd_screen_dbg_f32", xp, xbs, xps, xcs, B, N, _ptr(T), *th, *tail[:-1],
-                      screen_dbg["stats"].data_ptr(), _ptr(dS), _ptr(dE), int(screen_dbg.get("stop_after", 0)), tail[-1])
+            _lib.call("pc3d_pointmlp3_max_fwd_screen_dbg_%sf32" % sfx, xp, xbs, xps, xcs, B, N, _ptr(T), *th, *tail[:-1],
+                      screen_dbg["stats"].data_ptr(), _ptr(dS), _ptr(dE), int(screen_dbg.get("stop_after", 0)),
+                      *(prep or ()), tail[-1])
         elif T_head is not None:
             _lib.call("pc3d_pointmlp3_max_fwd_%sth_f32" % sfx, xp, xbs, xps, xcs, B, N, h.data_ptr(), Wt.data_ptr(), bt.data_ptr(),
-                      h.shape[1], T_out.data_ptr(), *tail)
+                      h.shape[1], T_out.data_ptr(), *tail[:-1], *(prep or ()), tail[-1])
         else:
-            _lib.call("pc3d_pointmlp3_max_fwd_%sf32" % sfx, xp, xbs, xps, xcs, B, N, _ptr(T), *tail)
+            _lib.call("pc3d_pointmlp3_max_fwd_%sf32" % sfx, xp, xbs, xps, xcs, B, N, _ptr(T), *tail[:-1], *(prep or ()), tail[-1])
         if fold and serial:
             _lib.call("pc3d_pointmlp3_fold_f32", part_val.data_ptr(), part_idx.data_ptr(), B, ntiles, C3,
                       1 if relu_last else 0, pooled.data_ptr(), argidx.data_ptr(), 1, _stream())
@@ -497,9 +534,10 @@ class _PointMLP3MaxFn(torch.autograd.Function):
     """x [B,3,N] -> pooled [B,C3] through the fused tower; differentiable in x only (frozen weights)."""
 
     @staticmethod
-    def forward(ctx, x, relu_last, W1, b1, W2, b2, W3, b3, W2T, blocked_bwd=False):
+    def forward(ctx, x, relu_last, W1, b1, W2, b2, W3, b3, W2T, blocked_bwd=False, pack=None):
         weights = (W1, b1, W2, b2, W3, b3, W2T)
-        pooled, argidx, masks = pointmlp3_max_fwd_raw(x, weights, relu_last, want_masks=True)
+        pooled, argidx, masks = pointmlp3_max_fwd_raw(x, weights if pack is None else weights + (pack,), relu_last,
+                                                      want_masks=True)
         ctx.save_for_backward(x, argidx, pooled, masks[0], masks[1], *weights)
         ctx.relu_last, ctx.blocked_bwd = relu_last, blocked_bwd
         return pooled
@@ -513,15 +551,16 @@ class _PointMLP3MaxFn(torch.autograd.Function):
             gx = pointnet_ft_tower_bwd_raw(x, None, weights[0], weights[2], weights[4], argidx, g, (m1, m2), None, 0)[0]
         else:
             gx = pointmlp3_max_bwd_raw(x, tuple(weights), argidx, g, (m1, m2))
-        return (gx,) + (None,) * 9
+        return (gx,) + (None,) * 10
 
 
 def pointmlp3_max(x, weights, relu_last, blocked_bwd=False):
-    """weights: (W1,b1,W2,b2,W3,b3[,W2T]) with eval-BN folded; W2T is derived when absent. blocked_bwd: the backward
-    runs on pointnet_ft_tower_bwd_raw's plain form (a point's channels summed in blocks: the feature-transform victim)."""
+    """weights: (W1,b1,W2,b2,W3,b3[,W2T[,pack]]) with eval-BN folded; W2T is derived when absent; pack: the list of
+    pointmlp3_max_fwd_raw's weights[7]. blocked_bwd: the backward runs on pointnet_ft_tower_bwd_raw's plain form (a
+    point's channels summed in blocks: the feature-transform victim)."""
     if len(weights) == 6:
         weights = tuple(weights) + (weights[2].t().contiguous(),)
-    return _PointMLP3MaxFn.apply(x, relu_last, *weights, blocked_bwd)
+    return _PointMLP3MaxFn.apply(x, relu_last, *weights[:7], blocked_bwd, weights[7] if len(weights) > 7 else None)
 
 
 # ------------------------------------------------------------------------------------------------------

@@ -411,6 +411,32 @@ int pc3d_pointmlp3_max_fwd_screen_dbg_f32(const float* x, int64_t x_bs, int64_t 
                                           int relu_last, float* part_val, int32_t* part_idx, float* pooled,
                                           int32_t* argidx, uint64_t* mask1, uint32_t* mask2, int32_t* stats,
                                           float* dbg_S, float* dbg_E, int stop_after, void* stream);
+/* The prepared image of the folded W3 [C3,128] (a frozen victim weight: made once per fold, csrc/pointmlp_screen.hip):
+ * w3_bf [C3/32][8][2][64][8] bf16 (block, k-step, hi / lo, lane r + 32 h, the 8 terms of W3[32 cb + r][16 t + 8 h + 0..7]),
+ * w3_nw [C3] f32 (the screen's upper bound of the row norm), w3_q [32][C3][4] f32 (w3_q[t][c] = W3[c][4t..4t+3]). */
+int pc3d_pointmlp3_w3_prepare_f32(const float* W3, int C3, void* w3_bf, float* w3_nw, float* w3_q, void* stream);
+/* pc3d_pointmlp3_max_fwd_f32 / _th_f32 / _screen_dbg_f32 with the screen's operands and the recheck's rows read from the
+ * prepared image of the SAME W3 (the caller answers for that): the same bits in every output. */
+int pc3d_pointmlp3_max_fwd_prep_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N, const float* T,
+                                    const float* W1, const float* b1, const float* W2, const float* b2, const float* W3,
+                                    const float* b3, int C1, int C2, int C3, int relu_last, float* part_val,
+                                    int32_t* part_idx, float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2,
+                                    const void* w3_bf, const float* w3_nw, const float* w3_q, void* stream);
+int pc3d_pointmlp3_max_fwd_prep_th_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                       const float* th_in, const float* th_W, const float* th_b, int th_K, float* T_out,
+                                       const float* W1, const float* b1, const float* W2, const float* b2,
+                                       const float* W3, const float* b3, int C1, int C2, int C3, int relu_last,
+                                       float* part_val, int32_t* part_idx, float* pooled, int32_t* argidx,
+                                       uint64_t* mask1, uint32_t* mask2, const void* w3_bf, const float* w3_nw,
+                                       const float* w3_q, void* stream);
+int pc3d_pointmlp3_max_fwd_screen_dbg_prep_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                               const float* T, const float* th_in, const float* th_W, const float* th_b,
+                                               int th_K, float* T_out, const float* W1, const float* b1, const float* W2,
+                                               const float* b2, const float* W3, const float* b3, int C1, int C2, int C3,
+                                               int relu_last, float* part_val, int32_t* part_idx, float* pooled,
+                                               int32_t* argidx, uint64_t* mask1, uint32_t* mask2, int32_t* stats,
+                                               float* dbg_S, float* dbg_E, int stop_after, const void* w3_bf,
+                                               const float* w3_nw, const float* w3_q, void* stream);
 
 /* Backward-to-input of the above (weights are frozen during an attack: no weight gradients, SURVEY A-14).
  * g_pooled [B,C3] is the upstream gradient on `pooled`; with relu_last the caller zeroes it where pooled <= 0.

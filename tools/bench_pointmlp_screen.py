@@ -1,9 +1,11 @@
-"""Stand-alone timing of the PointNet tower forward with layer 3 screened on bf16 MFMA (the default launch) against
-the exact fp32 kernel (exact=True): both inside replayed hipGraphs, alternated, at B = 32 and N = 1024 / 2048 / 4096,
-for both towers of bench.py's victim (seeded weights 0) on bench.py's kind of cloud. Also the screened launch cut
-short after each phase (prologue + norms, + screen, + selection; the debug instantiation) and the `stats` of the
-full launch: candidates rechecked per (tile, channel), channel blocks that fell back to the exact block.
-One JSON line per (tower, N); --json PATH also writes the list."""
+"""Stand-alone timing of the PointNet tower forward with layer 3 screened on bf16 MFMA against the exact fp32 kernel
+(exact=True), in both screened forms: `in_launch` makes its bf16 operands and norms from W3 inside every launch,
+`prepared` (the default for a folded tower) reads them from the image made once per fold. All inside replayed
+hipGraphs, alternated, at B = 32 and N = 1024 / 2048 / 4096, for both towers of bench.py's victim (seeded weights 0) on
+bench.py's kind of cloud. Also both screened launches cut short after each phase (prologue + norms, + screen,
++ selection; the debug instantiations) and the `stats` of the full launches: candidates rechecked per (tile, channel),
+channel blocks that fell back to the exact block. Every time is the least of the rounds; *_spread_us is the largest
+minus the least round of that graph. One JSON line per (tower, N); --json PATH also writes the list."""
 import argparse, importlib, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -22,8 +24,9 @@ def unit_cloud(rng, n):      # bench.py's
     return (p / np.max(np.linalg.norm(p, axis=1))).astype(np.float32)
 
 
-def graph_us(fns, per=20, reps=30, rounds=3):
-    """us per call of each fn: `per` calls captured into one graph each, the graphs replayed alternately."""
+def graph_us(fns, per=20, reps=30, rounds=5):
+    """(least, largest) us per call of each fn over the rounds: `per` calls captured into one graph each, the graphs
+    replayed alternately."""
     side = torch.cuda.Stream()
     graphs = []
     with torch.cuda.stream(side):
@@ -35,7 +38,7 @@ def graph_us(fns, per=20, reps=30, rounds=3):
                 for _ in range(per):
                     fn()
             graphs.append(g)
-        best = [float("inf")] * len(fns)
+        best, worst = [float("inf")] * len(fns), [0.0] * len(fns)
         for g in graphs:
             for _ in range(5):
                 g.replay()
@@ -47,8 +50,9 @@ def graph_us(fns, per=20, reps=30, rounds=3):
                     g.replay()
                 e1.record(side)
                 e1.synchronize()
-                best[i] = min(best[i], e0.elapsed_time(e1) / (per * reps) * 1e3)
-    return best
+                us = e0.elapsed_time(e1) / (per * reps) * 1e3
+                best[i], worst[i] = min(best[i], us), max(worst[i], us)
+    return best, worst
 
 
 ap = argparse.ArgumentParser()
@@ -70,24 +74,33 @@ for N in [int(s) for s in args.sizes.split(",")]:
         kw = {}
         if tower == "tower_c":     # the trunk runs behind the STN's transform
             kw["T"] = (torch.eye(3, device=dev)[None] + 0.05 * torch.randn(B, 3, 3, device=dev)).contiguous()
+        assert len(w) > 7 and isinstance(w[7], list)     # the folded tower carries the image's holder
         ex = ops.pointmlp3_max_fwd_raw(x, w, relu_last, want_masks=True, exact=True, **kw)
-        sc = ops.pointmlp3_max_fwd_raw(x, w, relu_last, want_masks=True, **kw)
-        same = all(torch.equal(a, b) for a, b in zip((ex[0], ex[1]) + ex[2], (sc[0], sc[1]) + sc[2]))
-        dbg = {}
-        ops.pointmlp3_max_fwd_raw(x, w, relu_last, fold=False, screen_dbg=dbg, **kw)
-        st = dbg["stats"].double()
-        ntiles = st.shape[1]
-        fns = [lambda: ops.pointmlp3_max_fwd_raw(x, w, relu_last, fold=False, exact=True, **kw),
-               lambda: ops.pointmlp3_max_fwd_raw(x, w, relu_last, fold=False, **kw)]
-        for stop in (1, 2, 3, 0):
-            fns.append(lambda stop=stop: ops.pointmlp3_max_fwd_raw(x, w, relu_last, fold=False,
-                                                                   screen_dbg={"stop_after": stop}, **kw))
-        t = graph_us(fns)
-        row = {"tower": tower, "B": B, "N": N, "bit_equal": bool(same), "exact_us": t[0], "screened_us": t[1],
-               "dbg_prologue_us": t[2], "dbg_screen_us": t[3], "dbg_select_us": t[4], "dbg_all_us": t[5],
-               "candidates_per_tile_channel": float(st[..., 0].sum() / (B * ntiles * w[4].shape[0])),
-               "candidates_per_tile_max": float(st[..., 0].max()),
-               "fallback_blocks": int(st[..., 1].sum()), "blocks": int(B * ntiles * w[4].shape[0] // 32)}
+        same = {}
+        row = {"tower": tower, "B": B, "N": N}
+        C3 = w[4].shape[0]
+        fns = [lambda: ops.pointmlp3_max_fwd_raw(x, w, relu_last, fold=False, exact=True, **kw)]
+        names = ["exact"]
+        for form, il in (("in_launch", True), ("prepared", False)):
+            sc = ops.pointmlp3_max_fwd_raw(x, w, relu_last, want_masks=True, in_launch=il, **kw)
+            row["bit_equal_" + form] = bool(all(torch.equal(a, b) for a, b in zip((ex[0], ex[1]) + ex[2], (sc[0], sc[1]) + sc[2])))
+            dbg = {}
+            ops.pointmlp3_max_fwd_raw(x, w, relu_last, fold=False, screen_dbg=dbg, in_launch=il, **kw)
+            st = dbg["stats"].double()
+            ntiles = st.shape[1]
+            row[form + "_candidates_per_tile_channel"] = float(st[..., 0].sum() / (B * ntiles * C3))
+            row[form + "_fallback_blocks"] = int(st[..., 1].sum())
+            fns.append(lambda il=il: ops.pointmlp3_max_fwd_raw(x, w, relu_last, fold=False, in_launch=il, **kw))
+            names.append(form)
+            for stop, cut in ((1, "prologue"), (2, "screen"), (3, "select"), (0, "all")):
+                fns.append(lambda stop=stop, il=il: ops.pointmlp3_max_fwd_raw(x, w, relu_last, fold=False, in_launch=il,
+                                                                              screen_dbg={"stop_after": stop}, **kw))
+                names.append(form + "_dbg_" + cut)
+        assert len(w[7]) == 4                            # the prepared rows did run from the image
+        row["blocks"] = int(B * ntiles * C3 // 32)
+        best, worst = graph_us(fns)
+        for name, lo, hi in zip(names, best, worst):
+            row[name + "_us"], row[name + "_spread_us"] = lo, hi - lo
         rows.append(row)
         print(json.dumps(row), flush=True)
 if args.json:
