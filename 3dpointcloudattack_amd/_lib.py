@@ -102,6 +102,12 @@ SIGNATURES = {
     "pc3d_graph_laplacian_f32": _PTS + [_P, _I, _I, _I, _P, _P],
     "pc3d_spectral_reproject_f32": [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
     "pc3d_spectral_reproject_sum_f32": [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
+    "pc3d_graph_laplacian_csr_f32": _PTS + [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "pc3d_lowband_block": [_I, _I, _I, _I],
+    "pc3d_lowband_ws_bytes": [_I, _I, _I, _I],
+    "pc3d_lowband_basis_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _I, _P, _P, _P, _P, _P, _L, _P],
+    "pc3d_band_reproject_ws_floats": [_I, _I, _I],
+    "pc3d_band_reproject_f32": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "pc3d_aof_record_f32": [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "pc3d_aof_update_f32": [_P] * 8 + [_I, _I, _D, _D, _D, _D, _F, _P, _I, _P],
     "pc3d_rowdot3_f32": [_P, _P, _I, _I, _I, _I, _P, _P, _P],
@@ -197,7 +203,8 @@ SIGNATURES = {
 # entry points that do not return a status code
 RESTYPES = {"pc3d_nn_bidir_shared_ws_bytes": c_int64, "pc3d_curve_attn_bwd_ws_floats": c_int64,
             "pc3d_group_reverse_list_len": c_int64, "pc3d_curve_agg_lds_bytes": c_int64,
-            "pc3d_curve_walk_bwd_ws_floats": c_int64}
+            "pc3d_curve_walk_bwd_ws_floats": c_int64, "pc3d_lowband_ws_bytes": c_int64,
+            "pc3d_band_reproject_ws_floats": c_int64}
 
 _lib = None
 

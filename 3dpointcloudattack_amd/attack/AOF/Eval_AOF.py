@@ -28,6 +28,9 @@ the loss needs anyway), pc3d_aof_update_f32 (gradient sum + Adam + lfc + hfc + c
 (which writes lfc, hfc and the next iterate lfc + hfc straight into the stacked buffer); the buffers and the captured graphs
 stay on the ``AOF`` object, so the batches of a loader share one capture. Anything else runs the same loop through autograd
 on this package's ops.
+
+``basis="lowband"`` (default ``"full"``) computes the [B,N,low_pass] basis of the Laplacian's low band on this package's own
+kernels instead of the dense decomposition and re-projects on it (see TAOF_attack.py), in both loops.
 """
 import time
 
@@ -39,7 +42,7 @@ from ... import graphed as _graphed
 from ... import ops
 from ..CW.CW_utils import adv_utils as _adv_utils
 from ..CW.CW_utils import clip_utils as _clip_utils
-from .TAOF_attack import _logits_of, get_Laplace_from_pc, knn     # noqa: F401  (:46-62, :72-93: the same helpers)
+from .TAOF_attack import _logits_of, check_basis, get_Laplace_from_pc, get_lowband_from_pc, knn     # noqa: F401  (:46-62, :72-93)
 
 try:
     from tqdm import tqdm
@@ -81,9 +84,10 @@ class AOF:
     """The untargeted AOF attack on one batch (Eval_AOF.py:126-238); the defaults are the reference's argparse defaults."""
 
     def __init__(self, model, trans_model, adv_func, clip_func, lr=1e-2, low_pass=100, step=2, epochs=200, batch_size=1,
-                 device=None, verbose=False, fused=True, graph=True, deterministic=None):
+                 device=None, verbose=False, fused=True, graph=True, deterministic=None, basis="full"):
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.deterministic = deterministic     # None: ops.DETERMINISTIC; True / False: that mode during attack()
+        self.basis = check_basis(basis)     # "full": dense Laplacian + eigh, V and V^T; "lowband": ops.lowband_basis, U
         self.model = model.to(self.device)
         self.model.eval()
         self.trans_model = trans_model.to(self.device)
@@ -166,10 +170,15 @@ class AOF:
         data = ori_data
         for binary_step in range(self.step):
             data = self._noisy(ori_data)
-            _, V = get_Laplace_from_pc(data)
-            V = V.float().contiguous()
-            Vt = V.transpose(2, 1).contiguous()      # constant for the whole binary step
-            lfc, hfc = ops.spectral_reproject(data, V, Vt, lp)      # :145-147
+            if self.basis == "lowband":
+                U = get_lowband_from_pc(data, lp)      # constant for the whole binary step
+                reproject = lambda a: ops.band_reproject(a.contiguous(), U)
+            else:
+                _, V = get_Laplace_from_pc(data)
+                V = V.float().contiguous()
+                Vt = V.transpose(2, 1).contiguous()      # constant for the whole binary step
+                reproject = lambda a, V=V, Vt=Vt: ops.spectral_reproject(a.contiguous(), V, Vt, lp)
+            lfc, hfc = reproject(data)      # :145-147
             lfc.requires_grad_()
             opt = optim.Adam([lfc], lr=self.lr, weight_decay=0)
             for i in range(self.epochs):
@@ -187,7 +196,7 @@ class AOF:
                     adv_pc = lfc.detach() + hfc
                     if self.clip_func is not None:
                         adv_pc = self.clip_func(adv_pc, data)
-                    lfc.data, hfc = ops.spectral_reproject(adv_pc.contiguous(), V, Vt, lp)
+                    lfc.data, hfc = reproject(adv_pc)
         return data, st
 
     # ---- PointNet victim + this package's functor + ClipPointsLinf: no autograd, every buffer updated IN PLACE, the
@@ -203,7 +212,12 @@ class AOF:
         adv, lfc = buf[:B], buf[B:]
         hfc, coeff, clipped, data, ori = (torch.empty((B, 3, K), **f32) for _ in range(5))
         m, v = torch.zeros((B, 3, K), **f32), torch.zeros((B, 3, K), **f32)
-        V, Vt = torch.empty((B, K, K), **f32), torch.empty((B, K, K), **f32)
+        band = self.basis == "lowband"
+        if band:      # [B,N,lp] instead of V and V^T
+            ops.lowband_block(K, lp)      # refuse a low_pass past the block before anything is allocated
+            U = torch.empty((B, K, lp), **f32)
+        else:
+            V, Vt = torch.empty((B, K, K), **f32), torch.empty((B, K, K), **f32)
         step = torch.zeros((1,), dtype=torch.int32, device=dev)
         label2 = torch.zeros((2 * B,), dtype=torch.long, device=dev)
         label = label2[:B]
@@ -217,15 +231,24 @@ class AOF:
         def rewind_bests():
             st["o_bestdist"].fill_(1e10), st["o_bestscore"].fill_(-1), st["o_bestattack"].zero_()
 
+        def reproject(src):      # lfc, hfc and the next iterate lfc + hfc, straight into the stacked buffer
+            if band:
+                ops.band_reproject(src, U, lfc, hfc, sum=adv)
+            else:
+                ops.spectral_reproject(src, V, Vt, lp, lfc, hfc, coeff, sum=adv)
+
         def begin_step():
-            ops.spectral_reproject(data, V, Vt, lp, lfc, hfc, coeff, sum=adv)      # :145-147
+            reproject(data)      # :145-147
             m.zero_(), v.zero_(), step.zero_()
 
         def new_step():
             data.copy_(self._noisy(ori))
-            _, Vn = get_Laplace_from_pc(data)      # the eigen-decomposition: once per binary step
-            V.copy_(Vn)
-            Vt.copy_(Vn.transpose(2, 1))
+            if band:
+                U.copy_(get_lowband_from_pc(data, lp))      # the low band: once per binary step
+            else:
+                _, Vn = get_Laplace_from_pc(data)      # the eigen-decomposition: once per binary step
+                V.copy_(Vn)
+                Vt.copy_(Vn.transpose(2, 1))
             begin_step()
 
         def iterate():
@@ -234,7 +257,7 @@ class AOF:
                 ops.aof_record(adv, data, pred2[:B], pred2[B:], label, st["o_bestdist"], st["o_bestscore"], st["o_bestattack"],
                                step=step)      # also advances the Adam step word
                 ops.aof_update(lfc, g[:B], g[B:], m, v, hfc, data, step, lr, budget, out=clipped)
-                ops.spectral_reproject(clipped, V, Vt, lp, lfc, hfc, coeff, sum=adv)
+                reproject(clipped)
 
         return dict(iterate=iterate, begin_step=begin_step, new_step=new_step, load=load, rewind_bests=rewind_bests, data=data,
                     buf=buf, label2=label2, st=st, graphs=None)
@@ -245,7 +268,7 @@ class AOF:
         replayed iterations, and the reference's driver calls the attack once per batch of the loader. Rebuilt when the
         shape, the loop's constants, the kernel flavour or the victim's folded weights change."""
         from ...model.pointnet import fused_pack
-        key = (B, K, fk, float(self.lr), int(self.low_pass), float(self.clip_func.budget), bool(ops._det()))
+        key = (B, K, fk, float(self.lr), int(self.low_pass), float(self.clip_func.budget), bool(ops._det()), self.basis)
         c = self._fused_cache
         if c is None or c["key"] != key or c["pack"] is not fused_pack(self.model):
             c = self._fused_cache = self._fused_loop(B, K, fk)

@@ -10,6 +10,11 @@ a [B,N,N,3] tensor); with a PointNet victim and this package's adversarial funct
 the success-check forward use the launch-minimal fused path (no autograd) — the check on model(lfc) reuses the forward
 of the next iteration's loss on the same tensor; bookkeeping stays on the device (the reference copies the whole cloud
 to the host every iteration, :195-208).
+
+``basis="lowband"`` (default ``"full"``): only V[:, :low_pass] enters lfc and hfc = adv - lfc, so the binary step computes
+the [B,N,low_pass] basis of the Laplacian's low band on this package's own kernels (ops.lowband_basis: sparse Laplacian,
+filtered block iteration, no dense [B,N,N] operand and no library eigensolver) and every iteration re-projects on it
+(ops.band_reproject). The block holds low_pass + guard <= 128 columns; a larger low_pass raises ValueError.
 """
 import numpy as np
 import torch
@@ -35,6 +40,21 @@ def get_Laplace_from_pc(ori_pc):
     return e.to(ori_pc), v.to(ori_pc)
 
 
+BASES = ("full", "lowband")
+
+
+def check_basis(basis):
+    if basis not in BASES:
+        raise ValueError(f"basis must be one of {BASES}, got {basis!r}")
+    return basis
+
+
+def get_lowband_from_pc(ori_pc, low_pass):
+    """U [B,N,low_pass]: orthonormal columns spanning the low band of the same Laplacian (ops.lowband_basis)."""
+    with torch.no_grad():
+        return ops.lowband_basis(ori_pc.detach().float().contiguous(), low_pass, 30, cf=True)[0]
+
+
 def _logits_of(out):
     return out[0] if isinstance(out, tuple) else out
 
@@ -43,7 +63,8 @@ class CWTAOF:
     """Class for CW attack."""
 
     def __init__(self, model, adv_func, dist_func, attack_lr=1e-2, binary_step=2, num_iter=200, GAMMA=0.5,
-                 low_pass=100, clip_func=None, device=None, verbose=False, fused=True, graph=True, deterministic=None):
+                 low_pass=100, clip_func=None, device=None, verbose=False, fused=True, graph=True, deterministic=None,
+                 basis="full"):
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.deterministic = deterministic     # None: ops.DETERMINISTIC; True / False: that mode during attack()
         self.model = model.to(self.device)
@@ -59,6 +80,7 @@ class CWTAOF:
         self.verbose = verbose
         self.fused = fused
         self.graph = graph          # capture the fused iteration into a hipGraph (own functors only)
+        self.basis = check_basis(basis)     # "full": dense Laplacian + eigh, V and V^T; "lowband": ops.lowband_basis, U
 
     def _fused_kind(self):
         if not self.fused or not hasattr(self.model, "fused_loss_and_grad"):
@@ -104,10 +126,15 @@ class CWTAOF:
             o_bestdist, o_bestscore, o_bestattack, adv_data = self._attack_fused(ori_data, target, y_truth, fk, lp)
         for binary_step in range(self.binary_step if fk is None else 0):
             adv_data = ori_data.clone().detach() + torch.randn((B, 3, K)).to(dev) * 1e-7
-            Evs, V = get_Laplace_from_pc(adv_data)
-            V = V.float().contiguous()
-            Vt = V.transpose(2, 1).contiguous()     # constant for the whole binary step
-            lfc, hfc = ops.spectral_reproject(adv_data.contiguous(), V, Vt, lp)     # :114-126
+            if self.basis == "lowband":
+                U = get_lowband_from_pc(adv_data, lp)     # constant for the whole binary step
+                reproject = lambda a: ops.band_reproject(a.contiguous(), U)
+            else:
+                Evs, V = get_Laplace_from_pc(adv_data)
+                V = V.float().contiguous()
+                Vt = V.transpose(2, 1).contiguous()     # constant for the whole binary step
+                reproject = lambda a, V=V, Vt=Vt: ops.spectral_reproject(a.contiguous(), V, Vt, lp)
+            lfc, hfc = reproject(adv_data)     # :114-126
             lfc.requires_grad_()
             opt = optim.Adam([lfc], lr=self.attack_lr, weight_decay=0.)
 
@@ -124,7 +151,7 @@ class CWTAOF:
                     adv_data = lfc.detach() + hfc
                     if self.clip_func is not None:
                         adv_data = self.clip_func(adv_data.detach().clone(), ori_data)
-                    lfc.data, hfc = ops.spectral_reproject(adv_data.contiguous(), V, Vt, lp)     # :164-170
+                    lfc.data, hfc = reproject(adv_data)     # :164-170
                     pred = torch.argmax(_logits_of(self.model(adv_data)), dim=1)
                     lfc_pred = torch.argmax(_logits_of(self.model(lfc)), dim=1)
                     dist_val = torch.sqrt(torch.sum((adv_data - ori_data) ** 2, dim=[1, 2]))
@@ -155,9 +182,11 @@ class CWTAOF:
         dev = self.device
         B, _, K = ori_data.shape
         ffw = importlib_fused_forward()
+        band = self.basis == "lowband"
+        if band:
+            ops.lowband_block(K, lp)      # refuse a low_pass past the block before anything is allocated
         st = dict(
-            V=torch.empty((B, K, K), device=dev), Vt=torch.empty((B, K, K), device=dev),
-            coeff=torch.empty((B, 3, K), device=dev), lfc=torch.empty((B, 3, K), device=dev),
+            lfc=torch.empty((B, 3, K), device=dev),
             hfc=torch.empty((B, 3, K), device=dev), adv=torch.empty((B, 3, K), device=dev),
             m=torch.zeros((B, 3, K), device=dev), v=torch.zeros((B, 3, K), device=dev),
             step=torch.zeros((1,), dtype=torch.int32, device=dev),
@@ -167,13 +196,26 @@ class CWTAOF:
             # the success check of iteration i waits for iteration i + 1 (see iterate): what it needs from iteration i
             pend_pred=torch.zeros((B,), dtype=torch.long, device=dev),
             pend_dist=torch.full((B,), 1e10, dtype=torch.float32, device=dev))
+        if band:      # [B,N,lp] instead of V and V^T
+            st["U"] = torch.empty((B, K, lp), device=dev)
+        else:
+            st.update(V=torch.empty((B, K, K), device=dev), Vt=torch.empty((B, K, K), device=dev),
+                      coeff=torch.empty((B, 3, K), device=dev))
+
+        def reproject(adv, lfc, hfc):
+            if band:
+                ops.band_reproject(adv.contiguous(), st["U"], lfc, hfc)
+            else:
+                ops.spectral_reproject(adv.contiguous(), st["V"], st["Vt"], lp, lfc, hfc, st["coeff"])     # V, V^T read once each
 
         def begin_step(adv0, reuse_basis=False):
-            if not reuse_basis:      # the eigen-decomposition is the expensive part (~55 ms at B=32, N=1024)
+            if not reuse_basis and band:
+                st["U"].copy_(get_lowband_from_pc(adv0, lp))
+            elif not reuse_basis:      # the eigen-decomposition is the expensive part (~55 ms at B=32, N=1024)
                 _, V = get_Laplace_from_pc(adv0)
                 st["V"].copy_(V)
                 st["Vt"].copy_(V.transpose(2, 1))
-            ops.spectral_reproject(adv0.contiguous(), st["V"], st["Vt"], lp, st["lfc"], st["hfc"], st["coeff"])
+            reproject(adv0, st["lfc"], st["hfc"])
             st["m"].zero_(), st["v"].zero_(), st["step"].zero_()
             st["pend_dist"].fill_(1e10)      # nothing pending: `dist < o_bestdist` is false for every cloud
 
@@ -205,7 +247,7 @@ class CWTAOF:
                 adv = lfc + hfc
                 if self.clip_func is not None:
                     adv = self.clip_func(adv, ori_data)
-                ops.spectral_reproject(adv.contiguous(), st["V"], st["Vt"], lp, lfc, hfc, st["coeff"])     # V, V^T read once each
+                reproject(adv, lfc, hfc)
                 st["pend_pred"].copy_(torch.argmax(ffw(self.model, adv)[0], dim=1))
                 st["pend_dist"].copy_(torch.sqrt(torch.sum((adv - ori_data) ** 2, dim=[1, 2])))
                 st["adv"].copy_(adv)

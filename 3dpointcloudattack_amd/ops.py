@@ -2567,6 +2567,115 @@ def spectral_reproject(adv, V, Vt, low_pass, lfc=None, hfc=None, coeff=None, sum
     return lfc, hfc
 
 
+# The low-band basis (csrc/lowband.hip): block size m = min(N, lp + max(guard_min, ceil(lp / guard_div))) <=
+# max_block columns; `iters` outer iterations of a Chebyshev filter of degree <= `degree`, cut where its gain over the block
+# would pass min(range_max, range_first * range_growth ** it); Gram eigenvalues floored at gram_floor; the Jacobi solver's
+# thresholds. Settled on tests/lowband_restatement.py (tests/test_lowband_cpu.py), which reads them from here.
+LOWBAND_DEFAULTS = dict(k=30, degree=16, iters=12, guard_min=28, guard_div=4, max_block=128, range_first=100.0, range_growth=10.0,
+                        range_max=1e6, cut_min=1e-3, gram_floor=1e-5, jacobi_rel=6e-8, jacobi_abs=1e-10, jacobi_sweeps=30)
+
+
+def lowband_block(N, low_pass):
+    """Columns of the iteration's block for a cloud of N points; ValueError past the eigensolver's limit."""
+    d = LOWBAND_DEFAULTS
+    lp = int(low_pass)
+    if lp < 0 or lp > N:
+        raise ValueError(f"lowband: low_pass={lp} outside [0, N={N}]")
+    m = int(_lib.load().pc3d_lowband_block(int(N), lp, d["guard_min"], d["guard_div"]))
+    if m > d["max_block"]:
+        guard = m - lp
+        raise ValueError(f"lowband: low_pass={lp} needs a block of {lp} + {guard} guard columns, the limit is "
+                         f"{d['max_block']} (the m x m eigensolver lives in one workgroup's LDS); use basis=\"full\"")
+    return m
+
+
+def graph_laplacian_csr(xyz, k=30, cf=True, capacity=None):
+    """The Laplacian of graph_laplacian as per-cloud CSR: (rowptr [B,N+1] i32, col [B,cap] i32, val [B,cap] f32 — the
+    off-diagonal entries, columns ascending within a row — and deg [B,N], the diagonal). capacity: entries per cloud
+    (default 2 N k, which always fits); a cloud that does not fit raises Pc3dError (one device-to-host read)."""
+    p, bs, ps, cs, B, N = _pts(xyz, cf, "xyz")
+    _, idx = knn_raw(xyz, xyz, min(k, N), q_cf=cf, r_cf=cf)
+    K = idx.shape[2]
+    cap = 2 * N * K if capacity is None else int(capacity)
+    dev = xyz.device
+    rowptr = torch.empty((B, N + 1), dtype=torch.int32, device=dev)
+    col = torch.empty((B, cap), dtype=torch.int32, device=dev)
+    val = torch.empty((B, cap), dtype=torch.float32, device=dev)
+    deg = torch.empty((B, N), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call("pc3d_graph_laplacian_csr_f32", p, bs, ps, cs, idx.data_ptr(), B, N, K, cap, rowptr.data_ptr(), col.data_ptr(),
+                  val.data_ptr(), deg.data_ptr(), _stream())
+    if capacity is not None and B > 0:
+        need = int(rowptr[:, N].max().item())
+        if need > cap:
+            raise _lib.Pc3dError(f"graph_laplacian_csr: a cloud has {need} entries, capacity={cap}")
+    return rowptr, col, val, deg
+
+
+def lowband_basis_csr(rowptr, col, val, deg, low_pass, want_lost=False):
+    """lowband_basis on a CSR Laplacian as graph_laplacian_csr returns it."""
+    d = LOWBAND_DEFAULTS
+    _check(val, "val"), _check(deg, "deg")
+    B, N = deg.shape
+    lp = int(low_pass)
+    m = lowband_block(N, lp)
+    dev = deg.device
+    for nm, t, shape in (("rowptr", rowptr, (B, N + 1)), ("col", col, tuple(val.shape))):
+        if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"lowband_basis_csr: {nm} must be a contiguous int32 tensor of shape {shape} on deg's device")
+    if val.dim() != 2 or val.shape[0] != B or not val.is_contiguous() or not deg.is_contiguous():
+        raise ValueError("lowband_basis_csr: val [B,cap] and deg [B,N] contiguous expected")
+    U = torch.empty((B, N, lp), dtype=torch.float32, device=dev)
+    theta = torch.empty((B, lp), dtype=torch.float32, device=dev)
+    resid = torch.empty((B,), dtype=torch.float32, device=dev)
+    lost = torch.empty((B,), dtype=torch.int32, device=dev) if want_lost else None
+    nbytes = int(_lib.load().pc3d_lowband_ws_bytes(B, N, m, d["degree"]))
+    ws = torch.empty((max(nbytes, 8) // 8 + 1,), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call("pc3d_lowband_basis_f32", rowptr.data_ptr(), col.data_ptr(), val.data_ptr(), deg.data_ptr(), B, N, val.shape[1],
+                  lp, m, d["degree"], d["iters"], d["range_first"], d["range_growth"], d["range_max"], d["cut_min"],
+                  d["gram_floor"], d["jacobi_rel"], d["jacobi_abs"], d["jacobi_sweeps"], U.data_ptr(), theta.data_ptr(),
+                  resid.data_ptr(), _ptr(lost), ws.data_ptr(), ws.numel() * 8, _stream())
+    return (U, theta, resid, lost) if want_lost else (U, theta, resid)
+
+
+def lowband_basis(xyz, low_pass, k=30, cf=True):
+    """(U [B,N,lp], theta [B,lp], resid [B]): orthonormal columns spanning the eigenspace of the lowest low_pass eigenvalues
+    of the kNN-k Gaussian graph Laplacian of xyz, the Ritz values ascending, and max_i |L u_i - theta_i u_i|_inf — without
+    the dense [B,N,N] matrix and without a library eigensolver (LOWBAND_DEFAULTS: the schedule). low_pass + guard columns
+    must fit the 128-column block: ValueError otherwise. Draws nothing from torch's generators."""
+    N = xyz.shape[2] if cf else xyz.shape[1]
+    lowband_block(N, low_pass)      # refuse before any launch
+    return lowband_basis_csr(*graph_laplacian_csr(xyz, k, cf), low_pass)
+
+
+def band_reproject(adv, U, lfc=None, hfc=None, coeff=None, sum=None):
+    """AOF's re-projection on a band basis U [B,N,lp] (lowband_basis): (lfc, hfc) = ((adv U) U^T, adv - lfc) for adv
+    [B,3,N], written into the given buffers when passed; coeff [B,3,lp] receives adv U, sum [B,3,N] receives lfc + hfc as
+    that fp32 sum. The outputs may be slices along dim 0 of larger buffers. No gradient."""
+    for nm, t in (("adv", adv), ("U", U)):
+        _check(t, nm)
+        if not t.is_contiguous():
+            raise ValueError(f"band_reproject: {nm} must be contiguous")
+    B, three, N = adv.shape
+    if three != 3 or U.dim() != 3 or U.shape[:2] != (B, N) or U.device != adv.device:
+        raise ValueError("band_reproject: adv [B,3,N] and U [B,N,lp] on one device expected")
+    lp = U.shape[2]
+    mk = lambda t: torch.empty((B, 3, N), dtype=torch.float32, device=adv.device) if t is None else t
+    lfc, hfc = mk(lfc), mk(hfc)
+    for nm, t in (("lfc", lfc), ("hfc", hfc)) + ((("sum", sum),) if sum is not None else ()):
+        if t.shape != (B, 3, N) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != adv.device:
+            raise ValueError(f"band_reproject: {nm} must be a contiguous fp32 [B,3,N] tensor on adv's device")
+    if coeff is not None and (coeff.shape != (B, 3, lp) or coeff.dtype != torch.float32 or not coeff.is_contiguous()
+                              or coeff.device != adv.device):
+        raise ValueError("band_reproject: coeff must be a contiguous fp32 [B,3,lp] tensor on adv's device")
+    ws = torch.empty((max(1, int(_lib.load().pc3d_band_reproject_ws_floats(B, N, lp))),), dtype=torch.float32, device=adv.device)
+    with torch.cuda.device(adv.device):
+        _lib.call("pc3d_band_reproject_f32", adv.data_ptr(), U.data_ptr(), B, N, lp, _ptr(coeff), lfc.data_ptr(), hfc.data_ptr(),
+                  _ptr(sum), ws.data_ptr(), _stream())
+    return lfc, hfc
+
+
 def _aof_blocks(fn, B, N, dev, **tensors):
     for nm, t in tensors.items():
         if t is None:

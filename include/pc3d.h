@@ -934,6 +934,41 @@ int pc3d_spectral_reproject_sum_f32(const float* adv, const float* V, const floa
 int pc3d_rowdot3_f32(const float* mat, const float* vec, int B, int R, int K, int split, float* out_lo, float* out_hi,
                      void* stream);
 
+/* K12d  the low band of the Laplacian without a dense decomposition (csrc/lowband.hip).
+ *
+ * pc3d_graph_laplacian_csr_f32: the Laplacian of pc3d_graph_laplacian_f32 as per-cloud CSR. rowptr [B,N+1]; col, val
+ * [B,cap] hold the off-diagonal entries -exp(-|pi-pj|^2) (the same arithmetic, the same symmetrised mask, self excluded),
+ * columns ascending within a row; deg [B,N] is the diagonal, summed in a fixed order. A pure function of its inputs (no
+ * atomics). cap is the caller's capacity per cloud: nothing is written past it, and rowptr[b,N] > cap tells the caller
+ * that cloud b did not fit (2 N K always fits; there is no bound on a row's in-degree below N - 1). */
+int pc3d_graph_laplacian_csr_f32(const float* xyz, int64_t x_bs, int64_t x_ps, int64_t x_cs, const int32_t* idx, int B, int N,
+                                 int K, int cap, int32_t* rowptr, int32_t* col, float* val, float* deg, void* stream);
+/* The block size m = min(N, lp + max(guard_min, ceil(lp / guard_div))) of the iteration below (-1: bad arguments), and the
+ * bytes of its workspace. */
+int pc3d_lowband_block(int N, int lp, int guard_min, int guard_div);
+int64_t pc3d_lowband_ws_bytes(int B, int N, int m, int degree);
+/* U [B,N,lp] (orthonormal columns spanning the eigenspace of the lowest lp eigenvalues), theta [B,lp] (the Ritz values,
+ * ascending) and resid [B] = max_i |L u_i - theta_i u_i|_inf of the CSR Laplacian above, by Chebyshev-filtered block
+ * subspace iteration on m <= 128 columns: `iters` outer iterations of a filter of degree <= `degree` (cut where its gain
+ * over the block would pass min(range_max, range_first range_growth^it)), two symmetric orthonormalisations through the
+ * Gram matrix's eigendecomposition (eigenvalues floored at gram_floor; lost [B], may be NULL, counts the floored ones) and
+ * a Rayleigh-Ritz step, the m x m problems on a parallel cyclic Jacobi solver (rotations below jacobi_rel sqrt|a_pp a_qq|
+ * + jacobi_abs max|a_ii| skipped, at most jacobi_sweeps sweeps). Filter bounds on the device: upper 2 max deg, lower cut
+ * the largest Ritz value of the previous iteration, anchor the smallest, kept cut_min of the upper bound apart. The start
+ * block is a hash of (row, column). A fixed launch sequence without host synchronisation; each cloud is a function of its
+ * own rows alone. ws: pc3d_lowband_ws_bytes bytes, 8-byte aligned. */
+int pc3d_lowband_basis_f32(const int32_t* rowptr, const int32_t* col, const float* val, const float* deg, int B, int N, int cap,
+                           int lp, int m, int degree, int iters, float range_first, float range_growth, float range_max,
+                           float cut_min, float gram_floor, float jacobi_rel, float jacobi_abs, int jacobi_sweeps, float* U,
+                           float* theta, float* resid, int32_t* lost, void* ws, int64_t ws_bytes, void* stream);
+/* AOF's re-projection on the band basis: coeff = adv U [B,3,lp] (may be NULL), lfc = coeff U^T, hfc = adv - lfc, and with
+ * sum != NULL sum = lfc + hfc as that fp32 sum (the next iterate of the untargeted loop); adv, lfc, hfc, sum [B,3,N]
+ * contiguous, each output its own pointer (they may be slices of larger buffers), U [B,N,lp]. Two launches that read U
+ * once each, sums in a fixed order. ws: pc3d_band_reproject_ws_floats floats. */
+int64_t pc3d_band_reproject_ws_floats(int B, int N, int lp);
+int pc3d_band_reproject_f32(const float* adv, const float* U, int B, int N, int lp, float* coeff, float* lfc, float* hfc,
+                            float* sum, float* ws, void* stream);
+
 /* K12c  bookkeeping of the untargeted AOF loop on the device (attack/AOF/Eval_AOF.py:168-185), one workgroup per
  * cloud: dist = max |adv - data| over the whole [3,N] cloud (an exact maximum: the bits of torch.amax); where
  * pred != label && dist < o_bestdist && lfc_pred != label (strict <) update (o_bestdist, o_bestscore) and copy adv[b]

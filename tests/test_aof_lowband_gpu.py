@@ -1,0 +1,160 @@
+"""GPU: the AOF attacks on the low-band basis (basis="lowband") — against the real reference's runs with the acceptance
+statistics of the full-basis tests (tests/test_aof_gpu.py, tests/test_aof_untargeted_gpu.py), graph replay against eager bit
+for bit, and the default basis untouched."""
+import importlib
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import GOLDEN
+from helpers import hip_pointnet, unit_cloud
+
+pytestmark = pytest.mark.gpu
+
+
+def _mods():
+    m = importlib.import_module
+    return (m("3dpointcloudattack_amd.attack.AOF.TAOF_attack"), m("3dpointcloudattack_amd.attack.AOF.Eval_AOF"),
+            m("3dpointcloudattack_amd.attack.CW.CW_utils.adv_utils"), m("3dpointcloudattack_amd.attack.CW.CW_utils.dist_utils"),
+            m("3dpointcloudattack_amd.attack.CW.CW_utils.clip_utils"))
+
+
+def _clouds(seed, B, N):
+    rng = np.random.default_rng(seed)
+    return torch.from_numpy(np.stack([unit_cloud(rng, N) for _ in range(B)]))
+
+
+def _targets(net, pcs, dev):
+    with torch.no_grad():
+        lp = net(pcs.transpose(1, 2).contiguous().to(dev))[0]
+    return lp.argmax(1).cpu(), lp.topk(2)[1][:, 1].cpu()
+
+
+@pytest.mark.parametrize("fused", [False, True])
+def test_taof_lowband_vs_reference(dev, fused):
+    """The statistics of test_taof_attack_vs_reference, unchanged."""
+    ta, _, adv, dist, clip = _mods()
+    fx = np.load(os.path.join(GOLDEN, "aof.npz"))
+    net, _ = hip_pointnet(0, dev)
+    atk = ta.CWTAOF(net, adv.LogitsAdvLoss(kappa=0.), dist.L2Dist(), attack_lr=1e-2, binary_step=2, num_iter=10, GAMMA=0.5,
+                    low_pass=40, clip_func=clip.ClipPointsLinf(budget=0.18), fused=fused, basis="lowband")
+    torch.manual_seed(31)
+    np.random.seed(31)
+    bd, out, sn = atk.attack(torch.from_numpy(fx["atk_pc"]), torch.from_numpy(fx["atk_target"]), torch.from_numpy(fx["atk_ytruth"]))
+    dev_abs = np.abs(out - fx["atk_adv"])
+    print(f"lowband fused={fused}: success {sn} bestdist {bd} (reference {fx['atk_bestdist']}) clouds median {np.median(dev_abs):.2e} "
+          f"share <= 1e-4 {(dev_abs <= 1e-4).mean():.3f} q99 {np.quantile(dev_abs, 0.99):.2e}")
+    assert out.shape == fx["atk_adv"].shape and bd.shape == (1,)
+    assert sn == int(fx["atk_success"])
+    assert np.array_equal(bd < 1e9, fx["atk_bestdist"] < 1e9)
+    if (bd < 1e9).all():
+        np.testing.assert_allclose(bd, fx["atk_bestdist"], rtol=2e-2)
+    assert np.median(dev_abs) < 1e-5 and (dev_abs <= 1e-4).mean() > 0.9 and np.quantile(dev_abs, 0.99) < 1e-2
+
+
+@pytest.mark.parametrize("fused", [False, True])
+@pytest.mark.parametrize("case", ["mixed", "long"])
+def test_untargeted_lowband_vs_reference(dev, case, fused):
+    """The assertions of test_aof_untargeted_gpu.py::test_attack_vs_reference, unchanged."""
+    _, ea, adv, _, clip = _mods()
+    fx = np.load(os.path.join(GOLDEN, "aof_untargeted.npz"))
+    f = {k.split("/", 1)[1]: fx[k] for k in fx.files if k.startswith(case + "/")}
+    net, _ = hip_pointnet(0, dev)
+    trans, _ = hip_pointnet(1, dev)
+    atk = ea.AOF(net, trans, adv.UntargetedLogitsAdvLoss(kappa=float(f["kappa"])), clip.ClipPointsLinf(budget=float(f["budget"])),
+                 lr=float(f["lr"]), low_pass=int(f["low_pass"]), step=int(f["step"]), epochs=int(f["epochs"]),
+                 batch_size=int(f["batch_size"]), fused=fused, basis="lowband")
+    assert (atk._fused_kind() is not None) == fused
+    torch.manual_seed(int(f["torch_seed"]))
+    np.random.seed(int(f["torch_seed"]))
+    bd, out, sn = atk.attack(torch.from_numpy(f["data"]), torch.from_numpy(f["label"]))
+    assert out.shape == f["best_pc"].shape and out.dtype == np.float32 and bd.dtype == np.float64
+    found = f["o_bestscore"] >= 0
+    dev_abs = np.abs(out.astype(np.float64) - f["best_pc"])
+    ddist = np.abs(bd[found] - f["o_bestdist"][found])
+    print(f"lowband {case} fused={fused}: found {(bd < 1e9).astype(int).tolist()} o_bestdist {ddist.max() if found.any() else 0:.2e} "
+          f"(band {float(f['band_dist_abs']):.2e}) clouds median {np.median(dev_abs):.2e} q90 {np.quantile(dev_abs, 0.9):.2e} "
+          f"q99 {np.quantile(dev_abs, 0.99):.2e} max {dev_abs.max():.2e} (bands {float(f['band_pc_q50']):.2e} "
+          f"{float(f['band_pc_q90']):.2e} {float(f['band_pc_q99']):.2e})")
+    assert np.array_equal(bd < 1e9, found)
+    assert np.array_equal(atk.o_bestscore.cpu().numpy(), f["o_bestscore"])
+    assert np.array_equal(atk.preds.cpu().numpy(), f["preds"]) and np.array_equal(atk.trans_preds.cpu().numpy(), f["trans_preds"])
+    assert np.array_equal(atk.shuffle_preds.cpu().numpy(), f["shuffle_preds"])
+    assert np.array_equal(atk.shuffle_trans_preds.cpu().numpy(), f["shuffle_trans_preds"])
+    assert sn == int(f["at_num"]) and atk.trans_num == int(f["trans_num"])
+    assert np.all(bd[~found] == 1e10)
+    if (~found).any():
+        last = torch.from_numpy(f["data_last"]).to(dev)
+        want = clip.ClipPointsLinf(float(f["budget"]))(torch.zeros_like(last), last).transpose(1, 2).cpu().numpy()
+        assert np.array_equal(out[~found], want[~found])
+    assert ddist.max() <= float(f["band_dist_abs"])
+    assert np.median(dev_abs) <= float(f["band_pc_q50"]) and (dev_abs <= float(f["band_pc_q90"])).mean() >= 0.9 \
+        and np.quantile(dev_abs, 0.99) <= float(f["band_pc_q99"])
+
+
+def test_taof_lowband_graph_replay_equals_eager(dev):
+    ta, _, adv, dist, clip = _mods()
+    net, _ = hip_pointnet(0, dev)
+    pcs = _clouds(15, 3, 160)
+    y, tgt = _targets(net, pcs, dev)
+    outs = []
+    for graph in (False, True):
+        atk = ta.CWTAOF(net, adv.LogitsAdvLoss(0.), dist.L2Dist(), binary_step=2, num_iter=8, low_pass=30,
+                        clip_func=clip.ClipPointsLinf(0.18), graph=graph, basis="lowband")
+        assert atk._capturable() == graph
+        torch.manual_seed(4)
+        outs.append(atk.attack(pcs, tgt, y))
+    assert np.array_equal(outs[0][0], outs[1][0]) and np.array_equal(outs[0][1], outs[1][1]) and outs[0][2] == outs[1][2]
+
+
+def test_untargeted_lowband_graph_replay_equals_eager(dev):
+    _, ea, adv, _, clip = _mods()
+    net, _ = hip_pointnet(0, dev)
+    trans, _ = hip_pointnet(1, dev)
+    pcs = _clouds(15, 3, 160)
+    y = _targets(net, pcs, dev)[0]
+    res = []
+    for graph in (False, True):
+        atk = ea.AOF(net, trans, adv.UntargetedLogitsAdvLoss(kappa=30.), clip.ClipPointsLinf(0.18), low_pass=30, step=2, epochs=9,
+                     graph=graph, basis="lowband")
+        assert atk._fused_kind() is not None
+        torch.manual_seed(4)
+        np.random.seed(4)
+        res.append((atk, *atk.attack(pcs, y)))
+    (a0, bd0, out0, sn0), (a1, bd1, out1, sn1) = res
+    assert np.array_equal(bd0, bd1) and np.array_equal(out0, out1) and sn0 == sn1
+    assert torch.equal(a0.o_bestscore, a1.o_bestscore) and torch.equal(a0.shuffle_preds, a1.shuffle_preds)
+    # the basis is part of the cached loop's key
+    a1.basis = "full"
+    torch.manual_seed(4)
+    np.random.seed(4)
+    key = a1._fused_cache["key"]
+    a1.attack(pcs, y)
+    assert a1._fused_cache["key"] != key and a1._fused_cache["key"][-1] == "full"
+
+
+def test_default_basis_is_full_and_its_bits_are_those_of_the_explicit_option(dev):
+    """basis="full" is the default of both classes and takes the dense path: the default and the explicit option give the
+    same bits on test_taof_batched's case, and the dense path's bits are not those of the band path."""
+    ta, ea, adv, dist, clip = _mods()
+    net, _ = hip_pointnet(0, dev)
+    pcs = _clouds(5, 3, 128)
+    y, tgt = _targets(net, pcs, dev)
+    runs = {}
+    for name, kw in (("default", {}), ("full", dict(basis="full")), ("lowband", dict(basis="lowband"))):
+        atk = ta.CWTAOF(net, adv.LogitsAdvLoss(0.), dist.L2Dist(), binary_step=1, num_iter=5, low_pass=20,
+                        clip_func=clip.ClipPointsLinf(0.18), **kw)
+        torch.manual_seed(2)
+        runs[name] = atk.attack(pcs, tgt, y)
+    assert ta.CWTAOF(net, None, None).basis == "full" and ea.AOF(net, net, None, None).basis == "full"
+    assert np.array_equal(runs["default"][0], runs["full"][0]) and np.array_equal(runs["default"][1], runs["full"][1])
+    assert runs["default"][2] == runs["full"][2]
+    assert runs["lowband"][1].shape == (3, 128, 3) and np.isfinite(runs["lowband"][1]).all()
+    assert np.abs(runs["lowband"][1] - runs["full"][1]).max() < 1e-2      # the same attack, another rounding
+    with pytest.raises(ValueError, match="basis"):
+        ta.CWTAOF(net, None, None, basis="sparse")
+    with pytest.raises(ValueError, match=r"128.*full"):
+        ta.CWTAOF(net, adv.LogitsAdvLoss(0.), dist.L2Dist(), low_pass=120, basis="lowband").attack(
+            _clouds(1, 1, 256), torch.zeros(1, dtype=torch.long), torch.zeros(1, dtype=torch.long))
