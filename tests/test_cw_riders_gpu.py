@@ -176,7 +176,7 @@ def _tower(dev, C3, seed):
 
 
 @pytest.mark.parametrize("hits", ["natural", "one_tile"])
-@pytest.mark.parametrize("N", [256, 1024, 200, 77])
+@pytest.mark.parametrize("N", [256, 1024, 200, 77, 1025, 2048])     # past 1024: cw_update_kernel<2> on the other side
 @pytest.mark.parametrize("dist_kind", [0, 1, 2])
 def test_bwd_update_matches_bwd_then_cw_update(dev, dist_kind, N, hits):
     B, C3 = 6, 1024
