@@ -6,6 +6,9 @@ The loop (:99-141) runs on the device without host synchronisation: the per-iter
 (:113-115) is dropped from the loop (it only fed a discarded local), Adam + ProjectInnerClipLinf are ONE HIP launch
 when the clip functor is this package's own, and the regularisers are the fused NN / kNN kernels. B > 1 works; the
 transfer / fail counters are sums over the batch. Transfer models may be ``None`` (skipped).
+
+``device_loop=True`` (PointNet victims, see ``CWKNN._device_loop_plan``): the iteration is the victim's launch-minimal
+passes, the two searches and ONE update launch (pc3d_knn_attack_update_f32), replayed from a hipGraph without autograd.
 """
 import numpy as np
 import torch
@@ -50,12 +53,15 @@ class CWKNN:
 
     def __init__(self, model, pt_model, ptm_model, pts_model, dgcnn_model, cur_model, adv_func, dist_func, clip_func,
                  attack_lr=1e-3, num_iter=2500, attack_method='untarget', device=None, verbose=False, fused=True,
-                 graph=True, sample_seeds=None, global_batch=None, deterministic=None):
+                 graph=True, sample_seeds=None, global_batch=None, deterministic=None, device_loop=False):
         """Extra keywords (defaults = the reference's behaviour). For sharded runs: `sample_seeds` (one int
         per sample) draws every sample's start noise AND a PointNet++ victim's FPS start indices from that sample's own
         generator instead of the shared global stream, and `global_batch` is the size of the unsharded batch whose loss
         mean the shard is a part of — with both, a sample's trajectory does not depend on the batch or rank it runs in
-        (bit for bit: the backward kernels sum in a fixed order, ops.DETERMINISTIC)."""
+        (bit for bit: the backward kernels sum in a fixed order, ops.DETERMINISTIC).
+        `device_loop=True` runs the iteration as a captured chain of own kernels when the victim, the functors and the
+        cloud size allow it (_device_loop_plan), and silently the usual path otherwise; `last_path` says which one the
+        last attack() took: "device_loop", "direct" (own functors through autograd) or "generic"."""
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
 
         def prep(m):
@@ -91,6 +97,10 @@ class CWKNN:
         self.sample_seeds = sample_seeds
         self.global_batch = global_batch
         self.deterministic = deterministic     # None: ops.DETERMINISTIC; True / False: that mode during attack()
+        self.graph = graph
+        self.device_loop = device_loop
+        self.last_path = None
+        self._loop_cache = None                # the device loop's buffers and captured graphs, kept from call to call
 
     def _success(self, pred, target):
         return (pred != target) if self.attack_method == 'untarget' else (pred == target)
@@ -105,6 +115,107 @@ class CWKNN:
         if type(cf) in (_clip_utils.ClipPointsLinf, _dist_utils.ClipPointsLinf):
             return float(cf.budget), False
         return None
+
+    # ---- device loop (PointNet victim + own functors): no autograd, every buffer updated IN PLACE, replayed from hipGraphs ----
+    def _device_loop_plan(self, B, K, has_normal):
+        """The constants of the device loop when it applies, else None: a GPU victim with fused_attack_grad (the two
+        PointNetCls variants), an adversarial functor the CW loop maps to ops.LOSS_KINDS, ChamferkNNDist / ChamferDist
+        with 'adv2ori', a clip functor _fused_clip() recognises, and a cloud the update kernel holds."""
+        from ..CW.CW_attack import CW as _CW
+        victim = getattr(self.model, "model", self.model) if isinstance(self.model, _graphed.GraphedVictim) else self.model
+        fc = self._fused_clip()
+        if fc is None or self.device.type != "cuda" or not hasattr(victim, "fused_attack_grad") or K > ops.KNN_LOOP_MAX_POINTS:
+            return None
+        if next(victim.parameters()).device.type != "cuda":
+            return None
+        kind = _CW._own_adv_kind(self)          # the CW loop's mapping of the adversarial functors
+        if kind is None:
+            return None
+        df = self.dist_func
+        # The batch mean and the shard ratio together are 1 / G, G the size of the whole batch: the constants are prepared
+        # from G itself, so a sample's bits depend on neither the shard it runs in nor that shard's size. Without
+        # global_batch (G = B) these are the float32 steps of the direct path's per_sample_terms / scaled_gvec.
+        G = int(self.global_batch) if self.global_batch else B
+        up = np.float32(K)
+        if type(df) is _dist_utils.ChamferkNNDist and df.chamfer_dist.method == 'adv2ori':
+            k, alpha = int(df.knn_dist.k), float(df.knn_dist.alpha)
+            if not (1 <= k <= 63 and k + 1 <= K):
+                return None
+            c_ch, c_knn = ops.knn_attack_scales(K, k, G, up * np.float32(df.w1), up * np.float32(df.w2))
+        elif type(df) is _dist_utils.ChamferDist and df.method == 'adv2ori':
+            k, alpha = 0, 0.0
+            c_ch, c_knn = ops.knn_attack_scales(K, 0, G, up, None)
+        else:
+            return None
+        return dict(victim=victim, kind=kind, k=k, alpha=alpha, c_ch=float(c_ch), c_knn=float(c_knn), budget=fc[0],
+                    clip_mode="project_clip" if fc[1] else "clip", scale=1.0 / G, has_normal=bool(has_normal and fc[1]))
+
+    def _device_loop_state(self, plan, B, K):
+        """Buffers (static: the graphs point at them), the iteration body and the captured graphs, rebuilt when the shape,
+        a constant of the loop, the kernel flavour or the victim's weights change."""
+        victim, dev = plan["victim"], self.device
+        wkey = tuple((t.data_ptr(), t._version) for t in list(victim.parameters()) + list(victim.buffers()))
+        key = (B, K, float(self.attack_lr), bool(self.graph), bool(ops._det()), wkey,
+               tuple(sorted((n, v) for n, v in plan.items() if n != "victim")))
+        c = self._loop_cache
+        if c is not None and c["key"] == key:
+            return c
+        f32 = dict(dtype=torch.float32, device=dev)
+        adv, ori, m, v = (torch.zeros((B, 3, K), **f32) for _ in range(4))
+        normal = torch.zeros((B, 3, K), **f32) if plan["has_normal"] else None
+        k = plan["k"]
+        knn_d = torch.zeros((B, K, k + 1), **f32) if k else None
+        knn_idx = torch.zeros((B, K, k + 1), dtype=torch.int32, device=dev) if k else None      # also the search's hint
+        nn_d, nn_idx = torch.zeros((B, K), **f32), torch.zeros((B, K), dtype=torch.int32, device=dev)
+        step = torch.zeros((1,), dtype=torch.int32, device=dev)
+        pred = torch.zeros((B,), dtype=torch.long, device=dev)
+        target = torch.zeros((B,), dtype=torch.long, device=dev)
+        kind, kappa = plan["kind"]
+
+        def body():
+            # one chain on one stream: the victim's passes (the classifier tail advances the step word), the self-kNN
+            # search hinted by its own last result, the adv -> ori search, the update
+            with torch.no_grad():
+                _, _, gx = victim.fused_attack_grad(adv, target, kind, kappa, pred_out=pred, step=step, scale=plan["scale"])
+                if k:
+                    ops.knn_search_into(adv, knn_d, knn_idx)
+                ops.nn_search_into(adv, ori, nn_d, nn_idx)
+                ops.knn_attack_update(adv, ori, gx, m, v, step, self.attack_lr, knn_d, knn_idx, nn_idx, plan["c_ch"],
+                                      plan["c_knn"], plan["alpha"], plan["budget"], plan["clip_mode"], normal)
+
+        def rewind(adv0):
+            adv.copy_(adv0)
+            m.zero_(), v.zero_(), step.zero_()
+
+        c = self._loop_cache = dict(key=key, adv=adv, ori=ori, normal=normal, target=target, body=body, rewind=rewind,
+                                    graphs=None, plan=plan, m=m, v=v, step=step, pred=pred, knn_d=knn_d, knn_idx=knn_idx,
+                                    nn_d=nn_d, nn_idx=nn_idx)
+        return c
+
+    LOOP_BLOCK = 16      # iterations per graph replay; the remainder replays single-iteration graphs
+
+    def _run_device_loop(self, plan, adv_data, ori_data, normal, target):
+        B, _, K = adv_data.shape
+        c = self._device_loop_state(plan, B, K)
+        with torch.no_grad():
+            c["ori"].copy_(ori_data)
+            c["target"].copy_(target)
+            if c["normal"] is not None:
+                c["normal"].copy_(normal)
+            c["rewind"](adv_data)
+            if self.graph and c["graphs"] is None and self.num_iter > 0:
+                # capture once (after eager warm-up passes on a side stream, as torch requires), then rewind the state
+                c["graphs"] = _graphed.LoopGraph(c["body"], self.device, 2, counts=(1, self.LOOP_BLOCK), owners=(plan["victim"],))
+                c["rewind"](adv_data)
+            if not self.graph:
+                for _ in range(self.num_iter):
+                    c["body"]()
+            else:
+                for _ in range(self.num_iter // self.LOOP_BLOCK):
+                    c["graphs"].replay(self.LOOP_BLOCK)
+                for _ in range(self.num_iter % self.LOOP_BLOCK):
+                    c["graphs"].replay(1)
+            adv_data.copy_(c["adv"])
 
     def attack(self, data, target):
         """Attack on given data to target.
@@ -160,6 +271,11 @@ class CWKNN:
             opt = optim.Adam([adv_data], lr=self.attack_lr, weight_decay=0.)
         else:
             exp_avg, exp_avg_sq = torch.zeros_like(adv_data), torch.zeros_like(adv_data)
+        plan = self._device_loop_plan(B, K, normal is not ori_data) if self.device_loop else None
+        if plan is not None:
+            self.last_path = "device_loop"
+            self._run_device_loop(plan, adv_data, ori_data, normal, target)
+            return self._finish(adv_data, target, B)
         ori_t = ori_data.transpose(1, 2).contiguous()
         # Own functors on both sides: the loss is never assembled. Each functor hands back its per-sample terms with
         # d loss / d term built in (per_sample / per_sample_terms: the batch means, `* K`, the functor's own weights and the
@@ -170,6 +286,7 @@ class CWKNN:
         direct = (fc is not None and adv_data.is_cuda and type(self.dist_func) in own_dist
                   and hasattr(self.adv_func, "per_sample") and getattr(self, "direct_terms", True)
                   and clean_logits.dim() == 2 and 2 <= clean_logits.shape[1] <= 64 and clean_logits.dtype == torch.float32)
+        self.last_path = "direct" if direct else "generic"
         if direct:
             adv_alias = adv_data.detach().requires_grad_()           # same storage: follows the in-place updates
             up_adv = np.float32(ratio)
@@ -239,7 +356,9 @@ class CWKNN:
         finally:
             if predrawn is not None:
                 _pn2.set_fps_start_source(prev_source)
+        return self._finish(adv_data, target, B)
 
+    def _finish(self, adv_data, target, B):
         # end of CW attack
         with torch.no_grad():
             pred = torch.argmax(_logits_of(self.model(adv_data)), dim=-1)  # [B]

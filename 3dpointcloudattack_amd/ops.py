@@ -1055,6 +1055,92 @@ def cw_update(adv, ori, pred, label, untarget, bestdist, bestscore, o_bestdist, 
     return adv
 
 
+KNN_LOOP_MAX_POINTS = 4096      # pc3d_knn_attack_update_f32 keeps a sample in LDS: 32 B a point + 8 KiB = 136 KiB of 160 (include/pc3d.h)
+KNN_CLIP_MODES = {"clip": 0, "project_clip": 1}
+
+
+def knn_search_into(adv, d, idx, cf=True):
+    """The sorted self-kNN of adv into the caller's OWN buffers d (float32) / idx (int32) [B,N,K], idx also being the search's
+    hint (pc3d_knn_hint_f32 allows hint == idx): an attack loop keeps one pair for as long as its graph lives, so every
+    search starts from the previous iteration's neighbours. The result never depends on what idx held."""
+    p, bs, ps, cs, B, N = _pts(adv, cf, "adv")
+    K = idx.shape[-1]
+    for nm, t, dt in (("d", d, torch.float32), ("idx", idx, torch.int32)):
+        if t.dtype != dt or tuple(t.shape) != (B, N, K) or not t.is_contiguous() or t.device != adv.device:
+            raise ValueError(f"knn_search_into: {nm} must be a contiguous {dt} [B,N,K] tensor on adv's device")
+    if not (2 <= K <= min(64, N)):
+        raise ValueError(f"knn_search_into: K={K} out of range [2, min(64, N={N})]")
+    with torch.cuda.device(adv.device):
+        _lib.call("pc3d_knn_hint_f32", p, bs, ps, cs, p, bs, ps, cs, B, N, N, K, d.data_ptr(), idx.data_ptr(),
+                  idx.data_ptr() if KNN_HINTS and N >= KNN_HINT_MIN_M else 0, _stream())
+    return d, idx
+
+
+def nn_search_into(q, r, d, idx, cf=True):
+    """ops.nn_raw into the caller's own buffers d (float32) / idx (int32) [B,N]."""
+    qp, qbs, qps, qcs, B, N = _pts(q, cf, "q")
+    rp, rbs, rps, rcs, B2, M = _pts(r, cf, "r")
+    for nm, t, dt in (("d", d, torch.float32), ("idx", idx, torch.int32)):
+        if t.dtype != dt or tuple(t.shape) != (B, N) or not t.is_contiguous() or t.device != q.device:
+            raise ValueError(f"nn_search_into: {nm} must be a contiguous {dt} [B,N] tensor on q's device")
+    if B != B2 or M < 1:
+        raise ValueError("nn_search_into: q and r must share the batch dimension, r must not be empty")
+    with torch.cuda.device(q.device):
+        _lib.call("pc3d_nn_f32", qp, qbs, qps, qcs, rp, rbs, rps, rcs, B, N, M, d.data_ptr(), idx.data_ptr(), _stream())
+    return d, idx
+
+
+def knn_attack_update(adv, ori, g, m, v, step, lr, knn_d=None, knn_idx=None, nn_idx=None, c_chamfer=0.0, c_knn=0.0,
+                      alpha=1.05, budget=0.0, clip_mode="project_clip", normal=None, betas=(0.9, 0.999), eps=1e-8, cf=True):
+    """The kNN attack's update as one launch (see pc3d_knn_attack_update_f32): adv [B,3,N] (cf) is updated IN PLACE from
+    the victim's gradient g, the self-kNN result knn_d / knn_idx [B,N,k+1] and the adv -> ori arg-mins nn_idx [B,N]. `step`
+    (int32 device word or int) is only READ. c_chamfer / c_knn: float32 constants (the header says what they carry);
+    c_knn == 0 or no knn_idx: no kNN term. clip_mode: "clip" or "project_clip" (normal None: ori doubles as the normal)."""
+    _, _, _, _, B, N = _pts(adv, cf, "adv")
+    _check(g, "g"), _check(ori, "ori")
+    for nm, t in (("m", m), ("v", v)):
+        _check(t, nm)
+        if t.shape != adv.shape or t.stride() != adv.stride():
+            raise ValueError(f"knn_attack_update: {nm} must share adv's shape and strides")
+    for nm, t in (("ori", ori), ("g", g), ("normal", normal)):
+        if t is not None and (t.shape != adv.shape or t.device != adv.device):
+            raise ValueError(f"knn_attack_update: {nm} must have adv's shape and device")
+    k = 0
+    if knn_idx is not None:
+        if knn_d is None or knn_d.dtype != torch.float32 or knn_idx.dtype != torch.int32 or knn_d.shape != knn_idx.shape \
+                or knn_idx.dim() != 3 or tuple(knn_idx.shape[:2]) != (B, N) or not knn_d.is_contiguous() \
+                or not knn_idx.is_contiguous() or knn_d.device != adv.device or knn_idx.device != adv.device:
+            raise ValueError("knn_attack_update: knn_d (float32) / knn_idx (int32) must be contiguous [B,N,k+1] tensors on adv's device")
+        k = knn_idx.shape[2] - 1
+    if nn_idx is not None and (nn_idx.dtype != torch.int32 or tuple(nn_idx.shape) != (B, N) or not nn_idx.is_contiguous()
+                               or nn_idx.device != adv.device):
+        raise ValueError("knn_attack_update: nn_idx must be a contiguous int32 [B,N] tensor on adv's device")
+    if isinstance(step, torch.Tensor):
+        if step.dtype != torch.int32 or step.device != adv.device:
+            raise TypeError("knn_attack_update: the step word must be an int32 tensor on adv's device")
+        step_dev, step_host = step.data_ptr(), 0
+    else:
+        step_dev, step_host = 0, int(step)
+    with torch.cuda.device(adv.device):
+        _lib.call("pc3d_knn_attack_update_f32", *_pv(adv, cf, "adv"), *_pv(ori, cf, "ori"), *_pv(normal, cf, "normal"),
+                  *_pv(g, cf, "g"), m.data_ptr(), v.data_ptr(), B, N, int(k), _ptr(knn_d), _ptr(knn_idx), _ptr(nn_idx),
+                  float(lr), float(betas[0]), float(betas[1]), float(eps), float(budget),
+                  KNN_CLIP_MODES[clip_mode] if isinstance(clip_mode, str) else int(clip_mode), float(alpha),
+                  float(np.float32(c_chamfer)), float(np.float32(c_knn)), step_dev, step_host, _stream())
+    return adv
+
+
+def knn_attack_scales(N, k, B, up_chamfer, up_knn):
+    """(c_chamfer, c_knn) of ops.knn_attack_update for a loss that contains `up_chamfer * mean_b ChamferDist_b + up_knn *
+    mean_b KNNDist_b` over a batch of B clouds of N points, in the float32 steps the autograd path takes: scaled_gvec's
+    up / B, then the Chamfer backward's (1 / N) and the outlier kernel's 1 / (N k). up_knn None or k == 0: no kNN term."""
+    c_ch = np.float32(1.0 / N) * (np.float32(up_chamfer) / np.float32(B))
+    if up_knn is None or k == 0:
+        return c_ch, np.float32(0.0)
+    wv = np.float32(1.0) / (np.float32(N) * np.float32(k))
+    return c_ch, (np.float32(up_knn) / np.float32(B)) * wv
+
+
 # ------------------------------------------------------------------------------------------------------
 # CW-family loop: independent pieces carried by launches that exist anyway (csrc/linear_riders.hip, pointmlp.hip)
 # ------------------------------------------------------------------------------------------------------

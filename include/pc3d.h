@@ -1014,6 +1014,35 @@ int pc3d_cw_update_f32(float* adv, int64_t a_bs, int64_t a_ps, int64_t a_cs,
                        const int32_t* step_dev, int step_host, int dist_kind, const float* w,
                        const int32_t* nn_idx, void* stream);
 
+/* The kNN attack's update (attack/KNN/KNN_attack.py:117-136) as ONE launch, one workgroup per sample: the gradient of
+ * ChamferkNNDist('adv2ori') from the two search results, Adam and the clip, on the iterate adv (updated IN PLACE; m / v
+ * share its strides). It stands for pc3d_knn_outlier_loss_f32 + pc3d_knn_self_bwd_f32 + the Chamfer backward +
+ * pc3d_adam_clip_step_f32.
+ *   knn_d / knn_idx [B,N,k+1]: the sorted self-kNN of adv, the point itself first (pc3d_knn_hint_f32 with adv as both sets);
+ *   nn_idx [B,N]: arg-min over ori of every adv point (pc3d_nn_f32). Indices outside [0,N) are clamped.
+ * Per sample: value_i = mean_{j>=1} knn_d[i,j]; thr = mean_i value + alpha * std_i value (unbiased), the arithmetic and
+ * summation order of pc3d_knn_outlier_loss_f32; mask_i = value_i > thr, a constant of the graph (dist_utils.py:145-151).
+ *   g_knn[i] = mask_i sum_{e>=1} 2 c_knn (x_i - x_idx[i,e])  +  sum_{(i',e): mask_i', idx[i',e] = i} 2 c_knn (x_i - x_i')
+ * where the second sum runs over i' ascending, then e ascending (no float atomics: the bits depend on neither the batch
+ * nor the launch); g_chamfer[i] = 2 c_chamfer (x_i - ori[nn_idx[i]]); Adam (torch's, weight_decay 0, bias corrections
+ * from *step_dev or step_host >= 1, as pc3d_adam_clip_step_f32) on g + (g_chamfer + g_knn); then clip_mode 0:
+ * ClipPointsLinf(budget) (budget <= 0: none), clip_mode 1: ProjectInnerPoints with `normal` first (clip_utils.py:74-107;
+ * normal NULL: ori doubles as the normal, SURVEY A-11).
+ * c_chamfer / c_knn: d loss / d (mean_i |x_i - ori_nn(i)|^2) / N and d loss / d (KNNDist term) / (N k) of the sample, fp32
+ * constants prepared by the host (functor weights, the reference's `* K`, the batch mean, the shard ratio).
+ * c_knn == 0 or k == 0: no kNN term (plain ChamferDist; knn_d / knn_idx may be NULL); c_chamfer == 0: nn_idx may be NULL.
+ * N <= PC3D_KNN_ATTACK_UPDATE_MAX_POINTS: a sample's cloud, accumulators, values and masked list live in LDS, 32 bytes a
+ * point + 8 KiB of staged edges (136 KiB of the CU's 160 at the cap); 0 <= k <= 63, k + 1 <= N. */
+#define PC3D_KNN_ATTACK_UPDATE_MAX_POINTS 4096
+int pc3d_knn_attack_update_f32(float* adv, int64_t a_bs, int64_t a_ps, int64_t a_cs,
+                               const float* ori, int64_t o_bs, int64_t o_ps, int64_t o_cs,
+                               const float* normal, int64_t n_bs, int64_t n_ps, int64_t n_cs,
+                               const float* g, int64_t g_bs, int64_t g_ps, int64_t g_cs, float* m, float* v,
+                               int B, int N, int k, const float* knn_d, const int32_t* knn_idx,
+                               const int32_t* nn_idx, double lr, double beta1, double beta2, double eps,
+                               float budget, int clip_mode, float alpha, float c_chamfer, float c_knn,
+                               const int32_t* step_dev, int step_host, void* stream);
+
 /* The point-adding attacks' iteration (attack/Gen3DAdv CWAdd / CWAddClusters) as ONE launch, one workgroup per sample:
  * the set distance adv -> ori from the search output (nn_d / nn_idx [B,A], pc3d_nn_f32), bookkeeping on it, total
  * gradient (g, the victim's gradient on the A added columns, + w[b] * d distance / d adv) and Adam without clip, written
