@@ -9,6 +9,9 @@ DESIGN.md / SURVEY App. A:
     and curvature terms (the reference repeats it four times, each through a [B,N,N] matrix);
   * neighbour searches return true squared distances (A-2); the per-sample label drives the scale-constant update
     (A-7); transfer models get [B,3,N] (A-6) and may be None; debug .xyz dumps (is_debug) are not written.
+
+``cfg.device_loop = True`` (PointNet victims, see ``_device_loop_plan``): the iteration is the victim's launch-minimal passes
+around the loss launch, the searches and ONE update launch (pc3d_geoa3_update_f32), replayed from a hipGraph without autograd.
 """
 import numpy as np
 import torch
@@ -227,10 +230,203 @@ def _forward_step(net, pc_ori, input_curr_iter, normal_ori, ori_kappa, target, s
     return output_curr_iter, normal_curr_iter, loss, loss_n, cls_loss, dis_loss, hd_loss, curv_loss, constrain_loss, info
 
 
+# ---- device loop (cfg.device_loop = True, PointNet victims): no autograd, every buffer updated IN PLACE, replayed from hipGraphs ----
+LOOP_BLOCK = 16          # iterations per graph replay; the remainder replays single-iteration graphs
+LOOP_CACHE_MAX = 4       # loop states (buffers + graphs) kept on a victim (victim._geoa3_loop_cache), oldest dropped first
+
+
+def _device_loop_plan(net, cfg, b, n, targeted):
+    """The constants of the device loop when it applies, else None (the caller then takes the autograd path): a GPU
+    PointNetCls in eval mode, the CE / Margin classification loss, Chamfer (either side setting) or L2 without Hausdorff,
+    no uniform term, Adam, no partial variable / jitter / gradient projection / sub-sampling, and a cloud and neighbour
+    count pc3d_geoa3_update_f32 holds."""
+    from ...model import pointnet as _pointnet
+    victim = getattr(net, "model", net) if isinstance(net, _graphed.GraphedVictim) else net
+    if not isinstance(victim, _pointnet.PointNetCls) or victim.training:
+        return None
+    if next(victim.parameters()).device.type != "cuda":
+        return None
+    if cfg.cls_loss_type == 'CE':
+        kind = 2 if targeted else 3
+    elif cfg.cls_loss_type == 'Margin':
+        kind = 1 if targeted else 0
+    else:
+        return None
+    if cfg.dis_loss_type == 'CD':
+        two = not cfg.is_cd_single_side
+    elif cfg.dis_loss_type == 'L2' and cfg.hd_loss_weight == 0:
+        two = False
+    else:
+        return None
+    if cfg.uniform_loss_weight != 0 or cfg.optim != 'adam':
+        return None
+    if cfg.is_partial_var or cfg.is_pre_jitter_input or cfg.is_pro_grad:
+        return None
+    if n > cfg.npoint and cfg.is_subsample_opt:
+        return None
+    curv = cfg.curv_loss_weight != 0
+    k = int(cfg.curv_loss_knn) if curv else 0
+    if curv and not (1 <= k and k + 1 <= min(64, n)):
+        return None
+    if not ops.geoa3_update_fits(n, k, curv, two):
+        return None
+    gb = getattr(cfg, "global_batch", None)
+    return dict(victim=victim, kind=kind, kappa=float(cfg.confidence), dis_kind=cfg.dis_loss_type, two=two, curv=curv, k=k,
+                gval=float(np.float32(1.0) / np.float32(gb if gb else b)), w_dis=float(cfg.dis_loss_weight),
+                w_hd=float(cfg.hd_loss_weight), w_curv=float(cfg.curv_loss_weight), targeted=bool(targeted),
+                lr=float(cfg.lr), scheduler=bool(cfg.is_use_lr_scheduler), cc_linf=float(cfg.cc_linf),
+                steps=int(cfg.iter_max_steps), graph=getattr(cfg, "graph_victim", None) is not False)
+
+
+def _device_loop_state(plan, b, n, dev):
+    """Buffers (static: the graphs point at them), the iteration body and the captured graphs of one (plan, shape, weights)
+    key, kept on the victim and reused by later search steps and later calls."""
+    from ...model import pointnet as _pointnet
+    victim = plan["victim"]
+    wkey = tuple((t.data_ptr(), t._version) for t in list(victim.parameters()) + list(victim.buffers()))
+    key = (b, n, str(dev), bool(ops._det()), wkey, tuple(sorted((nm, v) for nm, v in plan.items() if nm != "victim")))
+    cache = victim.__dict__.setdefault("_geoa3_loop_cache", {})
+    s = cache.get(key)
+    if s is not None:
+        return s
+    f32 = dict(dtype=torch.float32, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    i64 = dict(dtype=torch.int64, device=dev)
+    s = dict(key=key, graphs=None)
+    for nm in ("x", "ori", "offset", "m", "v", "best_attack", "normal"):
+        s[nm] = torch.zeros((b, 3, n), **f32)
+    for nm in ("scale", "constrain", "best_loss", "iter_best_loss"):
+        s[nm] = torch.zeros((b,), **f32)
+    for nm in ("pred", "target", "best_bs", "best_step", "iter_best_score"):
+        s[nm] = torch.zeros((b,), **i64)
+    s["kappa_ori"] = torch.zeros((b, n), **f32)
+    s["step"], s["search"] = torch.zeros((b,), **i32), torch.zeros((1,), **i32)
+    s["lr"] = torch.zeros((b,), dtype=torch.float64, device=dev)
+    s["loss_rows"] = torch.zeros((plan["steps"], b), **f32)
+    need_ao = plan["dis_kind"] == 'CD' or plan["curv"]
+    k = plan["k"]
+    s["ao_d"], s["ao_i"] = (torch.zeros((b, n), **f32), torch.zeros((b, n), **i32)) if need_ao else (None, None)
+    s["oa_d"], s["oa_i"] = (torch.zeros((b, n), **f32), torch.zeros((b, n), **i32)) if plan["two"] else (None, None)
+    s["knn_d"], s["knn_i"] = ((torch.zeros((b, n, k + 1), **f32), torch.zeros((b, n, k + 1), **i32))     # knn_i: also the search's hint
+                              if plan["curv"] else (None, None))
+
+    def body():
+        # one chain on one stream: the victim's passes around the loss launch, the searches, the update
+        with torch.no_grad():
+            logits, ctx = _pointnet.fused_forward(victim, s["x"])
+            _, _, cls, g_logits = ops.cls_loss(logits, s["target"], plan["kind"], plan["kappa"], scale=plan["gval"],
+                                               pred_out=s["pred"])
+            gx = _pointnet.fused_input_grad(ctx, g_logits)
+            if need_ao:
+                ops.nn_search_into(s["x"], s["ori"], s["ao_d"], s["ao_i"])
+            if plan["two"]:
+                ops.nn_search_into(s["ori"], s["x"], s["oa_d"], s["oa_i"])
+            if plan["curv"]:
+                ops.knn_search_into(s["x"], s["knn_d"], s["knn_i"])
+            ops.geoa3_update(s["x"], s["ori"], s["offset"], gx, s["m"], s["v"], s["step"], s["search"], s["lr"], s["scale"],
+                             cls, s["pred"], s["target"], plan["targeted"], s["constrain"], s["loss_rows"], s["best_loss"],
+                             s["best_attack"], s["best_bs"], s["best_step"], s["iter_best_loss"], s["iter_best_score"],
+                             nn_ao=s["ao_i"], nn_oa=s["oa_i"], knn_idx=s["knn_i"],
+                             normal_ori=s["normal"] if plan["curv"] else None,
+                             kappa_ori=s["kappa_ori"] if plan["curv"] else None, dis_kind=plan["dis_kind"],
+                             gval=plan["gval"], w_dis=plan["w_dis"], w_hd=plan["w_hd"], w_curv=plan["w_curv"],
+                             scheduler=plan["scheduler"], cc_linf=plan["cc_linf"])
+
+    def rewind(offset0, scale_const, search_step):
+        """The state of a search step's first iteration, in place."""
+        s["offset"].copy_(offset0)
+        torch.add(s["ori"], s["offset"], out=s["x"])
+        s["m"].zero_(), s["v"].zero_(), s["step"].zero_()
+        s["lr"].fill_(plan["lr"]), s["constrain"].fill_(1e10)
+        s["iter_best_loss"].fill_(1e10), s["iter_best_score"].fill_(-1)
+        s["scale"].copy_(scale_const.float()), s["search"].fill_(int(search_step))
+
+    s["body"], s["rewind"] = body, rewind
+    while len(cache) >= LOOP_CACHE_MAX:
+        cache.pop(next(iter(cache)))
+    cache[key] = s
+    return s
+
+
+def _run_device_loop(plan, pc_ori, normal_ori, kappa_ori, target, gt_target, cfg, gens):
+    """The binary search (:271-404) around the captured iteration. Returns (best_attack, best_loss, best_attack_step,
+    loss rows [iter_max_steps,B] of the last search step)."""
+    b, _, n = pc_ori.shape
+    dev = pc_ori.device
+    targeted = plan["targeted"]
+    s = _device_loop_state(plan, b, n, dev)
+    lower_bound = torch.zeros(b)
+    scale_const = torch.ones(b) * cfg.initial_const
+    upper_bound = torch.ones(b) * 1e10
+    loss_rows = None
+    with torch.no_grad():
+        s["ori"].copy_(pc_ori)
+        s["target"].copy_(target if targeted else gt_target)
+        if plan["curv"]:
+            s["normal"].copy_(normal_ori), s["kappa_ori"].copy_(kappa_ori)
+        s["best_loss"].fill_(1e10), s["best_attack"].fill_(1.0), s["best_step"].fill_(-1), s["best_bs"].fill_(-1)
+        s["pred"].zero_()
+        if plan["graph"] and s["graphs"] is None and plan["steps"] > 0 and cfg.binary_max_steps > 0:
+            # capture once (after eager warm-up passes on a side stream, as torch requires) from the unperturbed cloud — no
+            # draw from any generator — then put back what the warm-up passes wrote
+            s["rewind"](torch.zeros_like(s["offset"]), scale_const, 0)
+            s["graphs"] = _graphed.LoopGraph(s["body"], dev, 2, counts=(1, LOOP_BLOCK), owners=(plan["victim"],))
+            s["best_loss"].fill_(1e10), s["best_attack"].fill_(1.0), s["best_step"].fill_(-1), s["best_bs"].fill_(-1)
+        for search_step in range(cfg.binary_max_steps):
+            s["rewind"](_draw_offset(b, 3, n, dev, cfg, gens), scale_const, search_step)
+            if plan["graph"]:
+                for _ in range(plan["steps"] // LOOP_BLOCK):
+                    s["graphs"].replay(LOOP_BLOCK)
+                for _ in range(plan["steps"] % LOOP_BLOCK):
+                    s["graphs"].replay(1)
+            else:
+                for _ in range(plan["steps"]):
+                    s["body"]()
+            # one read-back per search step: the loss rows, the last prediction and the step's best label (:393-404)
+            loss_rows = s["loss_rows"].cpu()
+            succ_now = _compare(s["pred"], target, gt_target, targeted).cpu()
+            ibs = s["iter_best_score"].cpu()
+            for k in range(b):
+                if bool(succ_now[k]) and int(ibs[k]) != -1:
+                    lower_bound[k] = max(lower_bound[k], scale_const[k])
+                    if upper_bound[k] < 1e9:
+                        scale_const[k] = (lower_bound[k] + upper_bound[k]) * 0.5
+                    else:
+                        scale_const[k] *= 2
+                else:
+                    upper_bound[k] = min(upper_bound[k], scale_const[k])
+                    if upper_bound[k] < 1e9:
+                        scale_const[k] = (lower_bound[k] + upper_bound[k]) * 0.5
+        return s["best_attack"].clone(), s["best_loss"].clone(), s["best_step"].clone(), loss_rows
+
+
+def _finish(transfer, best_attack, target, targeted, best_loss, best_attack_step, loss_rows):
+    """Transfer attack evaluation (:406-471), batched; counters exposed as a function attribute. loss_rows: a list of [B]
+    device tensors or one [steps,B] tensor."""
+    fails = []
+    with torch.no_grad():
+        for m in transfer:
+            if m is None:
+                fails.append(None)
+                continue
+            lab = torch.argmax(_logits_of(m(best_attack.float())), dim=1)
+            fails.append(int(((lab == target) if not targeted else (lab != target)).sum().item()))
+    geoA3_attack.last_transfer_fails = dict(zip(("pt", "ptm", "pts", "dgcnn", "cur"), fails))
+
+    if isinstance(loss_rows, torch.Tensor):
+        all_loss_list = loss_rows.cpu().tolist()
+    else:
+        all_loss_list = torch.stack(loss_rows).cpu().tolist() if loss_rows else []
+    return (best_attack, target, (best_loss.cpu().numpy() < 1e10), best_attack_step.cpu().tolist(), all_loss_list)
+
+
 def geoA3_attack(net, pt_model, ptm_model, pts_model, dgcnn_model, cur_model, pc, label, cfg, i, loader_len,
                  saved_dir=None):
     """cfg.deterministic (optional; None = the process-wide ops.DETERMINISTIC, default on): ordered backward sums, i.e.
-    bit-reproducible runs, for the duration of the call."""
+    bit-reproducible runs, for the duration of the call.
+    cfg.device_loop = True (optional): on a PointNet victim and a configuration _device_loop_plan admits, the iteration runs
+    as a captured chain of own kernels without autograd (pc3d_geoa3_update_f32); anything else silently takes the usual
+    path. geoA3_attack.last_path says which one the last call took: "device_loop" or "autograd"."""
     det = getattr(cfg, "deterministic", None)
     if det is None:
         return _geoA3_attack(net, pt_model, ptm_model, pts_model, dgcnn_model, cur_model, pc, label, cfg, i, loader_len, saved_dir)
@@ -267,6 +463,13 @@ def _geoA3_attack(net, pt_model, ptm_model, pts_model, dgcnn_model, cur_model, p
     seeds = getattr(cfg, "sample_seeds", None)
     gens = [torch.Generator().manual_seed(int(sd)) for sd in seeds] if seeds is not None else None
     assert gens is None or len(gens) == b, "cfg.sample_seeds needs one seed per sample"
+
+    plan = _device_loop_plan(net, cfg, b, n, targeted) if getattr(cfg, "device_loop", False) and pc_ori.is_cuda else None
+    geoA3_attack.last_path = "device_loop" if plan is not None else "autograd"
+    if plan is not None:
+        best_attack, best_loss, best_attack_step, loss_rows = _run_device_loop(plan, pc_ori, normal_ori, kappa_ori, target,
+                                                                               gt_target, cfg, gens)
+        return _finish(transfer, best_attack, target, targeted, best_loss, best_attack_step, loss_rows)
 
     lower_bound = torch.zeros(b)
     scale_const = torch.ones(b) * cfg.initial_const
@@ -438,16 +641,4 @@ def _geoA3_attack(net, pt_model, ptm_model, pts_model, dgcnn_model, cur_model, p
                 if upper_bound[k] < 1e9:
                     scale_const[k] = (lower_bound[k] + upper_bound[k]) * 0.5
 
-    # transfer attack evaluation (:406-471), batched; counters exposed as a function attribute
-    fails = []
-    with torch.no_grad():
-        for m in transfer:
-            if m is None:
-                fails.append(None)
-                continue
-            lab = torch.argmax(_logits_of(m(best_attack.float())), dim=1)
-            fails.append(int(((lab == target) if not targeted else (lab != target)).sum().item()))
-    geoA3_attack.last_transfer_fails = dict(zip(("pt", "ptm", "pts", "dgcnn", "cur"), fails))
-
-    all_loss_list = torch.stack(loss_curves).cpu().tolist() if loss_curves else []
-    return (best_attack, target, (best_loss.cpu().numpy() < 1e10), best_attack_step.cpu().tolist(), all_loss_list)
+    return _finish(transfer, best_attack, target, targeted, best_loss, best_attack_step, loss_curves)

@@ -1561,6 +1561,85 @@ def geoa3_terms(d_ao, d_oa, k_adv, k_ori, idx_ao, cls, scale, w_dis, w_hd, w_cur
     return _GeoTermsFn.apply(d_ao, d_oa, k_adv, k_ori, idx_ao, cls, scale, (float(w_dis), float(w_hd), float(w_curv)), gfix)
 
 
+GEOA3_LOOP_MAX_POINTS = 2048    # pc3d_geoa3_update_f32 keeps a cloud and the reverse index of its N k curvature edges in LDS (include/pc3d.h)
+GEOA3_DIS_KINDS = {"CD": 0, "L2": 1}
+
+
+def geoa3_update_lds_bytes(N, k, curv=True, two_sided=True):
+    """LDS bytes pc3d_geoa3_update_f32 asks for (csrc/geoa3_loop.hip: 38 N + 2 N k + 512 with every term on)."""
+    np_ = (int(N) + 3) & ~3
+    s = np_ * 12 + 512
+    if curv:
+        s += np_ * 20 + ((int(N) * int(k) * 2 + 15) & ~15)
+    if two_sided:
+        s += np_ * 4 + ((np_ * 2 + 15) & ~15)
+    return s
+
+
+def geoa3_update_fits(N, k, curv=True, two_sided=True):
+    return N <= GEOA3_LOOP_MAX_POINTS and geoa3_update_lds_bytes(N, k, curv, two_sided) <= 160 * 1024
+
+
+def geoa3_update(x, ori, offset, g, m, v, step, search_step, lr, scale, cls, pred, target, targeted, constrain, loss_rows,
+                 best_loss, best_attack, best_bs, best_step, iter_best_loss, iter_best_score, nn_ao=None, nn_oa=None,
+                 knn_idx=None, normal_ori=None, kappa_ori=None, dis_kind="CD", gval=1.0, w_dis=1.0, w_hd=0.0, w_curv=0.0,
+                 scheduler=False, cc_linf=0.0, betas=(0.9, 0.999), eps=1e-8, terms_out=None, hd_arg_out=None, g_out=None):
+    """One GeoA3 iteration after the victim's passes and the searches, one launch, everything IN PLACE (see
+    pc3d_geoa3_update_f32): record, terms, the gradient of gval * scale * constrain added to g, Adam on `offset`, the
+    scheduler, lp_clip and x = ori + offset. Point tensors are contiguous float32 [B,3,N]; step (int32) and lr (float64) are
+    PER-CLOUD words [B], search_step an int32 [1] word; nn_ao / nn_oa int32 [B,N], knn_idx int32 [B,N,k+1]. nn_oa None:
+    single-sided Chamfer; knn_idx None or w_curv == 0: no curvature term; dis_kind "L2" needs no search."""
+    _check(x, "x")
+    if x.dim() != 3 or x.shape[1] != 3:
+        raise ValueError(f"geoa3_update: x must be [B,3,N], got {tuple(x.shape)}")
+    B, _, N = x.shape
+    dev = x.device
+
+    def need(nm, t, dt, shape, optional=False):
+        if t is None:
+            if optional:
+                return
+            raise ValueError(f"geoa3_update: {nm} is required")
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != tuple(shape) or not t.is_contiguous() \
+                or t.device != dev:
+            raise ValueError(f"geoa3_update: {nm} must be a contiguous {dt} tensor of shape {list(shape)} on x's device")
+
+    f32, i32, i64 = torch.float32, torch.int32, torch.int64
+    for nm, t in (("x", x), ("ori", ori), ("offset", offset), ("g", g), ("m", m), ("v", v), ("best_attack", best_attack)):
+        need(nm, t, f32, (B, 3, N))
+    for nm, t in (("scale", scale), ("cls", cls), ("constrain", constrain), ("best_loss", best_loss),
+                  ("iter_best_loss", iter_best_loss)):
+        need(nm, t, f32, (B,))
+    for nm, t in (("pred", pred), ("target", target), ("best_bs", best_bs), ("best_step", best_step),
+                  ("iter_best_score", iter_best_score)):
+        need(nm, t, i64, (B,))
+    need("step", step, i32, (B,)), need("search_step", search_step, i32, (1,)), need("lr", lr, torch.float64, (B,))
+    if loss_rows.dim() != 2:
+        raise ValueError("geoa3_update: loss_rows must be [max_steps,B]")
+    need("loss_rows", loss_rows, f32, (loss_rows.shape[0], B))
+    need("nn_ao", nn_ao, i32, (B, N), optional=True), need("nn_oa", nn_oa, i32, (B, N), optional=True)
+    k = 0
+    if knn_idx is not None:
+        if knn_idx.dim() != 3:
+            raise ValueError("geoa3_update: knn_idx must be [B,N,k+1]")
+        k = knn_idx.shape[2] - 1
+        need("knn_idx", knn_idx, i32, (B, N, k + 1))
+    need("normal_ori", normal_ori, f32, (B, 3, N), optional=True), need("kappa_ori", kappa_ori, f32, (B, N), optional=True)
+    need("terms_out", terms_out, f32, (5, B), optional=True), need("hd_arg_out", hd_arg_out, i32, (B,), optional=True)
+    need("g_out", g_out, f32, (B, 3, N), optional=True)
+    with torch.cuda.device(dev):
+        _lib.call("pc3d_geoa3_update_f32", x.data_ptr(), ori.data_ptr(), offset.data_ptr(), g.data_ptr(), m.data_ptr(),
+                  v.data_ptr(), B, N, int(k), _ptr(nn_ao), _ptr(nn_oa), _ptr(knn_idx), _ptr(normal_ori), _ptr(kappa_ori),
+                  cls.data_ptr(), scale.data_ptr(), pred.data_ptr(), target.data_ptr(), 1 if targeted else 0,
+                  GEOA3_DIS_KINDS[dis_kind] if isinstance(dis_kind, str) else int(dis_kind), float(np.float32(gval)),
+                  float(w_dis), float(w_hd), float(w_curv), constrain.data_ptr(), loss_rows.data_ptr(),
+                  int(loss_rows.shape[0]), step.data_ptr(), search_step.data_ptr(), lr.data_ptr(), 1 if scheduler else 0,
+                  best_loss.data_ptr(), best_attack.data_ptr(), best_bs.data_ptr(), best_step.data_ptr(),
+                  iter_best_loss.data_ptr(), iter_best_score.data_ptr(), float(betas[0]), float(betas[1]), float(eps),
+                  float(cc_linf), _ptr(terms_out), _ptr(hd_arg_out), _ptr(g_out), _stream())
+    return x
+
+
 # ------------------------------------------------------------------------------------------------------
 # K8b: point-wise dense layers (frozen weights) on the fp32-MFMA GEMM
 # ------------------------------------------------------------------------------------------------------

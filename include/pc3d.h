@@ -1043,6 +1043,38 @@ int pc3d_knn_attack_update_f32(float* adv, int64_t a_bs, int64_t a_ps, int64_t a
                                float budget, int clip_mode, float alpha, float c_chamfer, float c_knn,
                                const int32_t* step_dev, int step_host, void* stream);
 
+/* GeoA3's iteration after the victim's passes and the searches (attack/GeoA3/GeoA3_attack.py:139-181, :321-351, lp_clip
+ * :92-102) as ONE launch, one workgroup per cloud; every point tensor is a contiguous [B,3,N]. In this order:
+ *   record   pc3d_geoa3_record_f32's decisions on pred[b] (the loss launch's prediction), target[b], constrain[b] as it
+ *            ARRIVES (the previous iteration's value; the caller puts 1e10 there before step 0) and the iterate x as it
+ *            stands; the step and search step written to best_step / best_bs are step[b] and *search_step;
+ *   terms    on the arg-mins nn_ao [B,N] (adv -> ori), nn_oa [B,N] (ori -> adv; NULL: single-sided Chamfer) and the self-kNN
+ *            lists knn_idx [B,N,k+1] (self first; NULL, k == 0 or w_curv == 0: no curvature term), squared distances
+ *            recomputed in the direct form: dis = mean_i d_ao (+ mean_j d_oa), or with dis_kind 1 the L2 sum over the
+ *            points (nn_ao then only serves the curvature term and may be NULL without one; w_hd must be 0);
+ *            hd = max_i d_ao, first index on ties; curv = mean_i (kappa_i - kappa_ori[nn_ao[i]])^2 with pc3d_kappa_f32's
+ *            arithmetic on the normals normal_ori[:, nn_ao[i]]; constrain = (w_dis dis + w_hd hd) + w_curv curv goes back
+ *            into constrain[b], loss_n = cls[b] + scale[b] constrain into loss_rows[step[b], b] (skipped past max_steps);
+ *   gradient of gval scale[b] constrain w.r.t. x, added to g (the victim's gradient, already scaled); every sum into a
+ *            point runs in a fixed order (own side in list order, then the incoming terms ascending by source): the bits
+ *            depend on neither the batch nor the launch; no float atomics;
+ *   update   Adam (pc3d_adam_clip_step_f32's arithmetic, bias corrections from step[b] + 1, lr[b]) on offset; step[b] += 1;
+ *            scheduler != 0: lr[b] *= 0.9990; cc_linf != 0: lp_clip; x = ori + offset.
+ * terms_out [5,B] (dis, hd, curv, constrain, loss_n), hd_arg_out [B] and g_out [B,3,N] (the total gradient) may be NULL.
+ * Indices outside [0,N) are clamped. N <= PC3D_GEOA3_UPDATE_MAX_POINTS and 38 N + 2 N k + 512 bytes of LDS <= 160 KiB:
+ * the cloud, the gathered normals and a reverse index of the N k curvature edges live in LDS (140.5 KiB at N = 2048,
+ * k = 16). */
+#define PC3D_GEOA3_UPDATE_MAX_POINTS 2048
+int pc3d_geoa3_update_f32(float* x, const float* ori, float* offset, const float* g, float* m, float* v, int B, int N,
+                          int k, const int32_t* nn_ao, const int32_t* nn_oa, const int32_t* knn_idx,
+                          const float* normal_ori, const float* kappa_ori, const float* cls, const float* scale,
+                          const int64_t* pred, const int64_t* target, int targeted, int dis_kind, float gval, float w_dis,
+                          float w_hd, float w_curv, float* constrain, float* loss_rows, int max_steps, int32_t* step,
+                          const int32_t* search_step, double* lr, int scheduler, float* best_loss, float* best_attack,
+                          int64_t* best_bs, int64_t* best_step, float* iter_best_loss, int64_t* iter_best_score,
+                          double beta1, double beta2, double eps, float cc_linf, float* terms_out, int32_t* hd_arg_out,
+                          float* g_out, void* stream);
+
 /* The point-adding attacks' iteration (attack/Gen3DAdv CWAdd / CWAddClusters) as ONE launch, one workgroup per sample:
  * the set distance adv -> ori from the search output (nn_d / nn_idx [B,A], pc3d_nn_f32), bookkeeping on it, total
  * gradient (g, the victim's gradient on the A added columns, + w[b] * d distance / d adv) and Adam without clip, written
