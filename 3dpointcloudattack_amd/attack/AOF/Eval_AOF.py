@@ -290,11 +290,8 @@ class AOF:
             if not self.graph:
                 for _ in range(self.epochs):
                     iterate()
-            else:
-                for _ in range(self.epochs // GRAPH_BLOCK):
-                    fl["graphs"].replay(GRAPH_BLOCK)
-                for _ in range(self.epochs % GRAPH_BLOCK):
-                    fl["graphs"].replay(1)
+            elif self.epochs > 0:
+                fl["graphs"].run(self.epochs)
         return (fl["data"] if self.step > 0 else ori_data), fl["st"]
 
 

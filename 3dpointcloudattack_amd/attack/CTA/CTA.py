@@ -283,7 +283,7 @@ def _loop_for(network, G, S, N, k, P, W, dev, mode, targeted, optimizer, fused, 
         c = _Loop(network, G, S, N, k, P, W, dev, mode, targeted, optimizer, fused)
         loader(c)
         return c
-    wkey = tuple((t.data_ptr(), t._version) for t in list(network.parameters()) + list(network.buffers()))
+    wkey = _graphed.weights_key(network)
     key = (id(network), G, S, N, k, P, W, dev, mode, targeted, optimizer, bool(ops._det()), wkey)
     c = _LOOPS.get(key)
     if c is None:

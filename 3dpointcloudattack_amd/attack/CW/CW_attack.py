@@ -58,10 +58,8 @@ class _GraphRunner:
             self.flush()
 
     def flush(self):
-        for n in self.sizes:
-            while self.pending >= n:
-                self.graphs[n].replay()
-                self.pending -= n
+        self.loop.run(self.pending)
+        self.pending = 0
 
 
 class CW:
@@ -451,7 +449,7 @@ class CW:
             return run
         if st["graph"] is not None:
             return st["graph_run"]
-        victim = self.model.model if isinstance(self.model, _graphed.GraphedVictim) else self.model
+        victim = _graphed.unwrap(self.model)
         # warm-up passes are real iterations; account for them by NOT rolling anything back: callers start counting
         # after _make_runner (bench) or use _begin_binary_step to reset the state (attack()).
         loop = _graphed.LoopGraph(lambda: self._iterate(st), self.device, warmup,

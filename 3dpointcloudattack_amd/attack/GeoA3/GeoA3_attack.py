@@ -241,7 +241,7 @@ def _device_loop_plan(net, cfg, b, n, targeted):
     no uniform term, Adam, no partial variable / jitter / gradient projection / sub-sampling, and a cloud and neighbour
     count pc3d_geoa3_update_f32 holds."""
     from ...model import pointnet as _pointnet
-    victim = getattr(net, "model", net) if isinstance(net, _graphed.GraphedVictim) else net
+    victim = _graphed.unwrap(net)
     if not isinstance(victim, _pointnet.PointNetCls) or victim.training:
         return None
     if next(victim.parameters()).device.type != "cuda":
@@ -283,7 +283,7 @@ def _device_loop_state(plan, b, n, dev):
     key, kept on the victim and reused by later search steps and later calls."""
     from ...model import pointnet as _pointnet
     victim = plan["victim"]
-    wkey = tuple((t.data_ptr(), t._version) for t in list(victim.parameters()) + list(victim.buffers()))
+    wkey = _graphed.weights_key(victim)
     key = (b, n, str(dev), bool(ops._det()), wkey, tuple(sorted((nm, v) for nm, v in plan.items() if nm != "victim")))
     cache = victim.__dict__.setdefault("_geoa3_loop_cache", {})
     s = cache.get(key)
@@ -374,11 +374,8 @@ def _run_device_loop(plan, pc_ori, normal_ori, kappa_ori, target, gt_target, cfg
             s["best_loss"].fill_(1e10), s["best_attack"].fill_(1.0), s["best_step"].fill_(-1), s["best_bs"].fill_(-1)
         for search_step in range(cfg.binary_max_steps):
             s["rewind"](_draw_offset(b, 3, n, dev, cfg, gens), scale_const, search_step)
-            if plan["graph"]:
-                for _ in range(plan["steps"] // LOOP_BLOCK):
-                    s["graphs"].replay(LOOP_BLOCK)
-                for _ in range(plan["steps"] % LOOP_BLOCK):
-                    s["graphs"].replay(1)
+            if plan["graph"] and plan["steps"] > 0:
+                s["graphs"].run(plan["steps"])
             else:
                 for _ in range(plan["steps"]):
                     s["body"]()

@@ -195,7 +195,7 @@ def _ctri_loop(victim, x, label, W, active, target, kappa, step_size, fused=True
     fast = bool(fused and hasattr(victim, "fused_loss_and_grad"))
     kind = 0 if target != 0 else 3          # pc3d_cls_loss_f32: the CW margin (+ kappa), or minus the cross-entropy
     if fast and graph and cache is not None:
-        wkey = tuple((t.data_ptr(), t._version) for t in list(victim.parameters()) + list(victim.buffers()))
+        wkey = _graphed.weights_key(victim)
         key = (B, N, x.device, kind, float(kappa), float(step_size), wkey)
         c = cache.get(key)
         if c is None:

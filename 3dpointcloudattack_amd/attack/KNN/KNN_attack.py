@@ -122,7 +122,7 @@ class CWKNN:
         PointNetCls variants), an adversarial functor the CW loop maps to ops.LOSS_KINDS, ChamferkNNDist / ChamferDist
         with 'adv2ori', a clip functor _fused_clip() recognises, and a cloud the update kernel holds."""
         from ..CW.CW_attack import CW as _CW
-        victim = getattr(self.model, "model", self.model) if isinstance(self.model, _graphed.GraphedVictim) else self.model
+        victim = _graphed.unwrap(self.model)
         fc = self._fused_clip()
         if fc is None or self.device.type != "cuda" or not hasattr(victim, "fused_attack_grad") or K > ops.KNN_LOOP_MAX_POINTS:
             return None
@@ -154,7 +154,7 @@ class CWKNN:
         """Buffers (static: the graphs point at them), the iteration body and the captured graphs, rebuilt when the shape,
         a constant of the loop, the kernel flavour or the victim's weights change."""
         victim, dev = plan["victim"], self.device
-        wkey = tuple((t.data_ptr(), t._version) for t in list(victim.parameters()) + list(victim.buffers()))
+        wkey = _graphed.weights_key(victim)
         key = (B, K, float(self.attack_lr), bool(self.graph), bool(ops._det()), wkey,
                tuple(sorted((n, v) for n, v in plan.items() if n != "victim")))
         c = self._loop_cache
@@ -210,11 +210,8 @@ class CWKNN:
             if not self.graph:
                 for _ in range(self.num_iter):
                     c["body"]()
-            else:
-                for _ in range(self.num_iter // self.LOOP_BLOCK):
-                    c["graphs"].replay(self.LOOP_BLOCK)
-                for _ in range(self.num_iter % self.LOOP_BLOCK):
-                    c["graphs"].replay(1)
+            elif self.num_iter > 0:
+                c["graphs"].run(self.num_iter)
             adv_data.copy_(c["adv"])
 
     def attack(self, data, target):
@@ -303,7 +300,7 @@ class CWKNN:
         # A PointNet++ victim draws an FPS start per sampling layer and forward from the CPU generator (SURVEY A-4): the
         # loop's draws are made here, in the same order, and uploaded once (pointnet2_utils.PredrawnFpsStarts)
         from ...model import pointnet2_utils as _pn2
-        victim = getattr(self.model, "model", self.model)
+        victim = _graphed.unwrap(self.model)
         predrawn = None
         if adv_data.is_cuda and hasattr(victim, "sampling_input_sizes") and getattr(self, "predraw_starts", True):
             predrawn = _pn2.PredrawnFpsStarts(victim.sampling_input_sizes(K), B, self.num_iter, dev, inner=_pn2.fps_start_source())

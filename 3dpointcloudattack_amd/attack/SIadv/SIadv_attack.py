@@ -315,7 +315,7 @@ class PointCloudAttack(object):
         if not self.graph:
             c = _Loop(v, B, N, x.device, self.step_size, self.eps)
         else:
-            wkey = tuple((t.data_ptr(), t._version) for t in list(v.parameters()) + list(v.buffers()))
+            wkey = _graphed.weights_key(v)
             key = (B, N, x.device, float(self.step_size), float(self.eps), wkey)
             c = self._loops.get(key)
             if c is None:
@@ -461,7 +461,7 @@ class PointCloudAttack(object):
         if not (fast and self.graph):
             return _QueryLoop(self, B, N, L, k, dev, frame, table_eps, fast)
         v = self.classifier
-        wkey = tuple((t.data_ptr(), t._version) for t in list(v.parameters()) + list(v.buffers()))
+        wkey = _graphed.weights_key(v)
         key = (B, N, L, k, dev, frame, table_eps, bool(self.top5_attack), wkey)
         c = self._query_loops.get(key)
         if c is None:

@@ -13,7 +13,7 @@
 // Tie rules (they matter: resampled clusters contain duplicate points): Hausdorff routes its gradient to the FIRST
 // maximal i; the farthest pair is the first maximum of torch's reduction order, inner max over x (first x), then over
 // y (first y). Every reduction runs in a fixed order, so a run is bit-reproducible.
-#include "pc3d_common.h"
+#include "update_body.h"
 
 namespace pc3d {
 
@@ -177,33 +177,20 @@ __global__ __launch_bounds__(kAddThreads) void add_update_kernel(AddArgs a) {
         dist = fs + dist * a.cd_w;
       }
     }
-    if (a.dist_val) a.dist_val[b] = dist;
-    const int64_t pr = a.pred[b], lb = a.label[b];
-    const bool succ = a.untarget ? (pr != lb) : (pr == lb);
-    if (succ && dist < a.bestdist[b]) {
-      a.bestdist[b] = dist;
-      a.bestscore[b] = pr;
-    }
-    int copy = 0;
-    if (succ && dist < a.o_bestdist[b]) {
-      a.o_bestdist[b] = dist;
-      a.o_bestscore[b] = pr;
-      copy = 1;
-    }
-    s_copy = copy;
+    s_copy = cw_book_decide(a.dist_val, a.bestdist, a.bestscore, a.o_bestdist, a.o_bestscore, a.untarget, b, dist,
+                            a.pred[b], a.label[b], a.bestdist[b], a.o_bestdist[b]);
     const int t = a.step_dev ? a.step_dev[0] : a.step_host;
-    s_step_size = (float)(a.lr / (1.0 - pow(a.b1, (double)t)));
-    s_bc2s = (float)sqrt(1.0 - pow(a.b2, (double)t));
+    s_step_size = adam_step_size(a.lr, a.b1, t);
+    s_bc2s = adam_bc2s(a.b2, t);
   }
   __syncthreads();
-  // 4. total gradient + Adam (pc3d_adam_clip_step_f32's arithmetic, no clip), written back through adv's strides
+  // 4. total gradient + Adam (adam_element, what pc3d_adam_clip_step_f32 runs; no clip), written back through adv's strides
   const bool copy = s_copy != 0;
   const float wb = a.w[b];
   // d distance / d a_i of the nearest-neighbour term: 2 (a_i - o_nn(i)) times cc (Chamfer: 1/A of the mean)
   const float cc = (a.kind == 2) ? 2.f * wb : 2.f * (wb * (far ? a.cd_w : 1.f)) / (float)A;
   const int hidx = (a.kind == 2) ? s_hidx : -1;
-  const float omb1 = (float)(1.0 - a.b1), omb2 = (float)(1.0 - a.b2), fb2 = (float)a.b2;
-  const float step_size = s_step_size, bc2s = s_bc2s;
+  const AdamConsts ad = adam_consts_with(a.b1, a.b2, a.eps, s_step_size, s_bc2s);
 #pragma unroll
   for (int i = 0; i < PER; ++i) {
     const int k = tid + i * kAddThreads;
@@ -228,13 +215,9 @@ __global__ __launch_bounds__(kAddThreads) void add_update_kernel(AddArgs a) {
     float* pp = a.adv.p + (int64_t)b * a.adv.bs + (int64_t)k * a.adv.ps;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      float m = m_[i][c], v = v_[i][c];
-      m = m + (g[c] - m) * omb1;
-      v = v * fb2 + omb2 * g[c] * g[c];
-      a.m[cb + (int64_t)c * A + k] = m;
-      a.v[cb + (int64_t)c * A + k] = v;
-      const float denom = __builtin_sqrtf(v) / bc2s + a.eps;
-      pp[c * a.adv.cs] = pin[c] - step_size * (m / denom);
+      pp[c * a.adv.cs] = adam_element(ad, pin[c], g[c], m_[i][c], v_[i][c]);
+      a.m[cb + (int64_t)c * A + k] = m_[i][c];
+      a.v[cb + (int64_t)c * A + k] = v_[i][c];
     }
   }
 }

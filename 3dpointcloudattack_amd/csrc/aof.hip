@@ -3,11 +3,11 @@
 //   * aof_record_kernel: the bookkeeping of :168-185 on the iterate that was just evaluated — dist = max |adv - data| over
 //     the whole cloud, the three-way decision, the conditional copy into o_bestattack. One workgroup per cloud.
 //   * aof_update_kernel: :187-195 between the backward and the re-projection — g = g1 + g2, torch's Adam on lfc, adv =
-//     lfc + hfc, ClipPointsLinf against data. One thread per point; the statements are those of adam_clip_kernel and
-//     clip_kernel (elementwise.hip), so the launch gives the bits of pc3d_adam_clip_step_f32 + torch.add + pc3d_clip_f32.
+//     lfc + hfc, ClipPointsLinf against data. One thread per point; adam_element and clip_linf (update_body.h) are what
+//     adam_clip_kernel and clip_kernel call, so the launch gives the bits of pc3d_adam_clip_step_f32 + torch.add + pc3d_clip_f32.
 // Every tensor is a contiguous [B,3,N] block given by its own pointer: the loop keeps (lfc + hfc | lfc) and the two
 // gradient terms as the halves of [2B,3,N] buffers of the victim's stacked pass.
-#include "cw_update_body.h"
+#include "update_body.h"
 
 namespace pc3d {
 
@@ -93,9 +93,7 @@ __global__ __launch_bounds__(256) void aof_update_kernel(AofUpdateArgs a) {
   const int b = blockIdx.y;
   if (k >= a.N) return;
   const int t = a.step_dev ? a.step_dev[0] : a.step_host;
-  const float omb1 = (float)(1.0 - a.b1), omb2 = (float)(1.0 - a.b2), fb2 = (float)a.b2;
-  const float step_size = cw_adam_step_size(a.lr, a.b1, t);
-  const float bc2s = cw_adam_bc2s(a.b2, t);
+  const AdamConsts ad = adam_consts(a.lr, a.b1, a.b2, a.eps, t);
   const int64_t base = (int64_t)b * 3 * a.N + k;
   float np_[3], o[3];
 #pragma unroll
@@ -104,22 +102,15 @@ __global__ __launch_bounds__(256) void aof_update_kernel(AofUpdateArgs a) {
     float g = a.g1[i];
     g += a.g2[i];
     float m = a.m[i], v = a.v[i];
-    m = m + (g - m) * omb1;
-    v = v * fb2 + omb2 * g * g;
+    const float p = adam_element(ad, a.lfc[i], g, m, v);
     a.m[i] = m;
     a.v[i] = v;
-    const float denom = __builtin_sqrtf(v) / bc2s + a.eps;
-    const float p = a.lfc[i] - step_size * (m / denom);
     a.lfc[i] = p;
     np_[c] = p + a.hfc[i];
     o[c] = a.data[i];
   }
   float dx = np_[0] - o[0], dy = np_[1] - o[1], dz = np_[2] - o[2];
-  if (a.budget > 0.f) {  // ClipPointsLinf (clip_utils.py:43-56)
-    const float norm = __builtin_sqrtf(dx * dx + dy * dy + dz * dz);
-    const float s = fminf(a.budget / (norm + 1e-9f), 1.f);
-    dx *= s, dy *= s, dz *= s;
-  }
+  clip_linf(dx, dy, dz, a.budget);
   a.out[base] = o[0] + dx;
   a.out[base + a.N] = o[1] + dy;
   a.out[base + 2 * (int64_t)a.N] = o[2] + dz;

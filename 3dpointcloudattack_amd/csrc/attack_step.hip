@@ -8,7 +8,8 @@
 
 namespace pc3d {
 
-// BookArgs, the bookkeeping decisions (cw_book_decide) and the per-point update (cw_point_update) live in cw_update_body.h
+// BookArgs and the per-point update (cw_point_update) live in cw_update_body.h; the Adam element, the clip and the
+// bookkeeping decision (cw_book_decide) it is made of in update_body.h
 
 // one workgroup per sample
 __global__ __launch_bounds__(256) void cw_bookkeep_kernel(BookArgs a) {
@@ -75,8 +76,6 @@ __global__ __launch_bounds__(256) void cw_step_kernel(StepArgs a) {
   const int b = blockIdx.y;
   if (k >= a.K) return;
   const int t = a.step_dev ? a.step_dev[0] : a.step_host;
-  const float omb1 = (float)(1.0 - a.b1), omb2 = (float)(1.0 - a.b2), fb2 = (float)a.b2;
-  const float step_size = cw_adam_step_size(a.lr, a.b1, t), bc2s = cw_adam_bc2s(a.b2, t);
   float* pp = a.p.p + (int64_t)b * a.p.bs + (int64_t)k * a.p.ps;
   const float* gp = a.g.p + (int64_t)b * a.g.bs + (int64_t)k * a.g.ps;
   float* mp = a.m.p + (int64_t)b * a.m.bs + (int64_t)k * a.m.ps;
@@ -91,7 +90,7 @@ __global__ __launch_bounds__(256) void cw_step_kernel(StepArgs a) {
     const float* qp = a.ori.p + (int64_t)b * a.ori.bs + (int64_t)j * a.ori.ps;
     q[0] = qp[0], q[1] = qp[a.ori.cs], q[2] = qp[2 * a.ori.cs];
   }
-  const CwPointConsts c{a.dist_kind, a.B, a.K, omb1, omb2, fb2, step_size, bc2s, a.eps, a.budget};
+  const CwPointConsts c{a.dist_kind, a.B, a.K, adam_consts(a.lr, a.b1, a.b2, a.eps, t), a.budget};
   const float pin[3] = {px, py, pz}, oin[3] = {ox, oy, oz};
   float m[3] = {mp[0], mp[a.m.cs], mp[2 * a.m.cs]}, v[3] = {vp[0], vp[a.v.cs], vp[2 * a.v.cs]}, np_[3];
   cw_point_update(c, pin, oin, g, q, a.dist_kind ? a.w[b] : 0.f, a.dist_kind == 1 ? a.l2norm[b] : 0.f, m, v, np_);
@@ -180,14 +179,13 @@ __global__ __launch_bounds__(1024) void cw_update_kernel(UpdateArgs u) {
     s_dist = dist;
     s_copy = cw_book_decide(a, b, dist, pr, lb, bd, obd);
     // Adam bias corrections in double (as torch): evaluated once per workgroup, not by all 1024 threads
-    s_step_size = cw_adam_step_size(s.lr, s.b1, t);
-    s_bc2s = cw_adam_bc2s(s.b2, t);
+    s_step_size = adam_step_size(s.lr, s.b1, t);
+    s_bc2s = adam_bc2s(s.b2, t);
   }
   __syncthreads();
   const bool copy = s_copy != 0;
   const float l2n = s_dist;
-  const float omb1 = (float)(1.0 - s.b1), omb2 = (float)(1.0 - s.b2), fb2 = (float)s.b2;
-  const float step_size = s_step_size, bc2s = s_bc2s;
+  const AdamConsts ad = adam_consts_with(s.b1, s.b2, s.eps, s_step_size, s_bc2s);
 #pragma unroll
   for (int i = 0; i < PER; ++i) {
     const int k = tid + i * 1024;
@@ -204,7 +202,7 @@ __global__ __launch_bounds__(1024) void cw_update_kernel(UpdateArgs u) {
     float* pp = s.p.p + (int64_t)b * s.p.bs + (int64_t)k * s.p.ps;
     float* mp = s.m.p + (int64_t)b * s.m.bs + (int64_t)k * s.m.ps;
     float* vp = s.v.p + (int64_t)b * s.v.bs + (int64_t)k * s.v.ps;
-    const CwPointConsts c{s.dist_kind, s.B, s.K, omb1, omb2, fb2, step_size, bc2s, s.eps, s.budget};
+    const CwPointConsts c{s.dist_kind, s.B, s.K, ad, s.budget};
     const float pin[3] = {px[i], py[i], pz[i]}, oin[3] = {ox[i], oy[i], oz[i]}, q[3] = {qx[i], qy[i], qz[i]};
     float np_[3];
     cw_point_update(c, pin, oin, g, q, wb, l2n, m_[i], v_[i], np_);

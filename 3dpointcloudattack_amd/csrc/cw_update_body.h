@@ -1,8 +1,9 @@
 // The CW iteration's per-point update and per-sample bookkeeping as device functions: the stand-alone kernels of
 // attack_step.hip, the bookkeeping rider of a linear launch (linear_riders.hip) and the update epilogue of the tower
 // backward (pointmlp.hip) compile these statements, so every form of the iteration computes the same bits.
+// The Adam element, ClipPointsLinf and the decision itself are update_body.h's.
 #pragma once
-#include "pc3d_common.h"
+#include "update_body.h"
 
 namespace pc3d {
 
@@ -22,17 +23,12 @@ struct BookArgs {
   int32_t* step;             // Adam step word, incremented once per launch (may be null)
 };
 
-// Adam's two bias-correction factors for step t, in double as torch evaluates them
-__device__ __forceinline__ float cw_adam_step_size(double lr, double b1, int t) { return (float)(lr / (1.0 - pow(b1, (double)t))); }
-__device__ __forceinline__ float cw_adam_bc2s(double b2, int t) { return (float)sqrt(1.0 - pow(b2, (double)t)); }
-
 // The constants of one update launch that do not depend on the point
 struct CwPointConsts {
   int dist_kind;             // 0: none, 1: L2Dist, 2: ChamferDist adv2ori
   int B, K;
-  float omb1, omb2, fb2;     // (float)(1 - beta1), (float)(1 - beta2), (float)beta2
-  float step_size, bc2s;     // cw_adam_step_size / cw_adam_bc2s
-  float eps, budget;
+  AdamConsts ad;
+  float budget;
 };
 
 // One point of the CW update: g = g_model + d/dadv [ mean_b w_b * D(adv_b, ori_b) ], then Adam, then ClipPointsLinf.
@@ -56,41 +52,18 @@ __device__ __forceinline__ void cw_point_update(const CwPointConsts& c, const fl
   }
   float np_[3];
 #pragma unroll
-  for (int e = 0; e < 3; ++e) {
-    float mm = m[e], vv = v[e];
-    mm = mm + (g[e] - mm) * c.omb1;
-    vv = vv * c.fb2 + c.omb2 * g[e] * g[e];
-    m[e] = mm;
-    v[e] = vv;
-    const float denom = __builtin_sqrtf(vv) / c.bc2s + c.eps;
-    np_[e] = p[e] - c.step_size * (mm / denom);
-  }
-  float dx = np_[0] - o[0], dy = np_[1] - o[1], dz = np_[2] - o[2];
-  if (c.budget > 0.f) {  // ClipPointsLinf (clip_utils.py:43-56)
-    const float norm = __builtin_sqrtf(dx * dx + dy * dy + dz * dz);
-    const float s = fminf(c.budget / (norm + 1e-9f), 1.f);
-    dx *= s, dy *= s, dz *= s;
-  }
-  np[0] = o[0] + dx;
-  np[1] = o[1] + dy;
-  np[2] = o[2] + dz;
+  for (int e = 0; e < 3; ++e) np_[e] = adam_element(c.ad, p[e], g[e], m[e], v[e]);
+  np[0] = np_[0] - o[0], np[1] = np_[1] - o[1], np[2] = np_[2] - o[2];
+  clip_linf(np[0], np[1], np[2], c.budget);
+  np[0] = o[0] + np[0];
+  np[1] = o[1] + np[1];
+  np[2] = o[2] + np[2];
 }
 
-// The decisions of the bookkeeping for one sample (one thread): returns 1 when the iterate becomes the overall best
+// the decision on a BookArgs. The kernels go through this form: with the six words passed at their call sites instead, the
+// register-bound cw_update_kernel<2/4/8> allocate worse (83 VGPRs for 77, scratch 36 for 0 and 504 for 280 bytes a lane)
 __device__ __forceinline__ int cw_book_decide(const BookArgs& a, int b, float dist, int64_t pr, int64_t lb, float bd, float obd) {
-  if (a.dist_val) a.dist_val[b] = dist;
-  const bool succ = a.untarget ? (pr != lb) : (pr == lb);
-  if (succ && dist < bd) {
-    a.bestdist[b] = dist;
-    a.bestscore[b] = pr;
-  }
-  int copy = 0;
-  if (succ && dist < obd) {
-    a.o_bestdist[b] = dist;
-    a.o_bestscore[b] = pr;
-    copy = 1;
-  }
-  return copy;
+  return cw_book_decide(a.dist_val, a.bestdist, a.bestscore, a.o_bestdist, a.o_bestscore, a.untarget, b, dist, pr, lb, bd, obd);
 }
 
 constexpr int kCwBookThreads = 512;
@@ -134,8 +107,8 @@ __device__ __forceinline__ void cw_book_body(const BookArgs& a, int b, double lr
     s_copy = cw_book_decide(a, b, dist, pr, lb, bd, obd);
     if (adam && b == 0) {
       const int t = step_dev[0];
-      adam[0] = cw_adam_step_size(lr, b1, t);
-      adam[1] = cw_adam_bc2s(b2, t);
+      adam[0] = adam_step_size(lr, b1, t);
+      adam[1] = adam_bc2s(b2, t);
     }
   }
   __syncthreads();

@@ -5,7 +5,7 @@
 //   * dense pairwise (squared) distance matrix for the callers that really want [B,N,M]
 //     (attack/CW/CW_utils/distance.py:15-32, utils/dis_utils_torch.py:8-11, utils/dis_utils_numpy.py:13-20)
 // One thread owns one POINT (3 coordinates), so the per-point norm/cross products need no communication.
-#include "pc3d_common.h"
+#include "update_body.h"
 
 namespace pc3d {
 
@@ -16,32 +16,7 @@ struct ClipArgs {
   float budget;  // per-point L2 budget ("Linf" in the reference's naming, SURVEY A-10); <= 0 -> no clip
 };
 
-// ProjectInnerPoints (clip_utils.py:67-108) then ClipPointsLinf (:43-56) on one point's perturbation.
-__device__ __forceinline__ void project_clip(float& dx, float& dy, float& dz, bool has_normal, float nx, float ny,
-                                             float nz, float budget) {
-  if (has_normal) {
-    const float inner = dx * nx + dy * ny + dz * nz;
-    if (inner < 0.f) {
-      // vng = n x d ; vref = vng x n
-      const float gx = ny * dz - nz * dy, gy = nz * dx - nx * dz, gz = nx * dy - ny * dx;
-      const float gnorm = __builtin_sqrtf(gx * gx + gy * gy + gz * gz);
-      const float rx = gy * nz - gz * ny, ry = gz * nx - gx * nz, rz = gx * ny - gy * nx;
-      const float rnorm = __builtin_sqrtf(rx * rx + ry * ry + rz * rz);
-      // reference: diff_proj = diff * vref / (|vref| + 1e-9)   (elementwise product, kept as written)
-      const float den = rnorm + 1e-9f;
-      float px = dx * rx / den, py = dy * ry / den, pz = dz * rz / den;
-      if (gnorm < 1e-6f) px = py = pz = 0.f;
-      dx = px, dy = py, dz = pz;
-    }
-  }
-  if (budget > 0.f) {
-    const float norm = __builtin_sqrtf(dx * dx + dy * dy + dz * dz);
-    float s = budget / (norm + 1e-9f);
-    s = fminf(s, 1.f);
-    dx *= s, dy *= s, dz *= s;
-  }
-}
-
+// the projection and the clip themselves (project_clip) are update_body.h's
 __global__ __launch_bounds__(256) void clip_kernel(ClipArgs a) {
   const int k = blockIdx.x * 256 + threadIdx.x;
   const int b = blockIdx.y;
@@ -116,9 +91,7 @@ __global__ __launch_bounds__(256) void adam_clip_kernel(AdamArgs a) {
   const int b = blockIdx.y;
   if (k >= a.K) return;
   const int t = a.step_dev ? a.step_dev[0] : a.step_host;
-  const float omb1 = (float)(1.0 - a.b1), omb2 = (float)(1.0 - a.b2), fb2 = (float)a.b2;
-  const float step_size = (float)(a.lr / (1.0 - pow(a.b1, (double)t)));
-  const float bc2s = (float)sqrt(1.0 - pow(a.b2, (double)t));
+  const AdamConsts ad = adam_consts(a.lr, a.b1, a.b2, a.eps, t);
   float* pp = a.p.p + (int64_t)b * a.p.bs + (int64_t)k * a.p.ps;
   const float* gp = a.g.p + (int64_t)b * a.g.bs + (int64_t)k * a.g.ps;
   const float* gq = a.g2.p ? a.g2.p + (int64_t)b * a.g2.bs + (int64_t)k * a.g2.ps : nullptr;
@@ -130,12 +103,9 @@ __global__ __launch_bounds__(256) void adam_clip_kernel(AdamArgs a) {
     float g = gp[c * a.g.cs];
     if (gq) g += gq[c * a.g2.cs];
     float m = mp[c * a.m.cs], v = vp[c * a.v.cs];
-    m = m + (g - m) * omb1;
-    v = v * fb2 + omb2 * g * g;
+    np_[c] = adam_element(ad, pp[c * a.p.cs], g, m, v);
     mp[c * a.m.cs] = m;
     vp[c * a.v.cs] = v;
-    const float denom = __builtin_sqrtf(v) / bc2s + a.eps;
-    np_[c] = pp[c * a.p.cs] - step_size * (m / denom);
   }
   if (a.ori.p) {
     const float* o = a.ori.p + (int64_t)b * a.ori.bs + (int64_t)k * a.ori.ps;

@@ -6,7 +6,7 @@
 //                index on ties), curv (mean of (kappa_adv - kappa_ori[nn])^2, kappa_fwd_kernel's arithmetic), constrain and
 //                loss_n = cls + scale * constrain, written to row `step` of the loss buffer;
 //   3. gradient of gval * scale * constrain w.r.t. the iterate, added to the victim's (already scaled) gradient;
-//   4. Adam on the offset (pc3d_adam_clip_step_f32's arithmetic), the scheduler's lr *= 0.9990, lp_clip, x = ori + offset.
+//   4. Adam on the offset (adam_element of update_body.h, what pc3d_adam_clip_step_f32 runs), the scheduler's lr *= 0.9990, lp_clip, x = ori + offset.
 // It stands for pc3d_geoa3_record_f32 + pc3d_kappa_gather_f32 + pc3d_geoa3_terms_f32 + pc3d_geoa3_terms_bwd_f32 +
 // pc3d_kappa_bwd_f32 + two pc3d_nn_bwd_f32 + pc3d_adam_clip_step_f32 in the captured iteration of
 // geoA3_attack(cfg.device_loop = True). Distances are direct-form squared distances recomputed from the points on the given
@@ -33,7 +33,7 @@
 // = 38 N + 2 N k + 512 B: 140.5 KiB at N = 2048, k = 16 — the cap. The CU has 160 KiB; N = 4096 at k = 16 would need 280 KiB
 // (the reverse index alone 128), and a reverse index in global memory would put back the round trips this launch removes.
 // Whatever N and k, a launch whose 38 N + 2 N k + 512 bytes exceed 160 KiB is refused (at N = 2048: k > 20).
-#include "pc3d_common.h"
+#include "update_body.h"
 
 namespace pc3d {
 
@@ -179,8 +179,8 @@ __global__ __launch_bounds__(kGuThreads) void geoa3_update_kernel(GeoUpdArgs a) 
     const int t0 = a.step[b];
     const double lrv = a.lr[b];
     const int t = t0 + 1;
-    s_c[0] = (float)(lrv / (1.0 - pow(a.b1, (double)t)));
-    s_c[1] = (float)sqrt(1.0 - pow(a.b2, (double)t));
+    s_c[0] = adam_step_size(lrv, a.b1, t);
+    s_c[1] = adam_bc2s(a.b2, t);
     a.step[b] = t;
     if (a.scheduler) a.lr[b] = lrv * 0.9990;
     const int64_t lab = a.pred[b];
@@ -307,10 +307,9 @@ __global__ __launch_bounds__(kGuThreads) void geoa3_update_kernel(GeoUpdArgs a) 
   __syncthreads();
 
   // ---- 3b / 4. gradient, Adam, lp_clip, the next iterate ----
-  const float step_size = s_c[0], bc2s = s_c[1];
+  const AdamConsts ad = adam_consts_with(a.b1, a.b2, a.eps, s_c[0], s_c[1]);
   const float g_dis = s_c[2], g_hd = s_c[3], g_cv = s_c[4];
   const int hd_arg = s_i[2];
-  const float omb1 = (float)(1.0 - a.b1), omb2 = (float)(1.0 - a.b2), fb2 = (float)a.b2;
   const float inv_k = 1.f / (float)(k > 0 ? k : 1);
   for (int p = tid; p < N; p += kGuThreads) {
     const float px = sx[p], py = sy[p], pz = sz[p];
@@ -379,12 +378,9 @@ __global__ __launch_bounds__(kGuThreads) void geoa3_update_kernel(GeoUpdArgs a) 
       const int64_t at = base3 + (int64_t)c * N + p;
       if (a.g_out) a.g_out[at] = gt[c];
       float mm = a.m[at], vv = a.v[at];
-      mm = mm + (gt[c] - mm) * omb1;
-      vv = vv * fb2 + omb2 * gt[c] * gt[c];
+      nw[c] = adam_element(ad, a.offset[at], gt[c], mm, vv);
       a.m[at] = mm;
       a.v[at] = vv;
-      const float denom = __builtin_sqrtf(vv) / bc2s + a.eps;
-      nw[c] = a.offset[at] - step_size * (mm / denom);
     }
     if (a.cc_linf != 0.f) {      // lp_clip (:92-102)
       const float len = __builtin_sqrtf((nw[0] * nw[0] + nw[1] * nw[1]) + nw[2] * nw[2]);

@@ -6,6 +6,7 @@
 //               the record of the evaluation, the weight gradient, Adam on the 9 parameters and the next iterate W x.
 // The clouds are tiny (12 KB at N = 1024): what counts is that a step adds one launch and no host round trip.
 #include "iso_body.h"
+#include "update_body.h"
 
 namespace pc3d {
 
@@ -88,19 +89,15 @@ __global__ __launch_bounds__(ISO_T) void iso_update_kernel(IsoUpdateArgs a) {
     if (a.g.p)
       iso_wgrad_block(a.g.p + (int64_t)b * a.g.bs, a.g.ps, a.g.cs, a.x.p + (int64_t)b * a.x.bs, a.x.ps, a.x.cs, a.N, s_part, s_gw);
     if (tid < 9) {
-      // torch.optim.Adam, single-tensor form, weight_decay 0, amsgrad off; the scalars in double, rounded to fp32 once
-      const float omb1 = (float)(1.0 - a.b1), omb2 = (float)(1.0 - a.b2), fb2 = (float)a.b2;
-      const float neg_step = -(float)(a.lr / (1.0 - pow(a.b1, (double)t)));
-      const float bc2s = (float)sqrt(1.0 - pow(a.b2, (double)t));
+      const AdamConsts ad = adam_consts(a.lr, a.b1, a.b2, a.eps, t);
       const int64_t k = (int64_t)b * 9 + tid;
       const float g = a.g.p ? s_gw[tid] : a.gW_in[k];
       float m = a.m[k], v = a.v[k];
-      m = m + (g - m) * omb1;
-      v = v * fb2 + omb2 * g * g;
+      const float denom = adam_moments(ad, g, m, v);
       a.m[k] = m;
       a.v[k] = v;
-      const float denom = __builtin_sqrtf(v) / bc2s + a.eps;
-      const float w = a.W[k] + (neg_step * m) / denom;
+      // this loop's own last line: (-step_size * m) / denom rounds differently from adam_element's step_size * (m / denom)
+      const float w = a.W[k] + (-ad.step_size * m) / denom;
       a.W[k] = w;
       s_w[tid] = w;
     }

@@ -3,8 +3,8 @@
 //     knn_outlier_loss_kernel, knn.hip: the same values, the same 256-strided partial sums, the same threshold),
 //   * the gradient of the masked kNN term — own side and neighbour side, summed in a fixed order without float atomics,
 //   * the Chamfer adv -> ori gradient on the given arg-mins,
-//   * Adam (pc3d_adam_clip_step_f32's arithmetic) on victim + Chamfer + kNN gradient,
-//   * ProjectInnerPoints (optional) and ClipPointsLinf (clip_utils.py:43-56, 67-108).
+//   * Adam on victim + Chamfer + kNN gradient, ProjectInnerPoints (optional) and ClipPointsLinf: adam_element and
+//     project_clip of update_body.h, the functions pc3d_adam_clip_step_f32 runs.
 // It replaces pc3d_knn_outlier_loss_f32 + pc3d_knn_self_bwd_f32 (+ its ordered-scatter scratch) + pc3d_nn_bwd_f32 +
 // pc3d_adam_clip_step_f32 in the captured iteration of CWKNN(device_loop=True).
 //
@@ -18,7 +18,7 @@
 // LDS per sample: the cloud (12 B / point: the iterate is updated in place, so neighbours are read from this copy), the
 // neighbour-side accumulators (12), the mean neighbour distances (4), the masked list (4) + the 8 KiB edge stage:
 // 32 N + 8 KiB + 48 B = 136 KiB at N = 4096, the cap (the CU has 160 KiB; 8192 points would need 264).
-#include "pc3d_common.h"
+#include "update_body.h"
 
 namespace pc3d {
 
@@ -46,30 +46,6 @@ struct KnnUpdArgs {
 static inline size_t knn_upd_lds_bytes(int N) {
   const size_t np = (size_t)((N + 3) & ~3);
   return np * 32 + (size_t)kKuEdges * 4 + 48;
-}
-
-// ProjectInnerPoints (clip_utils.py:67-108) then ClipPointsLinf (:43-56) on one point's perturbation: the statements of
-// elementwise.hip's project_clip
-__device__ __forceinline__ void ku_project_clip(float& dx, float& dy, float& dz, bool project, float nx, float ny, float nz,
-                                                float budget) {
-  if (project) {
-    const float inner = dx * nx + dy * ny + dz * nz;
-    if (inner < 0.f) {
-      const float gx = ny * dz - nz * dy, gy = nz * dx - nx * dz, gz = nx * dy - ny * dx;      // vng = n x d
-      const float gnorm = __builtin_sqrtf(gx * gx + gy * gy + gz * gz);
-      const float rx = gy * nz - gz * ny, ry = gz * nx - gx * nz, rz = gx * ny - gy * nx;      // vref = vng x n
-      const float rnorm = __builtin_sqrtf(rx * rx + ry * ry + rz * rz);
-      const float den = rnorm + 1e-9f;
-      float px = dx * rx / den, py = dy * ry / den, pz = dz * rz / den;      // elementwise product, as the reference writes it
-      if (gnorm < 1e-6f) px = py = pz = 0.f;
-      dx = px, dy = py, dz = pz;
-    }
-  }
-  if (budget > 0.f) {
-    const float norm = __builtin_sqrtf(dx * dx + dy * dy + dz * dz);
-    const float s = fminf(budget / (norm + 1e-9f), 1.f);
-    dx *= s, dy *= s, dz *= s;
-  }
 }
 
 // knn_outlier_loss_kernel's block_sum256 inside a 1024-thread workgroup: the first 256 threads carry the values
@@ -103,8 +79,8 @@ __global__ __launch_bounds__(kKuThreads) void knn_attack_update_kernel(KnnUpdArg
 
   if (tid == 0) {      // Adam's bias corrections in double (as torch), once per workgroup
     const int t = a.step_dev ? a.step_dev[0] : a.step_host;
-    s_adam[0] = (float)(a.lr / (1.0 - pow(a.b1, (double)t)));
-    s_adam[1] = (float)sqrt(1.0 - pow(a.b2, (double)t));
+    s_adam[0] = adam_step_size(a.lr, a.b1, t);
+    s_adam[1] = adam_bc2s(a.b2, t);
   }
   const float inv_k = 1.f / (float)(k > 0 ? k : 1);
   for (int p = tid; p < N; p += kKuThreads) {
@@ -185,8 +161,7 @@ __global__ __launch_bounds__(kKuThreads) void knn_attack_update_kernel(KnnUpdArg
   }
   __syncthreads();      // (s_adam for the clouds without a kNN term)
 
-  const float omb1 = (float)(1.0 - a.b1), omb2 = (float)(1.0 - a.b2), fb2 = (float)a.b2;
-  const float step_size = s_adam[0], bc2s = s_adam[1];
+  const AdamConsts ad = adam_consts_with(a.b1, a.b2, a.eps, s_adam[0], s_adam[1]);
   const float wc = 2.f * a.c_ch;
   const PtsView nrm = a.normal.p ? a.normal : a.ori;
   for (int p = tid; p < N; p += kKuThreads) {
@@ -223,12 +198,9 @@ __global__ __launch_bounds__(kKuThreads) void knn_attack_update_kernel(KnnUpdArg
     for (int c = 0; c < 3; ++c) {
       const float g = gp[c * a.g.cs] + g2[c];
       float mm = mp[c * a.m.cs], vv = vp[c * a.v.cs];
-      mm = mm + (g - mm) * omb1;
-      vv = vv * fb2 + omb2 * g * g;
+      nw[c] = adam_element(ad, x[c], g, mm, vv);
       mp[c * a.m.cs] = mm;
       vp[c * a.v.cs] = vv;
-      const float denom = __builtin_sqrtf(vv) / bc2s + a.eps;
-      nw[c] = x[c] - step_size * (mm / denom);
     }
     float dx = nw[0] - o[0], dy = nw[1] - o[1], dz = nw[2] - o[2];
     float nx = 0.f, ny = 0.f, nz = 0.f;
@@ -236,7 +208,7 @@ __global__ __launch_bounds__(kKuThreads) void knn_attack_update_kernel(KnnUpdArg
       const float* n = nrm.p + (int64_t)b * nrm.bs + (int64_t)p * nrm.ps;
       nx = n[0], ny = n[nrm.cs], nz = n[2 * nrm.cs];
     }
-    ku_project_clip(dx, dy, dz, a.clip_mode == 1, nx, ny, nz, a.budget);
+    project_clip(dx, dy, dz, a.clip_mode == 1, nx, ny, nz, a.budget);
     float* xp = a.adv.p + (int64_t)b * a.adv.bs + (int64_t)p * a.adv.ps;
     xp[0] = o[0] + dx;
     xp[a.adv.cs] = o[1] + dy;

@@ -545,7 +545,7 @@ constexpr int PM_UPD_LD = 3 * PM_BTP;   // parked operands: [p, ori, m, v, ori[n
 __device__ __forceinline__ void pm_bwd_update_point(const PMUpdArgs& u, const float* s_u, int N, int b, int n, int p,
                                                     float g0, float g1, float g2) {
   const float* s_uc = s_u + 5 * PM_UPD_LD;
-  const CwPointConsts c{u.dist_kind, u.B, N, u.omb1, u.omb2, u.fb2, s_uc[2], s_uc[3], u.eps, u.budget};
+  const CwPointConsts c{u.dist_kind, u.B, N, AdamConsts{u.omb1, u.omb2, u.fb2, s_uc[2], s_uc[3], u.eps}, u.budget};
   float pin[3], oin[3], m[3], v[3], q[3], np_[3], g[3] = {g0, g1, g2};
 #pragma unroll
   for (int e = 0; e < 3; ++e) {

@@ -93,6 +93,24 @@ class LoopGraph:
     def replay(self, n=1):
         self.graphs[n].replay()
 
+    def run(self, n):
+        """n passes, with the largest captured counts that fit, in descending order (the counts include 1)."""
+        for size in sorted(self.graphs, reverse=True):
+            while n >= size:
+                self.graphs[size].replay()
+                n -= size
+
+
+def weights_key(module):
+    """What a capture is keyed on to say "these are still the weights it was captured with": the address and version
+    counter of every parameter and buffer (loading other weights or moving the module changes it)."""
+    return tuple((t.data_ptr(), t._version) for t in list(module.parameters()) + list(module.buffers()))
+
+
+def unwrap(model):
+    """The victim behind a GraphedVictim, any other model as it is (whatever attributes it has)."""
+    return model.model if isinstance(model, GraphedVictim) else model
+
 
 MAX_CAPTURES = 4     # distinct (shape, mode, weights) keys per wrapper; the oldest is dropped beyond this
 MAX_REPLICAS = 4     # captures of ONE key that may wait for their backward at the same time (EOT-style loops that
@@ -227,7 +245,7 @@ class GraphedVictim(nn.Module):
         return self.model.load_state_dict(*a, **k)
 
     def _weights_key(self):
-        return tuple((t.data_ptr(), t._version) for t in list(self.model.parameters()) + list(self.model.buffers()))
+        return weights_key(self.model)
 
     def _capture(self, x, with_grad):
         """Capture under a saved host RNG state: the probe / warm-up / capture passes run the Python forward several

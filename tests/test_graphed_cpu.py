@@ -39,3 +39,42 @@ def test_copies_and_pickles_drop_the_captures():
     assert g3._slots == {} and g3.stats["captures"] == 0
     for a, b in zip(g3.model.state_dict().values(), m.state_dict().values()):
         assert torch.equal(a, b)
+
+
+def test_unwrap_only_a_graphed_victim():
+    m = pointnet.PointNetCls(k=5, feature_transform=False).eval()
+    assert graphed.unwrap(graphed.wrap(m)) is m and graphed.unwrap(m) is m
+    holder = torch.nn.Sequential()
+    holder.model = m                                    # any other module with a .model attribute is left as it is
+    assert graphed.unwrap(holder) is holder
+
+
+def test_weights_key_follows_loads_and_in_place_updates():
+    m = torch.nn.BatchNorm1d(4)
+    k0 = graphed.weights_key(m)
+    assert len(k0) == len(list(m.parameters())) + len(list(m.buffers())) and graphed.weights_key(m) == k0
+    m.load_state_dict(copy.deepcopy(m.state_dict()))
+    k1 = graphed.weights_key(m)
+    assert k1 != k0
+    with torch.no_grad():
+        m.running_mean.add_(1.0)
+    assert graphed.weights_key(m) != k1
+
+
+def test_loop_graph_run_takes_the_largest_counts_that_fit():
+    class Fake:
+        def __init__(self, n, log):
+            self.n, self.log = n, log
+
+        def replay(self):
+            self.log.append(self.n)
+
+    log = []
+    loop = graphed.LoopGraph.__new__(graphed.LoopGraph)     # no capture without a GPU: the replay policy alone
+    loop.graphs = {n: Fake(n, log) for n in (4, 1, 16)}
+    loop.run(37)
+    assert log == [16, 16, 4, 1]
+    del log[:]
+    loop.run(0)
+    loop.run(3)
+    assert log == [1, 1, 1]

@@ -121,6 +121,14 @@ def test_graph_replay_equals_eager_and_run_equals_run(dev, pn, case, num_iter):
     assert np.abs(g - case["pcs"]).max() > 1e-3
 
 
+def test_zero_iterations_capture_nothing_and_return_the_start(dev, pn, case):
+    """num_iter = 0 (what tools/bench_knn_attack.py times as the attack's fixed cost): no graph is captured, none is run."""
+    a, g, gs = _attack(pn, case["pcs"], case["labels"], num_iter=0, device_loop=True)
+    _, e, es = _attack(pn, case["pcs"], case["labels"], num_iter=0, device_loop=True, graph=False)
+    assert a.last_path == "device_loop" and a._loop_cache["graphs"] is None
+    assert np.array_equal(g, e) and gs == es
+
+
 def test_batch_of_three_equals_three_alone(dev, pn, case):
     seeds = [41, 42, 43]
     _, out, _ = _attack(pn, case["pcs"], case["labels"], device_loop=True, sample_seeds=seeds, global_batch=3)
