@@ -51,17 +51,6 @@ struct AddArgs {
   int P;                     // FarChamfer's points per cluster (A % P == 0, P <= 64)
 };
 
-// (value, index) maximum over the wavefront; ties go to the lower index. Every lane ends with the winner.
-__device__ __forceinline__ void wave_argmax_first(float& v, int& i, int& aux) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(v, o, 64);
-    const int oi = __shfl_xor(i, o, 64);
-    const int oa = __shfl_xor(aux, o, 64);
-    if (ov > v || (ov == v && oi < i)) v = ov, i = oi, aux = oa;
-  }
-}
-
 // FAR: the FarChamfer instantiation; only it reserves the LDS copy of the points (the others keep ~100 B of LDS, so
 // their residency is not capped by the pair term's 56 KiB)
 template <int PER, bool FAR>

@@ -34,12 +34,7 @@ __device__ __forceinline__ void cta_argmax(const float* v, int k, int lane, int 
     const int c = lane + 64 * j;
     if (c < k && c != skip && (v[j] > bv || (v[j] == bv && c < bi))) bv = v[j], bi = c;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float cv = __shfl_xor(bv, o, 64);
-    const int ci = __shfl_xor(bi, o, 64);
-    if (cv > bv || (cv == bv && ci < bi)) bv = cv, bi = ci;
-  }
+  wave_argmax_first(bv, bi);
 }
 
 __device__ __forceinline__ void cta_load_row(const float* row, int k, int lane, float* v) {
@@ -84,11 +79,7 @@ __global__ __launch_bounds__(1024) void ig_steps_kernel(IgStepsArgs a) {
       const float val = a.x.p[b * a.x.bs + (r / a.N) * a.x.cs + (r % a.N) * a.x.ps];
       acc = mn ? fminf(acc, val) : fmaxf(acc, val);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float c = __shfl_xor(acc, o, 64);
-      acc = mn ? fminf(acc, c) : fmaxf(acc, c);
-    }
+    acc = mn ? wave_min(acc) : wave_max(acc);
     if (lane == 0) s_part[wave] = acc;
     __syncthreads();
     base = s_part[0];

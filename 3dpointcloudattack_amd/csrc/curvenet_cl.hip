@@ -179,10 +179,7 @@ __global__ __launch_bounds__(256) void lpfa_prep_bwd_kernel(const float* __restr
     }
   }
 #pragma unroll
-  for (int o = LP / 2; o > 0; o >>= 1) {
-#pragma unroll
-    for (int d = 0; d < 3; ++d) s[d] += __shfl_xor(s[d], o, 64);
-  }
+  for (int d = 0; d < 3; ++d) s[d] = wave_sum<LP>(s[d]);
   if (live && l == 0) gpts[p * 3] = s[0], gpts[p * 3 + 1] = s[1], gpts[p * 3 + 2] = s[2];
 }
 

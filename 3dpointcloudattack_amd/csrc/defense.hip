@@ -31,23 +31,6 @@ struct SorArgs {
   PtsViewMut out;
 };
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);      // commutative at every level: the same bits in all lanes
-  return v;
-}
-
-// Sum over the workgroup in a fixed order (butterfly inside a wave, waves ascending); the same value in every thread.
-__device__ __forceinline__ double block_sum_f64(double v, double* red) {
-  v = wave_sum_f64(v);
-  __syncthreads();
-  if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int w = 0; w < kSorWaves; ++w) s += red[w];
-  return s;
-}
-
 // Everything after the search, for the cloud of this workgroup. d: the cloud's [K,k1] distances (thread t reads the rows
 // t, t + kSorThreads, ... only), kept: K ints of LDS.
 __device__ void sor_tail(const SorArgs& a, const float* d, int b, int* kept, double* red, int* wcnt) {
@@ -61,13 +44,13 @@ __device__ void sor_tail(const SorArgs& a, const float* d, int b, int* kept, dou
   };
   double part = 0.0;
   for (int i = tid; i < K; i += kSorThreads) part += vof(i);
-  const double mean = block_sum_f64(part, red) / (double)K;
+  const double mean = block_sum_ordered<kSorWaves>(part, red) / (double)K;
   part = 0.0;
   for (int i = tid; i < K; i += kSorThreads) {
     const double e = vof(i) - mean;
     part += e * e;
   }
-  const double var = block_sum_f64(part, red) / (double)(K - 1);
+  const double var = block_sum_ordered<kSorWaves>(part, red) / (double)(K - 1);
   const double thr = mean + a.alpha * sqrt(var);
   if (tid == 0 && a.thr) a.thr[b] = (float)thr;
 

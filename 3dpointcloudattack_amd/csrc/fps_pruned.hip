@@ -108,12 +108,7 @@ __device__ __forceinline__ float wave_max16_chain(float v) {
 // exclusive prefix sum over the 256 threads of the block (red: 4 ints of LDS); total via *tot
 __device__ __forceinline__ int block_excl_scan(int v, int* red, int tid, int* tot) {
   const int lane = tid & 63, wave = tid >> 6;
-  int inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
+  const int inc = wave_incl_scan(v, lane);
   if (lane == 63) red[wave] = inc;
   __syncthreads();
   int base = 0, all = 0;

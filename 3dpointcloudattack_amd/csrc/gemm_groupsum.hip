@@ -300,11 +300,7 @@ __global__ __launch_bounds__(1024) void gs_tiles_kernel(const uint32_t* __restri
       mx = mx > wt ? mx : wt;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int other = __shfl_xor(mx, o);
-    mx = mx > other ? mx : other;
-  }
+  mx = wave_max(mx);
   if (lane == 0) s_red[wave] = mx;
   __syncthreads();
   if (tid == 0) {
@@ -318,13 +314,8 @@ __global__ __launch_bounds__(1024) void gs_tiles_kernel(const uint32_t* __restri
   const int lo = tid * per < G ? tid * per : G, hi = lo + per < G ? lo + per : G;
   int sum = 0;
   for (int g = lo; g < hi; ++g) sum += w8[g];
-  int incl = sum;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int up = __shfl_up(incl, o);
-    if (lane >= o) incl += up;
-  }
-  __syncthreads();                                          // (s_red is read above)
+  const int incl = wave_incl_scan(sum, lane);
+  __syncthreads();                                         // (s_red is read above)
   if (lane == 63) s_red[wave] = incl;
   __syncthreads();
   int P = incl - sum;
@@ -365,12 +356,7 @@ __global__ __launch_bounds__(GS_T, (TN > 2 ? 2 : 3)) void gemm_groupsum_packed_k
 
   if (wave == 0) {
     const uint32_t word = lane < ng * NW ? a.amask[(int64_t)g0 * NW + lane] : 0u;
-    int incl = __builtin_popcount(word);
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) {
-      const int up = __shfl_up(incl, o);
-      if (lane >= o) incl += up;
-    }
+    const int incl = wave_incl_scan<16>(__builtin_popcount(word), lane & 15);      // (only lanes 0..15 hold words)
     if (lane < 16) s_aw[lane] = word, s_base[lane + 1] = incl;
     if (lane == 0) s_base[0] = 0, s_nzero = 0;
   }

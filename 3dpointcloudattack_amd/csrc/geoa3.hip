@@ -30,15 +30,6 @@ struct GeoTermsArgs {
   float* g_cls;           // [B]
 };
 
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 __global__ __launch_bounds__(256) void geoa3_terms_fwd_kernel(GeoTermsArgs a, int B) {
   __shared__ float red[4];
   __shared__ float redv[4];
@@ -59,15 +50,13 @@ __global__ __launch_bounds__(256) void geoa3_terms_fwd_kernel(GeoTermsArgs a, in
   float s_oa = 0.f;
   if (a.d_oa)
     for (int j = threadIdx.x; j < a.M; j += 256) s_oa += a.d_oa[(int64_t)b * a.M + j];
-  s_ao = block_sum(s_ao, red);
-  s_oa = block_sum(s_oa, red);
-  s_cv = block_sum(s_cv, red);
+  s_ao = block_sum4_pairwise(s_ao, red);
+  s_oa = block_sum4_pairwise(s_oa, red);
+  s_cv = block_sum4_pairwise(s_cv, red);
   // arg-max over the workgroup: (value, lowest index)
   {
-    const float wv = wave_max(mx);
-    int cand = (mx == wv) ? mi : 0x7fffffff;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cand = min(cand, __shfl_xor(cand, o, 64));
+    int cand = mi;
+    const float wv = wave_max_lowest_index(mx, cand);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) redv[wave] = wv, redi[wave] = cand;
     __syncthreads();
@@ -140,7 +129,7 @@ __global__ __launch_bounds__(256) void geoa3_record_kernel(GeoRecordArgs a) {
       const bool vnan = v != v;
       if (bi == 0x7fffffff || (!bnan && (vnan || v > bv))) bv = v, bi = c, bnan = vnan;
     }
-    // wave arg-max: NaN beats everything, then the larger value, then the lower index
+    // wave arg-max: NaN beats everything, then the larger value, then the lower index (NOT wave_argmax_first, where NaN loses)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       const float ov = __shfl_xor(bv, o, 64);

@@ -711,12 +711,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 8))) void
   {   // inclusive scan of s_off[1 .. NS] (NS <= 128: two bins per lane)
     const int e0 = 2 * lane + 1, e1 = 2 * lane + 2;
     const int v0 = e0 <= NS ? s_off[e0] : 0, v1 = e1 <= NS ? s_off[e1] : 0;
-    int sc = v0 + v1;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o = __shfl_up(sc, d, 64);
-      if (lane >= d) sc += o;
-    }
+    const int sc = wave_incl_scan(v0 + v1, lane);
     const int excl = sc - (v0 + v1);
     wave_lds_sync();
     if (e0 <= NS) s_off[e0] = excl + v0, s_cur[e0 - 1] = excl;

@@ -234,12 +234,7 @@ __global__ __launch_bounds__(64) void cls_loss_kernel(const float* logits, int l
     const float v = z[j];
     if (v > m) m = v, am = j;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(m, o, 64);
-    const int oi = __shfl_xor(am, o, 64);
-    if (ov > m || (ov == m && oi < am)) m = ov, am = oi;
-  }
+  wave_argmax_first(m, am);
   float se = 0.f;
   for (int j = lane; j < ncls; j += 64) se += expf(z[j] - m);
   se = wave_sum(se);
@@ -253,12 +248,7 @@ __global__ __launch_bounds__(64) void cls_loss_kernel(const float* logits, int l
     const float cand = (j == t) ? -10000.f : lp;   // (1-onehot)*logp - onehot*10000
     if (cand > other) other = cand, ao = j;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(other, o, 64);
-    const int oi = __shfl_xor(ao, o, 64);
-    if (ov > other || (ov == other && oi < ao)) other = ov, ao = oi;
-  }
+  wave_argmax_first(other, ao);
   const float real = z[t] - lse;
   float lval = 0.f, gt = 0.f, go = 0.f;  // d loss / d logp at the target / at the runner-up
   if (kind == 0) {
@@ -401,6 +391,8 @@ __global__ __launch_bounds__(CT_T) void cls_tail_kernel(ClsTailArgs a) {
     const float zj = (lane < a.ncls) ? ((acc[0] + acc[1]) + (acc[2] + acc[3]) + bias) : -__builtin_inff();
     float m = zj;
     int am = lane;
+    // wave_argmax_first's statements, kept in place here and below: this kernel is part of the headline step, and the call
+    // compiles to other instructions
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       const float ov = __shfl_xor(m, o, 64);

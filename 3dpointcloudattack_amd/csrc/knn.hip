@@ -329,14 +329,6 @@ __global__ __launch_bounds__(256) void knn_bwd_r_edges_kernel(KnnBwdArgs a, floa
 // and the weights the backward hands to the kNN backward: w[b,i,j] = [value_i > thr] / (N k) for j >= 1, 0 for j = 0.
 // One workgroup per sample, fixed-order reductions (deterministic); replaces ~15 ATen launches forward and as many backward.
 // ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float block_sum256(float v, float* part) {   // all 256 threads call it; result in every thread
-  v = wave_sum(v);
-  __syncthreads();                       // part may still be read from the previous call
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (part[0] + part[1]) + (part[2] + part[3]);
-}
-
 __global__ __launch_bounds__(256) void knn_outlier_loss_kernel(const float* __restrict__ d, int N, int K1, float alpha,
                                                                float* __restrict__ loss, float* __restrict__ w) {
   __shared__ float part[4];
@@ -349,7 +341,7 @@ __global__ __launch_bounds__(256) void knn_outlier_loss_kernel(const float* __re
     for (int j = 1; j < K1; ++j) v += db[(int64_t)i * K1 + j];
     s += v * inv_k;
   }
-  const float mean = block_sum256(s, part) / (float)N;
+  const float mean = block_sum4_pairwise(s, part) / (float)N;
   float q = 0.f;
   for (int i = threadIdx.x; i < N; i += 256) {
     float v = 0.f;
@@ -357,7 +349,7 @@ __global__ __launch_bounds__(256) void knn_outlier_loss_kernel(const float* __re
     const float dv = v * inv_k - mean;
     q += dv * dv;
   }
-  const float var = block_sum256(q, part) / (float)(N > 1 ? N - 1 : 1);
+  const float var = block_sum4_pairwise(q, part) / (float)(N > 1 ? N - 1 : 1);
   const float thr = mean + alpha * sqrtf(var);
   const float wv = 1.f / ((float)N * (float)k);
   float l = 0.f;
@@ -371,7 +363,7 @@ __global__ __launch_bounds__(256) void knn_outlier_loss_kernel(const float* __re
     wb[(int64_t)i * K1] = 0.f;
     for (int j = 1; j < K1; ++j) wb[(int64_t)i * K1 + j] = out ? wv : 0.f;
   }
-  l = block_sum256(l, part);
+  l = block_sum4_pairwise(l, part);
   if (threadIdx.x == 0) loss[b] = l / (float)N;
 }
 

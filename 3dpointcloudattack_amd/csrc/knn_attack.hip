@@ -48,15 +48,6 @@ static inline size_t knn_upd_lds_bytes(int N) {
   return np * 32 + (size_t)kKuEdges * 4 + 48;
 }
 
-// knn_outlier_loss_kernel's block_sum256 inside a 1024-thread workgroup: the first 256 threads carry the values
-__device__ __forceinline__ float ku_sum256(float v, float* part) {
-  v = wave_sum(v);
-  __syncthreads();
-  if (threadIdx.x < 256 && (threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (part[0] + part[1]) + (part[2] + part[3]);
-}
-
 __global__ __launch_bounds__(kKuThreads) void knn_attack_update_kernel(KnnUpdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float ku_lds[];
   const int N = a.N, np = (N + 3) & ~3, K1 = a.K1, k = K1 - 1;
@@ -102,14 +93,14 @@ __global__ __launch_bounds__(kKuThreads) void knn_attack_update_kernel(KnnUpdArg
     float s = 0.f;
     if (tid < 256)
       for (int i = tid; i < N; i += 256) s += s_val[i];
-    const float mean = ku_sum256(s, part) / (float)N;
+    const float mean = block_sum4_pairwise(s, part) / (float)N;
     float q = 0.f;
     if (tid < 256)
       for (int i = tid; i < N; i += 256) {
         const float dv = s_val[i] - mean;
         q += dv * dv;
       }
-    const float var = ku_sum256(q, part) / (float)(N > 1 ? N - 1 : 1);
+    const float var = block_sum4_pairwise(q, part) / (float)(N > 1 ? N - 1 : 1);
     thr = mean + a.alpha * sqrtf(var);
     // the masked points, ascending, by wave 0
     if (tid < 64) {

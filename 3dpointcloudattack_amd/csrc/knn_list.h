@@ -109,14 +109,12 @@ __device__ __forceinline__ float wave_min_dpp(float v) {
 
 // wave-wide maximum of one int per lane, the same way (integer: distance KEYS may be denormal bit patterns)
 __device__ __forceinline__ int wave_max_i32(int v) {
-#define PC3D_DPP_MAXI(ctrl) v = max(v, __builtin_amdgcn_update_dpp(v, v, ctrl, 0xf, 0xf, false))
-  PC3D_DPP_MAXI(0x111);
-  PC3D_DPP_MAXI(0x112);
-  PC3D_DPP_MAXI(0x114);
-  PC3D_DPP_MAXI(0x118);
-  PC3D_DPP_MAXI(0x142);
-  PC3D_DPP_MAXI(0x143);
-#undef PC3D_DPP_MAXI
+  PC3D_DPP_STEP_I(max, v, 0x111);
+  PC3D_DPP_STEP_I(max, v, 0x112);
+  PC3D_DPP_STEP_I(max, v, 0x114);
+  PC3D_DPP_STEP_I(max, v, 0x118);
+  PC3D_DPP_STEP_I(max, v, 0x142);
+  PC3D_DPP_STEP_I(max, v, 0x143);
   return __builtin_amdgcn_readlane(v, 63);
 }
 

@@ -131,18 +131,103 @@ __device__ __forceinline__ bool xcd_block(int gx, int gy, int& bx, int& by) {
   return true;
 }
 
-// Wave-level reductions through DPP/ds_swizzle-backed shuffles (64 lanes).
-__device__ __forceinline__ float wave_max(float v) {
+// ---------------------------------------------------------------------------------------------------------------------
+// Wave and workgroup reductions, scans and arg-max: the one definition of each ("Wave primitives"). The tie,
+// order and NaN rule of each is part of the bits the kernels produce; a site that needs another rule keeps its own loop and
+// says so in a comment.
+//
+// wave_sum / wave_max / wave_min<W>(v): xor butterfly over the aligned group of W lanes (W = 64, 32, 16, ... ; float, int
+// or double) that holds this lane, partner distances W/2, W/4, ..., 1 in that order. Every level adds (compares) the same
+// two values in both partner lanes, so every lane of the group ends with the same bits. Float max / min are fmaxf / fminf:
+// a NaN loses to a number.
+__device__ __forceinline__ float red_max_(float a, float b) { return fmaxf(a, b); }
+__device__ __forceinline__ double red_max_(double a, double b) { return fmax(a, b); }
+__device__ __forceinline__ int red_max_(int a, int b) { return a > b ? a : b; }
+__device__ __forceinline__ float red_min_(float a, float b) { return fminf(a, b); }
+__device__ __forceinline__ double red_min_(double a, double b) { return fmin(a, b); }
+__device__ __forceinline__ int red_min_(int a, int b) { return a < b ? a : b; }
+template <int W = 64, typename T>
+__device__ __forceinline__ T wave_max(T v) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  for (int o = W / 2; o > 0; o >>= 1) v = red_max_(v, __shfl_xor(v, o, 64));
   return v;
 }
-__device__ __forceinline__ float wave_sum(float v) {
+template <int W = 64, typename T>
+__device__ __forceinline__ T wave_min(T v) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  for (int o = W / 2; o > 0; o >>= 1) v = red_min_(v, __shfl_xor(v, o, 64));
+  return v;
+}
+template <int W = 64, typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+  for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
 
+// (value, index) maximum over the wavefront: the larger value wins, the lower index wins on a tie, and a NaN never displaces
+// a number (`ov > v` is false). On values without NaN every lane ends with the winner, which is torch.argmax's; callers
+// that must rank NaN (geoa3_record_kernel) keep a loop of their own. `aux` is a payload word that travels with the winner.
+__device__ __forceinline__ void wave_argmax_first(float& v, int& i, int& aux) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(v, o, 64);
+    const int oi = __shfl_xor(i, o, 64);
+    const int oa = __shfl_xor(aux, o, 64);
+    if (ov > v || (ov == v && oi < i)) v = ov, i = oi, aux = oa;
+  }
+}
+__device__ __forceinline__ void wave_argmax_first(float& v, int& i) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(v, o, 64);
+    const int oi = __shfl_xor(i, o, 64);
+    if (ov > v || (ov == v && oi < i)) v = ov, i = oi;
+  }
+}
+// The wave half of a workgroup arg-max: the wave's maximum (returned) and, in i, the lowest index among the lanes that
+// hold it (0x7fffffff if none does: every value NaN). The same in every lane.
+__device__ __forceinline__ float wave_max_lowest_index(float v, int& i) {
+  const float wv = wave_max(v);
+  i = wave_min((v == wv) ? i : 0x7fffffff);
+  return wv;
+}
+
+// Inclusive prefix sum of one int per lane over the aligned group of W lanes; lane_in_group = lane & (W - 1). Lanes of a
+// neighbouring group never contribute.
+template <int W = 64>
+__device__ __forceinline__ int wave_incl_scan(int v, int lane_in_group) {
+#pragma unroll
+  for (int o = 1; o < W; o <<= 1) {
+    const int up = __shfl_up(v, o, W);
+    if (lane_in_group >= o) v += up;
+  }
+  return v;
+}
+
+// Workgroup sums of one value per thread, the same bits in every thread. Both take the wave butterfly first; the NAME says
+// how the wave partials are added, and the two orders give different bits. red: one T per wave of LDS; the leading barrier
+// lets a call follow another on the same red.
+//   block_sum4_pairwise: (p0 + p1) + (p2 + p3) of waves 0..3. In a larger workgroup the first 256 threads carry the values.
+__device__ __forceinline__ float block_sum4_pairwise(float v, float* red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if (threadIdx.x < 256 && (threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+//   block_sum_ordered<WAVES>: ((0 + p0) + p1) + ... + p(WAVES-1), ascending, for a workgroup of exactly WAVES waves.
+template <int WAVES, typename T>
+__device__ __forceinline__ T block_sum_ordered(T v, T* red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  T s = 0;
+#pragma unroll
+  for (int w = 0; w < WAVES; ++w) s += red[w];
+  return s;
+}
 
 // Low-latency wave reductions on DPP row shifts / row broadcasts (VALU only, no LDS crossbar round trips): for
 // idempotent operators (max, min) overlapping contributions are harmless. The result is wave-uniform.

@@ -262,7 +262,7 @@ __global__ __launch_bounds__(256) void pointmlp3_max_bwd_twolist_kernel(PMBwdArg
   if (tid < PM_BTP) s_m1[tid] = ld_m1;
   for (int i = tid; i < PM_BTP * PM_LD2; i += 256) g2s[i] = 0.f;
   int packed = cnt0 | (cnt1 << 16);
-  int incl = packed;
+  int incl = packed;      // wave_incl_scan's statements, kept in place in this file: the headline's backward
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
     const int v = __shfl_up(incl, o, 64);
@@ -686,7 +686,7 @@ __device__ __forceinline__ void pm_bwd_body(const PMBwdArgs& a, const PMUpdArgs&
     }
   }
   for (int i = tid; i < PM_BTP * PM_LD2; i += 256) g2s[i] = 0.f;   // a point without a hit keeps a zero row
-  int incl = cnt;
+  int incl = cnt;      // wave_incl_scan's statements, kept in place
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
     const int v = __shfl_up(incl, o, 64);
@@ -747,7 +747,7 @@ __device__ __forceinline__ void pm_bwd_body(const PMBwdArgs& a, const PMUpdArgs&
       if (q < grp) before += v;
       p_tot += v;
     }
-    int inc = p_tot;
+    int inc = p_tot;      // wave_incl_scan<32>'s statements, kept in place
 #pragma unroll
     for (int o = 1; o < 32; o <<= 1) {
       const int v = __shfl_up(inc, o, 32);

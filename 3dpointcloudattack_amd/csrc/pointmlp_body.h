@@ -113,7 +113,7 @@ __device__ __forceinline__ void pm_fwd_prologue(const PMFwdArgs& a, float* lds) 
       } else {
         for (int k = l; k < a.th_K; k += 32) sacc = __builtin_fmaf(in[k], w[k], sacc);
       }
-#pragma unroll
+#pragma unroll      // wave_sum<32>'s statements, kept in place: the headline's forward prologue
       for (int o = 16; o > 0; o >>= 1) sacc += __shfl_xor(sacc, o, 32);
       if (l == 0) {
         const float t = sacc + a.th_b[j];

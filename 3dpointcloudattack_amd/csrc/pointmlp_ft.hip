@@ -365,12 +365,7 @@ __global__ __launch_bounds__(256) void ft_tower_bwd_kernel(FTBwdArgs a) {
   if (tid < PM_BTP) s_m1[tid] = ld_m1, s_mA[tid] = ld_mA;
   for (int i = tid; i < PM_BTP * PM_LD2; i += 256) g2s[i] = 0.f;
   int packed = cnt0 | (cnt1 << 16);
-  int incl = packed;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int v = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += v;
-  }
+  const int incl = wave_incl_scan(packed, lane);
   if (lane == 63) s_scan[wave] = incl;
   __syncthreads();
   int base = 0, total = 0;

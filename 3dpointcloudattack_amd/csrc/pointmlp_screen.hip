@@ -368,7 +368,7 @@ __global__ __launch_bounds__(PM_FT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
       return;
     }
     if (DBG && d.stats != nullptr) {
-#pragma unroll
+#pragma unroll      // wave_sum's statements, kept in place like the scan below
       for (int o = 32; o > 0; o >>= 1) ncand += __shfl_xor(ncand, o, 64);
       if (lane == 0) {
         int32_t* st = d.stats + ((int64_t)b * a.ntiles + tile) * 2;
@@ -505,7 +505,7 @@ __global__ __launch_bounds__(PM_FT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
       pms_flags(acc, s_na, cw, h, L, flags);
       flags[0] &= vmask[0], flags[1] &= vmask[1];
       const int cnt = __builtin_popcount(flags[0]) + __builtin_popcount(flags[1]);
-      int incl = cnt;
+      int incl = cnt;      // wave_incl_scan's statements, kept in place: the headline's forward
 #pragma unroll
       for (int o = 1; o < 64; o <<= 1) {
         const int v = __shfl_up(incl, o, 64);

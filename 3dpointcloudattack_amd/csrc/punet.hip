@@ -99,14 +99,6 @@ __device__ __forceinline__ float4 masked_g(const float* __restrict__ g, const fl
   return v;
 }
 
-__device__ __forceinline__ float sum16(float v) {      // over the 16 lanes of a point: the same bits in all of them
-  v += __shfl_xor(v, 8, 64);
-  v += __shfl_xor(v, 4, 64);
-  v += __shfl_xor(v, 2, 64);
-  v += __shfl_xor(v, 1, 64);
-  return v;
-}
-
 // 16 lanes per unknown point, 16 points per workgroup
 __global__ __launch_bounds__(256) void three_interp_bwd_points_kernel(InterpBwdArgs a) {
   const int b = blockIdx.y, l = threadIdx.x & 15;
@@ -130,7 +122,7 @@ __global__ __launch_bounds__(256) void three_interp_bwd_points_kernel(InterpBwdA
     }
   }
 #pragma unroll
-  for (int j = 0; j < 3; ++j) acc[j] = sum16(acc[j]);
+  for (int j = 0; j < 3; ++j) acc[j] = wave_sum<16>(acc[j]);      // over the 16 lanes of a point
   if (l != 0 || !valid) return;
   float w[3], r[3], s;
   interp_weights(a.d + row * 3, w, r, s);

@@ -1026,7 +1026,7 @@ __global__ __launch_bounds__(SP_T) void sa_unit_pack_kernel(const uint8_t* __res
       }
     }
   }
-  int incl = tiles;
+  int incl = tiles;      // wave_incl_scan's statements, kept in place (the call adds an instruction)
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {
     const int up = __shfl_up(incl, d, 64);

@@ -64,12 +64,7 @@ __global__ __launch_bounds__(256) void affine3_bwd_kernel(const float* __restric
       ax = __builtin_fmaf(v.w, c.y, ax), ay = __builtin_fmaf(v.w, c.z, ay), az = __builtin_fmaf(v.w, c.w, az);
     }
   }
-#pragma unroll
-  for (int d = L >> 1; d >= 1; d >>= 1) {
-    ax += __shfl_xor(ax, d, 64);
-    ay += __shfl_xor(ay, d, 64);
-    az += __shfl_xor(az, d, 64);
-  }
+  ax = wave_sum<L>(ax), ay = wave_sum<L>(ay), az = wave_sum<L>(az);
   if (live && l == 0) {
     const int64_t b = row / N, n = row - b * N;
     float rx = sign * ax, ry = sign * ay, rz = sign * az;

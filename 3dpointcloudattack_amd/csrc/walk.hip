@@ -97,19 +97,8 @@ __device__ __forceinline__ float walk_score(const WalkArgs& a, const float (&nb)
 }
 
 // A curve is walked by a GROUP of G lanes (one candidate neighbour per lane): G = 32 puts two curves in a wavefront
-// (k <= 32 and C <= 32: CurveNet's k = 20, C = 16 / 32), G = 64 one. Reductions stay inside the group.
-template <int G>
-__device__ __forceinline__ float group_max(float v) {
-#pragma unroll
-  for (int o = G / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-template <int G>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
+// (k <= 32 and C <= 32: CurveNet's k = 20, C = 16 / 32), G = 64 one. Reductions stay inside the group
+// (wave_max<G>, wave_sum<G>).
 // lowest set lane of this group's slice of a wave ballot, 0 if none
 template <int G>
 __device__ __forceinline__ int group_first(unsigned long long bal, int sub) {
@@ -175,10 +164,10 @@ __global__ __launch_bounds__(kWalkWaves * 64) void curve_walk_fwd_step_kernel(Wa
   float d;
   float sc = walk_score<C>(a, nb, pre, cur, s == 0, &d);
   sc = act ? sc : -INFINITY;
-  const float mx = group_max<G>(sc);
+  const float mx = wave_max<G>(sc);
   const float e = act ? expf(sc - mx) : 0.f;
-  const float y = e / group_sum<G>(e);
-  const float ymax = group_max<G>(y);
+  const float y = e / wave_sum<G>(e);
+  const float ymax = wave_max<G>(y);
   const int jstar = group_first<G>(__ballot(act && y == ymax), sub);  // lowest slot on ties
   const int next = __shfl(idx, sub * G + jstar, 64);
   wave_lds_sync();  // every lane has read cur / pre before cur is replaced
@@ -198,7 +187,7 @@ __global__ __launch_bounds__(kWalkWaves * 64) void curve_walk_fwd_step_kernel(Wa
       p0 = a.mw[gl] * cv + a.mw[C + gl] * pv;
       p1 = a.mw[2 * C + gl] * cv + a.mw[3 * C + gl] * pv;
     }
-    const float z0 = group_sum<G>(p0) + a.mb[0], z1 = group_sum<G>(p1) + a.mb[1];
+    const float z0 = wave_sum<G>(p0) + a.mb[0], z1 = wave_sum<G>(p1) + a.mb[1];
     const float zm = fmaxf(z0, z1), e0 = expf(z0 - zm), e1 = expf(z1 - zm), es = e0 + e1;
     if (valid && gl == 0) {
       a.mom[(o + 1) * 2] = e0 / es, a.mom[(o + 1) * 2 + 1] = e1 / es;
@@ -263,14 +252,14 @@ __global__ __launch_bounds__(kWalkWaves * 64) void curve_walk_bwd_step_kernel(Wa
   float d;
   float sc = walk_score<C>(a, nb, pre, curp, s == 0, &d);
   sc = act ? sc : -INFINITY;
-  const float mx = group_max<G>(sc);
+  const float mx = wave_max<G>(sc);
   const float e = act ? expf(sc - mx) : 0.f;
-  const float y = e / group_sum<G>(e);
+  const float y = e / wave_sum<G>(e);
   // cur = sum_j nb_j * (hard_j + y_j - stopgrad(y_j)):  d/d nb_j = hard_j,  d/d y_j = nb_j
   float gy = 0.f;
 #pragma unroll
   for (int ch = 0; ch < C; ++ch) gy += Gc[ch] * nb[ch];
-  const float t = group_sum<G>(act ? y * gy : 0.f);
+  const float t = wave_sum<G>(act ? y * gy : 0.f);
   const float gsc = act ? y * (gy - t) * d : 0.f;  // softmax backward, then through the (constant) factor d
   const int prow = __shfl(idx, sub * G + jstar, 64);
   const long rrec = (long)b * cn * (a.L + 1) + (long)cc * a.L + s;      // this (curve, step)'s row record
@@ -285,13 +274,13 @@ __global__ __launch_bounds__(kWalkWaves * 64) void curve_walk_bwd_step_kernel(Wa
     if (valid && act) atomicAdd(coef + idx, gsc);
     if (valid && gl < C) atomicAdd(gF + (long)prow * C + gl, gc_l);
   }
-  const float S = group_sum<G>(gsc);
+  const float S = wave_sum<G>(gsc);
   float gp = 0.f;
   if (gl < C) gp = gp_l + S * a.aw[C + gl];  // total gradient with respect to pre_s
   if (s > 0) {
     // pre_s = cur_{s-1} m0 + pre_{s-1} m1 with (m0, m1) = entries 2c, 2c+1 of the flattened [2,cn] softmax array
     const float* pp = a.pre + (o - 1) * C;
-    const float g0 = group_sum<G>(gl < C ? gp * curp[gl] : 0.f), g1 = group_sum<G>(gl < C ? gp * pp[gl] : 0.f);
+    const float g0 = wave_sum<G>(gl < C ? gp * curp[gl] : 0.f), g1 = wave_sum<G>(gl < C ? gp * pp[gl] : 0.f);
     float m0, m1;
     walk_momentum(a, b, cc, s, &m0, &m1);
     if (valid && gl == 0) gMw[2 * cc] = g0, gMw[2 * cc + 1] = g1;

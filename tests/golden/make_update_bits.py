@@ -24,12 +24,13 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))      # the repository
 import update_bits_cases as ubc  # noqa: E402
 
 
-def main():
-    out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(HERE, "update_bits.npz")
+def main(cases=ubc, name="update_bits.npz"):
+    """Record the ENTRIES of `cases` (a module like update_bits_cases; make_wave_bits.py passes wave_bits_cases)."""
+    out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(HERE, name)
     ops = importlib.import_module("3dpointcloudattack_amd.ops")
     dev = torch.device("cuda:0")
     rec = {}
-    for entry, fn in ubc.ENTRIES.items():
+    for entry, fn in cases.ENTRIES.items():
         first, second = fn(ops, dev), fn(ops, dev)
         torch.cuda.synchronize()
         for key, t in first.items():
