@@ -452,30 +452,34 @@ __global__ __launch_bounds__(256) void pointmlp3_max_bwd_twolist_kernel(PMBwdArg
 constexpr int PM_BSEG = 8;           // list segments (of 32 lanes = 32 bins each) of the counting sort
 constexpr int PM_BFLY = 32;          // W3 rows in flight per wave
 
-// phase C of both backward kernels: g1 = (g2 masked) . W2 on MFMA, K split over wave pairs, layer-1 mask applied
+// phase C of the backward kernels: g1 = (g2 masked) . W2 on MFMA, K split over wave pairs, layer-1 mask applied.
+// One call = one block of 32 rows of g2s / h1s / s_m1 and four waves (wave = 0..3). live: false for a group of waves
+// that has no row block left (the packed form); it then only keeps the barriers.
 __device__ __forceinline__ void pm_bwd_phase_c(const float4 (&w2tr)[PM_C2 / 16], float* g2s, float* h1s,
-                                               const uint64_t* s_m1, int wave, int r, int h) {
+                                               const uint64_t* s_m1, int wave, int r, int h, bool live = true) {
   f32x16 acc;
 #pragma unroll
   for (int e = 0; e < 16; ++e) acc[e] = 0.f;
   const int jb = wave & 1, kh = wave >> 1;
+  if (live) {
 #pragma unroll
-  for (int t = 0; t < PM_C2 / 16; ++t) {
-    const float4 bw = w2tr[t];
-    const float4 av = *reinterpret_cast<const float4*>(g2s + r * PM_LD2 + 64 * kh + 8 * t + 4 * h);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bw.x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bw.y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bw.z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bw.w, acc, 0, 0, 0);
+    for (int t = 0; t < PM_C2 / 16; ++t) {
+      const float4 bw = w2tr[t];
+      const float4 av = *reinterpret_cast<const float4*>(g2s + r * PM_LD2 + 64 * kh + 8 * t + 4 * h);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bw.x, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bw.y, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bw.z, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bw.w, acc, 0, 0, 0);
+    }
   }
   __syncthreads();   // g2s is dead once every wave has read its A operands: it doubles as the exchange buffer
   float* cr = g2s + jb * (32 * 33);
-  if (kh == 1) {
+  if (live && kh == 1) {
 #pragma unroll
     for (int e = 0; e < 16; ++e) cr[((e & 3) + 8 * (e >> 2) + 4 * h) * 33 + r] = acc[e];
   }
   __syncthreads();
-  if (kh == 0) {
+  if (live && kh == 0) {
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const int pt = (e & 3) + 8 * (e >> 2) + 4 * h;
@@ -485,18 +489,21 @@ __device__ __forceinline__ void pm_bwd_phase_c(const float4 (&w2tr)[PM_C2 / 16],
   }
 }
 
-// a finished point's row: layer-2 ReLU of the forward pass, one store (lane = k 2*lane, 2*lane + 1)
-__device__ __forceinline__ void pm_bwd_put_row(const uint32_t (*s_m2)[4], float* g2s, int pt, int lane, float2 acc) {
+// a finished point's row: layer-2 ReLU of the forward pass, one store (lane = k 2*lane, 2*lane + 1).
+// key = an entry >> 10: the point itself or, in the packed form, (row slot << 7 | point)
+template <bool PACKED>
+__device__ __forceinline__ void pm_bwd_put_row(const uint32_t (*s_m2)[4], float* g2s, int key, int lane, float2 acc) {
+  const int pt = PACKED ? (key & 127) : key, row = PACKED ? (key >> 7) : key;
   const uint32_t m = s_m2[pt][lane >> 4] >> ((2 * lane) & 31);
   float2 o;
   o.x = (m & 1u) ? acc.x : 0.f, o.y = (m & 2u) ? acc.y : 0.f;
-  *reinterpret_cast<float2*>(g2s + pt * PM_LD2 + 2 * lane) = o;
+  *reinterpret_cast<float2*>(g2s + row * PM_LD2 + 2 * lane) = o;
 }
 
 // NB entries of the wave's current chunk, from entry u on: lane s of my_e / my_g holds entry s (point << 10 | channel)
 // and its gradient; nb = entries in the chunk. TAIL: the batch may reach past nb (entries at or past nb repeat the
 // last one and are not accumulated). Everything but the row loads and the FMAs is scalar.
-template <int NB, bool TAIL>
+template <int NB, bool TAIL, bool PACKED = false>
 __device__ __forceinline__ void pm_bwd_rows(const float* W3, int my_e, int my_g, const uint32_t (*s_m2)[4], float* g2s,
                                             int u, int nb, int lane, float2& acc, int& cur) {
   int e[NB];
@@ -513,7 +520,7 @@ __device__ __forceinline__ void pm_bwd_rows(const float* W3, int my_e, int my_g,
       const float gv = __builtin_bit_cast(float, __builtin_amdgcn_readlane(my_g, u + t));
       const int n = e[t] >> 10;
       if (__builtin_expect(n != cur, 0)) {
-        if (cur >= 0) pm_bwd_put_row(s_m2, g2s, cur, lane, acc);
+        if (cur >= 0) pm_bwd_put_row<PACKED>(s_m2, g2s, cur, lane, acc);
         acc = make_float2(0.f, 0.f);
         cur = n;
       }
@@ -541,19 +548,22 @@ struct PMUpdArgs {
 };
 constexpr int PM_UPD_LD = 3 * PM_BTP;   // parked operands: [p, ori, m, v, ori[nn]][coordinate][point] + 4 per-sample words
 
-// lane p of wave 0: point n = n0 + p with its whole input gradient (g0, g1, g2)
+// the lane of point n = n0 + p (p = its index among the workgroup's TPTS points) with its whole input gradient
+// (g0, g1, g2); s_u = the operands parked at entry, [5][3][TPTS] + 4 per-sample words
+template <int TPTS = PM_BTP>
 __device__ __forceinline__ void pm_bwd_update_point(const PMUpdArgs& u, const float* s_u, int N, int b, int n, int p,
                                                     float g0, float g1, float g2) {
-  const float* s_uc = s_u + 5 * PM_UPD_LD;
+  constexpr int LD = 3 * TPTS;
+  const float* s_uc = s_u + 5 * LD;
   const CwPointConsts c{u.dist_kind, u.B, N, AdamConsts{u.omb1, u.omb2, u.fb2, s_uc[2], s_uc[3], u.eps}, u.budget};
   float pin[3], oin[3], m[3], v[3], q[3], np_[3], g[3] = {g0, g1, g2};
 #pragma unroll
   for (int e = 0; e < 3; ++e) {
-    pin[e] = s_u[0 * PM_UPD_LD + e * PM_BTP + p];
-    oin[e] = s_u[1 * PM_UPD_LD + e * PM_BTP + p];
-    m[e] = s_u[2 * PM_UPD_LD + e * PM_BTP + p];
-    v[e] = s_u[3 * PM_UPD_LD + e * PM_BTP + p];
-    q[e] = s_u[4 * PM_UPD_LD + e * PM_BTP + p];
+    pin[e] = s_u[0 * LD + e * TPTS + p];
+    oin[e] = s_u[1 * LD + e * TPTS + p];
+    m[e] = s_u[2 * LD + e * TPTS + p];
+    v[e] = s_u[3 * LD + e * TPTS + p];
+    q[e] = s_u[4 * LD + e * TPTS + p];
   }
   cw_point_update(c, pin, oin, g, q, s_uc[0], s_uc[1], m, v, np_);
   const int64_t off = (int64_t)b * u.adv.bs + (int64_t)n * u.adv.ps;
@@ -798,7 +808,7 @@ __device__ __forceinline__ void pm_bwd_body(const PMBwdArgs& a, const PMUpdArgs&
         for (; u < nb; u += 4) pm_bwd_rows<4, true>(a.W3, my_e, my_g, s_m2, g2s, u, nb, lane, acc, cur);
         i += nb;
       }
-      pm_bwd_put_row(s_m2, g2s, cur, lane, acc);
+      pm_bwd_put_row<false>(s_m2, g2s, cur, lane, acc);
     }
   }
   __syncthreads();   // also: the sort's counters in h1s are dead
@@ -877,6 +887,347 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void pointmlp3_max_bwd_update_kernel(PMBwdArgs a,
                                                                                                                    PMUpdArgs u) {
   pm_bwd_body<true>(a, u);
+}
+
+// The packed form. A workgroup owns PM_PTP = 128 consecutive points of one cloud (8 waves; one workgroup per CU at
+// B = 32, N = 1024), so argidx / g are classified and the W2 operand is fetched once per 128 points instead of once per
+// 32, and phase C multiplies LIVE rows only: a point with at least one hit gets a row slot — its rank among the
+// tile's live points in ascending point order — and g2s / h1s hold slots, not points. MFMA rows are independent, so a
+// live row's g1 has the bits it has in pm_bwd_body; a dead point's g' is +0 there (a zero g2 row gives +0
+// accumulators, and the W1 chains start from +0) and is set to +0 here. The hits (g == 0 dropped), a point's chain,
+// the masks and phase D are pm_bwd_body's; the eight waves share out whole points by position in the sorted list, as its
+// four do. Only the sort is another one: the stable counting sort, carried over with 4 segments x 128 bins, was the
+// longest phase (6.3 of 19.7 us: a thread walks a quarter of a list four times as long), so the list ordered by
+// (point, channel) is read off a [128][1024]-bit map instead (2.3 us) — same list, entry = (slot << 17 | point << 10 |
+// channel). From g' on the statements are pm_bwd_body's per 32-point sub-tile (wave s = sub-tile s, each point on the
+// lane it has there), a sub-tile without a hit takes that kernel's early exit (its stores are exact +0, which the
+// chain through T does not give for a negative T entry), and part_gT keeps one 16-word record per 32 points.
+// STOP: 0, or the phase after which the launch ends (tools/bench_pointmlp.py's phase table; production is STOP = 0).
+constexpr int PM_PTP = 128;                  // points per workgroup
+constexpr int PM_PNT = 512;                  // threads per workgroup
+constexpr int PM_PTQ = PM_PNT / PM_PTP;      // threads per point of the sort (each a quarter of the point's bitmap row)
+constexpr int PM_PSUB = PM_PTP / PM_BTP;     // 32-point sub-tiles
+
+// end of a truncated launch (timing only, outputs are not written): a store behind a test of what the phases left in
+// LDS keeps them from being dropped as dead code
+__device__ __forceinline__ void pm_bwdp_stop(const PMBwdArgs& a, const float* lds_word) {
+  if (threadIdx.x == 0 && __builtin_bit_cast(uint32_t, *lds_word) == 0x7fc12345u) a.gx.p[(int64_t)blockIdx.y * a.gx.bs] = 0.f;
+}
+
+template <bool UPD, int STOP>
+__device__ __forceinline__ void pm_bwdp_body(const PMBwdArgs& a, const PMUpdArgs& u) {
+  constexpr int TP = PM_PTP, NT = PM_PNT, NW = PM_PNT / 64, CPT = PM_MAXC3 / PM_PNT;
+  __shared__ __attribute__((aligned(16))) float g2s[TP * PM_LD2];   // [slot][132]  67.6 KB: every point may be live
+  __shared__ __attribute__((aligned(16))) float h1s[TP * PM_LD1];   // [slot][68]   g1; before that the sort's counters
+  __shared__ float s_g[PM_MAXC3];
+  __shared__ uint32_t s_sorted[PM_MAXC3];      // (slot << 17 | point << 10 | channel), by (point, channel)
+  __shared__ uint32_t s_m2[TP][4];
+  __shared__ uint64_t s_m1[TP], s_m1r[TP];     // layer-1 masks by point, and by row slot
+  __shared__ unsigned char s_pt[TP];           // point of a row slot
+  __shared__ float s_W1[PM_C1 * 3];
+  __shared__ float s_x[3 * TP], s_gxo[3 * TP], s_gp[3 * TP], s_T[12];
+  __shared__ int s_scan[NW], s_live[NW], s_wbeg[NW], s_wend[NW];
+  __shared__ float s_u[UPD ? 5 * 3 * TP + 4 : 1];
+  uint32_t* s_bits = reinterpret_cast<uint32_t*>(h1s);            // [128][32] bit c of row p: channel c hits point p
+  int* s_start = reinterpret_cast<int*>(s_bits + TP * (PM_MAXC3 / 32));   // [129] offset of point p in the sorted list
+  static_assert(PM_MAXC3 <= 1024 && PM_PTP <= 128, "a sorted entry is slot << 17 | point << 10 | channel, a key slot << 7 | point");
+  static_assert(CPT * PM_PNT == PM_MAXC3 && 3 * PM_PTP + 9 <= PM_PNT, "thread shares of the entry loads");
+  static_assert(PM_PTQ == 4 && PM_MAXC3 / 32 == 8 * PM_PTQ, "four threads per bitmap row, eight words (two uint4) each");
+  static_assert(TP * (PM_MAXC3 / 32) + TP + 1 <= TP * PM_LD1, "bitmap and offsets alias h1s");
+  const int tile = blockIdx.x, b = blockIdx.y;
+  const int n0 = tile * TP;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 31, h = lane >> 5;
+  const int pp = tid & (TP - 1), pc = tid >> 7;   // tid < 3 * TP: (point, coordinate) of the per-point operands
+
+  // ---- entry: every load that depends on nothing, smallest first (as pm_bwd_body)
+  float ld_u[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  if (UPD) {
+    if (tid < 3 * TP) {
+      if (n0 + pp < a.N) {
+        const int64_t off = (int64_t)b * u.adv.bs + (int64_t)(n0 + pp) * u.adv.ps + pc * u.adv.cs;
+        const float* ob = u.ori.p + (int64_t)b * u.ori.bs + pc * u.ori.cs;
+        const int j = (u.dist_kind == 2) ? u.nn_idx[(int64_t)b * a.N + n0 + pp] : 0;
+        ld_u[0] = u.adv.p[off];
+        ld_u[1] = ob[(int64_t)(n0 + pp) * u.ori.ps];
+        ld_u[2] = u.m[off];
+        ld_u[3] = u.v[off];
+        if (u.dist_kind == 2) ld_u[4] = ob[(int64_t)j * u.ori.ps];
+      }
+    } else if (tid < 3 * TP + 4) {
+      const int e = tid - 3 * TP;
+      if (e == 0) ld_u[0] = u.w ? u.w[b] : 0.f;
+      else if (e == 1) ld_u[0] = u.dist_val ? u.dist_val[b] : 0.f;
+      else ld_u[0] = u.adam[e - 2];
+    }
+  }
+  int ld_n[CPT];
+  float ld_g[CPT];
+#pragma unroll
+  for (int e = 0; e < CPT; ++e) {
+    const int c = tid * CPT + e;
+    ld_n[e] = (c < a.C3) ? a.argidx[(int64_t)b * a.C3 + c] : -1;
+    ld_g[e] = (c < a.C3) ? a.g[(int64_t)b * a.C3 + c] : 0.f;
+  }
+  uint32_t ld_m2 = 0u;
+  uint64_t ld_m1 = 0ull;
+  if (n0 + (tid >> 2) < a.N) ld_m2 = a.mask2[((int64_t)b * a.N + n0) * 4 + tid];
+  if (tid < TP && n0 + tid < a.N) ld_m1 = a.mask1[(int64_t)b * a.N + n0 + tid];
+  const bool want_gT = a.T != nullptr && a.part_gT != nullptr;
+  float ld_w1 = 0.f, ld_px = 0.f, ld_t = 0.f;
+  if (tid < PM_C1 * 3) ld_w1 = a.W1[tid];
+  if (tid < 3 * TP) {
+    if (n0 + pp < a.N) {
+      if (want_gT) ld_px = a.x.p[(int64_t)b * a.x.bs + (int64_t)(n0 + pp) * a.x.ps + pc * a.x.cs];
+      if (a.accumulate) ld_t = a.gx.p[(int64_t)b * a.gx.bs + (int64_t)(n0 + pp) * a.gx.ps + pc * a.gx.cs];
+    }
+  } else if (tid < 3 * TP + 9 && a.T) {
+    ld_t = a.T[(int64_t)b * 9 + tid - 3 * TP];
+  }
+  // MFMA B operand of phase C, once per 128 points: waves w and w + 4 hold the same (j block w&1, K half (w&3)>>1)
+  const int cw = wave & 3;
+  float4 w2tr[PM_C2 / 16];
+  {
+    const float* wcol = a.W2 + (64 * (cw >> 1) + 4 * h) * PM_C1 + 32 * (cw & 1) + r;
+#pragma unroll
+    for (int t = 0; t < PM_C2 / 16; ++t) {
+      w2tr[t].x = wcol[(8 * t + 0) * PM_C1];
+      w2tr[t].y = wcol[(8 * t + 1) * PM_C1];
+      w2tr[t].z = wcol[(8 * t + 2) * PM_C1];
+      w2tr[t].w = wcol[(8 * t + 3) * PM_C1];
+    }
+  }
+
+  // ---- A1. classify 2 consecutive channels per thread. The sort by (point, channel) goes through a bitmap: a hit
+  // sets bit `channel` of row `point` (an atomic OR: the result does not depend on the order), and reading the rows in
+  // order gives every point's channels ascending. Thread t owns words 8t..8t+7: quarter t & 3 of the row of point t >> 2.
+  reinterpret_cast<uint4*>(s_bits)[2 * tid] = make_uint4(0u, 0u, 0u, 0u);
+  reinterpret_cast<uint4*>(s_bits)[2 * tid + 1] = make_uint4(0u, 0u, 0u, 0u);
+  int myn[CPT];
+#pragma unroll
+  for (int e = 0; e < CPT; ++e) {
+    const int c = tid * CPT + e;
+    int n = -1;
+    if (c < a.C3) {
+      n = ld_n[e] - n0;
+      const float gv = ld_g[e];
+      if (n < 0 || n >= TP || gv == 0.f) n = -1;
+      s_g[c] = gv;
+    }
+    myn[e] = n;
+  }
+  s_m2[tid >> 2][tid & 3] = ld_m2;
+  if (tid < TP) s_m1[tid] = ld_m1;
+  if (tid < PM_C1 * 3) s_W1[tid] = ld_w1;
+  if (tid < 3 * TP) {
+    s_x[tid] = ld_px;
+    s_gxo[tid] = ld_t;
+    s_gp[tid] = 0.f;   // g' of a point without a hit
+  } else if (tid < 3 * TP + 9) {
+    s_T[tid - 3 * TP] = ld_t;
+  }
+  if (tid < NW) s_wbeg[tid] = PM_MAXC3, s_wend[tid] = 0;
+  if (UPD) {
+    if (tid < 3 * TP) {
+#pragma unroll
+      for (int e = 0; e < 5; ++e) s_u[e * 3 * TP + tid] = ld_u[e];
+    } else if (tid < 3 * TP + 4) {
+      s_u[5 * 3 * TP + tid - 3 * TP] = ld_u[0];
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int e = 0; e < CPT; ++e) {
+    const int c = tid * CPT + e;
+    if (myn[e] >= 0) atomicOr(&s_bits[myn[e] * (PM_MAXC3 / 32) + (c >> 5)], 1u << (c & 31));
+  }
+  __syncthreads();
+  uint32_t wd[8];   // this thread's eight words
+  {
+    const uint4 wa = reinterpret_cast<const uint4*>(s_bits)[2 * tid], wb = reinterpret_cast<const uint4*>(s_bits)[2 * tid + 1];
+    wd[0] = wa.x, wd[1] = wa.y, wd[2] = wa.z, wd[3] = wa.w, wd[4] = wb.x, wd[5] = wb.y, wd[6] = wb.z, wd[7] = wb.w;
+  }
+  int cnt = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) cnt += __builtin_popcount(wd[k]);
+  int incl = cnt;   // the sorted list in thread order: an inclusive scan of the counts gives every thread its offset
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int v = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += v;
+  }
+  int p_tot = cnt;  // hits of the point, in all four of its lanes
+  p_tot += __shfl_xor(p_tot, 1, 64);
+  p_tot += __shfl_xor(p_tot, 2, 64);
+  // live points of this wave (one bit per point, at its first lane); a point's row slot = live points in front of it
+  const uint64_t lv = __builtin_amdgcn_ballot_w64(p_tot > 0 && (lane & 3) == 0);
+  if (lane == 63) s_scan[wave] = incl, s_live[wave] = __builtin_popcountll(lv);
+  __syncthreads();
+  int base = 0, L = 0, slot = __builtin_popcountll(lv & ((1ull << (lane & ~3)) - 1ull)), nlive = 0;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) {
+    const int v = s_scan[w], q = s_live[w];
+    if (w < wave) base += v, slot += q;
+    L += v;
+    nlive += q;
+  }
+  int subL = 0;   // waves 0..3: hits in sub-tile `wave`
+  if (L > 0) {
+    if (STOP == 1) return pm_bwdp_stop(a, reinterpret_cast<const float*>(s_scan));
+    {
+      const int pt = tid >> 2;
+      int o = base + incl - cnt;
+      const int p_start = __shfl(o, lane & ~3, 64);
+      if ((lane & 3) == 0) {
+        s_start[pt] = p_start;
+        if (tid == 0) s_start[TP] = L;
+        if (p_tot > 0) {
+          s_pt[slot] = (unsigned char)pt;
+          s_m1r[slot] = s_m1[pt];
+          // A2: point p belongs to wave floor(8 * start[p] / L); a wave's points are consecutive in the sorted list
+          int owner = 0;
+#pragma unroll
+          for (int q = 1; q < NW; ++q) owner += (p_start * NW >= q * L) ? 1 : 0;
+          atomicMin(&s_wbeg[owner], p_start);
+          atomicMax(&s_wend[owner], p_start + p_tot);
+        }
+      }
+      const uint32_t key = ((uint32_t)slot << 17) | ((uint32_t)pt << 10) | (uint32_t)(256 * (tid & 3));
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        for (uint32_t wv = wd[k]; wv != 0u; wv &= wv - 1u) s_sorted[o++] = key | (uint32_t)(32 * k + __builtin_ctz(wv));
+    }
+    __syncthreads();
+    if (wave < PM_PSUB) subL = s_start[PM_BTP * (wave + 1)] - s_start[PM_BTP * wave];
+    if (STOP == 2) return pm_bwdp_stop(a, reinterpret_cast<const float*>(s_sorted));
+    const int nblk = (nlive + 31) >> 5;
+    for (int i = nlive * PM_LD2 + tid; i < nblk * 32 * PM_LD2; i += NT) g2s[i] = 0.f;   // the last block's spare rows
+
+    // ---- the gather: pm_bwd_body's walk over this wave's points
+    {
+      int i = __builtin_amdgcn_readfirstlane(s_wbeg[wave]);
+      const int end = __builtin_amdgcn_readfirstlane(s_wend[wave]);
+      if (i < end) {
+        float2 acc = make_float2(0.f, 0.f);
+        int cur = -1;
+        while (i < end) {
+          const int nb = end - i < 64 ? end - i : 64;
+          const int my_e = (int)s_sorted[i + (lane < nb ? lane : nb - 1)];
+          const int my_g = __builtin_bit_cast(int, s_g[my_e & (PM_MAXC3 - 1)]);
+          int q = 0;
+          for (; q + PM_BFLY <= nb; q += PM_BFLY) pm_bwd_rows<PM_BFLY, false, true>(a.W3, my_e, my_g, s_m2, g2s, q, nb, lane, acc, cur);
+          if (q + 16 <= nb) {
+            pm_bwd_rows<16, false, true>(a.W3, my_e, my_g, s_m2, g2s, q, nb, lane, acc, cur);
+            q += 16;
+          }
+          if (q + 8 <= nb) {
+            pm_bwd_rows<8, false, true>(a.W3, my_e, my_g, s_m2, g2s, q, nb, lane, acc, cur);
+            q += 8;
+          }
+          for (; q < nb; q += 4) pm_bwd_rows<4, true, true>(a.W3, my_e, my_g, s_m2, g2s, q, nb, lane, acc, cur);
+          i += nb;
+        }
+        pm_bwd_put_row<true>(s_m2, g2s, cur, lane, acc);
+      }
+    }
+    __syncthreads();   // also: the sort's counters in h1s are dead
+    if (STOP == 3) return pm_bwdp_stop(a, g2s);
+
+    // ---- C. ceil(live / 32) row blocks, two at a time: waves 0..3 take block 2i, waves 4..7 block 2i + 1
+    for (int i = 0; 2 * i < nblk; ++i) {
+      const int rb = 2 * i + (wave >> 2);
+      pm_bwd_phase_c(w2tr, g2s + rb * 32 * PM_LD2, h1s + rb * 32 * PM_LD1, s_m1r + rb * 32, cw, r, h, rb < nblk);
+      __syncthreads();
+    }
+    if (STOP == 4) return pm_bwdp_stop(a, h1s);
+
+    // ---- D. g' of the live rows, placed at the point's position (thread = (coordinate, row slot))
+    if (tid < 3 * TP && pp < nlive) {
+      const int c = pc;
+      float sa = 0.f, sb = 0.f;
+#pragma unroll
+      for (int j = 0; j < PM_C1; j += 4) {
+        const float4 hv = *reinterpret_cast<const float4*>(h1s + pp * PM_LD1 + j);
+        sa = __builtin_fmaf(s_W1[j * 3 + c], hv.x, sa);
+        sb = __builtin_fmaf(s_W1[(j + 1) * 3 + c], hv.y, sb);
+        sa = __builtin_fmaf(s_W1[(j + 2) * 3 + c], hv.z, sa);
+        sb = __builtin_fmaf(s_W1[(j + 3) * 3 + c], hv.w, sb);
+      }
+      s_gp[c * TP + s_pt[pp]] = sa + sb;
+    }
+    __syncthreads();
+    if (STOP == 5) return pm_bwdp_stop(a, s_gp);
+  }
+
+  // ---- the chain through T, the dT partial and the stores, per 32-point sub-tile as pm_bwd_body has them
+  const int ns = n0 + PM_BTP * wave;   // first point of this wave's sub-tile
+  if (wave >= PM_PSUB || ns >= a.N) return;
+  const int64_t rec = ((int64_t)b * ((a.N + PM_BTP - 1) / PM_BTP) + tile * PM_PSUB + wave) * 16;
+  const int p = lane & (PM_BTP - 1);
+  const int q = PM_BTP * wave + p;     // the point's index in the workgroup's tile
+  const bool live = lane < PM_BTP;
+  if (subL == 0) {   // no critical point in this sub-tile: gradient is exactly zero
+    if (UPD && live && ns + p < a.N)
+      pm_bwd_update_point<TP>(u, s_u, a.N, b, ns + p, q, s_gxo[q], s_gxo[TP + q], s_gxo[2 * TP + q]);
+    if (!a.accumulate && live && ns + p < a.N) {
+      float* o = a.gx.p + (int64_t)b * a.gx.bs + (int64_t)(ns + p) * a.gx.ps;
+      o[0] = 0.f, o[a.gx.cs] = 0.f, o[2 * a.gx.cs] = 0.f;
+    }
+    if (a.part_gT && lane < 16) a.part_gT[rec + lane] = 0.f;
+    return;
+  }
+  const float g0 = live ? s_gp[q] : 0.f, g1v = live ? s_gp[TP + q] : 0.f, g2v = live ? s_gp[2 * TP + q] : 0.f;
+  float o0 = g0, o1 = g1v, o2 = g2v;
+  if (a.T) {
+    const float* t = s_T;
+    o0 = __builtin_fmaf(g2v, t[2], __builtin_fmaf(g1v, t[1], g0 * t[0]));
+    o1 = __builtin_fmaf(g2v, t[5], __builtin_fmaf(g1v, t[4], g0 * t[3]));
+    o2 = __builtin_fmaf(g2v, t[8], __builtin_fmaf(g1v, t[7], g0 * t[6]));
+    if (a.part_gT) {
+      float xr[3] = {0.f, 0.f, 0.f};
+      if (live) xr[0] = s_x[q], xr[1] = s_x[TP + q], xr[2] = s_x[2 * TP + q];   // zeros past N
+      const float gv[3] = {g0, g1v, g2v};
+      float sum[9];
+#pragma unroll
+      for (int j = 0; j < 9; ++j) sum[j] = xr[j / 3] * gv[j % 3];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        float other[9];
+#pragma unroll
+        for (int j = 0; j < 9; ++j) other[j] = __shfl_xor(sum[j], o, 64);
+#pragma unroll
+        for (int j = 0; j < 9; ++j) sum[j] += other[j];
+      }
+      float mine = 0.f;
+#pragma unroll
+      for (int j = 0; j < 9; ++j) mine = (lane == j) ? sum[j] : mine;
+      if (lane < 16) a.part_gT[rec + lane] = mine;
+    }
+  }
+  if (UPD) {
+    if (live && ns + p < a.N)
+      pm_bwd_update_point<TP>(u, s_u, a.N, b, ns + p, q, s_gxo[q] + o0, s_gxo[TP + q] + o1, s_gxo[2 * TP + q] + o2);
+  } else if (live && ns + p < a.N) {
+    float* o = a.gx.p + (int64_t)b * a.gx.bs + (int64_t)(ns + p) * a.gx.ps;
+    if (a.accumulate) {
+      o[0] = s_gxo[q] + o0, o[a.gx.cs] = s_gxo[TP + q] + o1, o[2 * a.gx.cs] = s_gxo[2 * TP + q] + o2;
+    } else {
+      o[0] = o0, o[a.gx.cs] = o1, o[2 * a.gx.cs] = o2;
+    }
+  }
+}
+
+__global__ __launch_bounds__(PM_PNT) __attribute__((amdgpu_waves_per_eu(2, 2))) void pointmlp3_max_bwd_packed_kernel(PMBwdArgs a) {
+  pm_bwdp_body<false, 0>(a, PMUpdArgs{});
+}
+__global__ __launch_bounds__(PM_PNT) __attribute__((amdgpu_waves_per_eu(2, 2))) void pointmlp3_max_bwd_update_packed_kernel(
+    PMBwdArgs a, PMUpdArgs u) {
+  pm_bwdp_body<true, 0>(a, u);
+}
+template <int STOP>
+__global__ __launch_bounds__(PM_PNT) __attribute__((amdgpu_waves_per_eu(2, 2))) void pointmlp3_max_bwd_packed_dbg_kernel(PMBwdArgs a) {
+  pm_bwdp_body<false, STOP>(a, PMUpdArgs{});
 }
 
 }  // namespace pc3d
@@ -1069,7 +1420,11 @@ extern "C" int pc3d_pointmlp3_max_fwd_screen_dbg_prep_f32(const float* x, int64_
                        stop_after, &q);
 }
 
-static int pm_bwd_launch(const char* who, bool twolist, const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B,
+// which kernel the default entries launch (pc3d_pointmlp3_max_bwd_f32 / _update_f32); every form stays reachable by name
+constexpr bool PM_BWD_DEFAULT_PACKED = true;
+enum PMBwdForm { PM_BWD_PACKED = 0, PM_BWD_TILE32 = 1, PM_BWD_TWOLIST = 2 };   // 10 + k: packed, ended after phase k
+
+static int pm_bwd_launch(const char* who, int form, const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B,
                          int N, const float* T, const float* W1, const float* b1, const float* W2, const float* b2,
                          const float* W3, const float* W2T, int C1, int C2, int C3, const int32_t* argidx,
                          const uint64_t* mask1, const uint32_t* mask2, const float* g_pooled, float* grad_x,
@@ -1083,10 +1438,19 @@ static int pm_bwd_launch(const char* who, bool twolist, const float* x, int64_t 
                "%s: null pointer", who);
   PMBwdArgs a{{x, x_bs, x_ps, x_cs}, N, C3, T, W1, b1, W2, b2, W3, W2T, argidx, mask1, mask2, g_pooled, {grad_x, gx_bs, gx_ps, gx_cs},
               part_gT, accumulate};
-  if (twolist)
-    hipLaunchKernelGGL(pointmlp3_max_bwd_twolist_kernel, dim3(cdiv(N, PM_BTP), B), dim3(256), 0, as_stream(stream), a);
-  else
-    hipLaunchKernelGGL(pointmlp3_max_bwd_kernel, dim3(cdiv(N, PM_BTP), B), dim3(256), 0, as_stream(stream), a);
+  const dim3 g32(cdiv(N, PM_BTP), B), gp(cdiv(N, PM_PTP), B);
+  hipStream_t st = as_stream(stream);
+  switch (form) {
+    case PM_BWD_TWOLIST: hipLaunchKernelGGL(pointmlp3_max_bwd_twolist_kernel, g32, dim3(256), 0, st, a); break;
+    case PM_BWD_TILE32: hipLaunchKernelGGL(pointmlp3_max_bwd_kernel, g32, dim3(256), 0, st, a); break;
+    case PM_BWD_PACKED: hipLaunchKernelGGL(pointmlp3_max_bwd_packed_kernel, gp, dim3(PM_PNT), 0, st, a); break;
+    case 11: hipLaunchKernelGGL(pointmlp3_max_bwd_packed_dbg_kernel<1>, gp, dim3(PM_PNT), 0, st, a); break;
+    case 12: hipLaunchKernelGGL(pointmlp3_max_bwd_packed_dbg_kernel<2>, gp, dim3(PM_PNT), 0, st, a); break;
+    case 13: hipLaunchKernelGGL(pointmlp3_max_bwd_packed_dbg_kernel<3>, gp, dim3(PM_PNT), 0, st, a); break;
+    case 14: hipLaunchKernelGGL(pointmlp3_max_bwd_packed_dbg_kernel<4>, gp, dim3(PM_PNT), 0, st, a); break;
+    case 15: hipLaunchKernelGGL(pointmlp3_max_bwd_packed_dbg_kernel<5>, gp, dim3(PM_PNT), 0, st, a); break;
+    default: PC3D_REQUIRE(false, "%s: unknown form %d", who, form);
+  }
   PC3D_LAUNCH_CHECK(who);
   return PC3D_OK;
 }
@@ -1098,8 +1462,35 @@ extern "C" int pc3d_pointmlp3_max_bwd_f32(const float* x, int64_t x_bs, int64_t 
                                           const uint32_t* mask2, const float* g_pooled, float* grad_x,
                                           int64_t gx_bs, int64_t gx_ps, int64_t gx_cs, float* part_gT,
                                           int accumulate, void* stream) {
-  return pm_bwd_launch("pc3d_pointmlp3_max_bwd_f32", false, x, x_bs, x_ps, x_cs, B, N, T, W1, b1, W2, b2, W3, W2T, C1,
-                       C2, C3, argidx, mask1, mask2, g_pooled, grad_x, gx_bs, gx_ps, gx_cs, part_gT, accumulate, stream);
+  return pm_bwd_launch("pc3d_pointmlp3_max_bwd_f32", PM_BWD_DEFAULT_PACKED ? PM_BWD_PACKED : PM_BWD_TILE32, x, x_bs,
+                       x_ps, x_cs, B, N, T, W1, b1, W2, b2, W3, W2T, C1, C2, C3, argidx, mask1, mask2, g_pooled, grad_x,
+                       gx_bs, gx_ps, gx_cs, part_gT, accumulate, stream);
+}
+
+extern "C" int pc3d_pointmlp3_max_bwd_tile32_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B,
+                                                 int N, const float* T, const float* W1, const float* b1,
+                                                 const float* W2, const float* b2, const float* W3, const float* W2T,
+                                                 int C1, int C2, int C3, const int32_t* argidx,
+                                                 const uint64_t* mask1, const uint32_t* mask2, const float* g_pooled,
+                                                 float* grad_x, int64_t gx_bs, int64_t gx_ps, int64_t gx_cs,
+                                                 float* part_gT, int accumulate, void* stream) {
+  return pm_bwd_launch("pc3d_pointmlp3_max_bwd_tile32_f32", PM_BWD_TILE32, x, x_bs, x_ps, x_cs, B, N, T, W1, b1, W2, b2,
+                       W3, W2T, C1, C2, C3, argidx, mask1, mask2, g_pooled, grad_x, gx_bs, gx_ps, gx_cs, part_gT,
+                       accumulate, stream);
+}
+
+extern "C" int pc3d_pointmlp3_max_bwd_packed_dbg_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B,
+                                                     int N, const float* T, const float* W1, const float* b1,
+                                                     const float* W2, const float* b2, const float* W3,
+                                                     const float* W2T, int C1, int C2, int C3, const int32_t* argidx,
+                                                     const uint64_t* mask1, const uint32_t* mask2,
+                                                     const float* g_pooled, float* grad_x, int64_t gx_bs, int64_t gx_ps,
+                                                     int64_t gx_cs, float* part_gT, int accumulate, int stop_after,
+                                                     void* stream) {
+  PC3D_REQUIRE(stop_after >= 0 && stop_after <= 5, "pc3d_pointmlp3_max_bwd_packed_dbg_f32: stop_after = %d", stop_after);
+  return pm_bwd_launch("pc3d_pointmlp3_max_bwd_packed_dbg_f32", stop_after ? 10 + stop_after : PM_BWD_PACKED, x, x_bs,
+                       x_ps, x_cs, B, N, T, W1, b1, W2, b2, W3, W2T, C1, C2, C3, argidx, mask1, mask2, g_pooled, grad_x,
+                       gx_bs, gx_ps, gx_cs, part_gT, accumulate, stream);
 }
 
 extern "C" int pc3d_pointmlp3_max_bwd_twolist_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B,
@@ -1109,21 +1500,19 @@ extern "C" int pc3d_pointmlp3_max_bwd_twolist_f32(const float* x, int64_t x_bs, 
                                                   const uint64_t* mask1, const uint32_t* mask2, const float* g_pooled,
                                                   float* grad_x, int64_t gx_bs, int64_t gx_ps, int64_t gx_cs,
                                                   float* part_gT, int accumulate, void* stream) {
-  return pm_bwd_launch("pc3d_pointmlp3_max_bwd_twolist_f32", true, x, x_bs, x_ps, x_cs, B, N, T, W1, b1, W2, b2, W3, W2T,
+  return pm_bwd_launch("pc3d_pointmlp3_max_bwd_twolist_f32", PM_BWD_TWOLIST, x, x_bs, x_ps, x_cs, B, N, T, W1, b1, W2, b2, W3, W2T,
                        C1, C2, C3, argidx, mask1, mask2, g_pooled, grad_x, gx_bs, gx_ps, gx_cs, part_gT, accumulate,
                        stream);
 }
 
-extern "C" int pc3d_pointmlp3_max_bwd_update_f32(float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
-                                                 const float* W1, const float* b1, const float* W2, const float* b2,
-                                                 const float* W3, const float* W2T, int C1, int C2, int C3,
-                                                 const int32_t* argidx, const uint64_t* mask1, const uint32_t* mask2,
-                                                 const float* g_pooled, const float* grad_x, int64_t gx_bs, int64_t gx_ps,
-                                                 int64_t gx_cs, const float* ori, int64_t o_bs, int64_t o_ps, int64_t o_cs,
-                                                 float* m, float* v, double beta1, double beta2, double eps, float budget,
-                                                 const float* adam, int dist_kind, const float* w, const float* dist_val,
-                                                 const int32_t* nn_idx, void* stream) {
-  const char* who = "pc3d_pointmlp3_max_bwd_update_f32";
+static int pm_bwd_update_launch(const char* who, bool packed, float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B,
+                                int N, const float* W1, const float* b1, const float* W2, const float* b2,
+                                const float* W3, const float* W2T, int C1, int C2, int C3, const int32_t* argidx,
+                                const uint64_t* mask1, const uint32_t* mask2, const float* g_pooled,
+                                const float* grad_x, int64_t gx_bs, int64_t gx_ps, int64_t gx_cs, const float* ori,
+                                int64_t o_bs, int64_t o_ps, int64_t o_cs, float* m, float* v, double beta1, double beta2,
+                                double eps, float budget, const float* adam, int dist_kind, const float* w,
+                                const float* dist_val, const int32_t* nn_idx, void* stream) {
   PC3D_REQUIRE(B >= 0 && N >= 1, "%s: bad sizes B=%d N=%d", who, B, N);
   PC3D_REQUIRE(C1 == PM_C1 && C2 == PM_C2 && C3 >= 32 && C3 % 32 == 0 && C3 <= PM_MAXC3,
                "%s: unsupported widths %d/%d/%d", who, C1, C2, C3);
@@ -1140,7 +1529,31 @@ extern "C" int pc3d_pointmlp3_max_bwd_update_f32(float* x, int64_t x_bs, int64_t
               {const_cast<float*>(grad_x), gx_bs, gx_ps, gx_cs}, nullptr, 1};
   PMUpdArgs u{{x, x_bs, x_ps, x_cs}, m, v, {ori, o_bs, o_ps, o_cs}, nn_idx, w, dist_val, adam, B, dist_kind,
               (float)(1.0 - beta1), (float)(1.0 - beta2), (float)beta2, (float)eps, budget};
-  hipLaunchKernelGGL(pointmlp3_max_bwd_update_kernel, dim3(cdiv(N, PM_BTP), B), dim3(256), 0, as_stream(stream), a, u);
+  if (packed)
+    hipLaunchKernelGGL(pointmlp3_max_bwd_update_packed_kernel, dim3(cdiv(N, PM_PTP), B), dim3(PM_PNT), 0, as_stream(stream), a, u);
+  else
+    hipLaunchKernelGGL(pointmlp3_max_bwd_update_kernel, dim3(cdiv(N, PM_BTP), B), dim3(256), 0, as_stream(stream), a, u);
   PC3D_LAUNCH_CHECK(who);
   return PC3D_OK;
+}
+
+#define PM_BWD_UPDATE_PARAMS                                                                                            \
+  float *x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N, const float *W1, const float *b1, const float *W2, \
+      const float *b2, const float *W3, const float *W2T, int C1, int C2, int C3, const int32_t *argidx,               \
+      const uint64_t *mask1, const uint32_t *mask2, const float *g_pooled, const float *grad_x, int64_t gx_bs,         \
+      int64_t gx_ps, int64_t gx_cs, const float *ori, int64_t o_bs, int64_t o_ps, int64_t o_cs, float *m, float *v,    \
+      double beta1, double beta2, double eps, float budget, const float *adam, int dist_kind, const float *w,          \
+      const float *dist_val, const int32_t *nn_idx, void *stream
+#define PM_BWD_UPDATE_ARGS                                                                                             \
+  x, x_bs, x_ps, x_cs, B, N, W1, b1, W2, b2, W3, W2T, C1, C2, C3, argidx, mask1, mask2, g_pooled, grad_x, gx_bs, gx_ps, \
+      gx_cs, ori, o_bs, o_ps, o_cs, m, v, beta1, beta2, eps, budget, adam, dist_kind, w, dist_val, nn_idx, stream
+
+extern "C" int pc3d_pointmlp3_max_bwd_update_f32(PM_BWD_UPDATE_PARAMS) {
+  return pm_bwd_update_launch("pc3d_pointmlp3_max_bwd_update_f32", PM_BWD_DEFAULT_PACKED, PM_BWD_UPDATE_ARGS);
+}
+extern "C" int pc3d_pointmlp3_max_bwd_update_tile32_f32(PM_BWD_UPDATE_PARAMS) {
+  return pm_bwd_update_launch("pc3d_pointmlp3_max_bwd_update_tile32_f32", false, PM_BWD_UPDATE_ARGS);
+}
+extern "C" int pc3d_pointmlp3_max_bwd_update_packed_f32(PM_BWD_UPDATE_PARAMS) {
+  return pm_bwd_update_launch("pc3d_pointmlp3_max_bwd_update_packed_f32", true, PM_BWD_UPDATE_ARGS);
 }

@@ -498,11 +498,13 @@ def pointmlp3_max_fwd_raw(x, weights, relu_last, T=None, x_cf=True, fold=True, w
 
 
 def pointmlp3_max_bwd_raw(x, weights, argidx, g_pooled, masks, T=None, x_cf=True, out=None, accumulate=False,
-                          want_gT=False, twolist=False):
+                          want_gT=False, twolist=False, tile32=None, stop_after=0):
     """Gradient w.r.t. the tower input (T None) or w.r.t. the raw points through x' = x @ T (T given); same layout
     as x. masks: the (mask1, mask2) pair of the forward launch on the same x/T (want_masks=True).
     want_gT: also return the per-tile partials [B, ntiles, 16] of dL/dT. out/accumulate: add into `out`.
-    twolist: run the earlier two-list kernel (same bits; parity tests and tools/bench_pointmlp.py only)."""
+    twolist: run the earlier two-list kernel (same bits; parity tests and tools/bench_pointmlp.py only).
+    tile32: None — the default entry; True / False — the tile32 / the packed form of the balanced kernel by name (same
+    bits; parity test and bench tool only). stop_after 1..5 (tile32=False): end the packed launch after that phase."""
     xp, xbs, xps, xcs, B, N = _pts(x, x_cf, "x")
     W1, b1, W2, b2, W3, b3 = weights[:6]
     W2T = weights[6] if len(weights) > 6 else W2.t().contiguous()
@@ -521,12 +523,18 @@ def pointmlp3_max_bwd_raw(x, weights, argidx, g_pooled, masks, T=None, x_cf=True
         bt = _lib.load().pc3d_pointmlp3_bwd_tile_points()
         part_gT = torch.empty((B, (N + bt - 1) // bt, 16), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        _lib.call("pc3d_pointmlp3_max_bwd_twolist_f32" if twolist else "pc3d_pointmlp3_max_bwd_f32",
+        if twolist and tile32 is not None:
+            raise ValueError("pointmlp3_max_bwd_raw: twolist and tile32 name different kernels")
+        if stop_after and tile32 is not False:
+            raise ValueError("pointmlp3_max_bwd_raw: stop_after belongs to the packed form (tile32=False)")
+        name = "pc3d_pointmlp3_max_bwd_twolist_f32" if twolist else "pc3d_pointmlp3_max_bwd_f32" if tile32 is None \
+            else "pc3d_pointmlp3_max_bwd_tile32_f32" if tile32 else "pc3d_pointmlp3_max_bwd_packed_dbg_f32"
+        _lib.call(name,
                   xp, xbs, xps, xcs, B, N, _ptr(T),
                   W1.data_ptr(), b1.data_ptr(), W2.data_ptr(), b2.data_ptr(), W3.data_ptr(), W2T.data_ptr(),
                   C1, C2, C3, argidx.data_ptr(), m1.data_ptr(), m2.data_ptr(), g_pooled.data_ptr(), gp, gbs, gps, gcs,
                   _ptr(part_gT),
-                  1 if accumulate else 0, _stream())
+                  1 if accumulate else 0, *([int(stop_after)] if tile32 is False else []), _stream())
     return (gx, part_gT) if want_gT else gx
 
 
@@ -1204,10 +1212,11 @@ def linear_book(X, W, adv, ori, pred, label, untarget, bestdist, bestscore, o_be
 
 
 def pointmlp3_max_bwd_update(x, weights, argidx, g_pooled, masks, gx, ori, m, v, adam, budget, dist_kind=0, w=None,
-                             dist_val=None, nn_idx=None, betas=(0.9, 0.999), eps=1e-8, x_cf=True):
+                             dist_val=None, nn_idx=None, betas=(0.9, 0.999), eps=1e-8, x_cf=True, tile32=None):
     """pointmlp3_max_bwd_raw(..., out=gx, accumulate=True) followed by the update half of cw_update, as ONE launch
     (pc3d_pointmlp3_max_bwd_update_f32): x — the iterate — and the Adam moments m / v are updated in place, gx is only
-    read. adam: the [2] factors written by linear_book; dist_val: ||adv-ori|| per sample (dist_kind 1)."""
+    read. adam: the [2] factors written by linear_book; dist_val: ||adv-ori|| per sample (dist_kind 1).
+    tile32: as pointmlp3_max_bwd_raw's (None: the default entry)."""
     xp, xbs, xps, xcs, B, N = _pts(x, x_cf, "x")
     W1, b1, W2, b2, W3, b3 = weights[:6]
     W2T = weights[6] if len(weights) > 6 else W2.t().contiguous()
@@ -1227,7 +1236,8 @@ def pointmlp3_max_bwd_update(x, weights, argidx, g_pooled, masks, gx, ori, m, v,
     if nn_idx is not None and (nn_idx.dtype != torch.int32 or tuple(nn_idx.shape) != (B, N) or not nn_idx.is_contiguous()):
         raise ValueError("pointmlp3_max_bwd_update: nn_idx must be a contiguous int32 [B,N] tensor")
     with torch.cuda.device(x.device):
-        _lib.call("pc3d_pointmlp3_max_bwd_update_f32", xp, xbs, xps, xcs, B, N,
+        _lib.call("pc3d_pointmlp3_max_bwd_update_f32" if tile32 is None else "pc3d_pointmlp3_max_bwd_update_tile32_f32"
+                  if tile32 else "pc3d_pointmlp3_max_bwd_update_packed_f32", xp, xbs, xps, xcs, B, N,
                   W1.data_ptr(), b1.data_ptr(), W2.data_ptr(), b2.data_ptr(), W3.data_ptr(), W2T.data_ptr(),
                   C1, C2, C3, argidx.data_ptr(), m1.data_ptr(), m2.data_ptr(), g_pooled.data_ptr(),
                   *_pv(gx, x_cf, "gx"), *_pv(ori, x_cf, "ori"), m.data_ptr(), v.data_ptr(), float(betas[0]), float(betas[1]),

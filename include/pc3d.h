@@ -445,8 +445,9 @@ int pc3d_pointmlp3_max_fwd_screen_dbg_prep_f32(const float* x, int64_t x_bs, int
  * [B, ceil(N / pc3d_pointmlp3_bwd_tile_points()), 16], 9 used) the per-tile partial sums of dL/dT (row-major 3x3);
  * their sum over tiles is the gradient that flows on into the STN head. accumulate != 0: grad_x += (used to add the
  * STN tower's contribution on top of the trunk's).
- * W2T is W2 transposed ([64,128] row-major); required, but the balanced kernel behind this entry fetches its MFMA
- * operand from W2 itself (coalesced in that operand's lane order) and only the two-list entry below reads W2T.
+ * W2T is W2 transposed ([64,128] row-major); required, but the balanced kernel behind this entry (its packed form, see
+ * pc3d_pointmlp3_max_bwd_tile32_f32 below) fetches its MFMA operand from W2 itself (coalesced in that operand's lane
+ * order) and only the two-list entry below reads W2T.
  * mask1 / mask2 are the forward launch's outputs of those names (required).
  * The max-pool routes each channel to one point, so the layer-3 dgrad is a sparse ordered gather: the tile's hits are
  * sorted by point and each point's row is one fma chain in ascending channel order, whole points shared out over the
@@ -468,6 +469,27 @@ int pc3d_pointmlp3_max_bwd_twolist_f32(const float* x, int64_t x_bs, int64_t x_p
                                        const float* g_pooled,
                                        float* grad_x, int64_t gx_bs, int64_t gx_ps, int64_t gx_cs,
                                        float* part_gT, int accumulate, void* stream);
+/* The two forms of the balanced kernel by name, bit for bit the same results (tests/test_pointmlp_bwd_packed_gpu.py):
+ * tile32 — a workgroup per 32 points, every row of a tile through the W2 product; packed (stop_after = 0) — a workgroup
+ * per 128 points, argidx / g / W2 fetched once for them and the W2 product over the rows of points that have a hit
+ * only; part_gT keeps one record per pc3d_pointmlp3_bwd_tile_points() = 32 points in both. stop_after = 1..5 ends the
+ * packed launch after classification and count / sorted list / gather / W2 product / W1 product (timing only: outputs
+ * are not written).
+ * pc3d_pointmlp3_max_bwd_f32 launches one of the two; only the parity test and tools/bench_pointmlp.py call these. */
+int pc3d_pointmlp3_max_bwd_tile32_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                      const float* T, const float* W1, const float* b1, const float* W2,
+                                      const float* b2, const float* W3, const float* W2T, int C1, int C2, int C3,
+                                      const int32_t* argidx, const uint64_t* mask1, const uint32_t* mask2,
+                                      const float* g_pooled,
+                                      float* grad_x, int64_t gx_bs, int64_t gx_ps, int64_t gx_cs,
+                                      float* part_gT, int accumulate, void* stream);
+int pc3d_pointmlp3_max_bwd_packed_dbg_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                          const float* T, const float* W1, const float* b1, const float* W2,
+                                          const float* b2, const float* W3, const float* W2T, int C1, int C2, int C3,
+                                          const int32_t* argidx, const uint64_t* mask1, const uint32_t* mask2,
+                                          const float* g_pooled,
+                                          float* grad_x, int64_t gx_bs, int64_t gx_ps, int64_t gx_cs,
+                                          float* part_gT, int accumulate, int stop_after, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * PointNet with the feature transform (model/pointnet.py:51-87 STNkd, :101-117), eval mode, BatchNorm folded:
@@ -1198,6 +1220,26 @@ int pc3d_pointmlp3_max_bwd_update_f32(float* x, int64_t x_bs, int64_t x_ps, int6
                                       float* m, float* v, double beta1, double beta2, double eps, float budget,
                                       const float* adam, int dist_kind, const float* w, const float* dist_val,
                                       const int32_t* nn_idx, void* stream);
+/* The same launch by the tile32 / the packed form of the backward (see pc3d_pointmlp3_max_bwd_tile32_f32); the entry
+ * above launches one of the two. Parity test and bench tool only. */
+int pc3d_pointmlp3_max_bwd_update_tile32_f32(float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                             const float* W1, const float* b1, const float* W2, const float* b2,
+                                             const float* W3, const float* W2T, int C1, int C2, int C3,
+                                             const int32_t* argidx, const uint64_t* mask1, const uint32_t* mask2,
+                                             const float* g_pooled, const float* grad_x, int64_t gx_bs, int64_t gx_ps,
+                                             int64_t gx_cs, const float* ori, int64_t o_bs, int64_t o_ps, int64_t o_cs,
+                                             float* m, float* v, double beta1, double beta2, double eps, float budget,
+                                             const float* adam, int dist_kind, const float* w, const float* dist_val,
+                                             const int32_t* nn_idx, void* stream);
+int pc3d_pointmlp3_max_bwd_update_packed_f32(float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                             const float* W1, const float* b1, const float* W2, const float* b2,
+                                             const float* W3, const float* W2T, int C1, int C2, int C3,
+                                             const int32_t* argidx, const uint64_t* mask1, const uint32_t* mask2,
+                                             const float* g_pooled, const float* grad_x, int64_t gx_bs, int64_t gx_ps,
+                                             int64_t gx_cs, const float* ori, int64_t o_bs, int64_t o_ps, int64_t o_cs,
+                                             float* m, float* v, double beta1, double beta2, double eps, float budget,
+                                             const float* adam, int dist_kind, const float* w, const float* dist_val,
+                                             const int32_t* nn_idx, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * The isometry attack (attack/ISO/iso_attack.py): x' = W x with one 3x3 matrix per cloud, in front of a frozen victim.

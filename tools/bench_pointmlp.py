@@ -1,6 +1,8 @@
-"""Stand-alone timing of the fused PointNet tower (K8): forward and backward eagerly (event-timed), and BOTH backward
-entries (the balanced kernel behind pc3d_pointmlp3_max_bwd_f32 and the two-list kernel it replaced) inside replayed
-hipGraphs, the way the attack loops launch them. One JSON line per shape; --json PATH also writes the list."""
+"""Stand-alone timing of the fused PointNet tower (K8): forward and backward eagerly (event-timed), and the backward's
+kernels by name inside replayed hipGraphs, the way the attack loops launch them: the two forms of the balanced kernel
+(tile32: a workgroup per 32 points; packed: a workgroup per 128 points, the W2 product over live rows only) timed
+ALTERNATELY, the least of ROUNDS rounds with the round-to-round spread; the packed form ended after each phase (B = 32
+shapes); and the two-list kernel both replaced. One JSON line per shape; --json PATH also writes the list."""
 import argparse, importlib, sys, os, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -27,9 +29,11 @@ def graph_us(fn, per=20, reps=50):
     return e0.elapsed_time(e1) / (per * reps) * 1e3
 ap = argparse.ArgumentParser()
 ap.add_argument("--json", default=None)
+ap.add_argument("--rounds", type=int, default=5)
 args = ap.parse_args()
 rows = []
 torch.manual_seed(0)
+PHASES = ("compaction", "sort", "gather", "w2_product", "w1_product")   # stop_after = 1..5
 for B, N in ((32, 1024), (32, 2048), (64, 2048), (32, 4096)):
     x = torch.randn(B, 3, N, device=dev); ws = w(1024); ws = ws + (ws[2].t().contiguous(),)
     T = torch.randn(B, 3, 3, device=dev) * 0.5
@@ -50,10 +54,24 @@ for B, N in ((32, 1024), (32, 2048), (64, 2048), (32, 4096)):
     out = torch.zeros_like(x)
     hist = torch.bincount((i.long() // 32).flatten() + (N // 32) * torch.arange(B, device=dev).repeat_interleave(1024))
     row["busiest_tile_hits"] = int(hist.max())
-    for name, twolist in (("balanced", False), ("twolist", True)):
-        # the trunk's launch (T -> dx, per-tile dT) and the STN tower's (accumulating into the same gx)
-        row["graph_bwd_trunk_us_" + name] = graph_us(lambda: ops.pointmlp3_max_bwd_raw(x, ws, i, g, mk, T=T, want_gT=True, out=out, twolist=twolist))
-        row["graph_bwd_stn_us_" + name] = graph_us(lambda: ops.pointmlp3_max_bwd_raw(x, ws, i, g, mk, out=out, accumulate=True, twolist=twolist))
+    live = torch.zeros(B, N, dtype=torch.bool, device=dev).scatter_(1, i.long(), True)
+    row["live_points_per_cloud"] = float(live.sum(1).float().mean())
+    row["row_blocks_per_128_points"] = float(((live.view(B, -1, 128).sum(2) + 31) // 32).float().mean())
+    # the trunk's launch (T -> dx, per-tile dT) and the STN tower's (accumulating into the same gx)
+    launches = {"trunk": dict(T=T, want_gT=True), "stn": dict(accumulate=True)}
+    for tower, kw in launches.items():
+        row["graph_bwd_%s_us_twolist" % tower] = graph_us(lambda: ops.pointmlp3_max_bwd_raw(x, ws, i, g, mk, out=out, twolist=True, **kw))
+        t = {"tile32": [], "packed": []}
+        for _ in range(args.rounds):   # alternated: a drift of the clocks meets both forms
+            for name in t:
+                t[name].append(graph_us(lambda: ops.pointmlp3_max_bwd_raw(x, ws, i, g, mk, out=out, tile32=(name == "tile32"), **kw)))
+        for name, v in t.items():
+            row["graph_bwd_%s_us_%s" % (tower, name)] = min(v)
+            row["graph_bwd_%s_us_%s_spread" % (tower, name)] = max(v) - min(v)
+        if B == 32:   # the packed launch ended after each phase (loads nothing later needs are dropped with it)
+            for k, ph in enumerate(PHASES, 1):
+                row["graph_bwd_%s_us_packed_upto_%s" % (tower, ph)] = min(
+                    graph_us(lambda: ops.pointmlp3_max_bwd_raw(x, ws, i, g, mk, out=out, tile32=False, stop_after=k, **kw)) for _ in range(3))
     rows.append(row)
     print(json.dumps(row))
 if args.json:
