@@ -400,10 +400,11 @@ __global__ __launch_bounds__(256) void pointmlp3_max_bwd_twolist_kernel(PMBwdArg
     float o0 = g0, o1 = g1v, o2 = g2v;
     if (a.T) {
       // x' = x @ T  =>  dL/dx[c] = sum_c' g'[c'] T[c][c'] ;  dL/dT[c][c'] = sum_p x[p][c] g'[p][c']
+      // (the chain starts from +0, so a dead point, g' = +0, gets +0 and not -0 under a row of negative T entries)
       const float* t = a.T + (int64_t)b * 9;
-      o0 = __builtin_fmaf(g2v, t[2], __builtin_fmaf(g1v, t[1], g0 * t[0]));
-      o1 = __builtin_fmaf(g2v, t[5], __builtin_fmaf(g1v, t[4], g0 * t[3]));
-      o2 = __builtin_fmaf(g2v, t[8], __builtin_fmaf(g1v, t[7], g0 * t[6]));
+      o0 = __builtin_fmaf(g2v, t[2], __builtin_fmaf(g1v, t[1], __builtin_fmaf(g0, t[0], 0.f)));
+      o1 = __builtin_fmaf(g2v, t[5], __builtin_fmaf(g1v, t[4], __builtin_fmaf(g0, t[3], 0.f)));
+      o2 = __builtin_fmaf(g2v, t[8], __builtin_fmaf(g1v, t[7], __builtin_fmaf(g0, t[6], 0.f)));
       if (a.part_gT) {
         float xr[3] = {0.f, 0.f, 0.f};
         if (live && n0 + p < a.N) {
@@ -840,10 +841,11 @@ __device__ __forceinline__ void pm_bwd_body(const PMBwdArgs& a, const PMUpdArgs&
     float o0 = g0, o1 = g1v, o2 = g2v;
     if (a.T) {
       // x' = x @ T  =>  dL/dx[c] = sum_c' g'[c'] T[c][c'] ;  dL/dT[c][c'] = sum_p x[p][c] g'[p][c']
+      // (the chain starts from +0, so a dead point, g' = +0, gets +0 and not -0 under a row of negative T entries)
       const float* t = s_T;
-      o0 = __builtin_fmaf(g2v, t[2], __builtin_fmaf(g1v, t[1], g0 * t[0]));
-      o1 = __builtin_fmaf(g2v, t[5], __builtin_fmaf(g1v, t[4], g0 * t[3]));
-      o2 = __builtin_fmaf(g2v, t[8], __builtin_fmaf(g1v, t[7], g0 * t[6]));
+      o0 = __builtin_fmaf(g2v, t[2], __builtin_fmaf(g1v, t[1], __builtin_fmaf(g0, t[0], 0.f)));
+      o1 = __builtin_fmaf(g2v, t[5], __builtin_fmaf(g1v, t[4], __builtin_fmaf(g0, t[3], 0.f)));
+      o2 = __builtin_fmaf(g2v, t[8], __builtin_fmaf(g1v, t[7], __builtin_fmaf(g0, t[6], 0.f)));
       if (a.part_gT) {
         float xr[3] = {0.f, 0.f, 0.f};
         if (live) xr[0] = s_x[p], xr[1] = s_x[PM_BTP + p], xr[2] = s_x[2 * PM_BTP + p];   // zeros past N
@@ -900,8 +902,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 // longest phase (6.3 of 19.7 us: a thread walks a quarter of a list four times as long), so the list ordered by
 // (point, channel) is read off a [128][1024]-bit map instead (2.3 us) — same list, entry = (slot << 17 | point << 10 |
 // channel). From g' on the statements are pm_bwd_body's per 32-point sub-tile (wave s = sub-tile s, each point on the
-// lane it has there), a sub-tile without a hit takes that kernel's early exit (its stores are exact +0, which the
-// chain through T does not give for a negative T entry), and part_gT keeps one 16-word record per 32 points.
+// lane it has there), a sub-tile without a hit takes that kernel's early exit (its stores are exact +0; the chain
+// through T starts from +0, fma(g'[0], T[c][0], +0), so that a dead point next to a live one gets +0 as well, whatever
+// the signs in T), and part_gT keeps one 16-word record per 32 points.
 // STOP: 0, or the phase after which the launch ends (tools/bench_pointmlp.py's phase table; production is STOP = 0).
 constexpr int PM_PTP = 128;                  // points per workgroup
 constexpr int PM_PNT = 512;                  // threads per workgroup
@@ -1181,9 +1184,9 @@ __device__ __forceinline__ void pm_bwdp_body(const PMBwdArgs& a, const PMUpdArgs
   float o0 = g0, o1 = g1v, o2 = g2v;
   if (a.T) {
     const float* t = s_T;
-    o0 = __builtin_fmaf(g2v, t[2], __builtin_fmaf(g1v, t[1], g0 * t[0]));
-    o1 = __builtin_fmaf(g2v, t[5], __builtin_fmaf(g1v, t[4], g0 * t[3]));
-    o2 = __builtin_fmaf(g2v, t[8], __builtin_fmaf(g1v, t[7], g0 * t[6]));
+    o0 = __builtin_fmaf(g2v, t[2], __builtin_fmaf(g1v, t[1], __builtin_fmaf(g0, t[0], 0.f)));
+    o1 = __builtin_fmaf(g2v, t[5], __builtin_fmaf(g1v, t[4], __builtin_fmaf(g0, t[3], 0.f)));
+    o2 = __builtin_fmaf(g2v, t[8], __builtin_fmaf(g1v, t[7], __builtin_fmaf(g0, t[6], 0.f)));
     if (a.part_gT) {
       float xr[3] = {0.f, 0.f, 0.f};
       if (live) xr[0] = s_x[q], xr[1] = s_x[TP + q], xr[2] = s_x[2 * TP + q];   // zeros past N

@@ -528,10 +528,11 @@ __global__ __launch_bounds__(256) void ft_tower_bwd_kernel(FTBwdArgs a) {
     float o0 = g0, o1 = g1v, o2 = g2v;
     if (a.T) {
       // x' = x @ T  =>  dL/dx[c] = sum_c' g'[c'] T[c][c'] ;  dL/dT[c][c'] = sum_p x[p][c] g'[p][c']
+      // (the chain starts from +0, so a dead point, g' = +0, gets +0 and not -0 under a row of negative T entries)
       const float* t = a.T + (int64_t)b * 9;
-      o0 = __builtin_fmaf(g2v, t[2], __builtin_fmaf(g1v, t[1], g0 * t[0]));
-      o1 = __builtin_fmaf(g2v, t[5], __builtin_fmaf(g1v, t[4], g0 * t[3]));
-      o2 = __builtin_fmaf(g2v, t[8], __builtin_fmaf(g1v, t[7], g0 * t[6]));
+      o0 = __builtin_fmaf(g2v, t[2], __builtin_fmaf(g1v, t[1], __builtin_fmaf(g0, t[0], 0.f)));
+      o1 = __builtin_fmaf(g2v, t[5], __builtin_fmaf(g1v, t[4], __builtin_fmaf(g0, t[3], 0.f)));
+      o2 = __builtin_fmaf(g2v, t[8], __builtin_fmaf(g1v, t[7], __builtin_fmaf(g0, t[6], 0.f)));
       float xr[3] = {0.f, 0.f, 0.f};
       if (live && n0 + p < a.N) {
         const float* xp = a.x.p + (int64_t)b * a.x.bs + (int64_t)(n0 + p) * a.x.ps;

@@ -505,6 +505,8 @@ def pointmlp3_max_bwd_raw(x, weights, argidx, g_pooled, masks, T=None, x_cf=True
     twolist: run the earlier two-list kernel (same bits; parity tests and tools/bench_pointmlp.py only).
     tile32: None — the default entry; True / False — the tile32 / the packed form of the balanced kernel by name (same
     bits; parity test and bench tool only). stop_after 1..5 (tile32=False): end the packed launch after that phase."""
+    if want_gT and T is None:       # the kernels write the partials only with T: the tensor would go back unwritten
+        raise ValueError("pointmlp3_max_bwd_raw: T and part_gT go together (want_gT needs T)")
     xp, xbs, xps, xcs, B, N = _pts(x, x_cf, "x")
     W1, b1, W2, b2, W3, b3 = weights[:6]
     W2T = weights[6] if len(weights) > 6 else W2.t().contiguous()

@@ -10,6 +10,11 @@ kernels of that commit ARE the definition of the right bits, and the file is re-
 alter the arithmetic, never to make tests/test_wave_bits_gpu.py pass. The recorder is make_update_bits.py's: every case
 runs twice and nothing is written unless the two runs agree bit for bit; outputs of at most 4 KiB are stored as integer
 views, larger ones as the sha256 of that view.
+
+One entry has been re-recorded since: pointnet_tower/N333-C1024-thK256/gx, with the change that starts the tower
+backward's chain through T from +0 (tests/test_pointmlp_bwd_ref_gpu.py). Cloud 2 of that case has a row of T that is
+negative throughout, and its 224 words of points without a hit were -0; they are +0 now. With -0 put back the new
+output has the old hash, and the other 402 entries came out as they were.
 """
 import make_update_bits          # puts tests/ and the repository root on sys.path
 import wave_bits_cases
