@@ -17,8 +17,15 @@ Protocol kept from the reference:
 What changes: batches B > 1 work (the reference prints ``.item()`` and constrains only sample 0, :80-84,:268-275 —
 here the z-only / box constraint applies to every sample); bookkeeping stays on the device (one host read per
 binary-search step); the resampling draws ``K`` of ``2K`` indices (the reference hard-codes 4000 of 8000, :238).
+
+``device_loop=True`` (PointNet victims, see ``CW._device_loop_plan``): the iteration is ONE stacked victim pass of the
+iterate and its ten views between pc3d_eot_prepare_f32 and pc3d_eot_update_f32 (csrc/eot.hip), replayed from a hipGraph
+without autograd; the rotations and resampling indices are still drawn on the host, in the same order, a block of
+iterations ahead.
 """
 import random
+import time
+import types
 
 import numpy as np
 import torch
@@ -39,6 +46,30 @@ class AdvLossAdapter:
         return (self.targeted_func if whether_target else self.untargeted_func)(logits, label)
 
 
+class PerSampleDist:
+    """Gives a CW_utils.dist_utils functor the ``dist_func(adv, ori, weights)`` call of this attack with one distance per
+    sample (``batch_avg=False``): what the per-sample bookkeeping of a batch B > 1 needs, and what the device loop
+    recognises (``CW._device_loop_plan``)."""
+
+    def __init__(self, functor):
+        self.functor = functor
+
+    def __call__(self, adv, ori, weights=None):
+        return self.functor(adv, ori, weights, batch_avg=False)
+
+
+def _inverse_columns(cols, K, out):
+    """out [K,2] (int32): the at most two positions j with cols[j] == i, ascending, else -1 (K draws without replacement
+    from the 2K - 1 columns of cat((x, x), 2) hit a point at most twice)."""
+    out.fill(-1)
+    order = np.argsort(cols, kind="stable")
+    sc = cols[order]
+    first = np.ones(K, dtype=bool)
+    first[1:] = sc[1:] != sc[:-1]
+    out[sc[first], 0] = order[first]
+    out[sc[~first], 1] = order[~first]
+
+
 def _renormalize(x):
     """:107-115 / :224-230 — centre and scale [B,3,K] to the unit sphere (differentiable, like the reference)."""
     p = x.permute(0, 2, 1)
@@ -47,21 +78,24 @@ def _renormalize(x):
     return (p / var.unsqueeze(1)).permute(0, 2, 1)
 
 
-def _small_rotation(dev):
-    """:195-219 — one draw of (theta ~ 1e-2 N(0,1), axis choice): z / x / y rotation with probability 0.2 each, else
-    the identity. Consumes torch.randn(1) THEN random.random(), like the reference."""
+def _rotation_draw():
+    """:195-219 — one draw of (theta ~ 1e-2 N(0,1), axis choice) as a 3 x 3 list: z / x / y rotation with probability 0.2
+    each, else the identity. Consumes torch.randn(1) THEN random.random(), like the reference."""
     theta = torch.randn(1) * 1e-2
     c, s = float(torch.cos(theta)), float(torch.sin(theta))
     r = random.random()
     if r < 0.2:
-        m = [[c, s, 0], [-s, c, 0], [0, 0, 1]]
-    elif r < 0.4:
-        m = [[1, 0, 0], [0, c, s], [0, -s, c]]
-    elif r < 0.6:
-        m = [[c, 0, s], [0, 1, 0], [-s, 0, c]]
-    else:
-        m = [[1, 0, 0], [0, 1, 0], [0, 0, 1]]
-    return ops.h2d(torch.tensor(m, dtype=torch.float32), dev).unsqueeze(0)
+        return [[c, s, 0], [-s, c, 0], [0, 0, 1]]
+    if r < 0.4:
+        return [[1, 0, 0], [0, c, s], [0, -s, c]]
+    if r < 0.6:
+        return [[c, 0, s], [0, 1, 0], [-s, 0, c]]
+    return [[1, 0, 0], [0, 1, 0], [0, 0, 1]]
+
+
+def _small_rotation(dev):
+    """The draw as a [1,3,3] device tensor (the autograd path: one upload per view)."""
+    return ops.h2d(torch.tensor(_rotation_draw(), dtype=torch.float32), dev).unsqueeze(0)
 
 
 class CW:
@@ -70,7 +104,11 @@ class CW:
     def __init__(self, model, adv_func, dist_func, attack_lr=1e-2,
                  init_weight=10., max_weight=80., binary_step=10, num_iter=500, whether_target=True, whether_1d=True,
                  whether_renormalization=False,
-                 whether_3Dtransform=False, whether_resample=False, device=None, verbose=False, graph=True):
+                 whether_3Dtransform=False, whether_resample=False, device=None, verbose=False, graph=True,
+                 device_loop=False):
+        """`device_loop=True` runs the iteration as a captured chain of own kernels around ONE stacked victim pass when
+        the victim, the functors and the cloud size allow it (_device_loop_plan), and silently the usual path otherwise;
+        `last_path` says which one the last attack() took: "device_loop" or "autograd"."""
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.model = model.to(self.device)
         self.model.eval()
@@ -89,10 +127,203 @@ class CW:
         self.box_constraint = 0.4
         self.whether_resample = whether_resample
         self.verbose = verbose
+        self.graph = graph
+        self.device_loop = device_loop
+        self.last_path = None
+        self.draw_seconds = 0.0                # host time the last device-loop attack() spent drawing rotations / indices
+        self._loop_cache = None                # the device loop's buffers and captured graphs, kept from call to call
 
     def _forward(self, x):
         out = self.model(x)
         return out[0] if isinstance(out, tuple) else out
+
+    # ---- device loop (PointNet victim + own functors): no autograd, ONE stacked victim pass, replayed from hipGraphs ----
+    EOT_VIEWS = 10       # :193 — the expectation's ten views
+    LOOP_BLOCK = 16      # iterations per graph replay = per block of host draws; the remainder replays single iterations
+
+    def _device_loop_plan(self, B, K):
+        """The constants of the device loop when it applies, else None: a GPU victim with fused_attack_grad (the two
+        PointNetCls variants), an AdvLossAdapter around functors the CW loop maps to ops.LOSS_KINDS, ChamferDist('adv2ori')
+        or L2Dist — inside PerSampleDist, or bare at B = 1 where the batch mean is the identity — and a cloud the kernels
+        hold. ChamferkNNDist and arbitrary callables take the autograd path."""
+        from ..CW.CW_attack import CW as _CW
+        from ..CW.CW_utils import dist_utils as _dist_utils
+        victim = _graphed.unwrap(self.model)
+        if self.device.type != "cuda" or not hasattr(victim, "fused_attack_grad") or K > ops.EOT_MAX_POINTS:
+            return None
+        if next(victim.parameters()).device.type != "cuda":
+            return None
+        if type(self.adv_func) is not AdvLossAdapter:
+            return None
+        af = self.adv_func.targeted_func if self.whether_target else self.adv_func.untargeted_func
+        kind = _CW._own_adv_kind(types.SimpleNamespace(adv_func=af))
+        if kind is None:
+            return None
+        df = self.dist_func
+        if type(df) is PerSampleDist:
+            df = df.functor
+        elif B != 1:
+            return None
+        if type(df) is _dist_utils.ChamferDist and df.method == 'adv2ori':
+            dist_kind = "chamfer"
+        elif type(df) is _dist_utils.L2Dist:
+            dist_kind = "l2"
+        else:
+            return None
+        E = self.EOT_VIEWS if self.whether_3Dtransform else 0
+        renorm = bool(self.whether_renormalization)
+        return dict(victim=victim, kind=kind, dist_kind=dist_kind, E=E, renorm=renorm,
+                    resample=bool(E and self.whether_resample), prepare=bool(E or renorm), one_d=bool(self.whether_1d),
+                    untarget=not self.whether_target, box=float(self.box_constraint), scale=1.0 / ((E if E else 1) * B))
+
+    def _device_loop_state(self, plan, B, K):
+        """Buffers (static: the graphs point at them), the iteration body and the captured graphs, rebuilt when the shape,
+        a constant of the loop, the kernel flavour or the victim's weights change."""
+        victim, dev = plan["victim"], self.device
+        key = (B, K, float(self.attack_lr), bool(self.graph), bool(ops._det()), _graphed.weights_key(victim),
+               tuple(sorted((n, v) for n, v in plan.items() if n != "victim")))
+        c = self._loop_cache
+        if c is not None and c["key"] == key:
+            return c
+        E, LB = plan["E"], self.LOOP_BLOCK
+        S, T = 1 + E, 2 * LB
+        f32, i32, i64 = (dict(dtype=t, device=dev) for t in (torch.float32, torch.int32, torch.long))
+        adv, ori, m, v, o_bestattack, input_val = (torch.zeros((B, 3, K), **f32) for _ in range(6))
+        X = torch.zeros((S * B, 3, K), **f32) if plan["prepare"] else None
+        stats = torch.zeros((S * B, 4), **f32) if plan["prepare"] else None
+        arg = torch.zeros((S * B,), **i32) if plan["prepare"] else None
+        # the per-iteration tables: T = two blocks of rows on the device, two pinned blocks on the host
+        rot = torch.zeros((T, E, 3, 3), **f32) if E else None
+        idx = torch.zeros((T, E, K), **i32) if plan["resample"] else None
+        inv = torch.zeros((T, E, K, 2), **i32) if plan["resample"] else None
+        rot_pin = torch.zeros((2, LB, E, 3, 3), dtype=torch.float32).pin_memory() if E else None
+        idx_pin = torch.zeros((2, LB, E, K), dtype=torch.int32).pin_memory() if plan["resample"] else None
+        inv_pin = torch.zeros((2, LB, E, K, 2), dtype=torch.int32).pin_memory() if plan["resample"] else None
+        chamfer = plan["dist_kind"] == "chamfer"
+        nn_d = torch.zeros((B, K), **f32) if chamfer else None
+        nn_idx = torch.zeros((B, K), **i32) if chamfer else None
+        step = torch.zeros((1,), **i32)
+        pred, goal_s, goal = torch.zeros((S * B,), **i64), torch.zeros((S * B,), **i64), torch.zeros((B,), **i64)
+        w, bestdist, o_bestdist = (torch.zeros((B,), **f32) for _ in range(3))
+        bestscore, o_bestscore = (torch.zeros((B,), **i64) for _ in range(2))
+        kind, kappa = plan["kind"]
+
+        def body():
+            # one chain on one stream: the stacked input, the victim's passes on it (the classifier tail advances the step
+            # word), the adv -> ori search, the update
+            with torch.no_grad():
+                x_in = adv
+                if plan["prepare"]:
+                    ops.eot_prepare(adv, ori, rot, idx, plan["renorm"], step, out=X, stats=stats, arg=arg)
+                    x_in = X
+                _, _, gx = victim.fused_attack_grad(x_in, goal_s, kind, kappa, pred_out=pred, step=step, scale=plan["scale"])
+                if chamfer:
+                    ops.nn_search_into(adv, ori, nn_d, nn_idx)
+                ops.eot_update(adv, ori, gx, m, v, step, self.attack_lr, pred, goal, plan["untarget"], bestdist, bestscore,
+                               o_bestdist, o_bestscore, o_bestattack, rot=rot, inv=inv, renorm=plan["renorm"], stats=stats,
+                               arg=arg, input_val=input_val, dist_kind=plan["dist_kind"], w=w, nn_idx=nn_idx, batch_mean=B,
+                               one_d=plan["one_d"], box=plan["box"])
+
+        def begin_step():
+            bestdist.fill_(1e10), bestscore.fill_(-1)
+            m.zero_(), v.zero_(), step.zero_()
+
+        def rewind(adv0):
+            adv.copy_(adv0), input_val.copy_(adv0)
+            o_bestdist.fill_(1e10), o_bestscore.fill_(-1), o_bestattack.zero_()
+            begin_step()
+
+        c = self._loop_cache = dict(key=key, plan=plan, body=body, begin_step=begin_step, rewind=rewind, graphs=None, adv=adv,
+                                    ori=ori, m=m, v=v, o_bestattack=o_bestattack, input_val=input_val, X=X, stats=stats,
+                                    arg=arg, rot=rot, idx=idx, inv=inv, rot_pin=rot_pin, idx_pin=idx_pin, inv_pin=inv_pin,
+                                    nn_d=nn_d, nn_idx=nn_idx, step=step, pred=pred, goal_s=goal_s, goal=goal, w=w,
+                                    bestdist=bestdist, o_bestdist=o_bestdist, bestscore=bestscore, o_bestscore=o_bestscore,
+                                    uploaded=[torch.cuda.Event(), torch.cuda.Event()])
+        return c
+
+    def _draw_block(self, c, half, count, K):
+        """`count` iterations' rotations (and resampling indices with their inverse tables) into pinned block `half`, in
+        the order the autograd path draws them: per view torch.randn(1), random.random(), random.sample(range(1, 2K), K)."""
+        t0 = time.perf_counter()
+        rot = c["rot_pin"].numpy()
+        idx = c["idx_pin"].numpy() if c["idx_pin"] is not None else None
+        inv = c["inv_pin"].numpy() if c["inv_pin"] is not None else None
+        for it in range(count):
+            for e in range(c["plan"]["E"]):
+                rot[half, it, e] = _rotation_draw()
+                if idx is not None:
+                    idx[half, it, e] = random.sample(range(1, K * 2), K)
+                    _inverse_columns(idx[half, it, e] % K, K, inv[half, it, e])
+        self.draw_seconds += time.perf_counter() - t0
+
+    def _run_iterations(self, c, K):
+        """One binary-search step's num_iter iterations: block n of LOOP_BLOCK iterations reads rows (n mod 2) LOOP_BLOCK ...
+        of the tables (the step word counts from 0); its draws are uploaded in front of its replay, and the next block's
+        are made while it runs — never more than num_iter * EOT_VIEWS sets per step."""
+        LB, E = self.LOOP_BLOCK, c["plan"]["E"]
+        left = self.num_iter
+        if E and left:
+            c["uploaded"][0].synchronize()
+            self._draw_block(c, 0, min(LB, left), K)
+        n = 0
+        while left > 0:
+            cnt, half = min(LB, left), n % 2
+            if E:
+                rows = slice(half * LB, half * LB + cnt)
+                for nm in ("rot", "idx", "inv"):
+                    if c[nm] is not None:
+                        c[nm][rows].copy_(c[nm + "_pin"][half, :cnt], non_blocking=True)
+                c["uploaded"][half].record()
+            if c["graphs"] is not None:
+                c["graphs"].run(cnt)
+            else:
+                for _ in range(cnt):
+                    c["body"]()
+            left -= cnt
+            n += 1
+            if E and left:
+                c["uploaded"][n % 2].synchronize()      # the pinned block about to be rewritten has been read
+                self._draw_block(c, n % 2, min(LB, left), K)
+
+    def _attack_device_loop(self, plan, adv_data, ori_data, goal, B, K):
+        dev = self.device
+        c = self._device_loop_state(plan, B, K)
+        S = 1 + plan["E"]
+        lower_bound = np.zeros((B,))
+        upper_bound = np.ones((B,)) * self.max_weight
+        current_weight = np.ones((B,)) * self.init_weight
+        self.draw_seconds = 0.0
+        with torch.no_grad():
+            c["ori"].copy_(ori_data)
+            c["goal"].copy_(goal)
+            c["goal_s"].copy_(goal.repeat(S))
+            c["w"].fill_(float(self.init_weight))
+            c["rewind"](adv_data)
+            if self.graph and c["graphs"] is None and self.num_iter > 0 and self.binary_step > 0:
+                # capture once (after eager warm-up passes on a side stream, as torch requires), then rewind the state
+                c["graphs"] = _graphed.LoopGraph(c["body"], dev, 2, counts=(1, self.LOOP_BLOCK), owners=(plan["victim"],))
+                c["rewind"](adv_data)
+            goal_np = goal.cpu().numpy()
+            for binary_step in range(self.binary_step):
+                c["begin_step"]()
+                c["w"].copy_(ops.h2d(torch.from_numpy(current_weight).float(), dev))
+                self._run_iterations(c, K)
+                # adjust weight factor (:283-303) — one host read per binary-search step
+                bs, bd, obd = c["bestscore"].cpu().numpy(), c["bestdist"].cpu().numpy(), c["o_bestdist"].cpu().numpy()
+                for e in range(B):
+                    hit = (bs[e] == goal_np[e]) if self.whether_target else (bs[e] != goal_np[e])
+                    if hit and bs[e] != -1 and bd[e] <= obd[e]:
+                        lower_bound[e] = max(lower_bound[e], current_weight[e])
+                    else:
+                        upper_bound[e] = min(upper_bound[e], current_weight[e])
+                    current_weight[e] = (lower_bound[e] + upper_bound[e]) / 2.
+            fail_idx = torch.from_numpy(lower_bound == 0.).to(dev)
+            o_bestattack = torch.where(fail_idx[:, None, None], c["input_val"], c["o_bestattack"])
+            o_bestdist = c["o_bestdist"].double()
+        success_num = int((lower_bound > 0.).sum())
+        if self.verbose:
+            print('Successfully attack {}/{}   pred: {}'.format(success_num, B, c["pred"][:B].tolist()))
+        return (o_bestdist.cpu().numpy(), o_bestattack.double().cpu().numpy().transpose((0, 2, 1)), success_num)
 
     def attack(self, data, target=torch.Tensor([0]), origin_label=torch.Tensor([105])):
         """data [B,K,3] (or [B,3,K]); target [B] (targeted) / origin_label [B] (untargeted).
@@ -126,6 +357,10 @@ class CW:
 
         # ONE start point for the whole search: later binary steps continue from the previous step's iterate (:88-93)
         adv_data = ori_data.clone().detach() + torch.randn((B, 3, K)).to(dev) * 1e-7
+        plan = self._device_loop_plan(B, K) if self.device_loop else None
+        self.last_path = "device_loop" if plan is not None else "autograd"
+        if plan is not None:
+            return self._attack_device_loop(plan, adv_data, ori_data, goal, B, K)
         input_val = adv_data.detach().clone()
         for binary_step in range(self.binary_step):
             adv_data.requires_grad_()

@@ -1152,6 +1152,119 @@ def knn_attack_scales(N, k, B, up_chamfer, up_knn):
 
 
 # ------------------------------------------------------------------------------------------------------
+# the additional-experiments CW (EOT) loop: the two launches around its stacked victim pass (csrc/eot.hip)
+# ------------------------------------------------------------------------------------------------------
+EOT_MAX_POINTS = 8192       # PC3D_EOT_MAX_POINTS
+EOT_MAX_VIEWS = 16          # PC3D_EOT_MAX_VIEWS
+EOT_DIST_KINDS = {"none": 0, "l2": 1, "chamfer": 2}
+
+
+def _eot_dense(who, t, name, shape, dtype, dev):
+    if t is None:
+        return
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() \
+            or t.device != dev:
+        raise ValueError(f"{who}: {name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on the iterate's device")
+
+
+def _eot_step(who, step, dev):
+    if isinstance(step, torch.Tensor):
+        if step.dtype != torch.int32 or step.device != dev:
+            raise TypeError(f"{who}: the step word must be an int32 tensor on the iterate's device")
+        return step.data_ptr(), 0
+    return 0, int(step)
+
+
+def _eot_sizes(who, adv, rot):
+    _check(adv, "adv")
+    if adv.dim() != 3 or adv.shape[1] != 3 or not adv.is_contiguous():
+        raise ValueError(f"{who}: adv must be a contiguous [B,3,K] tensor, got {tuple(adv.shape)}")
+    B, _, K = adv.shape
+    if not 1 <= K <= EOT_MAX_POINTS:
+        raise ValueError(f"{who}: K={K} out of range [1, {EOT_MAX_POINTS}]")
+    T, E = (0, 0) if rot is None else tuple(rot.shape[:2])
+    if rot is not None:
+        if rot.dim() != 4 or not 1 <= E <= EOT_MAX_VIEWS or T < 1:
+            raise ValueError(f"{who}: rot must be [T,E,3,3] with 1 <= E <= {EOT_MAX_VIEWS}, got {tuple(rot.shape)}")
+        _eot_dense(who, rot, "rot", (T, E, 3, 3), torch.float32, adv.device)
+    return B, K, T, E
+
+
+def eot_prepare(adv, ori, rot=None, idx=None, renorm=False, step=0, out=None, stats=None, arg=None):
+    """The stacked victim input of one additional-experiments CW iteration (pc3d_eot_prepare_f32): X [(1+E) B,3,K],
+    slot-major, slot 0 the iterate and slot e >= 1 its e-th rotated view rot[step mod T, e-1] ori + (adv - ori), each
+    renormalised with `renorm`, the views resampled through idx [T,E,K] (int32) when given. rot None: no views (E = 0).
+    `step` (int32 device word or int) selects the table row. Returns (X, stats [(1+E) B,4], arg [(1+E) B])."""
+    who = "eot_prepare"
+    B, K, T, E = _eot_sizes(who, adv, rot)
+    dev = adv.device
+    _eot_dense(who, ori, "ori", adv.shape, torch.float32, dev)
+    if idx is not None and rot is None:
+        raise ValueError("eot_prepare: resampling needs views (rot)")
+    _eot_dense(who, idx, "idx", (T, E, K), torch.int32, dev)
+    S = 1 + E
+    X = out if out is not None else torch.empty((S * B, 3, K), dtype=torch.float32, device=dev)
+    stats = stats if stats is not None else torch.empty((S * B, 4), dtype=torch.float32, device=dev)
+    arg = arg if arg is not None else torch.empty((S * B,), dtype=torch.int32, device=dev)
+    _eot_dense(who, X, "out", (S * B, 3, K), torch.float32, dev)
+    _eot_dense(who, stats, "stats", (S * B, 4), torch.float32, dev)
+    _eot_dense(who, arg, "arg", (S * B,), torch.int32, dev)
+    step_dev, step_host = _eot_step(who, step, dev)
+    with torch.cuda.device(dev):
+        _lib.call("pc3d_eot_prepare_f32", adv.data_ptr(), ori.data_ptr(), B, K, E, T, _ptr(rot), _ptr(idx),
+                  1 if renorm else 0, step_dev, step_host, X.data_ptr(), stats.data_ptr(), arg.data_ptr(), _stream())
+    return X, stats, arg
+
+
+def eot_update(adv, ori, gx, m, v, step, lr, pred, goal, untarget, bestdist, bestscore, o_bestdist, o_bestscore, o_bestattack,
+               rot=None, inv=None, renorm=False, stats=None, arg=None, input_val=None, dist_val=None, dist_kind="chamfer",
+               w=None, nn_idx=None, batch_mean=None, one_d=True, box=0.4, betas=(0.9, 0.999), eps=1e-8, g_out=None):
+    """The rest of the iteration as one launch (pc3d_eot_update_f32): the record block on the iterate as it stands, the
+    gradient of the adversarial term from the stacked pass's input gradient gx [(1+E) B,3,K] (views 1 .. E through the
+    inverse resampling table inv [T,E,K,2] and, with `renorm`, through the renormalisation on eot_prepare's stats / arg),
+    the gradient of the distance term (dist_kind in EOT_DIST_KINDS; w [B] float32; nn_idx [B,K] int32 for Chamfer;
+    batch_mean: the batch size of the loss mean, default B), Adam and, with one_d, the z-only box. adv / m / v and the
+    best-so-far buffers are updated IN PLACE; `step` (int32 device word or int >= 1) is Adam's step number, the tables are
+    read at row (step - 1) mod T. g_out [B,3,K] (optional) receives the total gradient Adam consumes."""
+    who = "eot_update"
+    B, K, T, E = _eot_sizes(who, adv, rot)
+    dev = adv.device
+    f32, i32, i64 = torch.float32, torch.int32, torch.int64
+    for nm, t in (("ori", ori), ("m", m), ("v", v), ("o_bestattack", o_bestattack), ("input_val", input_val),
+                  ("g_out", g_out)):
+        _eot_dense(who, t, nm, adv.shape, f32, dev)
+    S = 1 + E
+    _eot_dense(who, gx, "gx", (S * B, 3, K), f32, dev)
+    if inv is not None and rot is None:
+        raise ValueError("eot_update: resampling needs views (rot)")
+    _eot_dense(who, inv, "inv", (T, E, K, 2), i32, dev)
+    if renorm and (stats is None or arg is None):
+        raise ValueError("eot_update: renorm needs eot_prepare's stats and arg")
+    _eot_dense(who, stats, "stats", (S * B, 4), f32, dev)
+    _eot_dense(who, arg, "arg", (S * B,), i32, dev)
+    if pred.dtype != i64 or pred.dim() != 1 or pred.shape[0] < B or not pred.is_contiguous() or pred.device != dev:
+        raise ValueError("eot_update: pred must be a contiguous int64 vector of at least B entries (slot 0 first)")
+    for nm, t, dt in (("goal", goal, i64), ("bestdist", bestdist, f32), ("bestscore", bestscore, i64),
+                      ("o_bestdist", o_bestdist, f32), ("o_bestscore", o_bestscore, i64), ("dist_val", dist_val, f32),
+                      ("w", w, f32)):
+        _eot_dense(who, t, nm, (B,), dt, dev)
+    dk = EOT_DIST_KINDS[dist_kind] if isinstance(dist_kind, str) else int(dist_kind)
+    if dk == 2 and nn_idx is None:
+        raise ValueError("eot_update: the Chamfer term needs nn_idx")
+    _eot_dense(who, nn_idx, "nn_idx", (B, K), i32, dev)
+    step_dev, step_host = _eot_step(who, step, dev)
+    with torch.cuda.device(dev):
+        _lib.call("pc3d_eot_update_f32", adv.data_ptr(), ori.data_ptr(), gx.data_ptr(), m.data_ptr(), v.data_ptr(), B, K, E, T,
+                  _ptr(rot), _ptr(inv), 1 if renorm else 0, _ptr(stats), _ptr(arg), pred.data_ptr(), goal.data_ptr(),
+                  1 if untarget else 0, bestdist.data_ptr(), bestscore.data_ptr(), o_bestdist.data_ptr(),
+                  o_bestscore.data_ptr(), o_bestattack.data_ptr(), _ptr(input_val), _ptr(dist_val), _ptr(g_out), dk, _ptr(w),
+                  _ptr(nn_idx),
+                  int(batch_mean if batch_mean is not None else B), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                  1 if one_d else 0, float(box), step_dev, step_host, _stream())
+    return adv
+
+
+# ------------------------------------------------------------------------------------------------------
 # CW-family loop: independent pieces carried by launches that exist anyway (csrc/linear_riders.hip, pointmlp.hip)
 # ------------------------------------------------------------------------------------------------------
 def _linear_args(who, X, W, bias, relu, gate, out, slope, gate_slope):

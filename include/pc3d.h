@@ -1065,6 +1065,50 @@ int pc3d_knn_attack_update_f32(float* adv, int64_t a_bs, int64_t a_ps, int64_t a
                                float budget, int clip_mode, float alpha, float c_chamfer, float c_knn,
                                const int32_t* step_dev, int step_host, void* stream);
 
+/* The additional-experiments CW (attack/additional_exp/CW_attack.py) around ONE stacked victim pass per iteration. Every
+ * point tensor is a contiguous [B,3,K]; K <= PC3D_EOT_MAX_POINTS, 0 <= E <= PC3D_EOT_MAX_VIEWS views.
+ * pc3d_eot_prepare_f32 writes the victim input X [(1+E) B,3,K], slot-major (row s B + b), one workgroup per (slot, cloud):
+ *   slot 0 = adv[b]; slot e >= 1 = rot[t,e-1] ori[b] + (adv[b] - ori[b]) with rot [T,E,3,3] row-major (bmm's product, summed
+ *   left to right) at table row t = step mod T (*step_dev, or step_host), the rotation shared by the batch;
+ *   renorm != 0: every slot is centred on its mean and divided by its largest point norm (both reductions in a fixed order;
+ *   the LOWEST index wins a tie); stats [(1+E) B,4] = centroid, scale and arg [(1+E) B] = the arg-max are written either way
+ *   (0, 0, 0, 1 and 0 without renorm);
+ *   idx [T,E,K] int32 (NULL: none): column j of slot e >= 1 is column idx[t,e-1,j] mod K of that slot's cloud (K of the 2K
+ *   columns of cat((x, x), 2)); slot 0 is never resampled.
+ * pc3d_eot_update_f32 does the rest of the iteration, one workgroup per cloud, without float atomics (a cloud's bits depend
+ * on neither the batch nor the launch); the step number t' >= 1 (*step_dev, or step_host) is the one Adam uses and the
+ * tables are read at row (t' - 1) mod T, the row the prepare launch read before the victim's tail advanced the word:
+ *   record   dist = w[b] d(adv, ori): dist_kind 2 Chamfer adv -> ori, the mean over i of |adv_i - ori[nn_idx[i]]|^2 (direct
+ *            form; nn_idx [B,K] from pc3d_nn_f32, clamped), 1 L2 (Frobenius norm), 0 none; the decisions of the CW loops
+ *            (strict <, a NaN distance updates nothing) on pred[b] (slot 0's prediction) and goal[b] into bestdist /
+ *            bestscore / o_bestdist / o_bestscore [B]; o_bestattack[b] = adv[b] when it becomes the overall best;
+ *            input_val = adv and dist_val[b] = dist (either may be NULL); g_out [B,3,K] (may be NULL) receives the total
+ *            gradient Adam consumes;
+ *   gradient of the adversarial term: for e = 1 .. E ascending, gx[e B + b] (the stacked pass's input gradient; with E > 0
+ *            slot 0's rows are ignored, with E == 0 they are the gradient) gathered through inv [T,E,K,2] int32 (NULL: no
+ *            resampling): the at most two columns that drew point i, or -1; then with renorm != 0 through the
+ *            renormalisation on the stored stats / arg: g_q = g_y / s, ds = -sum(g_y . q) / s^2 added to the arg-max point
+ *            along q / |q|, g_p = g_q - mean g_q (fixed summation order); the views are summed into the iterate's gradient;
+ *   gradient of the distance term: Chamfer 2 w[b] / (batch_mean K) (adv_i - ori[nn_idx[i]]); L2 w[b] / batch_mean
+ *            (adv - ori) / |adv - ori|_F (no guard at zero, as torch); batch_mean: the size of the batch of the loss mean;
+ *   Adam     torch's (pc3d_adam_clip_step_f32's arithmetic) on the sum; one_d != 0: x and y are copied from ori and z is
+ *            clamped to ori_z +- box. adv, m, v are updated in place.
+ * The update keeps the cloud's gradient accumulators in LDS, 12 bytes a point (96 KiB at the cap); the sums of the
+ * renormalisation's backward are accumulated in double. */
+#define PC3D_EOT_MAX_POINTS 8192
+#define PC3D_EOT_MAX_VIEWS 16
+int pc3d_eot_prepare_f32(const float* adv, const float* ori, int B, int K, int E, int T, const float* rot,
+                         const int32_t* idx, int renorm, const int32_t* step_dev, int step_host, float* X,
+                         float* stats, int32_t* arg, void* stream);
+int pc3d_eot_update_f32(float* adv, const float* ori, const float* gx, float* m, float* v, int B, int K, int E, int T,
+                        const float* rot, const int32_t* inv, int renorm, const float* stats, const int32_t* arg,
+                        const int64_t* pred, const int64_t* goal, int untarget, float* bestdist, int64_t* bestscore,
+                        float* o_bestdist, int64_t* o_bestscore, float* o_bestattack, float* input_val,
+                        float* dist_val, float* g_out, int dist_kind, const float* w, const int32_t* nn_idx,
+                        int batch_mean,
+                        double lr, double beta1, double beta2, double eps, int one_d, float box,
+                        const int32_t* step_dev, int step_host, void* stream);
+
 /* GeoA3's iteration after the victim's passes and the searches (attack/GeoA3/GeoA3_attack.py:139-181, :321-351, lp_clip
  * :92-102) as ONE launch, one workgroup per cloud; every point tensor is a contiguous [B,3,N]. In this order:
  *   record   pc3d_geoa3_record_f32's decisions on pred[b] (the loss launch's prediction), target[b], constrain[b] as it
