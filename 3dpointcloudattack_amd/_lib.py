@@ -88,6 +88,7 @@ SIGNATURES = {
     + _PTS + _PTS + [_I, _P],
     "pc3d_knn_f32": _PTS + _PTS + [_I, _I, _I, _I, _P, _P, _P],
     "pc3d_knn_hint_f32": _PTS + _PTS + [_I, _I, _I, _I, _P, _P, _P, _P],
+    "pc3d_knn_small_f32": _PTS + _PTS + [_I, _I, _I, _I, _P, _P],
     "pc3d_knn_bwd_f32": _PTS + _PTS + [_I, _I, _I, _I, _P, _P] + _PTS + _PTS + [_I, _P, _P],
     "pc3d_knn_self_bwd_f32": _PTS + [_I, _I, _I, _P, _P, _P] + _PTS + [_I, _P, _P],
     "pc3d_knn_outlier_loss_f32": [_P, _I, _I, _I, _F, _P, _P, _P],

@@ -13,8 +13,10 @@ a defended victim runs inside an attack loop and inside ``torch.cuda.graph``.
 ``DUPNet`` (SOR followed by the PU-Net upsampler, attack/SIadv/baselines/defense/DUP_Net) is exported from here too; it lives
 under the reference's import path.
 
-``Defended(model, head)`` is the composition as an ``nn.Module``; ``evaluate_defended`` is the after-the-attack table
-row. There is no CPU fallback: tensors must live on the GPU.
+``Defended(model, head)`` is the composition as an ``nn.Module`` (any model, any head, autograd);
+``FusedDefended(model, head)`` is a PointNet victim behind SOR that keeps the fused entry points, so the device-side
+attack loops run on it; ``evaluate_defended`` is the after-the-attack table row. There is no CPU fallback: tensors must
+live on the GPU.
 
 Deviation from the reference (SOR): ``K > npoint`` raises ``ValueError`` from the shapes alone. The reference's
 ``process_data`` only survives that case when the number of kept points happens to be <= npoint (it asserts otherwise),
@@ -32,6 +34,12 @@ from . import ops
 # profiles/defense_bench.json): the fused form puts one workgroup on each of B compute units while the search
 # of the two-launch form fills the chip, and loses from K = 1024 up at B = 32.
 SOR_FUSED = False
+# The search FusedDefended puts in front of pc3d_sor_select_f32: the list-per-lane kernel (pc3d_knn_small_f32, True; k <= 8)
+# or the wave-per-query kernel of ops.knn_raw (False). The same bits either way. Measured on MI355X
+# (tools/bench_fused_defended.py, profiles/fused_defended_bench.json): 9.3 against 21.3 us at B = 32,
+# K = 1024, k1 = 3, run-to-run spread 0.08 us; faster at K = 2048 / 4096 and at k1 = 9 too.
+SOR_SMALL_SEARCH = True
+SOR_SMALL_MAX_K = 8
 SOR_FUSED_MAX_POINTS = 4096
 SOR_MAX_POINTS = 8192
 SRS_DEVICE_MAX_POINTS = 4096
@@ -51,14 +59,19 @@ def _sor_shapes(K, k, npoint):
         raise ValueError(f"SORDefense: k={k} exceeds the search's limit of 63 neighbours")
 
 
-def sor_select(x, k=2, alpha=1.1, npoint=1024, cf=True, fused=None, want_stats=False):
+def sor_select(x, k=2, alpha=1.1, npoint=1024, cf=True, fused=None, want_stats=False, search=None):
     """SOR forward without autograd on x [B,3,K] (cf) or [B,K,3]: dict(out (same layout as x, npoint points), count [B]
     int32, rank [B,K] int32, src [B,npoint] int32) and with want_stats also v [B,K], thr [B] (fp32 copies of the fp64
-    values the mask was taken with)."""
+    values the mask was taken with). search (two-launch form only): None / "knn" = ops.knn_raw, "small" = the values-only
+    list-per-lane search ops.knn_small_dists (k <= 8) — the same distance bits, hence the same selection."""
     p, bs, ps, cs, B, K = ops._pts(x, cf, "x")
     _sor_shapes(K, int(k), int(npoint))
     k1 = int(k) + 1
     fused = SOR_FUSED if fused is None else bool(fused)
+    if search not in (None, "knn", "small"):
+        raise ValueError(f"sor_select: search={search!r} is not one of None, 'knn', 'small'")
+    if search == "small" and (fused or int(k) > SOR_SMALL_MAX_K):
+        raise ValueError(f"sor_select: search='small' takes the two-launch form and k <= {SOR_SMALL_MAX_K} (k={k}, fused={fused})")
     if fused and (K > SOR_FUSED_MAX_POINTS or k1 > 9):
         raise ValueError(f"the fused SOR launch takes K <= {SOR_FUSED_MAX_POINTS} and k <= 8 (K={K}, k={k})")
     dev = x.device
@@ -75,7 +88,7 @@ def sor_select(x, k=2, alpha=1.1, npoint=1024, cf=True, fused=None, want_stats=F
             _lib.call("pc3d_sor_fused_f32", p, bs, ps, cs, B, K, k1, float(alpha), int(npoint), d.data_ptr(), ops._ptr(v),
                       ops._ptr(thr), count.data_ptr(), rank.data_ptr(), src.data_ptr(), op, obs, opst, ocs, ops._stream())
     else:
-        d, _ = ops.knn_raw(x, x, k1, cf, cf)
+        d = ops.knn_small_dists(x, x, k1, cf, cf) if search == "small" else ops.knn_raw(x, x, k1, cf, cf)[0]
         with torch.cuda.device(dev):
             _lib.call("pc3d_sor_select_f32", d.data_ptr(), p, bs, ps, cs, B, K, k1, float(alpha), int(npoint), ops._ptr(v),
                       ops._ptr(thr), count.data_ptr(), rank.data_ptr(), src.data_ptr(), op, obs, opst, ocs, ops._stream())
@@ -85,11 +98,13 @@ def sor_select(x, k=2, alpha=1.1, npoint=1024, cf=True, fused=None, want_stats=F
     return res
 
 
-def sor_backward(g, count, rank, cf=True):
-    """grad_x of the SOR copies for upstream g (layout of the output): [B,3,K] (cf) or [B,K,3]."""
+def sor_backward(g, count, rank, cf=True, out=None):
+    """grad_x of the SOR copies for upstream g (layout of the output): [B,3,K] (cf) or [B,K,3]; written into `out` if given."""
     gp, gbs, gps, gcs, B, npoint = ops._pts(g, cf, "grad_out")
     K = rank.shape[1]
-    grad = torch.empty((B, 3, K) if cf else (B, K, 3), dtype=torch.float32, device=g.device)
+    grad = torch.empty((B, 3, K) if cf else (B, K, 3), dtype=torch.float32, device=g.device) if out is None else out
+    if tuple(grad.shape) != ((B, 3, K) if cf else (B, K, 3)):
+        raise ValueError(f"sor_backward: out has shape {tuple(grad.shape)}, the input cloud's is {(B, 3, K) if cf else (B, K, 3)}")
     rp, rbs, rps, rcs, _, _ = ops._pts(grad, cf, "grad_x")
     with torch.cuda.device(g.device):
         _lib.call("pc3d_sor_bwd_f32", gp, gbs, gps, gcs, count.data_ptr(), rank.data_ptr(), B, K, npoint, rp, rbs, rps, rcs,
@@ -101,8 +116,9 @@ class _SorFn(torch.autograd.Function):
     """The mask is a constant; the gradient flows back to x through the copies."""
 
     @staticmethod
-    def forward(ctx, x, k, alpha, npoint, fused):
-        r = sor_select(x, k, alpha, npoint, cf=True, fused=fused)
+    def forward(ctx, x, k, alpha, npoint, fused, search=None):
+        r = sor_select(x, k, alpha, npoint, cf=True, fused=fused, search=search)
+        ctx.n_extra = 4 if search is None else 5         # one gradient slot per argument apply() was given
         ctx.save_for_backward(r["count"], r["rank"])
         ctx.mark_non_differentiable(r["count"], r["src"])
         ctx.set_materialize_grads(False)
@@ -111,11 +127,11 @@ class _SorFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _gc, _gs):
         if g is None:
-            return None, None, None, None, None
+            return (None,) * (1 + ctx.n_extra)
         count, rank = ctx.saved_tensors
         if g.dtype != torch.float32:
             g = g.float()
-        return sor_backward(g, count, rank, cf=True), None, None, None, None
+        return (sor_backward(g, count, rank, cf=True),) + (None,) * ctx.n_extra
 
 
 class SORDefense(nn.Module):
@@ -232,6 +248,120 @@ class Defended(nn.Module):
 
     def forward(self, x):
         return _graphed.wrap(self.model, enable=self.graph)(self.head(x))
+
+
+class _DefendedCtx:
+    """What FusedDefended.fused_forward hands to fused_input_grad: the inner victim's ctx and SOR's (count, rank)."""
+    __slots__ = ("inner", "count", "rank")
+
+    def __init__(self, inner, count, rank):
+        self.inner, self.count, self.rank = inner, count, rank
+
+    def fused_input_grad(self, g_logits, out=None, g_c2=None):
+        from .model import pointnet as _pointnet
+        g = _pointnet.fused_input_grad(self.inner, g_logits, g_c2=g_c2)
+        return sor_backward(g, self.count, self.rank, cf=True, out=out)
+
+
+class FusedDefended(nn.Module):
+    """``PointNetCls`` behind a ``SORDefense`` WITH the fused entry points the device-side attack loops ask for, so a
+    defended victim runs inside them (CW, the additional-experiments CW, kNN, SI-Adv's white-box loop, AOF, CWTAOF, ISO,
+    CWAdd / CWAddClusters) instead of on their autograd paths. ``Defended`` stays the general composition (any model, any
+    head, autograd); this class is the one pair with fixed shapes and no host round trip on both sides.
+
+    model: a ``PointNetCls`` (plain or feature_transform=True; a GraphedVictim around one is unwrapped). head: a
+    ``SORDefense``. Anything else raises TypeError: SRSDefense (a fresh draw per forward) and DUPNet (the upsampler's
+    backward) are out of scope. The head's k, alpha and npoint are read ONCE, here, and are read-only afterwards (a
+    captured loop bakes them in); they also sit in a non-persistent buffer, so ``graphed.weights_key`` tells two wrappers
+    of one model apart while ``state_dict()`` is the inner model's.
+
+    Every fused call is four steps — the search, pc3d_sor_select_f32, the inner victim's fused call on the [B,3,npoint]
+    output, pc3d_sor_bwd_f32 — without a host sync and with every allocation from torch's pool, so it captures into a
+    hipGraph. The mask is a constant of the backward, as in ``_SorFn``: the gradient is exactly zero on dropped points.
+    ``forward`` is the differentiable composition, bit-equal to ``Defended(model, head)(x)``."""
+    deterministic_forward = True
+    has_fused_attack_update = False      # no riders iteration: CW takes fused_attack_grad + one update launch
+
+    def __init__(self, model, head):
+        super().__init__()
+        from .model import pointnet as _pointnet
+        model = _graphed.unwrap(model)
+        if not isinstance(model, _pointnet.PointNetCls):
+            raise TypeError(f"FusedDefended: model must be a PointNetCls (plain or feature_transform=True), got "
+                            f"{type(model).__name__}; use Defended for any other victim")
+        if not isinstance(head, SORDefense):
+            raise TypeError(f"FusedDefended: head must be a SORDefense, got {type(head).__name__}; SRSDefense and DUPNet "
+                            "heads run behind Defended (autograd path)")
+        k, alpha, npoint = int(head.k), float(head.alpha), int(head.npoint)
+        if not 1 <= k <= 63:
+            raise ValueError(f"FusedDefended: k={k} out of range [1, 63]")
+        self.model = model
+        object.__setattr__(self, "_settings", (k, alpha, npoint))
+        self.register_buffer("sor_settings", torch.tensor([k, alpha, npoint], dtype=torch.float64), persistent=False)
+        self.train(model.training)
+
+    k = property(lambda self: self._settings[0])
+    alpha = property(lambda self: self._settings[1])
+    npoint = property(lambda self: self._settings[2])
+
+    def state_dict(self, *a, **kw):
+        return self.model.state_dict(*a, **kw)
+
+    def load_state_dict(self, *a, **kw):
+        return self.model.load_state_dict(*a, **kw)
+
+    def _require_fused(self, x):
+        self.model._require_fused(x)
+
+    def _search(self):
+        return "small" if SOR_SMALL_SEARCH and self.k <= SOR_SMALL_MAX_K else None
+
+    def _select(self, x):
+        self._require_fused(x)
+        if x.dim() != 3 or x.shape[1] != 3:
+            raise ValueError(f"FusedDefended: expected a [B,3,K] tensor, got {tuple(x.shape)}")
+        k, alpha, npoint = self._settings
+        return sor_select(x, k, alpha, npoint, cf=True, fused=False, search=self._search())
+
+    def fused_pack(self):
+        """The inner victim's weight pack (what a loop compares to tell whether the weights it captured are current)."""
+        from .model import pointnet as _pointnet
+        return _pointnet.fused_pack(self.model)
+
+    def forward(self, x):
+        self._require_fused(x)
+        if x.dim() != 3 or x.shape[1] != 3:
+            raise ValueError(f"FusedDefended: expected a [B,3,K] tensor, got {tuple(x.shape)}")
+        if x.dtype != torch.float32:
+            x = x.float()
+        k, alpha, npoint = self._settings
+        out, _, _ = _SorFn.apply(x, k, alpha, npoint, False, self._search() or "knn")
+        return self.model(out)
+
+    def fused_forward(self, x, tail=True):
+        """(logits [B,classes] PRE-softmax or None, ctx) of the defended victim; ctx feeds fused_input_grad."""
+        from .model import pointnet as _pointnet
+        sel = self._select(x)
+        logits, inner = _pointnet.fused_forward(self.model, sel["out"], tail)
+        return logits, _DefendedCtx(inner, sel["count"], sel["rank"])
+
+    def fused_input_grad(self, ctx, g_logits, out=None, g_c2=None):
+        """dL/dx [B,3,K] for an upstream gradient on the logits (or on the last hidden layer, g_c2)."""
+        return ctx.fused_input_grad(g_logits, out=out, g_c2=g_c2)
+
+    def fused_loss_and_grad(self, x, target, kind, kappa=0.0, scale=None):
+        """PointNetCls.fused_loss_and_grad of the defended victim: (logp, pred, loss, dL/dx [B,3,K])."""
+        sel = self._select(x)
+        logp, pred, loss, g = self.model.fused_loss_and_grad(sel["out"], target, kind, kappa,
+                                                             scale=1.0 / x.shape[0] if scale is None else scale)
+        return logp, pred, loss, sor_backward(g, sel["count"], sel["rank"], cf=True)
+
+    def fused_attack_grad(self, x, target, kind, kappa=0.0, pred_out=None, step=None, scale=None):
+        """PointNetCls.fused_attack_grad of the defended victim: (pred, loss, dL/dx [B,3,K])."""
+        sel = self._select(x)
+        pred, loss, g = self.model.fused_attack_grad(sel["out"], target, kind, kappa, pred_out=pred_out, step=step,
+                                                     scale=1.0 / x.shape[0] if scale is None else scale)
+        return pred, loss, sor_backward(g, sel["count"], sel["rank"], cf=True)
 
 
 def evaluate_defended(model, head, clouds, labels, batch=32):

@@ -323,6 +323,8 @@ def _fused_sources(model):
 def fused_pack(model):
     """The launch-minimal path's weight pack, rebuilt when any of the folded caches it was built from was re-folded.
     Callers that bake its pointers into a hipGraph keep the returned dict alive next to the graph."""
+    if not isinstance(model, PointNetCls) and hasattr(model, "fused_pack"):
+        return model.fused_pack()          # a wrapper around a PointNetCls (defense.FusedDefended): the inner victim's pack
     pk = model.__dict__.get("_fused_cache")
     if pk is None or any(a is not b for a, b in zip(pk["src"], _fused_sources(model))):
         pk = _fused_pack(model)
@@ -348,7 +350,10 @@ def _fused_pack(model):
 def fused_forward(model, x, tail=True):
     """Launch-minimal forward of PointNetCls: 2 tower launches (+2 folds) + 5 head launches, no autograd graph.
     Returns (logits [B,k] PRE-softmax, ctx) — ctx feeds fused_input_grad.
-    A feature-transform victim: 3 tower launches (+3 folds), the W2 fold, 9 head launches; ctx has a 13th item."""
+    A feature-transform victim: 3 tower launches (+3 folds), the W2 fold, 9 head launches; ctx has a 13th item.
+    A model that is not a PointNetCls but brings its own ``fused_forward`` (defense.FusedDefended) runs that one."""
+    if not isinstance(model, PointNetCls) and hasattr(model, "fused_forward"):
+        return model.fused_forward(x, tail)
     model._require_fused(x)
     pk = fused_pack(model)
     w1s, b1s, w2s, b2s, w3s, b3s = pk["s"]
@@ -372,7 +377,10 @@ def fused_forward(model, x, tail=True):
 
 
 def fused_input_grad(ctx, g_logits, out=None, g_c2=None):
-    """Backward-to-input of fused_forward for an upstream gradient on the logits: 5 head launches + 2 tower launches."""
+    """Backward-to-input of fused_forward for an upstream gradient on the logits: 5 head launches + 2 tower launches.
+    A ctx that brings its own ``fused_input_grad`` (defense.FusedDefended's) runs that one."""
+    if hasattr(ctx, "fused_input_grad"):
+        return ctx.fused_input_grad(g_logits, out=out, g_c2=g_c2)
     x, pk, pooled_s, idx_s, a1, a2, trans, idx, c1, c2, masks_s, masks = ctx[:12]
     w1c_t, w2c_t, w3c_t = pk["c_t"]
     w1s_t, w2s_t, w3s_t = pk["s_t"]

@@ -850,6 +850,22 @@ def knn_raw(q, r, K, q_cf=False, r_cf=False):
     return d, i
 
 
+def knn_small_dists(q, r, k1, q_cf=False, r_cf=False):
+    """dists [B,N,k1] f32: the k1 (2 .. 9) smallest squared distances of every query, ascending, without indices — the
+    bits of ``knn_raw(q, r, k1)[0]`` from the list-per-lane kernel (pc3d_knn_small_f32, csrc/knn_small.hip)."""
+    qp, qbs, qps, qcs, B, N = _pts(q, q_cf, "q")
+    rp, rbs, rps, rcs, B2, M = _pts(r, r_cf, "r")
+    if B != B2:
+        raise ValueError("q and r must have the same batch dimension")
+    k1 = int(k1)
+    if not (2 <= k1 <= min(9, M)):
+        raise ValueError(f"knn_small_dists: k1={k1} out of range [2, min(9, M={M})]")
+    d = torch.empty((B, N, k1), dtype=torch.float32, device=q.device)
+    with torch.cuda.device(q.device):
+        _lib.call("pc3d_knn_small_f32", qp, qbs, qps, qcs, rp, rbs, rps, rcs, B, N, M, k1, d.data_ptr(), _stream())
+    return d
+
+
 def knn_graph(pts, k, cf=False):
     """(idx [B,N,k+1] self first, idx[:, :, 1:], idx[:, :, :k]) — int32, contiguous — of the self-kNN graph of pts [B,N,3]:
     the graph and the two views CurveNet's blocks gather through, written by ONE launch (pc3d_knn_graph_i32)."""

@@ -632,6 +632,14 @@ int pc3d_knn_hint_f32(const float* q, int64_t q_bs, int64_t q_ps, int64_t q_cs,
                       int B, int N, int M, int K, float* dists, int32_t* idx, const int32_t* hint, void* stream);
 int pc3d_knn_graph_hint_i32(const float* pts, int64_t p_bs, int64_t p_ps, int64_t p_cs, int B, int N, int K, int32_t* idx,
                             int32_t* idx_noself, int32_t* idx_first, int k2, const int32_t* hint, void* stream);
+/* Values only, small k: dists [B,N,k1] = the k1 smallest squared distances of every query, ascending, 2 <= k1 <= 9,
+ * k1 <= M; no indices. Bit for bit the dists of pc3d_knn_f32 (same distance arithmetic, same key order, NaN stored as
+ * +inf, the same far sentinels up to the next multiple of 64 candidates): the k1 smallest keys of a multiset do not
+ * depend on the order of the scan. One query per lane with its list in registers (csrc/knn_small.hip); what the SOR
+ * defence needs of a search (k1 = 3, attack/SIadv/baselines/defense/drop_points/SOR.py:34-43). */
+int pc3d_knn_small_f32(const float* q, int64_t q_bs, int64_t q_ps, int64_t q_cs,
+                       const float* r, int64_t r_bs, int64_t r_ps, int64_t r_cs,
+                       int B, int N, int M, int k1, float* dists, void* stream);
 
 
 /* Backward of the K distances with upstream w [B,N,K]: grad_q dense, grad_r scattered (float atomics; when
