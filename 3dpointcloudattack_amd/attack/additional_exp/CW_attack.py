@@ -21,7 +21,8 @@ binary-search step); the resampling draws ``K`` of ``2K`` indices (the reference
 ``device_loop=True`` (PointNet victims, see ``CW._device_loop_plan``): the iteration is ONE stacked victim pass of the
 iterate and its ten views between pc3d_eot_prepare_f32 and pc3d_eot_update_f32 (csrc/eot.hip), replayed from a hipGraph
 without autograd; the rotations and resampling indices are still drawn on the host, in the same order, a block of
-iterations ahead.
+iterations ahead — or, with ``device_rng=True``, on the device by pc3d_eot_draw_f32 (a counter-based stream of its own, NOT
+draw-for-draw comparable with the reference: see ``CW.__init__``).
 """
 import random
 import time
@@ -105,10 +106,19 @@ class CW:
                  init_weight=10., max_weight=80., binary_step=10, num_iter=500, whether_target=True, whether_1d=True,
                  whether_renormalization=False,
                  whether_3Dtransform=False, whether_resample=False, device=None, verbose=False, graph=True,
-                 device_loop=False):
+                 device_loop=False, device_rng=False, seed=None):
         """`device_loop=True` runs the iteration as a captured chain of own kernels around ONE stacked victim pass when
         the victim, the functors and the cloud size allow it (_device_loop_plan), and silently the usual path otherwise;
-        `last_path` says which one the last attack() took: "device_loop" or "autograd"."""
+        `last_path` says which one the last attack() took: "device_loop" or "autograd".
+
+        `device_rng=True` (off by default) lets the device loop draw its rotations and resampling tables on the device
+        (ops.eot_draw) instead of on the host: one launch in front of every block of iterations, nothing consumed from
+        Python's `random`, and from torch's CPU generator only the start noise. The stream is the library's own function
+        of (seed, draw index, view) — the reference's distributions, not its draws — where iteration `it` of binary step
+        `bs` has draw index `draw_base + bs * num_iter + it`; `draw_base` (public, 0 at construction) advances by
+        binary_step * num_iter at the end of every device-drawn attack(), and setting it back reproduces a run.
+        `seed=None` takes torch.initial_seed() at the first use. It takes effect only where the device loop runs with
+        views; `last_draws` says what the last attack() did: "device", "host" or None (no views)."""
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.model = model.to(self.device)
         self.model.eval()
@@ -129,7 +139,11 @@ class CW:
         self.verbose = verbose
         self.graph = graph
         self.device_loop = device_loop
+        self.device_rng = bool(device_rng)
+        self.seed = seed
+        self.draw_base = 0
         self.last_path = None
+        self.last_draws = None                 # who drew the last attack()'s views: "device", "host" or None (no views)
         self.draw_seconds = 0.0                # host time the last device-loop attack() spent drawing rotations / indices
         self._loop_cache = None                # the device loop's buffers and captured graphs, kept from call to call
 
@@ -180,7 +194,10 @@ class CW:
         """Buffers (static: the graphs point at them), the iteration body and the captured graphs, rebuilt when the shape,
         a constant of the loop, the kernel flavour or the victim's weights change."""
         victim, dev = plan["victim"], self.device
-        key = (B, K, float(self.attack_lr), bool(self.graph), bool(ops._det()), _graphed.weights_key(victim),
+        device_draws = bool(self.device_rng and plan["E"])
+        if device_draws and self.seed is None:
+            self.seed = int(torch.initial_seed()) & 0x7FFFFFFFFFFFFFFF
+        key = (B, K, float(self.attack_lr), device_draws, int(self.seed) if device_draws else None, bool(self.graph), bool(ops._det()), _graphed.weights_key(victim),
                tuple(sorted((n, v) for n, v in plan.items() if n != "victim")))
         c = self._loop_cache
         if c is not None and c["key"] == key:
@@ -192,13 +209,15 @@ class CW:
         X = torch.zeros((S * B, 3, K), **f32) if plan["prepare"] else None
         stats = torch.zeros((S * B, 4), **f32) if plan["prepare"] else None
         arg = torch.zeros((S * B,), **i32) if plan["prepare"] else None
-        # the per-iteration tables: T = two blocks of rows on the device, two pinned blocks on the host
+        # the per-iteration tables: T = two blocks of rows on the device, two pinned blocks on the host (none of those when
+        # the device draws)
         rot = torch.zeros((T, E, 3, 3), **f32) if E else None
         idx = torch.zeros((T, E, K), **i32) if plan["resample"] else None
         inv = torch.zeros((T, E, K, 2), **i32) if plan["resample"] else None
-        rot_pin = torch.zeros((2, LB, E, 3, 3), dtype=torch.float32).pin_memory() if E else None
-        idx_pin = torch.zeros((2, LB, E, K), dtype=torch.int32).pin_memory() if plan["resample"] else None
-        inv_pin = torch.zeros((2, LB, E, K, 2), dtype=torch.int32).pin_memory() if plan["resample"] else None
+        host_draws = bool(E) and not device_draws
+        rot_pin = torch.zeros((2, LB, E, 3, 3), dtype=torch.float32).pin_memory() if host_draws else None
+        idx_pin = torch.zeros((2, LB, E, K), dtype=torch.int32).pin_memory() if host_draws and plan["resample"] else None
+        inv_pin = torch.zeros((2, LB, E, K, 2), dtype=torch.int32).pin_memory() if host_draws and plan["resample"] else None
         chamfer = plan["dist_kind"] == "chamfer"
         nn_d = torch.zeros((B, K), **f32) if chamfer else None
         nn_idx = torch.zeros((B, K), **i32) if chamfer else None
@@ -233,7 +252,7 @@ class CW:
             o_bestdist.fill_(1e10), o_bestscore.fill_(-1), o_bestattack.zero_()
             begin_step()
 
-        c = self._loop_cache = dict(key=key, plan=plan, body=body, begin_step=begin_step, rewind=rewind, graphs=None, adv=adv,
+        c = self._loop_cache = dict(key=key, plan=plan, device_draws=device_draws, body=body, begin_step=begin_step, rewind=rewind, graphs=None, adv=adv,
                                     ori=ori, m=m, v=v, o_bestattack=o_bestattack, input_val=input_val, X=X, stats=stats,
                                     arg=arg, rot=rot, idx=idx, inv=inv, rot_pin=rot_pin, idx_pin=idx_pin, inv_pin=inv_pin,
                                     nn_d=nn_d, nn_idx=nn_idx, step=step, pred=pred, goal_s=goal_s, goal=goal, w=w,
@@ -256,19 +275,26 @@ class CW:
                     _inverse_columns(idx[half, it, e] % K, K, inv[half, it, e])
         self.draw_seconds += time.perf_counter() - t0
 
-    def _run_iterations(self, c, K):
+    def _run_iterations(self, c, K, binary_step=0):
         """One binary-search step's num_iter iterations: block n of LOOP_BLOCK iterations reads rows (n mod 2) LOOP_BLOCK ...
         of the tables (the step word counts from 0); its draws are uploaded in front of its replay, and the next block's
-        are made while it runs — never more than num_iter * EOT_VIEWS sets per step."""
+        are made while it runs — never more than num_iter * EOT_VIEWS sets per step. With device draws the block's rows
+        are filled by ONE launch on the current stream in front of its replay (outside the graph: the host knows the draw
+        index), and the host neither draws nor waits."""
         LB, E = self.LOOP_BLOCK, c["plan"]["E"]
         left = self.num_iter
-        if E and left:
+        host_draws = bool(E) and not c["device_draws"]
+        n0 = self.draw_base + binary_step * self.num_iter      # the block's first draw index (device draws)
+        if host_draws and left:
             c["uploaded"][0].synchronize()
             self._draw_block(c, 0, min(LB, left), K)
         n = 0
         while left > 0:
             cnt, half = min(LB, left), n % 2
-            if E:
+            if c["device_draws"]:
+                ops.eot_draw(self.seed, n0, (half * LB, cnt), c["rot"], c["idx"], c["inv"])
+                n0 += cnt
+            elif E:
                 rows = slice(half * LB, half * LB + cnt)
                 for nm in ("rot", "idx", "inv"):
                     if c[nm] is not None:
@@ -281,7 +307,7 @@ class CW:
                     c["body"]()
             left -= cnt
             n += 1
-            if E and left:
+            if host_draws and left:
                 c["uploaded"][n % 2].synchronize()      # the pinned block about to be rewritten has been read
                 self._draw_block(c, n % 2, min(LB, left), K)
 
@@ -307,7 +333,7 @@ class CW:
             for binary_step in range(self.binary_step):
                 c["begin_step"]()
                 c["w"].copy_(ops.h2d(torch.from_numpy(current_weight).float(), dev))
-                self._run_iterations(c, K)
+                self._run_iterations(c, K, binary_step)
                 # adjust weight factor (:283-303) — one host read per binary-search step
                 bs, bd, obd = c["bestscore"].cpu().numpy(), c["bestdist"].cpu().numpy(), c["o_bestdist"].cpu().numpy()
                 for e in range(B):
@@ -320,6 +346,8 @@ class CW:
             fail_idx = torch.from_numpy(lower_bound == 0.).to(dev)
             o_bestattack = torch.where(fail_idx[:, None, None], c["input_val"], c["o_bestattack"])
             o_bestdist = c["o_bestdist"].double()
+        if c["device_draws"]:
+            self.draw_base += self.binary_step * self.num_iter      # the next batch sees other draws
         success_num = int((lower_bound > 0.).sum())
         if self.verbose:
             print('Successfully attack {}/{}   pred: {}'.format(success_num, B, c["pred"][:B].tolist()))
@@ -359,6 +387,10 @@ class CW:
         adv_data = ori_data.clone().detach() + torch.randn((B, 3, K)).to(dev) * 1e-7
         plan = self._device_loop_plan(B, K) if self.device_loop else None
         self.last_path = "device_loop" if plan is not None else "autograd"
+        if plan is not None:
+            self.last_draws = ("device" if self.device_rng else "host") if plan["E"] else None
+        else:
+            self.last_draws = "host" if self.whether_3Dtransform else None
         if plan is not None:
             return self._attack_device_loop(plan, adv_data, ori_data, goal, B, K)
         input_val = adv_data.detach().clone()

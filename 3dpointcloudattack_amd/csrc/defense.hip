@@ -179,12 +179,6 @@ __global__ __launch_bounds__(256) void sor_bwd_kernel(SorBwdArgs a) {
   op[2 * a.grad.cs] = gz;
 }
 
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {          // the splitmix64 finaliser
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
 // keys[i] = hash(seed, call, b, i) with the point index in the low bits (all keys distinct: a total order, so the network's
 // result does not depend on how it is scheduled); pads sort to the end. Ascending bitonic network over P = 2^p >= K keys,
 // a barrier after EVERY stage.
@@ -200,19 +194,7 @@ __global__ __launch_bounds__(1024) void srs_select_kernel(uint64_t seed, const i
     keys[i] = i < K ? ((h & ~lowmask) | (uint64_t)i) : ~0ull;
   }
   __syncthreads();
-  for (int k = 2; k <= P; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int t = tid; t < (P >> 1); t += T) {
-        const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
-        const uint64_t x = keys[lo], y = keys[hi];
-        const bool up = (lo & k) == 0;
-        if ((x > y) == up) {
-          keys[lo] = y;
-          keys[hi] = x;
-        }
-      }
-      __syncthreads();
-    }
+  block_bitonic_sort_u64(keys, P, tid, T);
   for (int i = tid; i < M; i += T) idx[(int64_t)b * M + i] = (int32_t)(keys[i] & lowmask);
 }
 

@@ -9,6 +9,8 @@
 //   pc3d_eot_update_f32   everything after the victim's backward, one workgroup per cloud: the record block (:151-182), the
 //                         gradient of the adversarial term through resampling and renormalisation summed over the views in
 //                         ascending order, the gradient of the distance term, Adam and the z-only box (:266-275).
+//   pc3d_eot_draw_f32     (opt-in) rows of the tables the two read — rotations, resampling indices and their inverse —
+//                         drawn on the device from counter-based hash keys, one workgroup per (row, view).
 //
 // d x_e / d adv = I, so a view's gradient reaches the iterate through the renormalisation alone:
 //   y = q / s, q = p - mean p, s = |q_a| (a = arg-max of the norms, LOWEST index on a tie: torch's max(dim) on the CPU):
@@ -332,9 +334,99 @@ __global__ __launch_bounds__(kEuThreads) void eot_update_kernel(EotUpdArgs a) {
   }
 }
 
+// ---- the loop's tables drawn on the device: a pure function of (seed, n, e), include/pc3d.h states it ----
+constexpr int kEdIdxBits = 14;      // a column c < 2 K <= 2^14 rides in the low bits of its key
+static_assert(2 * kEotMaxPoints <= (1 << kEdIdxBits), "every column of cat((x, x), 2) fits the key's low bits");
+static_assert((size_t)2 * kEotMaxPoints * sizeof(uint64_t) <= 160 * 1024, "the keys of the largest cloud fit the CU's LDS");
+
+// One workgroup per (row, view). keys[c] for the columns c = 1 .. 2K - 1, pads (slot 0 and the slots from 2K on) sort to the
+// end; ascending bitonic network over P = 2^p >= 2K slots, a barrier after EVERY stage (block_bitonic_sort_u64, srs_select_kernel's). The
+// sorted array's upper part, dead after the sort (P - K >= K words of 8 bytes), then holds pos[2K] (column -> position or
+// -1), from which the inverse table is gathered: no atomics.
+__global__ __launch_bounds__(1024) void eot_draw_kernel(uint64_t seed, uint64_t n0, int row0, int E, int K, int P,
+                                                        float* __restrict__ rot, int32_t* __restrict__ idx,
+                                                        int32_t* __restrict__ inv) {
+  extern __shared__ __attribute__((aligned(16))) uint64_t ed_keys[];
+  const int e = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
+  const uint64_t n = n0 + (uint64_t)blockIdx.y;
+  const int64_t cell = (int64_t)(row0 + (int)blockIdx.y) * E + e;
+  const uint64_t s = mix64(seed + 0x9E3779B97F4A7C15ull * (16ull * n + (uint64_t)e + 1ull));
+  if (tid == 0) {
+    const double two53 = 1.0 / 9007199254740992.0;
+    const uint64_t u0 = mix64(s ^ (1ull << 32)), u1 = mix64(s ^ (1ull << 33)), u2 = mix64(s ^ (1ull << 34));
+    const double rad = sqrt(-2.0 * log((double)((u0 >> 11) + 1ull) * two53));
+    const double theta = 1e-2 * rad * cos(6.283185307179586476925286766559 * ((double)(u1 >> 11) * two53));
+    const float c = (float)cos(theta), sn = (float)sin(theta);
+    const double r = (double)(u2 >> 11) * two53;
+    float R[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+    if (r < 0.2)
+      R[0] = c, R[1] = sn, R[3] = -sn, R[4] = c;
+    else if (r < 0.4)
+      R[4] = c, R[5] = sn, R[7] = -sn, R[8] = c;
+    else if (r < 0.6)
+      R[0] = c, R[2] = sn, R[6] = -sn, R[8] = c;
+    float* rp = rot + cell * 9;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) rp[k] = R[k];
+  }
+  if (!idx) return;
+  const uint64_t lowmask = (1ull << kEdIdxBits) - 1ull;
+  for (int c = tid; c < P; c += T)
+    ed_keys[c] = (c >= 1 && c < 2 * K) ? ((mix64(s ^ (uint64_t)c) & ~lowmask) | (uint64_t)c) : ~0ull;
+  __syncthreads();
+  block_bitonic_sort_u64(ed_keys, P, tid, T);
+  int32_t* pos = reinterpret_cast<int32_t*>(ed_keys + K);      // [2K] int32 = K words, inside keys[K .. 2K) (2K <= P)
+  for (int c = tid; c < 2 * K; c += T) pos[c] = -1;
+  __syncthreads();
+  int32_t* ix = idx + cell * K;
+  for (int j = tid; j < K; j += T) {
+    const int c = (int)(ed_keys[j] & lowmask);      // 1 <= c <= 2K - 1: K <= 2K - 1 real keys sort in front of the pads
+    ix[j] = c;
+    pos[c] = j;
+  }
+  __syncthreads();
+  int32_t* iv = inv + cell * K * 2;
+  for (int i = tid; i < K; i += T) {      // point i is drawn by the columns i (none for i = 0: column 0 is never drawn) and i + K
+    const int a = i >= 1 ? pos[i] : -1, b = pos[i + K];
+    const int first = a < 0 ? b : (b < 0 ? a : min(a, b));
+    const int second = (a < 0 || b < 0) ? -1 : max(a, b);
+    iv[2 * i] = first, iv[2 * i + 1] = second;
+  }
+}
+
 }  // namespace pc3d
 
 using namespace pc3d;
+
+extern "C" int pc3d_eot_draw_f32(int64_t seed, int64_t n0, int row0, int cnt, int T, int E, int K, float* rot, int32_t* idx,
+                                 int32_t* inv, void* stream) {
+  PC3D_REQUIRE(K >= 1 && K <= kEotMaxPoints, "pc3d_eot_draw_f32: K=%d out of range [1,%d]", K, kEotMaxPoints);
+  PC3D_REQUIRE(E >= 1 && E <= kEotMaxViews, "pc3d_eot_draw_f32: E=%d out of range [1,%d]", E, kEotMaxViews);
+  PC3D_REQUIRE(n0 >= 0, "pc3d_eot_draw_f32: the draw index n0=%lld must be >= 0", (long long)n0);
+  PC3D_REQUIRE(row0 >= 0 && cnt >= 0 && T >= 0 && cnt <= T && row0 <= T - cnt,
+               "pc3d_eot_draw_f32: rows [%d, %d + %d) leave the table of T=%d rows", row0, row0, cnt, T);
+  PC3D_REQUIRE(cnt <= 65535, "pc3d_eot_draw_f32: cnt=%d exceeds grid.y limit", cnt);
+  PC3D_REQUIRE((idx == nullptr) == (inv == nullptr), "pc3d_eot_draw_f32: idx and inv are given together or not at all");
+  if (cnt == 0) return PC3D_OK;
+  PC3D_REQUIRE(rot, "pc3d_eot_draw_f32: null pointer");
+  int P = 2;
+  while (P < 2 * K) P <<= 1;
+  int threads = P / 2;
+  threads = threads < kWave ? kWave : (threads > 1024 ? 1024 : threads);
+  const size_t lds = idx ? (size_t)P * sizeof(uint64_t) : 0;
+  if (lds > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(eot_draw_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       2 * kEotMaxPoints * (int)sizeof(uint64_t));
+    if (e != hipSuccess) {
+      set_error("pc3d_eot_draw_f32: LDS opt-in failed: %s", hipGetErrorString(e));
+      return (int)e;
+    }
+  }
+  hipLaunchKernelGGL(eot_draw_kernel, dim3(E, cnt), dim3(threads), lds, as_stream(stream), (uint64_t)seed, (uint64_t)n0, row0, E,
+                     K, P, rot, idx, inv);
+  PC3D_LAUNCH_CHECK("pc3d_eot_draw_f32");
+  return PC3D_OK;
+}
 
 extern "C" int pc3d_eot_prepare_f32(const float* adv, const float* ori, int B, int K, int E, int T, const float* rot,
                                     const int32_t* idx, int renorm, const int32_t* step_dev, int step_host, float* X,

@@ -299,4 +299,30 @@ __device__ __forceinline__ int wave_min_dpp_i32(int v) {
   return __builtin_amdgcn_readlane(v, 63);
 }
 
+// The splitmix64 finaliser: the hash of the counter-based device draws (srs_select_kernel, eot_draw_kernel).
+__host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+// Ascending bitonic network over the P = 2^p 64-bit keys of an LDS array, by a workgroup of T threads that has made the keys
+// visible (a barrier) before the call; a barrier after EVERY stage, the last one included. With distinct keys the result
+// does not depend on how the stages are scheduled.
+__device__ __forceinline__ void block_bitonic_sort_u64(uint64_t* keys, int P, int tid, int T) {
+  for (int k = 2; k <= P; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = tid; t < (P >> 1); t += T) {
+        const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
+        const uint64_t x = keys[lo], y = keys[hi];
+        const bool up = (lo & k) == 0;
+        if ((x > y) == up) {
+          keys[lo] = y;
+          keys[hi] = x;
+        }
+      }
+      __syncthreads();
+    }
+}
+
 }  // namespace pc3d

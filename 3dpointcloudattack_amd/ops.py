@@ -1280,6 +1280,48 @@ def eot_update(adv, ori, gx, m, v, step, lr, pred, goal, untarget, bestdist, bes
     return adv
 
 
+def eot_draw(seed, n0, rows, rot, idx=None, inv=None):
+    """Draws rows of the loop's tables on the device (pc3d_eot_draw_f32; the stream is stated in include/pc3d.h): for
+    `rows` (a slice with step 1, or (row0, cnt)) of rot [T,E,3,3] — and of idx [T,E,K] / inv [T,E,K,2] (int32, given
+    together) — the draws of the indices n0, n0 + 1, ... under `seed`; the other rows are left alone. Not the host
+    generators' streams: nothing is consumed from torch's or Python's."""
+    who = "eot_draw"
+    if not isinstance(rot, torch.Tensor):
+        raise TypeError(f"{who}: rot: expected a torch.Tensor, got {type(rot)}")
+    for nm, t in (("rot", rot), ("idx", idx), ("inv", inv)):
+        if isinstance(t, torch.Tensor) and not t.is_cuda:
+            raise _lib.Pc3dError(f"{who}: {nm} is on {t.device}; pc3d ops run on the GPU only (no CPU fallback)")
+    if rot.dim() != 4 or not 1 <= rot.shape[1] <= EOT_MAX_VIEWS:
+        raise ValueError(f"{who}: rot must be [T,E,3,3] with 1 <= E <= {EOT_MAX_VIEWS}, got {tuple(rot.shape)}")
+    T, E = rot.shape[:2]
+    dev = rot.device
+    _eot_dense(who, rot, "rot", (T, E, 3, 3), torch.float32, dev)
+    if (idx is None) != (inv is None):
+        raise ValueError(f"{who}: idx and inv are given together or not at all")
+    K = 1
+    if idx is not None:
+        if not isinstance(idx, torch.Tensor) or idx.dim() != 3 or not 1 <= idx.shape[2] <= EOT_MAX_POINTS:
+            raise ValueError(f"{who}: idx must be [T,E,K] with 1 <= K <= {EOT_MAX_POINTS}")
+        K = idx.shape[2]
+        _eot_dense(who, idx, "idx", (T, E, K), torch.int32, dev)
+        _eot_dense(who, inv, "inv", (T, E, K, 2), torch.int32, dev)
+    if isinstance(rows, slice):
+        if rows.step not in (None, 1):
+            raise ValueError(f"{who}: rows must be consecutive, got {rows}")
+        row0 = 0 if rows.start is None else int(rows.start)
+        cnt = (T if rows.stop is None else int(rows.stop)) - row0
+    else:
+        row0, cnt = (int(r) for r in rows)
+    if row0 < 0 or cnt < 0 or row0 + cnt > T:
+        raise ValueError(f"{who}: rows [{row0}, {row0 + cnt}) leave the table of T={T} rows")
+    seed, n0 = int(seed), int(n0)
+    if not -(1 << 63) <= seed < (1 << 63) or not 0 <= n0 or n0 + cnt >= (1 << 63):
+        raise ValueError(f"{who}: seed must fit int64 and 0 <= n0 (seed={seed}, n0={n0})")
+    with torch.cuda.device(dev):
+        _lib.call("pc3d_eot_draw_f32", seed, n0, row0, cnt, T, E, K, rot.data_ptr(), _ptr(idx), _ptr(inv), _stream())
+    return rot, idx, inv
+
+
 # ------------------------------------------------------------------------------------------------------
 # CW-family loop: independent pieces carried by launches that exist anyway (csrc/linear_riders.hip, pointmlp.hip)
 # ------------------------------------------------------------------------------------------------------

@@ -1117,6 +1117,29 @@ int pc3d_eot_update_f32(float* adv, const float* ori, const float* gx, float* m,
                         double lr, double beta1, double beta2, double eps, int one_d, float box,
                         const int32_t* step_dev, int step_host, void* stream);
 
+/* The loop's per-iteration tables drawn on the device instead of by the host generators (opt-in; NOT draw-for-draw
+ * comparable with the reference's torch.randn / random.random / random.sample streams). Fills the rows row0 .. row0 + cnt - 1
+ * of rot [T,E,3,3], idx [T,E,K] and inv [T,E,K,2] (idx and inv NULL together: rot only) for the draw indices
+ * n = n0 + row - row0; no other row is touched. 0 <= row0, row0 + cnt <= T, 1 <= E <= PC3D_EOT_MAX_VIEWS,
+ * 1 <= K <= PC3D_EOT_MAX_POINTS, n0 >= 0; cnt == 0 is a no-op. One workgroup per (row, view), no atomics.
+ * The draw of (seed, n, e), e = 0 .. E - 1, is a pure function; all integer arithmetic is mod 2^64:
+ *   mix64(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^ (z >> 31)
+ *             (the splitmix64 finaliser);  G = 0x9E3779B97F4A7C15;
+ *   s   = mix64((uint64)seed + G * (16 * n + e + 1));
+ *   u_j = mix64(s ^ (1 << (32 + j))) for j = 0, 1, 2 (the column keys below hash s ^ c with c < 2^14: no shared input);
+ *   rotation, in double:  theta = 1e-2 * sqrt(-2 ln(((u_0 >> 11) + 1) * 2^-53)) * cos(2 pi ((u_1 >> 11) * 2^-53));
+ *             c = cos(theta), s_ = sin(theta), each rounded to float32;  r = (u_2 >> 11) * 2^-53, compared in double:
+ *             r < 0.2: [[c,s_,0],[-s_,c,0],[0,0,1]];  r < 0.4: [[1,0,0],[0,c,s_],[0,-s_,c]];
+ *             r < 0.6: [[c,0,s_],[0,1,0],[-s_,0,c]];  else the identity (the 0 and 1 entries are exact) — the matrices
+ *             of the reference's draw (:195-218): theta ~ 1e-2 N(0,1), the cases with probability 0.2 / 0.2 / 0.2 / 0.4;
+ *   resampling: for every column c = 1 .. 2K - 1, key(c) = (mix64(s ^ c) & ~0x3FFF) | c — distinct, so their order is
+ *             total; idx[j] = the c of the j-th smallest key, j < K: K columns of range(1, 2K) without replacement in
+ *             random order (random.sample(range(1, 2K), K)'s distribution), ONE draw per (n, e) shared by the batch;
+ *             inv[i] = the at most two positions j, ascending, with idx[j] mod K == i, else -1.
+ * The keys are sorted in LDS, 8 bytes a slot over 2^p >= 2K slots (128 KiB at the cap). */
+int pc3d_eot_draw_f32(int64_t seed, int64_t n0, int row0, int cnt, int T, int E, int K, float* rot, int32_t* idx,
+                      int32_t* inv, void* stream);
+
 /* GeoA3's iteration after the victim's passes and the searches (attack/GeoA3/GeoA3_attack.py:139-181, :321-351, lp_clip
  * :92-102) as ONE launch, one workgroup per cloud; every point tensor is a contiguous [B,3,N]. In this order:
  *   record   pc3d_geoa3_record_f32's decisions on pred[b] (the loss launch's prediction), target[b], constrain[b] as it
