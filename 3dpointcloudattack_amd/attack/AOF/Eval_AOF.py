@@ -42,7 +42,7 @@ from ... import graphed as _graphed
 from ... import ops
 from ..CW.CW_utils import adv_utils as _adv_utils
 from ..CW.CW_utils import clip_utils as _clip_utils
-from .TAOF_attack import _logits_of, check_basis, get_Laplace_from_pc, get_lowband_from_pc, knn     # noqa: F401  (:46-62, :72-93)
+from .TAOF_attack import check_basis, get_Laplace_from_pc, get_lowband_from_pc, knn     # noqa: F401  (:46-62, :72-93)
 
 try:
     from tqdm import tqdm
@@ -102,21 +102,14 @@ class AOF:
         self.verbose = verbose
         self.fused = fused
         self.graph = graph
-        self._fused_cache = None     # the fused loop's static buffers and graphs (see _fused_state)
+        self._fused_cache = _graphed.LoopCache(1)     # the fused loop (static buffers and graphs, see _fused_loop)
         self.trans_num = 0
         self.preds = self.trans_preds = self.shuffle_preds = self.shuffle_trans_preds = self.o_bestscore = None
 
     def _fused_kind(self):
         if not self.fused or not hasattr(self.model, "fused_loss_and_grad") or type(self.clip_func) is not _clip_utils.ClipPointsLinf:
             return None
-        af = self.adv_func
-        if type(af) is _adv_utils.UntargetedLogitsAdvLoss:
-            return "untargeted_logits", float(af.kappa)
-        if type(af) is _adv_utils.LogitsAdvLoss:
-            return "logits", float(af.kappa)
-        if type(af) is _adv_utils.CrossEntropyAdvLoss:
-            return "cross_entropy", 0.0
-        return None
+        return _adv_utils.own_adv_kind(self.adv_func)
 
     def attack(self, data, label):
         if self.deterministic is None:
@@ -140,11 +133,11 @@ class AOF:
             if self.clip_func is not None:
                 adv_pc = self.clip_func(adv_pc, data_last)
             adv_pc = adv_pc.contiguous()
-            preds = torch.argmax(_logits_of(self.model(adv_pc)), dim=-1)
-            trans_preds = torch.argmax(_logits_of(self.trans_model(adv_pc)), dim=-1)
+            preds = torch.argmax(_graphed.logits_of(self.model(adv_pc)), dim=-1)
+            trans_preds = torch.argmax(_graphed.logits_of(self.trans_model(adv_pc)), dim=-1)
             shuffle_pc = rand_row(adv_pc.transpose(2, 1).float()).transpose(2, 1).contiguous()
-            self.shuffle_preds = torch.argmax(_logits_of(self.model(shuffle_pc)), dim=-1)
-            self.shuffle_trans_preds = torch.argmax(_logits_of(self.trans_model(shuffle_pc)), dim=-1)
+            self.shuffle_preds = torch.argmax(_graphed.logits_of(self.model(shuffle_pc)), dim=-1)
+            self.shuffle_trans_preds = torch.argmax(_graphed.logits_of(self.trans_model(shuffle_pc)), dim=-1)
         self.preds, self.trans_preds, self.o_bestscore = preds, trans_preds, st["o_bestscore"].clone()
         success_num = int((preds != label).sum().item())
         self.trans_num = int((trans_preds != label).sum().item())
@@ -183,8 +176,8 @@ class AOF:
             opt = optim.Adam([lfc], lr=self.lr, weight_decay=0)
             for i in range(self.epochs):
                 adv_pc = lfc + hfc
-                logits = _logits_of(model(adv_pc))
-                lfc_logits = _logits_of(model(lfc))
+                logits = _graphed.logits_of(model(adv_pc))
+                lfc_logits = _graphed.logits_of(model(lfc))
                 with torch.no_grad():      # record values (:168-185)
                     ops.aof_record(adv_pc.detach(), data, torch.argmax(logits, dim=1), torch.argmax(lfc_logits, dim=1), label,
                                    st["o_bestdist"], st["o_bestscore"], st["o_bestattack"])
@@ -202,18 +195,27 @@ class AOF:
     # ---- PointNet victim + this package's functor + ClipPointsLinf: no autograd, every buffer updated IN PLACE, the
     # iteration replayed from hipGraphs ------------------------------------------------------------------------------------
     def _fused_loop(self, B, K, fk):
-        """The fused iteration's state (all static buffers: the graphs point at them) and its entry points: load(ori,
-        label) takes a batch in and rewinds the bests, new_step() draws the step's noisy cloud and its basis
-        (begin_step() alone rewinds to the start of the step), iterate() is one iteration — 3 launches beside the victim's."""
-        dev = self.device
+        """The fused iteration as a DeviceLoop: its state (all static buffers: the graphs point at them) in `bufs`, one
+        iteration — 3 launches beside the victim's — as the body. _load takes a batch in and rewinds the bests, _new_step
+        draws the step's noisy cloud and its basis, _begin_step alone rewinds to the start of the step.
+        The last loop is kept on the instance from one attack() call to the next: a capture (two eager warm-up passes,
+        GRAPH_BLOCK + 1 captured iterations, two graph instantiations) costs as much as ~150 replayed iterations, and the
+        reference's driver calls the attack once per batch of the loader. It is rebuilt when the shape, the loop's
+        constants, the kernel flavour or the victim's weights change (the victim re-folds its weight pack on exactly that
+        event: model/pointnet.py keys the folded caches on the same addresses and version counters)."""
+        dev, model = self.device, self.model
         lp, budget, lr = self.low_pass, float(self.clip_func.budget), self.lr
+        key = _graphed.loop_key(model, dev, B, K, fk, float(lr), int(lp), budget, bool(self.graph), self.basis)
+        loop = self._fused_cache.get(key)
+        if loop is not None:
+            return loop
         f32 = dict(dtype=torch.float32, device=dev)
         buf = torch.empty((2 * B, 3, K), **f32)      # rows [:B] = lfc + hfc, rows [B:] = lfc: the victim's stacked input
         adv, lfc = buf[:B], buf[B:]
         hfc, coeff, clipped, data, ori = (torch.empty((B, 3, K), **f32) for _ in range(5))
         m, v = torch.zeros((B, 3, K), **f32), torch.zeros((B, 3, K), **f32)
-        band = self.basis == "lowband"
-        if band:      # [B,N,lp] instead of V and V^T
+        U = V = Vt = None
+        if self.basis == "lowband":      # [B,N,lp] instead of V and V^T
             ops.lowband_block(K, lp)      # refuse a low_pass past the block before anything is allocated
             U = torch.empty((B, K, lp), **f32)
         else:
@@ -221,78 +223,70 @@ class AOF:
         step = torch.zeros((1,), dtype=torch.int32, device=dev)
         label2 = torch.zeros((2 * B,), dtype=torch.long, device=dev)
         label = label2[:B]
-        st = self._bests(B, K, dev)
-
-        def load(ori_data, lab):
-            ori.copy_(ori_data)
-            label2.copy_(lab.repeat(2))
-            rewind_bests()
-
-        def rewind_bests():
-            st["o_bestdist"].fill_(1e10), st["o_bestscore"].fill_(-1), st["o_bestattack"].zero_()
-
-        def reproject(src):      # lfc, hfc and the next iterate lfc + hfc, straight into the stacked buffer
-            if band:
-                ops.band_reproject(src, U, lfc, hfc, sum=adv)
-            else:
-                ops.spectral_reproject(src, V, Vt, lp, lfc, hfc, coeff, sum=adv)
-
-        def begin_step():
-            reproject(data)      # :145-147
-            m.zero_(), v.zero_(), step.zero_()
-
-        def new_step():
-            data.copy_(self._noisy(ori))
-            if band:
-                U.copy_(get_lowband_from_pc(data, lp))      # the low band: once per binary step
-            else:
-                _, Vn = get_Laplace_from_pc(data)      # the eigen-decomposition: once per binary step
-                V.copy_(Vn)
-                Vt.copy_(Vn.transpose(2, 1))
-            begin_step()
+        c = dict(buf=buf, adv=adv, lfc=lfc, hfc=hfc, coeff=coeff, clipped=clipped, data=data, ori=ori, m=m, v=v, U=U, V=V, Vt=Vt,
+                 lp=lp, step=step, label2=label2, **self._bests(B, K, dev))
 
         def iterate():
             with torch.no_grad():
-                _, pred2, _, g = self.model.fused_loss_and_grad(buf, label2, *fk, scale=0.5 / B)
-                ops.aof_record(adv, data, pred2[:B], pred2[B:], label, st["o_bestdist"], st["o_bestscore"], st["o_bestattack"],
+                _, pred2, _, g = model.fused_loss_and_grad(buf, label2, *fk, scale=0.5 / B)
+                ops.aof_record(adv, data, pred2[:B], pred2[B:], label, c["o_bestdist"], c["o_bestscore"], c["o_bestattack"],
                                step=step)      # also advances the Adam step word
                 ops.aof_update(lfc, g[:B], g[B:], m, v, hfc, data, step, lr, budget, out=clipped)
-                reproject(clipped)
+                _reproject(c, clipped)
 
-        return dict(iterate=iterate, begin_step=begin_step, new_step=new_step, load=load, rewind_bests=rewind_bests, data=data,
-                    buf=buf, label2=label2, st=st, graphs=None)
+        return self._fused_cache.put(key, _graphed.DeviceLoop(key, dev, owners=(model,), counts=(1, GRAPH_BLOCK), warmup=2,
+                                                              body=iterate, bufs=c))
 
-    def _fused_state(self, B, K, fk):
-        """The loop's buffers and captured graphs, kept on the instance from one attack() call to the next: a capture
-        (two eager warm-up passes, GRAPH_BLOCK + 1 captured iterations, two graph instantiations) costs as much as ~150
-        replayed iterations, and the reference's driver calls the attack once per batch of the loader. Rebuilt when the
-        shape, the loop's constants, the kernel flavour or the victim's folded weights change."""
-        from ...model.pointnet import fused_pack
-        key = (B, K, fk, float(self.lr), int(self.low_pass), float(self.clip_func.budget), bool(ops._det()), self.basis)
-        c = self._fused_cache
-        if c is None or c["key"] != key or c["pack"] is not fused_pack(self.model):
-            c = self._fused_cache = self._fused_loop(B, K, fk)
-            c["key"], c["pack"] = key, fused_pack(self.model)
-        return c
+    @staticmethod
+    def _load(c, ori_data, lab):
+        c["ori"].copy_(ori_data)
+        c["label2"].copy_(lab.repeat(2))
+        _rewind_bests(c)
+
+    def _new_step(self, c):
+        data = c["data"]
+        data.copy_(self._noisy(c["ori"]))
+        if c["U"] is not None:
+            c["U"].copy_(get_lowband_from_pc(data, c["lp"]))      # the low band: once per binary step
+        else:
+            _, Vn = get_Laplace_from_pc(data)      # the eigen-decomposition: once per binary step
+            c["V"].copy_(Vn)
+            c["Vt"].copy_(Vn.transpose(2, 1))
+        _begin_step(c)
 
     def _attack_fused(self, ori_data, label, fk):
         B, _, K = ori_data.shape
-        fl = self._fused_state(B, K, fk)
-        fl["load"](ori_data, label)
-        iterate = fl["iterate"]
+        loop = self._fused_loop(B, K, fk)
+        c = loop.bufs
+
+        def rewind():
+            _rewind_bests(c)
+            _begin_step(c)
+
+        self._load(c, ori_data, label)
         for binary_step in range(self.step):
-            fl["new_step"]()
-            if fl["graphs"] is None and self.graph and self.epochs > 0:
-                # capture once (after eager warm-up passes on a side stream, as torch requires), then rewind the state
-                fl["graphs"] = _graphed.LoopGraph(iterate, self.device, 2, counts=(1, GRAPH_BLOCK), owners=(self.model,))
-                fl["rewind_bests"]()
-                fl["begin_step"]()
-            if not self.graph:
-                for _ in range(self.epochs):
-                    iterate()
-            elif self.epochs > 0:
-                fl["graphs"].run(self.epochs)
-        return (fl["data"] if self.step > 0 else ori_data), fl["st"]
+            self._new_step(c)
+            if self.graph and self.epochs > 0:
+                loop.capture(rewind)
+            loop.run(self.epochs)
+        return (c["data"] if self.step > 0 else ori_data), c
+
+
+def _rewind_bests(c):
+    c["o_bestdist"].fill_(1e10), c["o_bestscore"].fill_(-1), c["o_bestattack"].zero_()
+
+
+def _reproject(c, src):
+    """lfc, hfc and the next iterate lfc + hfc of `src`, straight into the stacked buffer."""
+    if c["U"] is not None:
+        ops.band_reproject(src, c["U"], c["lfc"], c["hfc"], sum=c["adv"])
+    else:
+        ops.spectral_reproject(src, c["V"], c["Vt"], c["lp"], c["lfc"], c["hfc"], c["coeff"], sum=c["adv"])
+
+
+def _begin_step(c):
+    _reproject(c, c["data"])      # :145-147
+    c["m"].zero_(), c["v"].zero_(), c["step"].zero_()
 
 
 # ---- the reference's module-level driver (:118-259): the globals its __main__ sets --------------------------------------

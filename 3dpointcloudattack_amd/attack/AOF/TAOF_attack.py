@@ -55,10 +55,6 @@ def get_lowband_from_pc(ori_pc, low_pass):
         return ops.lowband_basis(ori_pc.detach().float().contiguous(), low_pass, 30, cf=True)[0]
 
 
-def _logits_of(out):
-    return out[0] if isinstance(out, tuple) else out
-
-
 class CWTAOF:
     """Class for CW attack."""
 
@@ -116,7 +112,7 @@ class CWTAOF:
         for param in self.model.parameters():
             param.requires_grad = False
         with torch.no_grad():
-            clean = torch.argmax(_logits_of(self.model(ori_data)), dim=1)
+            clean = torch.argmax(_graphed.logits_of(self.model(ori_data)), dim=1)
         if self.verbose:
             print(clean.tolist())
         fk = self._fused_kind()
@@ -140,10 +136,10 @@ class CWTAOF:
 
             for iteration in range(self.num_iter):
                 adv_data = lfc + hfc
-                adv_loss = (1 - self.GAMMA) * self.adv_func(_logits_of(self.model(adv_data)), target).mean()
+                adv_loss = (1 - self.GAMMA) * self.adv_func(_graphed.logits_of(self.model(adv_data)), target).mean()
                 opt.zero_grad()
                 adv_loss.backward()
-                lfc_adv_loss = self.GAMMA * self.adv_func(_logits_of(self.model(lfc)), target).mean()
+                lfc_adv_loss = self.GAMMA * self.adv_func(_graphed.logits_of(self.model(lfc)), target).mean()
                 lfc_adv_loss.backward()
                 opt.step()
 
@@ -152,8 +148,8 @@ class CWTAOF:
                     if self.clip_func is not None:
                         adv_data = self.clip_func(adv_data.detach().clone(), ori_data)
                     lfc.data, hfc = reproject(adv_data)     # :164-170
-                    pred = torch.argmax(_logits_of(self.model(adv_data)), dim=1)
-                    lfc_pred = torch.argmax(_logits_of(self.model(lfc)), dim=1)
+                    pred = torch.argmax(_graphed.logits_of(self.model(adv_data)), dim=1)
+                    lfc_pred = torch.argmax(_graphed.logits_of(self.model(lfc)), dim=1)
                     dist_val = torch.sqrt(torch.sum((adv_data - ori_data) ** 2, dim=[1, 2]))
                     upd = (dist_val < o_bestdist) & (pred == target) & (lfc_pred != y_truth)
                     o_bestdist = torch.where(upd, dist_val, o_bestdist)
@@ -164,7 +160,7 @@ class CWTAOF:
         fail_idx = o_bestscore < 0
         o_bestattack = torch.where(fail_idx[:, None, None], adv_data, o_bestattack)
         with torch.no_grad():
-            preds = torch.argmax(_logits_of(self.model(o_bestattack)), dim=-1)
+            preds = torch.argmax(_graphed.logits_of(self.model(o_bestattack)), dim=-1)
         success_num = int((preds == target).sum().item())
         if self.verbose:
             print('Successfully attack {}/{}'.format(success_num, B))
@@ -252,18 +248,18 @@ class CWTAOF:
                 st["pend_dist"].copy_(torch.sqrt(torch.sum((adv - ori_data) ** 2, dim=[1, 2])))
                 st["adv"].copy_(adv)
 
-        run = iterate
+        def rewind():
+            st["o_bestdist"].fill_(1e10), st["o_bestscore"].fill_(-1), st["o_bestattack"].zero_()
+            begin_step(adv0, reuse_basis=True)
+
+        # kept for this call only: no key, no cache
+        loop = _graphed.DeviceLoop(None, dev, owners=(self.model,), counts=(1,), warmup=2, body=iterate, bufs=st)
         for binary_step in range(self.binary_step):
             adv0 = ori_data.clone().detach() + torch.randn((B, 3, K)).to(dev) * 1e-7
             begin_step(adv0)
             if binary_step == 0 and self._capturable() and self.num_iter > 0:
-                # capture once (after eager warm-up passes on a side stream, as torch requires), then rewind the state
-                st["graph_keep"] = loop = _graphed.LoopGraph(iterate, dev, 2, owners=(self.model,))
-                run = loop.replay
-                st["o_bestdist"].fill_(1e10), st["o_bestscore"].fill_(-1), st["o_bestattack"].zero_()
-                begin_step(adv0, reuse_basis=True)
-            for _ in range(self.num_iter):
-                run()
+                loop.capture(rewind)
+            loop.run(self.num_iter)
             flush()
         adv_last = st["adv"] if self.num_iter > 0 else ori_data
         return st["o_bestdist"], st["o_bestscore"], st["o_bestattack"], adv_last

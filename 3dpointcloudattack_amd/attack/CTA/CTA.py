@@ -43,8 +43,7 @@ PASS_MAX = 1500          # a pass breaks at cur_step >= 1500
 TOTAL_MAX = 15000        # 'Fail' once a pass ends with step >= 15000
 IG_SET_SIZE = 2          # VanillaGradient.get_mask's default, which IntegratedGradients never overrides
 MAX_ROWS = 4096          # clouds per victim pass of the saliency: a chunk size chosen for memory, not a limit of the kernels
-_MAX_LOOPS = 4
-_LOOPS = {}
+_LOOPS = _graphed.LoopCache(4)
 _P_LATCH, _P_CUR, _P_STEP, _P_NPP = 50, 51, 52, 53
 
 
@@ -208,21 +207,24 @@ def rank(sal, g, variant):
 # ----------------------------------------------------------------------------------------------------------------------
 # the loop
 # ----------------------------------------------------------------------------------------------------------------------
-class _Loop:
-    """Static buffers of one problem shape, one step as a function, and (graph=True) its hipGraph of 25 steps."""
+class _Loop(_graphed.DeviceLoop):
+    """Static buffers of one problem shape (`s`), one step as the body, captured (graph=True) as ONE graph of a window's
+    25 steps: run_window() is its only use."""
 
-    def __init__(self, network, G, S, N, k, P, W, dev, mode, targeted, optimizer, fused):
+    def __init__(self, network, G, S, N, k, P, W, dev, mode, targeted, optimizer, fused, key=None):
+        super().__init__(key, dev, owners=(network,), counts=(WINDOW,), warmup=1)
         f32 = dict(dtype=torch.float32, device=dev)
         i32 = dict(dtype=torch.int32, device=dev)
         self.network, self.fused, self.G, self.S = network, fused, G, S
-        self.s = dict(x=torch.zeros((G * S, 3, N), **f32), proto=torch.zeros((G * S, 3, N), **f32),
-                      v=torch.zeros((G * S, 3, N), **f32), s_adam=torch.zeros((G * S, 3, N), **f32) if optimizer == "Adam" else None,
-                      sel=torch.full((G, P, W), -1, **i32), cap=0, poll=torch.zeros((G, ops.CTA_POLL_WORDS), **i32),
-                      ctrl=torch.zeros((G,), **i32), ori=torch.zeros((G,), **i32), tar=torch.zeros((G,), **i32),
-                      w=torch.zeros((S,), **f32), hist_ori=torch.zeros((G, ops.CTA_HISTORY), **f32),
-                      hist_max=torch.zeros((G, ops.CTA_HISTORY), **f32), zlast=torch.zeros((G * S, k), **f32),
-                      mode=mode, targeted=targeted, optimizer=optimizer, S=S)
-        self.graph = None
+        self.s = self.bufs
+        self.s.update(
+            x=torch.zeros((G * S, 3, N), **f32), proto=torch.zeros((G * S, 3, N), **f32), v=torch.zeros((G * S, 3, N), **f32),
+            s_adam=torch.zeros((G * S, 3, N), **f32) if optimizer == "Adam" else None,
+            sel=torch.full((G, P, W), -1, **i32), cap=0, poll=torch.zeros((G, ops.CTA_POLL_WORDS), **i32),
+            ctrl=torch.zeros((G,), **i32), ori=torch.zeros((G,), **i32), tar=torch.zeros((G,), **i32),
+            w=torch.zeros((S,), **f32), hist_ori=torch.zeros((G, ops.CTA_HISTORY), **f32),
+            hist_max=torch.zeros((G, ops.CTA_HISTORY), **f32), zlast=torch.zeros((G * S, k), **f32),
+            mode=mode, targeted=targeted, optimizer=optimizer, S=S)
         self.layer_activation, self.layer_name = None, None
         self.penalty = None            # (beta, per-set levels on the host): the Chamfer term of CTA.py:165-174
 
@@ -263,19 +265,14 @@ class _Loop:
             g = g.float().contiguous()
         ops.cta_update(s, g)
 
+    body = step
+
     def steps(self):
         for _ in range(WINDOW):
             self.step()
 
-    def capture(self, warmup=1):
-        """Capture 25 steps (after `warmup` eager ones on the side stream; they advance the state: load() again)."""
-        self.graph = _graphed.LoopGraph(self.step, self.s["x"].device, warmup, counts=(WINDOW,), owners=(self.network,))
-
     def run_window(self):
-        if self.graph is not None:
-            self.graph.replay(WINDOW)
-        else:
-            self.steps()
+        self.run(WINDOW)
 
 
 def _loop_for(network, G, S, N, k, P, W, dev, mode, targeted, optimizer, fused, graph, loader):
@@ -283,16 +280,12 @@ def _loop_for(network, G, S, N, k, P, W, dev, mode, targeted, optimizer, fused, 
         c = _Loop(network, G, S, N, k, P, W, dev, mode, targeted, optimizer, fused)
         loader(c)
         return c
-    wkey = _graphed.weights_key(network)
-    key = (id(network), G, S, N, k, P, W, dev, mode, targeted, optimizer, bool(ops._det()), wkey)
+    key = _graphed.loop_key(network, dev, G, S, N, k, P, W, mode, targeted, optimizer)
     c = _LOOPS.get(key)
     if c is None:
-        while len(_LOOPS) >= _MAX_LOOPS:
-            _LOOPS.pop(next(iter(_LOOPS)))
-        c = _Loop(network, G, S, N, k, P, W, dev, mode, targeted, optimizer, fused)
+        c = _LOOPS.put(key, _Loop(network, G, S, N, k, P, W, dev, mode, targeted, optimizer, fused, key))
         loader(c)
         c.capture()
-        _LOOPS[key] = c
     loader(c)
     return c
 

@@ -33,8 +33,16 @@ def rand_row(array):
     return array[:, row_sequence, :]
 
 
-def _logits_of(out):
-    return out[0] if isinstance(out, tuple) else out
+def bisect_weights(lower, upper, current, ok):
+    """The reference's weight adjustment (:182-200), sample by sample in float64, in place: an attack that succeeded
+    (ok[e]) raises the lower bound to the weight it ran with, any other lowers the upper bound; the next weight is the
+    midpoint."""
+    for e in range(len(current)):
+        if ok[e]:
+            lower[e] = max(lower[e], current[e])
+        else:
+            upper[e] = min(upper[e], current[e])
+        current[e] = (lower[e] + upper[e]) / 2.
 
 
 class _GraphRunner:
@@ -147,15 +155,7 @@ class CW:
         return self._own_adv_kind()
 
     def _own_adv_kind(self):
-        """(kind, kappa) of this package's own adversarial functors (their gradients are built into pc3d_cls_loss_f32)."""
-        af = self.adv_func
-        if type(af) is _adv_utils.UntargetedLogitsAdvLoss:
-            return "untargeted_logits", float(af.kappa)
-        if type(af) is _adv_utils.LogitsAdvLoss:
-            return "logits", float(af.kappa)
-        if type(af) is _adv_utils.CrossEntropyAdvLoss:
-            return "cross_entropy", 0.0
-        return None
+        return _adv_utils.own_adv_kind(self.adv_func)
 
     def _direct_terms(self, st):
         """The autograd pass without the loss: own functors on both sides, a fused clip and a victim that goes through
@@ -187,7 +187,7 @@ class CW:
         target = target.long().to(dev).detach().view(-1)
         label = target
         with torch.no_grad():
-            logits = _logits_of(self.model(ori_data))
+            logits = _graphed.logits_of(self.model(ori_data))
             pred = torch.argmax(logits, dim=1)
         if self.verbose:
             print("ori label:", pred.tolist())
@@ -338,7 +338,7 @@ class CW:
         if fork:
             with torch.cuda.stream(fork[1]):
                 terms = self.dist_func.per_sample_terms(alias, ori_data, st["gdist"], mean=False)
-        logits = _logits_of(self.model(adv_data))
+        logits = _graphed.logits_of(self.model(adv_data))
         kind, kappa = self._own_adv_kind()
         lg = logits if (logits.dtype == torch.float32 and logits.stride(1) == 1) else logits.float().contiguous()
         # the loss kernel in raw mode (+4: the functor's value on the logits as given): prediction into st["pred"],
@@ -388,7 +388,7 @@ class CW:
             if fork:
                 with torch.cuda.stream(fork[1]):
                     dist_loss = self.dist_func(adv_data, ori_data, st["weights"]).mean()
-            logits = _logits_of(self.model(adv_data))
+            logits = _graphed.logits_of(self.model(adv_data))
             pred = torch.argmax(logits, dim=1)  # [B]
         # record values (device side; reference :129-153)
         with torch.no_grad():
@@ -462,22 +462,12 @@ class CW:
 
     def _end_binary_step(self, st):
         """Adjust the weight factor (reference :182-200) — one host round trip per binary step."""
-        B = st["B"]
         bs = st["bestscore"].cpu().numpy()
         bd = st["bestdist"].double().cpu().numpy()
         obd = st["o_bestdist"].double().cpu().numpy()
         lab = st["label"].cpu().numpy()
-        lower_bound, upper_bound, current_weight = st["lower_bound"], st["upper_bound"], st["current_weight"]
-        for e in range(B):
-            if self.attack_method == 'untarget':
-                ok = bs[e] != lab[e] and bs[e] != -1 and bd[e] <= obd[e]
-            else:
-                ok = bs[e] == lab[e] and bs[e] != -1 and bd[e] <= obd[e]
-            if ok:
-                lower_bound[e] = max(lower_bound[e], current_weight[e])
-            else:
-                upper_bound[e] = min(upper_bound[e], current_weight[e])
-            current_weight[e] = (lower_bound[e] + upper_bound[e]) / 2.
+        hit = (bs != lab) if self.attack_method == 'untarget' else (bs == lab)
+        bisect_weights(st["lower_bound"], st["upper_bound"], st["current_weight"], hit & (bs != -1) & (bd <= obd))
 
     def attack(self, data, target):
         if self.deterministic is None:
@@ -542,16 +532,16 @@ class CW:
 
         with torch.no_grad():
             # Test attack (:211-224)
-            attack_pred = torch.argmax(_logits_of(self.model(o_bestattack)), dim=1)
+            attack_pred = torch.argmax(_graphed.logits_of(self.model(o_bestattack)), dim=1)
             self.attack_fail += int((~self._success(attack_pred, target)).sum().item())
             # Test shuffle attack (:226-241) — numpy global RNG like the reference
             best_np = o_bestattack.double().cpu().numpy()  # [B,3,K]
             shuffled = rand_row(best_np.transpose((0, 2, 1)))
             shuffled = torch.from_numpy(shuffled.transpose((0, 2, 1)).copy()).float().to(dev)
-            shuffle_pred = torch.argmax(_logits_of(self.model(shuffled)), dim=1)
+            shuffle_pred = torch.argmax(_graphed.logits_of(self.model(shuffled)), dim=1)
             self.shuffle_fail += int((~self._success(shuffle_pred, target)).sum().item())
             # Test transfer attack (:244-257)
-            trans_pred = torch.argmax(_logits_of(self.trans_model(o_bestattack)), dim=1)
+            trans_pred = torch.argmax(_graphed.logits_of(self.trans_model(o_bestattack)), dim=1)
             self.trans_fail += int((~self._success(trans_pred, target)).sum().item())
         if self.verbose:
             print('attack result: ', attack_pred.tolist(), 'shuffle result: ', shuffle_pred.tolist(),

@@ -95,3 +95,14 @@ class UntargetedLogitsAdvLoss(nn.Module):
             return fast
         real, other = _real_other(logits, targets)
         return torch.clamp(real - other + self.kappa, min=0.).mean()
+
+
+def own_adv_kind(adv_func):
+    """(kind, kappa) of this package's own adversarial functors (their gradients are built into pc3d_cls_loss_f32), else None."""
+    if type(adv_func) is UntargetedLogitsAdvLoss:
+        return "untargeted_logits", float(adv_func.kappa)
+    if type(adv_func) is LogitsAdvLoss:
+        return "logits", float(adv_func.kappa)
+    if type(adv_func) is CrossEntropyAdvLoss:
+        return "cross_entropy", 0.0
+    return None

@@ -22,14 +22,11 @@ import torch
 import torch.nn.functional as F
 import torch.optim as optim
 
+from ... import graphed as _graphed
 from ... import ops
 from ..CW.CW_attack import CW as _CW
 from ..CW.CW_attack import rand_row  # noqa: F401  (the reference defines the same function, :8-12)
 from ..CW.CW_utils import dist_utils as _dist_utils
-
-
-def _logits_of(out):
-    return out[0] if isinstance(out, tuple) else out
 
 
 def critical_scores(model, pc, label):
@@ -38,7 +35,7 @@ def critical_scores(model, pc, label):
     x = pc.detach().float().clone().requires_grad_()
     label = label.long().to(pc.device).view(-1)
     with torch.enable_grad():
-        loss = F.cross_entropy(_logits_of(model(x)), label)
+        loss = F.cross_entropy(_graphed.logits_of(model(x)), label)
         g, = torch.autograd.grad(loss, x)
     return (g ** 2).sum(1)
 
@@ -184,7 +181,7 @@ class CWAdd(_CW):
             # a victim without the fused entry point: its input gradient from autograd, the loss kernel in raw mode (+4:
             # the functor's value on the logits as given) writes the prediction and d loss / d logits
             alias = st["cat"].detach().requires_grad_()
-            lg = _logits_of(self.model(alias))
+            lg = _graphed.logits_of(self.model(alias))
             lg = lg if (lg.dtype == torch.float32 and lg.stride(1) == 1) else lg.float().contiguous()
             kind, kappa = self._own_adv_kind()
             _, _, _, g_logits = ops.cls_loss(lg.detach(), st["target"], ops.LOSS_KINDS[kind] + 4, kappa, scale,
@@ -197,7 +194,7 @@ class CWAdd(_CW):
         # generic: arbitrary callables, the reference's protocol (cat, dist_func on [B,A,3] / [B,K,3], Adam)
         adv = st["adv"]
         cat = torch.cat([ori, adv], dim=-1)
-        logits = _logits_of(self.model(cat))
+        logits = _graphed.logits_of(self.model(cat))
         pred = torch.argmax(logits, dim=-1)
         ori_t = ori.transpose(1, 2).contiguous()
         with torch.no_grad():
@@ -246,14 +243,14 @@ class CWAdd(_CW):
         # The checks run the victim, the shuffled cloud and the transfer model on the ADDED POINTS ALONE
         # ([B,3,A], :239-282), not on the concatenation the attack returns — the reference's behaviour, kept.
         with torch.no_grad():
-            attack_pred = torch.argmax(_logits_of(self.model(o_bestattack)), dim=1)
+            attack_pred = torch.argmax(_graphed.logits_of(self.model(o_bestattack)), dim=1)
             self.attack_fail += int((~self._success(attack_pred, target)).sum().item())
             best_np = o_bestattack.double().cpu().numpy()
             shuffled = rand_row(best_np.transpose((0, 2, 1)))       # numpy's global RNG, as the reference
             shuffled = torch.from_numpy(shuffled.transpose((0, 2, 1)).copy()).float().to(self.device)
-            shuffle_pred = torch.argmax(_logits_of(self.model(shuffled)), dim=1)
+            shuffle_pred = torch.argmax(_graphed.logits_of(self.model(shuffled)), dim=1)
             self.shuffle_fail += int((~self._success(shuffle_pred, target)).sum().item())
-            trans_pred = torch.argmax(_logits_of(self.trans_model(o_bestattack)), dim=1)
+            trans_pred = torch.argmax(_graphed.logits_of(self.trans_model(o_bestattack)), dim=1)
             self.trans_fail += int((~self._success(trans_pred, target)).sum().item())
         if self.verbose:
             print('attack result: ', attack_pred.tolist(), 'shuffle result: ', shuffle_pred.tolist(),

@@ -51,10 +51,6 @@ class _FusedAdam:
         self.lr *= gamma
 
 
-def _logits_of(out):
-    return out[0] if isinstance(out, tuple) else out
-
-
 def offset_proj(offset, ori_pc, ori_normal, project='dir'):
     """GeoA3_attack.py:62-80 — project each offset onto the normal of its nearest ori point (as written: the KNN query
     is the OFFSET itself, and the 'inner' condition is all-false so every offset is replaced by its projection)."""
@@ -119,7 +115,7 @@ def _forward_step(net, pc_ori, input_curr_iter, normal_ori, ori_kappa, target, s
             adv_t, ori_t = input_curr_iter.permute(0, 2, 1), pc_ori.permute(0, 2, 1)
             searches = (knn_points(adv_t, ori_t, K=1),
                         None if cfg.is_cd_single_side else knn_points(ori_t, adv_t, K=1).dists.squeeze(-1))
-    output_curr_iter = _logits_of(net(input_curr_iter))
+    output_curr_iter = _graphed.logits_of(net(input_curr_iter))
     if searches is not None:
         main.wait_stream(side)
 
@@ -279,20 +275,21 @@ def _device_loop_plan(net, cfg, b, n, targeted):
 
 
 def _device_loop_state(plan, b, n, dev):
-    """Buffers (static: the graphs point at them), the iteration body and the captured graphs of one (plan, shape, weights)
-    key, kept on the victim and reused by later search steps and later calls."""
+    """The loop of one (plan, shape, weights) key — buffers (static: the graphs point at them), the iteration body and the
+    captured graphs — kept on the victim and reused by later search steps and later calls. The API is a function, so the
+    victim is the only object that lives from call to call; the body needs the victim, hence victim -> cache -> loop ->
+    victim: the one loop cache that is freed by the cycle collector."""
     from ...model import pointnet as _pointnet
     victim = plan["victim"]
-    wkey = _graphed.weights_key(victim)
-    key = (b, n, str(dev), bool(ops._det()), wkey, tuple(sorted((nm, v) for nm, v in plan.items() if nm != "victim")))
-    cache = victim.__dict__.setdefault("_geoa3_loop_cache", {})
-    s = cache.get(key)
-    if s is not None:
-        return s
+    key = _graphed.loop_key(victim, dev, b, n, tuple(sorted((nm, v) for nm, v in plan.items() if nm != "victim")))
+    cache = victim.__dict__.setdefault("_geoa3_loop_cache", _graphed.LoopCache(LOOP_CACHE_MAX))
+    loop = cache.get(key)
+    if loop is not None:
+        return loop
     f32 = dict(dtype=torch.float32, device=dev)
     i32 = dict(dtype=torch.int32, device=dev)
     i64 = dict(dtype=torch.int64, device=dev)
-    s = dict(key=key, graphs=None)
+    s = {}
     for nm in ("x", "ori", "offset", "m", "v", "best_attack", "normal"):
         s[nm] = torch.zeros((b, 3, n), **f32)
     for nm in ("scale", "constrain", "best_loss", "iter_best_loss"):
@@ -332,20 +329,33 @@ def _device_loop_state(plan, b, n, dev):
                              gval=plan["gval"], w_dis=plan["w_dis"], w_hd=plan["w_hd"], w_curv=plan["w_curv"],
                              scheduler=plan["scheduler"], cc_linf=plan["cc_linf"])
 
-    def rewind(offset0, scale_const, search_step):
-        """The state of a search step's first iteration, in place."""
-        s["offset"].copy_(offset0)
-        torch.add(s["ori"], s["offset"], out=s["x"])
-        s["m"].zero_(), s["v"].zero_(), s["step"].zero_()
-        s["lr"].fill_(plan["lr"]), s["constrain"].fill_(1e10)
-        s["iter_best_loss"].fill_(1e10), s["iter_best_score"].fill_(-1)
-        s["scale"].copy_(scale_const.float()), s["search"].fill_(int(search_step))
+    return cache.put(key, _graphed.DeviceLoop(key, dev, owners=(victim,), counts=(1, LOOP_BLOCK), warmup=2, body=body, bufs=s))
 
-    s["body"], s["rewind"] = body, rewind
-    while len(cache) >= LOOP_CACHE_MAX:
-        cache.pop(next(iter(cache)))
-    cache[key] = s
-    return s
+
+def _rewind(s, plan, offset0, scale_const, search_step):
+    """The state of a search step's first iteration, in place."""
+    s["offset"].copy_(offset0)
+    torch.add(s["ori"], s["offset"], out=s["x"])
+    s["m"].zero_(), s["v"].zero_(), s["step"].zero_()
+    s["lr"].fill_(plan["lr"]), s["constrain"].fill_(1e10)
+    s["iter_best_loss"].fill_(1e10), s["iter_best_score"].fill_(-1)
+    s["scale"].copy_(scale_const.float()), s["search"].fill_(int(search_step))
+
+
+def _adjust_scale(lower_bound, upper_bound, scale_const, succ_now, iter_best_score):
+    """The scale constants after a search step (:393-404), sample by sample in place: bisect between the bounds once an
+    upper bound is known, double until then."""
+    for k in range(len(scale_const)):
+        if bool(succ_now[k]) and int(iter_best_score[k]) != -1:
+            lower_bound[k] = max(lower_bound[k], scale_const[k])
+            if upper_bound[k] < 1e9:
+                scale_const[k] = (lower_bound[k] + upper_bound[k]) * 0.5
+            else:
+                scale_const[k] *= 2
+        else:
+            upper_bound[k] = min(upper_bound[k], scale_const[k])
+            if upper_bound[k] < 1e9:
+                scale_const[k] = (lower_bound[k] + upper_bound[k]) * 0.5
 
 
 def _run_device_loop(plan, pc_ori, normal_ori, kappa_ori, target, gt_target, cfg, gens):
@@ -354,46 +364,36 @@ def _run_device_loop(plan, pc_ori, normal_ori, kappa_ori, target, gt_target, cfg
     b, _, n = pc_ori.shape
     dev = pc_ori.device
     targeted = plan["targeted"]
-    s = _device_loop_state(plan, b, n, dev)
+    loop = _device_loop_state(plan, b, n, dev)
+    s = loop.bufs
     lower_bound = torch.zeros(b)
     scale_const = torch.ones(b) * cfg.initial_const
     upper_bound = torch.ones(b) * 1e10
     loss_rows = None
+
+    def reset_best():
+        s["best_loss"].fill_(1e10), s["best_attack"].fill_(1.0), s["best_step"].fill_(-1), s["best_bs"].fill_(-1)
+
     with torch.no_grad():
         s["ori"].copy_(pc_ori)
         s["target"].copy_(target if targeted else gt_target)
         if plan["curv"]:
             s["normal"].copy_(normal_ori), s["kappa_ori"].copy_(kappa_ori)
-        s["best_loss"].fill_(1e10), s["best_attack"].fill_(1.0), s["best_step"].fill_(-1), s["best_bs"].fill_(-1)
+        reset_best()
         s["pred"].zero_()
-        if plan["graph"] and s["graphs"] is None and plan["steps"] > 0 and cfg.binary_max_steps > 0:
-            # capture once (after eager warm-up passes on a side stream, as torch requires) from the unperturbed cloud — no
-            # draw from any generator — then put back what the warm-up passes wrote
-            s["rewind"](torch.zeros_like(s["offset"]), scale_const, 0)
-            s["graphs"] = _graphed.LoopGraph(s["body"], dev, 2, counts=(1, LOOP_BLOCK), owners=(plan["victim"],))
-            s["best_loss"].fill_(1e10), s["best_attack"].fill_(1.0), s["best_step"].fill_(-1), s["best_bs"].fill_(-1)
+        if plan["graph"] and loop.graphs is None and plan["steps"] > 0 and cfg.binary_max_steps > 0:
+            # capture once from the unperturbed cloud — no draw from any generator — then put back what the warm-up passes
+            # wrote
+            _rewind(s, plan, torch.zeros_like(s["offset"]), scale_const, 0)
+            loop.capture(reset_best)
         for search_step in range(cfg.binary_max_steps):
-            s["rewind"](_draw_offset(b, 3, n, dev, cfg, gens), scale_const, search_step)
-            if plan["graph"] and plan["steps"] > 0:
-                s["graphs"].run(plan["steps"])
-            else:
-                for _ in range(plan["steps"]):
-                    s["body"]()
+            _rewind(s, plan, _draw_offset(b, 3, n, dev, cfg, gens), scale_const, search_step)
+            loop.run(plan["steps"])
             # one read-back per search step: the loss rows, the last prediction and the step's best label (:393-404)
             loss_rows = s["loss_rows"].cpu()
             succ_now = _compare(s["pred"], target, gt_target, targeted).cpu()
             ibs = s["iter_best_score"].cpu()
-            for k in range(b):
-                if bool(succ_now[k]) and int(ibs[k]) != -1:
-                    lower_bound[k] = max(lower_bound[k], scale_const[k])
-                    if upper_bound[k] < 1e9:
-                        scale_const[k] = (lower_bound[k] + upper_bound[k]) * 0.5
-                    else:
-                        scale_const[k] *= 2
-                else:
-                    upper_bound[k] = min(upper_bound[k], scale_const[k])
-                    if upper_bound[k] < 1e9:
-                        scale_const[k] = (lower_bound[k] + upper_bound[k]) * 0.5
+            _adjust_scale(lower_bound, upper_bound, scale_const, succ_now, ibs)
         return s["best_attack"].clone(), s["best_loss"].clone(), s["best_step"].clone(), loss_rows
 
 
@@ -406,7 +406,7 @@ def _finish(transfer, best_attack, target, targeted, best_loss, best_attack_step
             if m is None:
                 fails.append(None)
                 continue
-            lab = torch.argmax(_logits_of(m(best_attack.float())), dim=1)
+            lab = torch.argmax(_graphed.logits_of(m(best_attack.float())), dim=1)
             fails.append(int(((lab == target) if not targeted else (lab != target)).sum().item()))
     geoA3_attack.last_transfer_fails = dict(zip(("pt", "ptm", "pts", "dgcnn", "cur"), fails))
 
@@ -552,12 +552,12 @@ def _geoA3_attack(net, pt_model, ptm_model, pts_model, dgcnn_model, cur_model, p
                     if input_curr_iter.size(2) < input_all.size(2):
                         votes = torch.zeros(b, device=dev)
                         for _ in range(cfg.eval_num):
-                            lab = torch.max(_logits_of(net(farthest_points_sample(input_all, cfg.npoint))), 1)[1]
+                            lab = torch.max(_graphed.logits_of(net(farthest_points_sample(input_all, cfg.npoint))), 1)[1]
                             votes += _compare(lab, target, gt_target, targeted).float()
                             output_label = lab
                         attack_success = votes > 0.5 * cfg.eval_num
                     else:
-                        output_label = torch.argmax(_logits_of(net(input_curr_iter)), dim=1)
+                        output_label = torch.argmax(_graphed.logits_of(net(input_curr_iter)), dim=1)
                         attack_success = _compare(output_label, target, gt_target, targeted)
                     record(output_label, attack_success, constrain_loss.detach())
             else:
@@ -626,16 +626,6 @@ def _geoA3_attack(net, pt_model, ptm_model, pts_model, dgcnn_model, cur_model, p
         # adjust the scale constants (:393-404), one host round trip per search step
         succ_now = _compare(output_label, target, gt_target, targeted).cpu()
         ibs = iter_best_score.cpu()
-        for k in range(b):
-            if bool(succ_now[k]) and int(ibs[k]) != -1:
-                lower_bound[k] = max(lower_bound[k], scale_const[k])
-                if upper_bound[k] < 1e9:
-                    scale_const[k] = (lower_bound[k] + upper_bound[k]) * 0.5
-                else:
-                    scale_const[k] *= 2
-            else:
-                upper_bound[k] = min(upper_bound[k], scale_const[k])
-                if upper_bound[k] < 1e9:
-                    scale_const[k] = (lower_bound[k] + upper_bound[k]) * 0.5
+        _adjust_scale(lower_bound, upper_bound, scale_const, succ_now, ibs)
 
     return _finish(transfer, best_attack, target, targeted, best_loss, best_attack_step, loss_curves)

@@ -122,91 +122,82 @@ def thompson_sample_attack(thompson, obj, label, model, num_init=1):
     return torch.as_tensor(chosen, dtype=torch.float32).to(obj.device), thompson
 
 
-class _Ctri:
-    """The CTRI loop on B clouds: static buffers, one step as a function, and (fast path) its hipGraph. Clouds that take
+class _Ctri(_graphed.DeviceLoop):
+    """The CTRI loop on B clouds: static buffers, one step as the body, captured (fast path) as one step. Clouds that take
     no part (not attacked, or already fooled by TSI) are latched as done before the first step: their W, steps and kept_*
     never change, and the loop's shape — hence its captured graph — depends on the batch alone."""
 
-    def __init__(self, victim, B, N, dev, fast, kind, kappa, lr):
+    def __init__(self, victim, B, N, dev, fast, kind, kappa, lr, key=None):
+        # the graph bakes in the addresses of the folded weights: it holds what it points at (LoopGraph.keep)
+        super().__init__(key, dev, owners=(victim,), counts=(1,), warmup=2)
         self.victim, self.fast, self.kind, self.kappa, self.lr = victim, fast, kind, float(kappa), float(lr)
         f32 = dict(dtype=torch.float32, device=dev)
-        self.x, self.xo = torch.zeros((B, 3, N), **f32), torch.zeros((B, 3, N), **f32)
-        self.W, self.m, self.v = (torch.zeros((B, 3, 3), **f32) for _ in range(3))
-        self.label = torch.zeros((B,), dtype=torch.int64, device=dev)
-        self.kept_pred = torch.zeros((B,), dtype=torch.int64, device=dev)
-        self.done = torch.zeros((B,), dtype=torch.int32, device=dev)
-        self.steps = torch.zeros((B,), dtype=torch.int32, device=dev)
-        self.kept_out = None                   # [B, ncls], allocated by the first step from the victim's output
-        self.graph = None
+        b = self.bufs
+        b["x"], b["xo"] = torch.zeros((B, 3, N), **f32), torch.zeros((B, 3, N), **f32)
+        b["W"], b["m"], b["v"] = (torch.zeros((B, 3, 3), **f32) for _ in range(3))
+        b["label"] = torch.zeros((B,), dtype=torch.int64, device=dev)
+        b["kept_pred"] = torch.zeros((B,), dtype=torch.int64, device=dev)
+        b["done"] = torch.zeros((B,), dtype=torch.int32, device=dev)
+        b["steps"] = torch.zeros((B,), dtype=torch.int32, device=dev)
+        b["kept_out"] = None                   # [B, ncls], allocated by the first step from the victim's output
 
     def load(self, x, label, W, active=None):
         """active: bool [B], the clouds that run (default: all)."""
-        self.x.copy_(x), self.label.copy_(label), self.W.copy_(W.reshape(-1, 3, 3))
-        for t in (self.m, self.v, self.steps, self.kept_out, self.kept_pred):
+        b = self.bufs
+        b["x"].copy_(x), b["label"].copy_(label), b["W"].copy_(W.reshape(-1, 3, 3))
+        for t in (b["m"], b["v"], b["steps"], b["kept_out"], b["kept_pred"]):
             if t is not None:
                 t.zero_()
         if active is None:
-            self.done.zero_()
+            b["done"].zero_()
         else:
-            self.done.copy_((~active).to(torch.int32))
-        ops.iso_apply(self.x, self.W, out=self.xo)
+            b["done"].copy_((~active).to(torch.int32))
+        ops.iso_apply(b["x"], b["W"], out=b["xo"])
 
     def _update(self, pred, row, **grad):
-        if self.kept_out is None:
-            self.kept_out = torch.zeros_like(row)
-        ops.iso_update(self.x, self.xo, self.W, self.m, self.v, pred, self.label, row, self.done, self.steps,
-                       self.kept_out, self.kept_pred, self.lr, **grad)
+        b = self.bufs
+        if b["kept_out"] is None:
+            b["kept_out"] = torch.zeros_like(row)
+        ops.iso_update(b["x"], b["xo"], b["W"], b["m"], b["v"], pred, b["label"], row, b["done"], b["steps"],
+                       b["kept_out"], b["kept_pred"], self.lr, **grad)
 
     def step(self):
+        b = self.bufs
         if self.fast:     # the victim's fused passes (no autograd) + ONE launch for everything else
-            logp, pred, _, gx = self.victim.fused_loss_and_grad(self.xo, self.label, self.kind, self.kappa, scale=1.0)
+            logp, pred, _, gx = self.victim.fused_loss_and_grad(b["xo"], b["label"], self.kind, self.kappa, scale=1.0)
             self._update(pred, logp, g=gx)
             return
         # any victim: autograd through IsoTransform. The loss is taken on what the victim returns: the margin on the
         # output as given (kind + 4); the cross-entropy applies its own log-softmax to it, as F.cross_entropy does
-        Wp = self.W.detach().requires_grad_()
+        Wp = b["W"].detach().requires_grad_()
         with torch.enable_grad():
-            out = self.victim(ops.IsoTransform.apply(self.x, Wp))[0]
-        _, pred, _, g_out = ops.cls_loss(out.detach(), self.label, self.kind + 4 if self.kind == 0 else self.kind, self.kappa,
+            out = self.victim(ops.IsoTransform.apply(b["x"], Wp))[0]
+        _, pred, _, g_out = ops.cls_loss(out.detach(), b["label"], self.kind + 4 if self.kind == 0 else self.kind, self.kappa,
                                          scale=1.0)
         (gW,) = torch.autograd.grad(out, Wp, g_out)
         self._update(pred, out.detach().contiguous(), gW=gW.contiguous())
 
-    def capture(self, warmup=2):
-        """Capture one step (after `warmup` eager ones on the side stream; they advance the state: load() again)."""
-        # the graph bakes in the addresses of the folded weights: it holds what it points at (LoopGraph.keep)
-        self.graph = _graphed.LoopGraph(self.step, self.x.device, warmup, owners=(self.victim,))
-
-    def run(self, num_steps):
-        for _ in range(num_steps):
-            if self.graph is not None:
-                self.graph.replay()
-            else:
-                self.step()
+    body = step
 
 
 _MAX_CTRI_CACHE = 4
 
 
 def _ctri_loop(victim, x, label, W, active, target, kappa, step_size, fused=True, graph=True, cache=None):
-    """A loaded _Ctri for x [B,3,N] from the matrices W [B,3,3], ready to run(). cache: a dict that keeps captured
-    loops per (shape, settings, weights); None: nothing is captured."""
+    """A loaded _Ctri for x [B,3,N] from the matrices W [B,3,3], ready to run(). cache: a graphed.LoopCache (or any
+    dict) that keeps captured loops per (shape, settings, weights); None: nothing is captured."""
     B, _, N = x.shape
     fast = bool(fused and hasattr(victim, "fused_loss_and_grad"))
     kind = 0 if target != 0 else 3          # pc3d_cls_loss_f32: the CW margin (+ kappa), or minus the cross-entropy
-    if fast and graph and cache is not None:
-        wkey = _graphed.weights_key(victim)
-        key = (B, N, x.device, kind, float(kappa), float(step_size), wkey)
-        c = cache.get(key)
-        if c is None:
-            while len(cache) >= _MAX_CTRI_CACHE:
-                cache.pop(next(iter(cache)))
-            c = _Ctri(victim, B, N, x.device, True, kind, kappa, step_size)
+    cached = fast and graph and cache is not None
+    key = _graphed.loop_key(victim, x.device, B, N, kind, float(kappa), float(step_size)) if cached else None
+    c = cache.get(key) if cached else None
+    if c is None:
+        c = _Ctri(victim, B, N, x.device, fast, kind, kappa, step_size, key)
+        if cached:
+            cache[key] = c
             c.load(x, label, W, active)
             c.capture()
-            cache[key] = c
-    else:
-        c = _Ctri(victim, B, N, x.device, fast, kind, kappa, step_size)
     c.load(x, label, W, active)
     return c
 
@@ -246,7 +237,7 @@ class ISOAttack:
         self.num_steps, self.step_size, self.LAMBDA, self.target, self.kappa = num_steps, step_size, LAMBDA, target, kappa
         self.num_init, self.attack_type, self.tsi_batch, self.fused, self.graph = num_init, attack_type, tsi_batch, fused, graph
         self.thompson = thompson if thompson is not None else ts.BernThompson(ts.environment(d=d, a0=a, b0=b))
-        self._ctri_cache = {}
+        self._ctri_cache = _graphed.LoopCache(_MAX_CTRI_CACHE)
 
     def attack(self, pc, label):
         with torch.cuda.device(pc.device):

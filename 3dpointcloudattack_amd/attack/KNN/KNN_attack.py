@@ -17,6 +17,7 @@ import torch.optim as optim
 from ... import graphed as _graphed
 from ... import ops
 from ... import streams as _streams
+from ..CW.CW_utils import adv_utils as _adv_utils
 from ..CW.CW_utils import clip_utils as _clip_utils
 from ..CW.CW_utils import dist_utils as _dist_utils
 
@@ -27,10 +28,6 @@ def rand_row(array, dim_needed):
     row_sequence = np.arange(row_total)
     np.random.shuffle(row_sequence)
     return array[row_sequence[0:dim_needed], :]
-
-
-def _logits_of(out):
-    return out[0] if isinstance(out, tuple) else out
 
 
 TRANSFER_MODELS = (("pt_fail", "pt_model"), ("ptm_fail", "ptm_model"), ("pts_fail", "pts_model"),
@@ -44,7 +41,7 @@ def count_transfer_fails(attack, result, target):
         m = getattr(attack, attr)
         if m is None:
             continue
-        p = torch.argmax(_logits_of(m(result)), dim=1)
+        p = torch.argmax(_graphed.logits_of(m(result)), dim=1)
         setattr(attack, name, getattr(attack, name) + int((~attack._success(p, target)).sum().item()))
 
 
@@ -100,7 +97,7 @@ class CWKNN:
         self.graph = graph
         self.device_loop = device_loop
         self.last_path = None
-        self._loop_cache = None                # the device loop's buffers and captured graphs, kept from call to call
+        self._loop_cache = _graphed.LoopCache(1)    # the device loop (buffers and captured graphs), kept from call to call
 
     def _success(self, pred, target):
         return (pred != target) if self.attack_method == 'untarget' else (pred == target)
@@ -121,14 +118,13 @@ class CWKNN:
         """The constants of the device loop when it applies, else None: a GPU victim with fused_attack_grad (the two
         PointNetCls variants), an adversarial functor the CW loop maps to ops.LOSS_KINDS, ChamferkNNDist / ChamferDist
         with 'adv2ori', a clip functor _fused_clip() recognises, and a cloud the update kernel holds."""
-        from ..CW.CW_attack import CW as _CW
         victim = _graphed.unwrap(self.model)
         fc = self._fused_clip()
         if fc is None or self.device.type != "cuda" or not hasattr(victim, "fused_attack_grad") or K > ops.KNN_LOOP_MAX_POINTS:
             return None
         if next(victim.parameters()).device.type != "cuda":
             return None
-        kind = _CW._own_adv_kind(self)          # the CW loop's mapping of the adversarial functors
+        kind = _adv_utils.own_adv_kind(self.adv_func)          # the CW loop's mapping of the adversarial functors
         if kind is None:
             return None
         df = self.dist_func
@@ -151,15 +147,14 @@ class CWKNN:
                     clip_mode="project_clip" if fc[1] else "clip", scale=1.0 / G, has_normal=bool(has_normal and fc[1]))
 
     def _device_loop_state(self, plan, B, K):
-        """Buffers (static: the graphs point at them), the iteration body and the captured graphs, rebuilt when the shape,
-        a constant of the loop, the kernel flavour or the victim's weights change."""
-        victim, dev = plan["victim"], self.device
-        wkey = _graphed.weights_key(victim)
-        key = (B, K, float(self.attack_lr), bool(self.graph), bool(ops._det()), wkey,
-               tuple(sorted((n, v) for n, v in plan.items() if n != "victim")))
-        c = self._loop_cache
-        if c is not None and c["key"] == key:
-            return c
+        """The loop of this shape, these constants, this kernel flavour and these weights: its buffers (static: the graphs
+        point at them), the iteration body and, once captured, the graphs — the last one is kept from call to call."""
+        victim, dev, lr = plan["victim"], self.device, self.attack_lr
+        key = _graphed.loop_key(victim, dev, B, K, float(lr), bool(self.graph),
+                                tuple(sorted((n, v) for n, v in plan.items() if n != "victim")))
+        loop = self._loop_cache.get(key)
+        if loop is not None:
+            return loop
         f32 = dict(dtype=torch.float32, device=dev)
         adv, ori, m, v = (torch.zeros((B, 3, K), **f32) for _ in range(4))
         normal = torch.zeros((B, 3, K), **f32) if plan["has_normal"] else None
@@ -180,38 +175,34 @@ class CWKNN:
                 if k:
                     ops.knn_search_into(adv, knn_d, knn_idx)
                 ops.nn_search_into(adv, ori, nn_d, nn_idx)
-                ops.knn_attack_update(adv, ori, gx, m, v, step, self.attack_lr, knn_d, knn_idx, nn_idx, plan["c_ch"],
+                ops.knn_attack_update(adv, ori, gx, m, v, step, lr, knn_d, knn_idx, nn_idx, plan["c_ch"],
                                       plan["c_knn"], plan["alpha"], plan["budget"], plan["clip_mode"], normal)
 
-        def rewind(adv0):
-            adv.copy_(adv0)
-            m.zero_(), v.zero_(), step.zero_()
-
-        c = self._loop_cache = dict(key=key, adv=adv, ori=ori, normal=normal, target=target, body=body, rewind=rewind,
-                                    graphs=None, plan=plan, m=m, v=v, step=step, pred=pred, knn_d=knn_d, knn_idx=knn_idx,
-                                    nn_d=nn_d, nn_idx=nn_idx)
-        return c
+        bufs = dict(adv=adv, ori=ori, normal=normal, target=target, plan=plan, m=m, v=v, step=step, pred=pred, knn_d=knn_d,
+                    knn_idx=knn_idx, nn_d=nn_d, nn_idx=nn_idx)
+        return self._loop_cache.put(key, _graphed.DeviceLoop(key, dev, owners=(victim,), counts=(1, self.LOOP_BLOCK),
+                                                             warmup=2, body=body, bufs=bufs))
 
     LOOP_BLOCK = 16      # iterations per graph replay; the remainder replays single-iteration graphs
 
     def _run_device_loop(self, plan, adv_data, ori_data, normal, target):
         B, _, K = adv_data.shape
-        c = self._device_loop_state(plan, B, K)
+        loop = self._device_loop_state(plan, B, K)
+        c = loop.bufs
+
+        def rewind():
+            c["adv"].copy_(adv_data)
+            c["m"].zero_(), c["v"].zero_(), c["step"].zero_()
+
         with torch.no_grad():
             c["ori"].copy_(ori_data)
             c["target"].copy_(target)
             if c["normal"] is not None:
                 c["normal"].copy_(normal)
-            c["rewind"](adv_data)
-            if self.graph and c["graphs"] is None and self.num_iter > 0:
-                # capture once (after eager warm-up passes on a side stream, as torch requires), then rewind the state
-                c["graphs"] = _graphed.LoopGraph(c["body"], self.device, 2, counts=(1, self.LOOP_BLOCK), owners=(plan["victim"],))
-                c["rewind"](adv_data)
-            if not self.graph:
-                for _ in range(self.num_iter):
-                    c["body"]()
-            elif self.num_iter > 0:
-                c["graphs"].run(self.num_iter)
+            rewind()
+            if self.graph and self.num_iter > 0:
+                loop.capture(rewind)
+            loop.run(self.num_iter)
             adv_data.copy_(c["adv"])
 
     def attack(self, data, target):
@@ -253,7 +244,7 @@ class CWKNN:
         # clean forward (:76-78). Kept even when nothing is printed: a PointNet++ victim draws its FPS start indices
         # from the global RNG on every forward, so skipping it would shift the stream the reference sees.
         with torch.no_grad():
-            clean_logits = _logits_of(self.model(ori_data))
+            clean_logits = _graphed.logits_of(self.model(ori_data))
             clean_pred = torch.argmax(clean_logits, dim=1)
         if self.verbose:
             print("ori label:", clean_pred.tolist())
@@ -312,7 +303,7 @@ class CWKNN:
                         side.wait_stream(cur)
                         with torch.cuda.stream(side):
                             terms = self.dist_func.per_sample_terms(adv_alias, ori_data, up_dist)   # channel-first, zero-copy
-                    logits = _logits_of(self.model(adv_data))
+                    logits = _graphed.logits_of(self.model(adv_data))
                     a_term = self.adv_func.per_sample(logits.contiguous(), target, up_adv)
                     if a_term is None:
                         raise RuntimeError("CWKNN: the victim's logits changed shape / dtype between forwards")
@@ -331,7 +322,7 @@ class CWKNN:
                     with torch.cuda.stream(side):
                         # in the official tensorflow code they use sum instead of mean, hence * K (:119-123)
                         dist_loss = self.dist_func(adv_data.transpose(1, 2).contiguous(), ori_t).mean() * K
-                logits = _logits_of(self.model(adv_data))  # [B, num_classes]
+                logits = _graphed.logits_of(self.model(adv_data))  # [B, num_classes]
                 adv_loss = self.adv_func(logits, target).mean()
                 if side is not None:
                     cur.wait_stream(side)
@@ -358,13 +349,13 @@ class CWKNN:
     def _finish(self, adv_data, target, B):
         # end of CW attack
         with torch.no_grad():
-            pred = torch.argmax(_logits_of(self.model(adv_data)), dim=-1)  # [B]
+            pred = torch.argmax(_graphed.logits_of(self.model(adv_data)), dim=-1)  # [B]
             success_num = int(self._success(pred, target).sum().item())
             if self.verbose:
                 print('Successfully attack {}/{}'.format(success_num, B))
             result = adv_data.detach().float()
             # Test attack + transfer models (:160-240)
-            self.attack_fail += int((~self._success(torch.argmax(_logits_of(self.model(result)), dim=1), target)).sum().item())
+            self.attack_fail += int((~self._success(torch.argmax(_graphed.logits_of(self.model(result)), dim=1), target)).sum().item())
             count_transfer_fails(self, result, target)
 
         adv_np = adv_data.detach().transpose(1, 2).contiguous().cpu().numpy()  # [B, K, 3]

@@ -49,45 +49,39 @@ def _first(out):
     return out[0] if isinstance(out, (tuple, list)) else out
 
 
-class _Loop:
-    """The fast path's state for one batch shape: static buffers, one step as a function, and its hipGraph."""
+class _Loop(_graphed.DeviceLoop):
+    """The fast path's loop for one batch shape: static buffers, one step as the body, captured as one step."""
 
-    def __init__(self, victim, B, N, dev, step_size, eps):
+    def __init__(self, victim, B, N, dev, step_size, eps, key=None):
+        # the graph bakes in the addresses of the folded weights: it holds what it points at (LoopGraph.keep)
+        super().__init__(key, dev, owners=(victim,), counts=(1,), warmup=2)
         self.victim, self.step_size, self.eps = victim, float(step_size), float(eps)
         f32 = dict(dtype=torch.float32, device=dev)
-        self.x, self.ori, self.xe, self.nrm = (torch.zeros((B, 3, N), **f32) for _ in range(4))
-        self.label = torch.zeros((B,), dtype=torch.int64, device=dev)
-        self.graph = None
+        self.bufs.update({nm: torch.zeros((B, 3, N), **f32) for nm in ("x", "ori", "xe", "nrm")},
+                         label=torch.zeros((B,), dtype=torch.int64, device=dev))
 
     def load(self, x, ori, label):
-        self.x.copy_(x), self.ori.copy_(ori), self.label.copy_(label)
+        b = self.bufs
+        b["x"].copy_(x), b["ori"].copy_(ori), b["label"].copy_(label)
 
     def _move(self, nrm):
         # the victim is shown xe (si_frame), as in the reference; its loss is summed over the batch, not averaged: scale 1
-        g = self.victim.fused_attack_grad(self.xe, self.label, "untargeted_logits", 0.0, scale=1.0)[2]
-        ops.si_step(self.x, self.ori, g, self.step_size, self.eps, nrm=nrm)
+        b = self.bufs
+        g = self.victim.fused_attack_grad(b["xe"], b["label"], "untargeted_logits", 0.0, scale=1.0)[2]
+        ops.si_step(b["x"], b["ori"], g, self.step_size, self.eps, nrm=nrm)
 
     def first(self, nrm):
         """Step 0: the normals that came with the cloud."""
-        ops.si_frame(self.x, nrm=nrm, out=self.xe)
+        ops.si_frame(self.bufs["x"], nrm=nrm, out=self.bufs["xe"])
         self._move(nrm)
 
     def step(self):
-        _, idx = ops.knn_raw(self.x, self.x, KNN, q_cf=True, r_cf=True)
-        ops.si_frame(self.x, idx=idx, out=self.xe, nrm_out=self.nrm)
-        self._move(self.nrm)
+        b = self.bufs
+        _, idx = ops.knn_raw(b["x"], b["x"], KNN, q_cf=True, r_cf=True)
+        ops.si_frame(b["x"], idx=idx, out=b["xe"], nrm_out=b["nrm"])
+        self._move(b["nrm"])
 
-    def capture(self, warmup=2):
-        """Capture one step (after `warmup` eager ones on the side stream; they advance the state: load() again)."""
-        # the graph bakes in the addresses of the folded weights: it holds what it points at (LoopGraph.keep)
-        self.graph = _graphed.LoopGraph(self.step, self.x.device, warmup, owners=(self.victim,))
-
-    def run(self, steps):
-        for _ in range(steps):
-            if self.graph is not None:
-                self.graph.replay()
-            else:
-                self.step()
+    body = step
 
 
 def simba_basis(N):
@@ -118,14 +112,17 @@ def sign_order(step_size):
     return tuple({step_size, -step_size})
 
 
-class _QueryLoop:
-    """The query loops' state for one batch shape: static buffers, one step as a function, and its hipGraph of POLL steps.
+class _QueryLoop(_graphed.DeviceLoop):
+    """The query loops' loop for one batch shape: static buffers, POLL steps as the body, captured as one such round.
+    classifier / pre_head / top5: the attack's, handed in (the loop does not hold the attack, which holds the loop).
     frame: the shape-invariant mode (the state is P', a candidate is the whole cloud U^T (P' + pert) - t)."""
 
-    def __init__(self, attack, B, N, L, k, dev, frame, table_eps, fast):
-        self.attack, self.fast, self.L = attack, fast, L
+    def __init__(self, classifier, pre_head, top5, B, N, L, k, dev, frame, table_eps, fast, key=None):
+        super().__init__(key, dev, owners=(classifier,), counts=(1,), warmup=1)
+        self.classifier, self.pre_head, self.fast, self.L = classifier, pre_head, fast, L
         f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
-        s = self.s = dict(top=5 if attack.top5_attack else 1)
+        s = self.bufs
+        s["top"] = 5 if top5 else 1
         s["st"], s["last"] = torch.zeros((B, 3, N), **f32), torch.zeros((B, 3, N), **f32)
         s["cand"] = torch.zeros((2 * B, 3, N), **f32)
         s["ori"], s["nrm"], s["dir"] = ((torch.zeros((B, 3, N), **f32), torch.zeros((B, 3, N), **f32),
@@ -138,12 +135,11 @@ class _QueryLoop:
         s["label"] = torch.zeros((B,), dtype=torch.int64, device=dev)
         s["last_logp"] = torch.zeros((B, k), **f32)
         s["acc_trace"], s["loss_trace"] = torch.zeros((B, L), **i32), torch.zeros((B, L, 2), **f32)
-        self.graph = None
 
     def load(self, x, label, tab, eps, active, adv_target0, logp0, nrm=None, dirs=None):
         """The clean clouds x [B,3,N], the tables, the clouds whose loop runs, and the initial query's outcome; then the
         first candidates."""
-        s = self.s
+        s = self.bufs
         s["tab"].copy_(tab), s["eps"].copy_(eps), s["label"].copy_(label)
         s["pos"].zero_(), s["queries"].fill_(1), s["last_try"].zero_(), s["best"].fill_(-999.)
         s["done"].copy_(~active), s["adv_target"].copy_(adv_target0), s["last_logp"].copy_(logp0)
@@ -156,30 +152,23 @@ class _QueryLoop:
         ops.query_step(s, init=True)
 
     def step(self):
-        a, cand = self.attack, self.s["cand"]
+        cand = self.bufs["cand"]
         if self.fast:
-            logp = torch.log_softmax(_pointnet.fused_forward(a.classifier, cand)[0], dim=1)
+            logp = torch.log_softmax(_pointnet.fused_forward(self.classifier, cand)[0], dim=1)
         else:
-            logp = _first(a.classifier(a.pre_head(cand) if a.pre_head is not None else cand)).float().contiguous()
-        ops.query_step(self.s, logp)
+            logp = _first(self.classifier(self.pre_head(cand) if self.pre_head is not None else cand)).float().contiguous()
+        ops.query_step(self.bufs, logp)
 
-    def _steps(self):
+    def body(self):
         for _ in range(POLL):
             self.step()
 
-    def capture(self, warmup=1):
-        """Capture POLL steps (after `warmup` eager rounds on the side stream; they advance the state: load() again)."""
-        self.graph = _graphed.LoopGraph(self._steps, self.s["cand"].device, warmup, owners=(self.attack.classifier,))
-
-    def run(self):
-        """Steps until every cloud is latched; the latches come back to the host once per POLL steps. A latched cloud is
-        left alone by the kernel, so a round may run past the end of the tables."""
+    def run_polled(self):
+        """Rounds of POLL steps until every cloud is latched; the latches come back to the host once per round. A latched
+        cloud is left alone by the kernel, so a round may run past the end of the tables."""
         for _ in range((self.L + POLL - 1) // POLL):
-            if self.graph is not None:
-                self.graph.replay()
-            else:
-                self._steps()
-            if bool(self.s["done"].all()):
+            self.run(1)
+            if bool(self.bufs["done"].all()):
                 break
 
 
@@ -214,8 +203,8 @@ class PointCloudAttack(object):
         if self.defense_method is not None:
             self.pre_head = self.get_defense_head(self.defense_method)
         self.fused, self.graph = fused, graph
-        self._loops = {}
-        self._query_loops = {}
+        self._loops = _graphed.LoopCache(_MAX_LOOPS)
+        self._query_loops = _graphed.LoopCache(_MAX_LOOPS)
         self.generator = getattr(args, "generator", None)      # simbapp's draws (a torch.Generator on the clouds' device)
         self.last_query = None                                  # the last query loop's traces (see _query)
 
@@ -312,19 +301,14 @@ class PointCloudAttack(object):
         """A loaded _Loop for x [B,3,N]; with graph=True captured once per (shape, settings, weights)."""
         B, _, N = x.shape
         v = self.wb_classifier
-        if not self.graph:
-            c = _Loop(v, B, N, x.device, self.step_size, self.eps)
-        else:
-            wkey = _graphed.weights_key(v)
-            key = (B, N, x.device, float(self.step_size), float(self.eps), wkey)
-            c = self._loops.get(key)
-            if c is None:
-                while len(self._loops) >= _MAX_LOOPS:
-                    self._loops.pop(next(iter(self._loops)))
-                c = _Loop(v, B, N, x.device, self.step_size, self.eps)
+        key = _graphed.loop_key(v, x.device, B, N, float(self.step_size), float(self.eps)) if self.graph else None
+        c = self._loops.get(key) if self.graph else None
+        if c is None:
+            c = _Loop(v, B, N, x.device, self.step_size, self.eps, key)
+            if self.graph:
+                self._loops.put(key, c)
                 c.load(x, ori, target)
                 c.capture()
-                self._loops[key] = c
         c.load(x, ori, target)
         return c
 
@@ -458,18 +442,14 @@ class PointCloudAttack(object):
 
     def _query_loop(self, B, N, L, k, dev, frame, table_eps):
         fast = self._query_fast()
-        if not (fast and self.graph):
-            return _QueryLoop(self, B, N, L, k, dev, frame, table_eps, fast)
-        v = self.classifier
-        wkey = _graphed.weights_key(v)
-        key = (B, N, L, k, dev, frame, table_eps, bool(self.top5_attack), wkey)
-        c = self._query_loops.get(key)
+        cached = fast and self.graph
+        key = _graphed.loop_key(self.classifier, dev, B, N, L, k, frame, table_eps, bool(self.top5_attack)) if cached else None
+        c = self._query_loops.get(key) if cached else None
         if c is None:
-            while len(self._query_loops) >= _MAX_LOOPS:
-                self._query_loops.pop(next(iter(self._query_loops)))
-            c = _QueryLoop(self, B, N, L, k, dev, frame, table_eps, fast)
-            c.capture()                     # on the zeroed buffers (every table entry 0 is in range); load() follows
-            self._query_loops[key] = c
+            c = _QueryLoop(self.classifier, self.pre_head, self.top5_attack, B, N, L, k, dev, frame, table_eps, fast, key)
+            if cached:
+                self._query_loops.put(key, c)
+                c.capture()                 # on the zeroed buffers (every table entry 0 is in range); load() follows
         return c
 
     def _query(self, method, x, target, logp0, adv_target0, active, tab, eps, nrm=None, dirs=None):
@@ -486,8 +466,8 @@ class PointCloudAttack(object):
         with torch.cuda.device(dev), torch.no_grad():
             c = self._query_loop(B, N, L, logp0.shape[1], dev, frame, eps.dim() == 3)
             c.load(x, target, tab, eps, active, adv_target0.to(torch.int32), logp0, nrm, dirs)
-            c.run()
-            s = c.s
+            c.run_polled()
+            s = c.bufs
             adv_target = s["adv_target"].long()
             if bool((adv_target == -2).any()):
                 raise ValueError(f"{_QUERY_NAMES[method]}: a table entry or a label is out of range")

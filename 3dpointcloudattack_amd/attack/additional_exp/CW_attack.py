@@ -26,7 +26,6 @@ draw-for-draw comparable with the reference: see ``CW.__init__``).
 """
 import random
 import time
-import types
 
 import numpy as np
 import torch
@@ -34,6 +33,7 @@ import torch.optim as optim
 
 from ... import graphed as _graphed
 from ... import ops
+from ..CW.CW_attack import bisect_weights
 
 
 class AdvLossAdapter:
@@ -145,11 +145,10 @@ class CW:
         self.last_path = None
         self.last_draws = None                 # who drew the last attack()'s views: "device", "host" or None (no views)
         self.draw_seconds = 0.0                # host time the last device-loop attack() spent drawing rotations / indices
-        self._loop_cache = None                # the device loop's buffers and captured graphs, kept from call to call
+        self._loop_cache = _graphed.LoopCache(1)    # the device loop (buffers and captured graphs), kept from call to call
 
     def _forward(self, x):
-        out = self.model(x)
-        return out[0] if isinstance(out, tuple) else out
+        return _graphed.logits_of(self.model(x))
 
     # ---- device loop (PointNet victim + own functors): no autograd, ONE stacked victim pass, replayed from hipGraphs ----
     EOT_VIEWS = 10       # :193 — the expectation's ten views
@@ -160,7 +159,7 @@ class CW:
         PointNetCls variants), an AdvLossAdapter around functors the CW loop maps to ops.LOSS_KINDS, ChamferDist('adv2ori')
         or L2Dist — inside PerSampleDist, or bare at B = 1 where the batch mean is the identity — and a cloud the kernels
         hold. ChamferkNNDist and arbitrary callables take the autograd path."""
-        from ..CW.CW_attack import CW as _CW
+        from ..CW.CW_utils import adv_utils as _adv_utils
         from ..CW.CW_utils import dist_utils as _dist_utils
         victim = _graphed.unwrap(self.model)
         if self.device.type != "cuda" or not hasattr(victim, "fused_attack_grad") or K > ops.EOT_MAX_POINTS:
@@ -170,7 +169,7 @@ class CW:
         if type(self.adv_func) is not AdvLossAdapter:
             return None
         af = self.adv_func.targeted_func if self.whether_target else self.adv_func.untargeted_func
-        kind = _CW._own_adv_kind(types.SimpleNamespace(adv_func=af))
+        kind = _adv_utils.own_adv_kind(af)
         if kind is None:
             return None
         df = self.dist_func
@@ -191,17 +190,17 @@ class CW:
                     untarget=not self.whether_target, box=float(self.box_constraint), scale=1.0 / ((E if E else 1) * B))
 
     def _device_loop_state(self, plan, B, K):
-        """Buffers (static: the graphs point at them), the iteration body and the captured graphs, rebuilt when the shape,
-        a constant of the loop, the kernel flavour or the victim's weights change."""
-        victim, dev = plan["victim"], self.device
+        """The loop of this shape, these constants, this kernel flavour and these weights: its buffers (static: the graphs
+        point at them), the iteration body and, once captured, the graphs — the last one is kept from call to call."""
+        victim, dev, lr = plan["victim"], self.device, self.attack_lr
         device_draws = bool(self.device_rng and plan["E"])
         if device_draws and self.seed is None:
             self.seed = int(torch.initial_seed()) & 0x7FFFFFFFFFFFFFFF
-        key = (B, K, float(self.attack_lr), device_draws, int(self.seed) if device_draws else None, bool(self.graph), bool(ops._det()), _graphed.weights_key(victim),
-               tuple(sorted((n, v) for n, v in plan.items() if n != "victim")))
-        c = self._loop_cache
-        if c is not None and c["key"] == key:
-            return c
+        key = _graphed.loop_key(victim, dev, B, K, float(lr), device_draws, int(self.seed) if device_draws else None,
+                                bool(self.graph), tuple(sorted((n, v) for n, v in plan.items() if n != "victim")))
+        loop = self._loop_cache.get(key)
+        if loop is not None:
+            return loop
         E, LB = plan["E"], self.LOOP_BLOCK
         S, T = 1 + E, 2 * LB
         f32, i32, i64 = (dict(dtype=t, device=dev) for t in (torch.float32, torch.int32, torch.long))
@@ -238,27 +237,18 @@ class CW:
                 _, _, gx = victim.fused_attack_grad(x_in, goal_s, kind, kappa, pred_out=pred, step=step, scale=plan["scale"])
                 if chamfer:
                     ops.nn_search_into(adv, ori, nn_d, nn_idx)
-                ops.eot_update(adv, ori, gx, m, v, step, self.attack_lr, pred, goal, plan["untarget"], bestdist, bestscore,
+                ops.eot_update(adv, ori, gx, m, v, step, lr, pred, goal, plan["untarget"], bestdist, bestscore,
                                o_bestdist, o_bestscore, o_bestattack, rot=rot, inv=inv, renorm=plan["renorm"], stats=stats,
                                arg=arg, input_val=input_val, dist_kind=plan["dist_kind"], w=w, nn_idx=nn_idx, batch_mean=B,
                                one_d=plan["one_d"], box=plan["box"])
 
-        def begin_step():
-            bestdist.fill_(1e10), bestscore.fill_(-1)
-            m.zero_(), v.zero_(), step.zero_()
-
-        def rewind(adv0):
-            adv.copy_(adv0), input_val.copy_(adv0)
-            o_bestdist.fill_(1e10), o_bestscore.fill_(-1), o_bestattack.zero_()
-            begin_step()
-
-        c = self._loop_cache = dict(key=key, plan=plan, device_draws=device_draws, body=body, begin_step=begin_step, rewind=rewind, graphs=None, adv=adv,
-                                    ori=ori, m=m, v=v, o_bestattack=o_bestattack, input_val=input_val, X=X, stats=stats,
-                                    arg=arg, rot=rot, idx=idx, inv=inv, rot_pin=rot_pin, idx_pin=idx_pin, inv_pin=inv_pin,
-                                    nn_d=nn_d, nn_idx=nn_idx, step=step, pred=pred, goal_s=goal_s, goal=goal, w=w,
-                                    bestdist=bestdist, o_bestdist=o_bestdist, bestscore=bestscore, o_bestscore=o_bestscore,
-                                    uploaded=[torch.cuda.Event(), torch.cuda.Event()])
-        return c
+        bufs = dict(plan=plan, device_draws=device_draws, adv=adv, ori=ori, m=m, v=v, o_bestattack=o_bestattack,
+                    input_val=input_val, X=X, stats=stats, arg=arg, rot=rot, idx=idx, inv=inv, rot_pin=rot_pin, idx_pin=idx_pin,
+                    inv_pin=inv_pin, nn_d=nn_d, nn_idx=nn_idx, step=step, pred=pred, goal_s=goal_s, goal=goal, w=w,
+                    bestdist=bestdist, o_bestdist=o_bestdist, bestscore=bestscore, o_bestscore=o_bestscore,
+                    uploaded=[torch.cuda.Event(), torch.cuda.Event()])
+        return self._loop_cache.put(key, _graphed.DeviceLoop(key, dev, owners=(victim,), counts=(1, self.LOOP_BLOCK),
+                                                             warmup=2, body=body, bufs=bufs))
 
     def _draw_block(self, c, half, count, K):
         """`count` iterations' rotations (and resampling indices with their inverse tables) into pinned block `half`, in
@@ -275,12 +265,13 @@ class CW:
                     _inverse_columns(idx[half, it, e] % K, K, inv[half, it, e])
         self.draw_seconds += time.perf_counter() - t0
 
-    def _run_iterations(self, c, K, binary_step=0):
+    def _run_iterations(self, loop, K, binary_step=0):
         """One binary-search step's num_iter iterations: block n of LOOP_BLOCK iterations reads rows (n mod 2) LOOP_BLOCK ...
         of the tables (the step word counts from 0); its draws are uploaded in front of its replay, and the next block's
         are made while it runs — never more than num_iter * EOT_VIEWS sets per step. With device draws the block's rows
         are filled by ONE launch on the current stream in front of its replay (outside the graph: the host knows the draw
         index), and the host neither draws nor waits."""
+        c = loop.bufs
         LB, E = self.LOOP_BLOCK, c["plan"]["E"]
         left = self.num_iter
         host_draws = bool(E) and not c["device_draws"]
@@ -300,11 +291,7 @@ class CW:
                     if c[nm] is not None:
                         c[nm][rows].copy_(c[nm + "_pin"][half, :cnt], non_blocking=True)
                 c["uploaded"][half].record()
-            if c["graphs"] is not None:
-                c["graphs"].run(cnt)
-            else:
-                for _ in range(cnt):
-                    c["body"]()
+            loop.run(cnt)
             left -= cnt
             n += 1
             if host_draws and left:
@@ -313,36 +300,40 @@ class CW:
 
     def _attack_device_loop(self, plan, adv_data, ori_data, goal, B, K):
         dev = self.device
-        c = self._device_loop_state(plan, B, K)
+        loop = self._device_loop_state(plan, B, K)
+        c = loop.bufs
         S = 1 + plan["E"]
         lower_bound = np.zeros((B,))
         upper_bound = np.ones((B,)) * self.max_weight
         current_weight = np.ones((B,)) * self.init_weight
         self.draw_seconds = 0.0
+
+        def begin_step():
+            c["bestdist"].fill_(1e10), c["bestscore"].fill_(-1)
+            c["m"].zero_(), c["v"].zero_(), c["step"].zero_()
+
+        def rewind():
+            c["adv"].copy_(adv_data), c["input_val"].copy_(adv_data)
+            c["o_bestdist"].fill_(1e10), c["o_bestscore"].fill_(-1), c["o_bestattack"].zero_()
+            begin_step()
+
         with torch.no_grad():
             c["ori"].copy_(ori_data)
             c["goal"].copy_(goal)
             c["goal_s"].copy_(goal.repeat(S))
             c["w"].fill_(float(self.init_weight))
-            c["rewind"](adv_data)
-            if self.graph and c["graphs"] is None and self.num_iter > 0 and self.binary_step > 0:
-                # capture once (after eager warm-up passes on a side stream, as torch requires), then rewind the state
-                c["graphs"] = _graphed.LoopGraph(c["body"], dev, 2, counts=(1, self.LOOP_BLOCK), owners=(plan["victim"],))
-                c["rewind"](adv_data)
+            rewind()
+            if self.graph and self.num_iter > 0 and self.binary_step > 0:
+                loop.capture(rewind)
             goal_np = goal.cpu().numpy()
             for binary_step in range(self.binary_step):
-                c["begin_step"]()
+                begin_step()
                 c["w"].copy_(ops.h2d(torch.from_numpy(current_weight).float(), dev))
-                self._run_iterations(c, K, binary_step)
+                self._run_iterations(loop, K, binary_step)
                 # adjust weight factor (:283-303) — one host read per binary-search step
                 bs, bd, obd = c["bestscore"].cpu().numpy(), c["bestdist"].cpu().numpy(), c["o_bestdist"].cpu().numpy()
-                for e in range(B):
-                    hit = (bs[e] == goal_np[e]) if self.whether_target else (bs[e] != goal_np[e])
-                    if hit and bs[e] != -1 and bd[e] <= obd[e]:
-                        lower_bound[e] = max(lower_bound[e], current_weight[e])
-                    else:
-                        upper_bound[e] = min(upper_bound[e], current_weight[e])
-                    current_weight[e] = (lower_bound[e] + upper_bound[e]) / 2.
+                hit = (bs == goal_np) if self.whether_target else (bs != goal_np)
+                bisect_weights(lower_bound, upper_bound, current_weight, hit & (bs != -1) & (bd <= obd))
             fail_idx = torch.from_numpy(lower_bound == 0.).to(dev)
             o_bestattack = torch.where(fail_idx[:, None, None], c["input_val"], c["o_bestattack"])
             o_bestdist = c["o_bestdist"].double()
@@ -458,13 +449,8 @@ class CW:
             # adjust weight factor (:283-303) — one host read per binary-search step
             bs, bd, obd = bestscore.cpu().numpy(), bestdist.cpu().numpy(), o_bestdist.cpu().numpy()
             goal_np = goal.cpu().numpy()
-            for e in range(B):
-                hit = (bs[e] == goal_np[e]) if self.whether_target else (bs[e] != goal_np[e])
-                if hit and bs[e] != -1 and bd[e] <= obd[e]:
-                    lower_bound[e] = max(lower_bound[e], current_weight[e])
-                else:
-                    upper_bound[e] = min(upper_bound[e], current_weight[e])
-                current_weight[e] = (lower_bound[e] + upper_bound[e]) / 2.
+            hit = (bs == goal_np) if self.whether_target else (bs != goal_np)
+            bisect_weights(lower_bound, upper_bound, current_weight, hit & (bs != -1) & (bd <= obd))
 
         # fail to attack some examples: assign them the iterate the last pass started from (:309-310)
         fail_idx = torch.from_numpy(lower_bound == 0.).to(dev)

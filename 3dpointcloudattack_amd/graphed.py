@@ -45,10 +45,9 @@ def capturing():
 def capture_guard():
     """Run a hipGraph capture with Python's cyclic garbage collector off (after one explicit collection); yields the
     capture's keep-alive list (see note_captured) — whoever owns the graph must hold on to it.
-    A victim and its wrapper reference each other, as do an attack's state and its graph runner, so captured graphs
-    die in the CYCLE collector, at whatever allocation happens to trigger it — if that is inside another capture, the
-    graph's destructor runs HIP calls that are illegal while a stream is capturing and the process aborts (seen once
-    in a long test session: "Fatal Python error: Aborted ... Garbage-collecting" under torch.cuda.current_stream)."""
+    A victim and its wrapper reference each other (as do a victim and the GeoA3 loops kept on it), so their captured
+    graphs die in the CYCLE collector, at whatever allocation happens to trigger it — if that is inside another capture,
+    the graph's destructor runs HIP calls that are illegal while a stream is capturing and the process aborts."""
     was = gc.isenabled()
     gc.collect()
     gc.disable()
@@ -110,6 +109,78 @@ def weights_key(module):
 def unwrap(model):
     """The victim behind a GraphedVictim, any other model as it is (whatever attributes it has)."""
     return model.model if isinstance(model, GraphedVictim) else model
+
+
+def logits_of(out):
+    """The logits of a victim's output: the first element of a tuple, anything else as it is."""
+    return out[0] if isinstance(out, tuple) else out
+
+
+def loop_key(victim, device, *consts):
+    """What an attack's captured loop is keyed on: its own constants (shape, step sizes, plan), the device, the backward
+    kernel flavour (ordered sums / float atomics: baked into a capture) and the victim's weights_key."""
+    from . import ops as _ops
+    return (*consts, str(device), bool(_ops._det()), weights_key(victim))
+
+
+class DeviceLoop:
+    """One key's state of an attack's device-side loop: `key`, `bufs` (name -> tensor / None / Python constant: the
+    static buffers the body updates in place, kept nowhere else) and `graphs` (a LoopGraph once captured, else None).
+    The body is the callable given here or the method a subclass overrides. device / owners / counts / warmup are
+    LoopGraph's. A loop must not reference whatever holds the cache it is kept in (bodies take what they need from
+    that object as locals): loop and graphs then die with the cache's owner, by reference count."""
+
+    def __init__(self, key, device, owners=(), counts=(1,), warmup=2, body=None, bufs=None):
+        self.key, self.bufs, self.graphs = key, {} if bufs is None else bufs, None
+        self._capture_args = (device, warmup, counts, owners)
+        if body is not None:
+            self.body = body
+
+    def body(self):
+        raise NotImplementedError
+
+    def __getattr__(self, name):
+        """A buffer by its name (`loop.x` reads `loop.bufs["x"]`)."""
+        try:
+            return self.__dict__["bufs"][name]
+        except KeyError:
+            raise AttributeError(name) from None
+
+    def capture(self, rewind=None):
+        """Capture once (after the warm-up passes, which are real passes: `rewind()` then puts the state back).
+        Returns whether it captured."""
+        if self.graphs is not None:
+            return False
+        self.graphs = LoopGraph(self.body, *self._capture_args)
+        if rewind is not None:
+            rewind()
+        return True
+
+    def run(self, n):
+        """n passes: replayed when captured, eager launches otherwise."""
+        if self.graphs is not None:
+            self.graphs.run(n)
+        else:
+            for _ in range(n):
+                self.body()
+
+
+class LoopCache(dict):
+    """DeviceLoops by key, a dict that holds at most `max_entries`: an insertion beyond that drops the oldest INSERTED
+    entry first (a hit does not refresh its age)."""
+
+    def __init__(self, max_entries=4):
+        super().__init__()
+        self.max_entries = max_entries
+
+    def __setitem__(self, key, loop):
+        while len(self) >= self.max_entries:
+            self.pop(next(iter(self)))
+        super().__setitem__(key, loop)
+
+    def put(self, key, loop):
+        self[key] = loop
+        return loop
 
 
 MAX_CAPTURES = 4     # distinct (shape, mode, weights) keys per wrapper; the oldest is dropped beyond this

@@ -63,7 +63,7 @@ def _same(a, b):
 
 
 def _tables(atk):
-    c = atk._loop_cache
+    c = next(iter(atk._loop_cache.values())).bufs
     return [None if c[nm] is None else c[nm].cpu().numpy().copy() for nm in ("rot", "idx", "inv")]
 
 
@@ -82,7 +82,7 @@ def test_device_drawn_loop(dev, shape, resample):
     first, gen_first, (py0, py1) = _attack(dev, shape, atk)
     assert atk.last_path == "device_loop" and atk.last_draws == "device" and atk.draw_seconds == 0.0
     assert py0 == py1                                                     # nothing consumed from Python's random
-    c = atk._loop_cache
+    c = next(iter(atk._loop_cache.values())).bufs
     assert c["rot_pin"] is None and c["idx_pin"] is None and c["inv_pin"] is None
     assert (c["idx"] is not None) == resample and (c["inv"] is not None) == resample
     bd, ba, sn = first
@@ -138,7 +138,7 @@ def test_device_drawn_loop(dev, shape, resample):
     host._draw_block = same_tables
     fed, _, _ = _attack(dev, shape, host)
     assert host.last_path == "device_loop" and host.last_draws == "host" and drawn[0] == STEPS * ITERS and host.draw_base == 0
-    assert (host._loop_cache["idx_pin"] is not None) == resample
+    assert (next(iter(host._loop_cache.values())).bufs["idx_pin"] is not None) == resample
     assert _same(first, fed)
 
 
@@ -156,16 +156,16 @@ def test_seeds(dev):
     for a, b in ((SEED, SEED + 1), (SEED, None)):
         assert not np.array_equal(runs[a][1][1], runs[b][1][1]) and not np.array_equal(runs[a][1][0], runs[b][1][0])
     for seed, used in ((SEED, SEED), (SEED + 1, SEED + 1), (None, 2000)):
-        c = runs[seed][0]._loop_cache
+        c = next(iter(runs[seed][0]._loop_cache.values())).bufs
         want = [torch.zeros_like(c[nm]) for nm in ("rot", "idx", "inv")]
         ops.eot_draw(used, 0, (0, 2), *want)
         assert _tables_equal(runs[seed][1], [w.cpu().numpy()[:2] for w in want])
     atk = runs[SEED][0]
-    state = atk._loop_cache
+    state = next(iter(atk._loop_cache.values()))
     atk.seed = SEED + 1
     atk.draw_base = 0
     _attack(dev, shape, atk)
-    assert atk._loop_cache is not state and _tables_equal([t[:2] for t in _tables(atk)], runs[SEED + 1][1])
+    assert next(iter(atk._loop_cache.values())) is not state and _tables_equal([t[:2] for t in _tables(atk)], runs[SEED + 1][1])
 
 
 def test_elsewhere_the_host_draws(dev):

@@ -147,11 +147,11 @@ def test_second_call_reuses_the_graphs(dev, case):
     pn1, pn2 = hip_pointnet(0, dev)[0], hip_pointnet(0, dev)[0]
     first = _attack(pn1, case["pcs"], case["labels"], device_loop=True)
     states = list(pn1._geoa3_loop_cache.values())
-    assert len(states) == 1 and states[0]["graphs"] is not None
-    graphs = states[0]["graphs"]
+    assert len(states) == 1 and states[0].graphs is not None
+    graphs = states[0].graphs
     other = _clouds(9, 3, 200)
     second = _attack(pn1, other, case["labels"], device_loop=True)
-    assert list(pn1._geoa3_loop_cache.values())[0]["graphs"] is graphs and second["path"] == "device_loop"
+    assert list(pn1._geoa3_loop_cache.values())[0].graphs is graphs and second["path"] == "device_loop"
     fresh = _attack(pn2, other, case["labels"], device_loop=True)
     assert _same(second, fresh) and not np.array_equal(second["losses"], first["losses"])
 

@@ -2,8 +2,11 @@
 launches return, and never lets a replay overwrite memory an earlier forward still needs."""
 import gc
 import importlib
+import os
 import types
+import weakref
 
+import numpy as np
 import pytest
 import torch
 
@@ -219,3 +222,66 @@ def test_loop_graph_inside_an_open_guard(dev):
     assert not graphed.capturing() and gc.isenabled() == was
     loop.replay()
     assert torch.equal(x, torch.full_like(x, 2.0))
+
+
+# -- DeviceLoop: one key's buffers, body and graphs. The body is x += 1 on one float. -------------------------------------
+def test_device_loop_replay_equals_eager(dev):
+    x = torch.zeros(1, device=dev)
+    loop = graphed.DeviceLoop("k", dev, counts=(1, 16), warmup=2, body=lambda: x.add_(1), bufs=dict(x=x))
+    assert loop.capture(rewind=lambda: x.zero_()) is True and float(x) == 0.0
+    graphs = loop.graphs
+    assert sorted(graphs.graphs) == [1, 16]
+    x.fill_(5.0)
+    assert loop.capture(rewind=lambda: x.zero_()) is False and loop.graphs is graphs and float(x) == 5.0
+    y = torch.zeros(1, device=dev)
+    twin = graphed.DeviceLoop("k", dev, counts=(1, 16), warmup=2, body=lambda: y.add_(1), bufs=dict(x=y))
+    for n in (0, 1, 15, 16, 17, 33):
+        x.zero_(), y.zero_()
+        loop.run(n), twin.run(n)
+        assert float(x) == n and float(y) == n and twin.graphs is None
+
+
+def _knn_attack(dev):
+    t = importlib.import_module("test_knn_loop_gpu")
+    pcs = t._clouds(4, 3, 200)
+    atk, _, _ = t._attack(t.hip_pointnet(0, dev)[0], pcs, torch.zeros(3, dtype=torch.long), num_iter=2, device_loop=True)
+    assert atk.last_path == "device_loop"
+    return atk, atk._loop_cache
+
+
+def _eot_attack(dev):
+    t = importlib.import_module("test_eot_device_rng_gpu")
+    atk = t._make(dev, "B1_K64", True, binary_step=1, num_iter=2)
+    t._attack(dev, "B1_K64", atk)
+    assert atk.last_path == "device_loop"
+    return atk, atk._loop_cache
+
+
+def _iso_attack(dev):
+    t = importlib.import_module("test_iso_gpu")
+    fx = np.load(os.path.join(t.GOLDEN, "iso.npz"))
+    victim, _ = t.hip_pointnet(int(fx["weights_seed"]), dev)
+    atk = t._run(fx, "a_n64", victim, dev)[0]
+    return atk, atk._ctri_cache
+
+
+@pytest.mark.parametrize("make", [_knn_attack, _eot_attack, _iso_attack], ids=["cwknn", "eot_cw", "iso"])
+def test_an_attacks_loop_dies_with_the_attack_without_the_cycle_collector(dev, make):
+    """No reference cycle runs through a captured loop: dropping the attack frees it (and its graphs) by reference count,
+    at once, not at whatever allocation wakes the cycle collector — which may be inside another capture."""
+    atk, cache = make(dev)
+    assert len(cache) == 1
+    ref = weakref.ref(next(iter(cache.values())))
+    assert ref().graphs is not None
+    del cache
+    torch.cuda.synchronize()
+    was = gc.isenabled()
+    gc.collect()
+    gc.disable()
+    try:
+        assert ref() is not None
+        del atk
+        assert ref() is None
+    finally:
+        if was:
+            gc.enable()

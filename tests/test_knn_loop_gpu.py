@@ -125,7 +125,7 @@ def test_zero_iterations_capture_nothing_and_return_the_start(dev, pn, case):
     """num_iter = 0 (what tools/bench_knn_attack.py times as the attack's fixed cost): no graph is captured, none is run."""
     a, g, gs = _attack(pn, case["pcs"], case["labels"], num_iter=0, device_loop=True)
     _, e, es = _attack(pn, case["pcs"], case["labels"], num_iter=0, device_loop=True, graph=False)
-    assert a.last_path == "device_loop" and a._loop_cache["graphs"] is None
+    assert a.last_path == "device_loop" and next(iter(a._loop_cache.values())).graphs is None
     assert np.array_equal(g, e) and gs == es
 
 
@@ -141,12 +141,12 @@ def test_batch_of_three_equals_three_alone(dev, pn, case):
 
 def test_second_attack_reuses_the_graph(dev, pn, case):
     atk, first, _ = _attack(pn, case["pcs"], case["labels"], num_iter=20, device_loop=True)
-    graphs = atk._loop_cache["graphs"]
+    graphs = next(iter(atk._loop_cache.values())).graphs
     assert graphs is not None
     other = _clouds(9, 3, 200)
     torch.manual_seed(8)
     second, _ = atk.attack(torch.from_numpy(other), case["labels"])
-    assert atk._loop_cache["graphs"] is graphs and atk.last_path == "device_loop"
+    assert next(iter(atk._loop_cache.values())).graphs is graphs and atk.last_path == "device_loop"
     _, fresh, _ = _attack(pn, other, case["labels"], num_iter=20, device_loop=True)
     assert np.array_equal(second, fresh)
     assert not np.array_equal(second, first)

@@ -339,7 +339,7 @@ def test_graph_replay_equals_eager_and_run_equals_run(fx, nets, dev):
     points, target = torch.from_numpy(fx["points"]).to(dev), torch.from_numpy(fx["target"]).to(dev)
     graphed, eager = make_attack(fx, "s5", nets, max_steps=50), make_attack(fx, "s5", nets, max_steps=50, graph=False)
     a = graphed.iterate(points, target)
-    assert len(graphed._loops) == 1 and next(iter(graphed._loops.values())).graph is not None
+    assert len(graphed._loops) == 1 and next(iter(graphed._loops.values())).graphs is not None
     b = graphed.iterate(points, target)                                  # the captured graph again, reloaded
     c = eager.iterate(points, target)
     assert torch.isfinite(a).all()

@@ -364,7 +364,7 @@ def test_loop_reproduces_the_fixture(fx, replayed, case):
     assert dl <= band_loss
     if case == "simba":
         assert torch.equal(adv.cpu(), torch.from_numpy(fx["simba_adv_points"]))          # the same fp32 additions
-        assert atk.graph and len(atk._query_loops) == 1 and next(iter(atk._query_loops.values())).graph is not None
+        assert atk.graph and len(atk._query_loops) == 1 and next(iter(atk._query_loops.values())).graphs is not None
     else:
         assert dP <= band_P
 

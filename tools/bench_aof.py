@@ -135,10 +135,10 @@ def main():
     lab = label.to(dev)
     fk = atk._fused_kind()
     torch.manual_seed(0)
-    fl = atk._fused_loop(B, N, fk)
-    fl["load"](ori, lab)
-    fl["new_step"]()
-    st = fl["st"]
+    loop = atk._fused_loop(B, N, fk)
+    fl = st = loop.bufs
+    atk._load(fl, ori, lab)
+    atk._new_step(fl)
     buf, label2 = fl["buf"], fl["label2"]
 
     def stacked():
@@ -152,12 +152,12 @@ def main():
         ga = victim.fused_loss_and_grad(buf[:B], lab, *fk, scale=0.5 / B)[3]
         gb = victim.fused_loss_and_grad(buf[B:], lab, *fk, scale=0.5 / B)[3]
         out["stacked_equals_two_passes"] = bool(torch.equal(g2[:B], ga) and torch.equal(g2[B:], gb))
-        names = count_launches(fl["iterate"])
+        names = count_launches(loop.body)
         out["launches"] = {"fused_iteration": len(names), "victim_stacked_pass": len(count_launches(stacked)),
                            "beside_the_victim": [n for n in names if "aof" in n or "spectral" in n]}
-        fl["begin_step"]()
-        out["fused_iter_us"] = med(lambda: graph_us(fl["iterate"]))
-        fl["begin_step"]()
+        ea._begin_step(fl)
+        out["fused_iter_us"] = med(lambda: graph_us(loop.body))
+        ea._begin_step(fl)
         out["victim_stacked_us"] = med(lambda: graph_us(stacked))
         out["victim_two_passes_us"] = med(lambda: graph_us(two_passes))
         out["own_cost_us"] = out["fused_iter_us"]["median"] - out["victim_stacked_us"]["median"]

@@ -149,7 +149,8 @@ def one_config(victim, B, K, iters, resample, reps):
     out["loop_rng_draw_seconds"] = max(rng_draw_seconds)
 
     atk = atks[("loop", iters)]
-    c = atk._loop_cache
+    loop = next(iter(atk._loop_cache.values()))
+    c = loop.bufs
     plan = c["plan"]
     kind, kappa = plan["kind"]
     cur = torch.cuda.current_stream(dev)
@@ -157,14 +158,14 @@ def one_config(victim, B, K, iters, resample, reps):
     def victim_pass():
         plan["victim"].fused_attack_grad(c["X"], c["goal_s"], kind, kappa, pred_out=c["pred"], step=c["step"], scale=plan["scale"])
     with torch.no_grad():
-        names = count_launches(c["body"])
+        names = count_launches(loop.body)
         out["launches"] = {"loop_iteration": len(names), "victim_passes": len(count_launches(victim_pass)),
                            "beside_the_victim": [n for n in names if n.startswith("pc3d_eot") or n == "pc3d_nn_f32"]}
-        out["loop_gpu_us"] = med(lambda: replay_us(lambda: c["graphs"].replay(16), 16, 10, cur))
+        out["loop_gpu_us"] = med(lambda: replay_us(lambda: loop.graphs.replay(16), 16, 10, cur))
 
         def block_with_draws():                              # what device_rng=True enqueues per block of 16 iterations
             ops.eot_draw(DRAW_SEED, 0, (0, 16), c["rot"], c["idx"], c["inv"])
-            c["graphs"].replay(16)
+            loop.graphs.replay(16)
         out["loop_rng_gpu_us"] = med(lambda: replay_us(block_with_draws, 16, 10, cur))
         out["victim_stacked_us"] = med(lambda: graph_us(victim_pass))
         gx = torch.randn_like(c["X"]) * 1e-3

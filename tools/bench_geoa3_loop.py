@@ -134,7 +134,8 @@ def one_size(victim, B, N, iters, whole):
         return f
     out = {}
     run(16, True)()
-    s = next(st for st in victim._geoa3_loop_cache.values() if st["key"][1] == N and st["graphs"] is not None)
+    loop = next(lp for lp in victim._geoa3_loop_cache.values() if lp.key[1] == N and lp.graphs is not None)
+    s = loop.bufs
     tgt = s["target"]
 
     def victim_pass():
@@ -142,10 +143,10 @@ def one_size(victim, B, N, iters, whole):
         _, _, _, g = ops.cls_loss(logits, tgt, 3, 0.0, scale=1.0 / B, pred_out=s["pred"])
         return pointnet.fused_input_grad(ctx, g)
     with torch.no_grad():
-        names = count_launches(s["body"])
+        names = count_launches(loop.body)
         out["launches"] = {"loop_iteration": len(names), "beside_the_victim": names[-4:]}
         cur = torch.cuda.current_stream(dev)
-        out["loop_iter_us"] = med(lambda: replay_us(lambda: s["graphs"].replay(16), 16, 20, cur))
+        out["loop_iter_us"] = med(lambda: replay_us(lambda: loop.graphs.replay(16), 16, 20, cur))
         out["victim_us"] = med(lambda: graph_us(victim_pass))
     # The replays above carried the attack thousands of iterations on. The stand-alone kernels are timed on the state a
     # 2 x 16 attack ends in, with lr = 0 so that the update kernel leaves the iterate where it is (its cost depends on the

@@ -125,18 +125,19 @@ def one_size(victim, B, N, iters, whole, parts):
     atk = make(16, device_loop=True)
     run(atk)()
     assert atk.last_path == "device_loop"
-    c = atk._loop_cache
+    loop = next(iter(atk._loop_cache.values()))
+    c = loop.bufs
     plan = c["plan"]
     kind, kappa = plan["kind"]
 
     def victim_pass():
         plan["victim"].fused_attack_grad(c["adv"], c["target"], kind, kappa, pred_out=c["pred"], step=c["step"], scale=plan["scale"])
     with torch.no_grad():
-        names = count_launches(c["body"])
+        names = count_launches(loop.body)
         out["launches"] = {"loop_iteration": len(names), "victim_passes": len(count_launches(victim_pass)),
                            "beside_the_victim": names[-3:]}
         cur = torch.cuda.current_stream(dev)
-        out["loop_iter_us"] = med(lambda: replay_us(lambda: c["graphs"].replay(16), 16, 20, cur))
+        out["loop_iter_us"] = med(lambda: replay_us(lambda: loop.graphs.replay(16), 16, 20, cur))
         out["victim_us"] = med(lambda: graph_us(victim_pass))
         out["own_cost_us"] = out["loop_iter_us"]["median"] - out["victim_us"]["median"]
         if parts:

@@ -89,7 +89,7 @@ def main():
     eps = torch.tensor(si.sign_order(STEP), dtype=torch.float32)
     loops = {}
     for name, atk, tab, fr in (("coordinate", simba, tab_simba, None), ("frame", ours, order, (nrm, dirs))):
-        c = si._QueryLoop(atk, B, N, tab.shape[1], 40, dev, fr is not None, False, True)
+        c = si._QueryLoop(atk.classifier, atk.pre_head, atk.top5_attack, B, N, tab.shape[1], 40, dev, fr is not None, False, True)
         c.load(x, label, tab, eps.to(dev), torch.ones(B, dtype=torch.bool, device=dev), label.to(torch.int32), logp0,
                *(fr if fr else ()))
         loops[name] = c
@@ -100,10 +100,10 @@ def main():
         return real(name, *args_)
 
     def forward():
-        return torch.log_softmax(pointnet.fused_forward(tgt, loops["coordinate"].s["cand"])[0], dim=1)
+        return torch.log_softmax(pointnet.fused_forward(tgt, loops["coordinate"].bufs["cand"])[0], dim=1)
 
     def hold(c):                       # a step that decides nothing new: the clouds stay live, the timing is a live step's
-        c.s["pos"].zero_(), c.s["done"].zero_(), c.s["best"].fill_(-999.)
+        c.bufs["pos"].zero_(), c.bufs["done"].zero_(), c.bufs["best"].fill_(-999.)
         c.step()
     _lib.call = counted
     try:
@@ -119,7 +119,7 @@ def main():
     out["step_own_cost_us"] = {k: v["median"] - out["forward_us"]["median"] for k, v in out["step_us"].items()}
     lp = torch.cat([logp0, logp0]).contiguous()
     g = torch.randn(B, 3, N, device=dev)
-    out["kernels_us"] = {f"query_step_{k}": med(lambda c=c: graph_us(lambda: ops.query_step(c.s, lp))) for k, c in loops.items()}
+    out["kernels_us"] = {f"query_step_{k}": med(lambda c=c: graph_us(lambda: ops.query_step(c.bufs, lp))) for k, c in loops.items()}
     out["kernels_us"]["si_rank"] = med(lambda: graph_us(lambda: ops.si_rank(g, nrm)))
 
     plain_s, plain_t = oracle_pointnet(3)[0].to(dev).eval(), oracle_pointnet(4)[0].to(dev).eval()
