@@ -139,6 +139,9 @@ SIGNATURES = {
     "pc3d_cls_tail_serial_f32": [_P, _I, _I, _P, _P, _I, _P, _I, _F, _F, _P, _P, _P, _P, _P, _P],
     "pc3d_cw_update_f32": _PTS + _PTS + [_I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P] + _PTS + [_P, _P]
     + [_D, _D, _D, _D, _F, _P, _I, _I, _P, _P, _P],
+    "pc3d_cw_update_ragged_f32": _PTS + _PTS + [_I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P] + _PTS + [_P, _P]
+    + [_D, _D, _D, _D, _F, _P, _I, _I, _P, _P, _P],
+    "pc3d_pad_ragged_f32": _PTS + [_P, _I, _I, _P],
     "pc3d_knn_attack_update_f32": _PTS + _PTS + _PTS + _PTS + [_P, _P] + [_I, _I, _I, _P, _P, _P] + [_D, _D, _D, _D]
     + [_F, _I, _F, _F, _F, _P, _I, _P],
     "pc3d_eot_prepare_f32": [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P],

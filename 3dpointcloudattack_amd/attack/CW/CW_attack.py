@@ -33,6 +33,18 @@ def rand_row(array):
     return array[:, row_sequence, :]
 
 
+def rand_row_ragged(array, lengths):
+    """rand_row for clouds of different sizes, [B,Kmax,3] in place: cloud b's first lengths[b] rows are permuted — one
+    permutation per cloud from numpy's global stream, in batch order, the draw rand_row makes for that cloud alone — and
+    its further rows take the new row 0 again."""
+    for b, n in enumerate(lengths):
+        row_sequence = np.arange(int(n))
+        np.random.shuffle(row_sequence)
+        array[b, :int(n)] = array[b, row_sequence]
+        array[b, int(n):] = array[b, 0]
+    return array
+
+
 def bisect_weights(lower, upper, current, ok):
     """The reference's weight adjustment (:182-200), sample by sample in float64, in place: an attack that succeeded
     (ok[e]) raises the lower bound to the weight it ran with, any other lowers the upper bound; the next weight is the
@@ -72,6 +84,7 @@ class _GraphRunner:
 
 class CW:
     """Class for CW attack."""
+    ragged = True       # attack(data, target, lengths) exists; the point-adding subclasses switch it off
 
     def __init__(self, model, trans_model, adv_func, clip_func, dist_func, attack_lr=1e-2,
                  init_weight=10., max_weight=80., binary_step=10, num_iter=500, attack_method="untarget",
@@ -177,13 +190,52 @@ class CW:
         return 0
 
     # -- the hot loop, split so that bench.py / graph capture can drive single iterations ---------------
-    def _begin(self, data, target):
-        """Upload + clean prediction (reference :63-89). Returns the state dict the iteration works on."""
+    def _ragged_lengths(self, data, lengths):
+        """lengths as int64 numpy [B] after every check of the ragged path, or ValueError naming what does not fit: there is
+        no silent fall-back, since a pass that does not know the lengths would average over the padding."""
+        if not self.ragged:
+            raise ValueError(f"CW.attack(lengths=...): {type(self).__name__} has no ragged pass")
+        victim = _graphed.unwrap(self.model)
+        if not getattr(victim, "pad_invariant", False) or not hasattr(victim, "fused_attack_grad"):
+            raise ValueError(f"CW.attack(lengths=...): the victim {type(victim).__name__} does not declare pad_invariant or "
+                             "lacks the fused entry points (fused_attack_grad)")
+        if not self.fused:
+            raise ValueError("CW.attack(lengths=...): fused=False has no ragged pass")
+        if self._own_adv_kind() is None:
+            raise ValueError(f"CW.attack(lengths=...): adv_func {type(self.adv_func).__name__} is not one of this package's "
+                             "adversarial functors")
+        if self._fused_dist_kind() == 0:
+            raise ValueError(f"CW.attack(lengths=...): dist_func {type(self.dist_func).__name__} is neither L2Dist nor "
+                             "ChamferDist('adv2ori')")
+        if self._fused_clip_budget() is None:
+            raise ValueError(f"CW.attack(lengths=...): clip_func {type(self.clip_func).__name__} is not ClipPointsLinf")
+        if data.dim() != 3 or data.shape[2] != 3:
+            raise ValueError(f"CW.attack(lengths=...): data must be [B, Kmax, 3], got {tuple(data.shape)}")
+        B, K = data.shape[:2]
+        if K > ops.CW_UPDATE_MAX_POINTS:
+            raise ValueError(f"CW.attack(lengths=...): Kmax={K} exceeds CW_UPDATE_MAX_POINTS={ops.CW_UPDATE_MAX_POINTS}")
+        if torch.is_tensor(lengths):
+            lengths = lengths.detach().cpu().numpy()
+        lens = np.asarray(lengths)
+        if lens.shape != (B,) or not np.issubdtype(lens.dtype, np.integer):
+            raise ValueError(f"CW.attack(lengths=...): lengths must be {B} ints, got shape {lens.shape} dtype {lens.dtype}")
+        if lens.min() < 1 or lens.max() > K:
+            raise ValueError(f"CW.attack(lengths=...): lengths must lie in [1, Kmax={K}], got [{lens.min()}, {lens.max()}]")
+        return lens.astype(np.int64)
+
+    def _begin(self, data, target, lengths=None):
+        """Upload + clean prediction (reference :63-89). Returns the state dict the iteration works on. lengths (checked by
+        _ragged_lengths): the clouds' sizes; they live in an int32 device buffer of the state, which the kernels read as
+        data, and ori is padded with copies of every cloud's point 0."""
         dev = self.device
         B, K = data.shape[:2]
         data = data.float().to(dev).detach()
         data = data.transpose(1, 2).contiguous()
         ori_data = data.clone().detach()
+        lens_dev = None
+        if lengths is not None:
+            lens_dev = torch.from_numpy(np.asarray(lengths, dtype=np.int32)).to(dev)
+            ops.pad_ragged(ori_data, lens_dev)
         target = target.long().to(dev).detach().view(-1)
         label = target
         with torch.no_grad():
@@ -200,6 +252,8 @@ class CW:
             gens = [torch.Generator().manual_seed(int(sd)) for sd in self.sample_seeds]
         return dict(
             B=B, K=K, ori=ori_data, target=target, label=label, budget=self._fused_clip_budget(), gens=gens,
+            # ragged batch: the sizes on the host (start noise, final checks) and on the device (the update launch)
+            lengths_host=None if lengths is None else [int(n) for n in lengths], lengths=lens_dev,
             # losses are batch means (:160-165): a shard of a larger batch scales its terms by B/global_batch
             ratio=(float(B) / float(self.global_batch)) if self.global_batch else 1.0,
             # weight factor for budget regularization (host, consulted once per binary step)
@@ -220,10 +274,19 @@ class CW:
         dev, B, K = self.device, st["B"], st["K"]
         # same RNG stream as the reference: CPU generator, then upload (:94)
         if st["gens"] is None:
+            # (ragged: the batch-shaped draw stays, its padding columns are overwritten below; a cloud's noise then depends
+            # on the batch it is in, so this mode is not comparable cloud by cloud with runs alone)
             noise = torch.randn((B, 3, K))
-        else:
+        elif st.get("lengths") is None:
             noise = torch.stack([torch.randn((3, K), generator=g) for g in st["gens"]])
+        else:
+            # what a run of that cloud alone draws: (3, lengths[b]) from the sample's own generator
+            noise = torch.zeros((B, 3, K))
+            for b, (g, n) in enumerate(zip(st["gens"], st["lengths_host"])):
+                noise[b, :, :n] = torch.randn((3, n), generator=g)
         adv_data = st["ori"].clone().detach() + noise.to(dev) * 1e-7
+        if st.get("lengths") is not None:
+            ops.pad_ragged(adv_data, st["lengths"])
         adv_data.requires_grad_()
         if "adv" not in st:
             # first binary step: allocate the per-step state once; later steps refill it IN PLACE so a captured
@@ -257,6 +320,10 @@ class CW:
         in st["step"] on the device, so the body is identical every pass (hipGraph-replayable). Picks the pass."""
         fml = self._fused_model_loss() if st["budget"] is not None else None
         dk = self._fused_dist_kind() if fml is not None else 0
+        if st.get("lengths") is not None:
+            # ragged batch (attack() has checked everything): the 17-launch pass, its update launch given the lengths; the
+            # riders do not apply, their epilogue does not know lengths
+            return self._pass_fused_update(st, fml, dk)
         if dk:
             # launch-minimal passes: victim fwd/bwd (fused heads), bookkeeping, [NN search], one update launch
             if (self.riders and "adam" in st and hasattr(self.model, "fused_attack_update")
@@ -295,7 +362,7 @@ class CW:
                           st["bestscore"], st["o_bestdist"], st["o_bestscore"], st["o_bestattack"], gx_model,
                           st["exp_avg"], st["exp_avg_sq"], st["step"], self.attack_lr, st["budget"],
                           input_val=st["input_val"], dist_val=st["dist_val"], dist_kind=dk, w=st["weights"],
-                          nn_idx=nn_idx)
+                          nn_idx=nn_idx, lengths=st.get("lengths"))
 
     def _pass_fused_steps(self, st, fml, dk):
         """A victim with fused_loss_and_grad only (or a cloud too large for the update launch): bookkeeping, [the
@@ -469,11 +536,20 @@ class CW:
         hit = (bs != lab) if self.attack_method == 'untarget' else (bs == lab)
         bisect_weights(st["lower_bound"], st["upper_bound"], st["current_weight"], hit & (bs != -1) & (bd <= obd))
 
-    def attack(self, data, target):
+    def attack(self, data, target, lengths=None):
+        """lengths (default None: every cloud has data.shape[1] points, nothing changes): a sequence, array or tensor of B
+        ints, 1 <= lengths[b] <= Kmax = data.shape[1], the sizes of a batch of clouds of different sizes. Rows of data at and
+        beyond a cloud's length are ignored (dataset.cloud_io.stack_ragged builds such a batch). Every cloud is attacked as
+        it is — with `sample_seeds` and `global_batch` = B exactly as in a run of that cloud alone — in one batch, on a
+        pad_invariant victim (PointNetCls) with own functors (L2Dist or ChamferDist('adv2ori'), ClipPointsLinf); anything
+        else raises ValueError before any launch. Without `sample_seeds` the start noise is one batch-shaped draw whose
+        padding columns are ignored, which is NOT comparable cloud by cloud with runs alone. In the returned
+        o_bestattack [B,Kmax,3], rows at and beyond a cloud's length hold that cloud's row 0."""
+        args = (data, target) if lengths is None else (data, target, self._ragged_lengths(data, lengths))
         if self.deterministic is None:
-            return self._attack(data, target)
+            return self._attack(*args)
         with ops.deterministic(self.deterministic):
-            return self._attack(data, target)
+            return self._attack(*args)
 
     def _search(self, st):
         """The binary search (reference :93-200): every step restarts from a fresh start point, runs num_iter iterations
@@ -516,7 +592,15 @@ class CW:
         fail_idx = torch.from_numpy(st["lower_bound"] == 0.).to(self.device)
         return success_num, torch.where(fail_idx[:, None, None], st["input_val"], st["o_bestattack"])
 
-    def _attack(self, data, target):
+    def _trans_pred(self, model, o_bestattack, lens):
+        """The transfer model's prediction (:244-257). Ragged: on the padded batch when the model declares pad_invariant,
+        else cloud by cloud on its own [1,3,lengths[b]] slice (B forwards, once per attack)."""
+        if lens is None or getattr(_graphed.unwrap(model), "pad_invariant", False):
+            return torch.argmax(_graphed.logits_of(model(o_bestattack)), dim=1)
+        return torch.cat([torch.argmax(_graphed.logits_of(model(o_bestattack[b:b + 1, :, :n].contiguous())), dim=1)
+                          for b, n in enumerate(lens)])
+
+    def _attack(self, data, target, lengths=None):
         """Attack on given data to target.
         Args:
             data (torch.FloatTensor): victim data, [B, num_points, 3]
@@ -524,8 +608,8 @@ class CW:
         Returns (o_bestdist [B] float64, o_bestattack [B,K,3] float64, success_num) like the reference (:260).
         """
         dev = self.device
-        st = self._begin(data, target)
-        target = st["target"]
+        st = self._begin(data, target, lengths)
+        target, lens = st["target"], st["lengths_host"]
         self._search(st)
         success_num, o_bestattack = self._outcome(st)
         o_bestdist = st["o_bestdist"]
@@ -536,12 +620,15 @@ class CW:
             self.attack_fail += int((~self._success(attack_pred, target)).sum().item())
             # Test shuffle attack (:226-241) — numpy global RNG like the reference
             best_np = o_bestattack.double().cpu().numpy()  # [B,3,K]
-            shuffled = rand_row(best_np.transpose((0, 2, 1)))
+            if lens is None:
+                shuffled = rand_row(best_np.transpose((0, 2, 1)))
+            else:
+                shuffled = rand_row_ragged(best_np.transpose((0, 2, 1)).copy(), lens)
             shuffled = torch.from_numpy(shuffled.transpose((0, 2, 1)).copy()).float().to(dev)
             shuffle_pred = torch.argmax(_graphed.logits_of(self.model(shuffled)), dim=1)
             self.shuffle_fail += int((~self._success(shuffle_pred, target)).sum().item())
             # Test transfer attack (:244-257)
-            trans_pred = torch.argmax(_graphed.logits_of(self.trans_model(o_bestattack)), dim=1)
+            trans_pred = self._trans_pred(self.trans_model, o_bestattack, lens)
             self.trans_fail += int((~self._success(trans_pred, target)).sum().item())
         if self.verbose:
             print('attack result: ', attack_pred.tolist(), 'shuffle result: ', shuffle_pred.tolist(),

@@ -54,6 +54,7 @@ def get_critical_points(model, pc, label, num):
 
 class CWAdd(_CW):
     """Class for CW attack."""
+    ragged = False      # the added points' loop knows no per-cloud lengths: attack(..., lengths) raises ValueError
 
     def __init__(self, model, trans_model, adv_func, dist_func, attack_lr=1e-2, init_weight=5e3, max_weight=4e4,
                  binary_step=10, num_iter=500, num_add=512, attack_method='untarget', device=None, verbose=False,

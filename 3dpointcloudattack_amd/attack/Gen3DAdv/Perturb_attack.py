@@ -8,7 +8,7 @@ classified as in the reference (numpy's global RNG advances) but, as there, no c
 import torch
 
 from ..CW.CW_attack import CW as _CW
-from ..CW.CW_attack import rand_row
+from ..CW.CW_attack import rand_row, rand_row_ragged
 from ..KNN.KNN_attack import TRANSFER_MODELS, count_transfer_fails
 
 
@@ -31,15 +31,26 @@ class CW(_CW):
             setattr(self, attr, m)
             setattr(self, counter, 0)
 
-    def _attack(self, data, target):
-        """Returns (o_bestdist [B] float64, o_bestattack [B,K,3] float64, success_num) like the reference."""
-        st = self._begin(data, target)
-        target = st["target"]
+    def _attack(self, data, target, lengths=None):
+        """Returns (o_bestdist [B] float64, o_bestattack [B,K,3] float64, success_num) like the reference. lengths: the
+        CW mirror's ragged batch; a transfer model that does not declare pad_invariant then sees every cloud alone, on
+        its own [1,3,lengths[b]] slice."""
+        st = self._begin(data, target, lengths)
+        target, lens = st["target"], st["lengths_host"]
         self._search(st)
         success_num, o_bestattack = self._outcome(st)
         with torch.no_grad():
-            count_transfer_fails(self, o_bestattack, target)
+            if lens is None:
+                count_transfer_fails(self, o_bestattack, target)
+            else:
+                for name, attr in TRANSFER_MODELS:
+                    if getattr(self, attr) is not None:
+                        p = self._trans_pred(getattr(self, attr), o_bestattack, lens)
+                        setattr(self, name, getattr(self, name) + int((~self._success(p, target)).sum().item()))
             best_np = o_bestattack.double().cpu().numpy()
-            shuffled = rand_row(best_np.transpose((0, 2, 1)))
+            if lens is None:
+                shuffled = rand_row(best_np.transpose((0, 2, 1)))
+            else:
+                shuffled = rand_row_ragged(best_np.transpose((0, 2, 1)).copy(), lens)
             self.model(torch.from_numpy(shuffled.transpose((0, 2, 1)).copy()).float().to(self.device))
         return st["o_bestdist"].double().cpu().numpy(), best_np.transpose((0, 2, 1)), success_num

@@ -111,10 +111,26 @@ struct UpdateArgs {
   BookArgs bk;
   StepArgs st;
 };
+struct RaggedUpdateArgs : UpdateArgs {
+  const int32_t* lengths;    // [B] points that count per sample
+};
+template <bool RAGGED> struct UpdateArgsOf { using type = UpdateArgs; };
+template <> struct UpdateArgsOf<true> { using type = RaggedUpdateArgs; };
+
+// LDS of the ragged instantiations alone: point 0 before [0..2] and after [3..5] the update
+__device__ __forceinline__ float* cw_pad_slot() {
+  __shared__ float s_pad[6];
+  return s_pad;
+}
 
 // PER points per thread, all operands fetched up front (one memory round trip), then reduce -> decide -> update.
-template <int PER>
-__global__ __launch_bounds__(1024) void cw_update_kernel(UpdateArgs u) {
+// RAGGED: sample b counts L = lengths[b] <= K points (clamped to [1, K]); the rows from L on are padding, copies of the
+// sample's point 0. Only what sums, averages or updates over points sees L: rows >= L are never loaded (they may hold
+// anything), add 0.f to the norm at their place in the dense reduction tree, keep their m / v, and take the NEW point 0
+// after the update; the Chamfer factor is 2 w_b / (B L). With L = K every output has the dense instantiation's bits.
+// The dense instantiation compiles to the kernel it was before RAGGED existed (the parameter is a type of its own).
+template <int PER, bool RAGGED>
+__global__ __launch_bounds__(1024) void cw_update_kernel(typename UpdateArgsOf<RAGGED>::type u) {
   __shared__ float part[16];
   __shared__ int s_copy;
   __shared__ float s_dist, s_step_size, s_bc2s;
@@ -122,13 +138,15 @@ __global__ __launch_bounds__(1024) void cw_update_kernel(UpdateArgs u) {
   const StepArgs& s = u.st;
   const int b = blockIdx.x;
   const int tid = threadIdx.x;
+  int L = a.K;
+  if constexpr (RAGGED) L = min(max(u.lengths[b], 1), a.K);
   float px[PER], py[PER], pz[PER], ox[PER], oy[PER], oz[PER], gx[PER], gy[PER], gz[PER];
   float m_[PER][3], v_[PER][3], qx[PER], qy[PER], qz[PER];
   int nj[PER];
 #pragma unroll
   for (int i = 0; i < PER; ++i) {
     const int k = tid + i * 1024;
-    nj[i] = (s.dist_kind == 2 && k < a.K) ? s.nn_idx[(int64_t)b * s.K + k] : 0;
+    nj[i] = (s.dist_kind == 2 && k < L) ? s.nn_idx[(int64_t)b * s.K + k] : 0;
   }
   const int t = s.step_dev ? s.step_dev[0] : s.step_host;
   const int64_t pr = a.pred[b], lb = a.label[b];
@@ -138,7 +156,7 @@ __global__ __launch_bounds__(1024) void cw_update_kernel(UpdateArgs u) {
 #pragma unroll
   for (int i = 0; i < PER; ++i) {
     const int k = tid + i * 1024;
-    if (k < a.K) {
+    if (k < L) {
       const float* p = s.p.p + (int64_t)b * s.p.bs + (int64_t)k * s.p.ps;
       const float* o = s.ori.p + (int64_t)b * s.ori.bs + (int64_t)k * s.ori.ps;
       const float* gp = s.g.p + (int64_t)b * s.g.bs + (int64_t)k * s.g.ps;
@@ -189,7 +207,7 @@ __global__ __launch_bounds__(1024) void cw_update_kernel(UpdateArgs u) {
 #pragma unroll
   for (int i = 0; i < PER; ++i) {
     const int k = tid + i * 1024;
-    if (k >= a.K) continue;
+    if (k >= L) continue;
     if (a.input_val.p) {
       float* q = a.input_val.p + (int64_t)b * a.input_val.bs + (int64_t)k * a.input_val.ps;
       q[0] = px[i], q[a.input_val.cs] = py[i], q[2 * a.input_val.cs] = pz[i];
@@ -202,7 +220,7 @@ __global__ __launch_bounds__(1024) void cw_update_kernel(UpdateArgs u) {
     float* pp = s.p.p + (int64_t)b * s.p.bs + (int64_t)k * s.p.ps;
     float* mp = s.m.p + (int64_t)b * s.m.bs + (int64_t)k * s.m.ps;
     float* vp = s.v.p + (int64_t)b * s.v.bs + (int64_t)k * s.v.ps;
-    const CwPointConsts c{s.dist_kind, s.B, s.K, ad, s.budget};
+    const CwPointConsts c{s.dist_kind, s.B, RAGGED ? L : s.K, ad, s.budget};
     const float pin[3] = {px[i], py[i], pz[i]}, oin[3] = {ox[i], oy[i], oz[i]}, q[3] = {qx[i], qy[i], qz[i]};
     float np_[3];
     cw_point_update(c, pin, oin, g, q, wb, l2n, m_[i], v_[i], np_);
@@ -211,7 +229,47 @@ __global__ __launch_bounds__(1024) void cw_update_kernel(UpdateArgs u) {
     pp[0] = np_[0];
     pp[s.p.cs] = np_[1];
     pp[2 * s.p.cs] = np_[2];
+    if constexpr (RAGGED) {
+      // point 0 (thread 0, i = 0) before and after the update, for the padding rows
+      if (k == 0) {
+        float* s_pad = cw_pad_slot();
+#pragma unroll
+        for (int e = 0; e < 3; ++e) s_pad[e] = pin[e], s_pad[3 + e] = np_[e];
+      }
+    }
   }
+  if constexpr (RAGGED) {
+    // re-padding: the copies receive the iterate's point 0 as it was, the iterate's padding rows the new point 0, both
+    // through LDS behind the barrier (no thread re-reads global memory another thread of the workgroup writes)
+    __syncthreads();
+    const float* s_pad = cw_pad_slot();
+    const float o0[3] = {s_pad[0], s_pad[1], s_pad[2]}, n0[3] = {s_pad[3], s_pad[4], s_pad[5]};
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const int k = tid + i * 1024;
+      if (k < L || k >= a.K) continue;
+      if (a.input_val.p) {
+        float* q = a.input_val.p + (int64_t)b * a.input_val.bs + (int64_t)k * a.input_val.ps;
+        q[0] = o0[0], q[a.input_val.cs] = o0[1], q[2 * a.input_val.cs] = o0[2];
+      }
+      if (copy) {
+        float* q = a.o_bestattack.p + (int64_t)b * a.o_bestattack.bs + (int64_t)k * a.o_bestattack.ps;
+        q[0] = o0[0], q[a.o_bestattack.cs] = o0[1], q[2 * a.o_bestattack.cs] = o0[2];
+      }
+      float* pp = s.p.p + (int64_t)b * s.p.bs + (int64_t)k * s.p.ps;
+      pp[0] = n0[0], pp[s.p.cs] = n0[1], pp[2 * s.p.cs] = n0[2];
+    }
+  }
+}
+
+// x[b, :, k] = x[b, :, 0] for k >= lengths[b] (clamped to [1, K]): rows at and beyond the length are only written
+__global__ __launch_bounds__(256) void pad_ragged_kernel(PtsViewMut x, const int32_t* lengths, int K) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  const int b = blockIdx.y;
+  if (k >= K || k < min(max(lengths[b], 1), K)) return;
+  float* p0 = x.p + (int64_t)b * x.bs;
+  float* q = p0 + (int64_t)k * x.ps;
+  q[0] = p0[0], q[x.cs] = p0[x.cs], q[2 * x.cs] = p0[2 * x.cs];
 }
 
 }  // namespace pc3d
@@ -243,11 +301,58 @@ extern "C" int pc3d_cw_update_f32(float* adv, int64_t a_bs, int64_t a_ps, int64_
   u.st = StepArgs{{adv, a_bs, a_ps, a_cs}, {g, g_bs, g_ps, g_cs}, {m, a_bs, a_ps, a_cs}, {v, a_bs, a_ps, a_cs},
                   {ori, o_bs, o_ps, o_cs}, K, B, lr, beta1, beta2, (float)eps, budget, step_dev, step_host, dist_kind, w,
                   nullptr, nn_idx};
-  if (K <= 1024) hipLaunchKernelGGL(cw_update_kernel<1>, dim3(B), dim3(1024), 0, as_stream(stream), u);
-  else if (K <= 2048) hipLaunchKernelGGL(cw_update_kernel<2>, dim3(B), dim3(1024), 0, as_stream(stream), u);
-  else if (K <= 4096) hipLaunchKernelGGL(cw_update_kernel<4>, dim3(B), dim3(1024), 0, as_stream(stream), u);
-  else hipLaunchKernelGGL(cw_update_kernel<8>, dim3(B), dim3(1024), 0, as_stream(stream), u);
+  if (K <= 1024) hipLaunchKernelGGL((cw_update_kernel<1, false>), dim3(B), dim3(1024), 0, as_stream(stream), u);
+  else if (K <= 2048) hipLaunchKernelGGL((cw_update_kernel<2, false>), dim3(B), dim3(1024), 0, as_stream(stream), u);
+  else if (K <= 4096) hipLaunchKernelGGL((cw_update_kernel<4, false>), dim3(B), dim3(1024), 0, as_stream(stream), u);
+  else hipLaunchKernelGGL((cw_update_kernel<8, false>), dim3(B), dim3(1024), 0, as_stream(stream), u);
   PC3D_LAUNCH_CHECK("pc3d_cw_update_f32");
+  return PC3D_OK;
+}
+
+extern "C" int pc3d_cw_update_ragged_f32(float* adv, int64_t a_bs, int64_t a_ps, int64_t a_cs,
+                                         const float* ori, int64_t o_bs, int64_t o_ps, int64_t o_cs, int B, int K,
+                                         const int32_t* lengths, const int64_t* pred, const int64_t* label, int untarget,
+                                         float* bestdist, int64_t* bestscore, float* o_bestdist, int64_t* o_bestscore,
+                                         float* o_bestattack, float* input_val, float* dist_val,
+                                         const float* g, int64_t g_bs, int64_t g_ps, int64_t g_cs, float* m, float* v,
+                                         double lr, double beta1, double beta2, double eps, float budget,
+                                         const int32_t* step_dev, int step_host, int dist_kind, const float* w,
+                                         const int32_t* nn_idx, void* stream) {
+  PC3D_REQUIRE(B >= 0 && K >= 1 && K <= 8192, "pc3d_cw_update_ragged_f32: bad sizes B=%d K=%d (K <= 8192)", B, K);
+  PC3D_REQUIRE(step_dev != nullptr || step_host >= 1,
+               "pc3d_cw_update_ragged_f32: step_host must be >= 1 without a device counter");
+  PC3D_REQUIRE(dist_kind >= 0 && dist_kind <= 2, "pc3d_cw_update_ragged_f32: dist_kind=%d not in {0,1,2}", dist_kind);
+  if (B == 0) return PC3D_OK;
+  PC3D_REQUIRE(adv && ori && lengths && pred && label && bestdist && bestscore && o_bestdist && o_bestscore && o_bestattack &&
+                   g && m && v,
+               "pc3d_cw_update_ragged_f32: null pointer");
+  PC3D_REQUIRE(dist_kind == 0 || w != nullptr, "pc3d_cw_update_ragged_f32: distance term needs the weights w");
+  PC3D_REQUIRE(dist_kind != 2 || nn_idx != nullptr, "pc3d_cw_update_ragged_f32: Chamfer term needs nn_idx");
+  RaggedUpdateArgs u{};
+  u.bk = BookArgs{{adv, a_bs, a_ps, a_cs}, {ori, o_bs, o_ps, o_cs}, K, pred, label, untarget, bestdist, bestscore,
+                  o_bestdist, o_bestscore, {o_bestattack, a_bs, a_ps, a_cs}, {input_val, a_bs, a_ps, a_cs}, dist_val,
+                  nullptr};
+  u.st = StepArgs{{adv, a_bs, a_ps, a_cs}, {g, g_bs, g_ps, g_cs}, {m, a_bs, a_ps, a_cs}, {v, a_bs, a_ps, a_cs},
+                  {ori, o_bs, o_ps, o_cs}, K, B, lr, beta1, beta2, (float)eps, budget, step_dev, step_host, dist_kind, w,
+                  nullptr, nn_idx};
+  u.lengths = lengths;
+  // PER follows K, not the lengths: they are device data, and one captured launch serves every binary step
+  if (K <= 1024) hipLaunchKernelGGL((cw_update_kernel<1, true>), dim3(B), dim3(1024), 0, as_stream(stream), u);
+  else if (K <= 2048) hipLaunchKernelGGL((cw_update_kernel<2, true>), dim3(B), dim3(1024), 0, as_stream(stream), u);
+  else if (K <= 4096) hipLaunchKernelGGL((cw_update_kernel<4, true>), dim3(B), dim3(1024), 0, as_stream(stream), u);
+  else hipLaunchKernelGGL((cw_update_kernel<8, true>), dim3(B), dim3(1024), 0, as_stream(stream), u);
+  PC3D_LAUNCH_CHECK("pc3d_cw_update_ragged_f32");
+  return PC3D_OK;
+}
+
+extern "C" int pc3d_pad_ragged_f32(float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, const int32_t* lengths, int B, int K,
+                                   void* stream) {
+  PC3D_REQUIRE(B >= 0 && B <= 65535 && K >= 1, "pc3d_pad_ragged_f32: bad sizes B=%d K=%d", B, K);
+  if (B == 0) return PC3D_OK;
+  PC3D_REQUIRE(x && lengths, "pc3d_pad_ragged_f32: null pointer");
+  hipLaunchKernelGGL(pad_ragged_kernel, dim3(cdiv(K, 256), B), dim3(256), 0, as_stream(stream), PtsViewMut{x, x_bs, x_ps, x_cs},
+                     lengths, K);
+  PC3D_LAUNCH_CHECK("pc3d_pad_ragged_f32");
   return PC3D_OK;
 }
 

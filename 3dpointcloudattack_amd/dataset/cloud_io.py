@@ -47,6 +47,34 @@ def denormalize_cloud(xyz, center, dist):
     return np.asarray(xyz) * dist + center
 
 
+def stack_ragged(clouds):
+    """A list of [K_i, 3] clouds of different sizes -> (data [B, Kmax, 3] float32, lengths [B] int32), what
+    ``CW.attack(data, target, lengths)`` takes: cloud b fills rows 0 .. K_b - 1, its further rows are copies of its row 0
+    (the padding a pad_invariant victim does not see). ValueError for an empty list, a cloud without points or a last
+    dimension other than 3."""
+    clouds = [c.detach().cpu().numpy() if torch.is_tensor(c) else np.asarray(c) for c in clouds]
+    if not clouds:
+        raise ValueError("stack_ragged: empty list of clouds")
+    for i, c in enumerate(clouds):
+        if c.ndim != 2 or c.shape[1] != 3:
+            raise ValueError(f"stack_ragged: cloud {i} has shape {c.shape}, expected [K, 3]")
+        if c.shape[0] < 1:
+            raise ValueError(f"stack_ragged: cloud {i} has no points")
+    lengths = np.array([c.shape[0] for c in clouds], dtype=np.int32)
+    data = np.empty((len(clouds), int(lengths.max()), 3), dtype=np.float32)
+    for b, c in enumerate(clouds):
+        data[b, :c.shape[0]] = c
+        data[b, c.shape[0]:] = c[0]
+    return data, lengths
+
+
+def unstack_ragged(array, lengths):
+    """The inverse: [B, Kmax, 3] (numpy or tensor) and B lengths -> list of [lengths[b], 3] (views, padding rows dropped)."""
+    if len(array) != len(lengths):
+        raise ValueError(f"unstack_ragged: {len(array)} clouds, {len(lengths)} lengths")
+    return [array[b, :int(n)] for b, n in enumerate(lengths)]
+
+
 def adv_filename(idx, orig, target):
     """`idx-orig-target.txt` (the naming AdvData_dataset.read_PC parses, dataset/AdvData_dataset.py:27-31)."""
     return '{}-{}-{}.txt'.format(int(idx), int(orig), int(target))

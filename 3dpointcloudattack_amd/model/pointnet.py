@@ -209,6 +209,10 @@ class PointNetCls(_FrozenFusedMixin, nn.Module):
     """model/pointnet.py:130-148 — returns (log_softmax logits [B,k], trans [B,3,3], trans_feat): None, or with
     feature_transform=True the [B,64,64] feature transform, detached (see PointNetfeat)."""
     deterministic_forward = True   # forward is a pure function of its input (no RNG): attack loops may share it
+    # Copies of a cloud's point 0 appended behind the cloud change neither the logits nor the gradient of the other rows,
+    # and receive a gradient of exactly zero: every pooled value is a max over points whose ties go to the lowest index
+    # (csrc/pointmlp.hip). Both variants; CW.attack(data, target, lengths) asks for it. Nothing else declares it.
+    pad_invariant = True
 
     def __init__(self, k=2, feature_transform=False):
         super(PointNetCls, self).__init__()

@@ -1059,10 +1059,30 @@ def cls_tail(c2, w3, b3, target, kind, kappa=0.0, scale=1.0, pred_out=None, step
 CW_UPDATE_MAX_POINTS = 8192     # pc3d_cw_update_f32 keeps a sample's points in registers (8 per thread x 1024 threads)
 
 
+def _lengths_arg(who, lengths, B, device):
+    if (not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,)
+            or not lengths.is_contiguous() or lengths.device != device):
+        raise ValueError(f"{who}: lengths must be a contiguous int32 [B] tensor on the points' device")
+    return lengths.data_ptr()
+
+
+def pad_ragged(x, lengths, cf=True):
+    """x[b, :, k] = x[b, :, 0] for every k >= lengths[b], in place, one capturable launch (pc3d_pad_ragged_f32). x [B,3,K]
+    (cf) or [B,K,3]; lengths int32 [B] on x's device, read by the kernel as data (clamped to [1, K]). The rows at and beyond
+    the length are only written: they may hold anything, NaN included."""
+    xp, bs, ps, cs, B, K = _pts(x, cf, "x")
+    lp = _lengths_arg("pad_ragged", lengths, B, x.device)
+    with torch.cuda.device(x.device):
+        _lib.call("pc3d_pad_ragged_f32", xp, bs, ps, cs, lp, B, K, _stream())
+    return x
+
+
 def cw_update(adv, ori, pred, label, untarget, bestdist, bestscore, o_bestdist, o_bestscore, o_bestattack, g, m, v,
               step, lr, budget, input_val=None, dist_val=None, dist_kind=0, w=None, nn_idx=None,
-              betas=(0.9, 0.999), eps=1e-8, cf=True):
-    """cw_bookkeep + cw_step as one launch (see pc3d_cw_update_f32). `step` (int32 device word or int) is only READ."""
+              betas=(0.9, 0.999), eps=1e-8, cf=True, lengths=None):
+    """cw_bookkeep + cw_step as one launch (see pc3d_cw_update_f32). `step` (int32 device word or int) is only READ.
+    lengths (int32 [B] on the device, default None: the dense launch, unchanged): sample b counts lengths[b] points and its
+    further rows are padding, copies of its point 0 (pc3d_cw_update_ragged_f32)."""
     _, _, _, _, B, K = _pts(adv, cf, "adv")
     for nm, t in (("o_bestattack", o_bestattack), ("m", m), ("v", v), ("input_val", input_val)):
         if t is not None and (t.shape != adv.shape or t.stride() != adv.stride()):
@@ -1071,8 +1091,11 @@ def cw_update(adv, ori, pred, label, untarget, bestdist, bestscore, o_bestdist, 
         step_dev, step_host = step.data_ptr(), 0
     else:
         step_dev, step_host = 0, int(step)
+    name, extra = "pc3d_cw_update_f32", ()
+    if lengths is not None:
+        name, extra = "pc3d_cw_update_ragged_f32", (_lengths_arg("cw_update", lengths, B, adv.device),)
     with torch.cuda.device(adv.device):
-        _lib.call("pc3d_cw_update_f32", *_pv(adv, cf, "adv"), *_pv(ori, cf, "ori"), B, K, pred.data_ptr(),
+        _lib.call(name, *_pv(adv, cf, "adv"), *_pv(ori, cf, "ori"), B, K, *extra, pred.data_ptr(),
                   label.data_ptr(), 1 if untarget else 0, bestdist.data_ptr(), bestscore.data_ptr(),
                   o_bestdist.data_ptr(), o_bestscore.data_ptr(), o_bestattack.data_ptr(), _ptr(input_val),
                   _ptr(dist_val), *_pv(g, cf, "g"), m.data_ptr(), v.data_ptr(), float(lr), float(betas[0]),

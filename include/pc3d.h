@@ -1043,6 +1043,25 @@ int pc3d_cw_update_f32(float* adv, int64_t a_bs, int64_t a_ps, int64_t a_cs,
                        double lr, double beta1, double beta2, double eps, float budget,
                        const int32_t* step_dev, int step_host, int dist_kind, const float* w,
                        const int32_t* nn_idx, void* stream);
+/* pc3d_cw_update_f32 on a batch of clouds of different sizes: sample b counts lengths[b] points (int32 [B] on the
+ * device, read as data and clamped to [1, K]); its rows from lengths[b] on are padding, copies of its point 0. The norm,
+ * the Chamfer factor 2 w_b / (B lengths[b]), Adam and the clip run over the counted rows with the dense kernel's thread
+ * mapping and reduction order, so a sample has the bits of the dense launch on that cloud alone (K = lengths[b]); with
+ * all lengths = K every output equals pc3d_cw_update_f32's. Padding rows are never read (they may hold NaN): their m / v
+ * stay, adv takes the NEW point 0, input_val / o_bestattack the old one where the dense kernel copies. K <= 8192. */
+int pc3d_cw_update_ragged_f32(float* adv, int64_t a_bs, int64_t a_ps, int64_t a_cs,
+                              const float* ori, int64_t o_bs, int64_t o_ps, int64_t o_cs, int B, int K,
+                              const int32_t* lengths, const int64_t* pred, const int64_t* label, int untarget,
+                              float* bestdist, int64_t* bestscore, float* o_bestdist, int64_t* o_bestscore,
+                              float* o_bestattack, float* input_val, float* dist_val,
+                              const float* g, int64_t g_bs, int64_t g_ps, int64_t g_cs, float* m, float* v,
+                              double lr, double beta1, double beta2, double eps, float budget,
+                              const int32_t* step_dev, int step_host, int dist_kind, const float* w,
+                              const int32_t* nn_idx, void* stream);
+/* x[b, :, k] = x[b, :, 0] for every k >= lengths[b] (int32 [B] on the device, clamped to [1, K]), in place, one launch:
+ * the padding the ragged update keeps. Rows at and beyond the length are only written; B <= 65535. */
+int pc3d_pad_ragged_f32(float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, const int32_t* lengths, int B, int K,
+                        void* stream);
 
 /* The kNN attack's update (attack/KNN/KNN_attack.py:117-136) as ONE launch, one workgroup per sample: the gradient of
  * ChamferkNNDist('adv2ori') from the two search results, Adam and the clip, on the iterate adv (updated IN PLACE; m / v
