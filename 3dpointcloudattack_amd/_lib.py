@@ -88,6 +88,7 @@ SIGNATURES = {
     + _PTS + _PTS + [_I, _P],
     "pc3d_knn_f32": _PTS + _PTS + [_I, _I, _I, _I, _P, _P, _P],
     "pc3d_knn_hint_f32": _PTS + _PTS + [_I, _I, _I, _I, _P, _P, _P, _P],
+    "pc3d_knn_ragged_f32": _PTS + _PTS + [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "pc3d_knn_small_f32": _PTS + _PTS + [_I, _I, _I, _I, _P, _P],
     "pc3d_knn_bwd_f32": _PTS + _PTS + [_I, _I, _I, _I, _P, _P] + _PTS + _PTS + [_I, _P, _P],
     "pc3d_knn_self_bwd_f32": _PTS + [_I, _I, _I, _P, _P, _P] + _PTS + [_I, _P, _P],
@@ -144,6 +145,8 @@ SIGNATURES = {
     "pc3d_pad_ragged_f32": _PTS + [_P, _I, _I, _P],
     "pc3d_knn_attack_update_f32": _PTS + _PTS + _PTS + _PTS + [_P, _P] + [_I, _I, _I, _P, _P, _P] + [_D, _D, _D, _D]
     + [_F, _I, _F, _F, _F, _P, _I, _P],
+    "pc3d_knn_attack_update_ragged_f32": _PTS + _PTS + _PTS + _PTS + [_P, _P] + [_I, _I, _I, _P, _P, _P, _P]
+    + [_D, _D, _D, _D] + [_F, _I, _F, _P, _P, _P, _I, _P],
     "pc3d_eot_prepare_f32": [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P],
     "pc3d_eot_update_f32": [_P] * 5 + [_I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _I] + [_P] * 8 + [_I, _P, _P, _I]
     + [_D, _D, _D, _D, _I, _F, _P, _I, _P],

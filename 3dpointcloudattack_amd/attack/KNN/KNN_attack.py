@@ -9,6 +9,7 @@ transfer / fail counters are sums over the batch. Transfer models may be ``None`
 
 ``device_loop=True`` (PointNet victims, see ``CWKNN._device_loop_plan``): the iteration is the victim's launch-minimal
 passes, the two searches and ONE update launch (pc3d_knn_attack_update_f32), replayed from a hipGraph without autograd.
+``attack(data, target, lengths)`` runs that loop on a batch of clouds of different sizes.
 """
 import numpy as np
 import torch
@@ -34,14 +35,19 @@ TRANSFER_MODELS = (("pt_fail", "pt_model"), ("ptm_fail", "ptm_model"), ("pts_fai
                    ("dgcnn_fail", "dgcnn_model"), ("cur_fail", "cur_model"))
 
 
-def count_transfer_fails(attack, result, target):
+def count_transfer_fails(attack, result, target, lens=None):
     """The five transfer checks (reference :160-240): every transfer model the attack holds (None: skipped) classifies
-    `result` [B,3,K]; its counter grows by the samples on which the attack does not succeed there."""
+    `result` [B,3,K]; its counter grows by the samples on which the attack does not succeed there. lens (a ragged batch's
+    sizes): a model that does not declare pad_invariant sees every cloud alone, on its own [1,3,lens[b]] slice."""
     for name, attr in TRANSFER_MODELS:
         m = getattr(attack, attr)
         if m is None:
             continue
-        p = torch.argmax(_graphed.logits_of(m(result)), dim=1)
+        if lens is None or getattr(_graphed.unwrap(m), "pad_invariant", False):
+            p = torch.argmax(_graphed.logits_of(m(result)), dim=1)
+        else:
+            p = torch.cat([torch.argmax(_graphed.logits_of(m(result[b:b + 1, :, :int(n)].contiguous())), dim=1)
+                           for b, n in enumerate(lens)])
         setattr(attack, name, getattr(attack, name) + int((~attack._success(p, target)).sum().item()))
 
 
@@ -114,6 +120,68 @@ class CWKNN:
         return None
 
     # ---- device loop (PointNet victim + own functors): no autograd, every buffer updated IN PLACE, replayed from hipGraphs ----
+    def _dist_plan(self):
+        """(k, alpha, w1, w2) of a distance functor the device loop knows — ChamferkNNDist / ChamferDist with 'adv2ori'
+        (w2 None: no kNN term) — else None."""
+        df = self.dist_func
+        if type(df) is _dist_utils.ChamferkNNDist and df.chamfer_dist.method == 'adv2ori':
+            return int(df.knn_dist.k), float(df.knn_dist.alpha), float(df.w1), float(df.w2)
+        if type(df) is _dist_utils.ChamferDist and df.method == 'adv2ori':
+            return 0, 0.0, 1.0, None
+        return None
+
+    def _ragged_lengths(self, data, lengths):
+        """lengths as int64 numpy [B] after every check of the ragged loop, or ValueError naming what does not fit, before
+        any launch: there is no silent fall-back, since the direct and generic paths would count the padding copies of
+        point 0 as neighbours and as outlier statistics."""
+        who = "CWKNN.attack(lengths=...)"
+        if not self.device_loop:
+            raise ValueError(f"{who}: device_loop=False has no ragged pass")
+        if self.device.type != "cuda":
+            raise ValueError(f"{who}: the device {self.device} has no device loop")
+        victim = _graphed.unwrap(self.model)
+        if not getattr(victim, "pad_invariant", False) or not hasattr(victim, "fused_attack_grad"):
+            raise ValueError(f"{who}: the victim {type(victim).__name__} does not declare pad_invariant or lacks the fused "
+                             "entry points (fused_attack_grad)")
+        if _adv_utils.own_adv_kind(self.adv_func) is None:
+            raise ValueError(f"{who}: adv_func {type(self.adv_func).__name__} is not one of this package's adversarial functors")
+        dp = self._dist_plan()
+        if dp is None:
+            raise ValueError(f"{who}: dist_func {type(self.dist_func).__name__} is neither ChamferkNNDist nor ChamferDist "
+                             "with 'adv2ori'")
+        if self._fused_clip() is None:
+            raise ValueError(f"{who}: clip_func {type(self.clip_func).__name__} is neither ProjectInnerClipLinf nor "
+                             "ClipPointsLinf (or fused=False)")
+        if data.dim() != 3 or data.shape[2] not in (3, 6):
+            raise ValueError(f"{who}: data must be [B, Kmax, 3 or 6], got {tuple(data.shape)}")
+        B, K = data.shape[:2]
+        if K > ops.KNN_LOOP_MAX_POINTS:
+            raise ValueError(f"{who}: Kmax={K} exceeds KNN_LOOP_MAX_POINTS={ops.KNN_LOOP_MAX_POINTS}")
+        if dp[3] is not None and not 1 <= dp[0] <= 63:
+            raise ValueError(f"{who}: ChamferkNNDist's k={dp[0]} out of range [1, 63]")
+        if next(victim.parameters()).device.type != "cuda":
+            raise ValueError(f"{who}: the victim's parameters are not on the GPU")
+        if torch.is_tensor(lengths):
+            lengths = lengths.detach().cpu().numpy()
+        lens = np.asarray(lengths)
+        if lens.shape != (B,) or not np.issubdtype(lens.dtype, np.integer):
+            raise ValueError(f"{who}: lengths must be {B} ints, got shape {lens.shape} dtype {lens.dtype}")
+        low = max(1, dp[0] + 1)
+        if lens.min() < low or lens.max() > K:
+            raise ValueError(f"{who}: lengths must lie in [max(1, k + 1)={low}, Kmax={K}], got [{lens.min()}, {lens.max()}]")
+        return lens.astype(np.int64)
+
+    def _ragged_plan(self, B, has_normal):
+        """The constants of the ragged device loop (_ragged_lengths has checked everything). The two scales are per-cloud
+        device data, prepared by every call from its lengths: the plan, and so the loop's key, holds the functor's weights
+        and the size of the whole batch in their place, and the flag."""
+        k, alpha, w1, w2 = self._dist_plan()
+        fc = self._fused_clip()
+        G = int(self.global_batch) if self.global_batch else B
+        return dict(victim=_graphed.unwrap(self.model), kind=_adv_utils.own_adv_kind(self.adv_func), k=k, alpha=alpha, w1=w1,
+                    w2=w2, G=G, ragged=True, budget=fc[0], clip_mode="project_clip" if fc[1] else "clip", scale=1.0 / G,
+                    has_normal=bool(has_normal and fc[1]))
+
     def _device_loop_plan(self, B, K, has_normal):
         """The constants of the device loop when it applies, else None: a GPU victim with fused_attack_grad (the two
         PointNetCls variants), an adversarial functor the CW loop maps to ops.LOSS_KINDS, ChamferkNNDist / ChamferDist
@@ -166,6 +234,30 @@ class CWKNN:
         pred = torch.zeros((B,), dtype=torch.long, device=dev)
         target = torch.zeros((B,), dtype=torch.long, device=dev)
         kind, kappa = plan["kind"]
+        if plan.get("ragged"):
+            # the lengths and the per-cloud scales are DATA of the captured launches: another call's lengths replay the
+            # same graphs. lens_host: the host copy the search wrapper checks (filled in place by every call).
+            lens = torch.ones((B,), dtype=torch.int32, device=dev)
+            lens_host = np.ones((B,), dtype=np.int64)
+            c_ch, c_knn = torch.zeros((B,), **f32), torch.zeros((B,), **f32)
+
+            def body():
+                # the dense chain, launch for launch: the victim's passes on the padded batch (pad_invariant: the padding
+                # rows' gradient is exactly zero), the self-kNN search over every cloud's own points, the adv -> ori search
+                # unchanged (ori's padding rows are copies of its point 0 and lose every tie to it), the ragged update
+                with torch.no_grad():
+                    _, _, gx = victim.fused_attack_grad(adv, target, kind, kappa, pred_out=pred, step=step, scale=plan["scale"])
+                    if k:
+                        ops.knn_search_into(adv, knn_d, knn_idx, lengths=lens, lengths_host=lens_host)
+                    ops.nn_search_into(adv, ori, nn_d, nn_idx)
+                    ops.knn_attack_update(adv, ori, gx, m, v, step, lr, knn_d, knn_idx, nn_idx, c_ch, c_knn, plan["alpha"],
+                                          plan["budget"], plan["clip_mode"], normal, lengths=lens)
+
+            bufs = dict(adv=adv, ori=ori, normal=normal, target=target, plan=plan, m=m, v=v, step=step, pred=pred,
+                        knn_d=knn_d, knn_idx=knn_idx, nn_d=nn_d, nn_idx=nn_idx, lens=lens, lens_host=lens_host, c_ch=c_ch,
+                        c_knn=c_knn)
+            return self._loop_cache.put(key, _graphed.DeviceLoop(key, dev, owners=(victim,), counts=(1, self.LOOP_BLOCK),
+                                                                 warmup=2, body=body, bufs=bufs))
 
         def body():
             # one chain on one stream: the victim's passes (the classifier tail advances the step word), the self-kNN
@@ -185,10 +277,16 @@ class CWKNN:
 
     LOOP_BLOCK = 16      # iterations per graph replay; the remainder replays single-iteration graphs
 
-    def _run_device_loop(self, plan, adv_data, ori_data, normal, target):
+    def _run_device_loop(self, plan, adv_data, ori_data, normal, target, lens=None):
         B, _, K = adv_data.shape
         loop = self._device_loop_state(plan, B, K)
         c = loop.bufs
+        if lens is not None:
+            # what a run of every cloud alone prepares from its own point count (ops.knn_attack_scales_ragged)
+            c_ch, c_knn = ops.knn_attack_scales_ragged(lens, plan["k"], plan["G"], plan["w1"], plan["w2"])
+            c["lens_host"][:] = lens
+            c["lens"].copy_(torch.from_numpy(lens.astype(np.int32)))
+            c["c_ch"].copy_(torch.from_numpy(c_ch)), c["c_knn"].copy_(torch.from_numpy(c_knn))
 
         def rewind():
             c["adv"].copy_(adv_data)
@@ -205,27 +303,36 @@ class CWKNN:
             loop.run(self.num_iter)
             adv_data.copy_(c["adv"])
 
-    def attack(self, data, target):
+    def attack(self, data, target, lengths=None):
         """Attack on given data to target.
         Args:
             data (torch.FloatTensor): victim data, [B, num_points, 3] (or 6 with normals)
             target (torch.LongTensor): target output, [B]
-        Returns (adv [B,K,3] float32 numpy, success_num) like the reference (:244-246).
+            lengths (default None: every cloud has data.shape[1] points, nothing changes): B ints, the sizes of a batch of
+                clouds of different sizes as dataset.cloud_io.stack_ragged builds it, max(1, k + 1) <= lengths[b] <= Kmax =
+                data.shape[1]; rows of data at and beyond a length are ignored. Runs the device loop only (device_loop=True,
+                a pad_invariant PointNet victim, own functors, Kmax <= ops.KNN_LOOP_MAX_POINTS); anything else raises
+                ValueError before any launch. With `sample_seeds` and `global_batch` every cloud gets the bits of its run
+                alone; without seeds the start noise is one batch-shaped draw whose padding columns are ignored.
+        Returns (adv [B,K,3] float32 numpy, success_num) like the reference (:244-246); with lengths, adv's rows at and
+        beyond a cloud's length hold that cloud's row 0.
         """
+        if lengths is not None:
+            lengths = self._ragged_lengths(data, lengths)
         if self.deterministic is not None and self.deterministic != ops.DETERMINISTIC:
             with ops.deterministic(self.deterministic):
-                return self.attack(data, target)
+                return self.attack(data, target, lengths)
         if self.sample_seeds is None:
-            return self._attack(data, target, None)
+            return self._attack(data, target, None, lengths)
         from ...model import pointnet2_utils as _pn2
         assert len(self.sample_seeds) == data.shape[0], "sample_seeds needs one seed per sample"
         prev = _pn2.set_fps_start_source(_pn2.SeededFpsStarts([int(s) + 7919 for s in self.sample_seeds]))
         try:
-            return self._attack(data, target, [torch.Generator().manual_seed(int(s)) for s in self.sample_seeds])
+            return self._attack(data, target, [torch.Generator().manual_seed(int(s)) for s in self.sample_seeds], lengths)
         finally:
             _pn2.set_fps_start_source(prev)
 
-    def _attack(self, data, target, gens):
+    def _attack(self, data, target, gens, lens=None):
         dev = self.device
         B, K = data.shape[:2]
         ratio = (float(B) / float(self.global_batch)) if self.global_batch else 1.0
@@ -240,6 +347,13 @@ class CWKNN:
         else:
             normal = ori_data[:, 3:, :]
             ori_data = ori_data[:, :3, :]
+        lens_dev = None
+        if lens is not None:
+            # ragged batch: every cloud's rows from its length on become copies of its point 0 (the normals' are never read)
+            lens_dev = torch.from_numpy(lens.astype(np.int32)).to(dev)
+            if normal is not ori_data:
+                ori_data = ori_data.contiguous()
+            ops.pad_ragged(ori_data, lens_dev)
 
         # clean forward (:76-78). Kept even when nothing is printed: a PointNet++ victim draws its FPS start indices
         # from the global RNG on every forward, so skipping it would shift the stream the reference sees.
@@ -251,14 +365,27 @@ class CWKNN:
         target = target.long().to(dev).detach().view(-1)
 
         # init variables with small perturbation (CPU generator like the reference, :84-85)
-        noise = torch.randn((B, 3, K)) if gens is None else torch.stack([torch.randn((3, K), generator=g) for g in gens])
+        if gens is None or lens is None:
+            noise = torch.randn((B, 3, K)) if gens is None else torch.stack([torch.randn((3, K), generator=g) for g in gens])
+        else:
+            # what a run of that cloud alone draws: (3, lengths[b]) from the sample's own generator
+            noise = torch.zeros((B, 3, K))
+            for b, (g, n) in enumerate(zip(gens, lens)):
+                noise[b, :, :int(n)] = torch.randn((3, int(n)), generator=g)
         adv_data = ori_data.clone().detach() + noise.to(dev) * 1e-7
+        if lens is not None:
+            ops.pad_ragged(adv_data, lens_dev)
         adv_data.requires_grad_()
         fc = self._fused_clip()
         if fc is None:
             opt = optim.Adam([adv_data], lr=self.attack_lr, weight_decay=0.)
         else:
             exp_avg, exp_avg_sq = torch.zeros_like(adv_data), torch.zeros_like(adv_data)
+        if lens is not None:
+            plan = self._ragged_plan(B, normal is not ori_data)
+            self.last_path = "device_loop"
+            self._run_device_loop(plan, adv_data, ori_data, normal, target, lens)
+            return self._finish(adv_data, target, B, lens)
         plan = self._device_loop_plan(B, K, normal is not ori_data) if self.device_loop else None
         if plan is not None:
             self.last_path = "device_loop"
@@ -346,8 +473,8 @@ class CWKNN:
                 _pn2.set_fps_start_source(prev_source)
         return self._finish(adv_data, target, B)
 
-    def _finish(self, adv_data, target, B):
-        # end of CW attack
+    def _finish(self, adv_data, target, B, lens=None):
+        # end of CW attack (lens: a ragged batch — the victim is pad_invariant and sees the padded batch)
         with torch.no_grad():
             pred = torch.argmax(_graphed.logits_of(self.model(adv_data)), dim=-1)  # [B]
             success_num = int(self._success(pred, target).sum().item())
@@ -356,7 +483,7 @@ class CWKNN:
             result = adv_data.detach().float()
             # Test attack + transfer models (:160-240)
             self.attack_fail += int((~self._success(torch.argmax(_graphed.logits_of(self.model(result)), dim=1), target)).sum().item())
-            count_transfer_fails(self, result, target)
+            count_transfer_fails(self, result, target, lens)
 
         adv_np = adv_data.detach().transpose(1, 2).contiguous().cpu().numpy()  # [B, K, 3]
         return adv_np, success_num

@@ -23,6 +23,14 @@ struct KnnArgs {
   int k2 = 0;
   const int32_t* hint = nullptr; // [B,N,K] or null: K reference indices per query from an earlier, similar search (may be `i`)
 };
+// Clouds of different sizes in one batch: cloud b counts len_q[b] queries and len_r[b] candidates (int32 [B], read as data,
+// clamped to [0,N] / [0,M]); N and M are the capacities, the row strides of d / i / hint and the grid.
+struct KnnRaggedArgs : KnnArgs {
+  const int32_t* len_q;
+  const int32_t* len_r;
+};
+template <bool RAGGED> struct KnnArgsOf { using type = KnnArgs; };
+template <> struct KnnArgsOf<true> { using type = KnnRaggedArgs; };
 
 // ---------------------------------------------------------------------------------------------------------
 // Wave-per-query search: the 64 lanes of a wave hold 64 CANDIDATES of one LDS step and test them against 4 queries
@@ -38,13 +46,25 @@ struct KnnArgs {
 constexpr int kKwQPW = 4;          // queries scanned together by a wave
 constexpr int kKwTile = 2048;      // reference points per LDS tile (24 KiB SoA)
 
-template <int kKwWaves, bool KGE2>    // waves per workgroup: a workgroup serves 4 * kKwWaves queries from one staged copy of the cloud
-__global__ __launch_bounds__(kKwWaves * 64) void knn_wave_kernel(KnnArgs a) {
+// RAGGED: the queries below n = len_q[b] search the candidates below m = len_r[b]. The tiling starts at candidate 0 and the
+// tile does not depend on m, so a row has the bits (distances and indices) of the dense search of that cloud alone at N = n,
+// M = m; rows from n on are neither read nor written, a hint entry >= m is a bad hint. Precondition m >= K (the host's to
+// check: the lengths are device data); the clamps keep every access inside the buffers whatever the lengths hold.
+// The dense instantiations compile to the kernels they were before RAGGED existed (the parameter is a type of its own).
+template <int kKwWaves, bool KGE2, bool RAGGED = false>    // waves per workgroup: a workgroup serves 4 * kKwWaves queries from one staged copy of the cloud
+__global__ __launch_bounds__(kKwWaves * 64) void knn_wave_kernel(typename KnnArgsOf<RAGGED>::type a) {
   constexpr int kKwPasses = 1;
   constexpr int kKwThreads = kKwWaves * 64;
   __shared__ __attribute__((aligned(16))) float lds[3 * kKwTile];
-  const int N = a.N, M = a.M, K = a.K;
+  const int Ncap = a.N, K = a.K;     // Ncap: the row stride of d / i / hint
+  int N = a.N, M = a.M;
   const int b = blockIdx.y;
+  if constexpr (RAGGED) {
+    N = min(max(a.len_q[b], 0), a.N);
+    M = min(max(a.len_r[b], 0), a.M);
+    // a workgroup without a query leaves as a whole, before the first barrier (blockIdx and b only)
+    if ((int)blockIdx.x * (kKwWaves * kKwPasses * kKwQPW) >= N) return;
+  }
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // scalar: query loads / thresholds live in SGPRs
   const int qbase = blockIdx.x * (kKwWaves * kKwPasses * kKwQPW) + wave * (kKwPasses * kKwQPW);
@@ -93,7 +113,7 @@ __global__ __launch_bounds__(kKwWaves * 64) void knn_wave_kernel(KnnArgs a) {
       for (int u = 0; u < kKwQPW; ++u) {
         int qi = qbase + p * kKwQPW + u;
         if (qi >= N) qi = N - 1;
-        const int h = lane < K ? a.hint[((int64_t)b * N + qi) * K + lane] : -1 - lane;     // (distinct fillers above K)
+        const int h = lane < K ? a.hint[((int64_t)b * Ncap + qi) * K + lane] : -1 - lane;     // (distinct fillers above K)
         bool bad = lane < K && (unsigned)h >= (unsigned)M;
         for (int t = 0; t < K; ++t) bad |= lane > t && h == __builtin_amdgcn_readlane(h, t);
         int key = 0;
@@ -191,10 +211,10 @@ __global__ __launch_bounds__(kKwWaves * 64) void knn_wave_kernel(KnnArgs a) {
     for (int u = 0; u < kKwQPW; ++u) {
       const int qi = qbase + p * kKwQPW + u;
       if (qi < N && lane < K) {
-        if (a.d) a.d[((int64_t)b * N + qi) * K + lane] = __builtin_bit_cast(float, lk[p][u]);
-        if (a.i) a.i[((int64_t)b * N + qi) * K + lane] = li[p][u];
-        if (a.i_noself && lane >= 1) a.i_noself[((int64_t)b * N + qi) * (K - 1) + lane - 1] = li[p][u];
-        if (a.i_first && lane < a.k2) a.i_first[((int64_t)b * N + qi) * a.k2 + lane] = li[p][u];
+        if (a.d) a.d[((int64_t)b * Ncap + qi) * K + lane] = __builtin_bit_cast(float, lk[p][u]);
+        if (a.i) a.i[((int64_t)b * Ncap + qi) * K + lane] = li[p][u];
+        if (a.i_noself && lane >= 1) a.i_noself[((int64_t)b * Ncap + qi) * (K - 1) + lane - 1] = li[p][u];
+        if (a.i_first && lane < a.k2) a.i_first[((int64_t)b * Ncap + qi) * a.k2 + lane] = li[p][u];
       }
     }
 }
@@ -484,4 +504,27 @@ extern "C" int pc3d_knn_hint_f32(const float* q, int64_t q_bs, int64_t q_ps, int
                                  const float* r, int64_t r_bs, int64_t r_ps, int64_t r_cs,
                                  int B, int N, int M, int K, float* dists, int32_t* idx, const int32_t* hint, void* stream) {
   return knn_launch("pc3d_knn_hint_f32", q, q_bs, q_ps, q_cs, r, r_bs, r_ps, r_cs, B, N, M, K, dists, idx, hint, stream);
+}
+
+extern "C" int pc3d_knn_ragged_f32(const float* q, int64_t q_bs, int64_t q_ps, int64_t q_cs,
+                                   const float* r, int64_t r_bs, int64_t r_ps, int64_t r_cs,
+                                   int B, int N, int M, int K, float* dists, int32_t* idx, const int32_t* hint,
+                                   const int32_t* len_q, const int32_t* len_r, void* stream) {
+  const char* nm = "pc3d_knn_ragged_f32";
+  PC3D_REQUIRE(B >= 0 && N >= 0 && M >= 1, "%s: bad sizes B=%d N=%d M=%d", nm, B, N, M);
+  PC3D_REQUIRE(K >= 1 && K <= 64, "%s: K=%d out of range [1,64]", nm, K);
+  PC3D_REQUIRE(K <= M, "%s: K=%d exceeds the reference capacity M=%d", nm, K, M);
+  PC3D_REQUIRE(B <= 65535, "%s: B=%d exceeds grid.y limit", nm, B);
+  if (B == 0 || N == 0) return PC3D_OK;
+  PC3D_REQUIRE(q && r && len_q && len_r, "%s: null input pointer", nm);
+  KnnRaggedArgs a{};
+  a.q = {q, q_bs, q_ps, q_cs}, a.r = {r, r_bs, r_ps, r_cs};
+  a.N = N, a.M = M, a.K = K, a.d = dists, a.i = idx, a.hint = hint;
+  a.len_q = len_q, a.len_r = len_r;
+  hipStream_t st = as_stream(stream);
+  // the dense launch's grid over the capacity: the lengths are device data, and one captured launch serves any of them
+  if (K >= 2) hipLaunchKernelGGL((knn_wave_kernel<4, true, true>), dim3(cdiv(N, 16), B), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((knn_wave_kernel<4, false, true>), dim3(cdiv(N, 16), B), dim3(256), 0, st, a);
+  PC3D_LAUNCH_CHECK(nm);
+  return PC3D_OK;
 }

@@ -42,16 +42,37 @@ struct KnnUpdArgs {
   const int* step_dev;
   int step_host;
 };
+// Clouds of different sizes in one batch: sample b counts lengths[b] points (int32 [B], read as data, clamped to [1, N]) and
+// has constants of its own (what a run of that cloud alone prepares from its own N); c_ch / c_knn above are not read.
+struct KnnUpdRaggedArgs : KnnUpdArgs {
+  const int32_t* lengths;
+  const float* c_ch_b;     // [B]
+  const float* c_knn_b;    // [B]
+};
+template <bool RAGGED> struct KnnUpdArgsOf { using type = KnnUpdArgs; };
+template <> struct KnnUpdArgsOf<true> { using type = KnnUpdRaggedArgs; };
 
 static inline size_t knn_upd_lds_bytes(int N) {
   const size_t np = (size_t)((N + 3) & ~3);
   return np * 32 + (size_t)kKuEdges * 4 + 48;
 }
 
-__global__ __launch_bounds__(kKuThreads) void knn_attack_update_kernel(KnnUpdArgs a) {
+// RAGGED: N is the capacity — the stride of knn_d / knn_idx / nn_idx and the size of the LDS arrays — and every loop over
+// points, the statistics' divisors and the index clamps run over L = lengths[b] with the dense kernel's thread-to-point
+// mapping and summation order: rows < L have the bits of the dense launch at N = L on that cloud alone. Rows >= L are never
+// loaded (they may hold NaN), their m / v stay, and adv's take the NEW point 0 (the padding the victim's passes and the
+// adv -> ori search rely on). The dense instantiation compiles to the kernel it was before RAGGED existed.
+template <bool RAGGED>
+__global__ __launch_bounds__(kKuThreads) void knn_attack_update_kernel(typename KnnUpdArgsOf<RAGGED>::type a) {
   extern __shared__ __attribute__((aligned(16))) float ku_lds[];
   const int N = a.N, np = (N + 3) & ~3, K1 = a.K1, k = K1 - 1;
   const int b = blockIdx.x, tid = threadIdx.x;
+  int L = N;
+  float c_ch = a.c_ch, c_knn = a.c_knn;
+  if constexpr (RAGGED) {
+    L = min(max(a.lengths[b], 1), N);
+    c_ch = a.c_ch_b[b], c_knn = a.c_knn_b[b];
+  }
   float* sx = ku_lds;
   float* sy = sx + np;
   float* sz = sy + np;
@@ -64,7 +85,8 @@ __global__ __launch_bounds__(kKuThreads) void knn_attack_update_kernel(KnnUpdArg
   float* part = reinterpret_cast<float*>(s_edge + kKuEdges);      // [4]
   float* s_adam = part + 4;                                       // {step_size, bc2s}
   int* s_nm = reinterpret_cast<int*>(s_adam + 2);
-  const bool knn = k >= 1 && a.c_knn != 0.f;
+  [[maybe_unused]] float* s_pad = reinterpret_cast<float*>(s_nm + 1);     // [3] RAGGED: the new point 0 (40 of the 48 tail bytes)
+  const bool knn = k >= 1 && c_knn != 0.f;
   const float* db = a.knn_d + (int64_t)b * N * K1;
   const int32_t* ib = a.knn_idx + (int64_t)b * N * K1;
 
@@ -74,7 +96,7 @@ __global__ __launch_bounds__(kKuThreads) void knn_attack_update_kernel(KnnUpdArg
     s_adam[1] = adam_bc2s(a.b2, t);
   }
   const float inv_k = 1.f / (float)(k > 0 ? k : 1);
-  for (int p = tid; p < N; p += kKuThreads) {
+  for (int p = tid; p < L; p += kKuThreads) {
     const float* xp = a.adv.p + (int64_t)b * a.adv.bs + (int64_t)p * a.adv.ps;
     sx[p] = xp[0], sy[p] = xp[a.adv.cs], sz[p] = xp[2 * a.adv.cs];
     ax[p] = ay[p] = az[p] = 0.f;
@@ -87,27 +109,27 @@ __global__ __launch_bounds__(kKuThreads) void knn_attack_update_kernel(KnnUpdArg
   __syncthreads();
 
   float thr = 0.f;
-  const float w = 2.f * a.c_knn;
+  const float w = 2.f * c_knn;
   if (knn) {
     // mean and unbiased std of the mean neighbour distances, thr = mean + alpha std (knn_outlier_loss_kernel's order)
     float s = 0.f;
     if (tid < 256)
-      for (int i = tid; i < N; i += 256) s += s_val[i];
-    const float mean = block_sum4_pairwise(s, part) / (float)N;
+      for (int i = tid; i < L; i += 256) s += s_val[i];
+    const float mean = block_sum4_pairwise(s, part) / (float)L;
     float q = 0.f;
     if (tid < 256)
-      for (int i = tid; i < N; i += 256) {
+      for (int i = tid; i < L; i += 256) {
         const float dv = s_val[i] - mean;
         q += dv * dv;
       }
-    const float var = block_sum4_pairwise(q, part) / (float)(N > 1 ? N - 1 : 1);
+    const float var = block_sum4_pairwise(q, part) / (float)(L > 1 ? L - 1 : 1);
     thr = mean + a.alpha * sqrtf(var);
     // the masked points, ascending, by wave 0
     if (tid < 64) {
       int base = 0;
-      for (int i0 = 0; i0 < N; i0 += 64) {
+      for (int i0 = 0; i0 < L; i0 += 64) {
         const int i = i0 + tid;
-        const bool out = i < N && s_val[i] > thr;
+        const bool out = i < L && s_val[i] > thr;
         const unsigned long long bal = __ballot(out);
         if (out) s_list[base + __popcll(bal & ((1ull << tid) - 1ull))] = i;
         base += __popcll(bal);
@@ -123,7 +145,7 @@ __global__ __launch_bounds__(kKuThreads) void knn_attack_update_kernel(KnnUpdArg
         int ent = -1;
         if (f < total) {
           const int sl = f / k, e = f - sl * k + 1, i = s_list[sl];
-          const int j = min(max(ib[(int64_t)i * K1 + e], 0), N - 1);
+          const int j = min(max(ib[(int64_t)i * K1 + e], 0), L - 1);
           ent = (i << 16) | j;
         }
         s_edge[t] = ent;
@@ -153,15 +175,15 @@ __global__ __launch_bounds__(kKuThreads) void knn_attack_update_kernel(KnnUpdArg
   __syncthreads();      // (s_adam for the clouds without a kNN term)
 
   const AdamConsts ad = adam_consts_with(a.b1, a.b2, a.eps, s_adam[0], s_adam[1]);
-  const float wc = 2.f * a.c_ch;
+  const float wc = 2.f * c_ch;
   const PtsView nrm = a.normal.p ? a.normal : a.ori;
-  for (int p = tid; p < N; p += kKuThreads) {
+  for (int p = tid; p < L; p += kKuThreads) {
     const float x[3] = {sx[p], sy[p], sz[p]};
     const float* op = a.ori.p + (int64_t)b * a.ori.bs + (int64_t)p * a.ori.ps;
     const float o[3] = {op[0], op[a.ori.cs], op[2 * a.ori.cs]};
     float g2[3] = {0.f, 0.f, 0.f};
-    if (a.c_ch != 0.f) {
-      const int j = min(max(a.nn_idx[(int64_t)b * N + p], 0), N - 1);
+    if (c_ch != 0.f) {
+      const int j = min(max(a.nn_idx[(int64_t)b * N + p], 0), L - 1);
       const float* qp = a.ori.p + (int64_t)b * a.ori.bs + (int64_t)j * a.ori.ps;
       g2[0] = wc * (x[0] - qp[0]);
       g2[1] = wc * (x[1] - qp[a.ori.cs]);
@@ -171,7 +193,7 @@ __global__ __launch_bounds__(kKuThreads) void knn_attack_update_kernel(KnnUpdArg
       float own[3] = {0.f, 0.f, 0.f};
       if (s_val[p] > thr) {
         for (int e = 1; e < K1; ++e) {
-          const int j = min(max(ib[(int64_t)p * K1 + e], 0), N - 1);
+          const int j = min(max(ib[(int64_t)p * K1 + e], 0), L - 1);
           own[0] += w * (x[0] - sx[j]);
           own[1] += w * (x[1] - sy[j]);
           own[2] += w * (x[2] - sz[j]);
@@ -204,6 +226,19 @@ __global__ __launch_bounds__(kKuThreads) void knn_attack_update_kernel(KnnUpdArg
     xp[0] = o[0] + dx;
     xp[a.adv.cs] = o[1] + dy;
     xp[2 * a.adv.cs] = o[2] + dz;
+    if constexpr (RAGGED) {
+      if (p == 0) s_pad[0] = o[0] + dx, s_pad[1] = o[1] + dy, s_pad[2] = o[2] + dz;      // thread 0 owns point 0
+    }
+  }
+  if constexpr (RAGGED) {
+    // re-padding: adv's rows from L on take the new point 0, through LDS behind the barrier (no thread re-reads global
+    // memory another thread of the workgroup writes)
+    __syncthreads();
+    const float n0[3] = {s_pad[0], s_pad[1], s_pad[2]};
+    for (int p = L + tid; p < N; p += kKuThreads) {
+      float* xp = a.adv.p + (int64_t)b * a.adv.bs + (int64_t)p * a.adv.ps;
+      xp[0] = n0[0], xp[a.adv.cs] = n0[1], xp[2 * a.adv.cs] = n0[2];
+    }
   }
 }
 
@@ -235,14 +270,53 @@ extern "C" int pc3d_knn_attack_update_f32(float* adv, int64_t a_bs, int64_t a_ps
                budget, clip_mode, alpha, c_chamfer, c_knn, step_dev, step_host};
   const size_t lds = knn_upd_lds_bytes(N);
   if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(knn_attack_update_kernel),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(knn_attack_update_kernel<false>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)knn_upd_lds_bytes(kKuMaxPoints));
     if (e != hipSuccess) {
       set_error("pc3d_knn_attack_update_f32: LDS opt-in failed: %s", hipGetErrorString(e));
       return (int)e;
     }
   }
-  hipLaunchKernelGGL(knn_attack_update_kernel, dim3(B), dim3(kKuThreads), lds, as_stream(stream), a);
+  hipLaunchKernelGGL(knn_attack_update_kernel<false>, dim3(B), dim3(kKuThreads), lds, as_stream(stream), a);
   PC3D_LAUNCH_CHECK("pc3d_knn_attack_update_f32");
+  return PC3D_OK;
+}
+
+extern "C" int pc3d_knn_attack_update_ragged_f32(float* adv, int64_t a_bs, int64_t a_ps, int64_t a_cs,
+                                                 const float* ori, int64_t o_bs, int64_t o_ps, int64_t o_cs,
+                                                 const float* normal, int64_t n_bs, int64_t n_ps, int64_t n_cs,
+                                                 const float* g, int64_t g_bs, int64_t g_ps, int64_t g_cs, float* m, float* v,
+                                                 int B, int N, int k, const int32_t* lengths, const float* knn_d,
+                                                 const int32_t* knn_idx, const int32_t* nn_idx, double lr, double beta1,
+                                                 double beta2, double eps, float budget, int clip_mode, float alpha,
+                                                 const float* c_chamfer, const float* c_knn, const int32_t* step_dev,
+                                                 int step_host, void* stream) {
+  const char* nm = "pc3d_knn_attack_update_ragged_f32";
+  PC3D_REQUIRE(B >= 0 && N >= 1 && N <= kKuMaxPoints, "%s: bad sizes B=%d N=%d (1 <= N <= %d)", nm, B, N, kKuMaxPoints);
+  PC3D_REQUIRE(k >= 0 && k <= 63, "%s: k=%d out of range [0,63]", nm, k);
+  PC3D_REQUIRE(step_dev != nullptr || step_host >= 1, "%s: step_host must be >= 1 without a device counter", nm);
+  PC3D_REQUIRE(clip_mode == 0 || clip_mode == 1, "%s: clip_mode=%d not in {0,1}", nm, clip_mode);
+  PC3D_REQUIRE(k == 0 || k + 1 <= N, "%s: k + 1 = %d neighbours of N=%d points", nm, k + 1, N);
+  if (B == 0) return PC3D_OK;
+  // the per-cloud constants are device data: whether a cloud has a kNN or a Chamfer term is not known here
+  PC3D_REQUIRE(adv && ori && g && m && v && lengths && c_chamfer && c_knn && nn_idx, "%s: null pointer", nm);
+  PC3D_REQUIRE(k == 0 || (knn_d && knn_idx), "%s: k >= 1 needs knn_d and knn_idx", nm);
+  KnnUpdRaggedArgs a{};
+  static_cast<KnnUpdArgs&>(a) = KnnUpdArgs{{adv, a_bs, a_ps, a_cs}, {ori, o_bs, o_ps, o_cs}, {normal, n_bs, n_ps, n_cs},
+                                           {g, g_bs, g_ps, g_cs}, {m, a_bs, a_ps, a_cs}, {v, a_bs, a_ps, a_cs}, N, k + 1,
+                                           knn_d, knn_idx, nn_idx, lr, beta1, beta2, (float)eps, budget, clip_mode, alpha,
+                                           0.f, 0.f, step_dev, step_host};
+  a.lengths = lengths, a.c_ch_b = c_chamfer, a.c_knn_b = c_knn;
+  const size_t lds = knn_upd_lds_bytes(N);      // from the capacity: the lengths are device data
+  if (lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(knn_attack_update_kernel<true>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)knn_upd_lds_bytes(kKuMaxPoints));
+    if (e != hipSuccess) {
+      set_error("%s: LDS opt-in failed: %s", nm, hipGetErrorString(e));
+      return (int)e;
+    }
+  }
+  hipLaunchKernelGGL(knn_attack_update_kernel<true>, dim3(B), dim3(kKuThreads), lds, as_stream(stream), a);
+  PC3D_LAUNCH_CHECK(nm);
   return PC3D_OK;
 }

@@ -1108,10 +1108,54 @@ KNN_LOOP_MAX_POINTS = 4096      # pc3d_knn_attack_update_f32 keeps a sample in L
 KNN_CLIP_MODES = {"clip": 0, "project_clip": 1}
 
 
-def knn_search_into(adv, d, idx, cf=True):
+def _lengths_host(who, lengths, lengths_host, B, K, what="reference"):
+    """The host copy of a device lengths buffer (lengths_host, array-like of B ints; None: read back, which synchronises
+    and cannot happen inside a capture) checked against the search's precondition: every cloud holds at least K points."""
+    if lengths_host is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise ValueError(f"{who}: inside a capture the lengths cannot be read back; pass lengths_host")
+        lengths_host = lengths.cpu().numpy()
+    host = np.asarray(lengths_host)
+    if host.shape != (B,) or not np.issubdtype(host.dtype, np.integer):
+        raise ValueError(f"{who}: lengths_host must be {B} ints")
+    if host.size and int(host.min()) < K:
+        raise ValueError(f"{who}: K={K} exceeds the {what} length {int(host.min())} of cloud {int(host.argmin())}")
+    return host
+
+
+def knn_ragged(q, r, K, len_q, len_r=None, q_cf=False, r_cf=False, hint=None, lengths_host=None):
+    """ops.knn_raw on a batch of clouds of different sizes (pc3d_knn_ragged_f32): cloud b's first len_q[b] queries search its
+    first len_r[b] reference points (len_r None: len_q). len_q / len_r: int32 [B] on the device, read by the kernel as
+    data. Returns (dists [B,N,K] f32, idx [B,N,K] i32): rows below a length have the bits of knn_raw on that cloud alone,
+    rows at and beyond it are zero (never written). hint: an int32 [B,N,K] tensor from an earlier search, or None.
+    lengths_host: the host copy of len_r for the check K <= len_r[b] (None: read back)."""
+    qp, qbs, qps, qcs, B, N = _pts(q, q_cf, "q")
+    rp, rbs, rps, rcs, B2, M = _pts(r, r_cf, "r")
+    if B != B2:
+        raise ValueError("q and r must have the same batch dimension")
+    if not (1 <= K <= min(64, M)):
+        raise ValueError(f"K={K} out of range [1, min(64, M={M})]")
+    lq = _lengths_arg("knn_ragged", len_q, B, q.device)
+    lr = lq if len_r is None else _lengths_arg("knn_ragged", len_r, B, q.device)
+    _lengths_host("knn_ragged", len_q if len_r is None else len_r, lengths_host, B, K)
+    d = torch.zeros((B, N, K), dtype=torch.float32, device=q.device)
+    i = torch.zeros((B, N, K), dtype=torch.int32, device=q.device)
+    if hint is not None and (hint.dtype != torch.int32 or hint.shape != i.shape or not hint.is_contiguous()
+                             or hint.device != q.device):
+        raise ValueError("knn_ragged: hint must be a contiguous int32 [B,N,K] tensor on q's device")
+    with torch.cuda.device(q.device):
+        _lib.call("pc3d_knn_ragged_f32", qp, qbs, qps, qcs, rp, rbs, rps, rcs, B, N, M, K, d.data_ptr(), i.data_ptr(),
+                  _ptr(hint), lq, lr, _stream())
+    return d, i
+
+
+def knn_search_into(adv, d, idx, cf=True, lengths=None, lengths_host=None):
     """The sorted self-kNN of adv into the caller's OWN buffers d (float32) / idx (int32) [B,N,K], idx also being the search's
     hint (pc3d_knn_hint_f32 allows hint == idx): an attack loop keeps one pair for as long as its graph lives, so every
-    search starts from the previous iteration's neighbours. The result never depends on what idx held."""
+    search starts from the previous iteration's neighbours. The result never depends on what idx held.
+    lengths (int32 [B] on the device, default None: the dense launch, unchanged): cloud b counts lengths[b] points, as
+    queries and as candidates (pc3d_knn_ragged_f32); rows at and beyond a length are neither read nor written.
+    lengths_host: their host copy for the check K <= lengths[b] (None: read back, not inside a capture)."""
     p, bs, ps, cs, B, N = _pts(adv, cf, "adv")
     K = idx.shape[-1]
     for nm, t, dt in (("d", d, torch.float32), ("idx", idx, torch.int32)):
@@ -1119,6 +1163,13 @@ def knn_search_into(adv, d, idx, cf=True):
             raise ValueError(f"knn_search_into: {nm} must be a contiguous {dt} [B,N,K] tensor on adv's device")
     if not (2 <= K <= min(64, N)):
         raise ValueError(f"knn_search_into: K={K} out of range [2, min(64, N={N})]")
+    if lengths is not None:
+        lp = _lengths_arg("knn_search_into", lengths, B, adv.device)
+        _lengths_host("knn_search_into", lengths, lengths_host, B, K, "cloud")
+        with torch.cuda.device(adv.device):
+            _lib.call("pc3d_knn_ragged_f32", p, bs, ps, cs, p, bs, ps, cs, B, N, N, K, d.data_ptr(), idx.data_ptr(),
+                      idx.data_ptr() if KNN_HINTS and N >= KNN_HINT_MIN_M else 0, lp, lp, _stream())
+        return d, idx
     with torch.cuda.device(adv.device):
         _lib.call("pc3d_knn_hint_f32", p, bs, ps, cs, p, bs, ps, cs, B, N, N, K, d.data_ptr(), idx.data_ptr(),
                   idx.data_ptr() if KNN_HINTS and N >= KNN_HINT_MIN_M else 0, _stream())
@@ -1140,11 +1191,16 @@ def nn_search_into(q, r, d, idx, cf=True):
 
 
 def knn_attack_update(adv, ori, g, m, v, step, lr, knn_d=None, knn_idx=None, nn_idx=None, c_chamfer=0.0, c_knn=0.0,
-                      alpha=1.05, budget=0.0, clip_mode="project_clip", normal=None, betas=(0.9, 0.999), eps=1e-8, cf=True):
+                      alpha=1.05, budget=0.0, clip_mode="project_clip", normal=None, betas=(0.9, 0.999), eps=1e-8, cf=True,
+                      lengths=None):
     """The kNN attack's update as one launch (see pc3d_knn_attack_update_f32): adv [B,3,N] (cf) is updated IN PLACE from
     the victim's gradient g, the self-kNN result knn_d / knn_idx [B,N,k+1] and the adv -> ori arg-mins nn_idx [B,N]. `step`
     (int32 device word or int) is only READ. c_chamfer / c_knn: float32 constants (the header says what they carry);
-    c_knn == 0 or no knn_idx: no kNN term. clip_mode: "clip" or "project_clip" (normal None: ori doubles as the normal)."""
+    c_knn == 0 or no knn_idx: no kNN term. clip_mode: "clip" or "project_clip" (normal None: ori doubles as the normal).
+    lengths (int32 [B] on the device, default None: the dense launch, unchanged): sample b counts lengths[b] points, its
+    further rows are padding and take the new point 0 (pc3d_knn_attack_update_ragged_f32); c_chamfer / c_knn are then per
+    cloud: float32 [B] (knn_attack_scales_ragged), tensors on adv's device (a captured loop keeps them) or arrays, which
+    are uploaded; nn_idx is required."""
     _, _, _, _, B, N = _pts(adv, cf, "adv")
     _check(g, "g"), _check(ori, "ori")
     for nm, t in (("m", m), ("v", v)):
@@ -1170,6 +1226,24 @@ def knn_attack_update(adv, ori, g, m, v, step, lr, knn_d=None, knn_idx=None, nn_
         step_dev, step_host = step.data_ptr(), 0
     else:
         step_dev, step_host = 0, int(step)
+    if lengths is not None:
+        lp = _lengths_arg("knn_attack_update", lengths, B, adv.device)
+        if nn_idx is None:
+            raise ValueError("knn_attack_update: lengths need nn_idx")
+        cs_ = []
+        for nm, c in (("c_chamfer", c_chamfer), ("c_knn", c_knn)):
+            if not isinstance(c, torch.Tensor):
+                c = torch.from_numpy(np.array(np.broadcast_to(np.asarray(c, dtype=np.float32), (B,)))).to(adv.device)
+            if c.dtype != torch.float32 or tuple(c.shape) != (B,) or not c.is_contiguous() or c.device != adv.device:
+                raise ValueError(f"knn_attack_update: with lengths, {nm} must be float32 [B] on adv's device")
+            cs_.append(c)
+        with torch.cuda.device(adv.device):
+            _lib.call("pc3d_knn_attack_update_ragged_f32", *_pv(adv, cf, "adv"), *_pv(ori, cf, "ori"),
+                      *_pv(normal, cf, "normal"), *_pv(g, cf, "g"), m.data_ptr(), v.data_ptr(), B, N, int(k), lp, _ptr(knn_d),
+                      _ptr(knn_idx), _ptr(nn_idx), float(lr), float(betas[0]), float(betas[1]), float(eps), float(budget),
+                      KNN_CLIP_MODES[clip_mode] if isinstance(clip_mode, str) else int(clip_mode), float(alpha),
+                      cs_[0].data_ptr(), cs_[1].data_ptr(), step_dev, step_host, _stream())
+        return adv
     with torch.cuda.device(adv.device):
         _lib.call("pc3d_knn_attack_update_f32", *_pv(adv, cf, "adv"), *_pv(ori, cf, "ori"), *_pv(normal, cf, "normal"),
                   *_pv(g, cf, "g"), m.data_ptr(), v.data_ptr(), B, N, int(k), _ptr(knn_d), _ptr(knn_idx), _ptr(nn_idx),
@@ -1188,6 +1262,16 @@ def knn_attack_scales(N, k, B, up_chamfer, up_knn):
         return c_ch, np.float32(0.0)
     wv = np.float32(1.0) / (np.float32(N) * np.float32(k))
     return c_ch, (np.float32(up_knn) / np.float32(B)) * wv
+
+
+def knn_attack_scales_ragged(lengths, k, G, w1, w2):
+    """(c_chamfer [B], c_knn [B]) float32 numpy for ops.knn_attack_update(lengths=...): per cloud of L = lengths[b] points
+    knn_attack_scales(L, k, G, np.float32(L) * w1, np.float32(L) * w2) — the values a run of that cloud alone prepares (the
+    reference's `* K` is the cloud's own point count). G: the size of the whole batch; w2 None or k == 0: no kNN term."""
+    pairs = [knn_attack_scales(int(L), k, G, np.float32(int(L)) * np.float32(w1),
+                               None if w2 is None else np.float32(int(L)) * np.float32(w2)) for L in lengths]
+    return (np.array([c for c, _ in pairs], dtype=np.float32).reshape(-1),
+            np.array([c for _, c in pairs], dtype=np.float32).reshape(-1))
 
 
 # ------------------------------------------------------------------------------------------------------

@@ -632,6 +632,20 @@ int pc3d_knn_hint_f32(const float* q, int64_t q_bs, int64_t q_ps, int64_t q_cs,
                       int B, int N, int M, int K, float* dists, int32_t* idx, const int32_t* hint, void* stream);
 int pc3d_knn_graph_hint_i32(const float* pts, int64_t p_bs, int64_t p_ps, int64_t p_cs, int B, int N, int K, int32_t* idx,
                             int32_t* idx_noself, int32_t* idx_first, int k2, const int32_t* hint, void* stream);
+/* pc3d_knn_hint_f32 on a batch of clouds of different sizes. len_q / len_r: int32 [B] on the device (they may be the same
+ * pointer), read by the kernel as data, so one captured launch serves any lengths. N and M stay the capacities: the row
+ * strides of dists / idx / hint ([B,N,K]) and the grid. Cloud b, with n = clamp(len_q[b], 0, N), m = clamp(len_r[b], 0, M):
+ * the queries i < n search the candidates 0 .. m-1 only; rows i >= n of dists / idx are neither read nor written. The
+ * tiling starts at candidate 0 and the tile does not depend on m, ties keep the lowest index: row i of cloud b equals, in
+ * every bit (distances and indices), pc3d_knn_f32 on that cloud alone at N = n, M = m. A hint entry >= m makes its
+ * wavefront run the unhinted scan; the result never depends on the hint.
+ * PRECONDITION m >= K for every cloud with n > 0: the lengths are device data, so the caller checks it (on a cloud that
+ * breaks it the rows hold unspecified values). Whatever the two buffers hold, nothing outside the buffers is read or
+ * written (the clamps). K <= M is checked against the capacity. */
+int pc3d_knn_ragged_f32(const float* q, int64_t q_bs, int64_t q_ps, int64_t q_cs,
+                        const float* r, int64_t r_bs, int64_t r_ps, int64_t r_cs,
+                        int B, int N, int M, int K, float* dists, int32_t* idx, const int32_t* hint,
+                        const int32_t* len_q, const int32_t* len_r, void* stream);
 /* Values only, small k: dists [B,N,k1] = the k1 smallest squared distances of every query, ascending, 2 <= k1 <= 9,
  * k1 <= M; no indices. Bit for bit the dists of pc3d_knn_f32 (same distance arithmetic, same key order, NaN stored as
  * +inf, the same far sentinels up to the next multiple of 64 candidates): the k1 smallest keys of a multiset do not
@@ -1091,6 +1105,27 @@ int pc3d_knn_attack_update_f32(float* adv, int64_t a_bs, int64_t a_ps, int64_t a
                                const int32_t* nn_idx, double lr, double beta1, double beta2, double eps,
                                float budget, int clip_mode, float alpha, float c_chamfer, float c_knn,
                                const int32_t* step_dev, int step_host, void* stream);
+/* pc3d_knn_attack_update_f32 on a batch of clouds of different sizes: sample b counts L = lengths[b] points (int32 [B] on
+ * the device, read as data, clamped to [1, N]) and has its own constants c_chamfer[b] / c_knn[b] (float32 [B] on the
+ * device: what a run of that cloud alone prepares from its own point count); its kNN term exists when k >= 1 and
+ * c_knn[b] != 0. N is the capacity: the stride of knn_d / knn_idx ([B,N,k+1]) and nn_idx ([B,N]) and the size of the LDS
+ * arrays (N <= PC3D_KNN_ATTACK_UPDATE_MAX_POINTS). Every loop over points, the outlier statistics' / L and / (L - 1) and
+ * the index clamps [0, L-1] run over L with the dense kernel's thread-to-point mapping and summation order: rows < L of
+ * adv / m / v have the bits of the dense launch at N = L on that cloud alone, and with all lengths = N and equal constants
+ * every output equals pc3d_knn_attack_update_f32's. Rows >= L of adv, g, knn_d, knn_idx, nn_idx and normal are never read
+ * (they may hold NaN), their m / v are not written, and adv's take the NEW point 0: the padding the victim's passes and
+ * the adv -> ori search of the loop rely on. knn_d / knn_idx: from pc3d_knn_ragged_f32 on the same lengths.
+ * PRECONDITION L >= k + 1 where the kNN term exists (the caller's to check; indices are clamped either way). nn_idx must
+ * not be NULL. */
+int pc3d_knn_attack_update_ragged_f32(float* adv, int64_t a_bs, int64_t a_ps, int64_t a_cs,
+                                      const float* ori, int64_t o_bs, int64_t o_ps, int64_t o_cs,
+                                      const float* normal, int64_t n_bs, int64_t n_ps, int64_t n_cs,
+                                      const float* g, int64_t g_bs, int64_t g_ps, int64_t g_cs, float* m, float* v,
+                                      int B, int N, int k, const int32_t* lengths, const float* knn_d,
+                                      const int32_t* knn_idx, const int32_t* nn_idx, double lr, double beta1,
+                                      double beta2, double eps, float budget, int clip_mode, float alpha,
+                                      const float* c_chamfer, const float* c_knn, const int32_t* step_dev,
+                                      int step_host, void* stream);
 
 /* The additional-experiments CW (attack/additional_exp/CW_attack.py) around ONE stacked victim pass per iteration. Every
  * point tensor is a contiguous [B,3,K]; K <= PC3D_EOT_MAX_POINTS, 0 <= E <= PC3D_EOT_MAX_VIEWS views.
