@@ -172,6 +172,12 @@ SIGNATURES = {
     + [_P, _P, _P] + [_P],
     "pc3d_pointmlp3_max_fwd_screen_dbg_prep_f32": _PTS + [_I, _I] + [_P, _P, _P, _P, _I, _P] + [_P] * 6 + [_I, _I, _I, _I]
     + [_P] * 6 + [_P, _P, _P, _I] + [_P, _P, _P] + [_P],
+    "pc3d_pointmlp3_w3_prepare_h_f32": [_P, _I, _P, _P, _P, _P],
+    "pc3d_pointmlp3_max_fwd_h_f32": _PTS + [_I, _I] + [_P] * 7 + [_I, _I, _I, _I] + [_P] * 6 + [_P] * 5 + [_P],
+    "pc3d_pointmlp3_max_fwd_h_th_f32": _PTS + [_I, _I] + [_P, _P, _P, _I, _P] + [_P] * 6 + [_I, _I, _I, _I] + [_P] * 6
+    + [_P] * 5 + [_P],
+    "pc3d_pointmlp3_max_fwd_screen_dbg_h_f32": _PTS + [_I, _I] + [_P, _P, _P, _P, _I, _P] + [_P] * 6 + [_I, _I, _I, _I]
+    + [_P] * 6 + [_P, _P, _P, _I] + [_P] * 5 + [_P],
     "pc3d_linear_pre_f32": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P],
     "pc3d_pointmlp3_max_bwd_f32": _PTS + [_I, _I] + [_P] * 7 + [_I, _I, _I] + [_P, _P, _P, _P] + _PTS + [_P, _I, _P],
     "pc3d_pointmlp3_max_bwd_twolist_f32": _PTS + [_I, _I] + [_P] * 7 + [_I, _I, _I] + [_P, _P, _P, _P] + _PTS + [_P, _I, _P],

@@ -1246,7 +1246,7 @@ static int pm_fwd_launch(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_c
                          const float* b3, int C1, int C2, int C3, int relu_last, float* part_val, int32_t* part_idx,
                          float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2, void* stream,
                          bool exact = false, int32_t* stats = nullptr, float* dbg_S = nullptr, float* dbg_E = nullptr,
-                         int stop_after = 0, const PMScreenPrep* prep = nullptr) {
+                         int stop_after = 0, const PMScreenPrep* prep = nullptr, const PMScreenPrepH* hprep = nullptr) {
   PC3D_REQUIRE(B >= 0 && N >= 1, "pc3d_pointmlp3_max_fwd_f32: bad sizes B=%d N=%d", B, N);
   PC3D_REQUIRE(C1 == PM_C1 && C2 == PM_C2 && C3 >= 32 && C3 % 32 == 0 && C3 <= PM_MAXC3F,
                "pc3d_pointmlp3_max_fwd_f32: unsupported widths %d/%d/%d (need 64/128/multiple of 32 <= 1024)", C1, C2, C3);
@@ -1263,11 +1263,11 @@ static int pm_fwd_launch(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_c
               th_in, th_W, th_b, th_K, th_out};
   hipStream_t st = as_stream(stream);
   // Layer 3 screened on bf16 MFMA and rechecked exactly (pointmlp_screen.hip: the same bits) at every shape this entry
-  // accepts, from the prepared image of W3 when the caller passes one; the exact kernel on request, and when the screened
-  // one cannot be launched yet (see pm_fwd_screen_launch).
+  // accepts, from the prepared image of W3 when the caller passes one (with its fp16 image, hprep: the one-product fp16
+  // screen); the exact kernel on request, and when the screened one cannot be launched yet (see pm_fwd_screen_launch).
   int rc = 1;
   if (!exact) {
-    rc = pm_fwd_screen_launch(a, B, stream, stats, dbg_S, dbg_E, stop_after, prep);
+    rc = pm_fwd_screen_launch(a, B, stream, stats, dbg_S, dbg_E, stop_after, prep, hprep);
     if (rc < 0) return rc;
   }
   if (rc != 0) hipLaunchKernelGGL(pointmlp3_max_fwd_kernel, dim3(ntiles, B), dim3(PM_FT), 0, st, a);
@@ -1421,6 +1421,80 @@ extern "C" int pc3d_pointmlp3_max_fwd_screen_dbg_prep_f32(const float* x, int64_
   return pm_fwd_launch(x, x_bs, x_ps, x_cs, B, N, T, th_in, th_W, th_b, th_K, T_out, W1, b1, W2, b2, W3, b3, C1, C2, C3,
                        relu_last, part_val, part_idx, pooled, argidx, mask1, mask2, stream, false, stats, dbg_S, dbg_E,
                        stop_after, &q);
+}
+
+// ---- the same launches with layer 3 screened by ONE scaled fp16 product (the H form of pointmlp_screen.hip), fed from
+// the bf16 image's w3_nw / w3_q and the fp16 image w3_h / w3_cw that pc3d_pointmlp3_w3_prepare_h_f32 made from them. The
+// bf16 image itself is passed along: it serves when the H instantiation's first use on a device falls into a capture.
+extern "C" int pc3d_pointmlp3_w3_prepare_h_f32(const float* W3, int C3, const float* w3_nw, void* w3_h, float* w3_cw,
+                                               void* stream) {
+  PC3D_REQUIRE(C3 >= 32 && C3 % 32 == 0 && C3 <= PM_MAXC3F, "pc3d_pointmlp3_w3_prepare_h_f32: C3 = %d (need a multiple of 32 <= 1024)", C3);
+  PC3D_REQUIRE(W3 && w3_nw && w3_h && w3_cw, "pc3d_pointmlp3_w3_prepare_h_f32: null pointer");
+  pm_w3_prepare_h_launch(W3, C3, w3_nw, w3_h, w3_cw, stream);
+  PC3D_LAUNCH_CHECK("pc3d_pointmlp3_w3_prepare_h_f32");
+  return PC3D_OK;
+}
+
+static PMScreenPrepH pm_prep_h(const void* w3_h, const float* w3_cw, const float* w3_nw, const float* w3_q) {
+  return PMScreenPrepH{reinterpret_cast<decltype(PMScreenPrepH::w3_h)>(w3_h), w3_cw, w3_nw, reinterpret_cast<const float4*>(w3_q)};
+}
+
+extern "C" int pc3d_pointmlp3_max_fwd_h_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                            const float* T, const float* W1, const float* b1, const float* W2,
+                                            const float* b2, const float* W3, const float* b3, int C1, int C2, int C3,
+                                            int relu_last, float* part_val, int32_t* part_idx, float* pooled,
+                                            int32_t* argidx, uint64_t* mask1, uint32_t* mask2, const void* w3_bf,
+                                            const float* w3_nw, const float* w3_q, const void* w3_h, const float* w3_cw,
+                                            void* stream) {
+  PC3D_REQUIRE(w3_bf && w3_nw && w3_q && w3_h && w3_cw, "pc3d_pointmlp3_max_fwd_h_f32: both prepared images are needed");
+  const PMScreenPrep q = pm_prep(w3_bf, w3_nw, w3_q);
+  const PMScreenPrepH qh = pm_prep_h(w3_h, w3_cw, w3_nw, w3_q);
+  return pm_fwd_launch(x, x_bs, x_ps, x_cs, B, N, T, nullptr, nullptr, nullptr, 0, nullptr, W1, b1, W2, b2, W3, b3, C1, C2,
+                       C3, relu_last, part_val, part_idx, pooled, argidx, mask1, mask2, stream, false, nullptr, nullptr,
+                       nullptr, 0, &q, &qh);
+}
+
+extern "C" int pc3d_pointmlp3_max_fwd_h_th_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                               const float* th_in, const float* th_W, const float* th_b, int th_K,
+                                               float* T_out, const float* W1, const float* b1, const float* W2,
+                                               const float* b2, const float* W3, const float* b3, int C1, int C2, int C3,
+                                               int relu_last, float* part_val, int32_t* part_idx, float* pooled,
+                                               int32_t* argidx, uint64_t* mask1, uint32_t* mask2, const void* w3_bf,
+                                               const float* w3_nw, const float* w3_q, const void* w3_h,
+                                               const float* w3_cw, void* stream) {
+  PC3D_REQUIRE(th_in && th_W && th_b && T_out && th_K >= 1,
+               "pc3d_pointmlp3_max_fwd_h_th_f32: the transform head needs its input, weights [9,K], bias [9] and T_out");
+  PC3D_REQUIRE(w3_bf && w3_nw && w3_q && w3_h && w3_cw, "pc3d_pointmlp3_max_fwd_h_th_f32: both prepared images are needed");
+  const PMScreenPrep q = pm_prep(w3_bf, w3_nw, w3_q);
+  const PMScreenPrepH qh = pm_prep_h(w3_h, w3_cw, w3_nw, w3_q);
+  return pm_fwd_launch(x, x_bs, x_ps, x_cs, B, N, nullptr, th_in, th_W, th_b, th_K, T_out, W1, b1, W2, b2, W3, b3, C1, C2,
+                       C3, relu_last, part_val, part_idx, pooled, argidx, mask1, mask2, stream, false, nullptr, nullptr,
+                       nullptr, 0, &q, &qh);
+}
+
+// stats / dbg_S / dbg_E / stop_after as in pc3d_pointmlp3_max_fwd_screen_dbg_f32, of the H form; dbg_S and dbg_E come
+// back in the unscaled domain (S 2^-(sa + sw), E 2^-(sa + sw))
+extern "C" int pc3d_pointmlp3_max_fwd_screen_dbg_h_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B,
+                                                       int N, const float* T, const float* th_in, const float* th_W,
+                                                       const float* th_b, int th_K, float* T_out, const float* W1,
+                                                       const float* b1, const float* W2, const float* b2, const float* W3,
+                                                       const float* b3, int C1, int C2, int C3, int relu_last,
+                                                       float* part_val, int32_t* part_idx, float* pooled, int32_t* argidx,
+                                                       uint64_t* mask1, uint32_t* mask2, int32_t* stats, float* dbg_S,
+                                                       float* dbg_E, int stop_after, const void* w3_bf, const float* w3_nw,
+                                                       const float* w3_q, const void* w3_h, const float* w3_cw,
+                                                       void* stream) {
+  PC3D_REQUIRE(stats != nullptr, "pc3d_pointmlp3_max_fwd_screen_dbg_h_f32: stats [B, ntiles, 2] is required");
+  PC3D_REQUIRE((dbg_S == nullptr) == (dbg_E == nullptr), "pc3d_pointmlp3_max_fwd_screen_dbg_h_f32: dbg_S and dbg_E go together");
+  PC3D_REQUIRE(stop_after >= 0 && stop_after <= 3, "pc3d_pointmlp3_max_fwd_screen_dbg_h_f32: stop_after = %d", stop_after);
+  PC3D_REQUIRE(th_in == nullptr || (T == nullptr && th_W && th_b && T_out && th_K >= 1),
+               "pc3d_pointmlp3_max_fwd_screen_dbg_h_f32: T or a complete transform head, not both");
+  PC3D_REQUIRE(w3_bf && w3_nw && w3_q && w3_h && w3_cw, "pc3d_pointmlp3_max_fwd_screen_dbg_h_f32: both prepared images are needed");
+  const PMScreenPrep q = pm_prep(w3_bf, w3_nw, w3_q);
+  const PMScreenPrepH qh = pm_prep_h(w3_h, w3_cw, w3_nw, w3_q);
+  return pm_fwd_launch(x, x_bs, x_ps, x_cs, B, N, T, th_in, th_W, th_b, th_K, T_out, W1, b1, W2, b2, W3, b3, C1, C2, C3,
+                       relu_last, part_val, part_idx, pooled, argidx, mask1, mask2, stream, false, stats, dbg_S, dbg_E,
+                       stop_after, &q, &qh);
 }
 
 // which kernel the default entries launch (pc3d_pointmlp3_max_bwd_f32 / _update_f32); every form stays reachable by name

@@ -198,9 +198,20 @@ struct PMScreenPrep {
   const float* w3_nw;                                        // [C3]
   const float4* w3_q;                                        // [32][C3]
 };
+// hprep: the fp16 image of the same W3 (pm_w3_prepare_h_launch), or null. With it the H form runs: layer 3 screened with
+// ONE scaled fp16 product per k-step (pointmlp_screen_h_bound.h), the same recheck, the same bits in every output; it needs
+// neither prep nor its w3_bf. dbg_S / dbg_E of that form are written in the unscaled domain.
+struct PMScreenPrepH {
+  const __attribute__((ext_vector_type(8))) _Float16* w3_h;  // [C3/32][8][64] x 8 fp16: W3[32 cb + r][16 t + 8 h + 0..7] 2^sw
+  const float* w3_cw;                                        // [C3] the channel's factor of E, scaled; +inf: not screened
+  const float* w3_nw;                                        // [C3] (read by the dump instantiation only)
+  const float4* w3_q;                                        // [32][C3]
+};
 int pm_fwd_screen_launch(const PMFwdArgs& a, int B, void* stream, int32_t* stats, float* dbg_S, float* dbg_E,
-                         int stop_after, const PMScreenPrep* prep);
+                         int stop_after, const PMScreenPrep* prep, const PMScreenPrepH* hprep = nullptr);
 // w3_bf (C3 * 512 B), w3_nw (C3 floats), w3_q (C3 * 128 floats) from the folded fp32 W3 [C3,128]
 int pm_w3_prepare_launch(const float* W3, int C3, void* w3_bf, float* w3_nw, float* w3_q, void* stream);
+// w3_h (C3 * 256 B) and w3_cw (C3 floats) from W3 and the w3_nw that pm_w3_prepare_launch wrote for it
+int pm_w3_prepare_h_launch(const float* W3, int C3, const float* w3_nw, void* w3_h, float* w3_cw, void* stream);
 
 }  // namespace pc3d

@@ -30,9 +30,13 @@
 //          registers from two contiguous 512-B runs per load), over the channel's candidates in s_pts[c][PMS_PCAP]; the
 //          winner's key stays in registers: no list, no scan, no LDS atomics, no decode pass. A block in which a channel
 //          has more than PMS_PCAP candidates runs the exact block.
+//
+// H (further down): PREP with ONE fp16 product per k-step in place of the three bf16 ones, operands scaled by powers of
+// two into fp16's range; a bound eight times wider, sixteen slots per channel, the same recheck and the same bits.
 #include "pc3d_common.h"
 #include "pointmlp_body.h"
 #include "pointmlp_screen_bound.h"
+#include "pointmlp_screen_h_bound.h"
 
 namespace pc3d {
 
@@ -591,6 +595,320 @@ __global__ __launch_bounds__(PM_FT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
   }
 }
 
+// ---- H: the prepared form with ONE fp16 product per k-step (pointmlp_screen_h_bound.h). Same prologue, grid, tile,
+// select, recheck chain, key order and exact block as PREP; what differs:
+//  operands  a' = h2 2^sa, one exponent per TILE (the tile's largest na lands in [2^13, 2^14): one LDS max in the norms
+//            phase), as one fp16 image in LDS; w' = W3 2^sw[c] from the prepared image w3_h (pms_w3_prepare_h_kernel).
+//            Powers of two: the scaling is exact, and within a channel it moves S, E and v alike, so L, the flags and the
+//            candidates are formed in the scaled domain and nothing is scaled back.
+//  bound     E = s_na[p] cw, s_na[p] = na 2^sa + 1, cw = w3_cw[c] = PMH_C nw 2^sw (+inf: the channel's norm failed
+//            pms_norm_ok; its block runs the exact block, like a tile with a norm that failed).
+//  slots     PMH_PCAP = 16 candidates per (tile, channel): the bound is 8x the three-product one, and the LDS of the
+//            second image is free.
+using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
+
+constexpr int PMH_PCAP = 16;
+// H's dynamic LDS: h2 + xs | na [128] f32 | the tile's largest na (16 B) | pts [1024][PMH_PCAP] u8 | fp16 h2 = 120,848 B
+constexpr size_t PMH_AMAX_OFF = (size_t)PM_FWD_LDS_FLOATS * 4 + PM_TP * 4;
+constexpr size_t PMH_PTS_OFF = PMH_AMAX_OFF + 16;
+constexpr size_t PMH_A16_OFF = PMH_PTS_OFF + (size_t)PM_MAXC3F * PMH_PCAP;
+constexpr size_t PMH_LDS_BYTES = PMH_A16_OFF + (size_t)PM_TP * PMS_LDA * 2;
+static_assert(PMH_LDS_BYTES + 1024 <= 160 * 1024 && PMH_A16_OFF % 16 == 0 && PMH_PTS_OFF % 16 == 0, "H's LDS map");
+static_assert(PMH_PCAP >= 4 && PMH_PCAP <= 31 && 5 * PMS_SLOTS <= 32, "a channel's candidate count is kept in 5 bits per slot");
+static_assert(PM_TP <= 256, "a candidate point is one byte");
+
+__global__ __launch_bounds__(64) void pms_w3_prepare_h_kernel(const float* __restrict__ W3, const float* __restrict__ w3_nw,
+                                                              f16x8* __restrict__ w3_h, float* __restrict__ w3_cw) {
+  const int cb = blockIdx.x, lane = threadIdx.x;
+  const int r = lane & 31, h = lane >> 5;
+  const float nw = w3_nw[cb * 32 + r];
+  const bool ok = pms_norm_ok(nw);
+  const float two_sw = ok ? pmh_pow2(pmh_scale_exp(nw)) : 0.f;    // not screened: zeros, never multiplied
+  const float* wrow = W3 + (int64_t)(cb * 32 + r) * PM_C2 + 8 * h;
+#pragma unroll
+  for (int t = 0; t < PM_C2 / 16; ++t) {
+    const float4 lo = *reinterpret_cast<const float4*>(wrow + 16 * t), hi = *reinterpret_cast<const float4*>(wrow + 16 * t + 4);
+    const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    f16x8 o;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) o[i] = ok ? (_Float16)(v[i] * two_sw) : (_Float16)0.f;   // round to nearest even
+    w3_h[(cb * (PM_C2 / 16) + t) * 64 + lane] = o;
+  }
+  if (h == 0) w3_cw[cb * 32 + r] = ok ? pmh_cw(nw, two_sw) : __builtin_inff();
+}
+
+template <bool DBG, bool DUMP>
+__global__ __launch_bounds__(PM_FT) __attribute__((amdgpu_waves_per_eu(2, 2))) void pointmlp3_max_fwd_screen_h_kernel(
+    PMFwdArgs a, PMScreenDbg d, PMScreenPrepH w3) {
+  extern __shared__ __attribute__((aligned(16))) float pms_lds[];
+  float* h2 = pms_lds;                                                              // [128][132] fp32, kept to the end
+  float* s_na = pms_lds + PM_FWD_LDS_FLOATS;                                        // [128] na 2^sa + 1 (+inf: no such point)
+  unsigned* s_amax = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(pms_lds) + PMH_AMAX_OFF);
+  unsigned char* s_pts = reinterpret_cast<unsigned char*>(pms_lds) + PMH_PTS_OFF;   // [C3][PMH_PCAP] a channel's candidates
+  _Float16* s_a16 = reinterpret_cast<_Float16*>(reinterpret_cast<char*>(pms_lds) + PMH_A16_OFF);   // [128][PMS_LDA]
+  const int tile = blockIdx.x, b = blockIdx.y;
+  const int n0 = tile * PM_TP;
+  const int nvalid = a.N - n0;            // >= 1
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = lane & 31, h = lane >> 5;
+  const int64_t obase = ((int64_t)b * a.ntiles + tile) * a.C3;
+  const int nblk = a.C3 / 32;
+  const int nslots = wave < nblk ? (nblk - wave + PM_FT / 64 - 1) / (PM_FT / 64) : 0;   // <= PMS_SLOTS
+  // the wave's first block of B operands and its first cw: they depend on nothing the prologue computes
+  const f16x8* wb = w3.w3_h + lane;
+  f16x8 q[PM_C2 / 16];
+  float cw_next = 0.f;
+  if (nslots > 0) {
+#pragma unroll
+    for (int t = 0; t < PM_C2 / 16; ++t) q[t] = wb[(wave * (PM_C2 / 16) + t) * 64];
+    cw_next = w3.w3_cw[wave * 32 + r];
+  }
+  if (threadIdx.x == 0) *s_amax = 0u;     // outside what the prologue touches; its barriers publish it
+  pm_fwd_prologue(a, pms_lds);
+
+  // ---- one norm per point (4 threads per point, 32 k each, fixed order: PREP's na in every bit), the tile's largest,
+  // then h2's fp16 image with the tile's scale
+  bool bad;
+  float na;
+  float4 hv[8];
+  const int p = threadIdx.x >> 2, pq = threadIdx.x & 3;
+  {
+    const float* row = h2 + p * PM_LD2 + 32 * pq;
+    float ss = 0.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const float4 v = *reinterpret_cast<const float4*>(row + 8 * t), u = *reinterpret_cast<const float4*>(row + 8 * t + 4);
+      ss = __builtin_fmaf(v.x, v.x, ss), ss = __builtin_fmaf(v.y, v.y, ss);
+      ss = __builtin_fmaf(v.z, v.z, ss), ss = __builtin_fmaf(v.w, v.w, ss);
+      ss = __builtin_fmaf(u.x, u.x, ss), ss = __builtin_fmaf(u.y, u.y, ss);
+      ss = __builtin_fmaf(u.z, u.z, ss), ss = __builtin_fmaf(u.w, u.w, ss);
+      hv[2 * t] = v, hv[2 * t + 1] = u;
+    }
+    ss += __shfl_xor(ss, 1, 64);
+    ss += __shfl_xor(ss, 2, 64);
+    na = pms_norm_up(ss);
+    bad = !pms_norm_ok(na);               // NaN, inf or huge h2 anywhere in the tile: no screen for this tile
+    // all 128 rows count, the ones past the end of a ragged tile too: no image entry can leave fp16's range
+    const float wmax = wave_max(na);      // positive floats order as their bits do
+    if (lane == 0) atomicMax(s_amax, __builtin_bit_cast(unsigned, wmax));
+  }
+  const bool tile_bad = __syncthreads_or(bad ? 1 : 0) != 0;
+  float two_sa = 1.f;
+  if (!tile_bad) {                        // (uniform)
+    const float amax = __builtin_bit_cast(float, *s_amax);          // in [2^-45, 2^60]
+    two_sa = pmh_pow2(pmh_scale_exp(amax));
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const float4 v = hv[2 * t], u = hv[2 * t + 1];
+      const float x[8] = {v.x, v.y, v.z, v.w, u.x, u.y, u.z, u.w};
+      f16x8 o;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) o[i] = (_Float16)(x[i] * two_sa);   // round to nearest even (not cvt_pkrtz)
+      *reinterpret_cast<f16x8*>(s_a16 + p * PMS_LDA + 32 * pq + 8 * t) = o;
+    }
+    if (pq == 0) s_na[p] = p < nvalid ? pmh_na(na, two_sa) : __builtin_inff();   // past the end: see pms_lower
+  }
+  __syncthreads();
+  if (DBG && d.stop_after == 1) return;
+
+  unsigned vmask[2] = {0u, 0u};           // the lane's 64 points that exist (all of them but in a ragged last tile)
+#pragma unroll
+  for (int pt = 0; pt < 4; ++pt)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) vmask[pt >> 1] |= (pms_point(pt, e, h) < nvalid) ? (1u << (16 * (pt & 1) + e)) : 0u;
+  unsigned screened = 0u, cnts = 0u;      // bit slot: screened; bits 5 slot .. + 4: candidates of the lane's channel r
+  int ncand = 0, nfall = 0;
+  float sink = 0.f;
+#pragma unroll 1
+  for (int slot = 0; slot < nslots; ++slot) {
+    const int cb = wave + (PM_FT / 64) * slot;
+    const int nxt = slot + 1 < nslots ? cb + PM_FT / 64 : cb;   // past the wave's last block: a valid address, unused
+    const float cw = cw_next;             // the next one is loaded behind the products: the select hides its round trip
+    // (uniform) a non-finite or huge h2 in the tile, or such a W3 row in the block (its prepared cw says so)
+    bool fall = tile_bad || __builtin_amdgcn_ballot_w64(!pmh_cw_ok(cw)) != 0ull;
+    if (!fall) {
+      f32x16 acc[4];
+#pragma unroll
+      for (int pt = 0; pt < 4; ++pt)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[pt][e] = 0.f;
+#pragma unroll
+      for (int t = 0; t < PM_C2 / 16; ++t) {
+        const f16x8 bq = q[t];
+        q[t] = wb[(nxt * (PM_C2 / 16) + t) * 64];   // the ring: the same k-step of the wave's next block
+#pragma unroll
+        for (int pt = 0; pt < 4; ++pt) {   // A: lane (r, h) holds h2'[32 pt + r][16 t + 8 h + 0..7]
+          const f16x8 ah = *reinterpret_cast<const f16x8*>(s_a16 + (pt * 32 + r) * PMS_LDA + 16 * t + 8 * h);
+          acc[pt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bq, acc[pt], 0, 0, 0);
+        }
+      }
+      // the order of the 8 loads, 32 LDS reads and 32 MFMAs above, pinned as in PREP: a k-step's load leads it and lands
+      // a whole block later; the A operands are read two (pt) groups ahead
+      __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);        // 2 DS read
+#pragma unroll
+      for (int g = 0; g < 4 * (PM_C2 / 16); ++g) {
+        if (g % 4 == 0) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // 1 VMEM read
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // 1 MFMA
+        if (g + 2 < 4 * (PM_C2 / 16)) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      }
+      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);        // the next block's cw
+      cw_next = w3.w3_cw[nxt * 32 + r];
+      if (DBG && d.stop_after == 2) {
+#pragma unroll
+        for (int pt = 0; pt < 4; ++pt)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) sink += acc[pt][e];
+        continue;
+      }
+      if (DUMP && d.dbg_S != nullptr) {   // unscaled: S 2^-(sa + sw), E 2^-(sa + sw) (exact but for underflow)
+        int c3v = a.C3;
+        unsigned vm[2] = {vmask[0], vmask[1]};
+        asm volatile("" : "+v"(c3v), "+v"(vm[0]), "+v"(vm[1]));   // opaque: nothing of the 64 stores is hoisted out of the block loop
+        const int64_t o0 = ((int64_t)b * a.N + n0) * a.C3 + cb * 32 + r;
+        const float back_a = 1.f / two_sa, back_w = 1.f / pmh_pow2(pmh_scale_exp(w3.w3_nw[cb * 32 + r]));
+#pragma unroll
+        for (int pt = 0; pt < 4; ++pt)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) {
+            const int pp = pms_point(pt, e, h);
+            if ((vm[pt >> 1] >> (16 * (pt & 1) + e)) & 1u) {
+              d.dbg_S[o0 + (int64_t)pp * c3v] = acc[pt][e] * back_a * back_w;
+              d.dbg_E[o0 + (int64_t)pp * c3v] = pms_E(s_na[pp], cw) * back_a * back_w;
+            }
+          }
+      }
+      unsigned flags[2];
+      float L = pms_lower(acc, s_na, cw, h);
+      L = fmaxf(L, __shfl_xor(L, 32, 64));
+      pms_flags(acc, s_na, cw, h, L, flags);
+      flags[0] &= vmask[0], flags[1] &= vmask[1];
+      const int cnt = __builtin_popcount(flags[0]) + __builtin_popcount(flags[1]);
+      const int other = __shfl_xor(cnt, 32, 64);   // the channel's other half of the points
+      if (__builtin_amdgcn_ballot_w64(cnt + other > PMH_PCAP) != 0ull) {
+        fall = true;                      // (uniform) a channel with more candidates than its slots: the exact block instead
+      } else {
+        unsigned char* mine = s_pts + (cb * 32 + r) * PMH_PCAP + (h ? other : 0);   // h = 1 writes behind h = 0's
+#pragma unroll
+        for (int wd = 0; wd < 2; ++wd) {
+          unsigned f = flags[wd];
+          while (f) {
+            const int bit = __builtin_ctz(f);
+            f &= f - 1;
+            *mine++ = (unsigned char)pms_point(2 * wd + (bit >> 4), bit & 15, h);
+          }
+        }
+        cnts |= (unsigned)(cnt + other) << (5 * slot);
+        screened |= 1u << slot;
+        if (DBG) ncand += h ? 0 : cnt + other;
+      }
+    } else {                              // not screened: the ring moves on to the next block
+#pragma unroll
+      for (int t = 0; t < PM_C2 / 16; ++t) q[t] = wb[(nxt * (PM_C2 / 16) + t) * 64];
+      cw_next = w3.w3_cw[nxt * 32 + r];
+    }
+    if (fall) {
+      pms_exact_block(h2, a.W3, a.b3, cb, n0, a.N, a.part_val + obase, a.part_idx + obase);
+      ++nfall;
+    }
+  }
+  if (DBG && d.stop_after == 2) {
+    if (sink == 12345.678f) a.part_val[obase] = sink;   // keeps the products alive
+    return;
+  }
+  if (DBG && d.stats != nullptr) {
+    ncand = wave_sum(ncand);
+    if (lane == 0) {
+      int32_t* st = d.stats + ((int64_t)b * a.ntiles + tile) * 2;
+      if (ncand) atomicAdd(st, ncand);
+      if (nfall) atomicAdd(st + 1, nfall);
+    }
+  }
+  if (DBG && d.stop_after == 3) {
+    if (cnts == 0xffffffffu) a.part_val[obase] = 0.f;
+    return;
+  }
+
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the channels' candidate points, written by other lanes
+  // ---- recheck by channel, as in PREP: the exact kernel's chain from the UNSCALED fp32 h2 and fp32 row
+#pragma unroll 1
+  for (int j = 0; 2 * j < nslots; ++j) {
+    const int sl = 2 * j + h;
+    const bool live = sl < nslots && ((screened >> sl) & 1u);
+    const int n = live ? (int)((cnts >> (5 * sl)) & 31u) : 0;
+    if (__builtin_amdgcn_ballot_w64(n > 0) == 0ull) continue;   // (uniform)
+    const int c = (wave + (PM_FT / 64) * (live ? sl : 0)) * 32 + r;   // an idle lane: a valid row, unused
+    float4 wv[PM_C2 / 4];               // the whole row in flight at once: one round trip per trip
+#pragma unroll
+    for (int t = 0; t < PM_C2 / 4; ++t) wv[t] = w3.w3_q[(int64_t)t * a.C3 + c];
+    unsigned long long key = 0ull;
+#pragma unroll 1
+    for (int i = 0; i < PMH_PCAP; ++i) {
+      if (__builtin_amdgcn_ballot_w64(i < n) == 0ull) break;    // (uniform)
+      const int pc = i < n ? s_pts[c * PMH_PCAP + i] : 0;
+      const float4* ar = reinterpret_cast<const float4*>(h2 + pc * PM_LD2);
+      __builtin_amdgcn_sched_barrier(0);
+      float v = 0.f;
+#pragma unroll
+      for (int t = 0; t < PM_C2 / 8; ++t) {
+        const float4 a0 = ar[2 * t], a1 = ar[2 * t + 1];
+        const float4 w0 = wv[2 * t], w1 = wv[2 * t + 1];
+        v = __builtin_fmaf(a0.x, w0.x, v), v = __builtin_fmaf(a1.x, w1.x, v);
+        v = __builtin_fmaf(a0.y, w0.y, v), v = __builtin_fmaf(a1.y, w1.y, v);
+        v = __builtin_fmaf(a0.z, w0.z, v), v = __builtin_fmaf(a1.z, w1.z, v);
+        v = __builtin_fmaf(a0.w, w0.w, v), v = __builtin_fmaf(a1.w, w1.w, v);
+      }
+      // hipcc reads the h2 row two float4 ahead of the chain and then waits out an LDS round trip (64 lanes, 64 rows)
+      // per k-group of 8: pinned four groups ahead instead (32 VGPRs), the chain's order untouched
+      __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);        // 8 DS read
+#pragma unroll
+      for (int g = 0; g < PM_C2 / 8; ++g) {
+        __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);      // 8 VALU: the group's fmaf
+        if (g + 4 < PM_C2 / 8) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+      }
+      const unsigned vb = __builtin_bit_cast(unsigned, v);
+      const unsigned zb = (v == 0.f) ? 0u : vb;
+      const unsigned ord = (zb & 0x80000000u) ? ~zb : (zb | 0x80000000u);
+      const unsigned low = ((unsigned)(127 - pc) << 1) | ((vb == 0x80000000u) ? 1u : 0u);
+      const unsigned long long k = ((unsigned long long)ord << 32) | low;
+      if (i < n && k > key) key = k;
+    }
+    if (live) {
+      const unsigned ord = (unsigned)(key >> 32), low = (unsigned)key;
+      unsigned vb = (ord & 0x80000000u) ? (ord & 0x7fffffffu) : ~ord;
+      if (low & 1u) vb = 0x80000000u;
+      a.part_val[obase + c] = __builtin_bit_cast(float, vb) + a.b3[c];
+      a.part_idx[obase + c] = n0 + 127 - (int)((low >> 1) & 127u);
+    }
+  }
+}
+
+template <bool DBG, bool DUMP>
+static int pms_launch_h_t(const PMFwdArgs& a, int B, hipStream_t st, const PMScreenDbg& d, const PMScreenPrepH& q) {
+  static bool done[64] = {};
+  int dev = 0;
+  PC3D_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "pointmlp3 screen: no current device");
+  auto kernel = pointmlp3_max_fwd_screen_h_kernel<DBG, DUMP>;
+  if (!done[dev]) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
+      (void)hipGetLastError();
+      return 1;
+    }
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)PMH_LDS_BYTES);
+    PC3D_REQUIRE(e == hipSuccess, "pointmlp3 screen: hipFuncSetAttribute(MaxDynamicSharedMemorySize): %s", hipGetErrorString(e));
+    done[dev] = true;
+  }
+  hipLaunchKernelGGL(kernel, dim3(a.ntiles, B), dim3(PM_FT), PMH_LDS_BYTES, st, a, d, q);
+  return 0;
+}
+
+static int pms_launch_h(const PMFwdArgs& a, int B, hipStream_t st, const PMScreenDbg& d, const PMScreenPrepH& q) {
+  if (d.dbg_S || d.dbg_E) return pms_launch_h_t<true, true>(a, B, st, d, q);
+  if (d.stats || d.stop_after) return pms_launch_h_t<true, false>(a, B, st, d, q);
+  return pms_launch_h_t<false, false>(a, B, st, d, q);
+}
+
 // 0: launched. 1: not launched — the kernel needs its dynamic-LDS attribute, which is set at first use on a device and
 // never while the stream is capturing; the caller then launches the exact kernel.
 template <bool DBG, bool DUMP, bool PREP>
@@ -623,8 +941,11 @@ static int pms_launch_form(const PMFwdArgs& a, int B, hipStream_t st, const PMSc
 }
 
 int pm_fwd_screen_launch(const PMFwdArgs& a, int B, void* stream, int32_t* stats, float* dbg_S, float* dbg_E,
-                         int stop_after, const PMScreenPrep* prep) {
+                         int stop_after, const PMScreenPrep* prep, const PMScreenPrepH* hprep) {
   const PMScreenDbg d{stats, dbg_S, dbg_E, stop_after};
+  // the fp16 form when the caller asks for it by passing its image; like the forms below it steps aside while its
+  // first use on the device falls into a capture
+  if (hprep != nullptr && pms_launch_h(a, B, as_stream(stream), d, *hprep) == 0) return 0;
   // the prepared form when the caller has the image; the in-launch form without one, and when the prepared
   // instantiation cannot be launched yet (its first use on the device falls into a capture)
   if (prep != nullptr && pms_launch_form<true>(a, B, as_stream(stream), d, *prep) == 0) return 0;
@@ -634,6 +955,12 @@ int pm_fwd_screen_launch(const PMFwdArgs& a, int B, void* stream, int32_t* stats
 int pm_w3_prepare_launch(const float* W3, int C3, void* w3_bf, float* w3_nw, float* w3_q, void* stream) {
   hipLaunchKernelGGL(pms_w3_prepare_kernel, dim3(C3 / 32), dim3(64), 0, as_stream(stream), W3,
                      reinterpret_cast<bf16x8*>(w3_bf), w3_nw, reinterpret_cast<float4*>(w3_q), C3);
+  return 0;
+}
+
+int pm_w3_prepare_h_launch(const float* W3, int C3, const float* w3_nw, void* w3_h, float* w3_cw, void* stream) {
+  hipLaunchKernelGGL(pms_w3_prepare_h_kernel, dim3(C3 / 32), dim3(64), 0, as_stream(stream), W3, w3_nw,
+                     reinterpret_cast<f16x8*>(w3_h), w3_cw);
   return 0;
 }
 

@@ -396,12 +396,34 @@ def pointmlp3_w3_prepare(W3):
     C3 = W3.shape[0]
     if W3.dim() != 2 or W3.shape[1] != 128 or not W3.is_contiguous():
         raise ValueError("pointmlp3_w3_prepare: W3 must be a contiguous [C3,128] tensor")
-    bf = torch.empty((C3 // 32, 8, 2, 64, 8), dtype=torch.bfloat16, device=W3.device)
+    # ONE allocation: the bf16 image first, behind it the fp16 image (C3 * 256 B: [C3/32,8,64,8] fp16, W3 2^sw[c] in the
+    # bf16 image's lane order without the hi / lo dimension) and its per-channel cw [C3] f32 (_pm_w3_h reaches them).
+    # w3_bf is a view of the front, so whatever keeps w3_bf alive next to a captured graph keeps all three.
+    buf = torch.empty((C3 * _PM_W3_BYTES,), dtype=torch.uint8, device=W3.device)
+    bf = buf[:C3 * 512].view(torch.bfloat16).view(C3 // 32, 8, 2, 64, 8)
     nw = torch.empty((C3,), dtype=torch.float32, device=W3.device)
     q = torch.empty((32, C3, 4), dtype=torch.float32, device=W3.device)
     with torch.cuda.device(W3.device):
         _lib.call("pc3d_pointmlp3_w3_prepare_f32", W3.data_ptr(), C3, bf.data_ptr(), nw.data_ptr(), q.data_ptr(), _stream())
+        _lib.call("pc3d_pointmlp3_w3_prepare_h_f32", W3.data_ptr(), C3, nw.data_ptr(), bf.data_ptr() + C3 * 512,
+                  bf.data_ptr() + C3 * 768, _stream())
     return bf, nw, q
+
+
+_PM_W3_BYTES = 512 + 256 + 4      # per channel: bf16 hi / lo image, fp16 image, cw
+
+
+def _pm_w3_h(bf):
+    """(w3_h, w3_cw) of the allocation whose front w3_bf is, as (tensor views, device pointers), or None for a w3_bf that
+    pointmlp3_w3_prepare did not make."""
+    C3 = bf.shape[0] * 32
+    st = bf.untyped_storage()
+    if bf.storage_offset() != 0 or st.nbytes() < C3 * _PM_W3_BYTES:
+        return None
+    raw = torch.empty(0, dtype=torch.uint8, device=bf.device).set_(st, 0, (C3 * _PM_W3_BYTES,))
+    h = raw[C3 * 512:C3 * 768].view(torch.float16).view(C3 // 32, 8, 64, 8)
+    cw = raw[C3 * 768:].view(torch.float32)
+    return (h, cw), (bf.data_ptr() + C3 * 512, bf.data_ptr() + C3 * 768)
 
 
 def _pm_w3_pack(weights, W3):
@@ -418,22 +440,31 @@ def _pm_w3_pack(weights, W3):
     return pack[:3] if pack[3] == (W3.data_ptr(), W3._version) else None
 
 
+# What pointmlp3_max_fwd_raw(form=None) runs from a prepared image: "bf16" or "fp16" (the same bits either way). fp16 since
+# r11: -8.2 us per headline step, 8.7 x the run-to-run spread.
+PM_FWD_DEFAULT_FORM = "fp16"
+
+
 def pointmlp3_max_fwd_raw(x, weights, relu_last, T=None, x_cf=True, fold=True, want_masks=False, T_head=None, serial=False,
-                          exact=False, screen_dbg=None, in_launch=False):
+                          exact=False, screen_dbg=None, in_launch=False, form=None):
     """x [B,3,N] (x_cf) or [B,N,3]; weights = (W1[64,3], b1, W2[128,64], b2, W3[C3,128], b3) with eval-BN folded.
     Returns (pooled [B,C3] f32, argidx [B,C3] i32) and, with want_masks, a third item (mask1 [B,N] i64, mask2 [B,N,4]
     i32): the per-point ReLU decisions of layers 1 and 2 as bit masks, which pointmlp3_max_bwd_raw consumes.
     T_head = (h [B,K], W [9,K], b [9]): the input transform T = h @ W.T + b is computed in the launch's prologue
     (no launch of its own) and returned as a last extra item [B,9].
     serial: fold with the earlier fold kernel (same bits; parity tests and tools/bench_small_launches.py only).
-    exact: launch the exact fp32 kernel; the default screens layer 3 on bf16 MFMA and rechecks the survivors exactly
-    (the same bits). screen_dbg: a dict, for tests and tools — the screened launch's debug instantiation runs and the
+    exact: launch the exact fp32 kernel; the default screens layer 3 on the matrix pipe (see form) and rechecks the
+    survivors exactly (the same bits). screen_dbg: a dict, for tests and tools — the screened launch's debug instantiation runs and the
     dict receives "stats" [B,ntiles,2] i32 (candidates rechecked, channel blocks that fell back to the exact block);
     with screen_dbg["dump"] set also "S" and "E" [B,N,C3] (tiny shapes), with screen_dbg["stop_after"] = 1 / 2 / 3
     the launch ends after that phase (timing only: the outputs are undefined).
     weights[7], when present: a plain list that holds the prepared image of W3 (see _pm_w3_pack; model/pointnet.py puts an
     empty one into every folded tower). With it the screened launch reads its bf16 operands, norms and recheck rows from
-    the image instead of making them from W3 in every workgroup (the same bits). in_launch: do not use the image."""
+    the image instead of making them from W3 in every workgroup (the same bits). in_launch: do not use the image.
+    form: which screen runs from the image — "bf16" the three-product bf16 screen, "fp16" the one-product scaled fp16
+    screen (csrc/pointmlp_screen_h_bound.h; sixteen candidate slots per channel), None: PM_FWD_DEFAULT_FORM, but the
+    bf16 one under screen_dbg (its figures are that form's unless the caller names the other). The same bits in every
+    output either way. Under form="fp16" screen_dbg's "S" and "E" come back in the unscaled domain."""
     xp, xbs, xps, xcs, B, N = _pts(x, x_cf, "x")
     W1, b1, W2, b2, W3, b3 = weights[:6]
     for w in weights[:7]:
@@ -463,8 +494,15 @@ def pointmlp3_max_fwd_raw(x, weights, relu_last, T=None, x_cf=True, fold=True, w
     sfx = "exact_" if exact else ""
     with torch.cuda.device(dev):
         prep = None if exact or in_launch else _pm_w3_pack(weights, W3)
+        if form not in (None, "bf16", "fp16"):
+            raise ValueError("pointmlp3_max_fwd_raw: form is None, 'bf16' or 'fp16'")
+        if form is None:
+            form = PM_FWD_DEFAULT_FORM if screen_dbg is None else "bf16"
         if prep is not None:
+            hp = _pm_w3_h(prep[0]) if form == "fp16" else None
             sfx, prep = "prep_", tuple(t.data_ptr() for t in prep)
+            if hp is not None:
+                sfx, prep = "h_", prep + hp[1]
         if T_head is not None:
             if T is not None:
                 raise ValueError("pointmlp3_max_fwd_raw: give T or T_head, not both")

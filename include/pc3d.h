@@ -437,6 +437,37 @@ int pc3d_pointmlp3_max_fwd_screen_dbg_prep_f32(const float* x, int64_t x_bs, int
                                                int32_t* argidx, uint64_t* mask1, uint32_t* mask2, int32_t* stats,
                                                float* dbg_S, float* dbg_E, int stop_after, const void* w3_bf,
                                                const float* w3_nw, const float* w3_q, void* stream);
+/* The fp16 image of the same W3, made from it and from the w3_nw that pc3d_pointmlp3_w3_prepare_f32 wrote:
+ * w3_h [C3/32][8][64][8] fp16 (block, k-step, lane r + 32 h, the 8 values of W3[32 cb + r][16 t + 8 h + 0..7] * 2^sw[c],
+ * rounded to nearest even; sw[c] puts w3_nw[c] * 2^sw[c] into [2^13, 2^14)), w3_cw [C3] f32 (the channel's factor of the
+ * screen's bound in that scaled domain, csrc/pointmlp_screen_h_bound.h; +inf for a channel whose norm is out of range). */
+int pc3d_pointmlp3_w3_prepare_h_f32(const float* W3, int C3, const float* w3_nw, void* w3_h, float* w3_cw, void* stream);
+/* pc3d_pointmlp3_max_fwd_prep_f32 / _prep_th_f32 / _screen_dbg_prep_f32 with layer 3 screened by ONE scaled fp16 product
+ * per k-step instead of three bf16 ones (sixteen candidate slots per channel instead of eight): the same bits in every
+ * output. Both images of the SAME W3 are passed; the bf16 one serves when this form cannot be launched yet (its first
+ * use on a device falls into a stream capture). dbg_S / dbg_E come back in the unscaled domain. */
+int pc3d_pointmlp3_max_fwd_h_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N, const float* T,
+                                 const float* W1, const float* b1, const float* W2, const float* b2, const float* W3,
+                                 const float* b3, int C1, int C2, int C3, int relu_last, float* part_val,
+                                 int32_t* part_idx, float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2,
+                                 const void* w3_bf, const float* w3_nw, const float* w3_q, const void* w3_h,
+                                 const float* w3_cw, void* stream);
+int pc3d_pointmlp3_max_fwd_h_th_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                    const float* th_in, const float* th_W, const float* th_b, int th_K, float* T_out,
+                                    const float* W1, const float* b1, const float* W2, const float* b2,
+                                    const float* W3, const float* b3, int C1, int C2, int C3, int relu_last,
+                                    float* part_val, int32_t* part_idx, float* pooled, int32_t* argidx,
+                                    uint64_t* mask1, uint32_t* mask2, const void* w3_bf, const float* w3_nw,
+                                    const float* w3_q, const void* w3_h, const float* w3_cw, void* stream);
+int pc3d_pointmlp3_max_fwd_screen_dbg_h_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                            const float* T, const float* th_in, const float* th_W, const float* th_b,
+                                            int th_K, float* T_out, const float* W1, const float* b1, const float* W2,
+                                            const float* b2, const float* W3, const float* b3, int C1, int C2, int C3,
+                                            int relu_last, float* part_val, int32_t* part_idx, float* pooled,
+                                            int32_t* argidx, uint64_t* mask1, uint32_t* mask2, int32_t* stats,
+                                            float* dbg_S, float* dbg_E, int stop_after, const void* w3_bf,
+                                            const float* w3_nw, const float* w3_q, const void* w3_h, const float* w3_cw,
+                                            void* stream);
 
 /* Backward-to-input of the above (weights are frozen during an attack: no weight gradients, SURVEY A-14).
  * g_pooled [B,C3] is the upstream gradient on `pooled`; with relu_last the caller zeroes it where pooled <= 0.

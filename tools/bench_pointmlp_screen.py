@@ -1,8 +1,9 @@
-"""Stand-alone timing of the PointNet tower forward with layer 3 screened on bf16 MFMA against the exact fp32 kernel
-(exact=True), in both screened forms: `in_launch` makes its bf16 operands and norms from W3 inside every launch,
-`prepared` (the default for a folded tower) reads them from the image made once per fold. All inside replayed
+"""Stand-alone timing of the PointNet tower forward with layer 3 screened on the matrix pipe against the exact fp32 kernel
+(exact=True), in the three screened forms: `in_launch` makes its bf16 operands and norms from W3 inside every launch,
+`prepared` reads them from the image made once per fold (three bf16 products per k-step), `fp16` reads the scaled fp16
+image in the same allocation (one product per k-step, sixteen candidate slots per channel). All inside replayed
 hipGraphs, alternated, at B = 32 and N = 1024 / 2048 / 4096, for both towers of bench.py's victim (seeded weights 0) on
-bench.py's kind of cloud. Also both screened launches cut short after each phase (prologue + norms, + screen,
+bench.py's kind of cloud. Also the screened launches cut short after each phase (prologue + norms, + screen,
 + selection; the debug instantiations) and the `stats` of the full launches: candidates rechecked per (tile, channel),
 channel blocks that fell back to the exact block. Every time is the least of the rounds; *_spread_us is the largest
 minus the least round of that graph. One JSON line per (tower, N); --json PATH also writes the list."""
@@ -81,22 +82,22 @@ for N in [int(s) for s in args.sizes.split(",")]:
         C3 = w[4].shape[0]
         fns = [lambda: ops.pointmlp3_max_fwd_raw(x, w, relu_last, fold=False, exact=True, **kw)]
         names = ["exact"]
-        for form, il in (("in_launch", True), ("prepared", False)):
-            sc = ops.pointmlp3_max_fwd_raw(x, w, relu_last, want_masks=True, in_launch=il, **kw)
+        for form, sel in (("in_launch", dict(in_launch=True)), ("prepared", dict(form="bf16")), ("fp16", dict(form="fp16"))):
+            sc = ops.pointmlp3_max_fwd_raw(x, w, relu_last, want_masks=True, **sel, **kw)
             row["bit_equal_" + form] = bool(all(torch.equal(a, b) for a, b in zip((ex[0], ex[1]) + ex[2], (sc[0], sc[1]) + sc[2])))
             dbg = {}
-            ops.pointmlp3_max_fwd_raw(x, w, relu_last, fold=False, screen_dbg=dbg, in_launch=il, **kw)
+            ops.pointmlp3_max_fwd_raw(x, w, relu_last, fold=False, screen_dbg=dbg, **sel, **kw)
             st = dbg["stats"].double()
             ntiles = st.shape[1]
             row[form + "_candidates_per_tile_channel"] = float(st[..., 0].sum() / (B * ntiles * C3))
             row[form + "_fallback_blocks"] = int(st[..., 1].sum())
-            fns.append(lambda il=il: ops.pointmlp3_max_fwd_raw(x, w, relu_last, fold=False, in_launch=il, **kw))
+            fns.append(lambda sel=sel: ops.pointmlp3_max_fwd_raw(x, w, relu_last, fold=False, **sel, **kw))
             names.append(form)
             for stop, cut in ((1, "prologue"), (2, "screen"), (3, "select"), (0, "all")):
-                fns.append(lambda stop=stop, il=il: ops.pointmlp3_max_fwd_raw(x, w, relu_last, fold=False, in_launch=il,
-                                                                              screen_dbg={"stop_after": stop}, **kw))
+                fns.append(lambda stop=stop, sel=sel: ops.pointmlp3_max_fwd_raw(x, w, relu_last, fold=False,
+                                                                                screen_dbg={"stop_after": stop}, **sel, **kw))
                 names.append(form + "_dbg_" + cut)
-        assert len(w[7]) == 4                            # the prepared rows did run from the image
+        assert len(w[7]) == 4 and ops._pm_w3_h(w[7][0]) is not None   # the prepared and fp16 rows did run from the images
         row["blocks"] = int(B * ntiles * C3 // 32)
         best, worst = graph_us(fns)
         for name, lo, hi in zip(names, best, worst):
