@@ -178,6 +178,12 @@ SIGNATURES = {
     + [_P] * 5 + [_P],
     "pc3d_pointmlp3_max_fwd_screen_dbg_h_f32": _PTS + [_I, _I] + [_P, _P, _P, _P, _I, _P] + [_P] * 6 + [_I, _I, _I, _I]
     + [_P] * 6 + [_P, _P, _P, _I] + [_P] * 5 + [_P],
+    "pc3d_pointmlp3_max_fwd_h_pair_f32": _PTS + [_I, _I] + [_P] * 7 + [_I, _I, _I, _I] + [_P] * 6 + [_P] * 5 + [_P],
+    "pc3d_pointmlp3_max_fwd_h_pair_th_f32": _PTS + [_I, _I] + [_P, _P, _P, _I, _P] + [_P] * 6 + [_I, _I, _I, _I] + [_P] * 6
+    + [_P] * 5 + [_P],
+    "pc3d_pointmlp3_max_fwd_screen_dbg_h_pair_f32": _PTS + [_I, _I] + [_P, _P, _P, _P, _I, _P] + [_P] * 6 + [_I, _I, _I, _I]
+    + [_P] * 6 + [_P, _P, _P, _I] + [_P] * 5 + [_P],
+    "pc3d_pointmlp3_pair_recheck_ready": [],
     "pc3d_linear_pre_f32": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P],
     "pc3d_pointmlp3_max_bwd_f32": _PTS + [_I, _I] + [_P] * 7 + [_I, _I, _I] + [_P, _P, _P, _P] + _PTS + [_P, _I, _P],
     "pc3d_pointmlp3_max_bwd_twolist_f32": _PTS + [_I, _I] + [_P] * 7 + [_I, _I, _I] + [_P, _P, _P, _P] + _PTS + [_P, _I, _P],

@@ -205,6 +205,21 @@ __device__ __forceinline__ int wave_incl_scan(int v, int lane_in_group) {
   return v;
 }
 
+// Exclusive prefix sum over the wavefront of one SMALL count per lane (0 <= v < 2^BITS), and the wave's total: one ballot
+// per bit of v, the set lanes below this one counted with mbcnt. No cross-lane moves and no lane masks held in SGPRs.
+template <int BITS>
+__device__ __forceinline__ int wave_excl_scan_bits(int v, int& total) {
+  int excl = 0;
+  total = 0;
+#pragma unroll
+  for (int b = 0; b < BITS; ++b) {
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(((v >> b) & 1) != 0);
+    excl += (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u)) << b;
+    total += __builtin_popcountll(m) << b;
+  }
+  return excl;
+}
+
 // Workgroup sums of one value per thread, the same bits in every thread. Both take the wave butterfly first; the NAME says
 // how the wave partials are added, and the two orders give different bits. red: one T per wave of LDS; the leading barrier
 // lets a call follow another on the same red.

@@ -1246,7 +1246,8 @@ static int pm_fwd_launch(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_c
                          const float* b3, int C1, int C2, int C3, int relu_last, float* part_val, int32_t* part_idx,
                          float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2, void* stream,
                          bool exact = false, int32_t* stats = nullptr, float* dbg_S = nullptr, float* dbg_E = nullptr,
-                         int stop_after = 0, const PMScreenPrep* prep = nullptr, const PMScreenPrepH* hprep = nullptr) {
+                         int stop_after = 0, const PMScreenPrep* prep = nullptr, const PMScreenPrepH* hprep = nullptr,
+                         bool pair = false) {
   PC3D_REQUIRE(B >= 0 && N >= 1, "pc3d_pointmlp3_max_fwd_f32: bad sizes B=%d N=%d", B, N);
   PC3D_REQUIRE(C1 == PM_C1 && C2 == PM_C2 && C3 >= 32 && C3 % 32 == 0 && C3 <= PM_MAXC3F,
                "pc3d_pointmlp3_max_fwd_f32: unsupported widths %d/%d/%d (need 64/128/multiple of 32 <= 1024)", C1, C2, C3);
@@ -1267,7 +1268,7 @@ static int pm_fwd_launch(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_c
   // screen); the exact kernel on request, and when the screened one cannot be launched yet (see pm_fwd_screen_launch).
   int rc = 1;
   if (!exact) {
-    rc = pm_fwd_screen_launch(a, B, stream, stats, dbg_S, dbg_E, stop_after, prep, hprep);
+    rc = pm_fwd_screen_launch(a, B, stream, stats, dbg_S, dbg_E, stop_after, prep, hprep, pair);
     if (rc < 0) return rc;
   }
   if (rc != 0) hipLaunchKernelGGL(pointmlp3_max_fwd_kernel, dim3(ntiles, B), dim3(PM_FT), 0, st, a);
@@ -1439,63 +1440,74 @@ static PMScreenPrepH pm_prep_h(const void* w3_h, const float* w3_cw, const float
   return PMScreenPrepH{reinterpret_cast<decltype(PMScreenPrepH::w3_h)>(w3_h), w3_cw, w3_nw, reinterpret_cast<const float4*>(w3_q)};
 }
 
-extern "C" int pc3d_pointmlp3_max_fwd_h_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
-                                            const float* T, const float* W1, const float* b1, const float* W2,
-                                            const float* b2, const float* W3, const float* b3, int C1, int C2, int C3,
-                                            int relu_last, float* part_val, int32_t* part_idx, float* pooled,
-                                            int32_t* argidx, uint64_t* mask1, uint32_t* mask2, const void* w3_bf,
-                                            const float* w3_nw, const float* w3_q, const void* w3_h, const float* w3_cw,
-                                            void* stream) {
-  PC3D_REQUIRE(w3_bf && w3_nw && w3_q && w3_h && w3_cw, "pc3d_pointmlp3_max_fwd_h_f32: both prepared images are needed");
-  const PMScreenPrep q = pm_prep(w3_bf, w3_nw, w3_q);
-  const PMScreenPrepH qh = pm_prep_h(w3_h, w3_cw, w3_nw, w3_q);
-  return pm_fwd_launch(x, x_bs, x_ps, x_cs, B, N, T, nullptr, nullptr, nullptr, 0, nullptr, W1, b1, W2, b2, W3, b3, C1, C2,
-                       C3, relu_last, part_val, part_idx, pooled, argidx, mask1, mask2, stream, false, nullptr, nullptr,
-                       nullptr, 0, &q, &qh);
-}
-
-extern "C" int pc3d_pointmlp3_max_fwd_h_th_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
-                                               const float* th_in, const float* th_W, const float* th_b, int th_K,
-                                               float* T_out, const float* W1, const float* b1, const float* W2,
-                                               const float* b2, const float* W3, const float* b3, int C1, int C2, int C3,
-                                               int relu_last, float* part_val, int32_t* part_idx, float* pooled,
-                                               int32_t* argidx, uint64_t* mask1, uint32_t* mask2, const void* w3_bf,
-                                               const float* w3_nw, const float* w3_q, const void* w3_h,
-                                               const float* w3_cw, void* stream) {
-  PC3D_REQUIRE(th_in && th_W && th_b && T_out && th_K >= 1,
-               "pc3d_pointmlp3_max_fwd_h_th_f32: the transform head needs its input, weights [9,K], bias [9] and T_out");
-  PC3D_REQUIRE(w3_bf && w3_nw && w3_q && w3_h && w3_cw, "pc3d_pointmlp3_max_fwd_h_th_f32: both prepared images are needed");
-  const PMScreenPrep q = pm_prep(w3_bf, w3_nw, w3_q);
-  const PMScreenPrepH qh = pm_prep_h(w3_h, w3_cw, w3_nw, w3_q);
-  return pm_fwd_launch(x, x_bs, x_ps, x_cs, B, N, nullptr, th_in, th_W, th_b, th_K, T_out, W1, b1, W2, b2, W3, b3, C1, C2,
-                       C3, relu_last, part_val, part_idx, pooled, argidx, mask1, mask2, stream, false, nullptr, nullptr,
-                       nullptr, 0, &q, &qh);
-}
-
-// stats / dbg_S / dbg_E / stop_after as in pc3d_pointmlp3_max_fwd_screen_dbg_f32, of the H form; dbg_S and dbg_E come
-// back in the unscaled domain (S 2^-(sa + sw), E 2^-(sa + sw))
-extern "C" int pc3d_pointmlp3_max_fwd_screen_dbg_h_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B,
-                                                       int N, const float* T, const float* th_in, const float* th_W,
-                                                       const float* th_b, int th_K, float* T_out, const float* W1,
-                                                       const float* b1, const float* W2, const float* b2, const float* W3,
-                                                       const float* b3, int C1, int C2, int C3, int relu_last,
-                                                       float* part_val, int32_t* part_idx, float* pooled, int32_t* argidx,
-                                                       uint64_t* mask1, uint32_t* mask2, int32_t* stats, float* dbg_S,
-                                                       float* dbg_E, int stop_after, const void* w3_bf, const float* w3_nw,
-                                                       const float* w3_q, const void* w3_h, const float* w3_cw,
-                                                       void* stream) {
-  PC3D_REQUIRE(stats != nullptr, "pc3d_pointmlp3_max_fwd_screen_dbg_h_f32: stats [B, ntiles, 2] is required");
-  PC3D_REQUIRE((dbg_S == nullptr) == (dbg_E == nullptr), "pc3d_pointmlp3_max_fwd_screen_dbg_h_f32: dbg_S and dbg_E go together");
-  PC3D_REQUIRE(stop_after >= 0 && stop_after <= 3, "pc3d_pointmlp3_max_fwd_screen_dbg_h_f32: stop_after = %d", stop_after);
-  PC3D_REQUIRE(th_in == nullptr || (T == nullptr && th_W && th_b && T_out && th_K >= 1),
-               "pc3d_pointmlp3_max_fwd_screen_dbg_h_f32: T or a complete transform head, not both");
-  PC3D_REQUIRE(w3_bf && w3_nw && w3_q && w3_h && w3_cw, "pc3d_pointmlp3_max_fwd_screen_dbg_h_f32: both prepared images are needed");
+// one body for the H entries: T or a transform head or neither; stats null for the production instantiation, else the
+// debug one (stats / dbg_S / dbg_E / stop_after as in pc3d_pointmlp3_max_fwd_screen_dbg_f32; dbg_S and dbg_E come back
+// in the unscaled domain, S 2^-(sa + sw), E 2^-(sa + sw)). pair: the recheck by (channel, candidate) pair.
+static int pm_fwd_h(const char* who, bool pair, bool th, bool dbg, const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs,
+                    int B, int N, const float* T, const float* th_in, const float* th_W, const float* th_b, int th_K,
+                    float* T_out, const float* W1, const float* b1, const float* W2, const float* b2, const float* W3,
+                    const float* b3, int C1, int C2, int C3, int relu_last, float* part_val, int32_t* part_idx,
+                    float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2, int32_t* stats, float* dbg_S,
+                    float* dbg_E, int stop_after, const void* w3_bf, const float* w3_nw, const float* w3_q,
+                    const void* w3_h, const float* w3_cw, void* stream) {
+  if (dbg) {
+    PC3D_REQUIRE(stats != nullptr, "%s: stats [B, ntiles, 2] is required", who);
+    PC3D_REQUIRE((dbg_S == nullptr) == (dbg_E == nullptr), "%s: dbg_S and dbg_E go together", who);
+    PC3D_REQUIRE(stop_after >= 0 && stop_after <= 3, "%s: stop_after = %d", who, stop_after);
+    PC3D_REQUIRE(th_in == nullptr || (T == nullptr && th_W && th_b && T_out && th_K >= 1),
+                 "%s: T or a complete transform head, not both", who);
+  }
+  if (th)
+    PC3D_REQUIRE(th_in && th_W && th_b && T_out && th_K >= 1,
+                 "%s: the transform head needs its input, weights [9,K], bias [9] and T_out", who);
+  PC3D_REQUIRE(w3_bf && w3_nw && w3_q && w3_h && w3_cw, "%s: both prepared images are needed", who);
   const PMScreenPrep q = pm_prep(w3_bf, w3_nw, w3_q);
   const PMScreenPrepH qh = pm_prep_h(w3_h, w3_cw, w3_nw, w3_q);
   return pm_fwd_launch(x, x_bs, x_ps, x_cs, B, N, T, th_in, th_W, th_b, th_K, T_out, W1, b1, W2, b2, W3, b3, C1, C2, C3,
                        relu_last, part_val, part_idx, pooled, argidx, mask1, mask2, stream, false, stats, dbg_S, dbg_E,
-                       stop_after, &q, &qh);
+                       stop_after, &q, &qh, pair);
 }
+
+// the three H entries, and the same three with the recheck by pair (PC3D_H_ENTRIES(infix, pair))
+#define PC3D_H_ENTRIES(NAME, PAIR)                                                                                          \
+  extern "C" int pc3d_pointmlp3_max_fwd_##NAME##_f32(                                                                       \
+      const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N, const float* T, const float* W1,             \
+      const float* b1, const float* W2, const float* b2, const float* W3, const float* b3, int C1, int C2, int C3,         \
+      int relu_last, float* part_val, int32_t* part_idx, float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2, \
+      const void* w3_bf, const float* w3_nw, const float* w3_q, const void* w3_h, const float* w3_cw, void* stream) {       \
+    return pm_fwd_h("pc3d_pointmlp3_max_fwd_" #NAME "_f32", PAIR, false, false, x, x_bs, x_ps, x_cs, B, N, T, nullptr,     \
+                    nullptr, nullptr, 0, nullptr, W1, b1, W2, b2, W3, b3, C1, C2, C3, relu_last, part_val, part_idx,       \
+                    pooled, argidx, mask1, mask2, nullptr, nullptr, nullptr, 0, w3_bf, w3_nw, w3_q, w3_h, w3_cw, stream);  \
+  }                                                                                                                         \
+  extern "C" int pc3d_pointmlp3_max_fwd_##NAME##_th_f32(                                                                    \
+      const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N, const float* th_in, const float* th_W,       \
+      const float* th_b, int th_K, float* T_out, const float* W1, const float* b1, const float* W2, const float* b2,       \
+      const float* W3, const float* b3, int C1, int C2, int C3, int relu_last, float* part_val, int32_t* part_idx,         \
+      float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2, const void* w3_bf, const float* w3_nw,             \
+      const float* w3_q, const void* w3_h, const float* w3_cw, void* stream) {                                              \
+    return pm_fwd_h("pc3d_pointmlp3_max_fwd_" #NAME "_th_f32", PAIR, true, false, x, x_bs, x_ps, x_cs, B, N, nullptr,      \
+                    th_in, th_W, th_b, th_K, T_out, W1, b1, W2, b2, W3, b3, C1, C2, C3, relu_last, part_val, part_idx,     \
+                    pooled, argidx, mask1, mask2, nullptr, nullptr, nullptr, 0, w3_bf, w3_nw, w3_q, w3_h, w3_cw, stream);  \
+  }                                                                                                                         \
+  extern "C" int pc3d_pointmlp3_max_fwd_screen_dbg_##NAME##_f32(                                                            \
+      const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N, const float* T, const float* th_in,          \
+      const float* th_W, const float* th_b, int th_K, float* T_out, const float* W1, const float* b1, const float* W2,     \
+      const float* b2, const float* W3, const float* b3, int C1, int C2, int C3, int relu_last, float* part_val,           \
+      int32_t* part_idx, float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2, int32_t* stats, float* dbg_S,   \
+      float* dbg_E, int stop_after, const void* w3_bf, const float* w3_nw, const float* w3_q, const void* w3_h,            \
+      const float* w3_cw, void* stream) {                                                                                   \
+    return pm_fwd_h("pc3d_pointmlp3_max_fwd_screen_dbg_" #NAME "_f32", PAIR, false, true, x, x_bs, x_ps, x_cs, B, N, T,    \
+                    th_in, th_W, th_b, th_K, T_out, W1, b1, W2, b2, W3, b3, C1, C2, C3, relu_last, part_val, part_idx,     \
+                    pooled, argidx, mask1, mask2, stats, dbg_S, dbg_E, stop_after, w3_bf, w3_nw, w3_q, w3_h, w3_cw,        \
+                    stream);                                                                                                \
+  }
+PC3D_H_ENTRIES(h, false)
+PC3D_H_ENTRIES(h_pair, true)
+#undef PC3D_H_ENTRIES
+
+// 1 once the production pair instantiation can be launched on the current device (its dynamic-LDS attribute is set at
+// its first use outside a capture); 0 before: a launch that asks for the pair recheck then runs the channel one
+extern "C" int pc3d_pointmlp3_pair_recheck_ready(void) { return pm_fwd_pair_ready(); }
 
 // which kernel the default entries launch (pc3d_pointmlp3_max_bwd_f32 / _update_f32); every form stays reachable by name
 constexpr bool PM_BWD_DEFAULT_PACKED = true;

@@ -208,7 +208,11 @@ struct PMScreenPrepH {
   const float4* w3_q;                                        // [32][C3]
 };
 int pm_fwd_screen_launch(const PMFwdArgs& a, int B, void* stream, int32_t* stats, float* dbg_S, float* dbg_E,
-                         int stop_after, const PMScreenPrep* prep, const PMScreenPrepH* hprep = nullptr);
+                         int stop_after, const PMScreenPrep* prep, const PMScreenPrepH* hprep = nullptr, bool pair = false);
+// pair (with hprep): the H form's recheck runs one lane per (channel, candidate) pair instead of one lane per channel
+// (the same bits); an instantiation of its own, so its first use inside a capture takes the channel recheck.
+// pm_fwd_pair_ready: 1 once the production pair instantiation can be launched on the current device.
+int pm_fwd_pair_ready();
 // w3_bf (C3 * 512 B), w3_nw (C3 floats), w3_q (C3 * 128 floats) from the folded fp32 W3 [C3,128]
 int pm_w3_prepare_launch(const float* W3, int C3, void* w3_bf, float* w3_nw, float* w3_q, void* stream);
 // w3_h (C3 * 256 B) and w3_cw (C3 floats) from W3 and the w3_nw that pm_w3_prepare_launch wrote for it

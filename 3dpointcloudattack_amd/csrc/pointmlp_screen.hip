@@ -33,6 +33,8 @@
 //
 // H (further down): PREP with ONE fp16 product per k-step in place of the three bf16 ones, operands scaled by powers of
 // two into fp16's range; a bound eight times wider, sixteen slots per channel, the same recheck and the same bits.
+// H with PAIR: the recheck goes by (channel, candidate) pair instead, one lane each, over a per-wave list in LDS, and a
+// channel's pairs meet in its 64-bit LDS key as in the in-launch form; the same bits.
 #include "pc3d_common.h"
 #include "pointmlp_body.h"
 #include "pointmlp_screen_bound.h"
@@ -616,6 +618,14 @@ constexpr size_t PMH_LDS_BYTES = PMH_A16_OFF + (size_t)PM_TP * PMS_LDA * 2;
 static_assert(PMH_LDS_BYTES + 1024 <= 160 * 1024 && PMH_A16_OFF % 16 == 0 && PMH_PTS_OFF % 16 == 0, "H's LDS map");
 static_assert(PMH_PCAP >= 4 && PMH_PCAP <= 31 && 5 * PMS_SLOTS <= 32, "a channel's candidate count is kept in 5 bits per slot");
 static_assert(PM_TP <= 256, "a candidate point is one byte");
+// the PAIR recheck's LDS behind H's map: keys [8 waves][128 channels] u64 | lists [8 waves][2048] u16 = 161,808 B in all
+constexpr int PMP_WCH = 32 * PMS_SLOTS;                    // channels per wave
+constexpr int PMP_WLIST = PMP_WCH * PMH_PCAP;              // (channel, candidate) pairs per wave at most
+constexpr size_t PMP_KEY_OFF = PMH_LDS_BYTES;
+constexpr size_t PMP_LIST_OFF = PMP_KEY_OFF + (size_t)(PM_FT / 64) * PMP_WCH * 8;
+constexpr size_t PMP_LDS_BYTES = PMP_LIST_OFF + (size_t)(PM_FT / 64) * PMP_WLIST * 2;
+static_assert(PMP_LDS_BYTES + 1024 <= 160 * 1024 && PMP_KEY_OFF % 8 == 0 && PMP_LIST_OFF % 2 == 0, "the pair recheck's LDS map");
+static_assert(PMP_WCH <= 128 && PMS_SLOTS % 2 == 0 && PMH_PCAP == 16, "a list entry is channel-in-wave << 8 | point; a channel's slots are one 16-B read");
 
 __global__ __launch_bounds__(64) void pms_w3_prepare_h_kernel(const float* __restrict__ W3, const float* __restrict__ w3_nw,
                                                               f16x8* __restrict__ w3_h, float* __restrict__ w3_cw) {
@@ -637,7 +647,8 @@ __global__ __launch_bounds__(64) void pms_w3_prepare_h_kernel(const float* __res
   if (h == 0) w3_cw[cb * 32 + r] = ok ? pmh_cw(nw, two_sw) : __builtin_inff();
 }
 
-template <bool DBG, bool DUMP>
+// PAIR: the recheck goes by (channel, candidate) PAIR, one lane each, instead of by channel (further down).
+template <bool DBG, bool DUMP, bool PAIR>
 __global__ __launch_bounds__(PM_FT) __attribute__((amdgpu_waves_per_eu(2, 2))) void pointmlp3_max_fwd_screen_h_kernel(
     PMFwdArgs a, PMScreenDbg d, PMScreenPrepH w3) {
   extern __shared__ __attribute__((aligned(16))) float pms_lds[];
@@ -829,6 +840,93 @@ __global__ __launch_bounds__(PM_FT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
   }
 
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the channels' candidate points, written by other lanes
+  if constexpr (PAIR) {
+    // ---- recheck by pair: one lane per (channel, candidate) of the wave's screened blocks, so a trip's 64 chains are
+    // 64 chains somebody needs (by channel, a trip lasts as long as its fullest channel and most lanes idle behind their
+    // first chain). Only this wave touches its list and its keys: no barrier.
+    unsigned long long* my_key = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(pms_lds) + PMP_KEY_OFF) + wave * PMP_WCH;
+    unsigned short* my_list = reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(pms_lds) + PMP_LIST_OFF) + wave * PMP_WLIST;
+    // the schedule: channels slot-major then r, which is lane order within a pass (lane = 32 (slot & 1) + r); an
+    // exclusive scan of the counts gives a channel its first pair, and the channel's lane writes its pairs
+    int total = 0;                        // (uniform) <= PMP_WLIST
+#pragma unroll 1
+    for (int j = 0; 2 * j < nslots; ++j) {
+      const int sl = 2 * j + h;
+      const bool live = sl < nslots && ((screened >> sl) & 1u);   // a fallen or missing slot counts 0
+      const int n = live ? (int)((cnts >> (5 * sl)) & 31u) : 0;
+      int pass_total;
+      const int excl = wave_excl_scan_bits<5>(n, pass_total);   // n <= PMH_PCAP = 16
+      my_key[64 * j + lane] = 0ull;       // channel-in-wave 32 sl + r
+      const int c = (wave + (PM_FT / 64) * (live ? sl : 0)) * 32 + r;   // an idle lane: a valid row, unused
+      const uint4 pv = *reinterpret_cast<const uint4*>(s_pts + c * PMH_PCAP);   // the channel's sixteen slots
+      unsigned short* dst = my_list + total + excl;
+      const unsigned tag = (unsigned)(64 * j + lane) << 8;
+#pragma unroll 1
+      for (int i = 0; __builtin_amdgcn_ballot_w64(i < n) != 0ull; ++i) {   // (uniform) up to the fullest channel
+        const unsigned pw = i < 4 ? pv.x : i < 8 ? pv.y : i < 12 ? pv.z : pv.w;
+        if (i < n) dst[i] = (unsigned short)(tag | ((pw >> (8 * (i & 3))) & 255u));
+      }
+      total += pass_total;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the list and the zeroed keys
+    if (total > 0) {                      // (uniform)
+      // lane l of trip k takes pair 64 k + l; the lanes past the end of the last trip sit it out (their pair is the
+      // last one's, a valid row, and nothing of it is loaded, read or entered)
+      int e = my_list[min(lane, total - 1)];
+      int c3s = a.C3;
+      asm volatile("" : "+s"(c3s));       // opaque: the rows' 64-bit stride is formed here, not held from the kernel's head
+#pragma unroll 1
+      for (int k0 = 0; k0 < total; k0 += 64) {
+        const bool act = k0 + lane < total;
+        const int ci = e >> 8, pc = e & 255;
+        e = my_list[min(k0 + 64 + lane, total - 1)];   // the next trip's pair, asked for ahead of this trip's chain
+        if (!act) continue;
+        const int c = (wave + (PM_FT / 64) * (ci >> 5)) * 32 + (ci & 31);
+        float4 wv[PM_C2 / 4];             // ascending channels: a load covers a few contiguous runs of w3_q[t]
+#pragma unroll
+        for (int t = 0; t < PM_C2 / 4; ++t) wv[t] = w3.w3_q[(int64_t)t * c3s + c];
+        const float4* ar = reinterpret_cast<const float4*>(h2 + pc * PM_LD2);
+        __builtin_amdgcn_sched_barrier(0);
+        float v = 0.f;
+#pragma unroll
+        for (int t = 0; t < PM_C2 / 8; ++t) {   // the chain of the channel form, literally
+          const float4 a0 = ar[2 * t], a1 = ar[2 * t + 1];
+          const float4 w0 = wv[2 * t], w1 = wv[2 * t + 1];
+          v = __builtin_fmaf(a0.x, w0.x, v), v = __builtin_fmaf(a1.x, w1.x, v);
+          v = __builtin_fmaf(a0.y, w0.y, v), v = __builtin_fmaf(a1.y, w1.y, v);
+          v = __builtin_fmaf(a0.z, w0.z, v), v = __builtin_fmaf(a1.z, w1.z, v);
+          v = __builtin_fmaf(a0.w, w0.w, v), v = __builtin_fmaf(a1.w, w1.w, v);
+        }
+        // the h2 row's reads pinned four k-groups ahead of the chain, as in the channel form
+        __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);        // 8 DS read
+#pragma unroll
+        for (int g = 0; g < PM_C2 / 8; ++g) {
+          __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);      // 8 VALU: the group's fmaf
+          if (g + 4 < PM_C2 / 8) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+        }
+        const unsigned vb = __builtin_bit_cast(unsigned, v);
+        const unsigned zb = (v == 0.f) ? 0u : vb;
+        const unsigned ord = (zb & 0x80000000u) ? ~zb : (zb | 0x80000000u);
+        const unsigned low = ((unsigned)(127 - pc) << 1) | ((vb == 0x80000000u) ? 1u : 0u);
+        // a channel's pairs are neighbours but may straddle a trip: an LDS max on the channel's key, order-free
+        atomicMax(&my_key[ci], ((unsigned long long)ord << 32) | low);
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the keys, entered by other lanes
+#pragma unroll
+    for (int j = 0; j < PMS_SLOTS / 2; ++j) {
+      const int sl = 2 * j + h;
+      if (!(sl < nslots && ((screened >> sl) & 1u))) continue;   // a fallen block's channels were stored by the exact block
+      const int c = (wave + (PM_FT / 64) * sl) * 32 + r;
+      const unsigned long long key = my_key[64 * j + lane];
+      const unsigned ord = (unsigned)(key >> 32), low = (unsigned)key;
+      unsigned vb = (ord & 0x80000000u) ? (ord & 0x7fffffffu) : ~ord;
+      if (low & 1u) vb = 0x80000000u;
+      a.part_val[obase + c] = __builtin_bit_cast(float, vb) + a.b3[c];
+      a.part_idx[obase + c] = n0 + 127 - (int)((low >> 1) & 127u);
+    }
+    return;
+  }
   // ---- recheck by channel, as in PREP: the exact kernel's chain from the UNSCALED fp32 h2 and fp32 row
 #pragma unroll 1
   for (int j = 0; 2 * j < nslots; ++j) {
@@ -882,12 +980,15 @@ __global__ __launch_bounds__(PM_FT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
   }
 }
 
-template <bool DBG, bool DUMP>
+static bool pmp_ready[64] = {};   // the production PAIR instantiation has its LDS attribute on that device
+
+template <bool DBG, bool DUMP, bool PAIR>
 static int pms_launch_h_t(const PMFwdArgs& a, int B, hipStream_t st, const PMScreenDbg& d, const PMScreenPrepH& q) {
   static bool done[64] = {};
   int dev = 0;
   PC3D_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "pointmlp3 screen: no current device");
-  auto kernel = pointmlp3_max_fwd_screen_h_kernel<DBG, DUMP>;
+  auto kernel = pointmlp3_max_fwd_screen_h_kernel<DBG, DUMP, PAIR>;
+  constexpr size_t lds = PAIR ? PMP_LDS_BYTES : PMH_LDS_BYTES;
   if (!done[dev]) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
@@ -895,18 +996,25 @@ static int pms_launch_h_t(const PMFwdArgs& a, int B, hipStream_t st, const PMScr
       return 1;
     }
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)PMH_LDS_BYTES);
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     PC3D_REQUIRE(e == hipSuccess, "pointmlp3 screen: hipFuncSetAttribute(MaxDynamicSharedMemorySize): %s", hipGetErrorString(e));
     done[dev] = true;
+    if (PAIR && !DBG) pmp_ready[dev] = true;
   }
-  hipLaunchKernelGGL(kernel, dim3(a.ntiles, B), dim3(PM_FT), PMH_LDS_BYTES, st, a, d, q);
+  hipLaunchKernelGGL(kernel, dim3(a.ntiles, B), dim3(PM_FT), lds, st, a, d, q);
   return 0;
 }
 
+template <bool PAIR>
 static int pms_launch_h(const PMFwdArgs& a, int B, hipStream_t st, const PMScreenDbg& d, const PMScreenPrepH& q) {
-  if (d.dbg_S || d.dbg_E) return pms_launch_h_t<true, true>(a, B, st, d, q);
-  if (d.stats || d.stop_after) return pms_launch_h_t<true, false>(a, B, st, d, q);
-  return pms_launch_h_t<false, false>(a, B, st, d, q);
+  if (d.dbg_S || d.dbg_E) return pms_launch_h_t<true, true, PAIR>(a, B, st, d, q);
+  if (d.stats || d.stop_after) return pms_launch_h_t<true, false, PAIR>(a, B, st, d, q);
+  return pms_launch_h_t<false, false, PAIR>(a, B, st, d, q);
+}
+
+int pm_fwd_pair_ready() {
+  int dev = 0;
+  return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64 && pmp_ready[dev] ? 1 : 0;
 }
 
 // 0: launched. 1: not launched — the kernel needs its dynamic-LDS attribute, which is set at first use on a device and
@@ -941,11 +1049,13 @@ static int pms_launch_form(const PMFwdArgs& a, int B, hipStream_t st, const PMSc
 }
 
 int pm_fwd_screen_launch(const PMFwdArgs& a, int B, void* stream, int32_t* stats, float* dbg_S, float* dbg_E,
-                         int stop_after, const PMScreenPrep* prep, const PMScreenPrepH* hprep) {
+                         int stop_after, const PMScreenPrep* prep, const PMScreenPrepH* hprep, bool pair) {
   const PMScreenDbg d{stats, dbg_S, dbg_E, stop_after};
-  // the fp16 form when the caller asks for it by passing its image; like the forms below it steps aside while its
+  // the fp16 form when the caller asks for it by passing its image, its recheck by pair when asked for, else (and when
+  // that instantiation's first use falls into a capture) by channel; like the forms below it steps aside while its
   // first use on the device falls into a capture
-  if (hprep != nullptr && pms_launch_h(a, B, as_stream(stream), d, *hprep) == 0) return 0;
+  if (hprep != nullptr && pair && pms_launch_h<true>(a, B, as_stream(stream), d, *hprep) == 0) return 0;
+  if (hprep != nullptr && pms_launch_h<false>(a, B, as_stream(stream), d, *hprep) == 0) return 0;
   // the prepared form when the caller has the image; the in-launch form without one, and when the prepared
   // instantiation cannot be launched yet (its first use on the device falls into a capture)
   if (prep != nullptr && pms_launch_form<true>(a, B, as_stream(stream), d, *prep) == 0) return 0;

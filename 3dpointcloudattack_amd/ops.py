@@ -443,10 +443,21 @@ def _pm_w3_pack(weights, W3):
 # What pointmlp3_max_fwd_raw(form=None) runs from a prepared image: "bf16" or "fp16" (the same bits either way). fp16 since
 # r11: -8.2 us per headline step, 8.7 x the run-to-run spread.
 PM_FWD_DEFAULT_FORM = "fp16"
+# How the fp16 form rechecks its candidates when pointmlp3_max_fwd_raw(recheck=None): "channel" (a lane per channel, its
+# candidates in turn) or "pair" (a lane per (channel, candidate) pair); the same bits either way. pair since r12: -5.3 us
+# per headline step, 5.7 x the run-to-run spread.
+PM_FWD_DEFAULT_RECHECK = "pair"
+
+
+def pointmlp3_pair_recheck_ready(device):
+    """True once the pair recheck's production kernel can be launched on `device`: its dynamic-LDS attribute is set at
+    its first use outside a capture, and until then a launch that names recheck="pair" runs the channel recheck."""
+    with torch.cuda.device(device):
+        return bool(_lib.load().pc3d_pointmlp3_pair_recheck_ready())
 
 
 def pointmlp3_max_fwd_raw(x, weights, relu_last, T=None, x_cf=True, fold=True, want_masks=False, T_head=None, serial=False,
-                          exact=False, screen_dbg=None, in_launch=False, form=None):
+                          exact=False, screen_dbg=None, in_launch=False, form=None, recheck=None):
     """x [B,3,N] (x_cf) or [B,N,3]; weights = (W1[64,3], b1, W2[128,64], b2, W3[C3,128], b3) with eval-BN folded.
     Returns (pooled [B,C3] f32, argidx [B,C3] i32) and, with want_masks, a third item (mask1 [B,N] i64, mask2 [B,N,4]
     i32): the per-point ReLU decisions of layers 1 and 2 as bit masks, which pointmlp3_max_bwd_raw consumes.
@@ -464,7 +475,10 @@ def pointmlp3_max_fwd_raw(x, weights, relu_last, T=None, x_cf=True, fold=True, w
     form: which screen runs from the image — "bf16" the three-product bf16 screen, "fp16" the one-product scaled fp16
     screen (csrc/pointmlp_screen_h_bound.h; sixteen candidate slots per channel), None: PM_FWD_DEFAULT_FORM, but the
     bf16 one under screen_dbg (its figures are that form's unless the caller names the other). The same bits in every
-    output either way. Under form="fp16" screen_dbg's "S" and "E" come back in the unscaled domain."""
+    output either way. Under form="fp16" screen_dbg's "S" and "E" come back in the unscaled domain.
+    recheck: how the fp16 form rechecks — "channel", "pair" or None: PM_FWD_DEFAULT_RECHECK. Naming one with form=None
+    selects the fp16 form (under screen_dbg too, so "stats" and "stop_after" serve both); with form="bf16" it is an
+    error. The same bits in every output either way."""
     xp, xbs, xps, xcs, B, N = _pts(x, x_cf, "x")
     W1, b1, W2, b2, W3, b3 = weights[:6]
     for w in weights[:7]:
@@ -496,13 +510,19 @@ def pointmlp3_max_fwd_raw(x, weights, relu_last, T=None, x_cf=True, fold=True, w
         prep = None if exact or in_launch else _pm_w3_pack(weights, W3)
         if form not in (None, "bf16", "fp16"):
             raise ValueError("pointmlp3_max_fwd_raw: form is None, 'bf16' or 'fp16'")
+        if recheck not in (None, "channel", "pair"):
+            raise ValueError("pointmlp3_max_fwd_raw: recheck is None, 'channel' or 'pair'")
+        if recheck is not None and form == "bf16":
+            raise ValueError("pointmlp3_max_fwd_raw: recheck belongs to form='fp16'")
         if form is None:
-            form = PM_FWD_DEFAULT_FORM if screen_dbg is None else "bf16"
+            form = "fp16" if recheck is not None else PM_FWD_DEFAULT_FORM if screen_dbg is None else "bf16"
+        if recheck is None:
+            recheck = PM_FWD_DEFAULT_RECHECK
         if prep is not None:
             hp = _pm_w3_h(prep[0]) if form == "fp16" else None
             sfx, prep = "prep_", tuple(t.data_ptr() for t in prep)
             if hp is not None:
-                sfx, prep = "h_", prep + hp[1]
+                sfx, prep = "h_pair_" if recheck == "pair" else "h_", prep + hp[1]
         if T_head is not None:
             if T is not None:
                 raise ValueError("pointmlp3_max_fwd_raw: give T or T_head, not both")

@@ -468,6 +468,35 @@ int pc3d_pointmlp3_max_fwd_screen_dbg_h_f32(const float* x, int64_t x_bs, int64_
                                             float* dbg_S, float* dbg_E, int stop_after, const void* w3_bf,
                                             const float* w3_nw, const float* w3_q, const void* w3_h, const float* w3_cw,
                                             void* stream);
+/* The three entries above with the recheck laid out by (channel, candidate) PAIR, one lane each, instead of by channel
+ * (csrc/pointmlp_screen.hip): the same arguments, the same bits in every output, the same stats and stop_after cuts.
+ * A kernel instantiation of its own: while its first use on a device falls into a stream capture the launch runs the
+ * channel recheck. pc3d_pointmlp3_pair_recheck_ready: 1 once the production instantiation can be launched on the
+ * current device, 0 before. */
+int pc3d_pointmlp3_max_fwd_h_pair_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                      const float* T, const float* W1, const float* b1, const float* W2, const float* b2,
+                                      const float* W3, const float* b3, int C1, int C2, int C3, int relu_last,
+                                      float* part_val, int32_t* part_idx, float* pooled, int32_t* argidx,
+                                      uint64_t* mask1, uint32_t* mask2, const void* w3_bf, const float* w3_nw,
+                                      const float* w3_q, const void* w3_h, const float* w3_cw, void* stream);
+int pc3d_pointmlp3_max_fwd_h_pair_th_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                         const float* th_in, const float* th_W, const float* th_b, int th_K,
+                                         float* T_out, const float* W1, const float* b1, const float* W2,
+                                         const float* b2, const float* W3, const float* b3, int C1, int C2, int C3,
+                                         int relu_last, float* part_val, int32_t* part_idx, float* pooled,
+                                         int32_t* argidx, uint64_t* mask1, uint32_t* mask2, const void* w3_bf,
+                                         const float* w3_nw, const float* w3_q, const void* w3_h, const float* w3_cw,
+                                         void* stream);
+int pc3d_pointmlp3_max_fwd_screen_dbg_h_pair_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                                 const float* T, const float* th_in, const float* th_W,
+                                                 const float* th_b, int th_K, float* T_out, const float* W1,
+                                                 const float* b1, const float* W2, const float* b2, const float* W3,
+                                                 const float* b3, int C1, int C2, int C3, int relu_last, float* part_val,
+                                                 int32_t* part_idx, float* pooled, int32_t* argidx, uint64_t* mask1,
+                                                 uint32_t* mask2, int32_t* stats, float* dbg_S, float* dbg_E,
+                                                 int stop_after, const void* w3_bf, const float* w3_nw,
+                                                 const float* w3_q, const void* w3_h, const float* w3_cw, void* stream);
+int pc3d_pointmlp3_pair_recheck_ready(void);
 
 /* Backward-to-input of the above (weights are frozen during an attack: no weight gradients, SURVEY A-14).
  * g_pooled [B,C3] is the upstream gradient on `pooled`; with relu_last the caller zeroes it where pooled <= 0.

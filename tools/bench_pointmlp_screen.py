@@ -1,7 +1,9 @@
 """Stand-alone timing of the PointNet tower forward with layer 3 screened on the matrix pipe against the exact fp32 kernel
-(exact=True), in the three screened forms: `in_launch` makes its bf16 operands and norms from W3 inside every launch,
+(exact=True), in the screened forms: `in_launch` makes its bf16 operands and norms from W3 inside every launch,
 `prepared` reads them from the image made once per fold (three bf16 products per k-step), `fp16` reads the scaled fp16
-image in the same allocation (one product per k-step, sixteen candidate slots per channel). All inside replayed
+image in the same allocation (one product per k-step, sixteen candidate slots per channel) and rechecks by channel,
+`fp16_pair` is that form with the recheck by (channel, candidate) pair: its recheck + stores is
+fp16_pair_dbg_all_us - fp16_pair_dbg_select_us (the debug instantiation's columns), as for `fp16`. All inside replayed
 hipGraphs, alternated, at B = 32 and N = 1024 / 2048 / 4096, for both towers of bench.py's victim (seeded weights 0) on
 bench.py's kind of cloud. Also the screened launches cut short after each phase (prologue + norms, + screen,
 + selection; the debug instantiations) and the `stats` of the full launches: candidates rechecked per (tile, channel),
@@ -82,7 +84,8 @@ for N in [int(s) for s in args.sizes.split(",")]:
         C3 = w[4].shape[0]
         fns = [lambda: ops.pointmlp3_max_fwd_raw(x, w, relu_last, fold=False, exact=True, **kw)]
         names = ["exact"]
-        for form, sel in (("in_launch", dict(in_launch=True)), ("prepared", dict(form="bf16")), ("fp16", dict(form="fp16"))):
+        for form, sel in (("in_launch", dict(in_launch=True)), ("prepared", dict(form="bf16")),
+                          ("fp16", dict(form="fp16", recheck="channel")), ("fp16_pair", dict(form="fp16", recheck="pair"))):
             sc = ops.pointmlp3_max_fwd_raw(x, w, relu_last, want_masks=True, **sel, **kw)
             row["bit_equal_" + form] = bool(all(torch.equal(a, b) for a, b in zip((ex[0], ex[1]) + ex[2], (sc[0], sc[1]) + sc[2])))
             dbg = {}
