@@ -159,37 +159,15 @@ SIGNATURES = {
     "pc3d_cw_step_f32": _PTS + _PTS + [_P, _P] + _PTS + [_I, _I, _D, _D, _D, _D, _F, _P, _I, _I, _P, _P, _P, _P],
     "pc3d_pairwise_f32": _PTS + _PTS + [_I, _I, _I, _I, _P, _P],
     "pc3d_pointmlp3_tile_points": [],
-    "pc3d_pointmlp3_max_fwd_f32": _PTS + [_I, _I] + [_P] * 7 + [_I, _I, _I, _I] + [_P] * 6 + [_P],
-    "pc3d_pointmlp3_max_fwd_th_f32": _PTS + [_I, _I] + [_P, _P, _P, _I, _P] + [_P] * 6 + [_I, _I, _I, _I] + [_P] * 6 + [_P],
+    "pc3d_pointmlp3_max_fwd_f32": _PTS + [_I, _I] + [_P, _P, _P, _P, _I, _P] + [_P] * 6 + [_I, _I, _I, _I] + [_P] * 6
+    + [_I] + [_P] * 5 + [_P, _P, _P, _I] + [_P],
     "pc3d_pointmlp3_fold_f32": [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P],
-    "pc3d_pointmlp3_max_fwd_exact_f32": _PTS + [_I, _I] + [_P] * 7 + [_I, _I, _I, _I] + [_P] * 6 + [_P],
-    "pc3d_pointmlp3_max_fwd_exact_th_f32": _PTS + [_I, _I] + [_P, _P, _P, _I, _P] + [_P] * 6 + [_I, _I, _I, _I] + [_P] * 6 + [_P],
-    "pc3d_pointmlp3_max_fwd_screen_dbg_f32": _PTS + [_I, _I] + [_P, _P, _P, _P, _I, _P] + [_P] * 6 + [_I, _I, _I, _I]
-    + [_P] * 6 + [_P, _P, _P, _I, _P],
     "pc3d_pointmlp3_w3_prepare_f32": [_P, _I, _P, _P, _P, _P],
-    "pc3d_pointmlp3_max_fwd_prep_f32": _PTS + [_I, _I] + [_P] * 7 + [_I, _I, _I, _I] + [_P] * 6 + [_P, _P, _P] + [_P],
-    "pc3d_pointmlp3_max_fwd_prep_th_f32": _PTS + [_I, _I] + [_P, _P, _P, _I, _P] + [_P] * 6 + [_I, _I, _I, _I] + [_P] * 6
-    + [_P, _P, _P] + [_P],
-    "pc3d_pointmlp3_max_fwd_screen_dbg_prep_f32": _PTS + [_I, _I] + [_P, _P, _P, _P, _I, _P] + [_P] * 6 + [_I, _I, _I, _I]
-    + [_P] * 6 + [_P, _P, _P, _I] + [_P, _P, _P] + [_P],
     "pc3d_pointmlp3_w3_prepare_h_f32": [_P, _I, _P, _P, _P, _P],
-    "pc3d_pointmlp3_max_fwd_h_f32": _PTS + [_I, _I] + [_P] * 7 + [_I, _I, _I, _I] + [_P] * 6 + [_P] * 5 + [_P],
-    "pc3d_pointmlp3_max_fwd_h_th_f32": _PTS + [_I, _I] + [_P, _P, _P, _I, _P] + [_P] * 6 + [_I, _I, _I, _I] + [_P] * 6
-    + [_P] * 5 + [_P],
-    "pc3d_pointmlp3_max_fwd_screen_dbg_h_f32": _PTS + [_I, _I] + [_P, _P, _P, _P, _I, _P] + [_P] * 6 + [_I, _I, _I, _I]
-    + [_P] * 6 + [_P, _P, _P, _I] + [_P] * 5 + [_P],
-    "pc3d_pointmlp3_max_fwd_h_pair_f32": _PTS + [_I, _I] + [_P] * 7 + [_I, _I, _I, _I] + [_P] * 6 + [_P] * 5 + [_P],
-    "pc3d_pointmlp3_max_fwd_h_pair_th_f32": _PTS + [_I, _I] + [_P, _P, _P, _I, _P] + [_P] * 6 + [_I, _I, _I, _I] + [_P] * 6
-    + [_P] * 5 + [_P],
-    "pc3d_pointmlp3_max_fwd_screen_dbg_h_pair_f32": _PTS + [_I, _I] + [_P, _P, _P, _P, _I, _P] + [_P] * 6 + [_I, _I, _I, _I]
-    + [_P] * 6 + [_P, _P, _P, _I] + [_P] * 5 + [_P],
     "pc3d_pointmlp3_pair_recheck_ready": [],
     "pc3d_linear_pre_f32": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P],
-    "pc3d_pointmlp3_max_bwd_f32": _PTS + [_I, _I] + [_P] * 7 + [_I, _I, _I] + [_P, _P, _P, _P] + _PTS + [_P, _I, _P],
-    "pc3d_pointmlp3_max_bwd_twolist_f32": _PTS + [_I, _I] + [_P] * 7 + [_I, _I, _I] + [_P, _P, _P, _P] + _PTS + [_P, _I, _P],
-    "pc3d_pointmlp3_max_bwd_tile32_f32": _PTS + [_I, _I] + [_P] * 7 + [_I, _I, _I] + [_P, _P, _P, _P] + _PTS + [_P, _I, _P],
-    "pc3d_pointmlp3_max_bwd_packed_dbg_f32": _PTS + [_I, _I] + [_P] * 7 + [_I, _I, _I] + [_P, _P, _P, _P] + _PTS
-    + [_P, _I, _I, _P],
+    "pc3d_pointmlp3_max_bwd_f32": _PTS + [_I, _I] + [_P] * 7 + [_I, _I, _I] + [_P, _P, _P, _P] + _PTS
+    + [_P, _I, _I, _I, _P],
     "pc3d_pointmlp3_bwd_tile_points": [],
     "pc3d_pointnet_ft_tower_fwd_f32": _PTS + [_I, _I] + [_P] * 6 + [_L] + [_P] * 3 + [_I] + [_P] * 5 + [_P],
     "pc3d_pointnet_ft_fold_w2_f32": [_P, _P, _I, _P, _P],
@@ -202,11 +180,7 @@ SIGNATURES = {
     "pc3d_linear_book_f32": [_P, _I, _I, _I, _I, _P, _P, _I, _I, _F, _P, _I, _F, _P, _I] + _PTS + _PTS
     + [_I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P] + [_D, _D, _D, _P, _P, _I, _P],
     "pc3d_pointmlp3_max_bwd_update_f32": _PTS + [_I, _I] + [_P] * 6 + [_I, _I, _I] + [_P, _P, _P, _P] + _PTS + _PTS
-    + [_P, _P, _D, _D, _D, _F, _P, _I, _P, _P, _P, _P],
-    "pc3d_pointmlp3_max_bwd_update_tile32_f32": _PTS + [_I, _I] + [_P] * 6 + [_I, _I, _I] + [_P, _P, _P, _P] + _PTS + _PTS
-    + [_P, _P, _D, _D, _D, _F, _P, _I, _P, _P, _P, _P],
-    "pc3d_pointmlp3_max_bwd_update_packed_f32": _PTS + [_I, _I] + [_P] * 6 + [_I, _I, _I] + [_P, _P, _P, _P] + _PTS + _PTS
-    + [_P, _P, _D, _D, _D, _F, _P, _I, _P, _P, _P, _P],
+    + [_P, _P, _D, _D, _D, _F, _P, _I, _P, _P, _P, _I, _P],
     "pc3d_cls_loss_f32": [_P, _I, _I, _I, _P, _I, _F, _F, _P, _P, _P, _P, _P],
     "pc3d_sor_select_f32": [_P] + _PTS + [_I, _I, _I, _D, _I, _P, _P, _P, _P, _P] + _PTS + [_P],
     "pc3d_sor_fused_f32": _PTS + [_I, _I, _I, _D, _I, _P, _P, _P, _P, _P, _P] + _PTS + [_P],

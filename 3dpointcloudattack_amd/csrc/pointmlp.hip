@@ -1240,14 +1240,28 @@ using namespace pc3d;
 extern "C" int pc3d_pointmlp3_tile_points(void) { return PM_TP; }
 extern "C" int pc3d_pointmlp3_bwd_tile_points(void) { return PM_BTP; }
 
-static int pm_fwd_launch(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N, const float* T,
-                         const float* th_in, const float* th_W, const float* th_b, int th_K, float* th_out,
-                         const float* W1, const float* b1, const float* W2, const float* b2, const float* W3,
-                         const float* b3, int C1, int C2, int C3, int relu_last, float* part_val, int32_t* part_idx,
-                         float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2, void* stream,
-                         bool exact = false, int32_t* stats = nullptr, float* dbg_S = nullptr, float* dbg_E = nullptr,
-                         int stop_after = 0, const PMScreenPrep* prep = nullptr, const PMScreenPrepH* hprep = nullptr,
-                         bool pair = false) {
+// The tower forward in every form (include/pc3d.h states the argument rules; they are checked here, before any HIP call).
+// Layer 3 is screened on the matrix pipe and rechecked exactly (pointmlp_screen.hip: the same bits) at every shape this
+// entry accepts; the exact kernel on request, and when no screened instantiation can be launched yet.
+extern "C" int pc3d_pointmlp3_max_fwd_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                          const float* T, const float* th_in, const float* th_W, const float* th_b,
+                                          int th_K, float* T_out, const float* W1, const float* b1, const float* W2,
+                                          const float* b2, const float* W3, const float* b3, int C1, int C2, int C3,
+                                          int relu_last, float* part_val, int32_t* part_idx, float* pooled,
+                                          int32_t* argidx, uint64_t* mask1, uint32_t* mask2, int form, const void* w3_bf,
+                                          const float* w3_nw, const float* w3_q, const void* w3_h, const float* w3_cw,
+                                          int32_t* stats, float* dbg_S, float* dbg_E, int stop_after, void* stream) {
+  PC3D_REQUIRE(form >= PC3D_PM_FWD_EXACT && form <= PC3D_PM_FWD_SCREEN_H_PAIR, "pc3d_pointmlp3_max_fwd_f32: unknown form %d", form);
+  PC3D_REQUIRE(th_in == nullptr || (T == nullptr && th_W && th_b && T_out && th_K >= 1),
+               "pc3d_pointmlp3_max_fwd_f32: T or a complete transform head (input, weights [9,K], bias [9], T_out), not both");
+  PC3D_REQUIRE(stats != nullptr || (dbg_S == nullptr && dbg_E == nullptr && stop_after == 0),
+               "pc3d_pointmlp3_max_fwd_f32: dbg_S, dbg_E and stop_after belong to the debug launch, which stats [B, ntiles, 2] selects");
+  PC3D_REQUIRE((dbg_S == nullptr) == (dbg_E == nullptr), "pc3d_pointmlp3_max_fwd_f32: dbg_S and dbg_E go together");
+  PC3D_REQUIRE(stop_after >= 0 && stop_after <= 3, "pc3d_pointmlp3_max_fwd_f32: stop_after = %d", stop_after);
+  PC3D_REQUIRE(form != PC3D_PM_FWD_EXACT || stats == nullptr, "pc3d_pointmlp3_max_fwd_f32: stats belongs to a screened form");
+  PC3D_REQUIRE(form < PC3D_PM_FWD_SCREEN_PREP || (w3_bf && w3_nw && w3_q),
+               "pc3d_pointmlp3_max_fwd_f32: the prepared image needs w3_bf, w3_nw and w3_q");
+  PC3D_REQUIRE(form < PC3D_PM_FWD_SCREEN_H || (w3_h && w3_cw), "pc3d_pointmlp3_max_fwd_f32: both prepared images are needed");
   PC3D_REQUIRE(B >= 0 && N >= 1, "pc3d_pointmlp3_max_fwd_f32: bad sizes B=%d N=%d", B, N);
   PC3D_REQUIRE(C1 == PM_C1 && C2 == PM_C2 && C3 >= 32 && C3 % 32 == 0 && C3 <= PM_MAXC3F,
                "pc3d_pointmlp3_max_fwd_f32: unsupported widths %d/%d/%d (need 64/128/multiple of 32 <= 1024)", C1, C2, C3);
@@ -1261,14 +1275,13 @@ static int pm_fwd_launch(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_c
                "pc3d_pointmlp3_max_fwd_f32: mask1 and mask2 must both be given or both be NULL");
   const int ntiles = cdiv(N, PM_TP);
   PMFwdArgs a{{x, x_bs, x_ps, x_cs}, N, C3, ntiles, T, W1, b1, W2, b2, W3, b3, part_val, part_idx, mask1, mask2,
-              th_in, th_W, th_b, th_K, th_out};
+              th_in, th_W, th_b, th_K, T_out};
   hipStream_t st = as_stream(stream);
-  // Layer 3 screened on bf16 MFMA and rechecked exactly (pointmlp_screen.hip: the same bits) at every shape this entry
-  // accepts, from the prepared image of W3 when the caller passes one (with its fp16 image, hprep: the one-product fp16
-  // screen); the exact kernel on request, and when the screened one cannot be launched yet (see pm_fwd_screen_launch).
   int rc = 1;
-  if (!exact) {
-    rc = pm_fwd_screen_launch(a, B, stream, stats, dbg_S, dbg_E, stop_after, prep, hprep, pair);
+  if (form != PC3D_PM_FWD_EXACT) {
+    const PMScreenPrep q{reinterpret_cast<decltype(PMScreenPrep::w3_bf)>(w3_bf), w3_nw, reinterpret_cast<const float4*>(w3_q)};
+    const PMScreenPrepH qh{reinterpret_cast<decltype(PMScreenPrepH::w3_h)>(w3_h), w3_cw, w3_nw, reinterpret_cast<const float4*>(w3_q)};
+    rc = pm_fwd_screen_launch(a, B, stream, stats, dbg_S, dbg_E, stop_after, form, q, qh);
     if (rc < 0) return rc;
   }
   if (rc != 0) hipLaunchKernelGGL(pointmlp3_max_fwd_kernel, dim3(ntiles, B), dim3(PM_FT), 0, st, a);
@@ -1298,74 +1311,7 @@ extern "C" int pc3d_pointmlp3_fold_f32(const float* part_val, const int32_t* par
   return PC3D_OK;
 }
 
-extern "C" int pc3d_pointmlp3_max_fwd_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
-                                          const float* T, const float* W1, const float* b1, const float* W2,
-                                          const float* b2, const float* W3, const float* b3, int C1, int C2,
-                                          int C3, int relu_last, float* part_val, int32_t* part_idx,
-                                          float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2,
-                                          void* stream) {
-  return pm_fwd_launch(x, x_bs, x_ps, x_cs, B, N, T, nullptr, nullptr, nullptr, 0, nullptr, W1, b1, W2, b2, W3, b3, C1, C2,
-                       C3, relu_last, part_val, part_idx, pooled, argidx, mask1, mask2, stream);
-}
-
-extern "C" int pc3d_pointmlp3_max_fwd_th_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
-                                             const float* th_in, const float* th_W, const float* th_b, int th_K,
-                                             float* T_out, const float* W1, const float* b1, const float* W2,
-                                             const float* b2, const float* W3, const float* b3, int C1, int C2, int C3,
-                                             int relu_last, float* part_val, int32_t* part_idx, float* pooled,
-                                             int32_t* argidx, uint64_t* mask1, uint32_t* mask2, void* stream) {
-  PC3D_REQUIRE(th_in && th_W && th_b && T_out && th_K >= 1,
-               "pc3d_pointmlp3_max_fwd_th_f32: the transform head needs its input, weights [9,K], bias [9] and T_out");
-  return pm_fwd_launch(x, x_bs, x_ps, x_cs, B, N, nullptr, th_in, th_W, th_b, th_K, T_out, W1, b1, W2, b2, W3, b3, C1, C2,
-                       C3, relu_last, part_val, part_idx, pooled, argidx, mask1, mask2, stream);
-}
-
-extern "C" int pc3d_pointmlp3_max_fwd_exact_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
-                                                const float* T, const float* W1, const float* b1, const float* W2,
-                                                const float* b2, const float* W3, const float* b3, int C1, int C2,
-                                                int C3, int relu_last, float* part_val, int32_t* part_idx,
-                                                float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2,
-                                                void* stream) {
-  return pm_fwd_launch(x, x_bs, x_ps, x_cs, B, N, T, nullptr, nullptr, nullptr, 0, nullptr, W1, b1, W2, b2, W3, b3, C1, C2,
-                       C3, relu_last, part_val, part_idx, pooled, argidx, mask1, mask2, stream, true);
-}
-
-extern "C" int pc3d_pointmlp3_max_fwd_exact_th_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
-                                                   const float* th_in, const float* th_W, const float* th_b, int th_K,
-                                                   float* T_out, const float* W1, const float* b1, const float* W2,
-                                                   const float* b2, const float* W3, const float* b3, int C1, int C2,
-                                                   int C3, int relu_last, float* part_val, int32_t* part_idx,
-                                                   float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2,
-                                                   void* stream) {
-  PC3D_REQUIRE(th_in && th_W && th_b && T_out && th_K >= 1,
-               "pc3d_pointmlp3_max_fwd_exact_th_f32: the transform head needs its input, weights [9,K], bias [9] and T_out");
-  return pm_fwd_launch(x, x_bs, x_ps, x_cs, B, N, nullptr, th_in, th_W, th_b, th_K, T_out, W1, b1, W2, b2, W3, b3, C1, C2,
-                       C3, relu_last, part_val, part_idx, pooled, argidx, mask1, mask2, stream, true);
-}
-
-extern "C" int pc3d_pointmlp3_max_fwd_screen_dbg_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B,
-                                                     int N, const float* T, const float* th_in, const float* th_W,
-                                                     const float* th_b, int th_K, float* T_out, const float* W1,
-                                                     const float* b1, const float* W2, const float* b2, const float* W3,
-                                                     const float* b3, int C1, int C2, int C3, int relu_last,
-                                                     float* part_val, int32_t* part_idx, float* pooled, int32_t* argidx,
-                                                     uint64_t* mask1, uint32_t* mask2, int32_t* stats, float* dbg_S,
-                                                     float* dbg_E, int stop_after, void* stream) {
-  PC3D_REQUIRE(stats != nullptr, "pc3d_pointmlp3_max_fwd_screen_dbg_f32: stats [B, ntiles, 2] is required");
-  PC3D_REQUIRE((dbg_S == nullptr) == (dbg_E == nullptr), "pc3d_pointmlp3_max_fwd_screen_dbg_f32: dbg_S and dbg_E go together");
-  PC3D_REQUIRE(stop_after >= 0 && stop_after <= 3, "pc3d_pointmlp3_max_fwd_screen_dbg_f32: stop_after = %d", stop_after);
-  PC3D_REQUIRE(th_in == nullptr || (T == nullptr && th_W && th_b && T_out && th_K >= 1),
-               "pc3d_pointmlp3_max_fwd_screen_dbg_f32: T or a complete transform head, not both");
-  return pm_fwd_launch(x, x_bs, x_ps, x_cs, B, N, T, th_in, th_W, th_b, th_K, T_out, W1, b1, W2, b2, W3, b3, C1, C2, C3,
-                       relu_last, part_val, part_idx, pooled, argidx, mask1, mask2, stream, false, stats, dbg_S, dbg_E,
-                       stop_after);
-}
-
-// ---- the launches above fed from a prepared image of W3 (pc3d_pointmlp3_w3_prepare_f32 made it from the same W3)
-static PMScreenPrep pm_prep(const void* w3_bf, const float* w3_nw, const float* w3_q) {
-  return PMScreenPrep{reinterpret_cast<decltype(PMScreenPrep::w3_bf)>(w3_bf), w3_nw, reinterpret_cast<const float4*>(w3_q)};
-}
-
+// ---- the prepared images of W3 that the SCREEN_PREP and SCREEN_H forms read (pointmlp_screen.hip)
 extern "C" int pc3d_pointmlp3_w3_prepare_f32(const float* W3, int C3, void* w3_bf, float* w3_nw, float* w3_q, void* stream) {
   PC3D_REQUIRE(C3 >= 32 && C3 % 32 == 0 && C3 <= PM_MAXC3F, "pc3d_pointmlp3_w3_prepare_f32: C3 = %d (need a multiple of 32 <= 1024)", C3);
   PC3D_REQUIRE(W3 && w3_bf && w3_nw && w3_q, "pc3d_pointmlp3_w3_prepare_f32: null pointer");
@@ -1374,59 +1320,6 @@ extern "C" int pc3d_pointmlp3_w3_prepare_f32(const float* W3, int C3, void* w3_b
   return PC3D_OK;
 }
 
-extern "C" int pc3d_pointmlp3_max_fwd_prep_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
-                                               const float* T, const float* W1, const float* b1, const float* W2,
-                                               const float* b2, const float* W3, const float* b3, int C1, int C2, int C3,
-                                               int relu_last, float* part_val, int32_t* part_idx, float* pooled,
-                                               int32_t* argidx, uint64_t* mask1, uint32_t* mask2, const void* w3_bf,
-                                               const float* w3_nw, const float* w3_q, void* stream) {
-  PC3D_REQUIRE(w3_bf && w3_nw && w3_q, "pc3d_pointmlp3_max_fwd_prep_f32: the prepared image needs w3_bf, w3_nw and w3_q");
-  const PMScreenPrep q = pm_prep(w3_bf, w3_nw, w3_q);
-  return pm_fwd_launch(x, x_bs, x_ps, x_cs, B, N, T, nullptr, nullptr, nullptr, 0, nullptr, W1, b1, W2, b2, W3, b3, C1, C2,
-                       C3, relu_last, part_val, part_idx, pooled, argidx, mask1, mask2, stream, false, nullptr, nullptr,
-                       nullptr, 0, &q);
-}
-
-extern "C" int pc3d_pointmlp3_max_fwd_prep_th_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
-                                                  const float* th_in, const float* th_W, const float* th_b, int th_K,
-                                                  float* T_out, const float* W1, const float* b1, const float* W2,
-                                                  const float* b2, const float* W3, const float* b3, int C1, int C2,
-                                                  int C3, int relu_last, float* part_val, int32_t* part_idx,
-                                                  float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2,
-                                                  const void* w3_bf, const float* w3_nw, const float* w3_q, void* stream) {
-  PC3D_REQUIRE(th_in && th_W && th_b && T_out && th_K >= 1,
-               "pc3d_pointmlp3_max_fwd_prep_th_f32: the transform head needs its input, weights [9,K], bias [9] and T_out");
-  PC3D_REQUIRE(w3_bf && w3_nw && w3_q, "pc3d_pointmlp3_max_fwd_prep_th_f32: the prepared image needs w3_bf, w3_nw and w3_q");
-  const PMScreenPrep q = pm_prep(w3_bf, w3_nw, w3_q);
-  return pm_fwd_launch(x, x_bs, x_ps, x_cs, B, N, nullptr, th_in, th_W, th_b, th_K, T_out, W1, b1, W2, b2, W3, b3, C1, C2,
-                       C3, relu_last, part_val, part_idx, pooled, argidx, mask1, mask2, stream, false, nullptr, nullptr,
-                       nullptr, 0, &q);
-}
-
-extern "C" int pc3d_pointmlp3_max_fwd_screen_dbg_prep_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B,
-                                                          int N, const float* T, const float* th_in, const float* th_W,
-                                                          const float* th_b, int th_K, float* T_out, const float* W1,
-                                                          const float* b1, const float* W2, const float* b2,
-                                                          const float* W3, const float* b3, int C1, int C2, int C3,
-                                                          int relu_last, float* part_val, int32_t* part_idx, float* pooled,
-                                                          int32_t* argidx, uint64_t* mask1, uint32_t* mask2, int32_t* stats,
-                                                          float* dbg_S, float* dbg_E, int stop_after, const void* w3_bf,
-                                                          const float* w3_nw, const float* w3_q, void* stream) {
-  PC3D_REQUIRE(stats != nullptr, "pc3d_pointmlp3_max_fwd_screen_dbg_prep_f32: stats [B, ntiles, 2] is required");
-  PC3D_REQUIRE((dbg_S == nullptr) == (dbg_E == nullptr), "pc3d_pointmlp3_max_fwd_screen_dbg_prep_f32: dbg_S and dbg_E go together");
-  PC3D_REQUIRE(stop_after >= 0 && stop_after <= 3, "pc3d_pointmlp3_max_fwd_screen_dbg_prep_f32: stop_after = %d", stop_after);
-  PC3D_REQUIRE(th_in == nullptr || (T == nullptr && th_W && th_b && T_out && th_K >= 1),
-               "pc3d_pointmlp3_max_fwd_screen_dbg_prep_f32: T or a complete transform head, not both");
-  PC3D_REQUIRE(w3_bf && w3_nw && w3_q, "pc3d_pointmlp3_max_fwd_screen_dbg_prep_f32: the prepared image needs w3_bf, w3_nw and w3_q");
-  const PMScreenPrep q = pm_prep(w3_bf, w3_nw, w3_q);
-  return pm_fwd_launch(x, x_bs, x_ps, x_cs, B, N, T, th_in, th_W, th_b, th_K, T_out, W1, b1, W2, b2, W3, b3, C1, C2, C3,
-                       relu_last, part_val, part_idx, pooled, argidx, mask1, mask2, stream, false, stats, dbg_S, dbg_E,
-                       stop_after, &q);
-}
-
-// ---- the same launches with layer 3 screened by ONE scaled fp16 product (the H form of pointmlp_screen.hip), fed from
-// the bf16 image's w3_nw / w3_q and the fp16 image w3_h / w3_cw that pc3d_pointmlp3_w3_prepare_h_f32 made from them. The
-// bf16 image itself is passed along: it serves when the H instantiation's first use on a device falls into a capture.
 extern "C" int pc3d_pointmlp3_w3_prepare_h_f32(const float* W3, int C3, const float* w3_nw, void* w3_h, float* w3_cw,
                                                void* stream) {
   PC3D_REQUIRE(C3 >= 32 && C3 % 32 == 0 && C3 <= PM_MAXC3F, "pc3d_pointmlp3_w3_prepare_h_f32: C3 = %d (need a multiple of 32 <= 1024)", C3);
@@ -1436,113 +1329,12 @@ extern "C" int pc3d_pointmlp3_w3_prepare_h_f32(const float* W3, int C3, const fl
   return PC3D_OK;
 }
 
-static PMScreenPrepH pm_prep_h(const void* w3_h, const float* w3_cw, const float* w3_nw, const float* w3_q) {
-  return PMScreenPrepH{reinterpret_cast<decltype(PMScreenPrepH::w3_h)>(w3_h), w3_cw, w3_nw, reinterpret_cast<const float4*>(w3_q)};
-}
-
-// one body for the H entries: T or a transform head or neither; stats null for the production instantiation, else the
-// debug one (stats / dbg_S / dbg_E / stop_after as in pc3d_pointmlp3_max_fwd_screen_dbg_f32; dbg_S and dbg_E come back
-// in the unscaled domain, S 2^-(sa + sw), E 2^-(sa + sw)). pair: the recheck by (channel, candidate) pair.
-static int pm_fwd_h(const char* who, bool pair, bool th, bool dbg, const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs,
-                    int B, int N, const float* T, const float* th_in, const float* th_W, const float* th_b, int th_K,
-                    float* T_out, const float* W1, const float* b1, const float* W2, const float* b2, const float* W3,
-                    const float* b3, int C1, int C2, int C3, int relu_last, float* part_val, int32_t* part_idx,
-                    float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2, int32_t* stats, float* dbg_S,
-                    float* dbg_E, int stop_after, const void* w3_bf, const float* w3_nw, const float* w3_q,
-                    const void* w3_h, const float* w3_cw, void* stream) {
-  if (dbg) {
-    PC3D_REQUIRE(stats != nullptr, "%s: stats [B, ntiles, 2] is required", who);
-    PC3D_REQUIRE((dbg_S == nullptr) == (dbg_E == nullptr), "%s: dbg_S and dbg_E go together", who);
-    PC3D_REQUIRE(stop_after >= 0 && stop_after <= 3, "%s: stop_after = %d", who, stop_after);
-    PC3D_REQUIRE(th_in == nullptr || (T == nullptr && th_W && th_b && T_out && th_K >= 1),
-                 "%s: T or a complete transform head, not both", who);
-  }
-  if (th)
-    PC3D_REQUIRE(th_in && th_W && th_b && T_out && th_K >= 1,
-                 "%s: the transform head needs its input, weights [9,K], bias [9] and T_out", who);
-  PC3D_REQUIRE(w3_bf && w3_nw && w3_q && w3_h && w3_cw, "%s: both prepared images are needed", who);
-  const PMScreenPrep q = pm_prep(w3_bf, w3_nw, w3_q);
-  const PMScreenPrepH qh = pm_prep_h(w3_h, w3_cw, w3_nw, w3_q);
-  return pm_fwd_launch(x, x_bs, x_ps, x_cs, B, N, T, th_in, th_W, th_b, th_K, T_out, W1, b1, W2, b2, W3, b3, C1, C2, C3,
-                       relu_last, part_val, part_idx, pooled, argidx, mask1, mask2, stream, false, stats, dbg_S, dbg_E,
-                       stop_after, &q, &qh, pair);
-}
-
-// the three H entries, and the same three with the recheck by pair (PC3D_H_ENTRIES(infix, pair))
-#define PC3D_H_ENTRIES(NAME, PAIR)                                                                                          \
-  extern "C" int pc3d_pointmlp3_max_fwd_##NAME##_f32(                                                                       \
-      const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N, const float* T, const float* W1,             \
-      const float* b1, const float* W2, const float* b2, const float* W3, const float* b3, int C1, int C2, int C3,         \
-      int relu_last, float* part_val, int32_t* part_idx, float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2, \
-      const void* w3_bf, const float* w3_nw, const float* w3_q, const void* w3_h, const float* w3_cw, void* stream) {       \
-    return pm_fwd_h("pc3d_pointmlp3_max_fwd_" #NAME "_f32", PAIR, false, false, x, x_bs, x_ps, x_cs, B, N, T, nullptr,     \
-                    nullptr, nullptr, 0, nullptr, W1, b1, W2, b2, W3, b3, C1, C2, C3, relu_last, part_val, part_idx,       \
-                    pooled, argidx, mask1, mask2, nullptr, nullptr, nullptr, 0, w3_bf, w3_nw, w3_q, w3_h, w3_cw, stream);  \
-  }                                                                                                                         \
-  extern "C" int pc3d_pointmlp3_max_fwd_##NAME##_th_f32(                                                                    \
-      const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N, const float* th_in, const float* th_W,       \
-      const float* th_b, int th_K, float* T_out, const float* W1, const float* b1, const float* W2, const float* b2,       \
-      const float* W3, const float* b3, int C1, int C2, int C3, int relu_last, float* part_val, int32_t* part_idx,         \
-      float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2, const void* w3_bf, const float* w3_nw,             \
-      const float* w3_q, const void* w3_h, const float* w3_cw, void* stream) {                                              \
-    return pm_fwd_h("pc3d_pointmlp3_max_fwd_" #NAME "_th_f32", PAIR, true, false, x, x_bs, x_ps, x_cs, B, N, nullptr,      \
-                    th_in, th_W, th_b, th_K, T_out, W1, b1, W2, b2, W3, b3, C1, C2, C3, relu_last, part_val, part_idx,     \
-                    pooled, argidx, mask1, mask2, nullptr, nullptr, nullptr, 0, w3_bf, w3_nw, w3_q, w3_h, w3_cw, stream);  \
-  }                                                                                                                         \
-  extern "C" int pc3d_pointmlp3_max_fwd_screen_dbg_##NAME##_f32(                                                            \
-      const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N, const float* T, const float* th_in,          \
-      const float* th_W, const float* th_b, int th_K, float* T_out, const float* W1, const float* b1, const float* W2,     \
-      const float* b2, const float* W3, const float* b3, int C1, int C2, int C3, int relu_last, float* part_val,           \
-      int32_t* part_idx, float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2, int32_t* stats, float* dbg_S,   \
-      float* dbg_E, int stop_after, const void* w3_bf, const float* w3_nw, const float* w3_q, const void* w3_h,            \
-      const float* w3_cw, void* stream) {                                                                                   \
-    return pm_fwd_h("pc3d_pointmlp3_max_fwd_screen_dbg_" #NAME "_f32", PAIR, false, true, x, x_bs, x_ps, x_cs, B, N, T,    \
-                    th_in, th_W, th_b, th_K, T_out, W1, b1, W2, b2, W3, b3, C1, C2, C3, relu_last, part_val, part_idx,     \
-                    pooled, argidx, mask1, mask2, stats, dbg_S, dbg_E, stop_after, w3_bf, w3_nw, w3_q, w3_h, w3_cw,        \
-                    stream);                                                                                                \
-  }
-PC3D_H_ENTRIES(h, false)
-PC3D_H_ENTRIES(h_pair, true)
-#undef PC3D_H_ENTRIES
-
 // 1 once the production pair instantiation can be launched on the current device (its dynamic-LDS attribute is set at
 // its first use outside a capture); 0 before: a launch that asks for the pair recheck then runs the channel one
 extern "C" int pc3d_pointmlp3_pair_recheck_ready(void) { return pm_fwd_pair_ready(); }
 
-// which kernel the default entries launch (pc3d_pointmlp3_max_bwd_f32 / _update_f32); every form stays reachable by name
-constexpr bool PM_BWD_DEFAULT_PACKED = true;
-enum PMBwdForm { PM_BWD_PACKED = 0, PM_BWD_TILE32 = 1, PM_BWD_TWOLIST = 2 };   // 10 + k: packed, ended after phase k
-
-static int pm_bwd_launch(const char* who, int form, const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B,
-                         int N, const float* T, const float* W1, const float* b1, const float* W2, const float* b2,
-                         const float* W3, const float* W2T, int C1, int C2, int C3, const int32_t* argidx,
-                         const uint64_t* mask1, const uint32_t* mask2, const float* g_pooled, float* grad_x,
-                         int64_t gx_bs, int64_t gx_ps, int64_t gx_cs, float* part_gT, int accumulate, void* stream) {
-  PC3D_REQUIRE(B >= 0 && N >= 1, "%s: bad sizes B=%d N=%d", who, B, N);
-  PC3D_REQUIRE(C1 == PM_C1 && C2 == PM_C2 && C3 >= 32 && C3 % 32 == 0 && C3 <= PM_MAXC3,
-               "%s: unsupported widths %d/%d/%d", who, C1, C2, C3);
-  PC3D_REQUIRE(B <= 65535, "%s: B=%d exceeds grid.y limit", who, B);
-  if (B == 0) return PC3D_OK;
-  PC3D_REQUIRE(x && W1 && b1 && W2 && b2 && W3 && W2T && argidx && mask1 && mask2 && g_pooled && grad_x,
-               "%s: null pointer", who);
-  PMBwdArgs a{{x, x_bs, x_ps, x_cs}, N, C3, T, W1, b1, W2, b2, W3, W2T, argidx, mask1, mask2, g_pooled, {grad_x, gx_bs, gx_ps, gx_cs},
-              part_gT, accumulate};
-  const dim3 g32(cdiv(N, PM_BTP), B), gp(cdiv(N, PM_PTP), B);
-  hipStream_t st = as_stream(stream);
-  switch (form) {
-    case PM_BWD_TWOLIST: hipLaunchKernelGGL(pointmlp3_max_bwd_twolist_kernel, g32, dim3(256), 0, st, a); break;
-    case PM_BWD_TILE32: hipLaunchKernelGGL(pointmlp3_max_bwd_kernel, g32, dim3(256), 0, st, a); break;
-    case PM_BWD_PACKED: hipLaunchKernelGGL(pointmlp3_max_bwd_packed_kernel, gp, dim3(PM_PNT), 0, st, a); break;
-    case 11: hipLaunchKernelGGL(pointmlp3_max_bwd_packed_dbg_kernel<1>, gp, dim3(PM_PNT), 0, st, a); break;
-    case 12: hipLaunchKernelGGL(pointmlp3_max_bwd_packed_dbg_kernel<2>, gp, dim3(PM_PNT), 0, st, a); break;
-    case 13: hipLaunchKernelGGL(pointmlp3_max_bwd_packed_dbg_kernel<3>, gp, dim3(PM_PNT), 0, st, a); break;
-    case 14: hipLaunchKernelGGL(pointmlp3_max_bwd_packed_dbg_kernel<4>, gp, dim3(PM_PNT), 0, st, a); break;
-    case 15: hipLaunchKernelGGL(pointmlp3_max_bwd_packed_dbg_kernel<5>, gp, dim3(PM_PNT), 0, st, a); break;
-    default: PC3D_REQUIRE(false, "%s: unknown form %d", who, form);
-  }
-  PC3D_LAUNCH_CHECK(who);
-  return PC3D_OK;
-}
+// which kernel PC3D_PM_BWD_DEFAULT launches in the two backward entries; every form stays reachable by its own value
+constexpr int PM_BWD_DEFAULT_FORM = PC3D_PM_BWD_PACKED;
 
 extern "C" int pc3d_pointmlp3_max_bwd_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
                                           const float* T, const float* W1, const float* b1, const float* W2,
@@ -1550,99 +1342,70 @@ extern "C" int pc3d_pointmlp3_max_bwd_f32(const float* x, int64_t x_bs, int64_t 
                                           int C3, const int32_t* argidx, const uint64_t* mask1,
                                           const uint32_t* mask2, const float* g_pooled, float* grad_x,
                                           int64_t gx_bs, int64_t gx_ps, int64_t gx_cs, float* part_gT,
-                                          int accumulate, void* stream) {
-  return pm_bwd_launch("pc3d_pointmlp3_max_bwd_f32", PM_BWD_DEFAULT_PACKED ? PM_BWD_PACKED : PM_BWD_TILE32, x, x_bs,
-                       x_ps, x_cs, B, N, T, W1, b1, W2, b2, W3, W2T, C1, C2, C3, argidx, mask1, mask2, g_pooled, grad_x,
-                       gx_bs, gx_ps, gx_cs, part_gT, accumulate, stream);
-}
-
-extern "C" int pc3d_pointmlp3_max_bwd_tile32_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B,
-                                                 int N, const float* T, const float* W1, const float* b1,
-                                                 const float* W2, const float* b2, const float* W3, const float* W2T,
-                                                 int C1, int C2, int C3, const int32_t* argidx,
-                                                 const uint64_t* mask1, const uint32_t* mask2, const float* g_pooled,
-                                                 float* grad_x, int64_t gx_bs, int64_t gx_ps, int64_t gx_cs,
-                                                 float* part_gT, int accumulate, void* stream) {
-  return pm_bwd_launch("pc3d_pointmlp3_max_bwd_tile32_f32", PM_BWD_TILE32, x, x_bs, x_ps, x_cs, B, N, T, W1, b1, W2, b2,
-                       W3, W2T, C1, C2, C3, argidx, mask1, mask2, g_pooled, grad_x, gx_bs, gx_ps, gx_cs, part_gT,
-                       accumulate, stream);
-}
-
-extern "C" int pc3d_pointmlp3_max_bwd_packed_dbg_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B,
-                                                     int N, const float* T, const float* W1, const float* b1,
-                                                     const float* W2, const float* b2, const float* W3,
-                                                     const float* W2T, int C1, int C2, int C3, const int32_t* argidx,
-                                                     const uint64_t* mask1, const uint32_t* mask2,
-                                                     const float* g_pooled, float* grad_x, int64_t gx_bs, int64_t gx_ps,
-                                                     int64_t gx_cs, float* part_gT, int accumulate, int stop_after,
-                                                     void* stream) {
-  PC3D_REQUIRE(stop_after >= 0 && stop_after <= 5, "pc3d_pointmlp3_max_bwd_packed_dbg_f32: stop_after = %d", stop_after);
-  return pm_bwd_launch("pc3d_pointmlp3_max_bwd_packed_dbg_f32", stop_after ? 10 + stop_after : PM_BWD_PACKED, x, x_bs,
-                       x_ps, x_cs, B, N, T, W1, b1, W2, b2, W3, W2T, C1, C2, C3, argidx, mask1, mask2, g_pooled, grad_x,
-                       gx_bs, gx_ps, gx_cs, part_gT, accumulate, stream);
-}
-
-extern "C" int pc3d_pointmlp3_max_bwd_twolist_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B,
-                                                  int N, const float* T, const float* W1, const float* b1,
-                                                  const float* W2, const float* b2, const float* W3, const float* W2T,
-                                                  int C1, int C2, int C3, const int32_t* argidx,
-                                                  const uint64_t* mask1, const uint32_t* mask2, const float* g_pooled,
-                                                  float* grad_x, int64_t gx_bs, int64_t gx_ps, int64_t gx_cs,
-                                                  float* part_gT, int accumulate, void* stream) {
-  return pm_bwd_launch("pc3d_pointmlp3_max_bwd_twolist_f32", PM_BWD_TWOLIST, x, x_bs, x_ps, x_cs, B, N, T, W1, b1, W2, b2, W3, W2T,
-                       C1, C2, C3, argidx, mask1, mask2, g_pooled, grad_x, gx_bs, gx_ps, gx_cs, part_gT, accumulate,
-                       stream);
-}
-
-static int pm_bwd_update_launch(const char* who, bool packed, float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B,
-                                int N, const float* W1, const float* b1, const float* W2, const float* b2,
-                                const float* W3, const float* W2T, int C1, int C2, int C3, const int32_t* argidx,
-                                const uint64_t* mask1, const uint32_t* mask2, const float* g_pooled,
-                                const float* grad_x, int64_t gx_bs, int64_t gx_ps, int64_t gx_cs, const float* ori,
-                                int64_t o_bs, int64_t o_ps, int64_t o_cs, float* m, float* v, double beta1, double beta2,
-                                double eps, float budget, const float* adam, int dist_kind, const float* w,
-                                const float* dist_val, const int32_t* nn_idx, void* stream) {
-  PC3D_REQUIRE(B >= 0 && N >= 1, "%s: bad sizes B=%d N=%d", who, B, N);
+                                          int accumulate, int form, int stop_after, void* stream) {
+  PC3D_REQUIRE(form >= PC3D_PM_BWD_DEFAULT && form <= PC3D_PM_BWD_TWOLIST, "pc3d_pointmlp3_max_bwd_f32: unknown form %d", form);
+  PC3D_REQUIRE(stop_after >= 0 && stop_after <= 5 && (stop_after == 0 || form == PC3D_PM_BWD_PACKED),
+               "pc3d_pointmlp3_max_bwd_f32: stop_after = %d (1..5, with the packed form only)", stop_after);
+  PC3D_REQUIRE(B >= 0 && N >= 1, "pc3d_pointmlp3_max_bwd_f32: bad sizes B=%d N=%d", B, N);
   PC3D_REQUIRE(C1 == PM_C1 && C2 == PM_C2 && C3 >= 32 && C3 % 32 == 0 && C3 <= PM_MAXC3,
-               "%s: unsupported widths %d/%d/%d", who, C1, C2, C3);
-  PC3D_REQUIRE(B <= 65535, "%s: B=%d exceeds grid.y limit", who, B);
-  PC3D_REQUIRE(dist_kind >= 0 && dist_kind <= 2, "%s: dist_kind=%d not in {0,1,2}", who, dist_kind);
+               "pc3d_pointmlp3_max_bwd_f32: unsupported widths %d/%d/%d", C1, C2, C3);
+  PC3D_REQUIRE(B <= 65535, "pc3d_pointmlp3_max_bwd_f32: B=%d exceeds grid.y limit", B);
+  if (B == 0) return PC3D_OK;
+  PC3D_REQUIRE(x && W1 && b1 && W2 && b2 && W3 && W2T && argidx && mask1 && mask2 && g_pooled && grad_x,
+               "pc3d_pointmlp3_max_bwd_f32: null pointer");
+  PMBwdArgs a{{x, x_bs, x_ps, x_cs}, N, C3, T, W1, b1, W2, b2, W3, W2T, argidx, mask1, mask2, g_pooled, {grad_x, gx_bs, gx_ps, gx_cs},
+              part_gT, accumulate};
+  const dim3 g32(cdiv(N, PM_BTP), B), gp(cdiv(N, PM_PTP), B);
+  hipStream_t st = as_stream(stream);
+  switch (form == PC3D_PM_BWD_DEFAULT ? PM_BWD_DEFAULT_FORM : form) {
+    case PC3D_PM_BWD_TWOLIST: hipLaunchKernelGGL(pointmlp3_max_bwd_twolist_kernel, g32, dim3(256), 0, st, a); break;
+    case PC3D_PM_BWD_TILE32: hipLaunchKernelGGL(pointmlp3_max_bwd_kernel, g32, dim3(256), 0, st, a); break;
+    default:
+      switch (stop_after) {   // the packed form, whole or ended after phase stop_after
+        case 0: hipLaunchKernelGGL(pointmlp3_max_bwd_packed_kernel, gp, dim3(PM_PNT), 0, st, a); break;
+        case 1: hipLaunchKernelGGL(pointmlp3_max_bwd_packed_dbg_kernel<1>, gp, dim3(PM_PNT), 0, st, a); break;
+        case 2: hipLaunchKernelGGL(pointmlp3_max_bwd_packed_dbg_kernel<2>, gp, dim3(PM_PNT), 0, st, a); break;
+        case 3: hipLaunchKernelGGL(pointmlp3_max_bwd_packed_dbg_kernel<3>, gp, dim3(PM_PNT), 0, st, a); break;
+        case 4: hipLaunchKernelGGL(pointmlp3_max_bwd_packed_dbg_kernel<4>, gp, dim3(PM_PNT), 0, st, a); break;
+        default: hipLaunchKernelGGL(pointmlp3_max_bwd_packed_dbg_kernel<5>, gp, dim3(PM_PNT), 0, st, a); break;
+      }
+  }
+  PC3D_LAUNCH_CHECK("pc3d_pointmlp3_max_bwd_f32");
+  return PC3D_OK;
+}
+
+extern "C" int pc3d_pointmlp3_max_bwd_update_f32(float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                                 const float* W1, const float* b1, const float* W2, const float* b2,
+                                                 const float* W3, const float* W2T, int C1, int C2, int C3,
+                                                 const int32_t* argidx, const uint64_t* mask1, const uint32_t* mask2,
+                                                 const float* g_pooled, const float* grad_x, int64_t gx_bs,
+                                                 int64_t gx_ps, int64_t gx_cs, const float* ori, int64_t o_bs,
+                                                 int64_t o_ps, int64_t o_cs, float* m, float* v, double beta1,
+                                                 double beta2, double eps, float budget, const float* adam,
+                                                 int dist_kind, const float* w, const float* dist_val,
+                                                 const int32_t* nn_idx, int form, void* stream) {
+  PC3D_REQUIRE(form >= PC3D_PM_BWD_DEFAULT && form <= PC3D_PM_BWD_TILE32,
+               "pc3d_pointmlp3_max_bwd_update_f32: unknown form %d (the default, the packed or the tile32 one)", form);
+  PC3D_REQUIRE(B >= 0 && N >= 1, "pc3d_pointmlp3_max_bwd_update_f32: bad sizes B=%d N=%d", B, N);
+  PC3D_REQUIRE(C1 == PM_C1 && C2 == PM_C2 && C3 >= 32 && C3 % 32 == 0 && C3 <= PM_MAXC3,
+               "pc3d_pointmlp3_max_bwd_update_f32: unsupported widths %d/%d/%d", C1, C2, C3);
+  PC3D_REQUIRE(B <= 65535, "pc3d_pointmlp3_max_bwd_update_f32: B=%d exceeds grid.y limit", B);
+  PC3D_REQUIRE(dist_kind >= 0 && dist_kind <= 2, "pc3d_pointmlp3_max_bwd_update_f32: dist_kind=%d not in {0,1,2}", dist_kind);
   if (B == 0) return PC3D_OK;
   PC3D_REQUIRE(x && W1 && b1 && W2 && b2 && W3 && W2T && argidx && mask1 && mask2 && g_pooled && grad_x && ori && m && v && adam,
-               "%s: null pointer", who);
-  PC3D_REQUIRE(dist_kind == 0 || w != nullptr, "%s: distance term needs the weights w", who);
-  PC3D_REQUIRE(dist_kind != 1 || dist_val != nullptr, "%s: L2 term needs dist_val", who);
-  PC3D_REQUIRE(dist_kind != 2 || nn_idx != nullptr, "%s: Chamfer term needs nn_idx", who);
+               "pc3d_pointmlp3_max_bwd_update_f32: null pointer");
+  PC3D_REQUIRE(dist_kind == 0 || w != nullptr, "pc3d_pointmlp3_max_bwd_update_f32: distance term needs the weights w");
+  PC3D_REQUIRE(dist_kind != 1 || dist_val != nullptr, "pc3d_pointmlp3_max_bwd_update_f32: L2 term needs dist_val");
+  PC3D_REQUIRE(dist_kind != 2 || nn_idx != nullptr, "pc3d_pointmlp3_max_bwd_update_f32: Chamfer term needs nn_idx");
   // gx is only read here (the sum goes into the update, not back to memory)
   PMBwdArgs a{{x, x_bs, x_ps, x_cs}, N, C3, nullptr, W1, b1, W2, b2, W3, W2T, argidx, mask1, mask2, g_pooled,
               {const_cast<float*>(grad_x), gx_bs, gx_ps, gx_cs}, nullptr, 1};
   PMUpdArgs u{{x, x_bs, x_ps, x_cs}, m, v, {ori, o_bs, o_ps, o_cs}, nn_idx, w, dist_val, adam, B, dist_kind,
               (float)(1.0 - beta1), (float)(1.0 - beta2), (float)beta2, (float)eps, budget};
-  if (packed)
+  if ((form == PC3D_PM_BWD_DEFAULT ? PM_BWD_DEFAULT_FORM : form) == PC3D_PM_BWD_PACKED)
     hipLaunchKernelGGL(pointmlp3_max_bwd_update_packed_kernel, dim3(cdiv(N, PM_PTP), B), dim3(PM_PNT), 0, as_stream(stream), a, u);
   else
     hipLaunchKernelGGL(pointmlp3_max_bwd_update_kernel, dim3(cdiv(N, PM_BTP), B), dim3(256), 0, as_stream(stream), a, u);
-  PC3D_LAUNCH_CHECK(who);
+  PC3D_LAUNCH_CHECK("pc3d_pointmlp3_max_bwd_update_f32");
   return PC3D_OK;
-}
-
-#define PM_BWD_UPDATE_PARAMS                                                                                            \
-  float *x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N, const float *W1, const float *b1, const float *W2, \
-      const float *b2, const float *W3, const float *W2T, int C1, int C2, int C3, const int32_t *argidx,               \
-      const uint64_t *mask1, const uint32_t *mask2, const float *g_pooled, const float *grad_x, int64_t gx_bs,         \
-      int64_t gx_ps, int64_t gx_cs, const float *ori, int64_t o_bs, int64_t o_ps, int64_t o_cs, float *m, float *v,    \
-      double beta1, double beta2, double eps, float budget, const float *adam, int dist_kind, const float *w,          \
-      const float *dist_val, const int32_t *nn_idx, void *stream
-#define PM_BWD_UPDATE_ARGS                                                                                             \
-  x, x_bs, x_ps, x_cs, B, N, W1, b1, W2, b2, W3, W2T, C1, C2, C3, argidx, mask1, mask2, g_pooled, grad_x, gx_bs, gx_ps, \
-      gx_cs, ori, o_bs, o_ps, o_cs, m, v, beta1, beta2, eps, budget, adam, dist_kind, w, dist_val, nn_idx, stream
-
-extern "C" int pc3d_pointmlp3_max_bwd_update_f32(PM_BWD_UPDATE_PARAMS) {
-  return pm_bwd_update_launch("pc3d_pointmlp3_max_bwd_update_f32", PM_BWD_DEFAULT_PACKED, PM_BWD_UPDATE_ARGS);
-}
-extern "C" int pc3d_pointmlp3_max_bwd_update_tile32_f32(PM_BWD_UPDATE_PARAMS) {
-  return pm_bwd_update_launch("pc3d_pointmlp3_max_bwd_update_tile32_f32", false, PM_BWD_UPDATE_ARGS);
-}
-extern "C" int pc3d_pointmlp3_max_bwd_update_packed_f32(PM_BWD_UPDATE_PARAMS) {
-  return pm_bwd_update_launch("pc3d_pointmlp3_max_bwd_update_packed_f32", true, PM_BWD_UPDATE_ARGS);
 }

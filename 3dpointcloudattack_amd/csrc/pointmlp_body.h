@@ -188,30 +188,30 @@ __device__ __forceinline__ void pm_fwd_prologue(const PMFwdArgs& a, float* lds) 
 }
 
 
-// pointmlp_screen.hip: the same launch with layer 3 screened on bf16 MFMA and rechecked exactly (the same bits).
-// Returns 0 when launched, 1 when it could not be (first use on a device while the stream is capturing: the caller
-// launches the exact kernel), < 0 on an error. stats / dbg_S / dbg_E / stop_after: pc3d_pointmlp3_max_fwd_screen_dbg_f32.
-// prep: the prepared image of W3 (pm_w3_prepare_launch wrote it from THIS W3), or null: the operands are then made from
-// the fp32 rows inside the launch.
+// pointmlp_screen.hip: the same launch with layer 3 screened on the matrix pipe and rechecked exactly (the same bits).
+// The prepared image of W3 (pm_w3_prepare_launch wrote it from THIS W3) that PC3D_PM_FWD_SCREEN_PREP reads; the
+// in-launch form, PC3D_PM_FWD_SCREEN, makes the operands from the fp32 rows inside the launch.
 struct PMScreenPrep {
   const __attribute__((ext_vector_type(8))) __bf16* w3_bf;   // [C3/32][8][2][64] x 8 bf16
   const float* w3_nw;                                        // [C3]
   const float4* w3_q;                                        // [32][C3]
 };
-// hprep: the fp16 image of the same W3 (pm_w3_prepare_h_launch), or null. With it the H form runs: layer 3 screened with
-// ONE scaled fp16 product per k-step (pointmlp_screen_h_bound.h), the same recheck, the same bits in every output; it needs
-// neither prep nor its w3_bf. dbg_S / dbg_E of that form are written in the unscaled domain.
+// The fp16 image of the same W3 (pm_w3_prepare_h_launch) that the H forms read: layer 3 screened with ONE scaled fp16
+// product per k-step (pointmlp_screen_h_bound.h), the same recheck, the same bits in every output; they need neither the
+// bf16 image nor its w3_bf. dbg_S / dbg_E of these forms are written in the unscaled domain.
 struct PMScreenPrepH {
   const __attribute__((ext_vector_type(8))) _Float16* w3_h;  // [C3/32][8][64] x 8 fp16: W3[32 cb + r][16 t + 8 h + 0..7] 2^sw
   const float* w3_cw;                                        // [C3] the channel's factor of E, scaled; +inf: not screened
   const float* w3_nw;                                        // [C3] (read by the dump instantiation only)
   const float4* w3_q;                                        // [32][C3]
 };
+// Launches `form`, one of PC3D_PM_FWD_SCREEN .. PC3D_PM_FWD_SCREEN_H_PAIR (include/pc3d.h; stats / dbg_S / dbg_E /
+// stop_after as there). A form whose instantiation cannot be launched yet (first use on a device while the stream is
+// capturing) steps aside for the next of H_PAIR -> H -> PREP -> SCREEN. Returns 0 when launched, 1 when none could be
+// (the caller launches the exact kernel), < 0 on an error. prep / hprep: read by PREP and the H forms / by the H forms.
 int pm_fwd_screen_launch(const PMFwdArgs& a, int B, void* stream, int32_t* stats, float* dbg_S, float* dbg_E,
-                         int stop_after, const PMScreenPrep* prep, const PMScreenPrepH* hprep = nullptr, bool pair = false);
-// pair (with hprep): the H form's recheck runs one lane per (channel, candidate) pair instead of one lane per channel
-// (the same bits); an instantiation of its own, so its first use inside a capture takes the channel recheck.
-// pm_fwd_pair_ready: 1 once the production pair instantiation can be launched on the current device.
+                         int stop_after, int form, const PMScreenPrep& prep, const PMScreenPrepH& hprep);
+// pm_fwd_pair_ready: 1 once the production H_PAIR instantiation can be launched on the current device.
 int pm_fwd_pair_ready();
 // w3_bf (C3 * 512 B), w3_nw (C3 floats), w3_q (C3 * 128 floats) from the folded fp32 W3 [C3,128]
 int pm_w3_prepare_launch(const float* W3, int C3, void* w3_bf, float* w3_nw, float* w3_q, void* stream);

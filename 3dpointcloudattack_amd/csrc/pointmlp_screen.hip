@@ -980,87 +980,80 @@ __global__ __launch_bounds__(PM_FT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
   }
 }
 
-static bool pmp_ready[64] = {};   // the production PAIR instantiation has its LDS attribute on that device
+// A screened instantiation needs its dynamic-LDS attribute, which is set at its first use on a device and never while
+// the stream is capturing. pms_usable: per instantiation, per device, the attribute is set.
+template <auto KERNEL>
+static bool pms_usable[64] = {};
 
-template <bool DBG, bool DUMP, bool PAIR>
-static int pms_launch_h_t(const PMFwdArgs& a, int B, hipStream_t st, const PMScreenDbg& d, const PMScreenPrepH& q) {
-  static bool done[64] = {};
+// 0: launched. 1: not launched — the instantiation cannot be yet (the caller takes the next form). < 0: an error.
+template <auto KERNEL, size_t LDS, class Q>
+static int pms_launch_t(const PMFwdArgs& a, int B, hipStream_t st, const PMScreenDbg& d, const Q& q) {
   int dev = 0;
   PC3D_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "pointmlp3 screen: no current device");
-  auto kernel = pointmlp3_max_fwd_screen_h_kernel<DBG, DUMP, PAIR>;
-  constexpr size_t lds = PAIR ? PMP_LDS_BYTES : PMH_LDS_BYTES;
-  if (!done[dev]) {
+  if (!pms_usable<KERNEL>[dev]) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
       (void)hipGetLastError();
       return 1;
     }
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
     PC3D_REQUIRE(e == hipSuccess, "pointmlp3 screen: hipFuncSetAttribute(MaxDynamicSharedMemorySize): %s", hipGetErrorString(e));
-    done[dev] = true;
-    if (PAIR && !DBG) pmp_ready[dev] = true;
+    pms_usable<KERNEL>[dev] = true;
   }
-  hipLaunchKernelGGL(kernel, dim3(a.ntiles, B), dim3(PM_FT), lds, st, a, d, q);
+  hipLaunchKernelGGL(KERNEL, dim3(a.ntiles, B), dim3(PM_FT), LDS, st, a, d, q);
   return 0;
 }
 
+// the production, the statistics or the dump instantiation of a form, as d asks
 template <bool PAIR>
 static int pms_launch_h(const PMFwdArgs& a, int B, hipStream_t st, const PMScreenDbg& d, const PMScreenPrepH& q) {
-  if (d.dbg_S || d.dbg_E) return pms_launch_h_t<true, true, PAIR>(a, B, st, d, q);
-  if (d.stats || d.stop_after) return pms_launch_h_t<true, false, PAIR>(a, B, st, d, q);
-  return pms_launch_h_t<false, false, PAIR>(a, B, st, d, q);
+  constexpr size_t lds = PAIR ? PMP_LDS_BYTES : PMH_LDS_BYTES;
+  if (d.dbg_S || d.dbg_E) return pms_launch_t<pointmlp3_max_fwd_screen_h_kernel<true, true, PAIR>, lds>(a, B, st, d, q);
+  if (d.stats || d.stop_after) return pms_launch_t<pointmlp3_max_fwd_screen_h_kernel<true, false, PAIR>, lds>(a, B, st, d, q);
+  return pms_launch_t<pointmlp3_max_fwd_screen_h_kernel<false, false, PAIR>, lds>(a, B, st, d, q);
 }
 
-int pm_fwd_pair_ready() {
+// the production instantiation of pms_launch_h<PAIR> has its attribute on the current device (a template, so that it
+// names the kernel after pms_launch_h has: the kernels keep their order in the code object)
+template <bool PAIR>
+static bool pms_h_usable() {
   int dev = 0;
-  return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64 && pmp_ready[dev] ? 1 : 0;
-}
-
-// 0: launched. 1: not launched — the kernel needs its dynamic-LDS attribute, which is set at first use on a device and
-// never while the stream is capturing; the caller then launches the exact kernel.
-template <bool DBG, bool DUMP, bool PREP>
-static int pms_launch_t(const PMFwdArgs& a, int B, hipStream_t st, const PMScreenDbg& d, const PMScreenPrep& q) {
-  static bool done[64] = {};
-  int dev = 0;
-  PC3D_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "pointmlp3 screen: no current device");
-  auto kernel = pointmlp3_max_fwd_screen_kernel<DBG, DUMP, PREP>;
-  constexpr size_t lds = PREP ? PMS_LDS_BYTES_PREP : PMS_LDS_BYTES;
-  if (!done[dev]) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
-      (void)hipGetLastError();
-      return 1;
-    }
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    PC3D_REQUIRE(e == hipSuccess, "pointmlp3 screen: hipFuncSetAttribute(MaxDynamicSharedMemorySize): %s", hipGetErrorString(e));
-    done[dev] = true;
-  }
-  hipLaunchKernelGGL(kernel, dim3(a.ntiles, B), dim3(PM_FT), lds, st, a, d, q);
-  return 0;
+  return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64 &&
+         pms_usable<pointmlp3_max_fwd_screen_h_kernel<false, false, PAIR>>[dev];
 }
 
 template <bool PREP>
 static int pms_launch_form(const PMFwdArgs& a, int B, hipStream_t st, const PMScreenDbg& d, const PMScreenPrep& q) {
-  if (d.dbg_S || d.dbg_E) return pms_launch_t<true, true, PREP>(a, B, st, d, q);
-  if (d.stats || d.stop_after) return pms_launch_t<true, false, PREP>(a, B, st, d, q);
-  return pms_launch_t<false, false, PREP>(a, B, st, d, q);
+  constexpr size_t lds = PREP ? PMS_LDS_BYTES_PREP : PMS_LDS_BYTES;
+  if (d.dbg_S || d.dbg_E) return pms_launch_t<pointmlp3_max_fwd_screen_kernel<true, true, PREP>, lds>(a, B, st, d, q);
+  if (d.stats || d.stop_after) return pms_launch_t<pointmlp3_max_fwd_screen_kernel<true, false, PREP>, lds>(a, B, st, d, q);
+  return pms_launch_t<pointmlp3_max_fwd_screen_kernel<false, false, PREP>, lds>(a, B, st, d, q);
 }
 
 int pm_fwd_screen_launch(const PMFwdArgs& a, int B, void* stream, int32_t* stats, float* dbg_S, float* dbg_E,
-                         int stop_after, const PMScreenPrep* prep, const PMScreenPrepH* hprep, bool pair) {
+                         int stop_after, int form, const PMScreenPrep& prep, const PMScreenPrepH& hprep) {
   const PMScreenDbg d{stats, dbg_S, dbg_E, stop_after};
-  // the fp16 form when the caller asks for it by passing its image, its recheck by pair when asked for, else (and when
-  // that instantiation's first use falls into a capture) by channel; like the forms below it steps aside while its
-  // first use on the device falls into a capture
-  if (hprep != nullptr && pair && pms_launch_h<true>(a, B, as_stream(stream), d, *hprep) == 0) return 0;
-  if (hprep != nullptr && pms_launch_h<false>(a, B, as_stream(stream), d, *hprep) == 0) return 0;
-  // the prepared form when the caller has the image; the in-launch form without one, and when the prepared
-  // instantiation cannot be launched yet (its first use on the device falls into a capture)
-  if (prep != nullptr && pms_launch_form<true>(a, B, as_stream(stream), d, *prep) == 0) return 0;
-  return pms_launch_form<false>(a, B, as_stream(stream), d, PMScreenPrep{nullptr, nullptr, nullptr});
+  hipStream_t st = as_stream(stream);
+  // every case falls through to the next form when its own instantiation could not be launched (its first use on the
+  // device falls into a capture): the pair recheck to the channel one, the fp16 screen to the prepared bf16 one, that
+  // one to the in-launch form, which reads no image
+  switch (form) {
+    case PC3D_PM_FWD_SCREEN_H_PAIR:
+      if (pms_launch_h<true>(a, B, st, d, hprep) == 0) return 0;
+      [[fallthrough]];
+    case PC3D_PM_FWD_SCREEN_H:
+      if (pms_launch_h<false>(a, B, st, d, hprep) == 0) return 0;
+      [[fallthrough]];
+    case PC3D_PM_FWD_SCREEN_PREP:
+      if (pms_launch_form<true>(a, B, st, d, prep) == 0) return 0;
+      [[fallthrough]];
+    default:
+      return pms_launch_form<false>(a, B, st, d, PMScreenPrep{nullptr, nullptr, nullptr});
+  }
 }
+
+int pm_fwd_pair_ready() { return pms_h_usable<true>() ? 1 : 0; }
 
 int pm_w3_prepare_launch(const float* W3, int C3, void* w3_bf, float* w3_nw, float* w3_q, void* stream) {
   hipLaunchKernelGGL(pms_w3_prepare_kernel, dim3(C3 / 32), dim3(64), 0, as_stream(stream), W3,

@@ -448,6 +448,41 @@ PM_FWD_DEFAULT_FORM = "fp16"
 # per headline step, 5.7 x the run-to-run spread.
 PM_FWD_DEFAULT_RECHECK = "pair"
 
+# the `form` argument of pc3d_pointmlp3_max_fwd_f32 / of pc3d_pointmlp3_max_bwd_f32 and _update_f32 (include/pc3d.h)
+PM_FWD_EXACT, PM_FWD_SCREEN, PM_FWD_SCREEN_PREP, PM_FWD_SCREEN_H, PM_FWD_SCREEN_H_PAIR = range(5)
+PM_BWD_DEFAULT, PM_BWD_PACKED, PM_BWD_TILE32, PM_BWD_TWOLIST = range(4)
+
+
+def _pm_fwd_form(exact, in_launch, have_image, have_h_image, form, recheck, dbg):
+    """Which form of pc3d_pointmlp3_max_fwd_f32 pointmlp3_max_fwd_raw launches (its docstring states the arguments).
+    exact: PM_FWD_EXACT, and dbg (a screen_dbg dict was given) is then an error. in_launch, or no prepared image of W3
+    (have_image False): PM_FWD_SCREEN. Else form decides — None means "fp16" when recheck is named, "bf16" under dbg,
+    PM_FWD_DEFAULT_FORM otherwise. "bf16", or no fp16 image behind the bf16 one (have_h_image False):
+    PM_FWD_SCREEN_PREP. "fp16": PM_FWD_SCREEN_H_PAIR when recheck (None: PM_FWD_DEFAULT_RECHECK) is "pair", else
+    PM_FWD_SCREEN_H. form and recheck are validated whichever form runs; recheck with form="bf16" is an error."""
+    if dbg and exact:
+        raise ValueError("pointmlp3_max_fwd_raw: screen_dbg belongs to the screened launch, not to exact=True")
+    if form not in (None, "bf16", "fp16"):
+        raise ValueError("pointmlp3_max_fwd_raw: form is None, 'bf16' or 'fp16'")
+    if recheck not in (None, "channel", "pair"):
+        raise ValueError("pointmlp3_max_fwd_raw: recheck is None, 'channel' or 'pair'")
+    if recheck is not None and form == "bf16":
+        raise ValueError("pointmlp3_max_fwd_raw: recheck belongs to form='fp16'")
+    if exact:
+        return PM_FWD_EXACT
+    if in_launch or not have_image:
+        return PM_FWD_SCREEN
+    if form is None:
+        form = "fp16" if recheck is not None else "bf16" if dbg else PM_FWD_DEFAULT_FORM
+    if form == "bf16" or not have_h_image:
+        return PM_FWD_SCREEN_PREP
+    return PM_FWD_SCREEN_H_PAIR if (recheck or PM_FWD_DEFAULT_RECHECK) == "pair" else PM_FWD_SCREEN_H
+
+
+def _pm_bwd_form(twolist, tile32):
+    """The form of the two backward entries: twolist, else tile32 None / True / False = the default / tile32 / packed."""
+    return PM_BWD_TWOLIST if twolist else PM_BWD_DEFAULT if tile32 is None else PM_BWD_TILE32 if tile32 else PM_BWD_PACKED
+
 
 def pointmlp3_pair_recheck_ready(device):
     """True once the pair recheck's production kernel can be launched on `device`: its dynamic-LDS attribute is set at
@@ -503,26 +538,12 @@ def pointmlp3_max_fwd_raw(x, weights, relu_last, T=None, x_cf=True, fold=True, w
             pooled.data_ptr() if fold and not serial else 0, argidx.data_ptr() if fold and not serial else 0,
             masks[0].data_ptr() if masks else 0, masks[1].data_ptr() if masks else 0, _stream())
     T_out = None
-    if screen_dbg is not None and exact:
-        raise ValueError("pointmlp3_max_fwd_raw: screen_dbg belongs to the screened launch, not to exact=True")
-    sfx = "exact_" if exact else ""
     with torch.cuda.device(dev):
         prep = None if exact or in_launch else _pm_w3_pack(weights, W3)
-        if form not in (None, "bf16", "fp16"):
-            raise ValueError("pointmlp3_max_fwd_raw: form is None, 'bf16' or 'fp16'")
-        if recheck not in (None, "channel", "pair"):
-            raise ValueError("pointmlp3_max_fwd_raw: recheck is None, 'channel' or 'pair'")
-        if recheck is not None and form == "bf16":
-            raise ValueError("pointmlp3_max_fwd_raw: recheck belongs to form='fp16'")
-        if form is None:
-            form = "fp16" if recheck is not None else PM_FWD_DEFAULT_FORM if screen_dbg is None else "bf16"
-        if recheck is None:
-            recheck = PM_FWD_DEFAULT_RECHECK
-        if prep is not None:
-            hp = _pm_w3_h(prep[0]) if form == "fp16" else None
-            sfx, prep = "prep_", tuple(t.data_ptr() for t in prep)
-            if hp is not None:
-                sfx, prep = "h_pair_" if recheck == "pair" else "h_", prep + hp[1]
+        hp = _pm_w3_h(prep[0]) if prep is not None and form != "bf16" else None
+        kform = _pm_fwd_form(exact, in_launch, prep is not None, hp is not None, form, recheck, screen_dbg is not None)
+        img = (tuple(t.data_ptr() for t in prep) if prep is not None else (0, 0, 0)) + (hp[1] if hp is not None else (0, 0))
+        th = (0, 0, 0, 0, 0)
         if T_head is not None:
             if T is not None:
                 raise ValueError("pointmlp3_max_fwd_raw: give T or T_head, not both")
@@ -530,6 +551,8 @@ def pointmlp3_max_fwd_raw(x, weights, relu_last, T=None, x_cf=True, fold=True, w
             if h.shape[0] != B or Wt.shape != (9, h.shape[1]) or bt.numel() != 9 or not (h.is_contiguous() and Wt.is_contiguous()):
                 raise ValueError("pointmlp3_max_fwd_raw: T_head = (h [B,K], W [9,K], b [9]) contiguous expected")
             T_out = torch.empty((B, 9), dtype=torch.float32, device=dev)
+            th = (h.data_ptr(), Wt.data_ptr(), bt.data_ptr(), h.shape[1], T_out.data_ptr())
+        dbg = (0, 0, 0, 0)
         if screen_dbg is not None:
             screen_dbg["stats"] = torch.zeros((B, ntiles, 2), dtype=torch.int32, device=dev)
             dS = dE = None
@@ -537,15 +560,8 @@ def pointmlp3_max_fwd_raw(x, weights, relu_last, T=None, x_cf=True, fold=True, w
                 dS = torch.full((B, N, C3), float("nan"), dtype=torch.float32, device=dev)
                 dE = torch.full((B, N, C3), float("nan"), dtype=torch.float32, device=dev)
                 screen_dbg["S"], screen_dbg["E"] = dS, dE
-            th = (h.data_ptr(), Wt.data_ptr(), bt.data_ptr(), h.shape[1], T_out.data_ptr()) if T_head is not None else (0, 0, 0, 0, 0)
-            _lib.call("pc3d_pointmlp3_max_fwd_screen_dbg_%sf32" % sfx, xp, xbs, xps, xcs, B, N, _ptr(T), *th, *tail[:-1],
-                      screen_dbg["stats"].data_ptr(), _ptr(dS), _ptr(dE), int(screen_dbg.get("stop_after", 0)),
-                      *(prep or ()), tail[-1])
-        elif T_head is not None:
-            _lib.call("pc3d_pointmlp3_max_fwd_%sth_f32" % sfx, xp, xbs, xps, xcs, B, N, h.data_ptr(), Wt.data_ptr(), bt.data_ptr(),
-                      h.shape[1], T_out.data_ptr(), *tail[:-1], *(prep or ()), tail[-1])
-        else:
-            _lib.call("pc3d_pointmlp3_max_fwd_%sf32" % sfx, xp, xbs, xps, xcs, B, N, _ptr(T), *tail[:-1], *(prep or ()), tail[-1])
+            dbg = (screen_dbg["stats"].data_ptr(), _ptr(dS), _ptr(dE), int(screen_dbg.get("stop_after", 0)))
+        _lib.call("pc3d_pointmlp3_max_fwd_f32", xp, xbs, xps, xcs, B, N, _ptr(T), *th, *tail[:-1], kform, *img, *dbg, tail[-1])
         if fold and serial:
             _lib.call("pc3d_pointmlp3_fold_f32", part_val.data_ptr(), part_idx.data_ptr(), B, ntiles, C3,
                       1 if relu_last else 0, pooled.data_ptr(), argidx.data_ptr(), 1, _stream())
@@ -561,7 +577,7 @@ def pointmlp3_max_bwd_raw(x, weights, argidx, g_pooled, masks, T=None, x_cf=True
     as x. masks: the (mask1, mask2) pair of the forward launch on the same x/T (want_masks=True).
     want_gT: also return the per-tile partials [B, ntiles, 16] of dL/dT. out/accumulate: add into `out`.
     twolist: run the earlier two-list kernel (same bits; parity tests and tools/bench_pointmlp.py only).
-    tile32: None — the default entry; True / False — the tile32 / the packed form of the balanced kernel by name (same
+    tile32: None — the entry's default form; True / False — the tile32 / the packed form of the balanced kernel by name (same
     bits; parity test and bench tool only). stop_after 1..5 (tile32=False): end the packed launch after that phase."""
     if want_gT and T is None:       # the kernels write the partials only with T: the tensor would go back unwritten
         raise ValueError("pointmlp3_max_bwd_raw: T and part_gT go together (want_gT needs T)")
@@ -587,14 +603,12 @@ def pointmlp3_max_bwd_raw(x, weights, argidx, g_pooled, masks, T=None, x_cf=True
             raise ValueError("pointmlp3_max_bwd_raw: twolist and tile32 name different kernels")
         if stop_after and tile32 is not False:
             raise ValueError("pointmlp3_max_bwd_raw: stop_after belongs to the packed form (tile32=False)")
-        name = "pc3d_pointmlp3_max_bwd_twolist_f32" if twolist else "pc3d_pointmlp3_max_bwd_f32" if tile32 is None \
-            else "pc3d_pointmlp3_max_bwd_tile32_f32" if tile32 else "pc3d_pointmlp3_max_bwd_packed_dbg_f32"
-        _lib.call(name,
+        _lib.call("pc3d_pointmlp3_max_bwd_f32",
                   xp, xbs, xps, xcs, B, N, _ptr(T),
                   W1.data_ptr(), b1.data_ptr(), W2.data_ptr(), b2.data_ptr(), W3.data_ptr(), W2T.data_ptr(),
                   C1, C2, C3, argidx.data_ptr(), m1.data_ptr(), m2.data_ptr(), g_pooled.data_ptr(), gp, gbs, gps, gcs,
                   _ptr(part_gT),
-                  1 if accumulate else 0, *([int(stop_after)] if tile32 is False else []), _stream())
+                  1 if accumulate else 0, _pm_bwd_form(twolist, tile32), int(stop_after), _stream())
     return (gx, part_gT) if want_gT else gx
 
 
@@ -1554,7 +1568,7 @@ def pointmlp3_max_bwd_update(x, weights, argidx, g_pooled, masks, gx, ori, m, v,
     """pointmlp3_max_bwd_raw(..., out=gx, accumulate=True) followed by the update half of cw_update, as ONE launch
     (pc3d_pointmlp3_max_bwd_update_f32): x — the iterate — and the Adam moments m / v are updated in place, gx is only
     read. adam: the [2] factors written by linear_book; dist_val: ||adv-ori|| per sample (dist_kind 1).
-    tile32: as pointmlp3_max_bwd_raw's (None: the default entry)."""
+    tile32: as pointmlp3_max_bwd_raw's (None: the entry's default form)."""
     xp, xbs, xps, xcs, B, N = _pts(x, x_cf, "x")
     W1, b1, W2, b2, W3, b3 = weights[:6]
     W2T = weights[6] if len(weights) > 6 else W2.t().contiguous()
@@ -1574,13 +1588,12 @@ def pointmlp3_max_bwd_update(x, weights, argidx, g_pooled, masks, gx, ori, m, v,
     if nn_idx is not None and (nn_idx.dtype != torch.int32 or tuple(nn_idx.shape) != (B, N) or not nn_idx.is_contiguous()):
         raise ValueError("pointmlp3_max_bwd_update: nn_idx must be a contiguous int32 [B,N] tensor")
     with torch.cuda.device(x.device):
-        _lib.call("pc3d_pointmlp3_max_bwd_update_f32" if tile32 is None else "pc3d_pointmlp3_max_bwd_update_tile32_f32"
-                  if tile32 else "pc3d_pointmlp3_max_bwd_update_packed_f32", xp, xbs, xps, xcs, B, N,
+        _lib.call("pc3d_pointmlp3_max_bwd_update_f32", xp, xbs, xps, xcs, B, N,
                   W1.data_ptr(), b1.data_ptr(), W2.data_ptr(), b2.data_ptr(), W3.data_ptr(), W2T.data_ptr(),
                   C1, C2, C3, argidx.data_ptr(), m1.data_ptr(), m2.data_ptr(), g_pooled.data_ptr(),
                   *_pv(gx, x_cf, "gx"), *_pv(ori, x_cf, "ori"), m.data_ptr(), v.data_ptr(), float(betas[0]), float(betas[1]),
                   float(eps), float(budget), adam.data_ptr(), int(dist_kind), _ptr(w), _ptr(dist_val), _ptr(nn_idx),
-                  _stream())
+                  _pm_bwd_form(False, tile32), _stream())
     return x
 
 

@@ -349,207 +349,111 @@ int pc3d_nn_bwd_f32(const float* a, int64_t a_bs, int64_t a_ps, int64_t a_cs,
  * ReLU after layers 1-2 and optionally after the pool) fused with max-pool over the N points.
  * Replaces model/pointnet.py:34-37 (STN3d tower, relu_last=1) and :110-123 (PointNetfeat trunk, relu_last=0),
  * i.e. three Conv1d+BN(+ReLU) and torch.max(x, 2) with their [B,C,N] activations.
- *   x      B x N points (element strides); T optional [B,3,3] row-major input transform, x'[n,:] = x[n,:] @ T[b]
- *          (the torch.bmm of model/pointnet.py:106-109), NULL = identity
- *   W1 [64,3] b1[64]  W2 [128,64] b2[128]  W3 [C3,128] b3[C3]   row-major, BN already folded; C3 % 32 == 0
+ * One entry per launch; which kernel form runs is the argument `form`. Every form of a launch writes the same bits
+ * into every output. The rules below are checked before any HIP call; breaking one is PC3D_EINVAL.
+ *
+ * pc3d_pointmlp3_max_fwd_f32
+ *   x      B x N points (element strides)
+ *   T      optional [B,3,3] row-major input transform, x'[n,:] = x[n,:] @ T[b] (the torch.bmm of
+ *          model/pointnet.py:106-109), NULL = identity
+ *   th_in, th_W, th_b, th_K, T_out   the transform head. th_in != NULL: T[b] = th_W [9,th_K] . th_in[b] + th_b — the
+ *          last layer of STN3d (model/pointnet.py:45-47: fc3, with the flattened identity added into th_b) — is computed
+ *          in the launch's prologue instead of a launch of its own between the two towers, and T_out [B,9] receives it
+ *          (the backward launch reads it as its T). T must then be NULL, and th_W, th_b, T_out and th_K >= 1 are
+ *          required. th_in == NULL: the other four are not read.
+ *   W1 [64,3] b1[64]  W2 [128,64] b2[128]  W3 [C3,128] b3[C3]   row-major, BN already folded; C3 % 32 == 0, <= 1024
  *   part_val/part_idx  caller workspace [B, ceil(N / pc3d_pointmlp3_tile_points()), C3] f32 / i32
  *   pooled [B,C3] f32 (after the optional ReLU), argidx [B,C3] i32 = lowest point index attaining the max;
  *          pass both NULL to keep only the per-tile partials (no fold launch)
  *   mask1 [B,N] u64, mask2 [B,N,4] u32 (both or neither)  the ReLU decisions of layers 1 and 2 per point (bit c of
  *          mask1 = channel c of layer 1 is positive; word j bit r of mask2 = channel 32j+r of layer 2 is positive),
  *          which the backward launch consumes instead of recomputing the two layers
- * fp32 throughout: layer 2/3 are exact fp32 FMA chains (v_mfma_f32_32x32x2_f32; layer 3 screened, see below).
+ *   form   fp32 throughout: layers 2 and 3 are exact fp32 FMA chains (v_mfma_f32_32x32x2_f32) in
+ *          PC3D_PM_FWD_EXACT. The other forms SCREEN layer 3: a cheap product S of h2 and W3 on the matrix pipe with a
+ *          rigorous bound E, and only the points whose S + E reaches the tile's best S - E are recomputed as the exact
+ *          fp32 fmaf chain; tiles / channel blocks with non-finite or huge operands, or with more candidates than their
+ *          list holds, run the exact fp32 MFMA block.
+ *            PC3D_PM_FWD_SCREEN         both operands split in two bf16 terms inside the launch (three products on
+ *                                       v_mfma_f32_32x32x16_bf16; bound: csrc/pointmlp_screen_bound.h)
+ *            PC3D_PM_FWD_SCREEN_PREP    the same screen with its operands and the recheck's rows read from the
+ *                                       prepared image w3_bf / w3_nw / w3_q; the recheck goes by channel
+ *            PC3D_PM_FWD_SCREEN_H       ONE scaled fp16 product per k-step from the fp16 image w3_h / w3_cw (sixteen
+ *                                       candidate slots per channel instead of eight; csrc/pointmlp_screen_h_bound.h)
+ *            PC3D_PM_FWD_SCREEN_H_PAIR  SCREEN_H with the recheck laid out by (channel, candidate) PAIR, one lane each
+ *          A screened instantiation's first use on a device must fall outside a stream capture; while it has not, the
+ *          launch runs the next of H_PAIR -> H -> PREP -> SCREEN -> the exact kernel.
+ *          pc3d_pointmlp3_pair_recheck_ready: 1 once the production H_PAIR instantiation can be launched on the current
+ *          device, 0 before.
+ *   w3_bf, w3_nw, w3_q / w3_h, w3_cw   the prepared images of the SAME W3 (the caller answers for that), see
+ *          pc3d_pointmlp3_w3_prepare_f32 / _h_f32. SCREEN_PREP needs the first three, the H forms all five (the bf16
+ *          image serves while an H instantiation cannot be launched yet); EXACT and SCREEN read none.
+ *   stats  != NULL selects the debug instantiation of a screened form (tests and tools/bench_pointmlp_screen.py; an
+ *          error with EXACT). [B, ntiles, 2] i32, ADDED to (zero it first): candidates rechecked, channel blocks that
+ *          ran the exact block.
+ *   dbg_S, dbg_E   [B, N, C3] f32, both or neither, only with stats (tiny shapes): the screen's value and bound of every
+ *          (point, channel) of a screened block; the H forms write them in the unscaled domain.
+ *   stop_after   0..3, nonzero only with stats: 1 / 2 / 3 return after the prologue and norms / the screen / the
+ *          selection (timing only: the outputs are then undefined); 0: all.
  * ------------------------------------------------------------------------------------------------------- */
+enum { PC3D_PM_FWD_EXACT = 0, PC3D_PM_FWD_SCREEN = 1, PC3D_PM_FWD_SCREEN_PREP = 2, PC3D_PM_FWD_SCREEN_H = 3,
+       PC3D_PM_FWD_SCREEN_H_PAIR = 4 };
 int pc3d_pointmlp3_tile_points(void);
 int pc3d_pointmlp3_bwd_tile_points(void);
+int pc3d_pointmlp3_pair_recheck_ready(void);
 int pc3d_pointmlp3_max_fwd_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
-                               const float* T, const float* W1, const float* b1, const float* W2,
-                               const float* b2, const float* W3, const float* b3, int C1, int C2, int C3,
-                               int relu_last, float* part_val, int32_t* part_idx,
-                               float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2, void* stream);
+                               const float* T, const float* th_in, const float* th_W, const float* th_b, int th_K,
+                               float* T_out, const float* W1, const float* b1, const float* W2, const float* b2,
+                               const float* W3, const float* b3, int C1, int C2, int C3, int relu_last,
+                               float* part_val, int32_t* part_idx, float* pooled, int32_t* argidx, uint64_t* mask1,
+                               uint32_t* mask2, int form, const void* w3_bf, const float* w3_nw, const float* w3_q,
+                               const void* w3_h, const float* w3_cw, int32_t* stats, float* dbg_S, float* dbg_E,
+                               int stop_after, void* stream);
 /* The fold launch of the entry above on its own: pooled[b,c] = max_t part_val[b,t,c] (the first tile wins ties),
  * argidx the winner's part_idx, optional ReLU; part_* are [B,ntiles,C3]. serial = 1 runs the earlier kernel, which
  * loads one tile's value, compares, and then fetches the winner's index: the same bits. Parity tests and
  * tools/bench_small_launches.py only; nothing on a hot path calls it. */
 int pc3d_pointmlp3_fold_f32(const float* part_val, const int32_t* part_idx, int B, int ntiles, int C3, int relu_last,
                             float* pooled, int32_t* argidx, int serial, void* stream);
-/* The same launch with the input transform computed in its prologue: T[b] = th_W [9,th_K] . th_in[b] + th_b — the
- * last layer of STN3d (model/pointnet.py:45-47: fc3, with the flattened identity added into th_b) — instead of a
- * launch of its own between the two towers; T_out [B,9] receives it (the backward launch reads it as its T). */
-int pc3d_pointmlp3_max_fwd_th_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
-                                  const float* th_in, const float* th_W, const float* th_b, int th_K, float* T_out,
-                                  const float* W1, const float* b1, const float* W2, const float* b2, const float* W3,
-                                  const float* b3, int C1, int C2, int C3, int relu_last, float* part_val,
-                                  int32_t* part_idx, float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2,
-                                  void* stream);
-
-/* Layer 3 of the two entries above is SCREENED: S = h2 . W3 with both operands split in two bf16 terms (three products
- * on v_mfma_f32_32x32x16_bf16) with a rigorous bound E (csrc/pointmlp_screen_bound.h), and only the points whose S + E reaches the tile's best S - E are recomputed
- * as the exact fp32 fmaf chain; tiles / channel blocks with non-finite or huge operands, or with more candidates than
- * their list holds, run the exact fp32 MFMA block. Every output is the same bits as the exact kernel's, which these two
- * entries (same arguments) always launch: */
-int pc3d_pointmlp3_max_fwd_exact_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
-                                     const float* T, const float* W1, const float* b1, const float* W2,
-                                     const float* b2, const float* W3, const float* b3, int C1, int C2, int C3,
-                                     int relu_last, float* part_val, int32_t* part_idx,
-                                     float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2, void* stream);
-int pc3d_pointmlp3_max_fwd_exact_th_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
-                                        const float* th_in, const float* th_W, const float* th_b, int th_K, float* T_out,
-                                        const float* W1, const float* b1, const float* W2, const float* b2,
-                                        const float* W3, const float* b3, int C1, int C2, int C3, int relu_last,
-                                        float* part_val, int32_t* part_idx, float* pooled, int32_t* argidx,
-                                        uint64_t* mask1, uint32_t* mask2, void* stream);
-/* The screened launch with its optional outputs (a separate kernel instantiation: tests and tools/bench_pointmlp_screen.py).
- * T or (th_in, th_W, th_b, th_K, T_out) or neither. stats [B, ntiles, 2] i32 (required, ADDED to: zero it first):
- * candidates rechecked, channel blocks that ran the exact block. dbg_S / dbg_E [B, N, C3] f32 (both or neither; tiny
- * shapes): the screen's value and bound of every (point, channel) of a screened block. stop_after 1 / 2 / 3: return
- * after the prologue and norms / the screen / the selection (timing only: the outputs are then undefined); 0: all. */
-int pc3d_pointmlp3_max_fwd_screen_dbg_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
-                                          const float* T, const float* th_in, const float* th_W, const float* th_b,
-                                          int th_K, float* T_out, const float* W1, const float* b1, const float* W2,
-                                          const float* b2, const float* W3, const float* b3, int C1, int C2, int C3,
-                                          int relu_last, float* part_val, int32_t* part_idx, float* pooled,
-                                          int32_t* argidx, uint64_t* mask1, uint32_t* mask2, int32_t* stats,
-                                          float* dbg_S, float* dbg_E, int stop_after, void* stream);
 /* The prepared image of the folded W3 [C3,128] (a frozen victim weight: made once per fold, csrc/pointmlp_screen.hip):
  * w3_bf [C3/32][8][2][64][8] bf16 (block, k-step, hi / lo, lane r + 32 h, the 8 terms of W3[32 cb + r][16 t + 8 h + 0..7]),
  * w3_nw [C3] f32 (the screen's upper bound of the row norm), w3_q [32][C3][4] f32 (w3_q[t][c] = W3[c][4t..4t+3]). */
 int pc3d_pointmlp3_w3_prepare_f32(const float* W3, int C3, void* w3_bf, float* w3_nw, float* w3_q, void* stream);
-/* pc3d_pointmlp3_max_fwd_f32 / _th_f32 / _screen_dbg_f32 with the screen's operands and the recheck's rows read from the
- * prepared image of the SAME W3 (the caller answers for that): the same bits in every output. */
-int pc3d_pointmlp3_max_fwd_prep_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N, const float* T,
-                                    const float* W1, const float* b1, const float* W2, const float* b2, const float* W3,
-                                    const float* b3, int C1, int C2, int C3, int relu_last, float* part_val,
-                                    int32_t* part_idx, float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2,
-                                    const void* w3_bf, const float* w3_nw, const float* w3_q, void* stream);
-int pc3d_pointmlp3_max_fwd_prep_th_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
-                                       const float* th_in, const float* th_W, const float* th_b, int th_K, float* T_out,
-                                       const float* W1, const float* b1, const float* W2, const float* b2,
-                                       const float* W3, const float* b3, int C1, int C2, int C3, int relu_last,
-                                       float* part_val, int32_t* part_idx, float* pooled, int32_t* argidx,
-                                       uint64_t* mask1, uint32_t* mask2, const void* w3_bf, const float* w3_nw,
-                                       const float* w3_q, void* stream);
-int pc3d_pointmlp3_max_fwd_screen_dbg_prep_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
-                                               const float* T, const float* th_in, const float* th_W, const float* th_b,
-                                               int th_K, float* T_out, const float* W1, const float* b1, const float* W2,
-                                               const float* b2, const float* W3, const float* b3, int C1, int C2, int C3,
-                                               int relu_last, float* part_val, int32_t* part_idx, float* pooled,
-                                               int32_t* argidx, uint64_t* mask1, uint32_t* mask2, int32_t* stats,
-                                               float* dbg_S, float* dbg_E, int stop_after, const void* w3_bf,
-                                               const float* w3_nw, const float* w3_q, void* stream);
 /* The fp16 image of the same W3, made from it and from the w3_nw that pc3d_pointmlp3_w3_prepare_f32 wrote:
  * w3_h [C3/32][8][64][8] fp16 (block, k-step, lane r + 32 h, the 8 values of W3[32 cb + r][16 t + 8 h + 0..7] * 2^sw[c],
  * rounded to nearest even; sw[c] puts w3_nw[c] * 2^sw[c] into [2^13, 2^14)), w3_cw [C3] f32 (the channel's factor of the
  * screen's bound in that scaled domain, csrc/pointmlp_screen_h_bound.h; +inf for a channel whose norm is out of range). */
 int pc3d_pointmlp3_w3_prepare_h_f32(const float* W3, int C3, const float* w3_nw, void* w3_h, float* w3_cw, void* stream);
-/* pc3d_pointmlp3_max_fwd_prep_f32 / _prep_th_f32 / _screen_dbg_prep_f32 with layer 3 screened by ONE scaled fp16 product
- * per k-step instead of three bf16 ones (sixteen candidate slots per channel instead of eight): the same bits in every
- * output. Both images of the SAME W3 are passed; the bf16 one serves when this form cannot be launched yet (its first
- * use on a device falls into a stream capture). dbg_S / dbg_E come back in the unscaled domain. */
-int pc3d_pointmlp3_max_fwd_h_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N, const float* T,
-                                 const float* W1, const float* b1, const float* W2, const float* b2, const float* W3,
-                                 const float* b3, int C1, int C2, int C3, int relu_last, float* part_val,
-                                 int32_t* part_idx, float* pooled, int32_t* argidx, uint64_t* mask1, uint32_t* mask2,
-                                 const void* w3_bf, const float* w3_nw, const float* w3_q, const void* w3_h,
-                                 const float* w3_cw, void* stream);
-int pc3d_pointmlp3_max_fwd_h_th_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
-                                    const float* th_in, const float* th_W, const float* th_b, int th_K, float* T_out,
-                                    const float* W1, const float* b1, const float* W2, const float* b2,
-                                    const float* W3, const float* b3, int C1, int C2, int C3, int relu_last,
-                                    float* part_val, int32_t* part_idx, float* pooled, int32_t* argidx,
-                                    uint64_t* mask1, uint32_t* mask2, const void* w3_bf, const float* w3_nw,
-                                    const float* w3_q, const void* w3_h, const float* w3_cw, void* stream);
-int pc3d_pointmlp3_max_fwd_screen_dbg_h_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
-                                            const float* T, const float* th_in, const float* th_W, const float* th_b,
-                                            int th_K, float* T_out, const float* W1, const float* b1, const float* W2,
-                                            const float* b2, const float* W3, const float* b3, int C1, int C2, int C3,
-                                            int relu_last, float* part_val, int32_t* part_idx, float* pooled,
-                                            int32_t* argidx, uint64_t* mask1, uint32_t* mask2, int32_t* stats,
-                                            float* dbg_S, float* dbg_E, int stop_after, const void* w3_bf,
-                                            const float* w3_nw, const float* w3_q, const void* w3_h, const float* w3_cw,
-                                            void* stream);
-/* The three entries above with the recheck laid out by (channel, candidate) PAIR, one lane each, instead of by channel
- * (csrc/pointmlp_screen.hip): the same arguments, the same bits in every output, the same stats and stop_after cuts.
- * A kernel instantiation of its own: while its first use on a device falls into a stream capture the launch runs the
- * channel recheck. pc3d_pointmlp3_pair_recheck_ready: 1 once the production instantiation can be launched on the
- * current device, 0 before. */
-int pc3d_pointmlp3_max_fwd_h_pair_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
-                                      const float* T, const float* W1, const float* b1, const float* W2, const float* b2,
-                                      const float* W3, const float* b3, int C1, int C2, int C3, int relu_last,
-                                      float* part_val, int32_t* part_idx, float* pooled, int32_t* argidx,
-                                      uint64_t* mask1, uint32_t* mask2, const void* w3_bf, const float* w3_nw,
-                                      const float* w3_q, const void* w3_h, const float* w3_cw, void* stream);
-int pc3d_pointmlp3_max_fwd_h_pair_th_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
-                                         const float* th_in, const float* th_W, const float* th_b, int th_K,
-                                         float* T_out, const float* W1, const float* b1, const float* W2,
-                                         const float* b2, const float* W3, const float* b3, int C1, int C2, int C3,
-                                         int relu_last, float* part_val, int32_t* part_idx, float* pooled,
-                                         int32_t* argidx, uint64_t* mask1, uint32_t* mask2, const void* w3_bf,
-                                         const float* w3_nw, const float* w3_q, const void* w3_h, const float* w3_cw,
-                                         void* stream);
-int pc3d_pointmlp3_max_fwd_screen_dbg_h_pair_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
-                                                 const float* T, const float* th_in, const float* th_W,
-                                                 const float* th_b, int th_K, float* T_out, const float* W1,
-                                                 const float* b1, const float* W2, const float* b2, const float* W3,
-                                                 const float* b3, int C1, int C2, int C3, int relu_last, float* part_val,
-                                                 int32_t* part_idx, float* pooled, int32_t* argidx, uint64_t* mask1,
-                                                 uint32_t* mask2, int32_t* stats, float* dbg_S, float* dbg_E,
-                                                 int stop_after, const void* w3_bf, const float* w3_nw,
-                                                 const float* w3_q, const void* w3_h, const float* w3_cw, void* stream);
-int pc3d_pointmlp3_pair_recheck_ready(void);
 
 /* Backward-to-input of the above (weights are frozen during an attack: no weight gradients, SURVEY A-14).
  * g_pooled [B,C3] is the upstream gradient on `pooled`; with relu_last the caller zeroes it where pooled <= 0.
  * T == NULL: grad_x receives the gradient w.r.t. the tower input. T given: the kernel chains through x' = x @ T:
  * grad_x receives the gradient w.r.t. the RAW points x, and part_gT (if non-NULL, workspace
- * [B, ceil(N / pc3d_pointmlp3_bwd_tile_points()), 16], 9 used) the per-tile partial sums of dL/dT (row-major 3x3);
- * their sum over tiles is the gradient that flows on into the STN head. accumulate != 0: grad_x += (used to add the
- * STN tower's contribution on top of the trunk's).
- * W2T is W2 transposed ([64,128] row-major); required, but the balanced kernel behind this entry (its packed form, see
- * pc3d_pointmlp3_max_bwd_tile32_f32 below) fetches its MFMA operand from W2 itself (coalesced in that operand's lane
- * order) and only the two-list entry below reads W2T.
+ * [B, ceil(N / pc3d_pointmlp3_bwd_tile_points()), 16], 9 used) the per-tile partial sums of dL/dT (row-major 3x3), one
+ * record per 32 points in every form; their sum over tiles is the gradient that flows on into the STN head.
+ * accumulate != 0: grad_x += (used to add the STN tower's contribution on top of the trunk's).
+ * W2T is W2 transposed ([64,128] row-major); required, but only the two-list form reads it: the balanced kernel fetches
+ * its MFMA operand from W2 itself (coalesced in that operand's lane order).
  * mask1 / mask2 are the forward launch's outputs of those names (required).
  * The max-pool routes each channel to one point, so the layer-3 dgrad is a sparse ordered gather: the tile's hits are
  * sorted by point and each point's row is one fma chain in ascending channel order, whole points shared out over the
- * workgroup's waves: deterministic, and independent of which wave runs a point. */
+ * workgroup's waves: deterministic, and independent of which wave runs a point.
+ * form: the same computation, bit for bit (tests/test_pointmlp_bwd_packed_gpu.py); everything but PC3D_PM_BWD_DEFAULT
+ * is for the parity tests and tools/bench_pointmlp.py.
+ *   PC3D_PM_BWD_DEFAULT   the one of the next two that the library prefers (the packed form)
+ *   PC3D_PM_BWD_PACKED    the balanced kernel, a workgroup per 128 points: argidx / g / W2 fetched once for them and the
+ *                         W2 product over the rows of points that have a hit only
+ *   PC3D_PM_BWD_TILE32    the balanced kernel, a workgroup per 32 points, every row of a tile through the W2 product
+ *   PC3D_PM_BWD_TWOLIST   the earlier two-list kernel (hits split at points 0-15 / 16-31, rows accumulated through LDS)
+ * stop_after: 0, or with PC3D_PM_BWD_PACKED only 1..5: end the launch after classification and count / sorted list /
+ * gather / W2 product / W1 product (timing only: outputs are not written). */
+enum { PC3D_PM_BWD_DEFAULT = 0, PC3D_PM_BWD_PACKED = 1, PC3D_PM_BWD_TILE32 = 2, PC3D_PM_BWD_TWOLIST = 3 };
 int pc3d_pointmlp3_max_bwd_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
                                const float* T, const float* W1, const float* b1, const float* W2,
                                const float* b2, const float* W3, const float* W2T, int C1, int C2, int C3,
                                const int32_t* argidx, const uint64_t* mask1, const uint32_t* mask2,
                                const float* g_pooled,
                                float* grad_x, int64_t gx_bs, int64_t gx_ps, int64_t gx_cs,
-                               float* part_gT, int accumulate, void* stream);
-/* The same computation, bit for bit, by the earlier two-list kernel (hits split at points 0-15 / 16-31, rows
- * accumulated through LDS). Kept as the parity reference of the balanced kernel above and for tools/bench_pointmlp.py;
- * nothing on a hot path calls it. */
-int pc3d_pointmlp3_max_bwd_twolist_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
-                                       const float* T, const float* W1, const float* b1, const float* W2,
-                                       const float* b2, const float* W3, const float* W2T, int C1, int C2, int C3,
-                                       const int32_t* argidx, const uint64_t* mask1, const uint32_t* mask2,
-                                       const float* g_pooled,
-                                       float* grad_x, int64_t gx_bs, int64_t gx_ps, int64_t gx_cs,
-                                       float* part_gT, int accumulate, void* stream);
-/* The two forms of the balanced kernel by name, bit for bit the same results (tests/test_pointmlp_bwd_packed_gpu.py):
- * tile32 — a workgroup per 32 points, every row of a tile through the W2 product; packed (stop_after = 0) — a workgroup
- * per 128 points, argidx / g / W2 fetched once for them and the W2 product over the rows of points that have a hit
- * only; part_gT keeps one record per pc3d_pointmlp3_bwd_tile_points() = 32 points in both. stop_after = 1..5 ends the
- * packed launch after classification and count / sorted list / gather / W2 product / W1 product (timing only: outputs
- * are not written).
- * pc3d_pointmlp3_max_bwd_f32 launches one of the two; only the parity test and tools/bench_pointmlp.py call these. */
-int pc3d_pointmlp3_max_bwd_tile32_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
-                                      const float* T, const float* W1, const float* b1, const float* W2,
-                                      const float* b2, const float* W3, const float* W2T, int C1, int C2, int C3,
-                                      const int32_t* argidx, const uint64_t* mask1, const uint32_t* mask2,
-                                      const float* g_pooled,
-                                      float* grad_x, int64_t gx_bs, int64_t gx_ps, int64_t gx_cs,
-                                      float* part_gT, int accumulate, void* stream);
-int pc3d_pointmlp3_max_bwd_packed_dbg_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
-                                          const float* T, const float* W1, const float* b1, const float* W2,
-                                          const float* b2, const float* W3, const float* W2T, int C1, int C2, int C3,
-                                          const int32_t* argidx, const uint64_t* mask1, const uint32_t* mask2,
-                                          const float* g_pooled,
-                                          float* grad_x, int64_t gx_bs, int64_t gx_ps, int64_t gx_cs,
-                                          float* part_gT, int accumulate, int stop_after, void* stream);
+                               float* part_gT, int accumulate, int form, int stop_after, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * PointNet with the feature transform (model/pointnet.py:51-87 STNkd, :101-117), eval mode, BatchNorm folded:
@@ -574,7 +478,7 @@ int pc3d_pointnet_ft_tower_fwd_f32(const float* x, int64_t x_bs, int64_t x_ps, i
 /* W2b[b][c][i] = sum_j W2[c][j] Tf[b][i][j] (W2 [128,64], Tf [B,64,64], W2b [B,128,64]); ascending j. */
 int pc3d_pointnet_ft_fold_w2_f32(const float* W2, const float* Tf, int B, float* W2b, void* stream);
 /* Backward-to-input of pc3d_pointnet_ft_tower_fwd_f32 (winners only: the ordered gather of
- * pc3d_pointmlp3_max_bwd_twolist_f32, then the masked layers on MFMA). grad_x receives (accumulate != 0: is added) the
+ * pc3d_pointmlp3_max_bwd_f32's PC3D_PM_BWD_TWOLIST form, then the masked layers on MFMA). grad_x receives (accumulate != 0: is added) the
  * gradient w.r.t. the RAW points; rows [gT_off, gT_off + ceil(N / pc3d_pointmlp3_bwd_tile_points())) of part_gT
  * [B, gT_tiles, 16] the per-tile partials of dL/dT, so that both towers' partials sit in ONE workspace the STN head's
  * backward sums. WA / maskA given: the 64 -> 64 form (W2q, q NULL). W2q / q given: the trunk; W2 is the folded
@@ -1399,7 +1303,9 @@ int pc3d_linear_book_f32(const float* X, int ldx, int P, int B, int K, const flo
  * pc3d_cw_update_f32 to the tower's input x (= the iterate adv, updated IN PLACE together with m / v, which share its
  * strides) instead of storing grad_x + this tower's gradient: distance gradient (dist_kind 0 / 1 / 2 as
  * pc3d_cw_step_f32; dist_val = ||adv-ori|| per sample for kind 1, nn_idx for kind 2), Adam with the factors adam [2] of
- * pc3d_linear_book_f32, ClipPointsLinf (budget > 0). grad_x is only read. */
+ * pc3d_linear_book_f32, ClipPointsLinf (budget > 0). grad_x is only read.
+ * form: PC3D_PM_BWD_DEFAULT, or PC3D_PM_BWD_PACKED / PC3D_PM_BWD_TILE32 by name (the same bits; parity test and bench
+ * tool only); the two-list kernel has no update epilogue: PC3D_PM_BWD_TWOLIST is PC3D_EINVAL here. */
 int pc3d_pointmlp3_max_bwd_update_f32(float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
                                       const float* W1, const float* b1, const float* W2, const float* b2,
                                       const float* W3, const float* W2T, int C1, int C2, int C3,
@@ -1408,27 +1314,7 @@ int pc3d_pointmlp3_max_bwd_update_f32(float* x, int64_t x_bs, int64_t x_ps, int6
                                       int64_t gx_cs, const float* ori, int64_t o_bs, int64_t o_ps, int64_t o_cs,
                                       float* m, float* v, double beta1, double beta2, double eps, float budget,
                                       const float* adam, int dist_kind, const float* w, const float* dist_val,
-                                      const int32_t* nn_idx, void* stream);
-/* The same launch by the tile32 / the packed form of the backward (see pc3d_pointmlp3_max_bwd_tile32_f32); the entry
- * above launches one of the two. Parity test and bench tool only. */
-int pc3d_pointmlp3_max_bwd_update_tile32_f32(float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
-                                             const float* W1, const float* b1, const float* W2, const float* b2,
-                                             const float* W3, const float* W2T, int C1, int C2, int C3,
-                                             const int32_t* argidx, const uint64_t* mask1, const uint32_t* mask2,
-                                             const float* g_pooled, const float* grad_x, int64_t gx_bs, int64_t gx_ps,
-                                             int64_t gx_cs, const float* ori, int64_t o_bs, int64_t o_ps, int64_t o_cs,
-                                             float* m, float* v, double beta1, double beta2, double eps, float budget,
-                                             const float* adam, int dist_kind, const float* w, const float* dist_val,
-                                             const int32_t* nn_idx, void* stream);
-int pc3d_pointmlp3_max_bwd_update_packed_f32(float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
-                                             const float* W1, const float* b1, const float* W2, const float* b2,
-                                             const float* W3, const float* W2T, int C1, int C2, int C3,
-                                             const int32_t* argidx, const uint64_t* mask1, const uint32_t* mask2,
-                                             const float* g_pooled, const float* grad_x, int64_t gx_bs, int64_t gx_ps,
-                                             int64_t gx_cs, const float* ori, int64_t o_bs, int64_t o_ps, int64_t o_cs,
-                                             float* m, float* v, double beta1, double beta2, double eps, float budget,
-                                             const float* adam, int dist_kind, const float* w, const float* dist_val,
-                                             const int32_t* nn_idx, void* stream);
+                                      const int32_t* nn_idx, int form, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * The isometry attack (attack/ISO/iso_attack.py): x' = W x with one 3x3 matrix per cloud, in front of a frozen victim.

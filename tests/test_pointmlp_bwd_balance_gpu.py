@@ -1,6 +1,6 @@
 """GPU parity, no tolerances: the balanced tower backward (pc3d_pointmlp3_max_bwd_f32: hits sorted by point, whole
 points shared out over the four waves, rows accumulated in registers) against the two-list kernel it replaced
-(pc3d_pointmlp3_max_bwd_twolist_f32). Both form every point's row by the same fma chain in ascending channel order, so
+(the same entry's PC3D_PM_BWD_TWOLIST form). Both form every point's row by the same fma chain in ascending channel order, so
 gx and part_gT must agree in every bit: they are compared as int32 words, which also pins the sign of zero and of
 infinity. The one thing left open is WHICH NaN a NaN is: a NaN must sit where the other kernel has a NaN, but its sign
 and payload may differ (x + y of two NaNs returns the payload of whichever operand the compiler put first; torch.equal

@@ -111,7 +111,7 @@ def test_forward_relu_masks_match_torch(ops, dev, B, N):
 
 @pytest.mark.parametrize("B,N,K", [(3, 200, 256), (2, 1024, 256), (1, 70, 64)])
 def test_transform_head_in_prologue(ops, dev, B, N, K):
-    """pc3d_pointmlp3_max_fwd_th_f32: the input transform T = h @ W.T + b (STN3d's fc3 + identity, model/pointnet.py:45-47)
+    """pc3d_pointmlp3_max_fwd_f32 with the transform head (th_in): the input transform T = h @ W.T + b (STN3d's fc3 + identity, model/pointnet.py:45-47)
     evaluated in the launch's prologue == the two-launch form (linear, then the tower with T given): T to fp32 rounding
     of a different summation order, pooled values accordingly, and the same arg-max points."""
     g = torch.Generator().manual_seed(K + N)
