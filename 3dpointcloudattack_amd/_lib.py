@@ -168,6 +168,10 @@ SIGNATURES = {
     "pc3d_linear_pre_f32": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P],
     "pc3d_pointmlp3_max_bwd_f32": _PTS + [_I, _I] + [_P] * 7 + [_I, _I, _I] + [_P, _P, _P, _P] + _PTS
     + [_P, _I, _I, _I, _P],
+    "pc3d_pointmlp3_max_fwd_ragged_f32": _PTS + [_I, _I] + [_P, _P, _P, _P, _I, _P] + [_P] * 6 + [_I, _I, _I, _I]
+    + [_P] * 6 + [_I] + [_P] * 5 + [_P, _P, _P, _I] + [_P, _P],
+    "pc3d_pointmlp3_max_bwd_ragged_f32": _PTS + [_I, _I] + [_P] * 7 + [_I, _I, _I] + [_P, _P, _P, _P] + _PTS
+    + [_P, _I, _I, _I, _P, _P],
     "pc3d_pointmlp3_bwd_tile_points": [],
     "pc3d_pointnet_ft_tower_fwd_f32": _PTS + [_I, _I] + [_P] * 6 + [_L] + [_P] * 3 + [_I] + [_P] * 5 + [_P],
     "pc3d_pointnet_ft_fold_w2_f32": [_P, _P, _I, _P, _P],

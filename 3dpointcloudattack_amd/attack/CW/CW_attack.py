@@ -353,8 +353,12 @@ class CW:
         ori_data = st["ori"]
         with torch.no_grad():
             cur = st["adv"].detach()
+            # a ragged batch on a victim that declares fused_lengths: its towers are given the lengths and skip the padding
+            vlens = {}
+            if st.get("lengths") is not None and getattr(_graphed.unwrap(self.model), "fused_lengths", False):
+                vlens = dict(lengths=st["lengths"])
             _, _, gx_model = self.model.fused_attack_grad(cur, st["target"], *fml, pred_out=st["pred"],
-                                                          step=st["step"], scale=st["ratio"] / st["B"])
+                                                          step=st["step"], scale=st["ratio"] / st["B"], **vlens)
             nn_idx = None
             if dk == 2:
                 _, nn_idx = ops.nn_raw(cur, ori_data, True, True)

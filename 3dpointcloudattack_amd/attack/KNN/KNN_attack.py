@@ -240,13 +240,17 @@ class CWKNN:
             lens = torch.ones((B,), dtype=torch.int32, device=dev)
             lens_host = np.ones((B,), dtype=np.int64)
             c_ch, c_knn = torch.zeros((B,), **f32), torch.zeros((B,), **f32)
+            vlens = dict(lengths=lens) if getattr(_graphed.unwrap(victim), "fused_lengths", False) else {}
 
             def body():
-                # the dense chain, launch for launch: the victim's passes on the padded batch (pad_invariant: the padding
-                # rows' gradient is exactly zero), the self-kNN search over every cloud's own points, the adv -> ori search
-                # unchanged (ori's padding rows are copies of its point 0 and lose every tie to it), the ragged update
+                # the dense chain, launch for launch: the victim's passes — given the lengths when the victim declares
+                # fused_lengths (its towers then skip the padding), else on the padded batch (pad_invariant: the padding
+                # rows' gradient is exactly zero either way) —, the self-kNN search over every cloud's own points, the
+                # adv -> ori search unchanged (ori's padding rows are copies of its point 0 and lose every tie to it), the
+                # ragged update
                 with torch.no_grad():
-                    _, _, gx = victim.fused_attack_grad(adv, target, kind, kappa, pred_out=pred, step=step, scale=plan["scale"])
+                    _, _, gx = victim.fused_attack_grad(adv, target, kind, kappa, pred_out=pred, step=step, scale=plan["scale"],
+                                                        **vlens)
                     if k:
                         ops.knn_search_into(adv, knn_d, knn_idx, lengths=lens, lengths_host=lens_host)
                     ops.nn_search_into(adv, ori, nn_d, nn_idx)

@@ -22,12 +22,19 @@
 
 namespace pc3d {
 
-__global__ __launch_bounds__(PM_FT) __attribute__((amdgpu_waves_per_eu(2, 2))) void pointmlp3_max_fwd_kernel(PMFwdArgs a) {
+// RAGGED: the cloud ends at its length instead of at N (pointmlp_body.h, PMFwdArgsR); a tile beyond it is skipped.
+template <bool RAGGED>
+__global__ __launch_bounds__(PM_FT) __attribute__((amdgpu_waves_per_eu(2, 2))) void pointmlp3_max_fwd_kernel(PMFwdArgsT<RAGGED> a) {
   __shared__ __attribute__((aligned(16))) float lds[PM_FWD_LDS_FLOATS];  // 69,120 B static
-  pm_fwd_prologue(a, lds);   // layers 1-2, masks, transform head: h2 [128][132] at lds, behind a barrier
-  float* h2 = lds;
   const int tile = blockIdx.x, b = blockIdx.y;
   const int n0 = tile * PM_TP;
+  int nb = a.N;              // the cloud's points
+  if constexpr (RAGGED) {
+    nb = pm_ragged_len(a.lengths, b, a.N);
+    if (n0 >= nb) return pm_fwd_skip_tile(a, b, tile);   // (uniform) ahead of the first barrier
+  }
+  pm_fwd_prologue<RAGGED>(a, lds, nb);   // layers 1-2, masks, transform head: h2 [128][132] at lds, behind a barrier
+  float* h2 = lds;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r = lane & 31, h = lane >> 5;
 
@@ -79,14 +86,14 @@ __global__ __launch_bounds__(PM_FT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
     // bounds test only runs in a ragged last tile): the epilogue's VALU instructions do not overlap the other wave's MFMAs
     int be = 0;
     const int base = n0 + ptile * 32;
-    if (base + 32 <= a.N) {             // (uniform)
+    if (base + 32 <= nb) {              // (uniform)
 #pragma unroll
       for (int e = 0; e < 16; ++e)      // ascending point index in e for fixed h: strict > keeps the lowest
         if (acc[e] > best) best = acc[e], be = (e & 3) + 8 * (e >> 2);
     } else {
 #pragma unroll
       for (int e = 0; e < 16; ++e)
-        if (base + (e & 3) + 8 * (e >> 2) + 4 * h < a.N && acc[e] > best) best = acc[e], be = (e & 3) + 8 * (e >> 2);
+        if (base + (e & 3) + 8 * (e >> 2) + 4 * h < nb && acc[e] > best) best = acc[e], be = (e & 3) + 8 * (e >> 2);
     }
     int bi = best == -__builtin_inff() ? base : base + be + 4 * h;
     argmax_xor32(best, bi);
@@ -917,8 +924,12 @@ __device__ __forceinline__ void pm_bwdp_stop(const PMBwdArgs& a, const float* ld
   if (threadIdx.x == 0 && __builtin_bit_cast(uint32_t, *lds_word) == 0x7fc12345u) a.gx.p[(int64_t)blockIdx.y * a.gx.bs] = 0.f;
 }
 
-template <bool UPD, int STOP>
-__device__ __forceinline__ void pm_bwdp_body(const PMBwdArgs& a, const PMUpdArgs& u) {
+// RAGGED (UPD = false, STOP = 0 only): lengths [B] is given and cloud b ends at nb = clamp(lengths[b], 1, N): x, mask1 and
+// mask2 are read below nb only, a hit at or beyond nb is dropped, gx rows in [nb, N) are written 0 (accumulate: left
+// alone) and their sub-tile records are zero. A workgroup at or beyond nb writes those zeros and scans nothing.
+template <bool UPD, int STOP, bool RAGGED = false>
+__device__ __forceinline__ void pm_bwdp_body(const PMBwdArgs& a, const PMUpdArgs& u, const int32_t* lengths = nullptr) {
+  static_assert(!RAGGED || (!UPD && STOP == 0), "the ragged twin is the production packed form only");
   constexpr int TP = PM_PTP, NT = PM_PNT, NW = PM_PNT / 64, CPT = PM_MAXC3 / PM_PNT;
   __shared__ __attribute__((aligned(16))) float g2s[TP * PM_LD2];   // [slot][132]  67.6 KB: every point may be live
   __shared__ __attribute__((aligned(16))) float h1s[TP * PM_LD1];   // [slot][68]   g1; before that the sort's counters
@@ -943,6 +954,17 @@ __device__ __forceinline__ void pm_bwdp_body(const PMBwdArgs& a, const PMUpdArgs
   const int lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
   const int pp = tid & (TP - 1), pc = tid >> 7;   // tid < 3 * TP: (point, coordinate) of the per-point operands
+  int nb = a.N;              // the cloud's points
+  if constexpr (RAGGED) {
+    nb = pm_ragged_len(lengths, b, a.N);
+    if (n0 >= nb) {          // (uniform) ahead of the first barrier
+      if (tid < 3 * TP && !a.accumulate && n0 + pp < a.N)
+        a.gx.p[(int64_t)b * a.gx.bs + (int64_t)(n0 + pp) * a.gx.ps + pc * a.gx.cs] = 0.f;
+      if (a.part_gT && wave < PM_PSUB && n0 + PM_BTP * wave < a.N && lane < 16)
+        a.part_gT[((int64_t)b * ((a.N + PM_BTP - 1) / PM_BTP) + tile * PM_PSUB + wave) * 16 + lane] = 0.f;
+      return;
+    }
+  }
 
   // ---- entry: every load that depends on nothing, smallest first (as pm_bwd_body)
   float ld_u[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
@@ -975,13 +997,13 @@ __device__ __forceinline__ void pm_bwdp_body(const PMBwdArgs& a, const PMUpdArgs
   }
   uint32_t ld_m2 = 0u;
   uint64_t ld_m1 = 0ull;
-  if (n0 + (tid >> 2) < a.N) ld_m2 = a.mask2[((int64_t)b * a.N + n0) * 4 + tid];
-  if (tid < TP && n0 + tid < a.N) ld_m1 = a.mask1[(int64_t)b * a.N + n0 + tid];
+  if (n0 + (tid >> 2) < nb) ld_m2 = a.mask2[((int64_t)b * a.N + n0) * 4 + tid];
+  if (tid < TP && n0 + tid < nb) ld_m1 = a.mask1[(int64_t)b * a.N + n0 + tid];
   const bool want_gT = a.T != nullptr && a.part_gT != nullptr;
   float ld_w1 = 0.f, ld_px = 0.f, ld_t = 0.f;
   if (tid < PM_C1 * 3) ld_w1 = a.W1[tid];
   if (tid < 3 * TP) {
-    if (n0 + pp < a.N) {
+    if (n0 + pp < nb) {
       if (want_gT) ld_px = a.x.p[(int64_t)b * a.x.bs + (int64_t)(n0 + pp) * a.x.ps + pc * a.x.cs];
       if (a.accumulate) ld_t = a.gx.p[(int64_t)b * a.gx.bs + (int64_t)(n0 + pp) * a.gx.ps + pc * a.gx.cs];
     }
@@ -1016,6 +1038,7 @@ __device__ __forceinline__ void pm_bwdp_body(const PMBwdArgs& a, const PMUpdArgs
       n = ld_n[e] - n0;
       const float gv = ld_g[e];
       if (n < 0 || n >= TP || gv == 0.f) n = -1;
+      if constexpr (RAGGED) n = n0 + n < nb ? n : -1;
       s_g[c] = gv;
     }
     myn[e] = n;
@@ -1214,6 +1237,9 @@ __device__ __forceinline__ void pm_bwdp_body(const PMBwdArgs& a, const PMUpdArgs
   } else if (live && ns + p < a.N) {
     float* o = a.gx.p + (int64_t)b * a.gx.bs + (int64_t)(ns + p) * a.gx.ps;
     if (a.accumulate) {
+      if constexpr (RAGGED) {
+        if (ns + p >= nb) return;   // an accumulating launch leaves the rows beyond the length alone
+      }
       o[0] = s_gxo[q] + o0, o[a.gx.cs] = s_gxo[TP + q] + o1, o[2 * a.gx.cs] = s_gxo[2 * TP + q] + o2;
     } else {
       o[0] = o0, o[a.gx.cs] = o1, o[2 * a.gx.cs] = o2;
@@ -1227,6 +1253,12 @@ __global__ __launch_bounds__(PM_PNT) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 __global__ __launch_bounds__(PM_PNT) __attribute__((amdgpu_waves_per_eu(2, 2))) void pointmlp3_max_bwd_update_packed_kernel(
     PMBwdArgs a, PMUpdArgs u) {
   pm_bwdp_body<true, 0>(a, u);
+}
+struct PMBwdArgsR : PMBwdArgs {
+  const int32_t* lengths;   // [B] (device memory, read as data)
+};
+__global__ __launch_bounds__(PM_PNT) __attribute__((amdgpu_waves_per_eu(2, 2))) void pointmlp3_max_bwd_packed_ragged_kernel(PMBwdArgsR a) {
+  pm_bwdp_body<false, 0, true>(a, PMUpdArgs{}, a.lengths);
 }
 template <int STOP>
 __global__ __launch_bounds__(PM_PNT) __attribute__((amdgpu_waves_per_eu(2, 2))) void pointmlp3_max_bwd_packed_dbg_kernel(PMBwdArgs a) {
@@ -1284,12 +1316,63 @@ extern "C" int pc3d_pointmlp3_max_fwd_f32(const float* x, int64_t x_bs, int64_t 
     rc = pm_fwd_screen_launch(a, B, stream, stats, dbg_S, dbg_E, stop_after, form, q, qh);
     if (rc < 0) return rc;
   }
-  if (rc != 0) hipLaunchKernelGGL(pointmlp3_max_fwd_kernel, dim3(ntiles, B), dim3(PM_FT), 0, st, a);
+  if (rc != 0) hipLaunchKernelGGL(pointmlp3_max_fwd_kernel<false>, dim3(ntiles, B), dim3(PM_FT), 0, st, a);
   PC3D_LAUNCH_CHECK("pc3d_pointmlp3_max_fwd_f32");
   if (pooled) {  // NULL: leave the per-tile partials unfolded (a fused consumer, or kernel-only timing)
     hipLaunchKernelGGL(pointmlp3_fold_kernel<false>, dim3(cdiv(C3, 256), B), dim3(256), 0, st, part_val, part_idx, ntiles,
                        C3, relu_last, pooled, argidx);
     PC3D_LAUNCH_CHECK("pc3d_pointmlp3_max_fwd_f32/fold");
+  }
+  return PC3D_OK;
+}
+
+// The forward with per-cloud lengths (include/pc3d.h: the contract and the argument rules). The exact kernel or the
+// production screened one, each in its ragged instantiation; the fold launch is the dense entry's.
+extern "C" int pc3d_pointmlp3_max_fwd_ragged_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                                 const float* T, const float* th_in, const float* th_W, const float* th_b,
+                                                 int th_K, float* T_out, const float* W1, const float* b1, const float* W2,
+                                                 const float* b2, const float* W3, const float* b3, int C1, int C2, int C3,
+                                                 int relu_last, float* part_val, int32_t* part_idx, float* pooled,
+                                                 int32_t* argidx, uint64_t* mask1, uint32_t* mask2, int form,
+                                                 const void* w3_bf, const float* w3_nw, const float* w3_q, const void* w3_h,
+                                                 const float* w3_cw, int32_t* stats, float* dbg_S, float* dbg_E,
+                                                 int stop_after, const int32_t* lengths, void* stream) {
+  PC3D_REQUIRE(lengths != nullptr, "pc3d_pointmlp3_max_fwd_ragged_f32: lengths [B] is required");
+  PC3D_REQUIRE(form == PC3D_PM_FWD_EXACT || form == PC3D_PM_FWD_SCREEN_H_PAIR,
+               "pc3d_pointmlp3_max_fwd_ragged_f32: form %d has no ragged twin (PC3D_PM_FWD_EXACT or PC3D_PM_FWD_SCREEN_H_PAIR)", form);
+  PC3D_REQUIRE(form != PC3D_PM_FWD_SCREEN_H_PAIR || (w3_bf && w3_nw && w3_q && w3_h && w3_cw),
+               "pc3d_pointmlp3_max_fwd_ragged_f32: both prepared images are needed");
+  PC3D_REQUIRE(stats == nullptr && dbg_S == nullptr && dbg_E == nullptr && stop_after == 0,
+               "pc3d_pointmlp3_max_fwd_ragged_f32: stats, dbg_S, dbg_E and stop_after belong to the dense entry's debug launch");
+  PC3D_REQUIRE(th_in == nullptr || (T == nullptr && th_W && th_b && T_out && th_K >= 1),
+               "pc3d_pointmlp3_max_fwd_ragged_f32: T or a complete transform head (input, weights [9,K], bias [9], T_out), not both");
+  PC3D_REQUIRE(B >= 0 && N >= 1, "pc3d_pointmlp3_max_fwd_ragged_f32: bad sizes B=%d N=%d", B, N);
+  PC3D_REQUIRE(C1 == PM_C1 && C2 == PM_C2 && C3 >= 32 && C3 % 32 == 0 && C3 <= PM_MAXC3F,
+               "pc3d_pointmlp3_max_fwd_ragged_f32: unsupported widths %d/%d/%d (need 64/128/multiple of 32 <= 1024)", C1, C2, C3);
+  PC3D_REQUIRE(B <= 65535, "pc3d_pointmlp3_max_fwd_ragged_f32: B=%d exceeds grid.y limit", B);
+  if (B == 0) return PC3D_OK;
+  PC3D_REQUIRE(x && W1 && b1 && W2 && b2 && W3 && b3 && part_val && part_idx,
+               "pc3d_pointmlp3_max_fwd_ragged_f32: null pointer");
+  PC3D_REQUIRE((pooled == nullptr) == (argidx == nullptr),
+               "pc3d_pointmlp3_max_fwd_ragged_f32: pooled and argidx must both be given or both be NULL");
+  PC3D_REQUIRE((mask1 == nullptr) == (mask2 == nullptr),
+               "pc3d_pointmlp3_max_fwd_ragged_f32: mask1 and mask2 must both be given or both be NULL");
+  const int ntiles = cdiv(N, PM_TP);
+  const PMFwdArgsR a{{{x, x_bs, x_ps, x_cs}, N, C3, ntiles, T, W1, b1, W2, b2, W3, b3, part_val, part_idx, mask1, mask2,
+                      th_in, th_W, th_b, th_K, T_out}, lengths};
+  hipStream_t st = as_stream(stream);
+  int rc = 1;
+  if (form != PC3D_PM_FWD_EXACT) {
+    const PMScreenPrepH qh{reinterpret_cast<decltype(PMScreenPrepH::w3_h)>(w3_h), w3_cw, w3_nw, reinterpret_cast<const float4*>(w3_q)};
+    rc = pm_fwd_screen_ragged_launch(a, B, stream, qh);
+    if (rc < 0) return rc;
+  }
+  if (rc != 0) hipLaunchKernelGGL(pointmlp3_max_fwd_kernel<true>, dim3(ntiles, B), dim3(PM_FT), 0, st, a);
+  PC3D_LAUNCH_CHECK("pc3d_pointmlp3_max_fwd_ragged_f32");
+  if (pooled) {
+    hipLaunchKernelGGL(pointmlp3_fold_kernel<false>, dim3(cdiv(C3, 256), B), dim3(256), 0, st, part_val, part_idx, ntiles,
+                       C3, relu_last, pooled, argidx);
+    PC3D_LAUNCH_CHECK("pc3d_pointmlp3_max_fwd_ragged_f32/fold");
   }
   return PC3D_OK;
 }
@@ -1371,6 +1454,34 @@ extern "C" int pc3d_pointmlp3_max_bwd_f32(const float* x, int64_t x_bs, int64_t 
       }
   }
   PC3D_LAUNCH_CHECK("pc3d_pointmlp3_max_bwd_f32");
+  return PC3D_OK;
+}
+
+// The backward with per-cloud lengths: the packed form's ragged instantiation (include/pc3d.h).
+extern "C" int pc3d_pointmlp3_max_bwd_ragged_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                                 const float* T, const float* W1, const float* b1, const float* W2,
+                                                 const float* b2, const float* W3, const float* W2T, int C1, int C2,
+                                                 int C3, const int32_t* argidx, const uint64_t* mask1,
+                                                 const uint32_t* mask2, const float* g_pooled, float* grad_x,
+                                                 int64_t gx_bs, int64_t gx_ps, int64_t gx_cs, float* part_gT,
+                                                 int accumulate, int form, int stop_after, const int32_t* lengths,
+                                                 void* stream) {
+  PC3D_REQUIRE(lengths != nullptr, "pc3d_pointmlp3_max_bwd_ragged_f32: lengths [B] is required");
+  PC3D_REQUIRE(form == PC3D_PM_BWD_DEFAULT || form == PC3D_PM_BWD_PACKED,
+               "pc3d_pointmlp3_max_bwd_ragged_f32: form %d has no ragged twin (PC3D_PM_BWD_DEFAULT or PC3D_PM_BWD_PACKED)", form);
+  PC3D_REQUIRE(stop_after == 0, "pc3d_pointmlp3_max_bwd_ragged_f32: stop_after = %d belongs to the dense entry", stop_after);
+  static_assert(PM_BWD_DEFAULT_FORM == PC3D_PM_BWD_PACKED, "the ragged twin is the default form's");
+  PC3D_REQUIRE(B >= 0 && N >= 1, "pc3d_pointmlp3_max_bwd_ragged_f32: bad sizes B=%d N=%d", B, N);
+  PC3D_REQUIRE(C1 == PM_C1 && C2 == PM_C2 && C3 >= 32 && C3 % 32 == 0 && C3 <= PM_MAXC3,
+               "pc3d_pointmlp3_max_bwd_ragged_f32: unsupported widths %d/%d/%d", C1, C2, C3);
+  PC3D_REQUIRE(B <= 65535, "pc3d_pointmlp3_max_bwd_ragged_f32: B=%d exceeds grid.y limit", B);
+  if (B == 0) return PC3D_OK;
+  PC3D_REQUIRE(x && W1 && b1 && W2 && b2 && W3 && W2T && argidx && mask1 && mask2 && g_pooled && grad_x,
+               "pc3d_pointmlp3_max_bwd_ragged_f32: null pointer");
+  const PMBwdArgsR a{{{x, x_bs, x_ps, x_cs}, N, C3, T, W1, b1, W2, b2, W3, W2T, argidx, mask1, mask2, g_pooled,
+                      {grad_x, gx_bs, gx_ps, gx_cs}, part_gT, accumulate}, lengths};
+  hipLaunchKernelGGL(pointmlp3_max_bwd_packed_ragged_kernel, dim3(cdiv(N, PM_PTP), B), dim3(PM_PNT), 0, as_stream(stream), a);
+  PC3D_LAUNCH_CHECK("pc3d_pointmlp3_max_bwd_ragged_f32");
   return PC3D_OK;
 }
 

@@ -1,6 +1,7 @@
 // Device code shared by the PointNet tower kernels (pointmlp.hip, pointmlp_ft.hip): tile constants, the point load
 // with the 3 x 3 input transform, and layer 1 (3 -> 64, ReLU) into LDS with its decision masks.
 #pragma once
+#include <type_traits>
 #include "pc3d_common.h"
 
 namespace pc3d {
@@ -80,11 +81,48 @@ struct PMFwdArgs {
   float* th_out;
 };
 
+// The ragged instantiations' arguments: the dense ones and lengths [B] (device memory, read as data). A launch that
+// carries them treats cloud b as L = clamp(lengths[b], 1, N) points: N stays the buffers' row count (every stride and the
+// tile count), rows at and beyond L are never read and are handled as rows beyond N are (include/pc3d.h, the contract).
+struct PMFwdArgsR : PMFwdArgs {
+  const int32_t* lengths;
+};
+template <bool RAGGED>
+using PMFwdArgsT = std::conditional_t<RAGGED, PMFwdArgsR, PMFwdArgs>;
+
+__device__ __forceinline__ int pm_ragged_len(const int32_t* lengths, int b, int N) {
+  const int l = lengths[b];
+  return l < 1 ? 1 : l > N ? N : l;
+}
+
+// zero mask words for the workgroup's rows n0 + [0, 128) that lie in [from, N): thread = (row tid >> 2, mask2 word tid & 3)
+__device__ __forceinline__ void pm_fwd_zero_masks(const PMFwdArgs& a, int b, int n0, int from) {
+  if (a.mask1 == nullptr) return;
+  const int n = n0 + ((int)threadIdx.x >> 2);
+  if (threadIdx.x < 4 * PM_TP && n >= from && n < a.N) {
+    a.mask2[((int64_t)b * a.N + n) * 4 + (threadIdx.x & 3)] = 0u;
+    if ((threadIdx.x & 3) == 0) a.mask1[(int64_t)b * a.N + n] = 0ull;
+  }
+}
+
+// A workgroup whose whole tile lies at or beyond its cloud's length (tile >= 1: tile 0 always holds point 0). It leaves
+// ahead of the prologue's first barrier having written partials that the folds' strict `>` never takes and zero masks.
+__device__ __forceinline__ void pm_fwd_skip_tile(const PMFwdArgs& a, int b, int tile) {
+  const int64_t o = ((int64_t)b * a.ntiles + tile) * a.C3;
+  for (int ch = threadIdx.x; ch < a.C3; ch += PM_FT) {
+    a.part_val[o + ch] = -__builtin_inff();
+    a.part_idx[o + ch] = 0;
+  }
+  pm_fwd_zero_masks(a, b, tile * PM_TP, tile * PM_TP);
+}
+
 constexpr int PM_FWD_LDS_FLOATS = PM_TP * PM_LD2 + 3 * PM_TP;   // h2 tile [128][132] (h1 aliases it) + xs [3][128]
 
 // Transform head, x . T, layer 1 (VALU) and layer 2 (fp32 MFMA) of the workgroup's 128 points; mask1 / mask2 / th_out
 // leave here. On return h2 [128][PM_LD2] sits at lds and every wave has passed the barrier behind its last write.
-__device__ __forceinline__ void pm_fwd_prologue(const PMFwdArgs& a, float* lds) {
+// nb: the cloud's points, a.N in a dense launch, its length in a ragged one (rows in [nb, a.N) get zero mask words).
+template <bool RAGGED = false>
+__device__ __forceinline__ void pm_fwd_prologue(const PMFwdArgs& a, float* lds, int nb) {
   float* h1 = lds;                       // [128][68]   (dead after layer 2)
   float* h2 = lds;                       // [128][132]  (overwrites h1 behind a barrier)
   float* xs = lds + PM_TP * PM_LD2;      // [3][128]
@@ -96,7 +134,8 @@ __device__ __forceinline__ void pm_fwd_prologue(const PMFwdArgs& a, float* lds) 
   const float* Tb = a.T ? a.T + (int64_t)b * 9 : nullptr;
   // raw coordinates first (their load latency overlaps the transform head's), the transform is applied afterwards
   float px = 0.f, py = 0.f, pz = 0.f;
-  if (threadIdx.x < PM_TP) load_point(a.x, nullptr, b, n0 + threadIdx.x, a.N, px, py, pz);
+  if (threadIdx.x < PM_TP) load_point(a.x, nullptr, b, n0 + threadIdx.x, nb, px, py, pz);
+  if constexpr (RAGGED) pm_fwd_zero_masks(a, b, n0, nb);
   if (a.th_in) {   // 9 outputs x th_K: 32 lanes per output, strided partial sums + a half-wave reduction
     __shared__ float Ts[9];
     if (threadIdx.x < 9 * 32) {
@@ -136,7 +175,7 @@ __device__ __forceinline__ void pm_fwd_prologue(const PMFwdArgs& a, float* lds) 
     xs[2 * PM_TP + threadIdx.x] = pz;
   }
   __syncthreads();
-  layer1_to_lds<PM_TP, PM_FT>(xs, h1, a.W1, a.b1, a.mask1 ? a.mask1 + (int64_t)b * a.N + n0 : nullptr, a.N - n0);
+  layer1_to_lds<PM_TP, PM_FT>(xs, h1, a.W1, a.b1, a.mask1 ? a.mask1 + (int64_t)b * a.N + n0 : nullptr, nb - n0);
   __syncthreads();
 
   // ---- layer 2 on MFMA: D[pt][c2] = sum_k h1[pt][k] W2[c2][k]; wave owns c2 block (wave&3) and 2 of the 4 point tiles
@@ -180,8 +219,8 @@ __device__ __forceinline__ void pm_fwd_prologue(const PMFwdArgs& a, float* lds) 
       const int tl = lane >> 4, e = lane & 15;
       const int pt0 = n0 + (tl0 + tl) * 32 + (e & 3) + 8 * (e >> 2);
       uint32_t* m2 = a.mask2 + ((int64_t)b * a.N) * 4 + c2b;
-      if (pt0 < a.N) m2[(int64_t)pt0 * 4] = (uint32_t)mine;
-      if (pt0 + 4 < a.N) m2[(int64_t)(pt0 + 4) * 4] = (uint32_t)(mine >> 32);
+      if (pt0 < nb) m2[(int64_t)pt0 * 4] = (uint32_t)mine;
+      if (pt0 + 4 < nb) m2[(int64_t)(pt0 + 4) * 4] = (uint32_t)(mine >> 32);
     }
   }
   __syncthreads();
@@ -211,6 +250,9 @@ struct PMScreenPrepH {
 // (the caller launches the exact kernel), < 0 on an error. prep / hprep: read by PREP and the H forms / by the H forms.
 int pm_fwd_screen_launch(const PMFwdArgs& a, int B, void* stream, int32_t* stats, float* dbg_S, float* dbg_E,
                          int stop_after, int form, const PMScreenPrep& prep, const PMScreenPrepH& hprep);
+// The ragged instantiation of the production form, PC3D_PM_FWD_SCREEN_H_PAIR. Returns 0 when launched, 1 when it cannot
+// be yet (its first use on the device falls into a capture: the caller launches the ragged exact kernel), < 0 on an error.
+int pm_fwd_screen_ragged_launch(const PMFwdArgsR& a, int B, void* stream, const PMScreenPrepH& hprep);
 // pm_fwd_pair_ready: 1 once the production H_PAIR instantiation can be launched on the current device.
 int pm_fwd_pair_ready();
 // w3_bf (C3 * 512 B), w3_nw (C3 floats), w3_q (C3 * 128 floats) from the folded fp32 W3 [C3,128]

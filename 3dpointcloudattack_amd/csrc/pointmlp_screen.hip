@@ -208,7 +208,7 @@ __global__ __launch_bounds__(PM_FT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
   __bf16* s_a16 = reinterpret_cast<__bf16*>(reinterpret_cast<char*>(pms_lds) +
                                             (PREP ? PMS_A16_OFF_PREP : PMS_A16_OFF));   // [128][PMS_LDA] bf16 image of h2: hi
   __bf16* s_a16l = s_a16 + PM_TP * PMS_LDA;                                         // and lo terms
-  pm_fwd_prologue(a, pms_lds);
+  pm_fwd_prologue(a, pms_lds, a.N);
   const int tile = blockIdx.x, b = blockIdx.y;
   const int n0 = tile * PM_TP;
   const int nvalid = a.N - n0;            // >= 1
@@ -648,9 +648,12 @@ __global__ __launch_bounds__(64) void pms_w3_prepare_h_kernel(const float* __res
 }
 
 // PAIR: the recheck goes by (channel, candidate) PAIR, one lane each, instead of by channel (further down).
-template <bool DBG, bool DUMP, bool PAIR>
+// RAGGED (the production instantiation <false, false, true> only): the cloud ends at its length instead of at N
+// (pointmlp_body.h, PMFwdArgsR); a tile beyond it is skipped.
+template <bool DBG, bool DUMP, bool PAIR, bool RAGGED = false>
 __global__ __launch_bounds__(PM_FT) __attribute__((amdgpu_waves_per_eu(2, 2))) void pointmlp3_max_fwd_screen_h_kernel(
-    PMFwdArgs a, PMScreenDbg d, PMScreenPrepH w3) {
+    PMFwdArgsT<RAGGED> a, PMScreenDbg d, PMScreenPrepH w3) {
+  static_assert(!RAGGED || (!DBG && !DUMP && PAIR), "the ragged twin is the production form only");
   extern __shared__ __attribute__((aligned(16))) float pms_lds[];
   float* h2 = pms_lds;                                                              // [128][132] fp32, kept to the end
   float* s_na = pms_lds + PM_FWD_LDS_FLOATS;                                        // [128] na 2^sa + 1 (+inf: no such point)
@@ -659,7 +662,12 @@ __global__ __launch_bounds__(PM_FT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
   _Float16* s_a16 = reinterpret_cast<_Float16*>(reinterpret_cast<char*>(pms_lds) + PMH_A16_OFF);   // [128][PMS_LDA]
   const int tile = blockIdx.x, b = blockIdx.y;
   const int n0 = tile * PM_TP;
-  const int nvalid = a.N - n0;            // >= 1
+  int nb = a.N;                           // the cloud's points
+  if constexpr (RAGGED) {
+    nb = pm_ragged_len(a.lengths, b, a.N);
+    if (n0 >= nb) return pm_fwd_skip_tile(a, b, tile);   // (uniform) ahead of the first barrier
+  }
+  const int nvalid = nb - n0;             // >= 1
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r = lane & 31, h = lane >> 5;
   const int64_t obase = ((int64_t)b * a.ntiles + tile) * a.C3;
@@ -675,7 +683,7 @@ __global__ __launch_bounds__(PM_FT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
     cw_next = w3.w3_cw[wave * 32 + r];
   }
   if (threadIdx.x == 0) *s_amax = 0u;     // outside what the prologue touches; its barriers publish it
-  pm_fwd_prologue(a, pms_lds);
+  pm_fwd_prologue<RAGGED>(a, pms_lds, nb);
 
   // ---- one norm per point (4 threads per point, 32 k each, fixed order: PREP's na in every bit), the tile's largest,
   // then h2's fp16 image with the tile's scale
@@ -818,7 +826,7 @@ __global__ __launch_bounds__(PM_FT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
       cw_next = w3.w3_cw[nxt * 32 + r];
     }
     if (fall) {
-      pms_exact_block(h2, a.W3, a.b3, cb, n0, a.N, a.part_val + obase, a.part_idx + obase);
+      pms_exact_block(h2, a.W3, a.b3, cb, n0, nb, a.part_val + obase, a.part_idx + obase);
       ++nfall;
     }
   }
@@ -986,8 +994,8 @@ template <auto KERNEL>
 static bool pms_usable[64] = {};
 
 // 0: launched. 1: not launched — the instantiation cannot be yet (the caller takes the next form). < 0: an error.
-template <auto KERNEL, size_t LDS, class Q>
-static int pms_launch_t(const PMFwdArgs& a, int B, hipStream_t st, const PMScreenDbg& d, const Q& q) {
+template <auto KERNEL, size_t LDS, class Q, class A = PMFwdArgs>
+static int pms_launch_t(const A& a, int B, hipStream_t st, const PMScreenDbg& d, const Q& q) {
   int dev = 0;
   PC3D_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "pointmlp3 screen: no current device");
   if (!pms_usable<KERNEL>[dev]) {
@@ -1051,6 +1059,12 @@ int pm_fwd_screen_launch(const PMFwdArgs& a, int B, void* stream, int32_t* stats
     default:
       return pms_launch_form<false>(a, B, st, d, PMScreenPrep{nullptr, nullptr, nullptr});
   }
+}
+
+// (named behind every dense instantiation: the kernels keep their order in the code object)
+int pm_fwd_screen_ragged_launch(const PMFwdArgsR& a, int B, void* stream, const PMScreenPrepH& hprep) {
+  return pms_launch_t<pointmlp3_max_fwd_screen_h_kernel<false, false, true, true>, PMP_LDS_BYTES>(
+      a, B, as_stream(stream), PMScreenDbg{nullptr, nullptr, nullptr, 0}, hprep);
 }
 
 int pm_fwd_pair_ready() { return pms_h_usable<true>() ? 1 : 0; }

@@ -219,6 +219,9 @@ class PointNetCls(_FrozenFusedMixin, nn.Module):
         self.feature_transform = feature_transform
         # the 15-launch riders iteration exists for the two-tower victim only; attack loops ask the instance
         self.has_fused_attack_update = not feature_transform
+        # the fused passes take per-cloud lengths (fused_forward(..., lengths=)): the two-tower victim's tower kernels
+        # have ragged twins, the feature-transform victim's (csrc/pointmlp_ft.hip) do not and keep the padded pass
+        self.fused_lengths = not feature_transform
         self.feat = PointNetfeat(global_feat=True, feature_transform=feature_transform)
         self.fc1 = nn.Linear(1024, 512)
         self.fc2 = nn.Linear(512, 256)
@@ -234,18 +237,19 @@ class PointNetCls(_FrozenFusedMixin, nn.Module):
                 _fold_bn(self.fc2.weight, self.fc2.bias, self.bn2),   # dropout is identity in eval
                 _plain(self.fc3.weight, self.fc3.bias))
 
-    def fused_loss_and_grad(self, x, target, kind, kappa=0.0, scale=None):
+    def fused_loss_and_grad(self, x, target, kind, kappa=0.0, scale=None, lengths=None):
         """Attack fast path (no autograd): (logp [B,k], pred [B], per-sample adv loss [B], d mean(loss)/dx).
-        kind in ops.LOSS_KINDS. Numerically the same computation as forward() + autograd, in ~20 launches."""
-        logits, ctx = fused_forward(self, x)
+        kind in ops.LOSS_KINDS. Numerically the same computation as forward() + autograd, in ~20 launches.
+        lengths: see fused_forward; the gradient rows behind a cloud's length are zero."""
+        logits, ctx = fused_forward(self, x, lengths=lengths)
         logp, pred, loss, g_logits = ops.cls_loss(logits, target, kind, kappa,
                                                   scale=1.0 / x.shape[0] if scale is None else scale)
         return logp, pred, loss, fused_input_grad(ctx, g_logits)
 
-    def fused_attack_grad(self, x, target, kind, kappa=0.0, pred_out=None, step=None, scale=None):
+    def fused_attack_grad(self, x, target, kind, kappa=0.0, pred_out=None, step=None, scale=None, lengths=None):
         """fused_loss_and_grad for the attack loops: the classifier tail (fc3, loss, fc3 backward) is one launch that
         also writes the prediction into `pred_out` and advances the device step word. Returns (pred, loss, dL/dx)."""
-        _, ctx = fused_forward(self, x, tail=False)
+        _, ctx = fused_forward(self, x, tail=False, lengths=lengths)
         c2, pk = ctx[9], ctx[1]
         _, pred, loss, g_c2 = ops.cls_tail(c2, pk["c"][4], pk["c"][5], target, kind, kappa,
                                            scale=1.0 / x.shape[0] if scale is None else scale,
@@ -351,18 +355,30 @@ def _fused_pack(model):
                 s_t=(_t(w1s), _t(w2s), w3s_t.contiguous()), c_t=(_t(w1c), _t(w2c), _t(w3c)))
 
 
-def fused_forward(model, x, tail=True):
+class _LengthsCtx(tuple):
+    """fused_forward's ctx of a pass that was given lengths: the same twelve items, the lengths as an attribute."""
+    lengths = None
+
+
+def fused_forward(model, x, tail=True, lengths=None):
     """Launch-minimal forward of PointNetCls: 2 tower launches (+2 folds) + 5 head launches, no autograd graph.
     Returns (logits [B,k] PRE-softmax, ctx) — ctx feeds fused_input_grad.
     A feature-transform victim: 3 tower launches (+3 folds), the W2 fold, 9 head launches; ctx has a 13th item.
-    A model that is not a PointNetCls but brings its own ``fused_forward`` (defense.FusedDefended) runs that one."""
+    A model that is not a PointNetCls but brings its own ``fused_forward`` (defense.FusedDefended) runs that one.
+    lengths: None, or an int32 [B] device tensor — cloud b has lengths[b] points and both towers (and, through the ctx,
+    both tower backwards) run their ragged launches: the rows behind a length are never read, the logits are those of the
+    batch padded with copies of point 0, the gradient rows behind a length are zero. For a victim that declares
+    fused_lengths only (the two-tower one); any other raises."""
+    if lengths is not None and not (isinstance(model, PointNetCls) and model.fused_lengths):
+        raise ValueError("fused_forward: lengths need a victim that declares fused_lengths (PointNetCls without the "
+                         "feature transform); run the padded pass")
     if not isinstance(model, PointNetCls) and hasattr(model, "fused_forward"):
         return model.fused_forward(x, tail)
     model._require_fused(x)
     pk = fused_pack(model)
     w1s, b1s, w2s, b2s, w3s, b3s = pk["s"]
     w1c, b1c, w2c, b2c, w3c, b3c = pk["c"]
-    pooled_s, idx_s, masks_s = ops.pointmlp3_max_fwd_raw(x, pk["tower_s"], True, want_masks=True)
+    pooled_s, idx_s, masks_s = ops.pointmlp3_max_fwd_raw(x, pk["tower_s"], True, want_masks=True, lengths=lengths)
     a1 = ops.linear(pooled_s, w1s, b1s, relu=True)
     a2 = ops.linear(a1, w2s, b2s, relu=True)
     ft = None
@@ -372,11 +388,15 @@ def fused_forward(model, x, tail=True):
         idx = masks = None
     else:
         # the transform (STN fc3 + identity, [B,9]) is computed in the trunk tower's prologue: no launch of its own
-        pooled, idx, masks, trans = ops.pointmlp3_max_fwd_raw(x, pk["tower_c"], False, want_masks=True, T_head=(a2, w3s, b3s))
+        pooled, idx, masks, trans = ops.pointmlp3_max_fwd_raw(x, pk["tower_c"], False, want_masks=True, T_head=(a2, w3s, b3s),
+                                                              lengths=lengths)
     c1 = ops.linear(pooled, w1c, b1c, relu=True)
     c2 = ops.linear(c1, w2c, b2c, relu=True)
     logits = ops.linear(c2, w3c, b3c) if tail else None
     ctx = (x, pk, pooled_s, idx_s, a1, a2, trans, idx, c1, c2, masks_s, masks)
+    if lengths is not None:
+        ctx = _LengthsCtx(ctx)
+        ctx.lengths = lengths
     return logits, ctx if ft is None else ctx + (ft,)
 
 
@@ -386,6 +406,7 @@ def fused_input_grad(ctx, g_logits, out=None, g_c2=None):
     if hasattr(ctx, "fused_input_grad"):
         return ctx.fused_input_grad(g_logits, out=out, g_c2=g_c2)
     x, pk, pooled_s, idx_s, a1, a2, trans, idx, c1, c2, masks_s, masks = ctx[:12]
+    lengths = getattr(ctx, "lengths", None)   # a pass that was given lengths (the two-tower victim only)
     w1c_t, w2c_t, w3c_t = pk["c_t"]
     w1s_t, w2s_t, w3s_t = pk["s_t"]
     if g_c2 is None:
@@ -395,7 +416,8 @@ def fused_input_grad(ctx, g_logits, out=None, g_c2=None):
     if len(ctx) > 12:   # feature transform: trunk, dL/dTf, STNkd head and tower; both towers' dL/dT partials in part_gT
         gx, part_gT = ops.pointnet_ft_feat_bwd(ctx[12], g_pooled, out=out)
     else:
-        gx, part_gT = ops.pointmlp3_max_bwd_raw(x, pk["tower_c"], idx, g_pooled, masks, T=trans, want_gT=True, out=out)
+        gx, part_gT = ops.pointmlp3_max_bwd_raw(x, pk["tower_c"], idx, g_pooled, masks, T=trans, want_gT=True, out=out,
+                                                lengths=lengths)
     # fc3's backward (dL/dT partials summed, 9 -> 256, ReLU mask of a2) runs inside the launch of fc2's backward
     g_a1 = ops.linear_pre(part_gT, 9, pk["s"][4], a2, w2s_t, gate=a1)
     g_pooled_s = ops.linear(g_a1, w1s_t, gate=pooled_s)                 # ReLU after the STN max-pool
@@ -403,7 +425,7 @@ def fused_input_grad(ctx, g_logits, out=None, g_c2=None):
         ts = pk["tower_s"]
         ops.pointnet_ft_tower_bwd_raw(x, None, ts[0], ts[2], ts[4], idx_s, g_pooled_s, masks_s, None, 0, out=gx, accumulate=True)
     else:
-        ops.pointmlp3_max_bwd_raw(x, pk["tower_s"], idx_s, g_pooled_s, masks_s, out=gx, accumulate=True)
+        ops.pointmlp3_max_bwd_raw(x, pk["tower_s"], idx_s, g_pooled_s, masks_s, out=gx, accumulate=True, lengths=lengths)
     return gx
 
 

@@ -479,6 +479,15 @@ def _pm_fwd_form(exact, in_launch, have_image, have_h_image, form, recheck, dbg)
     return PM_FWD_SCREEN_H_PAIR if (recheck or PM_FWD_DEFAULT_RECHECK) == "pair" else PM_FWD_SCREEN_H
 
 
+def _pm_fwd_form_ragged(exact, have_image, have_h_image):
+    """Which form of pc3d_pointmlp3_max_fwd_ragged_f32 pointmlp3_max_fwd_raw(lengths=...) launches: PM_FWD_EXACT on
+    request, PM_FWD_SCREEN_H_PAIR (the production form, the only screened one with a ragged twin) when both prepared
+    images of W3 exist, PM_FWD_EXACT otherwise."""
+    if exact:
+        return PM_FWD_EXACT
+    return PM_FWD_SCREEN_H_PAIR if have_image and have_h_image else PM_FWD_EXACT
+
+
 def _pm_bwd_form(twolist, tile32):
     """The form of the two backward entries: twolist, else tile32 None / True / False = the default / tile32 / packed."""
     return PM_BWD_TWOLIST if twolist else PM_BWD_DEFAULT if tile32 is None else PM_BWD_TILE32 if tile32 else PM_BWD_PACKED
@@ -492,7 +501,7 @@ def pointmlp3_pair_recheck_ready(device):
 
 
 def pointmlp3_max_fwd_raw(x, weights, relu_last, T=None, x_cf=True, fold=True, want_masks=False, T_head=None, serial=False,
-                          exact=False, screen_dbg=None, in_launch=False, form=None, recheck=None):
+                          exact=False, screen_dbg=None, in_launch=False, form=None, recheck=None, lengths=None):
     """x [B,3,N] (x_cf) or [B,N,3]; weights = (W1[64,3], b1, W2[128,64], b2, W3[C3,128], b3) with eval-BN folded.
     Returns (pooled [B,C3] f32, argidx [B,C3] i32) and, with want_masks, a third item (mask1 [B,N] i64, mask2 [B,N,4]
     i32): the per-point ReLU decisions of layers 1 and 2 as bit masks, which pointmlp3_max_bwd_raw consumes.
@@ -513,8 +522,20 @@ def pointmlp3_max_fwd_raw(x, weights, relu_last, T=None, x_cf=True, fold=True, w
     output either way. Under form="fp16" screen_dbg's "S" and "E" come back in the unscaled domain.
     recheck: how the fp16 form rechecks — "channel", "pair" or None: PM_FWD_DEFAULT_RECHECK. Naming one with form=None
     selects the fp16 form (under screen_dbg too, so "stats" and "stop_after" serve both); with form="bf16" it is an
-    error. The same bits in every output either way."""
+    error. The same bits in every output either way.
+    lengths: None, or an int32 [B] device tensor — cloud b has clamp(lengths[b], 1, N) points and the rows behind them are
+    never read (pc3d_pointmlp3_max_fwd_ragged_f32, include/pc3d.h: the same bits as the dense launch on the rows below a
+    length, zero mask words behind it). The production form runs when both prepared images exist, else (and with
+    exact=True) the exact kernel; in_launch, form="bf16", recheck="channel", screen_dbg and serial name launches that
+    have no ragged twin: ValueError."""
+    if lengths is not None:     # (checked first: the options are refused whatever else is given)
+        refused = {"in_launch": in_launch, "form='bf16'": form == "bf16", "recheck='channel'": recheck == "channel",
+                   "screen_dbg": screen_dbg is not None, "serial": serial}
+        if any(refused.values()):
+            raise ValueError("pointmlp3_max_fwd_raw: no ragged twin (lengths) for " + ", ".join(k for k, v in refused.items() if v))
     xp, xbs, xps, xcs, B, N = _pts(x, x_cf, "x")
+    if lengths is not None:
+        _lengths_arg("pointmlp3_max_fwd_raw", lengths, B, x.device)
     W1, b1, W2, b2, W3, b3 = weights[:6]
     for w in weights[:7]:
         _check(w, "weight")
@@ -541,7 +562,11 @@ def pointmlp3_max_fwd_raw(x, weights, relu_last, T=None, x_cf=True, fold=True, w
     with torch.cuda.device(dev):
         prep = None if exact or in_launch else _pm_w3_pack(weights, W3)
         hp = _pm_w3_h(prep[0]) if prep is not None and form != "bf16" else None
-        kform = _pm_fwd_form(exact, in_launch, prep is not None, hp is not None, form, recheck, screen_dbg is not None)
+        if lengths is not None:
+            _pm_fwd_form(exact, False, prep is not None, hp is not None, form, recheck, False)   # form / recheck validated
+            kform = _pm_fwd_form_ragged(exact, prep is not None, hp is not None)
+        else:
+            kform = _pm_fwd_form(exact, in_launch, prep is not None, hp is not None, form, recheck, screen_dbg is not None)
         img = (tuple(t.data_ptr() for t in prep) if prep is not None else (0, 0, 0)) + (hp[1] if hp is not None else (0, 0))
         th = (0, 0, 0, 0, 0)
         if T_head is not None:
@@ -561,7 +586,13 @@ def pointmlp3_max_fwd_raw(x, weights, relu_last, T=None, x_cf=True, fold=True, w
                 dE = torch.full((B, N, C3), float("nan"), dtype=torch.float32, device=dev)
                 screen_dbg["S"], screen_dbg["E"] = dS, dE
             dbg = (screen_dbg["stats"].data_ptr(), _ptr(dS), _ptr(dE), int(screen_dbg.get("stop_after", 0)))
-        _lib.call("pc3d_pointmlp3_max_fwd_f32", xp, xbs, xps, xcs, B, N, _ptr(T), *th, *tail[:-1], kform, *img, *dbg, tail[-1])
+        if lengths is not None:
+            if kform == PM_FWD_EXACT:
+                img = (0, 0, 0, 0, 0)
+            _lib.call("pc3d_pointmlp3_max_fwd_ragged_f32", xp, xbs, xps, xcs, B, N, _ptr(T), *th, *tail[:-1], kform, *img, *dbg,
+                      lengths.data_ptr(), tail[-1])
+        else:
+            _lib.call("pc3d_pointmlp3_max_fwd_f32", xp, xbs, xps, xcs, B, N, _ptr(T), *th, *tail[:-1], kform, *img, *dbg, tail[-1])
         if fold and serial:
             _lib.call("pc3d_pointmlp3_fold_f32", part_val.data_ptr(), part_idx.data_ptr(), B, ntiles, C3,
                       1 if relu_last else 0, pooled.data_ptr(), argidx.data_ptr(), 1, _stream())
@@ -572,16 +603,23 @@ def pointmlp3_max_fwd_raw(x, weights, relu_last, T=None, x_cf=True, fold=True, w
 
 
 def pointmlp3_max_bwd_raw(x, weights, argidx, g_pooled, masks, T=None, x_cf=True, out=None, accumulate=False,
-                          want_gT=False, twolist=False, tile32=None, stop_after=0):
+                          want_gT=False, twolist=False, tile32=None, stop_after=0, lengths=None):
     """Gradient w.r.t. the tower input (T None) or w.r.t. the raw points through x' = x @ T (T given); same layout
     as x. masks: the (mask1, mask2) pair of the forward launch on the same x/T (want_masks=True).
     want_gT: also return the per-tile partials [B, ntiles, 16] of dL/dT. out/accumulate: add into `out`.
     twolist: run the earlier two-list kernel (same bits; parity tests and tools/bench_pointmlp.py only).
     tile32: None — the entry's default form; True / False — the tile32 / the packed form of the balanced kernel by name (same
-    bits; parity test and bench tool only). stop_after 1..5 (tile32=False): end the packed launch after that phase."""
+    bits; parity test and bench tool only). stop_after 1..5 (tile32=False): end the packed launch after that phase.
+    lengths: None, or the int32 [B] device tensor the forward launch was given (pc3d_pointmlp3_max_bwd_ragged_f32: rows
+    behind a length are not read, their gradient is written 0 — left untouched under accumulate — and their partials of
+    dL/dT are zero). The packed form only: twolist, tile32=True and stop_after with lengths raise ValueError."""
     if want_gT and T is None:       # the kernels write the partials only with T: the tensor would go back unwritten
         raise ValueError("pointmlp3_max_bwd_raw: T and part_gT go together (want_gT needs T)")
+    if lengths is not None and (twolist or tile32 is True or stop_after):
+        raise ValueError("pointmlp3_max_bwd_raw: lengths go with the packed form only (no twolist, tile32=True or stop_after)")
     xp, xbs, xps, xcs, B, N = _pts(x, x_cf, "x")
+    if lengths is not None:
+        _lengths_arg("pointmlp3_max_bwd_raw", lengths, B, x.device)
     W1, b1, W2, b2, W3, b3 = weights[:6]
     W2T = weights[6] if len(weights) > 6 else W2.t().contiguous()
     C1, C2, C3 = W1.shape[0], W2.shape[0], W3.shape[0]
@@ -603,12 +641,15 @@ def pointmlp3_max_bwd_raw(x, weights, argidx, g_pooled, masks, T=None, x_cf=True
             raise ValueError("pointmlp3_max_bwd_raw: twolist and tile32 name different kernels")
         if stop_after and tile32 is not False:
             raise ValueError("pointmlp3_max_bwd_raw: stop_after belongs to the packed form (tile32=False)")
-        _lib.call("pc3d_pointmlp3_max_bwd_f32",
-                  xp, xbs, xps, xcs, B, N, _ptr(T),
-                  W1.data_ptr(), b1.data_ptr(), W2.data_ptr(), b2.data_ptr(), W3.data_ptr(), W2T.data_ptr(),
-                  C1, C2, C3, argidx.data_ptr(), m1.data_ptr(), m2.data_ptr(), g_pooled.data_ptr(), gp, gbs, gps, gcs,
-                  _ptr(part_gT),
-                  1 if accumulate else 0, _pm_bwd_form(twolist, tile32), int(stop_after), _stream())
+        args = (xp, xbs, xps, xcs, B, N, _ptr(T),
+                W1.data_ptr(), b1.data_ptr(), W2.data_ptr(), b2.data_ptr(), W3.data_ptr(), W2T.data_ptr(),
+                C1, C2, C3, argidx.data_ptr(), m1.data_ptr(), m2.data_ptr(), g_pooled.data_ptr(), gp, gbs, gps, gcs,
+                _ptr(part_gT),
+                1 if accumulate else 0, _pm_bwd_form(twolist, tile32), int(stop_after))
+        if lengths is not None:
+            _lib.call("pc3d_pointmlp3_max_bwd_ragged_f32", *args, lengths.data_ptr(), _stream())
+        else:
+            _lib.call("pc3d_pointmlp3_max_bwd_f32", *args, _stream())
     return (gx, part_gT) if want_gT else gx
 
 

@@ -455,6 +455,41 @@ int pc3d_pointmlp3_max_bwd_f32(const float* x, int64_t x_bs, int64_t x_ps, int64
                                float* grad_x, int64_t gx_bs, int64_t gx_ps, int64_t gx_cs,
                                float* part_gT, int accumulate, int form, int stop_after, void* stream);
 
+/* The two launches above with per-cloud lengths: lengths [B] i32 in device memory, read as data by the kernels (a
+ * captured launch serves any lengths written into that buffer later). Cloud b has L = clamp(lengths[b], 1, N) points;
+ * N stays the buffers' row count: it is used for every stride, for the tile count and for the workspaces' shapes, and
+ * every other argument is the dense entry's.
+ * The contract: a launch given lengths reads no row n >= L of x, and on the rows below L (and in pooled, argidx, T_out,
+ * part_gT's sum) it writes the bits the dense launch writes for that cloud, whether the dense launch is given the L rows
+ * alone or the N rows padded with copies of point 0.
+ * Forward: rows in [L, N) of mask1 / mask2 are written as zero words. A 128-point tile that lies wholly at or beyond L
+ * is skipped: its workgroup leaves ahead of its first barrier and writes only part_val = -inf, part_idx = 0 for its C3
+ * entries (the folds' strict `>` never takes them; tile 0 is never skipped and keeps the T_out store) and those zero mask
+ * words. form is PC3D_PM_FWD_EXACT or PC3D_PM_FWD_SCREEN_H_PAIR (the production form; all five image pointers are then
+ * needed), the other forms have no ragged twin; stats, dbg_S and dbg_E must be NULL and stop_after 0. While the ragged
+ * H_PAIR instantiation's first use on a device falls into a stream capture, the launch runs the ragged exact kernel.
+ * Backward: form is PC3D_PM_BWD_DEFAULT or PC3D_PM_BWD_PACKED (the packed kernel's ragged twin), stop_after 0. x,
+ * mask1 and mask2 are read below L only and a route (argidx) at or beyond L is dropped; grad_x rows in [L, N) are written
+ * 0 (accumulate != 0: left untouched) and part_gT's records of the 32-point sub-tiles at and beyond L are zero. A
+ * workgroup whose 128 points lie at or beyond L writes those zeros and scans nothing.
+ * lengths == NULL, another form, a debug argument: PC3D_EINVAL before any HIP call. B == 0 is a no-op. */
+int pc3d_pointmlp3_max_fwd_ragged_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                      const float* T, const float* th_in, const float* th_W, const float* th_b, int th_K,
+                                      float* T_out, const float* W1, const float* b1, const float* W2, const float* b2,
+                                      const float* W3, const float* b3, int C1, int C2, int C3, int relu_last,
+                                      float* part_val, int32_t* part_idx, float* pooled, int32_t* argidx, uint64_t* mask1,
+                                      uint32_t* mask2, int form, const void* w3_bf, const float* w3_nw, const float* w3_q,
+                                      const void* w3_h, const float* w3_cw, int32_t* stats, float* dbg_S, float* dbg_E,
+                                      int stop_after, const int32_t* lengths, void* stream);
+int pc3d_pointmlp3_max_bwd_ragged_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, int B, int N,
+                                      const float* T, const float* W1, const float* b1, const float* W2,
+                                      const float* b2, const float* W3, const float* W2T, int C1, int C2, int C3,
+                                      const int32_t* argidx, const uint64_t* mask1, const uint32_t* mask2,
+                                      const float* g_pooled,
+                                      float* grad_x, int64_t gx_bs, int64_t gx_ps, int64_t gx_cs,
+                                      float* part_gT, int accumulate, int form, int stop_after, const int32_t* lengths,
+                                      void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------
  * PointNet with the feature transform (model/pointnet.py:51-87 STNkd, :101-117), eval mode, BatchNorm folded:
  *   x' = x @ T,  h = relu(W1 x' + b1),  Tf = I + head(max_n tower_{64->64->128->1024}(h)),

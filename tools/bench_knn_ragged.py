@@ -6,8 +6,12 @@ UntargetedLogitsAdvLoss(15), ChamferkNNDist(), ProjectInnerClipLinf(0.18).
                    (attack(data, target, lengths)), `dense` (32 clouds of K = 1024 points, the yardstick) and `alone_sum` (the
                    same 32 clouds as 32 attacks at B = 1, each at its own size: the sum of their iterations, what a user does
                    without lengths). The candidates are timed alternately, `--repeats` windows each; median, min, max, spread.
-  victim_us        fused_attack_grad alone on the ragged loop's padded buffers and on the dense loop's: what the padded DATA
-                   costs the victim's data-dependent tower forward, apart from the two new kernels
+  victim_us        fused_attack_grad alone on the ragged loop's padded buffers (`padded_data`: without lengths; `lengths`:
+                   given them) and on the dense loop's: what the padded DATA costs the victim's
+                   data-dependent tower forward, apart from the two new kernels
+  --towers         iter_us `ragged` and `dense` and victim_us only (no runs alone, no search / update rows): the measurement
+                   of §8.19, taken on this tree and on its parent in alternated processes (a tree whose victim takes no
+                   lengths has no `lengths` candidate)
   search_us        the self-kNN search alone: pc3d_knn_ragged_f32 on the padded batch, the same kernel with all lengths = Kmax
                    on the dense clouds, and its dense twin pc3d_knn_hint_f32 on the dense clouds (all hinted by their own result)
   update_us        the update launch alone, likewise
@@ -79,6 +83,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "knn_ragged_bench.json"))
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--towers", action="store_true", help="the ragged and dense iteration and the victim alone, nothing else")
     a = ap.parse_args()
     B, K = 32, 1024
     rng = np.random.default_rng(2024)
@@ -99,17 +104,22 @@ def main():
 
     ragged = captured_loop(attacker(model, sample_seeds=list(range(B))), torch.from_numpy(data), labels, lens)
     full = captured_loop(attacker(model), dense, dense_labels)
-    alone = [captured_loop(attacker(model, sample_seeds=[b], global_batch=B), torch.from_numpy(c)[None], labels[b:b + 1])
-             for b, c in enumerate(clouds)]
-    v = {"ragged": [], "dense": [], "alone_sum": []}
+    alone = [] if a.towers else [
+        captured_loop(attacker(model, sample_seeds=[b], global_batch=B), torch.from_numpy(c)[None], labels[b:b + 1])
+        for b, c in enumerate(clouds)]
+    v = {"ragged": [], "dense": []}
+    if alone:
+        v["alone_sum"] = []
     for _ in range(a.repeats):
         v["ragged"].append(loop_us(ragged))
         v["dense"].append(loop_us(full))
-        v["alone_sum"].append(sum(loop_us(lp, 2) for lp in alone))
+        if alone:
+            v["alone_sum"].append(sum(loop_us(lp, 2) for lp in alone))
     it = {k: stats(t) for k, t in v.items()}
     it["ragged_minus_dense"] = round(it["ragged"]["median"] - it["dense"]["median"], 2)
     it["larger_spread"] = max(it["ragged"]["spread"], it["dense"]["spread"])
-    it["alone_over_ragged"] = round(it["alone_sum"]["median"] / it["ragged"]["median"], 2)
+    if alone:
+        it["alone_over_ragged"] = round(it["alone_sum"]["median"] / it["ragged"]["median"], 2)
     res["iter_us"] = it
     print(json.dumps(it), flush=True)
 
@@ -123,16 +133,21 @@ def main():
     gx = torch.randn(B, 3, K, device=dev) * 1e-3
     gx_r = ops.pad_ragged(gx.clone(), r["lens"])
 
-    def vpass(c):
+    def vpass(c, **kw):
         return lambda: plan["victim"].fused_attack_grad(c["adv"], c["target"], kind, kappa, pred_out=c["pred"], step=c["step"],
-                                                        scale=plan["scale"])
+                                                        scale=plan["scale"], **kw)
 
     def update(c, g, **kw):
         return lambda: ops.knn_attack_update(c["adv"], c["ori"], g, c["m"], c["v"], one, LR, c["knn_d"], c["knn_idx"],
                                              c["nn_idx"], alpha=plan["alpha"], budget=plan["budget"], clip_mode=plan["clip_mode"],
                                              normal=c["normal"], **kw)
     with torch.no_grad():
-        res["victim_us"] = alternate({"padded_data": vpass(r), "dense_data": vpass(d)}, a.repeats)
+        vp = {"padded_data": vpass(r), "dense_data": vpass(d)}
+        if getattr(plan["victim"], "fused_lengths", False):
+            vp["lengths"] = vpass(r, lengths=r["lens"])
+        res["victim_us"] = alternate(vp, a.repeats)
+        if a.towers:
+            return finish(res, a.out)
         res["search_us"] = alternate({
             "ragged": lambda: ops.knn_search_into(r["adv"], r["knn_d"], r["knn_idx"], lengths=r["lens"], lengths_host=r["lens_host"]),
             "ragged_kernel_full_lengths": lambda: ops.knn_search_into(d["adv"], d["knn_d"], d["knn_idx"], lengths=lens_full,
@@ -142,10 +157,14 @@ def main():
             "ragged": update(r, gx_r, c_chamfer=r["c_ch"], c_knn=r["c_knn"], lengths=r["lens"]),
             "ragged_kernel_full_lengths": update(d, gx, c_chamfer=c_ch_full, c_knn=c_knn_full, lengths=lens_full),
             "dense": update(d, gx, c_chamfer=plan["c_ch"], c_knn=plan["c_knn"])}, a.repeats)
+    finish(res, a.out)
+
+
+def finish(res, out):
     doc = json.dumps(res, indent=1)
     print(doc)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
         f.write(doc + "\n")
 
 

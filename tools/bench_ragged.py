@@ -12,10 +12,17 @@ ClipPointsLinf.
                    `--repeats` windows each; median, min, max, and the difference ragged - dense against the larger spread.
   update_us        the update launch alone, ragged against dense, on the same state
   pad_us           the padding launch alone
+  --towers         the measurement of the towers that take lengths and nothing else: cw_ms `ragged` and
+                   `dense_riders_off`, `tower_forwards_us` and `tower_backwards_us` — the victim's two tower forwards /
+                   backwards on the padded batch without lengths (`padded_data`), with them (`lengths`) and on the dense
+                   clouds (`dense_data`). Run from a checkout whose ops take no lengths (the parent of 8.19) it measures
+                   that tree: `ragged` is then the padded pass and there is no `lengths` candidate; the two trees are run
+                   alternated in pairs, a process each (profiles/ragged_tower_bench.json).
 Replayed timings start after >= 150 ms of the same work. Writes profiles/ragged_bench.json.
-Usage: python tools/bench_ragged.py [--out FILE] [--repeats N]"""
+Usage: python tools/bench_ragged.py [--out FILE] [--repeats N] [--towers]"""
 import argparse
 import importlib
+import inspect
 import json
 import os
 import statistics
@@ -56,6 +63,57 @@ def stats(t, nd=4):
                 spread=round(max(t) - min(t), nd))
 
 
+def tower_rows(model, xp, xd, lengths, repeats):
+    """The victim's two tower forwards and its two tower backwards alone, in us: on the padded batch without lengths, with
+    them (where ops takes them) and on the dense clouds."""
+    pk = M("3dpointcloudattack_amd.model.pointnet").fused_pack(model)
+    have_lengths = "lengths" in inspect.signature(ops.pointmlp3_max_fwd_raw).parameters
+    lens = torch.from_numpy(np.asarray(lengths, dtype=np.int32)).to(dev)
+    B = xp.shape[0]
+    g_c, g_s = torch.randn(B, 1024, device=dev), torch.randn(B, 1024, device=dev)
+
+    def forwards(x, **kw):
+        s = ops.pointmlp3_max_fwd_raw(x, pk["tower_s"], True, want_masks=True, **kw)
+        c = ops.pointmlp3_max_fwd_raw(x, pk["tower_c"], False, want_masks=True, **kw)
+        return s, c
+
+    def backwards(x, state, **kw):
+        (_, idx_s, masks_s), (_, idx, masks), T, gx = state
+        ops.pointmlp3_max_bwd_raw(x, pk["tower_c"], idx, g_c, masks, T=T, want_gT=True, out=gx, **kw)
+        ops.pointmlp3_max_bwd_raw(x, pk["tower_s"], idx_s, g_s, masks_s, out=gx, accumulate=True, **kw)
+
+    cands = {"padded_data": (xp, {}), "dense_data": (xd, {})}
+    if have_lengths:
+        cands["lengths"] = (xp, dict(lengths=lens))
+    T = torch.eye(3, device=dev).repeat(B, 1, 1) + 0.1 * torch.randn(B, 3, 3, device=dev)
+    fwd, bwd = {}, {}
+    for name, (x, kw) in cands.items():
+        state = forwards(x, **kw) + (T, torch.empty_like(x))
+        fwd[name] = lambda x=x, kw=kw: forwards(x, **kw)
+        bwd[name] = lambda x=x, kw=kw, state=state: backwards(x, state, **kw)
+    return dict(tower_forwards_us=alternate(fwd, repeats), tower_backwards_us=alternate(bwd, repeats))
+
+
+def towers_only(B, K, lengths, clouds, repeats):
+    """--towers: the ragged and the dense CW iteration and the towers alone."""
+    model, trans = victim(0), victim(1)
+    data, lens = cloud_io.stack_ragged(clouds)
+    dense = torch.from_numpy(np.stack([unit_cloud(np.random.default_rng(100 + b), K) for b in range(B)]))
+    with torch.no_grad():
+        labels = model(torch.from_numpy(data).transpose(1, 2).contiguous().to(dev))[0].argmax(1).cpu()
+        dense_labels = model(dense.transpose(1, 2).contiguous().to(dev))[0].argmax(1).cpu()
+    runs = {"ragged": runner(attacker(model, trans, sample_seeds=list(range(B))), torch.from_numpy(data), labels, lens)[0],
+            "dense_riders_off": runner(attacker(model, trans, riders=False), dense, dense_labels)[0]}
+    v = {k: [] for k in runs}
+    for _ in range(repeats):
+        for k, r in runs.items():
+            v[k].append(cw_ms(r))
+    out = dict(cw_ms={k: stats(t) for k, t in v.items()})
+    xp, xd = torch.from_numpy(data).transpose(1, 2).contiguous().to(dev), dense.transpose(1, 2).contiguous().to(dev)
+    out.update(tower_rows(model, xp, xd, lengths, repeats))
+    return out
+
+
 def cw_rows(B, K, lengths, clouds, repeats):
     model, trans = victim(0), victim(1)
     data, lens = cloud_io.stack_ragged(clouds)
@@ -82,13 +140,9 @@ def cw_rows(B, K, lengths, clouds, repeats):
     out["points_counted_share"] = round(float(np.sum(lengths)) / (B * K), 3)
     # the victim's tower forward is data dependent (candidates of the screened max: every exact tie is rechecked, and a tile of
     # copies is nothing but ties): the two towers of the plain victim on the padded and on the dense clouds
-    pk = M("3dpointcloudattack_amd.model.pointnet").fused_pack(model)
     xp, xd = torch.from_numpy(data).transpose(1, 2).contiguous().to(dev), dense.transpose(1, 2).contiguous().to(dev)
 
-    def towers(x):
-        ops.pointmlp3_max_fwd_raw(x, pk["tower_s"], True, want_masks=True)
-        ops.pointmlp3_max_fwd_raw(x, pk["tower_c"], False, want_masks=True)
-    out["tower_forwards_us"] = alternate({"padded_data": lambda: towers(xp), "dense_data": lambda: towers(xd)}, repeats)
+    out.update(tower_rows(model, xp, xd, lengths, repeats))
     return out
 
 
@@ -127,6 +181,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ragged_bench.json"))
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--towers", action="store_true", help="the ragged and dense iteration and the towers alone, nothing else")
     a = ap.parse_args()
     B, K = 32, 1024
     rng = np.random.default_rng(2024)
@@ -135,9 +190,12 @@ def main():
     res = {"what": "tools/bench_ragged.py on one MI355X, one process; replayed hipGraphs after 150 ms of the same work, candidates "
                    f"timed alternately, {a.repeats} windows each (median, min, max; spread = max - min)",
            "device": torch.cuda.get_device_name(0), "B": B, "Kmax": K, "lengths": [int(n) for n in lengths]}
-    res.update(launch_rows(B, K, lengths, a.repeats))
-    print(json.dumps({k: res[k] for k in ("update_us", "pad_us")}), flush=True)
-    res["cw_ms"] = cw_rows(B, K, lengths, clouds, a.repeats)
+    if a.towers:
+        res.update(towers_only(B, K, lengths, clouds, a.repeats))
+    else:
+        res.update(launch_rows(B, K, lengths, a.repeats))
+        print(json.dumps({k: res[k] for k in ("update_us", "pad_us")}), flush=True)
+        res["cw_ms"] = cw_rows(B, K, lengths, clouds, a.repeats)
     doc = json.dumps(res, indent=1)
     print(doc)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

@@ -6,7 +6,8 @@ flags (nn.hip with its EXTRA). Needs hipcc, no GPU.
     tools/isa_resources.py PARENT_CSRC NEW_CSRC [-j JOBS] > profiles/<name>_isa.txt
 
 Lists every kernel whose figures differ, then the full table. Exit status 1 if a kernel gained scratch, lost occupancy
-or changed its LDS.
+or changed its LDS. A kernel that gained a trailing template parameter whose value is `false` (a dense instantiation
+beside a new twin, as profiles/ragged_tower_isa.txt) is listed under its new name against the parent's figures.
 """
 import argparse
 import concurrent.futures
@@ -60,6 +61,14 @@ def demangled(names):
     return dict(zip(names, short))
 
 
+def parent_name(name, old):
+    """The parent's name of the new kernel `name`: itself, or `name` without a trailing template argument `false`."""
+    for cand in (name, re.sub(r"<false>$", "", name), re.sub(r", false>$", ">", name)):
+        if cand in old:
+            return cand
+    return None
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("parent")
@@ -73,8 +82,15 @@ def main():
     rows, bad = [], []
     for f in files:
         short = demangled(sorted(set(old[f]) | set(new[f])))
+        old_short = {short[n]: k for n, k in old[f].items()}
+        twins = {parent_name(short[n], old_short) for n in new[f]}
         for n, s in short.items():
-            o, w = old[f].get(n), new[f].get(n)
+            if n in new[f]:
+                o, w = old_short.get(parent_name(s, old_short)), new[f][n]
+            elif s in twins:
+                continue            # listed under its new name
+            else:
+                o, w = old[f][n], None
             rows.append((f, s, o, w))
             if o and w and (w["scratch"] > o["scratch"] or w["occ"] < o["occ"] or w["lds"] != o["lds"]):
                 bad.append((f, s))
