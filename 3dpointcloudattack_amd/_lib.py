@@ -165,7 +165,7 @@ SIGNATURES = {
     "pc3d_pointmlp3_w3_prepare_f32": [_P, _I, _P, _P, _P, _P],
     "pc3d_pointmlp3_w3_prepare_h_f32": [_P, _I, _P, _P, _P, _P],
     "pc3d_pointmlp3_pair_recheck_ready": [],
-    "pc3d_linear_pre_f32": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P],
+    "pc3d_linear_pre_f32": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P],
     "pc3d_pointmlp3_max_bwd_f32": _PTS + [_I, _I] + [_P] * 7 + [_I, _I, _I] + [_P, _P, _P, _P] + _PTS
     + [_P, _I, _I, _I, _P],
     "pc3d_pointmlp3_max_fwd_ragged_f32": _PTS + [_I, _I] + [_P, _P, _P, _P, _I, _P] + [_P] * 6 + [_I, _I, _I, _I]
@@ -178,11 +178,12 @@ SIGNATURES = {
     "pc3d_pointnet_ft_tower_bwd_f32": _PTS + [_I, _I] + [_P] * 4 + [_L] + [_P, _P, _I] + [_P] * 5 + _PTS
     + [_P, _I, _I, _P, _I, _P],
     "pc3d_pointnet_ft_dtf_f32": _PTS + [_I, _I] + [_P] * 5 + [_P],
-    "pc3d_linear_f32": [_P, _I, _I, _I, _I, _P, _P, _I, _I, _F, _P, _I, _F, _P, _I, _P],
+    "pc3d_linear_tile": [_I, _I, _I],
+    "pc3d_linear_f32": [_P, _I, _I, _I, _I, _P, _P, _I, _I, _F, _P, _I, _F, _P, _I, _I, _P],
     "pc3d_linear_nn_f32": [_P, _I, _I, _I, _I, _P, _P, _I, _I, _F, _P, _I, _F, _P, _I] + _PTS + _PTS
-    + [_I, _I, _I, _P, _P, _I, _P],
+    + [_I, _I, _I, _P, _P, _I, _I, _P],
     "pc3d_linear_book_f32": [_P, _I, _I, _I, _I, _P, _P, _I, _I, _F, _P, _I, _F, _P, _I] + _PTS + _PTS
-    + [_I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P] + [_D, _D, _D, _P, _P, _I, _P],
+    + [_I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P] + [_D, _D, _D, _P, _P, _I, _I, _P],
     "pc3d_pointmlp3_max_bwd_update_f32": _PTS + [_I, _I] + [_P] * 6 + [_I, _I, _I] + [_P, _P, _P, _P] + _PTS + _PTS
     + [_P, _P, _D, _D, _D, _F, _P, _I, _P, _P, _P, _I, _P],
     "pc3d_cls_loss_f32": [_P, _I, _I, _I, _P, _I, _F, _F, _P, _P, _P, _P, _P],

@@ -116,10 +116,11 @@ __global__ __launch_bounds__(LN_T) void linear_kernel(LinArgs a) {
   }
 }
 
-// 32 rows x 16 outputs per workgroup on v_mfma_f32_16x16x4_f32 (linear16_body.h)
-__global__ __launch_bounds__(LN_T) void linear16_kernel(LinArgs a) { linear16_body(a, blockIdx.x, blockIdx.y); }
+// TR rows x TC outputs per workgroup on v_mfma_f32_16x16x4_f32 (linear16_body.h)
+template <int TR, int TC>
+__global__ __launch_bounds__(LN_T) void linear16_kernel(LinArgs a) { linear16_body<TR, TC>(a, blockIdx.x, blockIdx.y); }
 
-// The same 32 x 16 tiling with the X operand produced on the fly by a tiny PRE-layer:
+// The same tiling with the X operand produced on the fly by a tiny PRE-layer:
 //     X[b,k] = gate_pre[b,k] > 0 ? sum_{j<J} S[b,j] Wp[j,k] : 0,      S[b,j] = sum_p parts[b,p,j]
 // — the backward of STN3d's fc3 (9 -> 256, model/pointnet.py:45) folded into the launch of fc2's backward
 // (256 -> 512): `parts` are the per-tile dL/dT partials of the trunk's backward, Wp = fc3's weight [9,256], gate_pre
@@ -138,7 +139,12 @@ struct LinPreArgs {
   int B, K, O;
 };
 
-__global__ __launch_bounds__(LN_T) void linear16_pre_kernel(LinPreArgs a) {
+// (the primary template: the forms with one row tile, defined below; the 32 x 16 statements are its specialisation)
+template <int TR, int TC>
+__global__ __launch_bounds__(LN_T) void linear16_pre_kernel(LinPreArgs a);
+
+template <>
+__global__ __launch_bounds__(LN_T) void linear16_pre_kernel<32, 16>(LinPreArgs a) {
   __shared__ float red[LN_W][32][17];
   __shared__ float S[32][16];
   const int o0 = blockIdx.x * 16, b0 = blockIdx.y * 32;
@@ -201,6 +207,79 @@ __global__ __launch_bounds__(LN_T) void linear16_pre_kernel(LinPreArgs a) {
   __syncthreads();
   {
     const int row = threadIdx.x >> 4, col = threadIdx.x & 15;
+    float sum = red[0][row][col];
+#pragma unroll
+    for (int w = 1; w < LN_W; ++w) sum += red[w][row][col];
+    const int b = b0 + row, o = o0 + col;
+    if (b < a.B && o < a.O) {
+      if (a.gate && !(a.gate[(int64_t)b * a.ldg + o] > 0.f)) sum = 0.f;
+      a.Y[(int64_t)b * a.ldy + o] = sum;
+    }
+  }
+}
+
+// TR <= 16 rows x TC <= 16 outputs (linear16_body_small's tiling): the S slab and the on-the-fly X follow the row
+// tile; lanes outside the tile load neither gate_pre nor W and feed 0.0f. The same FMA chain per X element, the same
+// chunk -> wave assignment and epilogue order: the bits of the 32 x 16 form.
+template <int TR, int TC>
+__global__ __launch_bounds__(LN_T) void linear16_pre_kernel(LinPreArgs a) {
+  static_assert((TR == 16 || TR == 8) && (TC == 16 || TC == 8), "tile forms: 16 x 16, 16 x 8, 8 x 8");
+  __shared__ float red[LN_W][TR][TC + 1];
+  __shared__ float S[TR][16];
+  const int o0 = blockIdx.x * TC, b0 = blockIdx.y * TR;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = lane & 15, q = lane >> 4;
+  if (threadIdx.x < TR * 16) {   // S: TR rows x 16 columns, one element per thread, slabs summed in ascending order
+    const int row = threadIdx.x >> 4, j = threadIdx.x & 15;
+    const int bb = (b0 + row < a.B) ? b0 + row : a.B - 1;
+    float sacc = 0.f;
+    if (j < a.J) {
+      const float* pp = a.parts + (int64_t)bb * a.P * a.Jp + j;
+      int p = 0;
+      for (; p + 8 <= a.P; p += 8) {       // eight slabs in flight; summed in ascending order
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = pp[(int64_t)(p + u) * a.Jp];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) sacc += v[u];
+      }
+      for (; p < a.P; ++p) sacc += pp[(int64_t)p * a.Jp];
+    }
+    S[row][j] = sacc;
+  }
+  __syncthreads();
+  const bool xin = r < TR, win = r < TC;
+  const int xb = (b0 + r < a.B) ? b0 + r : a.B - 1;
+  const int wo = (o0 + r < a.O) ? o0 + r : a.O - 1;
+  const float* wr = a.W + (int64_t)wo * a.K + 4 * q;
+  const int nchunk = a.K / 16;
+  using f32x4 = __attribute__((ext_vector_type(4))) float;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  for (int c = wave; c < nchunk; c += LN_W) {
+    const int k0 = 16 * c + 4 * q;
+    float x[4] = {0.f, 0.f, 0.f, 0.f};
+    float4 g = make_float4(0.f, 0.f, 0.f, 0.f), wv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (xin) {
+      for (int j = 0; j < a.J; ++j) {
+        const float4 wp = *reinterpret_cast<const float4*>(a.Wp + (int64_t)j * a.K + k0);
+        const float s = S[r][j];
+        x[0] = __builtin_fmaf(s, wp.x, x[0]), x[1] = __builtin_fmaf(s, wp.y, x[1]);
+        x[2] = __builtin_fmaf(s, wp.z, x[2]), x[3] = __builtin_fmaf(s, wp.w, x[3]);
+      }
+      g = *reinterpret_cast<const float4*>(a.gate_pre + (int64_t)xb * a.ldgp + k0);
+    }
+    if (win) wv = *reinterpret_cast<const float4*>(wr + 16 * c);
+    const float ge[4] = {g.x, g.y, g.z, g.w}, we[4] = {wv.x, wv.y, wv.z, wv.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ge[e] > 0.f ? x[e] : 0.f, we[e], acc, 0, 0, 0);
+  }
+  if (win && 4 * q < TR) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) red[wave][4 * q + e][r] = acc[e];
+  }
+  __syncthreads();
+  if (threadIdx.x < TR * TC) {
+    const int row = threadIdx.x / TC, col = threadIdx.x % TC;
     float sum = red[0][row][col];
 #pragma unroll
     for (int w = 1; w < LN_W; ++w) sum += red[w][row][col];
@@ -497,21 +576,27 @@ extern "C" int pc3d_cls_tail_serial_f32(const float* c2, int B, int K2, const fl
 
 extern "C" int pc3d_linear_f32(const float* X, int ldx, int P, int B, int K, const float* W, const float* bias,
                                int O, int relu, float slope, const float* gate, int ldg, float gate_slope, float* Y, int ldy,
-                               void* stream) {
+                               int tile, void* stream) {
   PC3D_REQUIRE(B >= 0 && K >= 1 && O >= 1 && P >= 1, "pc3d_linear_f32: bad sizes B=%d K=%d O=%d P=%d", B, K, O, P);
   PC3D_REQUIRE(ldx >= P * K && ldy >= O, "pc3d_linear_f32: leading dimensions too small (ldx=%d ldy=%d)", ldx, ldy);
   PC3D_REQUIRE((K % 8 != 0) || (ldx % 4 == 0), "pc3d_linear_f32: ldx=%d must be a multiple of 4 for 16-byte loads", ldx);
+  PC3D_REQUIRE(tile >= 0 && tile <= kLinTileForms, "pc3d_linear_f32: tile=%d names no form (0 = the rule, 1..%d)", tile,
+               kLinTileForms);
   if (B == 0) return PC3D_OK;
   PC3D_REQUIRE(X && W && Y, "pc3d_linear_f32: null pointer");
   PC3D_REQUIRE(gate == nullptr || ldg >= O, "pc3d_linear_f32: ldg=%d too small", ldg);
   LinArgs a{X, ldx, P, W, bias, gate, ldg, Y, ldy, B, K, O, relu, slope, gate_slope};
-  if (linear16_applies(K, P, O))
-    hipLaunchKernelGGL(linear16_kernel, dim3(cdiv(O, 16), cdiv(B, 32)), dim3(LN_T), 0, as_stream(stream), a);
-  else
+  if (linear16_applies(K, P, O)) {   // (a forced tile on a shape outside the tiling is ignored: linear_kernel has one form)
+    PC3D_LIN_TILE_SWITCH(linear_tile_pick(tile, B, K, O),
+                         hipLaunchKernelGGL((linear16_kernel<TR, TC>), dim3(cdiv(O, TC), cdiv(B, TR)), dim3(LN_T), 0,
+                                            as_stream(stream), a));
+  } else
     hipLaunchKernelGGL(linear_kernel, dim3(cdiv(O, 32), cdiv(B, 32)), dim3(LN_T), 0, as_stream(stream), a);
   PC3D_LAUNCH_CHECK("pc3d_linear_f32");
   return PC3D_OK;
 }
+
+extern "C" int pc3d_linear_tile(int B, int K, int O) { return linear_tile_rule(B, K, O); }
 
 extern "C" int pc3d_cls_loss_f32(const float* logits, int ld, int B, int ncls, const int64_t* target, int kind,
                                  float kappa, float scale, float* logp, int64_t* pred, float* loss,
@@ -528,14 +613,18 @@ extern "C" int pc3d_cls_loss_f32(const float* logits, int ld, int B, int ncls, c
 
 extern "C" int pc3d_linear_pre_f32(const float* parts, int P, int Jp, int J, const float* Wp, const float* gate_pre,
                                    int ldgp, int B, int K, const float* W, int O, const float* gate, int ldg, float* Y,
-                                   int ldy, void* stream) {
+                                   int ldy, int tile, void* stream) {
   PC3D_REQUIRE(B >= 0 && P >= 1 && J >= 1 && J <= 16 && Jp >= J && K >= 16 && K % 16 == 0 && O >= 1,
                "pc3d_linear_pre_f32: bad sizes B=%d P=%d J=%d Jp=%d K=%d O=%d (J <= 16, K %% 16 == 0)", B, P, J, Jp, K, O);
+  PC3D_REQUIRE(tile >= 0 && tile <= kLinTileForms, "pc3d_linear_pre_f32: tile=%d names no form (0 = the rule, 1..%d)", tile,
+               kLinTileForms);
   if (B == 0) return PC3D_OK;
   PC3D_REQUIRE(parts && Wp && gate_pre && W && Y && ldgp >= K && ldy >= O && (!gate || ldg >= O),
                "pc3d_linear_pre_f32: null pointer or row stride smaller than the row");
   LinPreArgs a{parts, P, Jp, J, Wp, gate_pre, ldgp, W, gate, ldg, Y, ldy, B, K, O};
-  hipLaunchKernelGGL(linear16_pre_kernel, dim3(cdiv(O, 16), cdiv(B, 32)), dim3(LN_T), 0, as_stream(stream), a);
+  PC3D_LIN_TILE_SWITCH(linear_tile_pick(tile, B, K, O),
+                       hipLaunchKernelGGL((linear16_pre_kernel<TR, TC>), dim3(cdiv(O, TC), cdiv(B, TR)), dim3(LN_T), 0,
+                                          as_stream(stream), a));
   PC3D_LAUNCH_CHECK("pc3d_linear_pre_f32");
   return PC3D_OK;
 }

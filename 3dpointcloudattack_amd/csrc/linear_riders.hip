@@ -13,13 +13,14 @@
 
 namespace pc3d {
 
+template <int TR, int TC>
 __global__ __launch_bounds__(LN_T) void linear16_nn_kernel(LinArgs a, int lin_gx, int lin_wgs, NNDir D, int mt_cap,
                                                            int nn_gx, int nn_total) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int wg = blockIdx.x;
   if (wg < lin_wgs) {
     const int by = wg / lin_gx;
-    linear16_body(a, wg - by * lin_gx, by);
+    linear16_body<TR, TC>(a, wg - by * lin_gx, by);
     return;
   }
   // a cloud's search workgroups on one XCD (ids are dealt round-robin to the XCDs: a constant offset keeps the bands)
@@ -30,6 +31,7 @@ __global__ __launch_bounds__(LN_T) void linear16_nn_kernel(LinArgs a, int lin_gx
 }
 
 // Reference points up to which the search rides: the staged tile (12 B per point) + the merge area + the layer's 17 KB
+// (the 32 x 16 form's `red`; 8.5 / 4.5 / 2.25 KB for 16 x 16 / 16 x 8 / 8 x 8, so the smaller tiles only add room)
 // stay under 64 KB per workgroup, so two workgroups share a CU as the stand-alone layer's do. Larger clouds (one tile up
 // to kNNMaxTile = 4096 points) keep the search's own launch.
 constexpr int kRiderMaxRef = 2048;
@@ -41,12 +43,13 @@ struct BookRiderArgs {
   float* adam;     // [2] out: {step_size, bc2s} of the step word's value, or null
 };
 
+template <int TR, int TC>
 __global__ __launch_bounds__(LN_T) void linear16_book_kernel(LinArgs a, int lin_gx, int lin_wgs, BookRiderArgs r) {
   static_assert(kCwBookThreads == LN_T, "the bookkeeping rider is written for the linear launch's workgroup size");
   const int wg = blockIdx.x;
   if (wg < lin_wgs) {
     const int by = wg / lin_gx;
-    linear16_body(a, wg - by * lin_gx, by);
+    linear16_body<TR, TC>(a, wg - by * lin_gx, by);
     return;
   }
   cw_book_body(r.bk, wg - lin_wgs, r.lr, r.b1, r.b2, r.step_dev, r.adam);
@@ -65,15 +68,17 @@ extern "C" int pc3d_linear_nn_f32(const float* X, int ldx, int P, int B, int K, 
                                   int relu, float slope, const float* gate, int ldg, float gate_slope, float* Y, int ldy,
                                   const float* q, int64_t q_bs, int64_t q_ps, int64_t q_cs,
                                   const float* r, int64_t r_bs, int64_t r_ps, int64_t r_cs,
-                                  int NB, int N, int M, float* min_d2, int32_t* idx, int ride, void* stream) {
+                                  int NB, int N, int M, float* min_d2, int32_t* idx, int ride, int tile, void* stream) {
   // the search's own checks (as pc3d_nn_f32); the linear's are made by pc3d_linear_f32 below or repeated here
   PC3D_REQUIRE(NB >= 0 && N >= 0 && M >= 1, "pc3d_linear_nn_f32: bad sizes NB=%d N=%d M=%d (M must be >= 1)", NB, N, M);
+  PC3D_REQUIRE(tile >= 0 && tile <= kLinTileForms, "pc3d_linear_nn_f32: tile=%d names no form (0 = the rule, 1..%d)", tile,
+               kLinTileForms);
   int Q = 0, waves = 0;
   if (NB > 0 && N > 0) nn_plan(N, M, NB, 1, &Q, &waves);
   const bool fits = ride && B > 0 && NB > 0 && N > 0 && K >= 1 && O >= 1 && P >= 1 && linear16_applies(K, P, O) &&
                     waves == 8 && M <= kRiderMaxRef;
   if (!fits) {   // outside the rider's range: the two existing launches
-    const int rc = pc3d_linear_f32(X, ldx, P, B, K, W, bias, O, relu, slope, gate, ldg, gate_slope, Y, ldy, stream);
+    const int rc = pc3d_linear_f32(X, ldx, P, B, K, W, bias, O, relu, slope, gate, ldg, gate_slope, Y, ldy, tile, stream);
     if (rc != PC3D_OK) return rc;
     return pc3d_nn_f32(q, q_bs, q_ps, q_cs, r, r_bs, r_ps, r_cs, NB, N, M, min_d2, idx, stream);
   }
@@ -86,10 +91,13 @@ extern "C" int pc3d_linear_nn_f32(const float* X, int ldx, int P, int B, int K, 
   const NNDir D{{q, q_bs, q_ps, q_cs}, {r, r_bs, r_ps, r_cs}, N, M, min_d2, idx};
   int mt_cap;
   const size_t lds = nn_lds_bytes(M, 1, 8, &mt_cap);
-  const int lin_gx = cdiv(O, 16), lin_wgs = lin_gx * cdiv(B, 32);
+  const int form = linear_tile_pick(tile, B, K, O);
+  int tr = 32, tc = 16;
+  linear_tile_dims(form, &tr, &tc);
+  const int lin_gx = cdiv(O, tc), lin_wgs = lin_gx * cdiv(B, tr);   // the layer's workgroups stay first in dispatch order
   const int nn_gx = cdiv(N, kWave), nn_total = nn_gx * NB;
-  hipLaunchKernelGGL(linear16_nn_kernel, dim3(lin_wgs + xcd_grid(nn_total)), dim3(LN_T), lds, as_stream(stream), a, lin_gx,
-                     lin_wgs, D, mt_cap, nn_gx, nn_total);
+  PC3D_LIN_TILE_SWITCH(form, hipLaunchKernelGGL((linear16_nn_kernel<TR, TC>), dim3(lin_wgs + xcd_grid(nn_total)), dim3(LN_T),
+                                                lds, as_stream(stream), a, lin_gx, lin_wgs, D, mt_cap, nn_gx, nn_total));
   PC3D_LAUNCH_CHECK("pc3d_linear_nn_f32");
   return PC3D_OK;
 }
@@ -102,9 +110,11 @@ extern "C" int pc3d_linear_book_f32(const float* X, int ldx, int P, int B, int K
                                     float* bestdist, int64_t* bestscore, float* o_bestdist, int64_t* o_bestscore,
                                     float* o_bestattack, float* input_val, float* dist_val,
                                     double lr, double beta1, double beta2, const int32_t* step_dev, float* adam,
-                                    int ride, void* stream) {
+                                    int ride, int tile, void* stream) {
   PC3D_REQUIRE(NB >= 0 && NK >= 1 && NK <= 8192, "pc3d_linear_book_f32: bad sizes NB=%d NK=%d (NK <= 8192)", NB, NK);
   PC3D_REQUIRE(adam == nullptr || step_dev != nullptr, "pc3d_linear_book_f32: the Adam factors need the device step word");
+  PC3D_REQUIRE(tile >= 0 && tile <= kLinTileForms, "pc3d_linear_book_f32: tile=%d names no form (0 = the rule, 1..%d)", tile,
+               kLinTileForms);
   PC3D_REQUIRE(NB == 0 || (adv && ori && pred && label && bestdist && bestscore && o_bestdist && o_bestscore && o_bestattack),
                "pc3d_linear_book_f32: null pointer");
   // o_bestattack / input_val share adv's layout (as pc3d_cw_update_f32)
@@ -114,7 +124,7 @@ extern "C" int pc3d_linear_book_f32(const float* X, int ldx, int P, int B, int K
                   lr, beta1, beta2, step_dev, adam};
   const bool fits = ride && B > 0 && NB > 0 && K >= 1 && O >= 1 && P >= 1 && linear16_applies(K, P, O);
   if (!fits) {
-    const int rc = pc3d_linear_f32(X, ldx, P, B, K, W, bias, O, relu, slope, gate, ldg, gate_slope, Y, ldy, stream);
+    const int rc = pc3d_linear_f32(X, ldx, P, B, K, W, bias, O, relu, slope, gate, ldg, gate_slope, Y, ldy, tile, stream);
     if (rc != PC3D_OK || NB == 0) return rc;
     hipLaunchKernelGGL(cw_book_kernel, dim3(NB), dim3(LN_T), 0, as_stream(stream), r);
     PC3D_LAUNCH_CHECK("pc3d_linear_book_f32/book");
@@ -125,8 +135,15 @@ extern "C" int pc3d_linear_book_f32(const float* X, int ldx, int P, int B, int K
   PC3D_REQUIRE(X && W && Y, "pc3d_linear_book_f32: null pointer");
   PC3D_REQUIRE(gate == nullptr || ldg >= O, "pc3d_linear_book_f32: ldg=%d too small", ldg);
   LinArgs a{X, ldx, P, W, bias, gate, ldg, Y, ldy, B, K, O, relu, slope, gate_slope};
-  const int lin_gx = cdiv(O, 16), lin_wgs = lin_gx * cdiv(B, 32);
-  hipLaunchKernelGGL(linear16_book_kernel, dim3(lin_wgs + NB), dim3(LN_T), 0, as_stream(stream), a, lin_gx, lin_wgs, r);
+  // tile 0 is 32 x 16 here, not the rule: this launch lasts as long as its bookkeeping workgroups, which start behind the
+  // layer's — at the step's shape (B = 32, 256 -> 512) no smaller tile measured faster and 8 x 8 (256 workgroups in front
+  // of the bookkeeping) measured 19 % slower (profiles/linear_tiles_bench.json)
+  const int form = tile == 0 ? 1 : tile;
+  int tr = 32, tc = 16;
+  linear_tile_dims(form, &tr, &tc);
+  const int lin_gx = cdiv(O, tc), lin_wgs = lin_gx * cdiv(B, tr);
+  PC3D_LIN_TILE_SWITCH(form, hipLaunchKernelGGL((linear16_book_kernel<TR, TC>), dim3(lin_wgs + NB), dim3(LN_T), 0,
+                                                as_stream(stream), a, lin_gx, lin_wgs, r));
   PC3D_LAUNCH_CHECK("pc3d_linear_book_f32");
   return PC3D_OK;
 }

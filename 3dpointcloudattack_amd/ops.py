@@ -1078,9 +1078,30 @@ def knn_outlier_loss(pc, k=5, alpha=1.05, cf=False, gvec=None):
 # ------------------------------------------------------------------------------------------------------
 # classifier heads
 # ------------------------------------------------------------------------------------------------------
-def linear(X, W, bias=None, relu=False, gate=None, parts=1, out=None, slope=0.0, gate_slope=0.0):
+LINEAR_TILES = {"32x16": 1, "16x16": 2, "16x8": 3, "8x8": 4}     # include/pc3d.h: PC3D_LIN_TILE_*
+
+
+def _linear_tile(who, tile):
+    """tile=None -> 0 (the entry's rule, pc3d_linear_tile); a form by name -> its number."""
+    if tile is None:
+        return 0
+    if tile not in LINEAR_TILES:
+        raise ValueError(f"{who}: tile must be None or one of {sorted(LINEAR_TILES)}, got {tile!r}")
+    return LINEAR_TILES[tile]
+
+
+def linear_tile(B, K, O):
+    """The tile form (a key of LINEAR_TILES) the small-batch linear entries take for a layer shape by themselves
+    (pc3d_linear_tile: a pure function of the three sizes)."""
+    n = _lib.load().pc3d_linear_tile(int(B), int(K), int(O))
+    return next(k for k, v in LINEAR_TILES.items() if v == n)
+
+
+def linear(X, W, bias=None, relu=False, gate=None, parts=1, out=None, slope=0.0, gate_slope=0.0, tile=None):
     """Y = epi(X @ W.T + bias). X [B,K] (or [B,parts,K] summed over parts), W [O,K] contiguous fp32. relu: (Leaky)ReLU
-    with `slope` in the epilogue; gate [B,O]: Y = gate > 0 ? Y : gate_slope * Y afterwards (a saved activation's mask)."""
+    with `slope` in the epilogue; gate [B,O]: Y = gate > 0 ? Y : gate_slope * Y afterwards (a saved activation's mask).
+    tile: a key of LINEAR_TILES forces that form of the small-batch kernel (the same bits; tests and the bench tool)."""
+    tile = _linear_tile("linear", tile)
     _check(X, "X")
     _check(W, "W")
     if parts == 1:
@@ -1100,13 +1121,15 @@ def linear(X, W, bias=None, relu=False, gate=None, parts=1, out=None, slope=0.0,
     with torch.cuda.device(X.device):
         _lib.call("pc3d_linear_f32", X.data_ptr(), ldx, parts, B, K, W.data_ptr(), _ptr(bias), O, 1 if relu else 0,
                   float(slope), _ptr(gate), gate.stride(0) if gate is not None else 0, float(gate_slope), Y.data_ptr(),
-                  Y.stride(0), _stream())
+                  Y.stride(0), tile, _stream())
     return Y
 
 
-def linear_pre(parts, J, Wp, gate_pre, W, gate=None):
+def linear_pre(parts, J, Wp, gate_pre, W, gate=None, tile=None):
     """Y = gate(X @ W.T) with X[b,k] = gate_pre[b,k] > 0 ? sum_{j<J} (sum_p parts[b,p,j]) Wp[j,k] : 0 in ONE launch
-    (pc3d_linear_pre_f32): parts [B,P,Jp] contiguous, Wp [J,K], gate_pre [B,K], W [O,K], gate [B,O] or None."""
+    (pc3d_linear_pre_f32): parts [B,P,Jp] contiguous, Wp [J,K], gate_pre [B,K], W [O,K], gate [B,O] or None.
+    tile: as linear's."""
+    tile = _linear_tile("linear_pre", tile)
     _check(parts, "parts"), _check(Wp, "Wp"), _check(gate_pre, "gate_pre"), _check(W, "W")
     B, P, Jp = parts.shape
     K, O = Wp.shape[1], W.shape[0]
@@ -1117,7 +1140,7 @@ def linear_pre(parts, J, Wp, gate_pre, W, gate=None):
     with torch.cuda.device(parts.device):
         _lib.call("pc3d_linear_pre_f32", parts.data_ptr(), P, Jp, int(J), Wp.data_ptr(), gate_pre.data_ptr(),
                   gate_pre.stride(0), B, K, W.data_ptr(), O, _ptr(gate), gate.stride(0) if gate is not None else 0,
-                  Y.data_ptr(), Y.stride(0), _stream())
+                  Y.data_ptr(), Y.stride(0), tile, _stream())
     return Y
 
 
@@ -1561,10 +1584,11 @@ def _linear_args(who, X, W, bias, relu, gate, out, slope, gate_slope):
 
 
 def linear_nn(X, W, bias=None, relu=False, gate=None, q=None, r=None, q_cf=False, r_cf=False, want_idx=True, ride=True,
-              out=None, slope=0.0, gate_slope=0.0):
+              out=None, slope=0.0, gate_slope=0.0, tile=None):
     """linear(X, W, ...) and nn_raw(q, r, ...) as ONE launch (pc3d_linear_nn_f32): the search's workgroups ride behind
     the layer's. Returns (Y, min_d2, idx), the same bits as the two calls. Shapes outside the rider's range, or
-    ride=False, run the two launches — the entry decides."""
+    ride=False, run the two launches — the entry decides. tile: as linear's."""
+    tile = _linear_tile("linear_nn", tile)
     args, Y = _linear_args("linear_nn", X, W, bias, relu, gate, out, slope, gate_slope)
     qp, qbs, qps, qcs, B, N = _pts(q, q_cf, "q")
     rp, rbs, rps, rcs, B2, M = _pts(r, r_cf, "r")
@@ -1576,16 +1600,18 @@ def linear_nn(X, W, bias=None, relu=False, gate=None, q=None, r=None, q_cf=False
     i = torch.empty((B, N), dtype=torch.int32, device=q.device) if want_idx else None
     with torch.cuda.device(X.device):
         _lib.call("pc3d_linear_nn_f32", *args, qp, qbs, qps, qcs, rp, rbs, rps, rcs, B, N, M, d.data_ptr(), _ptr(i),
-                  1 if ride else 0, _stream())
+                  1 if ride else 0, tile, _stream())
     return Y, d, i
 
 
 def linear_book(X, W, adv, ori, pred, label, untarget, bestdist, bestscore, o_bestdist, o_bestscore, o_bestattack,
                 bias=None, relu=False, gate=None, input_val=None, dist_val=None, step=None, lr=0.0, adam=None,
-                betas=(0.9, 0.999), cf=True, ride=True, out=None, slope=0.0, gate_slope=0.0):
+                betas=(0.9, 0.999), cf=True, ride=True, out=None, slope=0.0, gate_slope=0.0, tile=None):
     """linear(X, W, ...) and the bookkeeping half of cw_update (||adv-ori|| into dist_val, best-distance decisions, the
     input_val / o_bestattack copies; the same bits) as ONE launch (pc3d_linear_book_f32). adam: float32 [2] to receive
-    Adam's {step size, sqrt of the second bias correction} for the value of the device step word `step`. Returns Y."""
+    Adam's {step size, sqrt of the second bias correction} for the value of the device step word `step`. Returns Y.
+    tile: as linear's."""
+    tile = _linear_tile("linear_book", tile)
     args, Y = _linear_args("linear_book", X, W, bias, relu, gate, out, slope, gate_slope)
     _, _, _, _, B, K = _pts(adv, cf, "adv")
     if K > CW_UPDATE_MAX_POINTS:
@@ -1600,7 +1626,7 @@ def linear_book(X, W, adv, ori, pred, label, untarget, bestdist, bestscore, o_be
                   label.data_ptr(), 1 if untarget else 0, bestdist.data_ptr(), bestscore.data_ptr(),
                   o_bestdist.data_ptr(), o_bestscore.data_ptr(), o_bestattack.data_ptr(), _ptr(input_val),
                   _ptr(dist_val), float(lr), float(betas[0]), float(betas[1]), _ptr(step), _ptr(adam),
-                  1 if ride else 0, _stream())
+                  1 if ride else 0, tile, _stream())
     return Y
 
 

@@ -542,15 +542,42 @@ int pc3d_pointnet_ft_dtf_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t
  * kernel the backward of Linear + (Leaky)ReLU when W is passed transposed: dX_prev = gate_prev(dY . W)).
  * Replaces F.linear / BatchNorm1d(eval, folded) / ReLU of model/pointnet.py:38-47,144-147 (LeakyReLU(0.2): the DGCNN
  * head, model/dgcnn.py:322-326) and their autograd.
+ *
+ * Shapes with K % 16 == 0, K <= 1024, P == 1 and O >= 64 run a kernel whose eight waves split K in chunks of 16
+ * (chunk c belongs to wave c % 8) and whose tile — rows x outputs per workgroup — is one of four forms:
+ *   PC3D_LIN_TILE_32X16   two row tiles of 16 per workgroup, grid (O/16, ceil(B/32))
+ *   PC3D_LIN_TILE_16X16   one row tile,                      grid (O/16, ceil(B/16))
+ *   PC3D_LIN_TILE_16X8    eight outputs,                     grid (O/8,  ceil(B/16))
+ *   PC3D_LIN_TILE_8X8     eight rows, eight outputs,         grid (O/8,  ceil(B/8))
+ * A workgroup pulls 4 K (rows + outputs) bytes, and above the launch floor a launch lasts as long as one workgroup's
+ * pull: the smaller tiles spread the same layer over more CUs. Every form computes the SAME BITS (an output depends on
+ * its own row of X and of W only; the k order, the chunk -> wave assignment and the order in which the waves' partial
+ * sums are added do not depend on the tile; tests/test_linear_tiles_gpu.py). tile = PC3D_LIN_TILE_RULE (0) takes
+ * pc3d_linear_tile(B, K, O); a form by name is for the parity tests and the bench tool. Other shapes run 32 x 32 tiles
+ * and ignore `tile`.
+ *
+ * pc3d_linear_tile: the rule, a pure function of the layer's shape (no timing, environment or process state). Its
+ * table, fixed from profiles/linear_tiles_bench.json and the headline pairs, with
+ * wgs(form) = ceil(O / outputs) * ceil(B / rows):
+ *   K < 256 (not measured)                      ->  PC3D_LIN_TILE_32X16
+ *   otherwise the first of 8X8, 16X8, 16X16 with wgs(form) <= 256 (one workgroup per CU), else 32X16
+ * At B = 32: 1024 -> 512, 512 -> 256 and 256 -> 512 take 8X8 (256, 128, 256 workgroups), 512 -> 1024 takes 16X8 (256).
+ * pc3d_linear_book_f32 alone does not take the rule for tile 0 (see there).
  * ------------------------------------------------------------------------------------------------------- */
+enum { PC3D_LIN_TILE_RULE = 0, PC3D_LIN_TILE_32X16 = 1, PC3D_LIN_TILE_16X16 = 2, PC3D_LIN_TILE_16X8 = 3,
+       PC3D_LIN_TILE_8X8 = 4 };
+int pc3d_linear_tile(int B, int K, int O);
 int pc3d_linear_f32(const float* X, int ldx, int P, int B, int K, const float* W, const float* bias, int O,
-                    int relu, float slope, const float* gate, int ldg, float gate_slope, float* Y, int ldy, void* stream);
+                    int relu, float slope, const float* gate, int ldg, float gate_slope, float* Y, int ldy, int tile,
+                    void* stream);
 /* The same layer with its X operand produced on the fly by a tiny pre-layer (the backward of STN3d's fc3, 9 -> 256,
  * folded into the launch of fc2's backward, model/pointnet.py:44-45 and their autograd):
  *   X[b,k] = gate_pre[b,k] > 0 ? sum_{j<J} (sum_p parts[b,p,j]) Wp[j,k] : 0 ;   Y[b,o] = gate(sum_k X[b,k] W[o,k])
- * parts [B,P,Jp] (J <= Jp columns used, J <= 16), Wp [J,K] row-major, gate_pre [B,K] (row stride ldgp), K % 16 == 0. */
+ * parts [B,P,Jp] (J <= Jp columns used, J <= 16), Wp [J,K] row-major, gate_pre [B,K] (row stride ldgp), K % 16 == 0.
+ * tile: as pc3d_linear_f32's (the summed slab S and the on-the-fly X follow the row tile; the same bits in every form). */
 int pc3d_linear_pre_f32(const float* parts, int P, int Jp, int J, const float* Wp, const float* gate_pre, int ldgp, int B,
-                        int K, const float* W, int O, const float* gate, int ldg, float* Y, int ldy, void* stream);
+                        int K, const float* W, int O, const float* gate, int ldg, float* Y, int ldy, int tile,
+                        void* stream);
 
 /* log_softmax (model/pointnet.py:148) + argmax + adversarial loss on the log-probabilities and its gradient w.r.t.
  * the LOGITS, one launch. kind 0 = UntargetedLogitsAdvLoss, 1 = LogitsAdvLoss, 2 = CrossEntropyAdvLoss, 3 = minus kind 2
@@ -1313,18 +1340,22 @@ int pc3d_pcd_tail_bwd_f32(const float* g, const uint32_t* mask, const float* w4,
  *
  * pc3d_linear_nn_f32: pc3d_linear_f32 (first 15 arguments) + pc3d_nn_f32 (q, r, NB clouds, N queries, M reference
  * points, min_d2 / idx) as ONE launch: the search's workgroups ride behind the layer's. ride = 0, or a shape outside
- * the rider's range (the layer not on the 32 x 16 tiling, the search not on its 512-thread form or M > 2048), runs the
- * two existing launches instead: callers always make one call.
+ * the rider's range (the layer not on the tiled kernel of pc3d_linear_f32, the search not on its 512-thread form or
+ * M > 2048), runs the two existing launches instead: callers always make one call. tile: the layer's tile as
+ * pc3d_linear_f32's; the layer's workgroups, however many the tile makes them, come first in dispatch order.
  * ------------------------------------------------------------------------------------------------------- */
 int pc3d_linear_nn_f32(const float* X, int ldx, int P, int B, int K, const float* W, const float* bias, int O,
                        int relu, float slope, const float* gate, int ldg, float gate_slope, float* Y, int ldy,
                        const float* q, int64_t q_bs, int64_t q_ps, int64_t q_cs,
                        const float* r, int64_t r_bs, int64_t r_ps, int64_t r_cs,
-                       int NB, int N, int M, float* min_d2, int32_t* idx, int ride, void* stream);
+                       int NB, int N, int M, float* min_d2, int32_t* idx, int ride, int tile, void* stream);
 /* pc3d_linear_f32 + the bookkeeping half of pc3d_cw_update_f32 (||adv-ori|| into dist_val, best-distance decisions,
  * the input_val / o_bestattack copies; same reduction tree, same bits) for NB samples of NK <= 8192 points, as NB extra
  * workgroups of the layer's launch. adam [2] (may be NULL) receives Adam's {lr / (1 - beta1^t), sqrt(1 - beta2^t)} for
- * the value t of the device step word step_dev. ride = 0 or a layer outside the 32 x 16 tiling: two launches. */
+ * the value t of the device step word step_dev. ride = 0 or a layer outside the tiled kernel: two launches (the layer
+ * then as pc3d_linear_f32 with the same tile). tile: a form by name as pc3d_linear_f32's; 0 is PC3D_LIN_TILE_32X16 in
+ * the one launch — it lasts as long as the bookkeeping workgroups behind the layer's, and no smaller tile measured
+ * faster there. */
 int pc3d_linear_book_f32(const float* X, int ldx, int P, int B, int K, const float* W, const float* bias, int O,
                          int relu, float slope, const float* gate, int ldg, float gate_slope, float* Y, int ldy,
                          const float* adv, int64_t a_bs, int64_t a_ps, int64_t a_cs,
@@ -1333,7 +1364,7 @@ int pc3d_linear_book_f32(const float* X, int ldx, int P, int B, int K, const flo
                          float* bestdist, int64_t* bestscore, float* o_bestdist, int64_t* o_bestscore,
                          float* o_bestattack, float* input_val, float* dist_val,
                          double lr, double beta1, double beta2, const int32_t* step_dev, float* adam,
-                         int ride, void* stream);
+                         int ride, int tile, void* stream);
 /* pc3d_pointmlp3_max_bwd_f32 in accumulate form (T = NULL, no dL/dT) whose epilogue applies the update half of
  * pc3d_cw_update_f32 to the tower's input x (= the iterate adv, updated IN PLACE together with m / v, which share its
  * strides) instead of storing grad_x + this tower's gradient: distance gradient (dist_kind 0 / 1 / 2 as
