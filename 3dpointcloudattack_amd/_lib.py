@@ -153,6 +153,8 @@ SIGNATURES = {
     "pc3d_eot_draw_f32": [_L, _L, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     "pc3d_geoa3_update_f32": [_P] * 6 + [_I, _I, _I] + [_P] * 9 + [_I, _I, _F, _F, _F, _F, _P, _P, _I, _P, _P, _P, _I]
     + [_P] * 6 + [_D, _D, _D, _F, _P, _P, _P, _P],
+    "pc3d_geoa3_update_ragged_f32": [_P] * 6 + [_I, _I, _I] + [_P] * 9 + [_I, _I, _F, _F, _F, _F, _P, _P, _I, _P, _P, _P, _I]
+    + [_P] * 6 + [_D, _D, _D, _F, _P, _P, _P, _P, _P],
     "pc3d_add_update_f32": _PTS + _PTS + [_I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P] + _PTS + [_P, _P]
     + [_D, _D, _D, _D, _P, _I, _I, _P, _F, _I, _P],
     "pc3d_cw_bookkeep_f32": _PTS + _PTS + [_I, _I, _P, _P, _I, _P, _P, _P, _P] + _PTS + _PTS + [_P, _P, _P],

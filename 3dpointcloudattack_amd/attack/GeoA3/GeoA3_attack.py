@@ -12,6 +12,7 @@ DESIGN.md / SURVEY App. A:
 
 ``cfg.device_loop = True`` (PointNet victims, see ``_device_loop_plan``): the iteration is the victim's launch-minimal passes
 around the loss launch, the searches and ONE update launch (pc3d_geoa3_update_f32), replayed from a hipGraph without autograd.
+``cfg.lengths`` (one int per cloud) runs that loop on a batch of clouds of different sizes.
 """
 import numpy as np
 import torch
@@ -23,9 +24,9 @@ from ... import ops
 from ... import streams as _streams
 
 from .knn_utils import knn_gather, knn_points
-from .loss_utils import (_get_kappa_adv, _get_kappa_ori, chamfer_loss, curvature_loss, hausdorff_loss, norm_l2_loss,
-                         pseudo_chamfer_loss, uniform_loss)
-from .utility import (_compare, estimate_normal, estimate_perpendicular, farthest_points_sample,
+from .loss_utils import (_get_kappa_adv, _get_kappa_ori, _get_kappa_ori_ragged, chamfer_loss, curvature_loss, hausdorff_loss,
+                         norm_l2_loss, pseudo_chamfer_loss, uniform_loss)
+from .utility import (_compare, estimate_normal, estimate_normal_ragged, estimate_perpendicular, farthest_points_sample,
                       pad_larger_tensor_with_index_batch)
 
 
@@ -74,11 +75,18 @@ def lp_clip(offset, cc_linf):
     return torch.where(lengths < cc_linf, offset, offset_scaled)
 
 
-def _draw_offset(b, c, n, dev, cfg, gens):
+def _draw_offset(b, c, n, dev, cfg, gens, lens=None):
     """The N(0, 1e-3) start offsets (:278-279, :293-294). Default: drawn on the device like the reference on a GPU.
     ``cfg.host_rng = True`` draws them from torch's global CPU generator (what the reference does on a CPU-only box —
     the golden fixtures); ``cfg.sample_seeds`` (one int per sample) draws sample i's offsets from its own CPU
-    generator, so a sample's trajectory does not depend on which batch / rank it runs in."""
+    generator, so a sample's trajectory does not depend on which batch / rank it runs in.
+    lens (a ragged batch, with gens): sample i draws (c, lens[i]) values — what its run alone draws — into its first
+    columns; the others stay 0. Without gens the draw is batch-shaped whatever the lengths."""
+    if gens is not None and lens is not None:
+        o = torch.zeros(b, c, n)
+        for i, (g, ln) in enumerate(zip(gens, lens)):
+            o[i, :, :int(ln)] = torch.zeros(c, int(ln)).normal_(0., 1e-3, generator=g)
+        return o.to(dev)
     if gens is not None:
         return torch.stack([torch.zeros(c, n).normal_(0., 1e-3, generator=g) for g in gens]).to(dev)
     if getattr(cfg, "host_rng", False):
@@ -306,6 +314,41 @@ def _device_loop_state(plan, b, n, dev):
     s["oa_d"], s["oa_i"] = (torch.zeros((b, n), **f32), torch.zeros((b, n), **i32)) if plan["two"] else (None, None)
     s["knn_d"], s["knn_i"] = ((torch.zeros((b, n, k + 1), **f32), torch.zeros((b, n, k + 1), **i32))     # knn_i: also the search's hint
                               if plan["curv"] else (None, None))
+    if plan.get("ragged"):
+        # the lengths are DATA of the captured launches: another call's lengths replay the same graphs. lens_host: the host
+        # copy the search wrapper checks (filled in place by every call).
+        s["lens"] = torch.full((b,), n, **i32)
+        s["lens_host"] = np.full((b,), n, dtype=np.int64)
+        vlens = dict(lengths=s["lens"]) if getattr(victim, "fused_lengths", False) else {}
+
+        def body():
+            # the dense chain, launch for launch: the victim's passes — given the lengths when the victim declares
+            # fused_lengths (its towers then skip the padding), else on the padded batch (pad_invariant: the padding rows'
+            # gradient is exactly zero either way) —, the loss launch, both nearest-neighbour searches unchanged (the padding
+            # rows of ori and of the iterate are copies of their row 0 and lose every tie to it), the self-kNN search over
+            # every cloud's own points, the ragged update, which pads the new iterate
+            with torch.no_grad():
+                logits, ctx = _pointnet.fused_forward(victim, s["x"], **vlens)
+                _, _, cls, g_logits = ops.cls_loss(logits, s["target"], plan["kind"], plan["kappa"], scale=plan["gval"],
+                                                   pred_out=s["pred"])
+                gx = _pointnet.fused_input_grad(ctx, g_logits)
+                if need_ao:
+                    ops.nn_search_into(s["x"], s["ori"], s["ao_d"], s["ao_i"])
+                if plan["two"]:
+                    ops.nn_search_into(s["ori"], s["x"], s["oa_d"], s["oa_i"])
+                if plan["curv"]:
+                    ops.knn_search_into(s["x"], s["knn_d"], s["knn_i"], lengths=s["lens"], lengths_host=s["lens_host"])
+                ops.geoa3_update(s["x"], s["ori"], s["offset"], gx, s["m"], s["v"], s["step"], s["search"], s["lr"], s["scale"],
+                                 cls, s["pred"], s["target"], plan["targeted"], s["constrain"], s["loss_rows"], s["best_loss"],
+                                 s["best_attack"], s["best_bs"], s["best_step"], s["iter_best_loss"], s["iter_best_score"],
+                                 nn_ao=s["ao_i"], nn_oa=s["oa_i"], knn_idx=s["knn_i"],
+                                 normal_ori=s["normal"] if plan["curv"] else None,
+                                 kappa_ori=s["kappa_ori"] if plan["curv"] else None, dis_kind=plan["dis_kind"],
+                                 gval=plan["gval"], w_dis=plan["w_dis"], w_hd=plan["w_hd"], w_curv=plan["w_curv"],
+                                 scheduler=plan["scheduler"], cc_linf=plan["cc_linf"], lengths=s["lens"])
+
+        return cache.put(key, _graphed.DeviceLoop(key, dev, owners=(victim,), counts=(1, LOOP_BLOCK), warmup=2, body=body,
+                                                  bufs=s))
 
     def body():
         # one chain on one stream: the victim's passes around the loss launch, the searches, the update
@@ -333,9 +376,12 @@ def _device_loop_state(plan, b, n, dev):
 
 
 def _rewind(s, plan, offset0, scale_const, search_step):
-    """The state of a search step's first iteration, in place."""
+    """The state of a search step's first iteration, in place. A ragged loop pads the start iterate: its rows at and beyond
+    a length become copies of its row 0, whatever the offset holds there."""
     s["offset"].copy_(offset0)
     torch.add(s["ori"], s["offset"], out=s["x"])
+    if s.get("lens") is not None:
+        ops.pad_ragged(s["x"], s["lens"])
     s["m"].zero_(), s["v"].zero_(), s["step"].zero_()
     s["lr"].fill_(plan["lr"]), s["constrain"].fill_(1e10)
     s["iter_best_loss"].fill_(1e10), s["iter_best_score"].fill_(-1)
@@ -358,9 +404,10 @@ def _adjust_scale(lower_bound, upper_bound, scale_const, succ_now, iter_best_sco
                 scale_const[k] = (lower_bound[k] + upper_bound[k]) * 0.5
 
 
-def _run_device_loop(plan, pc_ori, normal_ori, kappa_ori, target, gt_target, cfg, gens):
+def _run_device_loop(plan, pc_ori, normal_ori, kappa_ori, target, gt_target, cfg, gens, lens=None):
     """The binary search (:271-404) around the captured iteration. Returns (best_attack, best_loss, best_attack_step,
-    loss rows [iter_max_steps,B] of the last search step)."""
+    loss rows [iter_max_steps,B] of the last search step). lens (int64 numpy [B], with a plan that carries the ragged flag):
+    the clouds' sizes, copied into the loop's own buffers before anything runs."""
     b, _, n = pc_ori.shape
     dev = pc_ori.device
     targeted = plan["targeted"]
@@ -375,6 +422,9 @@ def _run_device_loop(plan, pc_ori, normal_ori, kappa_ori, target, gt_target, cfg
         s["best_loss"].fill_(1e10), s["best_attack"].fill_(1.0), s["best_step"].fill_(-1), s["best_bs"].fill_(-1)
 
     with torch.no_grad():
+        if lens is not None:
+            s["lens_host"][:] = lens
+            s["lens"].copy_(torch.from_numpy(lens.astype(np.int32)))
         s["ori"].copy_(pc_ori)
         s["target"].copy_(target if targeted else gt_target)
         if plan["curv"]:
@@ -387,7 +437,7 @@ def _run_device_loop(plan, pc_ori, normal_ori, kappa_ori, target, gt_target, cfg
             _rewind(s, plan, torch.zeros_like(s["offset"]), scale_const, 0)
             loop.capture(reset_best)
         for search_step in range(cfg.binary_max_steps):
-            _rewind(s, plan, _draw_offset(b, 3, n, dev, cfg, gens), scale_const, search_step)
+            _rewind(s, plan, _draw_offset(b, 3, n, dev, cfg, gens, lens), scale_const, search_step)
             loop.run(plan["steps"])
             # one read-back per search step: the loss rows, the last prediction and the step's best label (:393-404)
             loss_rows = s["loss_rows"].cpu()
@@ -397,16 +447,21 @@ def _run_device_loop(plan, pc_ori, normal_ori, kappa_ori, target, gt_target, cfg
         return s["best_attack"].clone(), s["best_loss"].clone(), s["best_step"].clone(), loss_rows
 
 
-def _finish(transfer, best_attack, target, targeted, best_loss, best_attack_step, loss_rows):
+def _finish(transfer, best_attack, target, targeted, best_loss, best_attack_step, loss_rows, lens=None):
     """Transfer attack evaluation (:406-471), batched; counters exposed as a function attribute. loss_rows: a list of [B]
-    device tensors or one [steps,B] tensor."""
+    device tensors or one [steps,B] tensor. lens (a ragged batch): a transfer model that declares pad_invariant sees the
+    padded batch, any other every cloud alone, [1,3,lens[b]]."""
     fails = []
     with torch.no_grad():
         for m in transfer:
             if m is None:
                 fails.append(None)
                 continue
-            lab = torch.argmax(_graphed.logits_of(m(best_attack.float())), dim=1)
+            if lens is not None and not getattr(_graphed.unwrap(m), "pad_invariant", False):
+                lab = torch.cat([torch.argmax(_graphed.logits_of(m(best_attack[b:b + 1, :, :int(ln)].float().contiguous())), dim=1)
+                                 for b, ln in enumerate(lens)])
+            else:
+                lab = torch.argmax(_graphed.logits_of(m(best_attack.float())), dim=1)
             fails.append(int(((lab == target) if not targeted else (lab != target)).sum().item()))
     geoA3_attack.last_transfer_fails = dict(zip(("pt", "ptm", "pts", "dgcnn", "cur"), fails))
 
@@ -417,24 +472,75 @@ def _finish(transfer, best_attack, target, targeted, best_loss, best_attack_step
     return (best_attack, target, (best_loss.cpu().numpy() < 1e10), best_attack_step.cpu().tolist(), all_loss_list)
 
 
+def _ragged_lengths(net, pc, cfg, lengths):
+    """lengths as int64 numpy [B] after every check of the ragged loop, or ValueError naming what does not fit, before any
+    launch: there is no silent fall-back, since the autograd path would count a cloud's padding in every mean, in the
+    Hausdorff maximum and as curvature neighbours at distance 0."""
+    who = "geoA3_attack(cfg.lengths)"
+    if not getattr(cfg, "device_loop", False):
+        raise ValueError(f"{who}: cfg.device_loop is not set; the autograd path has no ragged pass")
+    if not torch.is_tensor(pc) or pc.dim() != 3 or pc.shape[2] != 3:
+        raise ValueError(f"{who}: pc must be [B, Kmax, 3], got {tuple(pc.shape) if torch.is_tensor(pc) else type(pc).__name__}")
+    b, n = int(pc.shape[0]), int(pc.shape[1])
+    if torch.is_tensor(lengths):
+        lengths = lengths.detach().cpu().numpy()
+    lens = np.asarray(lengths)
+    if lens.shape != (b,) or not np.issubdtype(lens.dtype, np.integer):
+        raise ValueError(f"{who}: lengths must be {b} ints, got shape {lens.shape} dtype {lens.dtype}")
+    curv = cfg.curv_loss_weight != 0
+    k = int(cfg.curv_loss_knn) if curv else 0
+    two = cfg.dis_loss_type == 'CD' and not cfg.is_cd_single_side
+    if not ops.geoa3_update_fits(n, k, curv, two):
+        raise ValueError(f"{who}: Kmax={n} with k={k} curvature neighbours exceeds what pc3d_geoa3_update_f32 holds "
+                         f"(GEOA3_LOOP_MAX_POINTS={ops.GEOA3_LOOP_MAX_POINTS}, 160 KiB of LDS)")
+    low = max(4, k + 1)           # 4: the normals' k = 3 search
+    if b and (lens.min() < low or lens.max() > n):
+        raise ValueError(f"{who}: lengths must lie in [max(4, curv_loss_knn + 1)={low}, Kmax={n}], got [{lens.min()}, {lens.max()}]")
+    victim = _graphed.unwrap(net)
+    if not getattr(victim, "pad_invariant", False):
+        raise ValueError(f"{who}: the victim {type(victim).__name__} does not declare pad_invariant")
+    params = list(victim.parameters())
+    if not params or params[0].device.type != "cuda":
+        raise ValueError(f"{who}: the victim is on {params[0].device if params else 'no device'}: the device loop needs a GPU")
+    if _device_loop_plan(net, cfg, b, n, cfg.attack_method != 'untarget') is None:
+        raise ValueError(f"{who}: the device loop refuses this victim or configuration (_device_loop_plan: a PointNetCls in "
+                         "eval mode, CE / Margin, Chamfer or L2 without Hausdorff, Adam, no uniform term, no partial "
+                         "variable / jitter / gradient projection / sub-sampling)")
+    return lens.astype(np.int64)
+
+
 def geoA3_attack(net, pt_model, ptm_model, pts_model, dgcnn_model, cur_model, pc, label, cfg, i, loader_len,
                  saved_dir=None):
     """cfg.deterministic (optional; None = the process-wide ops.DETERMINISTIC, default on): ordered backward sums, i.e.
     bit-reproducible runs, for the duration of the call.
     cfg.device_loop = True (optional): on a PointNet victim and a configuration _device_loop_plan admits, the iteration runs
     as a captured chain of own kernels without autograd (pc3d_geoa3_update_f32); anything else silently takes the usual
-    path. geoA3_attack.last_path says which one the last call took: "device_loop" or "autograd"."""
+    path. geoA3_attack.last_path says which one the last call took: "device_loop" or "autograd".
+    cfg.lengths (optional; absent or None: every cloud has pc.shape[1] points, nothing changes — an attribute like the other
+    options of this mirror, so that the function keeps the reference's parameter list): B ints, a sequence or a tensor — the sizes of
+    a batch of clouds of different sizes as dataset.cloud_io.stack_ragged builds it, max(4, curv_loss_knn + 1) <= lengths[b]
+    <= Kmax = pc.shape[1]; rows of pc at and beyond a length are ignored (they may hold NaN). Runs the device loop only
+    (cfg.device_loop, a pad_invariant PointNet victim on the GPU, a configuration _device_loop_plan admits, Kmax and
+    curv_loss_knn within ops.geoa3_update_fits); anything else raises ValueError before any launch. With cfg.sample_seeds
+    and cfg.global_batch every cloud gets the bits of its run alone; without seeds the start offsets are one batch-shaped
+    draw whose padding columns are ignored. best_attack is [B,3,Kmax]: columns at and beyond a length hold that cloud's
+    column 0 (the all-ones cloud where nothing was found, as dense)."""
+    lengths = getattr(cfg, "lengths", None)
+    if lengths is not None:
+        lengths = _ragged_lengths(net, pc, cfg, lengths)
     det = getattr(cfg, "deterministic", None)
     if det is None:
-        return _geoA3_attack(net, pt_model, ptm_model, pts_model, dgcnn_model, cur_model, pc, label, cfg, i, loader_len, saved_dir)
+        return _geoA3_attack(net, pt_model, ptm_model, pts_model, dgcnn_model, cur_model, pc, label, cfg, i, loader_len, saved_dir,
+                             lengths)
     with ops.deterministic(det):
-        return _geoA3_attack(net, pt_model, ptm_model, pts_model, dgcnn_model, cur_model, pc, label, cfg, i, loader_len, saved_dir)
+        return _geoA3_attack(net, pt_model, ptm_model, pts_model, dgcnn_model, cur_model, pc, label, cfg, i, loader_len, saved_dir,
+                             lengths)
 
 
 def _geoA3_attack(net, pt_model, ptm_model, pts_model, dgcnn_model, cur_model, pc, label, cfg, i, loader_len,
-                  saved_dir=None):
+                  saved_dir=None, lens=None):
     """:185-473. pc [B,N,3], label [B]. Returns (best_attack [B,3,N] tensor, target [B], success mask np.bool [B],
-    best_attack_step list[B], all_loss_list [iter_max_steps][B])."""
+    best_attack_step list[B], all_loss_list [iter_max_steps][B]). lens: what _ragged_lengths returned, or None."""
     dev = next(net.parameters()).device if any(True for _ in net.parameters()) else torch.device("cuda")
     transfer = []
     for m in (pt_model, ptm_model, pts_model, dgcnn_model, cur_model):
@@ -448,25 +554,42 @@ def _geoA3_attack(net, pt_model, ptm_model, pts_model, dgcnn_model, cur_model, p
     net = _graphed.wrap(net, enable=getattr(cfg, "graph_victim", None))
 
     pc = pc.transpose(2, 1).float().to(dev)
-    normal = estimate_normal(pc, k=3)
+    lens_dev = None
+    if lens is not None:
+        # ragged batch: a copy of the input whose rows from a length on become copies of the cloud's point 0, once; the
+        # normals and kappa_ori from searches over every cloud's own points
+        lens_dev = torch.from_numpy(lens.astype(np.int32)).to(dev)
+        pc = ops.pad_ragged(pc.clone(memory_format=torch.contiguous_format), lens_dev)
+        normal = estimate_normal_ragged(pc, 3, lens_dev, lens)
+    else:
+        normal = estimate_normal(pc, k=3)
     b, _, n = pc.size()
     pc_ori = pc.contiguous().view(b, 3, n)
     normal_ori = normal.view(b, 3, n)
     gt_target = label.view(-1).to(dev)
     target = gt_target
 
-    kappa_ori = _get_kappa_ori(pc_ori, normal_ori, cfg.curv_loss_knn) if cfg.curv_loss_weight != 0 else None
+    if cfg.curv_loss_weight == 0:
+        kappa_ori = None
+    elif lens is not None:
+        kappa_ori = _get_kappa_ori_ragged(pc_ori, normal_ori, cfg.curv_loss_knn, lens_dev, lens)
+    else:
+        kappa_ori = _get_kappa_ori(pc_ori, normal_ori, cfg.curv_loss_knn)
 
     seeds = getattr(cfg, "sample_seeds", None)
     gens = [torch.Generator().manual_seed(int(sd)) for sd in seeds] if seeds is not None else None
     assert gens is None or len(gens) == b, "cfg.sample_seeds needs one seed per sample"
 
     plan = _device_loop_plan(net, cfg, b, n, targeted) if getattr(cfg, "device_loop", False) and pc_ori.is_cuda else None
+    if lens is not None:
+        if plan is None:       # _ragged_lengths has asked the same question
+            raise ValueError("geoA3_attack(cfg.lengths): the device loop refuses this victim or configuration")
+        plan = dict(plan, ragged=True)      # the flag, not the lengths: other lengths replay the same graphs
     geoA3_attack.last_path = "device_loop" if plan is not None else "autograd"
     if plan is not None:
         best_attack, best_loss, best_attack_step, loss_rows = _run_device_loop(plan, pc_ori, normal_ori, kappa_ori, target,
-                                                                               gt_target, cfg, gens)
-        return _finish(transfer, best_attack, target, targeted, best_loss, best_attack_step, loss_rows)
+                                                                               gt_target, cfg, gens, lens)
+        return _finish(transfer, best_attack, target, targeted, best_loss, best_attack_step, loss_rows, lens)
 
     lower_bound = torch.zeros(b)
     scale_const = torch.ones(b) * cfg.initial_const
@@ -587,7 +710,7 @@ def _geoA3_attack(net, pt_model, ptm_model, pts_model, dgcnn_model, cur_model, p
                     if (lg.is_cuda and lg.dtype == torch.float32 and lg.dim() == 2 and lg.stride(1) == 1
                             and isinstance(prev_constrain, torch.Tensor) and prev_constrain.shape == (b,)
                             and prev_constrain.dtype == torch.float32 and it_.is_contiguous()):
-                        from ... import ops     # arg-max, success test and the six conditional updates: one launch
+                        # arg-max, success test and the six conditional updates: one launch
                         output_label = ops.geoa3_record(lg, target if targeted else gt_target, targeted,
                                                         prev_constrain.detach().contiguous(), it_, search_step, step,
                                                         best_loss, best_attack, best_attack_BS_idx, best_attack_step,

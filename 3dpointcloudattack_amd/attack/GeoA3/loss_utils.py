@@ -61,6 +61,21 @@ def _get_kappa_ori(pc, normal, k=2):
     return _kappa(pc, normal, k)
 
 
+def _get_kappa_ori_ragged(pc, normal, k, lengths, lengths_host=None):
+    """_get_kappa_ori on a batch of clouds of different sizes: pc / normal [b,3,n], cloud i counting lengths[i] points (int32
+    [b] on pc's device; lengths_host: their host copy), k + 1 <= lengths[i]. The search is ops.knn_ragged, the curvature
+    launch runs on its lists (zero at and beyond a length). Columns below a length have the bits of _get_kappa_ori on that
+    cloud alone, those at and beyond it are 0. pc's and normal's columns there are not read."""
+    from ... import ops
+    with torch.no_grad():
+        pts = ops.pad_ragged(pc.detach().float().clone(memory_format=torch.contiguous_format), lengths)
+        nrm = ops.pad_ragged(normal.detach().float().clone(memory_format=torch.contiguous_format), lengths)
+        idx = ops.knn_ragged(pts, pts, k + 1, lengths, q_cf=True, r_cf=True, lengths_host=lengths_host)[1]
+        kap = ops.kappa(pts, nrm, idx, cf=True)
+        behind = torch.arange(pts.shape[2], device=pts.device)[None, :] >= lengths[:, None]
+        return kap.masked_fill_(behind, 0.)
+
+
 def _get_kappa_adv(adv_pc, ori_pc, ori_normal, k=2, nn_ao=None, knn_idx=None):
     """:72-90 — normals of the nearest ori point, curvature proxy from the adv cloud's own k-NN. knn_idx: int32 [B,N,k+1]
     neighbour lists of adv_pc (self first) when the caller already has them (the victim's own input graph,

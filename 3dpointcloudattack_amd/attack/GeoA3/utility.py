@@ -42,6 +42,19 @@ def estimate_normal(pc, k):
         return ops.estimate_normal(pts, idx).permute(0, 2, 1).contiguous()
 
 
+def estimate_normal_ragged(pc, k, lengths, lengths_host=None):
+    """estimate_normal on a batch of clouds of different sizes: pc [b,3,n], cloud i counting lengths[i] points (int32 [b] on
+    pc's device; lengths_host: their host copy, None: read back), k + 1 <= lengths[i]. knn_points ignores lengths as the
+    reference does, so the search is ops.knn_ragged — a cloud's padding never is a neighbour — and the normals' launch runs
+    on its lists, zero at and beyond a length. Columns below a length have the bits of estimate_normal on that cloud alone;
+    those at and beyond it hold the cloud's normal 0 (ops.pad_ragged). pc's columns there are not read."""
+    with torch.no_grad():
+        pts = ops.pad_ragged(pc.float().clone(memory_format=torch.contiguous_format), lengths)
+        idx = ops.knn_ragged(pts, pts, k + 1, lengths, q_cf=True, r_cf=True, lengths_host=lengths_host)[1]
+        normal = ops.estimate_normal(pts, idx, cf=True).permute(0, 2, 1).contiguous()
+        return ops.pad_ragged(normal, lengths)
+
+
 def estimate_normal_via_ori_normal(pc_adv, pc_ori, normal_ori, k):
     """utility.py:94-111."""
     intra_KNN = knn_points(pc_adv.permute(0, 2, 1), pc_ori.permute(0, 2, 1), K=k)

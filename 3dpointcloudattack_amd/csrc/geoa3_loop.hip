@@ -80,6 +80,12 @@ struct GeoUpdArgs {
   int32_t* hd_arg_out;       // [B] or null
   float* g_out;              // [B,3,N] the total gradient, or null
 };
+// Clouds of different sizes in one batch: cloud b counts lengths[b] points (int32 [B], read as data, clamped to [1, N]).
+struct GeoUpdRaggedArgs : GeoUpdArgs {
+  const int32_t* lengths;
+};
+template <bool RAGGED> struct GeoUpdArgsOf { using type = GeoUpdArgs; };
+template <> struct GeoUpdArgsOf<true> { using type = GeoUpdRaggedArgs; };
 
 static inline size_t geo_upd_lds_bytes(int N, int k, bool curv, bool two) {
   const size_t np = (size_t)((N + 3) & ~3);
@@ -138,10 +144,20 @@ __device__ __forceinline__ void gu_sort_bucket(uint16_t* rev, int s, int e) {
   }
 }
 
-__global__ __launch_bounds__(kGuThreads) void geoa3_update_kernel(GeoUpdArgs a) {
+// RAGGED: N is the capacity — the row stride of every [B,3,N], [B,N] and [B,N,K1] buffer and the size of the LDS arrays —
+// and every loop over points, the means' divisors, the index clamps, the bucket bounds and the scans run over L =
+// clamp(lengths[b], 1, N) with the dense kernel's thread-to-point mapping and summation order: rows < L have the bits of the
+// dense launch at N = L on that cloud alone. Rows >= L of no input are loaded (they may hold NaN or any integer); those of
+// m, v, offset and g_out stay; x's take the NEW point 0 — the padding the victim's passes and the next searches rely on: an
+// exact copy of row 0 loses every tie to index 0 — and the record copies the iterate's row 0 into best_attack's. The dense
+// instantiation compiles to the kernel it was before RAGGED existed (the parameter is a type of its own).
+template <bool RAGGED>
+__global__ __launch_bounds__(kGuThreads) void geoa3_update_kernel(typename GeoUpdArgsOf<RAGGED>::type a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char gu_lds[];
   const int N = a.N, np = (N + 3) & ~3, K1 = a.K1, k = K1 - 1;
   const int b = blockIdx.x, tid = threadIdx.x;
+  int L = N;
+  if constexpr (RAGGED) L = min(max(a.lengths[b], 1), N);
   const bool curv = a.knn_idx != nullptr && k >= 1 && a.w_curv != 0.f;
   const bool two = a.dis_kind == 0 && a.nn_oa != nullptr;
   const bool chamfer = a.dis_kind == 0;
@@ -152,6 +168,7 @@ __global__ __launch_bounds__(kGuThreads) void geoa3_update_kernel(GeoUpdArgs a) 
   int* redi = reinterpret_cast<int*>(scr + 32);                  // [16]
   float* s_c = scr + 48;                                         // broadcast constants
   int* s_i = reinterpret_cast<int*>(scr + 64);                   // broadcast integers
+  [[maybe_unused]] float* s_pad = scr + 80;                      // [3] RAGGED: the new point 0
   float* sx = scr + kGuScratch / 4;
   float* sy = sx + np;
   float* sz = sy + np;
@@ -192,15 +209,19 @@ __global__ __launch_bounds__(kGuThreads) void geoa3_update_kernel(GeoUpdArgs a) 
     s_i[0] = upd ? 1 : 0;
     s_i[1] = t0;
   }
-  for (int p = tid; p < N; p += kGuThreads) {
+  for (int p = tid; p < L; p += kGuThreads) {
     sx[p] = xg[p], sy[p] = xg[N + p], sz[p] = xg[2 * N + p];
     if (curv) {
-      const int q = min(max(a.nn_ao[base1 + p], 0), N - 1);
+      const int q = min(max(a.nn_ao[base1 + p], 0), L - 1);
       const float* nb = a.normal_ori + base3;
       nx[p] = nb[q], ny[p] = nb[N + q], nz[p] = nb[2 * N + q];
       off[p] = 0;
     }
     if (two) off2[p] = 0;
+  }
+  if constexpr (RAGGED) {      // the iterate's padding rows are copies of its row 0: written so, not read
+    const float x0 = xg[0], y0 = xg[N], z0 = xg[2 * N];
+    for (int p = L + tid; p < N; p += kGuThreads) sx[p] = x0, sy[p] = y0, sz[p] = z0;
   }
   __syncthreads();
   if (s_i[0]) {
@@ -211,17 +232,17 @@ __global__ __launch_bounds__(kGuThreads) void geoa3_update_kernel(GeoUpdArgs a) 
   // ---- 2. terms ----
   float s_ao = 0.f, s_oa = 0.f, s_cv = 0.f, mx = -__builtin_inff();
   int mi = 0x7fffffff;
-  for (int p = tid; p < N; p += kGuThreads) {
+  for (int p = tid; p < L; p += kGuThreads) {
     const float px = sx[p], py = sy[p], pz = sz[p];
     if (a.nn_ao != nullptr || !chamfer) {
-      const int q = chamfer ? min(max(a.nn_ao[base1 + p], 0), N - 1) : p;
+      const int q = chamfer ? min(max(a.nn_ao[base1 + p], 0), L - 1) : p;
       const float dx = px - og[q], dy = py - og[N + q], dz = pz - og[2 * N + q];
       const float d = dx * dx + dy * dy + dz * dz;
       s_ao += d;
       if (chamfer && d > mx) mx = d, mi = p;      // ascending p within a thread: strict > keeps the first maximum
     }
     if (two) {
-      const int i = min(max(a.nn_oa[base1 + p], 0), N - 1);
+      const int i = min(max(a.nn_oa[base1 + p], 0), L - 1);
       const float dx = og[p] - sx[i], dy = og[N + p] - sy[i], dz = og[2 * N + p] - sz[i];
       s_oa += dx * dx + dy * dy + dz * dz;
       atomicAdd(off2 + i, 1);
@@ -231,13 +252,13 @@ __global__ __launch_bounds__(kGuThreads) void geoa3_update_kernel(GeoUpdArgs a) 
       const int32_t* nb = ib + (int64_t)p * K1;
       float s = 0.f;
       for (int e = 1; e < K1; ++e) {
-        const int j = min(max(nb[e], 0), N - 1);
+        const int j = min(max(nb[e], 0), L - 1);
         const float dx = sx[j] - px, dy = sy[j] - py, dz = sz[j] - pz;
         const float len = fmaxf(sqrtf(dx * dx + dy * dy + dz * dz), 1e-12f);
         s += fabsf((dx / len) * ux + (dy / len) * uy + (dz / len) * uz);
         atomicAdd(off + j, 1);
       }
-      const int q = min(max(a.nn_ao[base1 + p], 0), N - 1);
+      const int q = min(max(a.nn_ao[base1 + p], 0), L - 1);
       const float t = s / (float)k - a.kappa_ori[base1 + q];
       kd[p] = t;
       s_cv += t * t;
@@ -260,9 +281,9 @@ __global__ __launch_bounds__(kGuThreads) void geoa3_update_kernel(GeoUpdArgs a) 
     for (int w = 1; w < kGuWaves; ++w)
       if (redv[w] > mx || (redv[w] == mx && redi[w] < mi)) mx = redv[w], mi = redi[w];
     const bool has_hd = chamfer && mi != 0x7fffffff;
-    const float dis = chamfer ? s_ao / (float)N + (two ? s_oa / (float)N : 0.f) : s_ao;
+    const float dis = chamfer ? s_ao / (float)L + (two ? s_oa / (float)L : 0.f) : s_ao;
     const float hd = has_hd ? mx : 0.f;
-    const float cv = curv ? s_cv / (float)N : 0.f;
+    const float cv = curv ? s_cv / (float)L : 0.f;
     const float con = (a.w_dis * dis + a.w_hd * hd) + a.w_curv * cv;
     const float sc = a.scale[b];
     const float ln = a.cls[b] + sc * con;
@@ -285,23 +306,23 @@ __global__ __launch_bounds__(kGuThreads) void geoa3_update_kernel(GeoUpdArgs a) 
 
   // ---- 3a. the reverse indices ----
   if (curv) {
-    gu_exclusive_scan(off, N, redi);
-    const int total = N * k;
-    for (int p = tid; p < N; p += kGuThreads) {
+    gu_exclusive_scan(off, L, redi);
+    const int total = L * k;
+    for (int p = tid; p < L; p += kGuThreads) {
       const int32_t* nb = ib + (int64_t)p * K1;
       for (int e = 1; e < K1; ++e) {
-        const int j = min(max(nb[e], 0), N - 1);
+        const int j = min(max(nb[e], 0), L - 1);
         const int pos = atomicAdd(off + j, 1);      // afterwards off[j] is the END of bucket j
         if (pos < total) rev[pos] = (uint16_t)p;
       }
     }
   }
   if (two) {
-    gu_exclusive_scan(off2, N, redi);
-    for (int p = tid; p < N; p += kGuThreads) {
-      const int i = min(max(a.nn_oa[base1 + p], 0), N - 1);
+    gu_exclusive_scan(off2, L, redi);
+    for (int p = tid; p < L; p += kGuThreads) {
+      const int i = min(max(a.nn_oa[base1 + p], 0), L - 1);
       const int pos = atomicAdd(off2 + i, 1);
-      if (pos < N) rev2[pos] = (uint16_t)p;
+      if (pos < L) rev2[pos] = (uint16_t)p;
     }
   }
   __syncthreads();
@@ -311,19 +332,19 @@ __global__ __launch_bounds__(kGuThreads) void geoa3_update_kernel(GeoUpdArgs a) 
   const float g_dis = s_c[2], g_hd = s_c[3], g_cv = s_c[4];
   const int hd_arg = s_i[2];
   const float inv_k = 1.f / (float)(k > 0 ? k : 1);
-  for (int p = tid; p < N; p += kGuThreads) {
+  for (int p = tid; p < L; p += kGuThreads) {
     const float px = sx[p], py = sy[p], pz = sz[p];
     float gx = 0.f, gy = 0.f, gz = 0.f;
     if (chamfer) {
       if (a.nn_ao != nullptr) {
-        const int q = min(max(a.nn_ao[base1 + p], 0), N - 1);
-        const float w = g_dis / (float)N + (p == hd_arg ? g_hd : 0.f);
+        const int q = min(max(a.nn_ao[base1 + p], 0), L - 1);
+        const float w = g_dis / (float)L + (p == hd_arg ? g_hd : 0.f);
         gx = 2.f * (px - og[q]) * w, gy = 2.f * (py - og[N + q]) * w, gz = 2.f * (pz - og[2 * N + q]) * w;
       }
       if (two) {
-        const int s = p ? off2[p - 1] : 0, e = min(off2[p], N);
+        const int s = p ? off2[p - 1] : 0, e = min(off2[p], L);
         gu_sort_bucket(rev2, s, e);
-        const float w = g_dis / (float)N;
+        const float w = g_dis / (float)L;
         for (int t = s; t < e; ++t) {
           const int j = rev2[t];
           gx += 2.f * (px - og[j]) * w, gy += 2.f * (py - og[N + j]) * w, gz += 2.f * (pz - og[2 * N + j]) * w;
@@ -336,11 +357,11 @@ __global__ __launch_bounds__(kGuThreads) void geoa3_update_kernel(GeoUpdArgs a) 
       // own side: kappa_bwd_kernel's edge arithmetic, -sum to the point itself
       {
         const float ux = nx[p], uy = ny[p], uz = nz[p];
-        const float gk = (g_cv * 2.f * kd[p] / (float)N) * inv_k;
+        const float gk = (g_cv * 2.f * kd[p] / (float)L) * inv_k;
         const int32_t* nb = ib + (int64_t)p * K1;
         float ox = 0.f, oy = 0.f, oz = 0.f;
         for (int e = 1; e < K1; ++e) {
-          const int j = min(max(nb[e], 0), N - 1);
+          const int j = min(max(nb[e], 0), L - 1);
           const float dx = sx[j] - px, dy = sy[j] - py, dz = sz[j] - pz;
           const float nrm = sqrtf(dx * dx + dy * dy + dz * dz);
           const bool clamped = !(nrm > 1e-12f);
@@ -354,12 +375,12 @@ __global__ __launch_bounds__(kGuThreads) void geoa3_update_kernel(GeoUpdArgs a) 
         gx -= ox, gy -= oy, gz -= oz;
       }
       // neighbour side: the points that list p, ascending
-      const int s = p ? off[p - 1] : 0, e = min(off[p], N * k);
+      const int s = p ? off[p - 1] : 0, e = min(off[p], L * k);
       gu_sort_bucket(rev, s, e);
       for (int t = s; t < e; ++t) {
         const int i = rev[t];
         const float ux = nx[i], uy = ny[i], uz = nz[i];
-        const float gk = (g_cv * 2.f * kd[i] / (float)N) * inv_k;
+        const float gk = (g_cv * 2.f * kd[i] / (float)L) * inv_k;
         const float dx = px - sx[i], dy = py - sy[i], dz = pz - sz[i];
         const float nrm = sqrtf(dx * dx + dy * dy + dz * dz);
         const bool clamped = !(nrm > 1e-12f);
@@ -394,14 +415,80 @@ __global__ __launch_bounds__(kGuThreads) void geoa3_update_kernel(GeoUpdArgs a) 
     for (int c = 0; c < 3; ++c) {
       const int64_t at = base3 + (int64_t)c * N + p;
       a.offset[at] = nw[c];
-      a.x[at] = og[(int64_t)c * N + p] + nw[c];
+      const float xn = og[(int64_t)c * N + p] + nw[c];
+      a.x[at] = xn;
+      if constexpr (RAGGED) {
+        if (p == 0) s_pad[c] = xn;      // thread 0 owns point 0
+      }
     }
+  }
+  if constexpr (RAGGED) {
+    // re-padding: x's rows from L on take the new point 0, through LDS behind the barrier (no thread re-reads global memory
+    // another thread of the workgroup writes)
+    __syncthreads();
+    const float n0[3] = {s_pad[0], s_pad[1], s_pad[2]};
+    float* xo = a.x + base3;
+    for (int p = L + tid; p < N; p += kGuThreads) xo[p] = n0[0], xo[N + p] = n0[1], xo[2 * N + p] = n0[2];
   }
 }
 
 }  // namespace pc3d
 
 using namespace pc3d;
+
+// the checks, the argument block and the launch of both entries; lengths null: the dense kernel
+static int geo_upd_launch(const char* nm, float* x, const float* ori, float* offset, const float* g, float* m, float* v, int B,
+                          int N, int k, const int32_t* nn_ao, const int32_t* nn_oa, const int32_t* knn_idx,
+                          const float* normal_ori, const float* kappa_ori, const float* cls, const float* scale,
+                          const int64_t* pred, const int64_t* target, int targeted, int dis_kind, float gval, float w_dis,
+                          float w_hd, float w_curv, float* constrain, float* loss_rows, int max_steps, int32_t* step,
+                          const int32_t* search_step, double* lr, int scheduler, float* best_loss, float* best_attack,
+                          int64_t* best_bs, int64_t* best_step, float* iter_best_loss, int64_t* iter_best_score, double beta1,
+                          double beta2, double eps, float cc_linf, float* terms_out, int32_t* hd_arg_out, float* g_out,
+                          const int32_t* lengths, bool ragged, void* stream) {
+  PC3D_REQUIRE(B >= 0 && N >= 1 && N <= kGuMaxPoints, "%s: bad sizes B=%d N=%d (1 <= N <= %d)", nm, B, N, kGuMaxPoints);
+  PC3D_REQUIRE(k >= 0 && k <= 63, "%s: k=%d out of range [0,63]", nm, k);
+  PC3D_REQUIRE(dis_kind == 0 || dis_kind == 1, "%s: dis_kind=%d not in {0,1}", nm, dis_kind);
+  PC3D_REQUIRE(max_steps >= 1, "%s: max_steps=%d", nm, max_steps);
+  const bool curv = knn_idx != nullptr && k >= 1 && w_curv != 0.f;
+  const bool two = dis_kind == 0 && nn_oa != nullptr;
+  PC3D_REQUIRE(!curv || k + 1 <= N, "%s: k + 1 = %d neighbours of N=%d points", nm, k + 1, N);
+  PC3D_REQUIRE(dis_kind == 0 || w_hd == 0.f, "%s: the L2 kind has no Hausdorff term", nm);
+  const size_t lds = geo_upd_lds_bytes(N, k, curv, two);      // from the capacity: the lengths are device data
+  PC3D_REQUIRE(lds <= kGuLdsLimit, "%s: N=%d, k=%d need %zu bytes of LDS (limit %zu)", nm, N, k, lds, kGuLdsLimit);
+  if (B == 0) return PC3D_OK;
+  PC3D_REQUIRE(!ragged || lengths != nullptr, "%s: null lengths", nm);
+  PC3D_REQUIRE(x && ori && offset && g && m && v && cls && scale && pred && target && constrain && loss_rows && step &&
+                   search_step && lr && best_loss && best_attack && best_bs && best_step && iter_best_loss && iter_best_score,
+               "%s: null pointer", nm);
+  PC3D_REQUIRE(dis_kind == 1 || nn_ao != nullptr, "%s: the Chamfer kind needs nn_ao", nm);
+  PC3D_REQUIRE(!curv || (nn_ao && normal_ori && kappa_ori), "%s: the curvature term needs nn_ao, normal_ori and kappa_ori", nm);
+  GeoUpdRaggedArgs a{};
+  a.x = x, a.ori = ori, a.offset = offset, a.g = g, a.m = m, a.v = v, a.N = N, a.K1 = k + 1;
+  a.nn_ao = nn_ao, a.nn_oa = nn_oa, a.knn_idx = knn_idx, a.normal_ori = normal_ori, a.kappa_ori = kappa_ori;
+  a.cls = cls, a.scale = scale, a.pred = pred, a.target = target, a.targeted = targeted, a.dis_kind = dis_kind;
+  a.gval = gval, a.w_dis = w_dis, a.w_hd = w_hd, a.w_curv = w_curv, a.constrain = constrain, a.loss_rows = loss_rows;
+  a.max_steps = max_steps, a.B = B, a.step = step, a.search_step = search_step, a.lr = lr, a.scheduler = scheduler;
+  a.best_loss = best_loss, a.best_attack = best_attack, a.best_bs = best_bs, a.best_step = best_step;
+  a.iter_best_loss = iter_best_loss, a.iter_best_score = iter_best_score, a.b1 = beta1, a.b2 = beta2, a.eps = (float)eps;
+  a.cc_linf = cc_linf, a.terms_out = terms_out, a.hd_arg_out = hd_arg_out, a.g_out = g_out, a.lengths = lengths;
+  if (lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(ragged ? reinterpret_cast<const void*>(geoa3_update_kernel<true>)
+                                              : reinterpret_cast<const void*>(geoa3_update_kernel<false>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGuLdsLimit);
+    if (e != hipSuccess) {
+      set_error("%s: LDS opt-in failed: %s", nm, hipGetErrorString(e));
+      return (int)e;
+    }
+  }
+  if (ragged)
+    hipLaunchKernelGGL(geoa3_update_kernel<true>, dim3(B), dim3(kGuThreads), lds, as_stream(stream), a);
+  else
+    hipLaunchKernelGGL(geoa3_update_kernel<false>, dim3(B), dim3(kGuThreads), lds, as_stream(stream),
+                       static_cast<const GeoUpdArgs&>(a));
+  PC3D_LAUNCH_CHECK(nm);
+  return PC3D_OK;
+}
 
 extern "C" int pc3d_geoa3_update_f32(float* x, const float* ori, float* offset, const float* g, float* m, float* v, int B,
                                      int N, int k, const int32_t* nn_ao, const int32_t* nn_oa, const int32_t* knn_idx,
@@ -413,41 +500,25 @@ extern "C" int pc3d_geoa3_update_f32(float* x, const float* ori, float* offset, 
                                      float* iter_best_loss, int64_t* iter_best_score, double beta1, double beta2,
                                      double eps, float cc_linf, float* terms_out, int32_t* hd_arg_out, float* g_out,
                                      void* stream) {
-  PC3D_REQUIRE(B >= 0 && N >= 1 && N <= kGuMaxPoints, "pc3d_geoa3_update_f32: bad sizes B=%d N=%d (1 <= N <= %d)", B, N,
-               kGuMaxPoints);
-  PC3D_REQUIRE(k >= 0 && k <= 63, "pc3d_geoa3_update_f32: k=%d out of range [0,63]", k);
-  PC3D_REQUIRE(dis_kind == 0 || dis_kind == 1, "pc3d_geoa3_update_f32: dis_kind=%d not in {0,1}", dis_kind);
-  PC3D_REQUIRE(max_steps >= 1, "pc3d_geoa3_update_f32: max_steps=%d", max_steps);
-  const bool curv = knn_idx != nullptr && k >= 1 && w_curv != 0.f;
-  const bool two = dis_kind == 0 && nn_oa != nullptr;
-  PC3D_REQUIRE(!curv || k + 1 <= N, "pc3d_geoa3_update_f32: k + 1 = %d neighbours of N=%d points", k + 1, N);
-  PC3D_REQUIRE(dis_kind == 0 || w_hd == 0.f, "pc3d_geoa3_update_f32: the L2 kind has no Hausdorff term");
-  const size_t lds = geo_upd_lds_bytes(N, k, curv, two);
-  PC3D_REQUIRE(lds <= kGuLdsLimit, "pc3d_geoa3_update_f32: N=%d, k=%d need %zu bytes of LDS (limit %zu)", N, k, lds, kGuLdsLimit);
-  if (B == 0) return PC3D_OK;
-  PC3D_REQUIRE(x && ori && offset && g && m && v && cls && scale && pred && target && constrain && loss_rows && step &&
-                   search_step && lr && best_loss && best_attack && best_bs && best_step && iter_best_loss && iter_best_score,
-               "pc3d_geoa3_update_f32: null pointer");
-  PC3D_REQUIRE(dis_kind == 1 || nn_ao != nullptr, "pc3d_geoa3_update_f32: the Chamfer kind needs nn_ao");
-  PC3D_REQUIRE(!curv || (nn_ao && normal_ori && kappa_ori), "pc3d_geoa3_update_f32: the curvature term needs nn_ao, normal_ori and kappa_ori");
-  GeoUpdArgs a{};
-  a.x = x, a.ori = ori, a.offset = offset, a.g = g, a.m = m, a.v = v, a.N = N, a.K1 = k + 1;
-  a.nn_ao = nn_ao, a.nn_oa = nn_oa, a.knn_idx = knn_idx, a.normal_ori = normal_ori, a.kappa_ori = kappa_ori;
-  a.cls = cls, a.scale = scale, a.pred = pred, a.target = target, a.targeted = targeted, a.dis_kind = dis_kind;
-  a.gval = gval, a.w_dis = w_dis, a.w_hd = w_hd, a.w_curv = w_curv, a.constrain = constrain, a.loss_rows = loss_rows;
-  a.max_steps = max_steps, a.B = B, a.step = step, a.search_step = search_step, a.lr = lr, a.scheduler = scheduler;
-  a.best_loss = best_loss, a.best_attack = best_attack, a.best_bs = best_bs, a.best_step = best_step;
-  a.iter_best_loss = iter_best_loss, a.iter_best_score = iter_best_score, a.b1 = beta1, a.b2 = beta2, a.eps = (float)eps;
-  a.cc_linf = cc_linf, a.terms_out = terms_out, a.hd_arg_out = hd_arg_out, a.g_out = g_out;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(geoa3_update_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGuLdsLimit);
-    if (e != hipSuccess) {
-      set_error("pc3d_geoa3_update_f32: LDS opt-in failed: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-  }
-  hipLaunchKernelGGL(geoa3_update_kernel, dim3(B), dim3(kGuThreads), lds, as_stream(stream), a);
-  PC3D_LAUNCH_CHECK("pc3d_geoa3_update_f32");
-  return PC3D_OK;
+  return geo_upd_launch("pc3d_geoa3_update_f32", x, ori, offset, g, m, v, B, N, k, nn_ao, nn_oa, knn_idx, normal_ori, kappa_ori,
+                        cls, scale, pred, target, targeted, dis_kind, gval, w_dis, w_hd, w_curv, constrain, loss_rows, max_steps,
+                        step, search_step, lr, scheduler, best_loss, best_attack, best_bs, best_step, iter_best_loss,
+                        iter_best_score, beta1, beta2, eps, cc_linf, terms_out, hd_arg_out, g_out, nullptr, false, stream);
+}
+
+extern "C" int pc3d_geoa3_update_ragged_f32(float* x, const float* ori, float* offset, const float* g, float* m, float* v,
+                                            int B, int N, int k, const int32_t* nn_ao, const int32_t* nn_oa,
+                                            const int32_t* knn_idx, const float* normal_ori, const float* kappa_ori,
+                                            const float* cls, const float* scale, const int64_t* pred, const int64_t* target,
+                                            int targeted, int dis_kind, float gval, float w_dis, float w_hd, float w_curv,
+                                            float* constrain, float* loss_rows, int max_steps, int32_t* step,
+                                            const int32_t* search_step, double* lr, int scheduler, float* best_loss,
+                                            float* best_attack, int64_t* best_bs, int64_t* best_step, float* iter_best_loss,
+                                            int64_t* iter_best_score, double beta1, double beta2, double eps, float cc_linf,
+                                            float* terms_out, int32_t* hd_arg_out, float* g_out, const int32_t* lengths,
+                                            void* stream) {
+  return geo_upd_launch("pc3d_geoa3_update_ragged_f32", x, ori, offset, g, m, v, B, N, k, nn_ao, nn_oa, knn_idx, normal_ori,
+                        kappa_ori, cls, scale, pred, target, targeted, dis_kind, gval, w_dis, w_hd, w_curv, constrain, loss_rows,
+                        max_steps, step, search_step, lr, scheduler, best_loss, best_attack, best_bs, best_step, iter_best_loss,
+                        iter_best_score, beta1, beta2, eps, cc_linf, terms_out, hd_arg_out, g_out, lengths, true, stream);
 }

@@ -2011,12 +2011,16 @@ def geoa3_update_fits(N, k, curv=True, two_sided=True):
 def geoa3_update(x, ori, offset, g, m, v, step, search_step, lr, scale, cls, pred, target, targeted, constrain, loss_rows,
                  best_loss, best_attack, best_bs, best_step, iter_best_loss, iter_best_score, nn_ao=None, nn_oa=None,
                  knn_idx=None, normal_ori=None, kappa_ori=None, dis_kind="CD", gval=1.0, w_dis=1.0, w_hd=0.0, w_curv=0.0,
-                 scheduler=False, cc_linf=0.0, betas=(0.9, 0.999), eps=1e-8, terms_out=None, hd_arg_out=None, g_out=None):
+                 scheduler=False, cc_linf=0.0, betas=(0.9, 0.999), eps=1e-8, terms_out=None, hd_arg_out=None, g_out=None,
+                 lengths=None):
     """One GeoA3 iteration after the victim's passes and the searches, one launch, everything IN PLACE (see
     pc3d_geoa3_update_f32): record, terms, the gradient of gval * scale * constrain added to g, Adam on `offset`, the
     scheduler, lp_clip and x = ori + offset. Point tensors are contiguous float32 [B,3,N]; step (int32) and lr (float64) are
     PER-CLOUD words [B], search_step an int32 [1] word; nn_ao / nn_oa int32 [B,N], knn_idx int32 [B,N,k+1]. nn_oa None:
-    single-sided Chamfer; knn_idx None or w_curv == 0: no curvature term; dis_kind "L2" needs no search."""
+    single-sided Chamfer; knn_idx None or w_curv == 0: no curvature term; dis_kind "L2" needs no search.
+    lengths (int32 [B] on the device, default None: the dense launch, unchanged): cloud b counts lengths[b] points, N is the
+    capacity; its further rows are padding: none is loaded, x's take the new point 0, m / v / offset / g_out's stay
+    (pc3d_geoa3_update_ragged_f32). With a curvature term k + 1 <= lengths[b]."""
     _check(x, "x")
     if x.dim() != 3 or x.shape[1] != 3:
         raise ValueError(f"geoa3_update: x must be [B,3,N], got {tuple(x.shape)}")
@@ -2055,8 +2059,11 @@ def geoa3_update(x, ori, offset, g, m, v, step, search_step, lr, scale, cls, pre
     need("normal_ori", normal_ori, f32, (B, 3, N), optional=True), need("kappa_ori", kappa_ori, f32, (B, N), optional=True)
     need("terms_out", terms_out, f32, (5, B), optional=True), need("hd_arg_out", hd_arg_out, i32, (B,), optional=True)
     need("g_out", g_out, f32, (B, 3, N), optional=True)
+    name, extra = "pc3d_geoa3_update_f32", ()
+    if lengths is not None:
+        name, extra = "pc3d_geoa3_update_ragged_f32", (_lengths_arg("geoa3_update", lengths, B, dev),)
     with torch.cuda.device(dev):
-        _lib.call("pc3d_geoa3_update_f32", x.data_ptr(), ori.data_ptr(), offset.data_ptr(), g.data_ptr(), m.data_ptr(),
+        _lib.call(name, x.data_ptr(), ori.data_ptr(), offset.data_ptr(), g.data_ptr(), m.data_ptr(),
                   v.data_ptr(), B, N, int(k), _ptr(nn_ao), _ptr(nn_oa), _ptr(knn_idx), _ptr(normal_ori), _ptr(kappa_ori),
                   cls.data_ptr(), scale.data_ptr(), pred.data_ptr(), target.data_ptr(), 1 if targeted else 0,
                   GEOA3_DIS_KINDS[dis_kind] if isinstance(dis_kind, str) else int(dis_kind), float(np.float32(gval)),
@@ -2064,7 +2071,7 @@ def geoa3_update(x, ori, offset, g, m, v, step, search_step, lr, scale, cls, pre
                   int(loss_rows.shape[0]), step.data_ptr(), search_step.data_ptr(), lr.data_ptr(), 1 if scheduler else 0,
                   best_loss.data_ptr(), best_attack.data_ptr(), best_bs.data_ptr(), best_step.data_ptr(),
                   iter_best_loss.data_ptr(), iter_best_score.data_ptr(), float(betas[0]), float(betas[1]), float(eps),
-                  float(cc_linf), _ptr(terms_out), _ptr(hd_arg_out), _ptr(g_out), _stream())
+                  float(cc_linf), _ptr(terms_out), _ptr(hd_arg_out), _ptr(g_out), *extra, _stream())
     return x
 
 

@@ -1252,6 +1252,27 @@ int pc3d_geoa3_update_f32(float* x, const float* ori, float* offset, const float
                           double beta1, double beta2, double eps, float cc_linf, float* terms_out, int32_t* hd_arg_out,
                           float* g_out, void* stream);
 
+/* pc3d_geoa3_update_f32 on a batch of clouds of different sizes: cloud b counts L = lengths[b] points (int32 [B] on the
+ * device, read as data, clamped to [1, N]; must not be NULL). N stays the capacity — the row stride of every [B,3,N], [B,N]
+ * and [B,N,k+1] buffer and the size the LDS request and every check above are computed from. Every loop over points, every
+ * mean's divisor, the Hausdorff maximum, both reverse indices and every index clamp range over L with the dense launch's
+ * thread-to-point mapping and summation order: rows < L of every output, the cloud's words and its loss_rows column have
+ * the bits of pc3d_geoa3_update_f32 at N = L on that cloud alone. Rows >= L of x, g, m, v, offset, nn_ao, nn_oa, knn_idx,
+ * normal_ori, kappa_ori and ori are never loaded (they may hold NaN or any integer); those of m, v, offset and g_out are
+ * not written; x's take the NEW row 0 (the padding the victim's passes and the next searches rely on: an exact copy of
+ * row 0 loses every tie to index 0), and a record copies the iterate with its rows >= L set to its row 0 into best_attack.
+ * Precondition: k + 1 <= lengths[b] with a curvature term (the searches that fill knn_idx need as many points); whatever
+ * the buffers hold, the clamps keep every access inside them. */
+int pc3d_geoa3_update_ragged_f32(float* x, const float* ori, float* offset, const float* g, float* m, float* v, int B, int N,
+                                 int k, const int32_t* nn_ao, const int32_t* nn_oa, const int32_t* knn_idx,
+                                 const float* normal_ori, const float* kappa_ori, const float* cls, const float* scale,
+                                 const int64_t* pred, const int64_t* target, int targeted, int dis_kind, float gval,
+                                 float w_dis, float w_hd, float w_curv, float* constrain, float* loss_rows, int max_steps,
+                                 int32_t* step, const int32_t* search_step, double* lr, int scheduler, float* best_loss,
+                                 float* best_attack, int64_t* best_bs, int64_t* best_step, float* iter_best_loss,
+                                 int64_t* iter_best_score, double beta1, double beta2, double eps, float cc_linf,
+                                 float* terms_out, int32_t* hd_arg_out, float* g_out, const int32_t* lengths, void* stream);
+
 /* The point-adding attacks' iteration (attack/Gen3DAdv CWAdd / CWAddClusters) as ONE launch, one workgroup per sample:
  * the set distance adv -> ori from the search output (nn_d / nn_idx [B,A], pc3d_nn_f32), bookkeeping on it, total
  * gradient (g, the victim's gradient on the A added columns, + w[b] * d distance / d adv) and Adam without clip, written
