@@ -19,6 +19,7 @@ import torch.optim as optim
 
 from ... import graphed as _graphed
 from ... import ops
+from ... import ragged as _ragged
 from ... import streams as _streams
 from .CW_utils import adv_utils as _adv_utils
 from .CW_utils import clip_utils as _clip_utils
@@ -214,14 +215,7 @@ class CW:
         B, K = data.shape[:2]
         if K > ops.CW_UPDATE_MAX_POINTS:
             raise ValueError(f"CW.attack(lengths=...): Kmax={K} exceeds CW_UPDATE_MAX_POINTS={ops.CW_UPDATE_MAX_POINTS}")
-        if torch.is_tensor(lengths):
-            lengths = lengths.detach().cpu().numpy()
-        lens = np.asarray(lengths)
-        if lens.shape != (B,) or not np.issubdtype(lens.dtype, np.integer):
-            raise ValueError(f"CW.attack(lengths=...): lengths must be {B} ints, got shape {lens.shape} dtype {lens.dtype}")
-        if lens.min() < 1 or lens.max() > K:
-            raise ValueError(f"CW.attack(lengths=...): lengths must lie in [1, Kmax={K}], got [{lens.min()}, {lens.max()}]")
-        return lens.astype(np.int64)
+        return _ragged.check_lengths("CW.attack(lengths=...)", lengths, B, K)
 
     def _begin(self, data, target, lengths=None):
         """Upload + clean prediction (reference :63-89). Returns the state dict the iteration works on. lengths (checked by
@@ -280,10 +274,8 @@ class CW:
         elif st.get("lengths") is None:
             noise = torch.stack([torch.randn((3, K), generator=g) for g in st["gens"]])
         else:
-            # what a run of that cloud alone draws: (3, lengths[b]) from the sample's own generator
-            noise = torch.zeros((B, 3, K))
-            for b, (g, n) in enumerate(zip(st["gens"], st["lengths_host"])):
-                noise[b, :, :n] = torch.randn((3, n), generator=g)
+            noise = _ragged.per_cloud_draw(B, 3, K, st["lengths_host"],
+                                           lambda b, n: torch.randn((3, n), generator=st["gens"][b]))
         adv_data = st["ori"].clone().detach() + noise.to(dev) * 1e-7
         if st.get("lengths") is not None:
             ops.pad_ragged(adv_data, st["lengths"])
@@ -353,12 +345,9 @@ class CW:
         ori_data = st["ori"]
         with torch.no_grad():
             cur = st["adv"].detach()
-            # a ragged batch on a victim that declares fused_lengths: its towers are given the lengths and skip the padding
-            vlens = {}
-            if st.get("lengths") is not None and getattr(_graphed.unwrap(self.model), "fused_lengths", False):
-                vlens = dict(lengths=st["lengths"])
-            _, _, gx_model = self.model.fused_attack_grad(cur, st["target"], *fml, pred_out=st["pred"],
-                                                          step=st["step"], scale=st["ratio"] / st["B"], **vlens)
+            _, _, gx_model = self.model.fused_attack_grad(cur, st["target"], *fml, pred_out=st["pred"], step=st["step"],
+                                                          scale=st["ratio"] / st["B"],
+                                                          **_ragged.victim_kwargs(self.model, st.get("lengths")))
             nn_idx = None
             if dk == 2:
                 _, nn_idx = ops.nn_raw(cur, ori_data, True, True)
@@ -596,14 +585,6 @@ class CW:
         fail_idx = torch.from_numpy(st["lower_bound"] == 0.).to(self.device)
         return success_num, torch.where(fail_idx[:, None, None], st["input_val"], st["o_bestattack"])
 
-    def _trans_pred(self, model, o_bestattack, lens):
-        """The transfer model's prediction (:244-257). Ragged: on the padded batch when the model declares pad_invariant,
-        else cloud by cloud on its own [1,3,lengths[b]] slice (B forwards, once per attack)."""
-        if lens is None or getattr(_graphed.unwrap(model), "pad_invariant", False):
-            return torch.argmax(_graphed.logits_of(model(o_bestattack)), dim=1)
-        return torch.cat([torch.argmax(_graphed.logits_of(model(o_bestattack[b:b + 1, :, :n].contiguous())), dim=1)
-                          for b, n in enumerate(lens)])
-
     def _attack(self, data, target, lengths=None):
         """Attack on given data to target.
         Args:
@@ -632,7 +613,7 @@ class CW:
             shuffle_pred = torch.argmax(_graphed.logits_of(self.model(shuffled)), dim=1)
             self.shuffle_fail += int((~self._success(shuffle_pred, target)).sum().item())
             # Test transfer attack (:244-257)
-            trans_pred = self._trans_pred(self.trans_model, o_bestattack, lens)
+            trans_pred = _ragged.predict(self.trans_model, o_bestattack, lens)
             self.trans_fail += int((~self._success(trans_pred, target)).sum().item())
         if self.verbose:
             print('attack result: ', attack_pred.tolist(), 'shuffle result: ', shuffle_pred.tolist(),

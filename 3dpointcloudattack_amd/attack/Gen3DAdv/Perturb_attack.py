@@ -40,13 +40,7 @@ class CW(_CW):
         self._search(st)
         success_num, o_bestattack = self._outcome(st)
         with torch.no_grad():
-            if lens is None:
-                count_transfer_fails(self, o_bestattack, target)
-            else:
-                for name, attr in TRANSFER_MODELS:
-                    if getattr(self, attr) is not None:
-                        p = self._trans_pred(getattr(self, attr), o_bestattack, lens)
-                        setattr(self, name, getattr(self, name) + int((~self._success(p, target)).sum().item()))
+            count_transfer_fails(self, o_bestattack, target, lens)
             best_np = o_bestattack.double().cpu().numpy()
             if lens is None:
                 shuffled = rand_row(best_np.transpose((0, 2, 1)))

@@ -21,6 +21,7 @@ import torch.optim as optim
 
 from ... import graphed as _graphed
 from ... import ops
+from ... import ragged as _ragged
 from ... import streams as _streams
 
 from .knn_utils import knn_gather, knn_points
@@ -83,10 +84,8 @@ def _draw_offset(b, c, n, dev, cfg, gens, lens=None):
     lens (a ragged batch, with gens): sample i draws (c, lens[i]) values — what its run alone draws — into its first
     columns; the others stay 0. Without gens the draw is batch-shaped whatever the lengths."""
     if gens is not None and lens is not None:
-        o = torch.zeros(b, c, n)
-        for i, (g, ln) in enumerate(zip(gens, lens)):
-            o[i, :, :int(ln)] = torch.zeros(c, int(ln)).normal_(0., 1e-3, generator=g)
-        return o.to(dev)
+        return _ragged.per_cloud_draw(b, c, n, lens,
+                                      lambda i, ln: torch.zeros(c, ln).normal_(0., 1e-3, generator=gens[i])).to(dev)
     if gens is not None:
         return torch.stack([torch.zeros(c, n).normal_(0., 1e-3, generator=g) for g in gens]).to(dev)
     if getattr(cfg, "host_rng", False):
@@ -314,46 +313,20 @@ def _device_loop_state(plan, b, n, dev):
     s["oa_d"], s["oa_i"] = (torch.zeros((b, n), **f32), torch.zeros((b, n), **i32)) if plan["two"] else (None, None)
     s["knn_d"], s["knn_i"] = ((torch.zeros((b, n, k + 1), **f32), torch.zeros((b, n, k + 1), **i32))     # knn_i: also the search's hint
                               if plan["curv"] else (None, None))
+    lens = lens_host = None
     if plan.get("ragged"):
-        # the lengths are DATA of the captured launches: another call's lengths replay the same graphs. lens_host: the host
-        # copy the search wrapper checks (filled in place by every call).
-        s["lens"] = torch.full((b,), n, **i32)
-        s["lens_host"] = np.full((b,), n, dtype=np.int64)
-        vlens = dict(lengths=s["lens"]) if getattr(victim, "fused_lengths", False) else {}
-
-        def body():
-            # the dense chain, launch for launch: the victim's passes — given the lengths when the victim declares
-            # fused_lengths (its towers then skip the padding), else on the padded batch (pad_invariant: the padding rows'
-            # gradient is exactly zero either way) —, the loss launch, both nearest-neighbour searches unchanged (the padding
-            # rows of ori and of the iterate are copies of their row 0 and lose every tie to it), the self-kNN search over
-            # every cloud's own points, the ragged update, which pads the new iterate
-            with torch.no_grad():
-                logits, ctx = _pointnet.fused_forward(victim, s["x"], **vlens)
-                _, _, cls, g_logits = ops.cls_loss(logits, s["target"], plan["kind"], plan["kappa"], scale=plan["gval"],
-                                                   pred_out=s["pred"])
-                gx = _pointnet.fused_input_grad(ctx, g_logits)
-                if need_ao:
-                    ops.nn_search_into(s["x"], s["ori"], s["ao_d"], s["ao_i"])
-                if plan["two"]:
-                    ops.nn_search_into(s["ori"], s["x"], s["oa_d"], s["oa_i"])
-                if plan["curv"]:
-                    ops.knn_search_into(s["x"], s["knn_d"], s["knn_i"], lengths=s["lens"], lengths_host=s["lens_host"])
-                ops.geoa3_update(s["x"], s["ori"], s["offset"], gx, s["m"], s["v"], s["step"], s["search"], s["lr"], s["scale"],
-                                 cls, s["pred"], s["target"], plan["targeted"], s["constrain"], s["loss_rows"], s["best_loss"],
-                                 s["best_attack"], s["best_bs"], s["best_step"], s["iter_best_loss"], s["iter_best_score"],
-                                 nn_ao=s["ao_i"], nn_oa=s["oa_i"], knn_idx=s["knn_i"],
-                                 normal_ori=s["normal"] if plan["curv"] else None,
-                                 kappa_ori=s["kappa_ori"] if plan["curv"] else None, dis_kind=plan["dis_kind"],
-                                 gval=plan["gval"], w_dis=plan["w_dis"], w_hd=plan["w_hd"], w_curv=plan["w_curv"],
-                                 scheduler=plan["scheduler"], cc_linf=plan["cc_linf"], lengths=s["lens"])
-
-        return cache.put(key, _graphed.DeviceLoop(key, dev, owners=(victim,), counts=(1, LOOP_BLOCK), warmup=2, body=body,
-                                                  bufs=s))
+        # the lengths are DATA of the captured launches: another call's lengths replay the same graphs (_run_device_loop
+        # fills both buffers in place)
+        lens, lens_host = s["lens"], s["lens_host"] = _ragged.loop_lengths(b, n, dev)
+    vlens = _ragged.victim_kwargs(victim, lens)
 
     def body():
-        # one chain on one stream: the victim's passes around the loss launch, the searches, the update
+        # one chain on one stream: the victim's passes around the loss launch, the searches, the update. Ragged (lens: the
+        # lengths, else None and every launch is the dense one): the same chain, launch for launch — both nearest-neighbour
+        # searches unchanged (the padding rows of ori and of the iterate are copies of their row 0 and lose every tie to
+        # it), the self-kNN search over every cloud's own points, the ragged update, which pads the new iterate
         with torch.no_grad():
-            logits, ctx = _pointnet.fused_forward(victim, s["x"])
+            logits, ctx = _pointnet.fused_forward(victim, s["x"], **vlens)
             _, _, cls, g_logits = ops.cls_loss(logits, s["target"], plan["kind"], plan["kappa"], scale=plan["gval"],
                                                pred_out=s["pred"])
             gx = _pointnet.fused_input_grad(ctx, g_logits)
@@ -362,7 +335,7 @@ def _device_loop_state(plan, b, n, dev):
             if plan["two"]:
                 ops.nn_search_into(s["ori"], s["x"], s["oa_d"], s["oa_i"])
             if plan["curv"]:
-                ops.knn_search_into(s["x"], s["knn_d"], s["knn_i"])
+                ops.knn_search_into(s["x"], s["knn_d"], s["knn_i"], lengths=lens, lengths_host=lens_host)
             ops.geoa3_update(s["x"], s["ori"], s["offset"], gx, s["m"], s["v"], s["step"], s["search"], s["lr"], s["scale"],
                              cls, s["pred"], s["target"], plan["targeted"], s["constrain"], s["loss_rows"], s["best_loss"],
                              s["best_attack"], s["best_bs"], s["best_step"], s["iter_best_loss"], s["iter_best_score"],
@@ -370,7 +343,7 @@ def _device_loop_state(plan, b, n, dev):
                              normal_ori=s["normal"] if plan["curv"] else None,
                              kappa_ori=s["kappa_ori"] if plan["curv"] else None, dis_kind=plan["dis_kind"],
                              gval=plan["gval"], w_dis=plan["w_dis"], w_hd=plan["w_hd"], w_curv=plan["w_curv"],
-                             scheduler=plan["scheduler"], cc_linf=plan["cc_linf"])
+                             scheduler=plan["scheduler"], cc_linf=plan["cc_linf"], lengths=lens)
 
     return cache.put(key, _graphed.DeviceLoop(key, dev, owners=(victim,), counts=(1, LOOP_BLOCK), warmup=2, body=body, bufs=s))
 
@@ -423,8 +396,7 @@ def _run_device_loop(plan, pc_ori, normal_ori, kappa_ori, target, gt_target, cfg
 
     with torch.no_grad():
         if lens is not None:
-            s["lens_host"][:] = lens
-            s["lens"].copy_(torch.from_numpy(lens.astype(np.int32)))
+            _ragged.set_loop_lengths(s, lens)
         s["ori"].copy_(pc_ori)
         s["target"].copy_(target if targeted else gt_target)
         if plan["curv"]:
@@ -457,11 +429,7 @@ def _finish(transfer, best_attack, target, targeted, best_loss, best_attack_step
             if m is None:
                 fails.append(None)
                 continue
-            if lens is not None and not getattr(_graphed.unwrap(m), "pad_invariant", False):
-                lab = torch.cat([torch.argmax(_graphed.logits_of(m(best_attack[b:b + 1, :, :int(ln)].float().contiguous())), dim=1)
-                                 for b, ln in enumerate(lens)])
-            else:
-                lab = torch.argmax(_graphed.logits_of(m(best_attack.float())), dim=1)
+            lab = _ragged.predict(m, best_attack.float(), lens)
             fails.append(int(((lab == target) if not targeted else (lab != target)).sum().item()))
     geoA3_attack.last_transfer_fails = dict(zip(("pt", "ptm", "pts", "dgcnn", "cur"), fails))
 
@@ -482,20 +450,14 @@ def _ragged_lengths(net, pc, cfg, lengths):
     if not torch.is_tensor(pc) or pc.dim() != 3 or pc.shape[2] != 3:
         raise ValueError(f"{who}: pc must be [B, Kmax, 3], got {tuple(pc.shape) if torch.is_tensor(pc) else type(pc).__name__}")
     b, n = int(pc.shape[0]), int(pc.shape[1])
-    if torch.is_tensor(lengths):
-        lengths = lengths.detach().cpu().numpy()
-    lens = np.asarray(lengths)
-    if lens.shape != (b,) or not np.issubdtype(lens.dtype, np.integer):
-        raise ValueError(f"{who}: lengths must be {b} ints, got shape {lens.shape} dtype {lens.dtype}")
     curv = cfg.curv_loss_weight != 0
     k = int(cfg.curv_loss_knn) if curv else 0
     two = cfg.dis_loss_type == 'CD' and not cfg.is_cd_single_side
     if not ops.geoa3_update_fits(n, k, curv, two):
         raise ValueError(f"{who}: Kmax={n} with k={k} curvature neighbours exceeds what pc3d_geoa3_update_f32 holds "
                          f"(GEOA3_LOOP_MAX_POINTS={ops.GEOA3_LOOP_MAX_POINTS}, 160 KiB of LDS)")
-    low = max(4, k + 1)           # 4: the normals' k = 3 search
-    if b and (lens.min() < low or lens.max() > n):
-        raise ValueError(f"{who}: lengths must lie in [max(4, curv_loss_knn + 1)={low}, Kmax={n}], got [{lens.min()}, {lens.max()}]")
+    # 4: the normals' k = 3 search
+    lens = _ragged.check_lengths(who, lengths, b, n, max(4, k + 1), "max(4, curv_loss_knn + 1)", empty_ok=True)
     victim = _graphed.unwrap(net)
     if not getattr(victim, "pad_invariant", False):
         raise ValueError(f"{who}: the victim {type(victim).__name__} does not declare pad_invariant")
@@ -506,7 +468,7 @@ def _ragged_lengths(net, pc, cfg, lengths):
         raise ValueError(f"{who}: the device loop refuses this victim or configuration (_device_loop_plan: a PointNetCls in "
                          "eval mode, CE / Margin, Chamfer or L2 without Hausdorff, Adam, no uniform term, no partial "
                          "variable / jitter / gradient projection / sub-sampling)")
-    return lens.astype(np.int64)
+    return lens
 
 
 def geoA3_attack(net, pt_model, ptm_model, pts_model, dgcnn_model, cur_model, pc, label, cfg, i, loader_len,

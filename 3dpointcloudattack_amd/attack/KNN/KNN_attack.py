@@ -17,6 +17,7 @@ import torch.optim as optim
 
 from ... import graphed as _graphed
 from ... import ops
+from ... import ragged as _ragged
 from ... import streams as _streams
 from ..CW.CW_utils import adv_utils as _adv_utils
 from ..CW.CW_utils import clip_utils as _clip_utils
@@ -43,11 +44,7 @@ def count_transfer_fails(attack, result, target, lens=None):
         m = getattr(attack, attr)
         if m is None:
             continue
-        if lens is None or getattr(_graphed.unwrap(m), "pad_invariant", False):
-            p = torch.argmax(_graphed.logits_of(m(result)), dim=1)
-        else:
-            p = torch.cat([torch.argmax(_graphed.logits_of(m(result[b:b + 1, :, :int(n)].contiguous())), dim=1)
-                           for b, n in enumerate(lens)])
+        p = _ragged.predict(m, result, lens)
         setattr(attack, name, getattr(attack, name) + int((~attack._success(p, target)).sum().item()))
 
 
@@ -137,81 +134,61 @@ class CWKNN:
         who = "CWKNN.attack(lengths=...)"
         if not self.device_loop:
             raise ValueError(f"{who}: device_loop=False has no ragged pass")
-        if self.device.type != "cuda":
-            raise ValueError(f"{who}: the device {self.device} has no device loop")
-        victim = _graphed.unwrap(self.model)
-        if not getattr(victim, "pad_invariant", False) or not hasattr(victim, "fused_attack_grad"):
-            raise ValueError(f"{who}: the victim {type(victim).__name__} does not declare pad_invariant or lacks the fused "
-                             "entry points (fused_attack_grad)")
-        if _adv_utils.own_adv_kind(self.adv_func) is None:
-            raise ValueError(f"{who}: adv_func {type(self.adv_func).__name__} is not one of this package's adversarial functors")
-        dp = self._dist_plan()
-        if dp is None:
-            raise ValueError(f"{who}: dist_func {type(self.dist_func).__name__} is neither ChamferkNNDist nor ChamferDist "
-                             "with 'adv2ori'")
-        if self._fused_clip() is None:
-            raise ValueError(f"{who}: clip_func {type(self.clip_func).__name__} is neither ProjectInnerClipLinf nor "
-                             "ClipPointsLinf (or fused=False)")
         if data.dim() != 3 or data.shape[2] not in (3, 6):
             raise ValueError(f"{who}: data must be [B, Kmax, 3 or 6], got {tuple(data.shape)}")
         B, K = data.shape[:2]
-        if K > ops.KNN_LOOP_MAX_POINTS:
-            raise ValueError(f"{who}: Kmax={K} exceeds KNN_LOOP_MAX_POINTS={ops.KNN_LOOP_MAX_POINTS}")
-        if dp[3] is not None and not 1 <= dp[0] <= 63:
-            raise ValueError(f"{who}: ChamferkNNDist's k={dp[0]} out of range [1, 63]")
-        if next(victim.parameters()).device.type != "cuda":
-            raise ValueError(f"{who}: the victim's parameters are not on the GPU")
-        if torch.is_tensor(lengths):
-            lengths = lengths.detach().cpu().numpy()
-        lens = np.asarray(lengths)
-        if lens.shape != (B,) or not np.issubdtype(lens.dtype, np.integer):
-            raise ValueError(f"{who}: lengths must be {B} ints, got shape {lens.shape} dtype {lens.dtype}")
-        low = max(1, dp[0] + 1)
-        if lens.min() < low or lens.max() > K:
-            raise ValueError(f"{who}: lengths must lie in [max(1, k + 1)={low}, Kmax={K}], got [{lens.min()}, {lens.max()}]")
-        return lens.astype(np.int64)
+        plan = self._device_loop_plan(B, K, data.shape[2] == 6, ragged=True)
+        if isinstance(plan, str):
+            raise ValueError(f"{who}: {plan}")
+        return _ragged.check_lengths(who, lengths, B, K, max(1, plan["k"] + 1), "max(1, k + 1)")
 
-    def _ragged_plan(self, B, has_normal):
-        """The constants of the ragged device loop (_ragged_lengths has checked everything). The two scales are per-cloud
-        device data, prepared by every call from its lengths: the plan, and so the loop's key, holds the functor's weights
-        and the size of the whole batch in their place, and the flag."""
-        k, alpha, w1, w2 = self._dist_plan()
-        fc = self._fused_clip()
-        G = int(self.global_batch) if self.global_batch else B
-        return dict(victim=_graphed.unwrap(self.model), kind=_adv_utils.own_adv_kind(self.adv_func), k=k, alpha=alpha, w1=w1,
-                    w2=w2, G=G, ragged=True, budget=fc[0], clip_mode="project_clip" if fc[1] else "clip", scale=1.0 / G,
-                    has_normal=bool(has_normal and fc[1]))
-
-    def _device_loop_plan(self, B, K, has_normal):
-        """The constants of the device loop when it applies, else None: a GPU victim with fused_attack_grad (the two
+    def _device_loop_plan(self, B, K, has_normal, ragged=False):
+        """The one gate of the device loop: its constants when it applies — a GPU victim with fused_attack_grad (the two
         PointNetCls variants), an adversarial functor the CW loop maps to ops.LOSS_KINDS, ChamferkNNDist / ChamferDist
-        with 'adv2ori', a clip functor _fused_clip() recognises, and a cloud the update kernel holds."""
+        with 'adv2ori', a clip functor _fused_clip() recognises, and a cloud the update kernel holds. Where it does not,
+        the dense gate returns None (the caller takes the usual path) and the ragged one the reason, a string (the caller
+        raises it). ragged: the victim must declare pad_invariant, and the two scales are per-cloud device data that
+        every call prepares from its lengths, so the plan, and with it the loop's key, holds the functor's weights and
+        the size of the whole batch in their place, and the flag."""
         victim = _graphed.unwrap(self.model)
-        fc = self._fused_clip()
-        if fc is None or self.device.type != "cuda" or not hasattr(victim, "fused_attack_grad") or K > ops.KNN_LOOP_MAX_POINTS:
-            return None
-        if next(victim.parameters()).device.type != "cuda":
-            return None
+        fc, dp = self._fused_clip(), self._dist_plan()
         kind = _adv_utils.own_adv_kind(self.adv_func)          # the CW loop's mapping of the adversarial functors
-        if kind is None:
-            return None
-        df = self.dist_func
+        if self.device.type != "cuda":
+            why = f"the device {self.device} has no device loop"
+        elif not hasattr(victim, "fused_attack_grad") or (ragged and not getattr(victim, "pad_invariant", False)):
+            why = (f"the victim {type(victim).__name__} does not declare pad_invariant or lacks the fused entry points "
+                   "(fused_attack_grad)")
+        elif kind is None:
+            why = f"adv_func {type(self.adv_func).__name__} is not one of this package's adversarial functors"
+        elif dp is None:
+            why = f"dist_func {type(self.dist_func).__name__} is neither ChamferkNNDist nor ChamferDist with 'adv2ori'"
+        elif fc is None:
+            why = (f"clip_func {type(self.clip_func).__name__} is neither ProjectInnerClipLinf nor ClipPointsLinf "
+                   "(or fused=False)")
+        elif K > ops.KNN_LOOP_MAX_POINTS:
+            why = f"Kmax={K} exceeds KNN_LOOP_MAX_POINTS={ops.KNN_LOOP_MAX_POINTS}"
+        elif dp[3] is not None and not 1 <= dp[0] <= 63:
+            why = f"ChamferkNNDist's k={dp[0]} out of range [1, 63]"
+        elif dp[0] + 1 > K:
+            why = f"ChamferkNNDist's k + 1 = {dp[0] + 1} neighbours of Kmax={K} points"
+        elif next(victim.parameters()).device.type != "cuda":
+            why = "the victim's parameters are not on the GPU"
+        else:
+            why = None
+        if why is not None:
+            return why if ragged else None
+        k, alpha, w1, w2 = dp
         # The batch mean and the shard ratio together are 1 / G, G the size of the whole batch: the constants are prepared
         # from G itself, so a sample's bits depend on neither the shard it runs in nor that shard's size. Without
         # global_batch (G = B) these are the float32 steps of the direct path's per_sample_terms / scaled_gvec.
         G = int(self.global_batch) if self.global_batch else B
-        up = np.float32(K)
-        if type(df) is _dist_utils.ChamferkNNDist and df.chamfer_dist.method == 'adv2ori':
-            k, alpha = int(df.knn_dist.k), float(df.knn_dist.alpha)
-            if not (1 <= k <= 63 and k + 1 <= K):
-                return None
-            c_ch, c_knn = ops.knn_attack_scales(K, k, G, up * np.float32(df.w1), up * np.float32(df.w2))
-        elif type(df) is _dist_utils.ChamferDist and df.method == 'adv2ori':
-            k, alpha = 0, 0.0
-            c_ch, c_knn = ops.knn_attack_scales(K, 0, G, up, None)
+        if ragged:
+            scales = dict(w1=w1, w2=w2, G=G, ragged=True)
         else:
-            return None
-        return dict(victim=victim, kind=kind, k=k, alpha=alpha, c_ch=float(c_ch), c_knn=float(c_knn), budget=fc[0],
+            up = np.float32(K)
+            c_ch, c_knn = ops.knn_attack_scales(K, k, G, up * np.float32(w1), None if w2 is None else up * np.float32(w2))
+            scales = dict(c_ch=float(c_ch), c_knn=float(c_knn))
+        return dict(victim=victim, kind=kind, k=k, alpha=alpha, **scales, budget=fc[0],
                     clip_mode="project_clip" if fc[1] else "clip", scale=1.0 / G, has_normal=bool(has_normal and fc[1]))
 
     def _device_loop_state(self, plan, B, K):
@@ -234,48 +211,33 @@ class CWKNN:
         pred = torch.zeros((B,), dtype=torch.long, device=dev)
         target = torch.zeros((B,), dtype=torch.long, device=dev)
         kind, kappa = plan["kind"]
+        bufs = dict(adv=adv, ori=ori, normal=normal, target=target, plan=plan, m=m, v=v, step=step, pred=pred, knn_d=knn_d,
+                    knn_idx=knn_idx, nn_d=nn_d, nn_idx=nn_idx)
+        lens = lens_host = None
+        c_ch, c_knn = plan.get("c_ch"), plan.get("c_knn")
         if plan.get("ragged"):
             # the lengths and the per-cloud scales are DATA of the captured launches: another call's lengths replay the
-            # same graphs. lens_host: the host copy the search wrapper checks (filled in place by every call).
-            lens = torch.ones((B,), dtype=torch.int32, device=dev)
-            lens_host = np.ones((B,), dtype=np.int64)
+            # same graphs (_run_device_loop fills them in place)
+            lens, lens_host = _ragged.loop_lengths(B, K, dev)
             c_ch, c_knn = torch.zeros((B,), **f32), torch.zeros((B,), **f32)
-            vlens = dict(lengths=lens) if getattr(_graphed.unwrap(victim), "fused_lengths", False) else {}
-
-            def body():
-                # the dense chain, launch for launch: the victim's passes — given the lengths when the victim declares
-                # fused_lengths (its towers then skip the padding), else on the padded batch (pad_invariant: the padding
-                # rows' gradient is exactly zero either way) —, the self-kNN search over every cloud's own points, the
-                # adv -> ori search unchanged (ori's padding rows are copies of its point 0 and lose every tie to it), the
-                # ragged update
-                with torch.no_grad():
-                    _, _, gx = victim.fused_attack_grad(adv, target, kind, kappa, pred_out=pred, step=step, scale=plan["scale"],
-                                                        **vlens)
-                    if k:
-                        ops.knn_search_into(adv, knn_d, knn_idx, lengths=lens, lengths_host=lens_host)
-                    ops.nn_search_into(adv, ori, nn_d, nn_idx)
-                    ops.knn_attack_update(adv, ori, gx, m, v, step, lr, knn_d, knn_idx, nn_idx, c_ch, c_knn, plan["alpha"],
-                                          plan["budget"], plan["clip_mode"], normal, lengths=lens)
-
-            bufs = dict(adv=adv, ori=ori, normal=normal, target=target, plan=plan, m=m, v=v, step=step, pred=pred,
-                        knn_d=knn_d, knn_idx=knn_idx, nn_d=nn_d, nn_idx=nn_idx, lens=lens, lens_host=lens_host, c_ch=c_ch,
-                        c_knn=c_knn)
-            return self._loop_cache.put(key, _graphed.DeviceLoop(key, dev, owners=(victim,), counts=(1, self.LOOP_BLOCK),
-                                                                 warmup=2, body=body, bufs=bufs))
+            bufs.update(lens=lens, lens_host=lens_host, c_ch=c_ch, c_knn=c_knn)
+        vlens = _ragged.victim_kwargs(victim, lens)
 
         def body():
             # one chain on one stream: the victim's passes (the classifier tail advances the step word), the self-kNN
-            # search hinted by its own last result, the adv -> ori search, the update
+            # search hinted by its own last result, the adv -> ori search, the update. Ragged (lens: the lengths, else None
+            # and every launch is the dense one): the same chain, launch for launch — the self-kNN search over every cloud's
+            # own points, the adv -> ori search unchanged (ori's padding rows are copies of its point 0 and lose every tie
+            # to it), the ragged update
             with torch.no_grad():
-                _, _, gx = victim.fused_attack_grad(adv, target, kind, kappa, pred_out=pred, step=step, scale=plan["scale"])
+                _, _, gx = victim.fused_attack_grad(adv, target, kind, kappa, pred_out=pred, step=step, scale=plan["scale"],
+                                                    **vlens)
                 if k:
-                    ops.knn_search_into(adv, knn_d, knn_idx)
+                    ops.knn_search_into(adv, knn_d, knn_idx, lengths=lens, lengths_host=lens_host)
                 ops.nn_search_into(adv, ori, nn_d, nn_idx)
-                ops.knn_attack_update(adv, ori, gx, m, v, step, lr, knn_d, knn_idx, nn_idx, plan["c_ch"],
-                                      plan["c_knn"], plan["alpha"], plan["budget"], plan["clip_mode"], normal)
+                ops.knn_attack_update(adv, ori, gx, m, v, step, lr, knn_d, knn_idx, nn_idx, c_ch, c_knn, plan["alpha"],
+                                      plan["budget"], plan["clip_mode"], normal, lengths=lens)
 
-        bufs = dict(adv=adv, ori=ori, normal=normal, target=target, plan=plan, m=m, v=v, step=step, pred=pred, knn_d=knn_d,
-                    knn_idx=knn_idx, nn_d=nn_d, nn_idx=nn_idx)
         return self._loop_cache.put(key, _graphed.DeviceLoop(key, dev, owners=(victim,), counts=(1, self.LOOP_BLOCK),
                                                              warmup=2, body=body, bufs=bufs))
 
@@ -288,8 +250,7 @@ class CWKNN:
         if lens is not None:
             # what a run of every cloud alone prepares from its own point count (ops.knn_attack_scales_ragged)
             c_ch, c_knn = ops.knn_attack_scales_ragged(lens, plan["k"], plan["G"], plan["w1"], plan["w2"])
-            c["lens_host"][:] = lens
-            c["lens"].copy_(torch.from_numpy(lens.astype(np.int32)))
+            _ragged.set_loop_lengths(c, lens)
             c["c_ch"].copy_(torch.from_numpy(c_ch)), c["c_knn"].copy_(torch.from_numpy(c_knn))
 
         def rewind():
@@ -372,10 +333,7 @@ class CWKNN:
         if gens is None or lens is None:
             noise = torch.randn((B, 3, K)) if gens is None else torch.stack([torch.randn((3, K), generator=g) for g in gens])
         else:
-            # what a run of that cloud alone draws: (3, lengths[b]) from the sample's own generator
-            noise = torch.zeros((B, 3, K))
-            for b, (g, n) in enumerate(zip(gens, lens)):
-                noise[b, :, :int(n)] = torch.randn((3, int(n)), generator=g)
+            noise = _ragged.per_cloud_draw(B, 3, K, lens, lambda b, n: torch.randn((3, n), generator=gens[b]))
         adv_data = ori_data.clone().detach() + noise.to(dev) * 1e-7
         if lens is not None:
             ops.pad_ragged(adv_data, lens_dev)
@@ -385,16 +343,12 @@ class CWKNN:
             opt = optim.Adam([adv_data], lr=self.attack_lr, weight_decay=0.)
         else:
             exp_avg, exp_avg_sq = torch.zeros_like(adv_data), torch.zeros_like(adv_data)
-        if lens is not None:
-            plan = self._ragged_plan(B, normal is not ori_data)
+        # (with lens, _ragged_lengths has asked the gate already: a plan, never a reason)
+        plan = self._device_loop_plan(B, K, normal is not ori_data, ragged=lens is not None) if self.device_loop else None
+        if plan is not None:
             self.last_path = "device_loop"
             self._run_device_loop(plan, adv_data, ori_data, normal, target, lens)
             return self._finish(adv_data, target, B, lens)
-        plan = self._device_loop_plan(B, K, normal is not ori_data) if self.device_loop else None
-        if plan is not None:
-            self.last_path = "device_loop"
-            self._run_device_loop(plan, adv_data, ori_data, normal, target)
-            return self._finish(adv_data, target, B)
         ori_t = ori_data.transpose(1, 2).contiguous()
         # Own functors on both sides: the loss is never assembled. Each functor hands back its per-sample terms with
         # d loss / d term built in (per_sample / per_sample_terms: the batch means, `* K`, the functor's own weights and the

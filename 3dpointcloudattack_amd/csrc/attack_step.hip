@@ -276,6 +276,47 @@ __global__ __launch_bounds__(256) void pad_ragged_kernel(PtsViewMut x, const int
 
 using namespace pc3d;
 
+// PER follows K, not the lengths: they are device data, and one captured launch serves every binary step
+template <bool RAGGED>
+static void cw_update_per(const typename UpdateArgsOf<RAGGED>::type& u, int B, int K, void* stream) {
+  if (K <= 1024) hipLaunchKernelGGL((cw_update_kernel<1, RAGGED>), dim3(B), dim3(1024), 0, as_stream(stream), u);
+  else if (K <= 2048) hipLaunchKernelGGL((cw_update_kernel<2, RAGGED>), dim3(B), dim3(1024), 0, as_stream(stream), u);
+  else if (K <= 4096) hipLaunchKernelGGL((cw_update_kernel<4, RAGGED>), dim3(B), dim3(1024), 0, as_stream(stream), u);
+  else hipLaunchKernelGGL((cw_update_kernel<8, RAGGED>), dim3(B), dim3(1024), 0, as_stream(stream), u);
+}
+
+// the checks, the argument block and the launch of both entries; ragged false: the dense kernel, lengths unused
+static int cw_update_launch(const char* nm, float* adv, int64_t a_bs, int64_t a_ps, int64_t a_cs, const float* ori,
+                            int64_t o_bs, int64_t o_ps, int64_t o_cs, int B, int K, const int64_t* pred,
+                            const int64_t* label, int untarget, float* bestdist, int64_t* bestscore, float* o_bestdist,
+                            int64_t* o_bestscore, float* o_bestattack, float* input_val, float* dist_val, const float* g,
+                            int64_t g_bs, int64_t g_ps, int64_t g_cs, float* m, float* v, double lr, double beta1,
+                            double beta2, double eps, float budget, const int32_t* step_dev, int step_host, int dist_kind,
+                            const float* w, const int32_t* nn_idx, const int32_t* lengths, bool ragged, void* stream) {
+  PC3D_REQUIRE(B >= 0 && K >= 1 && K <= 8192, "%s: bad sizes B=%d K=%d (K <= 8192)", nm, B, K);
+  PC3D_REQUIRE(step_dev != nullptr || step_host >= 1, "%s: step_host must be >= 1 without a device counter", nm);
+  PC3D_REQUIRE(dist_kind >= 0 && dist_kind <= 2, "%s: dist_kind=%d not in {0,1,2}", nm, dist_kind);
+  if (B == 0) return PC3D_OK;
+  PC3D_REQUIRE(adv && ori && (!ragged || lengths) && pred && label && bestdist && bestscore && o_bestdist && o_bestscore &&
+                   o_bestattack && g && m && v,
+               "%s: null pointer", nm);
+  PC3D_REQUIRE(dist_kind == 0 || w != nullptr, "%s: distance term needs the weights w", nm);
+  PC3D_REQUIRE(dist_kind != 2 || nn_idx != nullptr, "%s: Chamfer term needs nn_idx", nm);
+  RaggedUpdateArgs u{};
+  // o_bestattack / input_val / m / v share adv's layout
+  u.bk = BookArgs{{adv, a_bs, a_ps, a_cs}, {ori, o_bs, o_ps, o_cs}, K, pred, label, untarget, bestdist, bestscore,
+                  o_bestdist, o_bestscore, {o_bestattack, a_bs, a_ps, a_cs}, {input_val, a_bs, a_ps, a_cs}, dist_val,
+                  nullptr};
+  u.st = StepArgs{{adv, a_bs, a_ps, a_cs}, {g, g_bs, g_ps, g_cs}, {m, a_bs, a_ps, a_cs}, {v, a_bs, a_ps, a_cs},
+                  {ori, o_bs, o_ps, o_cs}, K, B, lr, beta1, beta2, (float)eps, budget, step_dev, step_host, dist_kind, w,
+                  nullptr, nn_idx};
+  u.lengths = lengths;
+  if (!ragged) cw_update_per<false>(u, B, K, stream);
+  else cw_update_per<true>(u, B, K, stream);
+  PC3D_LAUNCH_CHECK(nm);
+  return PC3D_OK;
+}
+
 extern "C" int pc3d_cw_update_f32(float* adv, int64_t a_bs, int64_t a_ps, int64_t a_cs,
                                   const float* ori, int64_t o_bs, int64_t o_ps, int64_t o_cs, int B, int K,
                                   const int64_t* pred, const int64_t* label, int untarget,
@@ -285,28 +326,9 @@ extern "C" int pc3d_cw_update_f32(float* adv, int64_t a_bs, int64_t a_ps, int64_
                                   double lr, double beta1, double beta2, double eps, float budget,
                                   const int32_t* step_dev, int step_host, int dist_kind, const float* w,
                                   const int32_t* nn_idx, void* stream) {
-  PC3D_REQUIRE(B >= 0 && K >= 1 && K <= 8192, "pc3d_cw_update_f32: bad sizes B=%d K=%d (K <= 8192)", B, K);
-  PC3D_REQUIRE(step_dev != nullptr || step_host >= 1, "pc3d_cw_update_f32: step_host must be >= 1 without a device counter");
-  PC3D_REQUIRE(dist_kind >= 0 && dist_kind <= 2, "pc3d_cw_update_f32: dist_kind=%d not in {0,1,2}", dist_kind);
-  if (B == 0) return PC3D_OK;
-  PC3D_REQUIRE(adv && ori && pred && label && bestdist && bestscore && o_bestdist && o_bestscore && o_bestattack && g && m && v,
-               "pc3d_cw_update_f32: null pointer");
-  PC3D_REQUIRE(dist_kind == 0 || w != nullptr, "pc3d_cw_update_f32: distance term needs the weights w");
-  PC3D_REQUIRE(dist_kind != 2 || nn_idx != nullptr, "pc3d_cw_update_f32: Chamfer term needs nn_idx");
-  UpdateArgs u{};
-  // o_bestattack / input_val / m / v share adv's layout
-  u.bk = BookArgs{{adv, a_bs, a_ps, a_cs}, {ori, o_bs, o_ps, o_cs}, K, pred, label, untarget, bestdist, bestscore,
-                  o_bestdist, o_bestscore, {o_bestattack, a_bs, a_ps, a_cs}, {input_val, a_bs, a_ps, a_cs}, dist_val,
-                  nullptr};
-  u.st = StepArgs{{adv, a_bs, a_ps, a_cs}, {g, g_bs, g_ps, g_cs}, {m, a_bs, a_ps, a_cs}, {v, a_bs, a_ps, a_cs},
-                  {ori, o_bs, o_ps, o_cs}, K, B, lr, beta1, beta2, (float)eps, budget, step_dev, step_host, dist_kind, w,
-                  nullptr, nn_idx};
-  if (K <= 1024) hipLaunchKernelGGL((cw_update_kernel<1, false>), dim3(B), dim3(1024), 0, as_stream(stream), u);
-  else if (K <= 2048) hipLaunchKernelGGL((cw_update_kernel<2, false>), dim3(B), dim3(1024), 0, as_stream(stream), u);
-  else if (K <= 4096) hipLaunchKernelGGL((cw_update_kernel<4, false>), dim3(B), dim3(1024), 0, as_stream(stream), u);
-  else hipLaunchKernelGGL((cw_update_kernel<8, false>), dim3(B), dim3(1024), 0, as_stream(stream), u);
-  PC3D_LAUNCH_CHECK("pc3d_cw_update_f32");
-  return PC3D_OK;
+  return cw_update_launch("pc3d_cw_update_f32", adv, a_bs, a_ps, a_cs, ori, o_bs, o_ps, o_cs, B, K, pred, label, untarget,
+                          bestdist, bestscore, o_bestdist, o_bestscore, o_bestattack, input_val, dist_val, g, g_bs, g_ps, g_cs,
+                          m, v, lr, beta1, beta2, eps, budget, step_dev, step_host, dist_kind, w, nn_idx, nullptr, false, stream);
 }
 
 extern "C" int pc3d_cw_update_ragged_f32(float* adv, int64_t a_bs, int64_t a_ps, int64_t a_cs,
@@ -318,31 +340,10 @@ extern "C" int pc3d_cw_update_ragged_f32(float* adv, int64_t a_bs, int64_t a_ps,
                                          double lr, double beta1, double beta2, double eps, float budget,
                                          const int32_t* step_dev, int step_host, int dist_kind, const float* w,
                                          const int32_t* nn_idx, void* stream) {
-  PC3D_REQUIRE(B >= 0 && K >= 1 && K <= 8192, "pc3d_cw_update_ragged_f32: bad sizes B=%d K=%d (K <= 8192)", B, K);
-  PC3D_REQUIRE(step_dev != nullptr || step_host >= 1,
-               "pc3d_cw_update_ragged_f32: step_host must be >= 1 without a device counter");
-  PC3D_REQUIRE(dist_kind >= 0 && dist_kind <= 2, "pc3d_cw_update_ragged_f32: dist_kind=%d not in {0,1,2}", dist_kind);
-  if (B == 0) return PC3D_OK;
-  PC3D_REQUIRE(adv && ori && lengths && pred && label && bestdist && bestscore && o_bestdist && o_bestscore && o_bestattack &&
-                   g && m && v,
-               "pc3d_cw_update_ragged_f32: null pointer");
-  PC3D_REQUIRE(dist_kind == 0 || w != nullptr, "pc3d_cw_update_ragged_f32: distance term needs the weights w");
-  PC3D_REQUIRE(dist_kind != 2 || nn_idx != nullptr, "pc3d_cw_update_ragged_f32: Chamfer term needs nn_idx");
-  RaggedUpdateArgs u{};
-  u.bk = BookArgs{{adv, a_bs, a_ps, a_cs}, {ori, o_bs, o_ps, o_cs}, K, pred, label, untarget, bestdist, bestscore,
-                  o_bestdist, o_bestscore, {o_bestattack, a_bs, a_ps, a_cs}, {input_val, a_bs, a_ps, a_cs}, dist_val,
-                  nullptr};
-  u.st = StepArgs{{adv, a_bs, a_ps, a_cs}, {g, g_bs, g_ps, g_cs}, {m, a_bs, a_ps, a_cs}, {v, a_bs, a_ps, a_cs},
-                  {ori, o_bs, o_ps, o_cs}, K, B, lr, beta1, beta2, (float)eps, budget, step_dev, step_host, dist_kind, w,
-                  nullptr, nn_idx};
-  u.lengths = lengths;
-  // PER follows K, not the lengths: they are device data, and one captured launch serves every binary step
-  if (K <= 1024) hipLaunchKernelGGL((cw_update_kernel<1, true>), dim3(B), dim3(1024), 0, as_stream(stream), u);
-  else if (K <= 2048) hipLaunchKernelGGL((cw_update_kernel<2, true>), dim3(B), dim3(1024), 0, as_stream(stream), u);
-  else if (K <= 4096) hipLaunchKernelGGL((cw_update_kernel<4, true>), dim3(B), dim3(1024), 0, as_stream(stream), u);
-  else hipLaunchKernelGGL((cw_update_kernel<8, true>), dim3(B), dim3(1024), 0, as_stream(stream), u);
-  PC3D_LAUNCH_CHECK("pc3d_cw_update_ragged_f32");
-  return PC3D_OK;
+  return cw_update_launch("pc3d_cw_update_ragged_f32", adv, a_bs, a_ps, a_cs, ori, o_bs, o_ps, o_cs, B, K, pred, label,
+                          untarget, bestdist, bestscore, o_bestdist, o_bestscore, o_bestattack, input_val, dist_val, g, g_bs,
+                          g_ps, g_cs, m, v, lr, beta1, beta2, eps, budget, step_dev, step_host, dist_kind, w, nn_idx, lengths,
+                          true, stream);
 }
 
 extern "C" int pc3d_pad_ragged_f32(float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, const int32_t* lengths, int B, int K,
