@@ -205,6 +205,10 @@ SIGNATURES = {
     "pc3d_pca_normal_f32": _PTS + [_P, _I, _I, _I] + _PTS + [_P],
     "pc3d_si_frame_f32": _PTS + _PTS + [_P, _I, _I, _I] + _PTS + _PTS + [_P],
     "pc3d_si_step_f32": _PTS + _PTS + _PTS + _PTS + [_P, _I, _I, _I] + _PTS + [_D, _D, _P],
+    # clouds of different sizes in one batch: the dense signatures with lengths [B] behind the sizes
+    "pc3d_pca_normal_ragged_f32": _PTS + [_P, _I, _I, _I, _P] + _PTS + [_P],
+    "pc3d_si_frame_ragged_f32": _PTS + _PTS + [_P, _I, _I, _I, _P] + _PTS + _PTS + [_P],
+    "pc3d_si_step_ragged_f32": _PTS + _PTS + _PTS + _PTS + [_P, _I, _I, _I, _P] + _PTS + [_D, _D, _P],
     "pc3d_query_step_f32": [_P, _I, _P, _I] + _PTS + _PTS + _PTS + [_P, _I, _P, _P, _L, _L] + [_P] * 7 + _PTS + _PTS
     + [_P, _P, _I, _I, _I, _P],
     "pc3d_si_rank_f32": _PTS + _PTS + [_I, _I, _P, _P, _P, _P, _P],

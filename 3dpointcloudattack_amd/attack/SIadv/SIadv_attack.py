@@ -10,6 +10,9 @@ previous step's lists), ``pc3d_si_frame_f32`` (the PCA normals from the lists an
 reference shows the victim), the surrogate's passes, and ``pc3d_si_step_f32`` (the step). The loop has no data-dependent
 exit, so with a PointNet surrogate (fused passes, no autograd) the step is captured into a hipGraph and replayed. Any
 other surrogate, a defence head or the top-5 loss take autograd for the gradient and the same two kernels.
+``run(points, target, lengths)`` runs the fast path on a batch of clouds of different sizes: every cloud
+gets the bits of its run alone, launch for launch the dense step with the search, the frame and the step in their
+``_ragged`` forms; anything but the fast path raises.
 
 Black box (``simba``, ``simbapp``, ``ours``: ``simba_attack``, ``simbapp_attack``, ``shape_invariant_query_attack``). The
 reference queries the target once per signed try of one table entry of one cloud and reads the loss back each time. Here
@@ -35,6 +38,7 @@ import torch
 
 from ... import graphed as _graphed
 from ... import ops
+from ... import ragged as _ragged
 from ...model import pointnet as _pointnet
 from .baselines import ClipPointsLinf, DUPNet, SORDefense, SRSDefense
 
@@ -50,35 +54,57 @@ def _first(out):
 
 
 class _Loop(_graphed.DeviceLoop):
-    """The fast path's loop for one batch shape: static buffers, one step as the body, captured as one step."""
+    """The fast path's loop for one batch shape: static buffers, one step as the body, captured as one step.
+    ragged: a batch of clouds of different sizes, N the capacity. The lengths are DATA of the launches (bufs "lens", and
+    "lens_host" for the search wrapper's check; every call refills them), so one captured graph serves every set of
+    lengths; the search writes the loop's own d / idx [B,N,KNN], idx also being its hint. The step is the dense step launch
+    for launch: the search over every cloud's own points, the frame, whose xe repeats its row 0 in the padding rows (the
+    surrogate is pad_invariant, or skips them: ragged.victim_kwargs), and the step, which pads the new iterate."""
 
-    def __init__(self, victim, B, N, dev, step_size, eps, key=None):
+    def __init__(self, victim, B, N, dev, step_size, eps, key=None, ragged=False):
         # the graph bakes in the addresses of the folded weights: it holds what it points at (LoopGraph.keep)
         super().__init__(key, dev, owners=(victim,), counts=(1,), warmup=2)
-        self.victim, self.step_size, self.eps = victim, float(step_size), float(eps)
+        self.victim, self.step_size, self.eps, self.ragged = victim, float(step_size), float(eps), bool(ragged)
         f32 = dict(dtype=torch.float32, device=dev)
         self.bufs.update({nm: torch.zeros((B, 3, N), **f32) for nm in ("x", "ori", "xe", "nrm")},
-                         label=torch.zeros((B,), dtype=torch.int64, device=dev))
+                         label=torch.zeros((B,), dtype=torch.int64, device=dev), lens=None, lens_host=None)
+        if self.ragged:
+            lens, lens_host = _ragged.loop_lengths(B, N, dev)
+            self.bufs.update(lens=lens, lens_host=lens_host, d=torch.zeros((B, N, KNN), **f32),
+                             idx=torch.zeros((B, N, KNN), dtype=torch.int32, device=dev))
+        self.vlens = _ragged.victim_kwargs(victim, self.bufs["lens"])
 
-    def load(self, x, ori, label):
+    def load(self, x, ori, label, nrm=None, lens=None):
+        """The call's state. Ragged (lens: int64 numpy [B]): the lengths first, then x, ori and the given normals (kept in
+        the loop's own nrm) with their rows at and beyond a length made copies of row 0."""
         b = self.bufs
         b["x"].copy_(x), b["ori"].copy_(ori), b["label"].copy_(label)
+        if self.ragged:
+            _ragged.set_loop_lengths(b, lens)
+            if nrm is not None:
+                b["nrm"].copy_(nrm)
+            for nm in ("x", "ori") + (("nrm",) if nrm is not None else ()):
+                ops.pad_ragged(b[nm], b["lens"])
 
     def _move(self, nrm):
         # the victim is shown xe (si_frame), as in the reference; its loss is summed over the batch, not averaged: scale 1
         b = self.bufs
-        g = self.victim.fused_attack_grad(b["xe"], b["label"], "untargeted_logits", 0.0, scale=1.0)[2]
-        ops.si_step(b["x"], b["ori"], g, self.step_size, self.eps, nrm=nrm)
+        g = self.victim.fused_attack_grad(b["xe"], b["label"], "untargeted_logits", 0.0, scale=1.0, **self.vlens)[2]
+        ops.si_step(b["x"], b["ori"], g, self.step_size, self.eps, nrm=nrm, lengths=b["lens"])
 
     def first(self, nrm):
-        """Step 0: the normals that came with the cloud."""
-        ops.si_frame(self.bufs["x"], nrm=nrm, out=self.bufs["xe"])
+        """Step 0: the normals that came with the cloud (ragged: the loop's own copy of them, see load)."""
+        nrm = self.bufs["nrm"] if self.ragged else nrm
+        ops.si_frame(self.bufs["x"], nrm=nrm, out=self.bufs["xe"], lengths=self.bufs["lens"])
         self._move(nrm)
 
     def step(self):
         b = self.bufs
-        _, idx = ops.knn_raw(b["x"], b["x"], KNN, q_cf=True, r_cf=True)
-        ops.si_frame(b["x"], idx=idx, out=b["xe"], nrm_out=b["nrm"])
+        if self.ragged:
+            idx = ops.knn_search_into(b["x"], b["d"], b["idx"], lengths=b["lens"], lengths_host=b["lens_host"])[1]
+        else:
+            _, idx = ops.knn_raw(b["x"], b["x"], KNN, q_cf=True, r_cf=True)
+        ops.si_frame(b["x"], idx=idx, out=b["xe"], nrm_out=b["nrm"], lengths=b["lens"])
         self._move(b["nrm"])
 
     body = step
@@ -179,6 +205,8 @@ class PointCloudAttack(object):
     ``run(points [B,N,6], target [B])`` returns (adv_points [B,N,3], adv_target [B], number of misclassified clouds).
     With a query method, ``run(points [B,N,3 or 6], target [B])`` returns (adv_points [B,N,3], adv_target [B] int64,
     query_costs [B] int64).
+    ``run(points [B,Kmax,6 or 3], target [B], lengths)`` (the white-box attack only): a batch of clouds of different sizes as
+    dataset.cloud_io.stack_ragged builds it, see shape_invariant_ifgm.
     fused / graph: use the models' fused passes when they have them, and replay the step from a hipGraph."""
 
     def __init__(self, args, wb_classifier=None, classifier=None, fused=True, graph=True):
@@ -222,10 +250,11 @@ class PointCloudAttack(object):
             return torch.sum(torch.max(other - real, kappa))
         return torch.sum(torch.max(real - other, kappa))
 
-    def run(self, points, target):
-        """points [B,N,6] (coordinates and normals; the query attacks use the coordinates only), target [B]."""
-        if self.attack_method == 'ifgm_ours':
-            return self.shape_invariant_ifgm(points, target)
+    def run(self, points, target, lengths=None):
+        """points [B,N,6] (coordinates and normals; the query attacks use the coordinates only), target [B].
+        lengths (default None): the sizes of a ragged batch, for the white-box attack only (shape_invariant_ifgm)."""
+        if self.attack_method == 'ifgm_ours' or (lengths is not None and self.attack_method in QUERY_METHODS):
+            return self.shape_invariant_ifgm(points, target, lengths)
         if self.attack_method == 'simba':
             return self.simba_attack(points, target)
         if self.attack_method == 'simbapp':
@@ -246,13 +275,20 @@ class PointCloudAttack(object):
             raise NotImplementedError
         return pre_head
 
-    def get_normal_vector(self, points):
+    def get_normal_vector(self, points, lengths=None):
         """Normals [B,N,3] of points [B,N,3] on the GPU: the self-kNN search (K = 20, the point included) and the PCA
         normal of every list (pc3d_pca_normal_f32) — the definition open3d documents for
-        estimate_normals(KDTreeSearchParamKNN(knn=20)); the sign is this library's."""
+        estimate_normals(KDTreeSearchParamKNN(knn=20)); the sign is this library's.
+        lengths (B ints, KNN <= lengths[b] <= N; default None: every cloud has N points): cloud b's first lengths[b] rows
+        are searched and get the normals of the cloud alone, the rows behind them (never read) row 0's normal."""
         if points.shape[1] < KNN:
             raise ValueError(f"get_normal_vector: N = {points.shape[1]} points, the {KNN}-neighbour normals need N >= {KNN}")
         points = points.detach().float()
+        if lengths is not None:
+            lens = _ragged.check_lengths("get_normal_vector", lengths, points.shape[0], points.shape[1], low=KNN, low_text="KNN")
+            lens_dev = torch.from_numpy(lens.astype(np.int32)).to(points.device)
+            _, idx = ops.knn_ragged(points.contiguous(), points.contiguous(), KNN, lens_dev, lengths_host=lens)
+            return ops.pca_normal(points, idx, lengths=lens_dev)
         _, idx = ops.knn_raw(points, points, KNN)
         return ops.pca_normal(points, idx)
 
@@ -297,20 +333,50 @@ class PointCloudAttack(object):
         return bool(self.fused and self.pre_head is None and not self.top5_attack
                     and hasattr(self.wb_classifier, "fused_attack_grad"))
 
-    def _loop(self, x, ori, target):
-        """A loaded _Loop for x [B,3,N]; with graph=True captured once per (shape, settings, weights)."""
+    def _loop_key(self, device, B, N, ragged=False):
+        """The dense loop's key as it always was; a ragged loop's carries the flag, never the lengths."""
+        consts = (B, N, float(self.step_size), float(self.eps)) + ((("ragged", True),) if ragged else ())
+        return _graphed.loop_key(self.wb_classifier, device, *consts)
+
+    def _loop(self, x, ori, target, nrm=None, lens=None):
+        """A loaded _Loop for x [B,3,N]; with graph=True captured once per (shape, settings, weights). lens (int64 numpy
+        [B]): the ragged loop of that shape, loaded with these lengths and the given normals nrm."""
         B, _, N = x.shape
         v = self.wb_classifier
-        key = _graphed.loop_key(v, x.device, B, N, float(self.step_size), float(self.eps)) if self.graph else None
+        ragged = lens is not None
+        state = dict(nrm=nrm, lens=lens) if ragged else {}
+        key = self._loop_key(x.device, B, N, ragged) if self.graph else None
         c = self._loops.get(key) if self.graph else None
         if c is None:
-            c = _Loop(v, B, N, x.device, self.step_size, self.eps, key)
+            c = _Loop(v, B, N, x.device, self.step_size, self.eps, key, ragged=ragged)
             if self.graph:
                 self._loops.put(key, c)
-                c.load(x, ori, target)
+                c.load(x, ori, target, **state)
                 c.capture()
-        c.load(x, ori, target)
+        c.load(x, ori, target, **state)
         return c
+
+    def _ragged_lengths(self, points, lengths):
+        """lengths as int64 numpy [B] after every gate of the ragged pass, or ValueError naming what does not fit, before
+        any launch. There is no silent fall-back: the generic path would count the padding copies of row 0 as neighbours
+        (a degenerate covariance and the default normal for row 0 and every point near it), and a surrogate that is not
+        pad_invariant would see them as points."""
+        who = "shape_invariant_ifgm"
+        sur = _graphed.unwrap(self.wb_classifier)
+        if self.attack_method in QUERY_METHODS:
+            raise ValueError(f"{who}: lengths go with the white-box attack only, not with the query attack "
+                             f"'{self.attack_method}'")
+        if not self._fast():
+            why = ("fused=False" if not self.fused else f"the defence head '{self.defense_method}'" if self.pre_head is not None
+                   else "top5_attack" if self.top5_attack
+                   else f"the surrogate {type(sur).__name__} has no fused entry points (fused_attack_grad)")
+            raise ValueError(f"{who}: lengths run the fast path only ({why} takes the generic path, which has no ragged pass)")
+        if not getattr(sur, "pad_invariant", False):
+            raise ValueError(f"{who}: the surrogate {type(sur).__name__} does not declare pad_invariant")
+        if not isinstance(points, torch.Tensor) or points.dim() != 3 or points.shape[2] not in (3, 6):
+            raise ValueError(f"{who}: points must be [B,Kmax,6] (or [B,Kmax,3]), got "
+                             f"{tuple(points.shape) if isinstance(points, torch.Tensor) else type(points)}")
+        return _ragged.check_lengths(who, lengths, points.shape[0], points.shape[1], low=KNN, low_text="KNN")
 
     def _generic_grad(self, xe, target):
         """dL/dxe [B,3,N] by autograd through the defence head and the surrogate, at the cloud xe = U^T P' - t that
@@ -326,10 +392,13 @@ class PointCloudAttack(object):
             (g,) = torch.autograd.grad(loss, P)
         return g.contiguous(), loss.detach()
 
-    def iterate(self, points, target, steps=None, ori=None):
+    def iterate(self, points, target, steps=None, ori=None, lengths=None):
         """The loop alone: the coordinates [B,3,N] after `steps` (default max_steps) steps from points [B,N,6]. With
         points [B,N,3] (no normals) the first step estimates them like the later ones do. ori [B,N,3]: the clean cloud the
-        clamp refers to when the run continues from an iterate (default: the coordinates given)."""
+        clamp refers to when the run continues from an iterate (default: the coordinates given).
+        lengths (B ints, KNN <= lengths[b] <= N; default None: every cloud has N points): a ragged batch, see
+        shape_invariant_ifgm. Columns below a length have the bits of that cloud's run alone, the others equal column 0."""
+        lens = self._ragged_lengths(points, lengths) if lengths is not None else None
         steps = self.max_steps if steps is None else steps
         points = points.detach().float()
         B, N, C = points.shape
@@ -346,10 +415,10 @@ class PointCloudAttack(object):
         x = points[:, :, :3].transpose(1, 2).contiguous()
         ori = x.clone() if ori is None else ori.detach().float().transpose(1, 2).contiguous()
         if steps < 1:
-            return x
+            return x if lens is None else ops.pad_ragged(x, torch.from_numpy(lens.astype(np.int32)).to(x.device))
         with torch.cuda.device(x.device), torch.no_grad():
             if self._fast():
-                c = self._loop(x, ori, target)
+                c = self._loop(x, ori, target, nrm, lens)
                 if nrm is not None:
                     c.first(nrm)
                 c.run(steps - (nrm is not None))
@@ -366,9 +435,22 @@ class PointCloudAttack(object):
                 ops.si_step(x, ori, g, self.step_size, self.eps, nrm=nrm)
         return x
 
-    def shape_invariant_ifgm(self, points, target):
+    def shape_invariant_ifgm(self, points, target, lengths=None):
         """White-box I-FGM on shape-invariant sensitivity maps, transferred to the target model.
-        points [B,N,6], target [B] -> (adv_points [B,N,3], adv_target [B], number of clouds the target misclassifies)."""
+        points [B,N,6], target [B] -> (adv_points [B,N,3], adv_target [B], number of clouds the target misclassifies).
+        lengths (default None: every cloud has N points, nothing changes): B ints (sequence, array or tensor), the sizes of
+        a batch of clouds of different sizes, KNN <= lengths[b] <= Kmax = N. Rows of points at and beyond a length may hold
+        anything (they are only written); adv_points' are copies of the cloud's row 0 (dataset.cloud_io.unstack_ragged drops
+        them). Every cloud gets the bits of its run alone. The fast path only — fused, no defence head, no top-5 loss, a
+        surrogate with fused_attack_grad that declares pad_invariant — anything else raises ValueError before any launch.
+        A target model that does not declare pad_invariant sees every cloud alone (ragged.predict)."""
+        if lengths is not None:
+            lens = self._ragged_lengths(points, lengths)
+            x = self.iterate(points, target, lengths=lens)
+            target = target.detach().reshape(-1).long().to(x.device)
+            with torch.no_grad():
+                pred = _ragged.predict(self.classifier, x, lens)
+            return x.transpose(1, 2).contiguous(), pred, (pred != target).sum().item()
         x = self.iterate(points, target)
         target = target.detach().reshape(-1).long().to(x.device)
         with torch.no_grad():

@@ -60,11 +60,26 @@ struct PcaNormalArgs {
   PtsViewMut out;
 };
 
-__global__ __launch_bounds__(256) void pca_normal_kernel(PcaNormalArgs a) {
+// Clouds of different sizes in one batch (the three _ragged entries): cloud b counts L = clamp(lengths[b], 1, N) points,
+// lengths int32 [B] read as data, and N is the capacity: the row stride of idx and of the LDS stage.
+struct PcaNormalRaggedArgs : PcaNormalArgs { const int32_t* lengths; };
+template <bool RAGGED> struct PcaNormalArgsOf { using type = PcaNormalArgs; };
+template <> struct PcaNormalArgsOf<true> { using type = PcaNormalRaggedArgs; };
+
+__device__ __forceinline__ int si_ragged_len(const int32_t* lengths, int b, int N) { return min(max(lengths[b], 1), N); }
+
+// RAGGED: a row i < L is the dense row of the cloud alone at N = L (a neighbour index is checked against L); a row i >= L
+// repeats row 0's arithmetic on row 0's inputs — the same instructions on the same values, the same bits — and stores it
+// at i: the padding rows of out are copies of row 0's normal, and no row >= L of x or idx is read. The dense instantiation
+// compiles to the kernel it was before RAGGED existed (the parameter is a type of its own).
+template <bool RAGGED>
+__global__ __launch_bounds__(256) void pca_normal_kernel(typename PcaNormalArgsOf<RAGGED>::type a) {
   const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
   if (i >= a.N) return;
+  int L = a.N, r = i;
+  if constexpr (RAGGED) L = si_ragged_len(a.lengths, b, a.N), r = i < L ? i : 0;
   float nx, ny, nz;
-  pca_normal_point(a.x.p + (int64_t)b * a.x.bs, a.x.ps, a.x.cs, a.idx + ((int64_t)b * a.N + i) * a.K, a.K, a.N, nx, ny, nz);
+  pca_normal_point(a.x.p + (int64_t)b * a.x.bs, a.x.ps, a.x.cs, a.idx + ((int64_t)b * a.N + r) * a.K, a.K, L, nx, ny, nz);
   float* o = a.out.p + (int64_t)b * a.out.bs + (int64_t)i * a.out.ps;
   o[0] = nx, o[a.out.cs] = ny, o[2 * a.out.cs] = nz;
 }
@@ -113,20 +128,29 @@ struct SiFrameArgs {
   PtsViewMut xe, nout;   // the cloud the victim is shown; the normals used (p may be null)
 };
 
+struct SiFrameRaggedArgs : SiFrameArgs { const int32_t* lengths; };
+template <bool RAGGED> struct SiFrameArgsOf { using type = SiFrameArgs; };
+template <> struct SiFrameArgsOf<true> { using type = SiFrameRaggedArgs; };
+
 // The cloud the reference hands to the victim (:293-298): not P but U^T (U (P + t)) - t. Away from the rewritten rows of
 // U that is P up to rounding; at those rows U is not the frame of n and the point is displaced by up to ~1e-4 |P|.
-__global__ __launch_bounds__(256) void si_frame_kernel(SiFrameArgs a) {
+// RAGGED: as in pca_normal_kernel — a row i >= L computes row 0 again and stores it at i, so that xe's (and nout's) padding rows
+// are copies of their row 0 in every bit (what a pad_invariant victim is shown); rows >= L of x, nrm and idx are not read.
+template <bool RAGGED>
+__global__ __launch_bounds__(256) void si_frame_kernel(typename SiFrameArgsOf<RAGGED>::type a) {
   const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
   if (i >= a.N) return;
+  int L = a.N, r = i;
+  if constexpr (RAGGED) L = si_ragged_len(a.lengths, b, a.N), r = i < L ? i : 0;
   const float* xb = a.x.p + (int64_t)b * a.x.bs;
   float nx, ny, nz;
   if (a.nrm.p) {
-    const float* np_ = a.nrm.p + (int64_t)b * a.nrm.bs + (int64_t)i * a.nrm.ps;
+    const float* np_ = a.nrm.p + (int64_t)b * a.nrm.bs + (int64_t)r * a.nrm.ps;
     nx = np_[0], ny = np_[a.nrm.cs], nz = np_[2 * a.nrm.cs];
   } else {
-    pca_normal_point(xb, a.x.ps, a.x.cs, a.idx + ((int64_t)b * a.N + i) * a.K, a.K, a.N, nx, ny, nz);
+    pca_normal_point(xb, a.x.ps, a.x.cs, a.idx + ((int64_t)b * a.N + r) * a.K, a.K, L, nx, ny, nz);
   }
-  const float* xp = xb + (int64_t)i * a.x.ps;
+  const float* xp = xb + (int64_t)r * a.x.ps;
   float u[9], t3[3], r3[3];
   si_frame(nx, ny, nz, u);
   si_to_frame(u, xp[0], xp[a.x.cs], xp[2 * a.x.cs], nx, ny, nz, t3, r3);
@@ -149,10 +173,21 @@ struct SiStepArgs {
   float cstep, eps;      // step_size * sqrt(3 * 1024); the clamp
 };
 
-__global__ __launch_bounds__(SI_T) void si_step_kernel(SiStepArgs a) {
+struct SiStepRaggedArgs : SiStepArgs { const int32_t* lengths; };
+template <bool RAGGED> struct SiStepArgsOf { using type = SiStepArgs; };
+template <> struct SiStepArgsOf<true> { using type = SiStepRaggedArgs; };
+
+// RAGGED: both passes run over n < L with the dense thread-to-point mapping and the dense reduction order, so rows < L have
+// the bits of the dense launch on the cloud alone at N = L (a.N stays the capacity: the row stride of idx and of the LDS
+// stage). Rows >= L of ori, g, nrm and idx are never read; x's take the NEW row 0 and nout's row 0's normal, both handed
+// over through LDS behind a barrier (row 0 is rewritten in place by thread 0 in the same pass).
+template <bool RAGGED>
+__global__ __launch_bounds__(SI_T) void si_step_kernel(typename SiStepArgsOf<RAGGED>::type a) {
   extern __shared__ float si_lds[];                 // [3][N] normals (idx mode with lds_stage)
-  __shared__ float s_part[SI_WAVES];
+  __shared__ float s_part[SI_WAVES + (RAGGED ? 6 : 0)];     // RAGGED: behind the wave sums, the new row 0 and its normal
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  int L = a.N;
+  if constexpr (RAGGED) L = si_ragged_len(a.lengths, b, a.N);
   float* xb = a.x.p + (int64_t)b * a.x.bs;
   const float* gb = a.g.p + (int64_t)b * a.g.bs;
   // where pass 2 finds the normals pass 1 used: the caller's, the LDS stage, or nrm_out
@@ -167,13 +202,13 @@ __global__ __launch_bounds__(SI_T) void si_step_kernel(SiStepArgs a) {
   }
   // pass 1: normals (idx mode; this is the last read of any OTHER point's coordinates) and the cloud's sum of g'^2
   float acc = 0.f;
-  for (int n = tid; n < a.N; n += SI_T) {
+  for (int n = tid; n < L; n += SI_T) {
     float nx, ny, nz;
     if (a.nrm.p) {
       const float* np_ = nb + (int64_t)n * nps;
       nx = np_[0], ny = np_[ncs], nz = np_[2 * ncs];
     } else {
-      pca_normal_point(xb, a.x.ps, a.x.cs, a.idx + ((int64_t)b * a.N + n) * a.K, a.K, a.N, nx, ny, nz);
+      pca_normal_point(xb, a.x.ps, a.x.cs, a.idx + ((int64_t)b * a.N + n) * a.K, a.K, L, nx, ny, nz);
       float* ns = const_cast<float*>(nb) + (int64_t)n * nps;
       ns[0] = nx, ns[ncs] = ny, ns[2 * ncs] = nz;
     }
@@ -193,7 +228,7 @@ __global__ __launch_bounds__(SI_T) void si_step_kernel(SiStepArgs a) {
   const float denom = __builtin_sqrtf(ss) + 1e-9f;
   // pass 2: P' = U (P + t), P' -= c g' / (|g'| + 1e-9), P = U^T P' - t, clamp to ori +- eps (:293-320)
   const float* ob = a.ori.p + (int64_t)b * a.ori.bs;
-  for (int n = tid; n < a.N; n += SI_T) {
+  for (int n = tid; n < L; n += SI_T) {
     const float* np_ = nb + (int64_t)n * nps;
     const float nx = np_[0], ny = np_[ncs], nz = np_[2 * ncs];
     float* xp = xb + (int64_t)n * a.x.ps;
@@ -213,10 +248,30 @@ __global__ __launch_bounds__(SI_T) void si_step_kernel(SiStepArgs a) {
       const float d = si_from_frame(u, r3, t3, c) - o3[c];
       const float dc = d < -a.eps ? -a.eps : (d > a.eps ? a.eps : d);     // NaN stays NaN, as torch.clamp
       xp[c * a.x.cs] = o3[c] + dc;
+      if constexpr (RAGGED) {
+        if (n == 0) s_part[SI_WAVES + c] = o3[c] + dc;                    // thread 0 owns row 0
+      }
+    }
+    if constexpr (RAGGED) {
+      if (n == 0) s_part[SI_WAVES + 3] = nx, s_part[SI_WAVES + 4] = ny, s_part[SI_WAVES + 5] = nz;
     }
     if (a.nout.p && nb != a.nout.p + (int64_t)b * a.nout.bs) {
       float* no = a.nout.p + (int64_t)b * a.nout.bs + (int64_t)n * a.nout.ps;
       no[0] = nx, no[a.nout.cs] = ny, no[2 * a.nout.cs] = nz;
+    }
+  }
+  if constexpr (RAGGED) {
+    // re-padding: no thread reads back from global memory what another thread of the workgroup writes
+    __syncthreads();
+    const float* p0 = s_part + SI_WAVES;
+    const float x0 = p0[0], y0 = p0[1], z0 = p0[2], n0x = p0[3], n0y = p0[4], n0z = p0[5];
+    for (int n = L + tid; n < a.N; n += SI_T) {
+      float* xp = xb + (int64_t)n * a.x.ps;
+      xp[0] = x0, xp[a.x.cs] = y0, xp[2 * a.x.cs] = z0;
+      if (a.nout.p) {
+        float* no = a.nout.p + (int64_t)b * a.nout.bs + (int64_t)n * a.nout.ps;
+        no[0] = n0x, no[a.nout.cs] = n0y, no[2 * a.nout.cs] = n0z;
+      }
     }
   }
 }
@@ -490,16 +545,59 @@ __global__ __launch_bounds__(1024) void si_rank_kernel(SiRankArgs a) {
 
 using namespace pc3d;
 
+// the checks, the argument block and the launch of a dense entry and its _ragged twin; ragged false: the dense kernel,
+// lengths unused
+static int pca_normal_launch(const char* nm, const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, const int32_t* idx, int B,
+                             int N, int K, const int32_t* lengths, bool ragged, float* out, int64_t o_bs, int64_t o_ps,
+                             int64_t o_cs, void* stream) {
+  PC3D_REQUIRE(B >= 0 && N >= 1 && K >= 1, "%s: bad sizes B=%d N=%d K=%d", nm, B, N, K);
+  PC3D_REQUIRE(B <= 65535, "%s: B=%d exceeds grid.y limit", nm, B);
+  if (B == 0) return PC3D_OK;
+  PC3D_REQUIRE(x && idx && out && (!ragged || lengths), "%s: null pointer", nm);
+  PC3D_REQUIRE(x != out, "%s: out must not alias x (a point reads its neighbours)", nm);
+  PcaNormalRaggedArgs a{{{x, x_bs, x_ps, x_cs}, idx, N, K, {out, o_bs, o_ps, o_cs}}, lengths};
+  if (ragged)
+    hipLaunchKernelGGL(pca_normal_kernel<true>, dim3(cdiv(N, 256), B), dim3(256), 0, as_stream(stream), a);
+  else
+    hipLaunchKernelGGL(pca_normal_kernel<false>, dim3(cdiv(N, 256), B), dim3(256), 0, as_stream(stream),
+                       static_cast<const PcaNormalArgs&>(a));
+  PC3D_LAUNCH_CHECK(nm);
+  return PC3D_OK;
+}
+
 extern "C" int pc3d_pca_normal_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, const int32_t* idx, int B,
                                    int N, int K, float* out, int64_t o_bs, int64_t o_ps, int64_t o_cs, void* stream) {
-  PC3D_REQUIRE(B >= 0 && N >= 1 && K >= 1, "pc3d_pca_normal_f32: bad sizes B=%d N=%d K=%d", B, N, K);
-  PC3D_REQUIRE(B <= 65535, "pc3d_pca_normal_f32: B=%d exceeds grid.y limit", B);
+  return pca_normal_launch("pc3d_pca_normal_f32", x, x_bs, x_ps, x_cs, idx, B, N, K, nullptr, false, out, o_bs, o_ps, o_cs,
+                           stream);
+}
+
+extern "C" int pc3d_pca_normal_ragged_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, const int32_t* idx,
+                                          int B, int N, int K, const int32_t* lengths, float* out, int64_t o_bs,
+                                          int64_t o_ps, int64_t o_cs, void* stream) {
+  return pca_normal_launch("pc3d_pca_normal_ragged_f32", x, x_bs, x_ps, x_cs, idx, B, N, K, lengths, true, out, o_bs, o_ps,
+                           o_cs, stream);
+}
+
+static int si_frame_launch(const char* nm, const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs,
+                           const float* nrm, int64_t n_bs, int64_t n_ps, int64_t n_cs, const int32_t* idx, int K, int B, int N,
+                           const int32_t* lengths, bool ragged, float* xe, int64_t e_bs, int64_t e_ps, int64_t e_cs,
+                           float* nrm_out, int64_t no_bs, int64_t no_ps, int64_t no_cs, void* stream) {
+  PC3D_REQUIRE(B >= 0 && N >= 1, "%s: bad sizes B=%d N=%d", nm, B, N);
+  PC3D_REQUIRE(B <= 65535, "%s: B=%d exceeds grid.y limit", nm, B);
+  PC3D_REQUIRE((nrm != nullptr) != (idx != nullptr), "%s: give either the normals nrm or the neighbour lists idx", nm);
+  PC3D_REQUIRE(idx == nullptr || K >= 1, "%s: bad K=%d", nm, K);
   if (B == 0) return PC3D_OK;
-  PC3D_REQUIRE(x && idx && out, "pc3d_pca_normal_f32: null pointer");
-  PC3D_REQUIRE(x != out, "pc3d_pca_normal_f32: out must not alias x (a point reads its neighbours)");
-  PcaNormalArgs a{{x, x_bs, x_ps, x_cs}, idx, N, K, {out, o_bs, o_ps, o_cs}};
-  hipLaunchKernelGGL(pca_normal_kernel, dim3(cdiv(N, 256), B), dim3(256), 0, as_stream(stream), a);
-  PC3D_LAUNCH_CHECK("pc3d_pca_normal_f32");
+  PC3D_REQUIRE(x && xe && (!ragged || lengths), "%s: null pointer", nm);
+  PC3D_REQUIRE(xe != x && nrm_out != x && (nrm_out == nullptr || (nrm_out != nrm && nrm_out != xe)),
+               "%s: xe and nrm_out must not alias the inputs or each other (a point reads its neighbours)", nm);
+  SiFrameRaggedArgs a{{{x, x_bs, x_ps, x_cs}, {nrm, n_bs, n_ps, n_cs}, idx, K, N, {xe, e_bs, e_ps, e_cs},
+                       {nrm_out, no_bs, no_ps, no_cs}}, lengths};
+  if (ragged)
+    hipLaunchKernelGGL(si_frame_kernel<true>, dim3(cdiv(N, 256), B), dim3(256), 0, as_stream(stream), a);
+  else
+    hipLaunchKernelGGL(si_frame_kernel<false>, dim3(cdiv(N, 256), B), dim3(256), 0, as_stream(stream),
+                       static_cast<const SiFrameArgs&>(a));
+  PC3D_LAUNCH_CHECK(nm);
   return PC3D_OK;
 }
 
@@ -508,17 +606,45 @@ extern "C" int pc3d_si_frame_f32(const float* x, int64_t x_bs, int64_t x_ps, int
                                  const int32_t* idx, int K, int B, int N,
                                  float* xe, int64_t e_bs, int64_t e_ps, int64_t e_cs,
                                  float* nrm_out, int64_t no_bs, int64_t no_ps, int64_t no_cs, void* stream) {
-  PC3D_REQUIRE(B >= 0 && N >= 1, "pc3d_si_frame_f32: bad sizes B=%d N=%d", B, N);
-  PC3D_REQUIRE(B <= 65535, "pc3d_si_frame_f32: B=%d exceeds grid.y limit", B);
-  PC3D_REQUIRE((nrm != nullptr) != (idx != nullptr), "pc3d_si_frame_f32: give either the normals nrm or the neighbour lists idx");
-  PC3D_REQUIRE(idx == nullptr || K >= 1, "pc3d_si_frame_f32: bad K=%d", K);
+  return si_frame_launch("pc3d_si_frame_f32", x, x_bs, x_ps, x_cs, nrm, n_bs, n_ps, n_cs, idx, K, B, N, nullptr, false, xe,
+                         e_bs, e_ps, e_cs, nrm_out, no_bs, no_ps, no_cs, stream);
+}
+
+extern "C" int pc3d_si_frame_ragged_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs,
+                                        const float* nrm, int64_t n_bs, int64_t n_ps, int64_t n_cs,
+                                        const int32_t* idx, int K, int B, int N, const int32_t* lengths,
+                                        float* xe, int64_t e_bs, int64_t e_ps, int64_t e_cs,
+                                        float* nrm_out, int64_t no_bs, int64_t no_ps, int64_t no_cs, void* stream) {
+  return si_frame_launch("pc3d_si_frame_ragged_f32", x, x_bs, x_ps, x_cs, nrm, n_bs, n_ps, n_cs, idx, K, B, N, lengths, true,
+                         xe, e_bs, e_ps, e_cs, nrm_out, no_bs, no_ps, no_cs, stream);
+}
+
+static int si_step_launch(const char* nm, float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs,
+                          const float* ori, int64_t o_bs, int64_t o_ps, int64_t o_cs,
+                          const float* g, int64_t g_bs, int64_t g_ps, int64_t g_cs,
+                          const float* nrm, int64_t n_bs, int64_t n_ps, int64_t n_cs, const int32_t* idx, int K, int B, int N,
+                          const int32_t* lengths, bool ragged, float* nrm_out, int64_t no_bs, int64_t no_ps, int64_t no_cs,
+                          double step_size, double eps, void* stream) {
+  PC3D_REQUIRE(B >= 0 && N >= 1, "%s: bad sizes B=%d N=%d", nm, B, N);
+  PC3D_REQUIRE((nrm != nullptr) != (idx != nullptr), "%s: give either the normals nrm or the neighbour lists idx", nm);
+  PC3D_REQUIRE(idx == nullptr || K >= 1, "%s: bad K=%d", nm, K);
+  PC3D_REQUIRE(eps >= 0.0, "%s: eps must not be negative", nm);
   if (B == 0) return PC3D_OK;
-  PC3D_REQUIRE(x && xe, "pc3d_si_frame_f32: null pointer");
-  PC3D_REQUIRE(xe != x && nrm_out != x && (nrm_out == nullptr || (nrm_out != nrm && nrm_out != xe)),
-               "pc3d_si_frame_f32: xe and nrm_out must not alias the inputs or each other (a point reads its neighbours)");
-  SiFrameArgs a{{x, x_bs, x_ps, x_cs}, {nrm, n_bs, n_ps, n_cs}, idx, K, N, {xe, e_bs, e_ps, e_cs}, {nrm_out, no_bs, no_ps, no_cs}};
-  hipLaunchKernelGGL(si_frame_kernel, dim3(cdiv(N, 256), B), dim3(256), 0, as_stream(stream), a);
-  PC3D_LAUNCH_CHECK("pc3d_si_frame_f32");
+  PC3D_REQUIRE(x && ori && g && (!ragged || lengths), "%s: null pointer", nm);
+  PC3D_REQUIRE(x != ori && x != g && x != nrm && x != nrm_out, "%s: x (updated in place) must not alias ori, g, nrm or nrm_out", nm);
+  PC3D_REQUIRE(nrm_out == nullptr || nrm_out != nrm, "%s: nrm_out must not alias nrm", nm);
+  const int lds_stage = (idx != nullptr && N <= SI_LDS_MAXN) ? 1 : 0;      // from the capacity: the lengths are device data
+  PC3D_REQUIRE(idx == nullptr || lds_stage || nrm_out != nullptr,
+               "%s: N=%d > %d in idx mode needs nrm_out (the normals pass through it)", nm, N, SI_LDS_MAXN);
+  SiStepRaggedArgs a{{{x, x_bs, x_ps, x_cs}, {ori, o_bs, o_ps, o_cs}, {g, g_bs, g_ps, g_cs}, {nrm, n_bs, n_ps, n_cs}, idx, K,
+                      {nrm_out, no_bs, no_ps, no_cs}, N, lds_stage, (float)(step_size * sqrt(3.0 * 1024.0)), (float)eps},
+                     lengths};
+  const size_t lds = lds_stage ? (size_t)3 * N * sizeof(float) : 0;
+  if (ragged)
+    hipLaunchKernelGGL(si_step_kernel<true>, dim3((unsigned)B), dim3(SI_T), lds, as_stream(stream), a);
+  else
+    hipLaunchKernelGGL(si_step_kernel<false>, dim3((unsigned)B), dim3(SI_T), lds, as_stream(stream), static_cast<const SiStepArgs&>(a));
+  PC3D_LAUNCH_CHECK(nm);
   return PC3D_OK;
 }
 
@@ -529,23 +655,19 @@ extern "C" int pc3d_si_step_f32(float* x, int64_t x_bs, int64_t x_ps, int64_t x_
                                 const int32_t* idx, int K, int B, int N,
                                 float* nrm_out, int64_t no_bs, int64_t no_ps, int64_t no_cs,
                                 double step_size, double eps, void* stream) {
-  PC3D_REQUIRE(B >= 0 && N >= 1, "pc3d_si_step_f32: bad sizes B=%d N=%d", B, N);
-  PC3D_REQUIRE((nrm != nullptr) != (idx != nullptr), "pc3d_si_step_f32: give either the normals nrm or the neighbour lists idx");
-  PC3D_REQUIRE(idx == nullptr || K >= 1, "pc3d_si_step_f32: bad K=%d", K);
-  PC3D_REQUIRE(eps >= 0.0, "pc3d_si_step_f32: eps must not be negative");
-  if (B == 0) return PC3D_OK;
-  PC3D_REQUIRE(x && ori && g, "pc3d_si_step_f32: null pointer");
-  PC3D_REQUIRE(x != ori && x != g && x != nrm && x != nrm_out, "pc3d_si_step_f32: x (updated in place) must not alias ori, g, nrm or nrm_out");
-  PC3D_REQUIRE(nrm_out == nullptr || nrm_out != nrm, "pc3d_si_step_f32: nrm_out must not alias nrm");
-  const int lds_stage = (idx != nullptr && N <= SI_LDS_MAXN) ? 1 : 0;
-  PC3D_REQUIRE(idx == nullptr || lds_stage || nrm_out != nullptr,
-               "pc3d_si_step_f32: N=%d > %d in idx mode needs nrm_out (the normals pass through it)", N, SI_LDS_MAXN);
-  SiStepArgs a{{x, x_bs, x_ps, x_cs}, {ori, o_bs, o_ps, o_cs}, {g, g_bs, g_ps, g_cs}, {nrm, n_bs, n_ps, n_cs}, idx, K,
-               {nrm_out, no_bs, no_ps, no_cs}, N, lds_stage, (float)(step_size * sqrt(3.0 * 1024.0)), (float)eps};
-  const size_t lds = lds_stage ? (size_t)3 * N * sizeof(float) : 0;
-  hipLaunchKernelGGL(si_step_kernel, dim3((unsigned)B), dim3(SI_T), lds, as_stream(stream), a);
-  PC3D_LAUNCH_CHECK("pc3d_si_step_f32");
-  return PC3D_OK;
+  return si_step_launch("pc3d_si_step_f32", x, x_bs, x_ps, x_cs, ori, o_bs, o_ps, o_cs, g, g_bs, g_ps, g_cs, nrm, n_bs, n_ps,
+                        n_cs, idx, K, B, N, nullptr, false, nrm_out, no_bs, no_ps, no_cs, step_size, eps, stream);
+}
+
+extern "C" int pc3d_si_step_ragged_f32(float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs,
+                                       const float* ori, int64_t o_bs, int64_t o_ps, int64_t o_cs,
+                                       const float* g, int64_t g_bs, int64_t g_ps, int64_t g_cs,
+                                       const float* nrm, int64_t n_bs, int64_t n_ps, int64_t n_cs,
+                                       const int32_t* idx, int K, int B, int N, const int32_t* lengths,
+                                       float* nrm_out, int64_t no_bs, int64_t no_ps, int64_t no_cs,
+                                       double step_size, double eps, void* stream) {
+  return si_step_launch("pc3d_si_step_ragged_f32", x, x_bs, x_ps, x_cs, ori, o_bs, o_ps, o_cs, g, g_bs, g_ps, g_cs, nrm, n_bs,
+                        n_ps, n_cs, idx, K, B, N, lengths, true, nrm_out, no_bs, no_ps, no_cs, step_size, eps, stream);
 }
 
 extern "C" int pc3d_query_step_f32(const float* logp, int k, const int64_t* label, int top,

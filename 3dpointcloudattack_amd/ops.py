@@ -4085,22 +4085,40 @@ def _knn_lists(idx, B, N, who):
     return idx.shape[2]
 
 
-def pca_normal(pts, idx, cf=False):
+def _si_ragged(who, dense, lengths, x):
+    """(entry name, the extra argument) of a shape-invariant kernel's call: the dense entry, or its _ragged twin with the
+    lengths pointer. The lengths are checked first, whatever else is given: against x's batch size and device alone."""
+    if lengths is None:
+        return dense, ()
+    if not isinstance(x, torch.Tensor) or x.dim() != 3:
+        raise ValueError(f"{who}: lengths go with a [B,N,3] or [B,3,N] tensor")
+    return dense[:-len("f32")] + "ragged_f32", (_lengths_arg(who, lengths, x.shape[0], x.device),)
+
+
+def pca_normal(pts, idx, cf=False, lengths=None):
     """Normals of pts [B,N,3] ([B,3,N] with cf), in pts' layout, from neighbour lists idx [B,N,K] int32 that include
     the point itself: the smallest eigenvector of the covariance of the K listed points about their mean (see
-    pc3d_pca_normal_f32: sign rule, (0,0,1) for degenerate lists, NaN for an index outside [0,N))."""
+    pc3d_pca_normal_f32: sign rule, (0,0,1) for degenerate lists, NaN for an index outside [0,N)).
+    lengths (int32 [B] on pts' device, default None: the dense launch, unchanged): cloud b counts L = lengths[b] points
+    (pc3d_pca_normal_ragged_f32). Read: rows < L of pts and idx only, an index >= L giving NaN. Written: every row — rows < L
+    with the bits of the cloud alone at N = L, rows >= L with row 0's normal."""
+    name, extra = _si_ragged("pca_normal", "pc3d_pca_normal_f32", lengths, pts)
     p, bs, ps, cs, B, N = _pts(pts, cf, "pts")
     K = _knn_lists(idx, B, N, "pca_normal")
     out = torch.empty((B, 3, N) if cf else (B, N, 3), dtype=torch.float32, device=pts.device)
     with torch.cuda.device(pts.device):
-        _lib.call("pc3d_pca_normal_f32", p, bs, ps, cs, idx.data_ptr(), B, N, K, *_pts(out, cf, "out")[:4], _stream())
+        _lib.call(name, p, bs, ps, cs, idx.data_ptr(), B, N, K, *extra, *_pts(out, cf, "out")[:4], _stream())
     return out
 
 
-def si_frame(x, nrm=None, idx=None, nrm_out=None, cf=True, out=None):
+def si_frame(x, nrm=None, idx=None, nrm_out=None, cf=True, out=None, lengths=None):
     """The cloud the shape-invariant attack shows its victim: U^T (U (x + t)) - t per point (pc3d_si_frame_f32), a new
     tensor (or `out`) in x's layout [B,3,N] ([B,N,3] with cf=False). Exactly one of nrm (normals) and idx (int32 [B,N,K]
-    neighbour lists, self included) is given; nrm_out receives the normals used."""
+    neighbour lists, self included) is given; nrm_out receives the normals used.
+    lengths (int32 [B] on x's device, default None: the dense launch, unchanged): cloud b counts L = lengths[b] points
+    (pc3d_si_frame_ragged_f32). Read: rows < L of x, nrm and idx only. Written: every row of out and nrm_out — rows < L with
+    the bits of the cloud alone at N = L, rows >= L bit-equal to the tensor's own row 0."""
+    name, extra = _si_ragged("si_frame", "pc3d_si_frame_f32", lengths, x)
     xp, xbs, xps, xcs, B, N = _pts(x, cf, "x")
     if (nrm is None) == (idx is None):
         raise ValueError("si_frame: give exactly one of nrm (normals) and idx (neighbour lists)")
@@ -4117,15 +4135,20 @@ def si_frame(x, nrm=None, idx=None, nrm_out=None, cf=True, out=None):
         views.append(v[:4])
     K = _knn_lists(idx, B, N, "si_frame") if idx is not None else 0
     with torch.cuda.device(x.device):
-        _lib.call("pc3d_si_frame_f32", xp, xbs, xps, xcs, *views[0], _ptr(idx), K, B, N, *views[1], *views[2], _stream())
+        _lib.call(name, xp, xbs, xps, xcs, *views[0], _ptr(idx), K, B, N, *extra, *views[1], *views[2], _stream())
     return out
 
 
-def si_step(x, ori, g, step_size, eps, nrm=None, idx=None, nrm_out=None, cf=True):
+def si_step(x, ori, g, step_size, eps, nrm=None, idx=None, nrm_out=None, cf=True, lengths=None):
     """One shape-invariant I-FGM step, IN PLACE on x [B,3,N] ([B,N,3] with cf=False; ori, g, nrm, nrm_out share the
     layout), one launch (see pc3d_si_step_f32). g = the victim's gradient at si_frame(x). Exactly one of nrm (the normals) and idx (int32 [B,N,K]
     neighbour lists, self included: the normals are computed as pca_normal does) is given; nrm_out receives the
-    normals used. Returns x."""
+    normals used. Returns x.
+    lengths (int32 [B] on x's device, default None: the dense launch, unchanged): cloud b counts L = lengths[b] points
+    (pc3d_si_step_ragged_f32). Read: rows < L of x, ori, g, nrm and idx only; the cloud's gradient norm sums over them.
+    Written: rows < L of x (and nrm_out) with the bits of the cloud alone at N = L, rows >= L of x with the NEW row 0 and of
+    nrm_out with row 0's normal."""
+    name, extra = _si_ragged("si_step", "pc3d_si_step_f32", lengths, x)
     xp, xbs, xps, xcs, B, N = _pts(x, cf, "x")
     if (nrm is None) == (idx is None):
         raise ValueError("si_step: give exactly one of nrm (normals) and idx (neighbour lists)")
@@ -4140,7 +4163,7 @@ def si_step(x, ori, g, step_size, eps, nrm=None, idx=None, nrm_out=None, cf=True
         views.append(v[:4])
     K = _knn_lists(idx, B, N, "si_step") if idx is not None else 0
     with torch.cuda.device(x.device):
-        _lib.call("pc3d_si_step_f32", xp, xbs, xps, xcs, *views[0], *views[1], *views[2], _ptr(idx), K, B, N, *views[3],
+        _lib.call(name, xp, xbs, xps, xcs, *views[0], *views[1], *views[2], _ptr(idx), K, B, N, *extra, *views[3],
                   float(step_size), float(eps), _stream())
     return x
 

@@ -1477,6 +1477,35 @@ int pc3d_si_step_f32(float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs,
                      const int32_t* idx, int K, int B, int N,
                      float* nrm_out, int64_t no_bs, int64_t no_ps, int64_t no_cs,
                      double step_size, double eps, void* stream);
+/* The three entries above on a batch of clouds of different sizes: cloud b counts L = clamp(lengths[b], 1, N) points
+ * (lengths int32 [B] on the device, read by the kernel as data, never NULL) and N is the capacity, the row stride of every
+ * buffer. The kernels are the second instantiations of the dense bodies; the argument checks, the aliasing rules and the
+ * limits are the dense entries' (the LDS stage of pc3d_si_step_ragged_f32 is decided by N, not by L, and its step keeps
+ * sqrt(3 * 1024) whatever L is). The contract of all three: rows < L have the bits of the dense entry on that cloud alone
+ * at N = L, and the rows >= L of every output are copies of the output's row 0.
+ *   pc3d_pca_normal_ragged_f32   a neighbour index is checked against L (an entry >= L is never dereferenced: NaN for
+ *                                that point). Rows >= L of x and idx are never read.
+ *   pc3d_si_frame_ragged_f32     rows >= L of xe and of nrm_out (when given) repeat row 0's arithmetic, so they equal row 0
+ *                                in every bit: what a victim whose pooling ignores copies of a point must be shown. Rows
+ *                                >= L of x, nrm and idx are never read.
+ *   pc3d_si_step_ragged_f32      the cloud's sum of g'^2 runs over n < L in the dense order; rows >= L of x receive the NEW
+ *                                row 0 and rows >= L of nrm_out row 0's normal, in the same launch (handed over through
+ *                                LDS: row 0 is rewritten in place). Rows >= L of ori, g, nrm and idx are never read. */
+int pc3d_pca_normal_ragged_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs, const int32_t* idx, int B, int N,
+                               int K, const int32_t* lengths, float* out, int64_t o_bs, int64_t o_ps, int64_t o_cs,
+                               void* stream);
+int pc3d_si_frame_ragged_f32(const float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs,
+                             const float* nrm, int64_t n_bs, int64_t n_ps, int64_t n_cs,
+                             const int32_t* idx, int K, int B, int N, const int32_t* lengths,
+                             float* xe, int64_t e_bs, int64_t e_ps, int64_t e_cs,
+                             float* nrm_out, int64_t no_bs, int64_t no_ps, int64_t no_cs, void* stream);
+int pc3d_si_step_ragged_f32(float* x, int64_t x_bs, int64_t x_ps, int64_t x_cs,
+                            const float* ori, int64_t o_bs, int64_t o_ps, int64_t o_cs,
+                            const float* g, int64_t g_bs, int64_t g_ps, int64_t g_cs,
+                            const float* nrm, int64_t n_bs, int64_t n_ps, int64_t n_cs,
+                            const int32_t* idx, int K, int B, int N, const int32_t* lengths,
+                            float* nrm_out, int64_t no_bs, int64_t no_ps, int64_t no_cs,
+                            double step_size, double eps, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * SI-Adv's query attacks (simba_attack, simbapp_attack, shape_invariant_query_attack, SIadv_attack.py:343-624) as one
