@@ -151,6 +151,11 @@ SIGNATURES = {
     "pc3d_eot_update_f32": [_P] * 5 + [_I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _I] + [_P] * 8 + [_I, _P, _P, _I]
     + [_D, _D, _D, _D, _I, _F, _P, _I, _P],
     "pc3d_eot_draw_f32": [_L, _L, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    # clouds of different sizes in one batch: lengths [B] behind the sizes (the draw gains B as well: a table per cloud)
+    "pc3d_eot_prepare_ragged_f32": [_P, _P, _I, _I, _P, _I, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P],
+    "pc3d_eot_update_ragged_f32": [_P] * 5 + [_I, _I, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P, _I] + [_P] * 8 + [_I, _P, _P, _I]
+    + [_D, _D, _D, _D, _I, _F, _P, _I, _P],
+    "pc3d_eot_draw_ragged_f32": [_L, _L, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "pc3d_geoa3_update_f32": [_P] * 6 + [_I, _I, _I] + [_P] * 9 + [_I, _I, _F, _F, _F, _F, _P, _P, _I, _P, _P, _P, _I]
     + [_P] * 6 + [_D, _D, _D, _F, _P, _P, _P, _P],
     "pc3d_geoa3_update_ragged_f32": [_P] * 6 + [_I, _I, _I] + [_P] * 9 + [_I, _I, _F, _F, _F, _F, _P, _P, _I, _P, _P, _P, _I]

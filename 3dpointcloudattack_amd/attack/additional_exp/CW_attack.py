@@ -23,6 +23,10 @@ iterate and its ten views between pc3d_eot_prepare_f32 and pc3d_eot_update_f32 (
 without autograd; the rotations and resampling indices are still drawn on the host, in the same order, a block of
 iterations ahead — or, with ``device_rng=True``, on the device by pc3d_eot_draw_f32 (a counter-based stream of its own, NOT
 draw-for-draw comparable with the reference: see ``CW.__init__``).
+
+``attack(..., lengths=...)``: clouds of different sizes in one batch on that device loop — the lengths reach
+the three kernels of csrc/eot.hip through their ``_ragged_f32`` twins and, with resampling, the per-cloud tables the device
+draws; every cloud comes out as from a run of that cloud alone.
 """
 import random
 import time
@@ -33,6 +37,7 @@ import torch.optim as optim
 
 from ... import graphed as _graphed
 from ... import ops
+from ... import ragged as _ragged
 from ..CW.CW_attack import bisect_weights
 
 
@@ -106,7 +111,7 @@ class CW:
                  init_weight=10., max_weight=80., binary_step=10, num_iter=500, whether_target=True, whether_1d=True,
                  whether_renormalization=False,
                  whether_3Dtransform=False, whether_resample=False, device=None, verbose=False, graph=True,
-                 device_loop=False, device_rng=False, seed=None):
+                 device_loop=False, device_rng=False, seed=None, sample_seeds=None, global_batch=None):
         """`device_loop=True` runs the iteration as a captured chain of own kernels around ONE stacked victim pass when
         the victim, the functors and the cloud size allow it (_device_loop_plan), and silently the usual path otherwise;
         `last_path` says which one the last attack() took: "device_loop" or "autograd".
@@ -118,7 +123,13 @@ class CW:
         `bs` has draw index `draw_base + bs * num_iter + it`; `draw_base` (public, 0 at construction) advances by
         binary_step * num_iter at the end of every device-drawn attack(), and setting it back reproduces a run.
         `seed=None` takes torch.initial_seed() at the first use. It takes effect only where the device loop runs with
-        views; `last_draws` says what the last attack() did: "device", "host" or None (no views)."""
+        views; `last_draws` says what the last attack() did: "device", "host" or None (no views).
+
+        `sample_seeds` (one int per sample of the batch handed to attack(); None: one batch-shaped draw from torch's global
+        CPU generator, as the reference) draws each sample's 1e-7 start noise from its own CPU generator, and `global_batch`
+        (None: the batch handed to attack()) is the size of the batch whose `.mean()` the losses belong to — it takes effect
+        in the device loop; both as in attack/CW/CW_attack.py: with them a sample's trajectory does not depend on the batch
+        it is attacked in."""
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.model = model.to(self.device)
         self.model.eval()
@@ -141,6 +152,8 @@ class CW:
         self.device_loop = device_loop
         self.device_rng = bool(device_rng)
         self.seed = seed
+        self.sample_seeds = sample_seeds
+        self.global_batch = global_batch
         self.draw_base = 0
         self.last_path = None
         self.last_draws = None                 # who drew the last attack()'s views: "device", "host" or None (no views)
@@ -154,11 +167,13 @@ class CW:
     EOT_VIEWS = 10       # :193 — the expectation's ten views
     LOOP_BLOCK = 16      # iterations per graph replay = per block of host draws; the remainder replays single iterations
 
-    def _device_loop_plan(self, B, K):
+    def _device_loop_plan(self, B, K, ragged=False):
         """The constants of the device loop when it applies, else None: a GPU victim with fused_attack_grad (the two
         PointNetCls variants), an AdvLossAdapter around functors the CW loop maps to ops.LOSS_KINDS, ChamferDist('adv2ori')
         or L2Dist — inside PerSampleDist, or bare at B = 1 where the batch mean is the identity — and a cloud the kernels
-        hold. ChamferkNNDist and arbitrary callables take the autograd path."""
+        hold. ChamferkNNDist and arbitrary callables take the autograd path. `ragged`: the plan of a batch of clouds of
+        different sizes (the flag enters the loop's key; the lengths never do). A `global_batch` adds the entry
+        "batch_mean" and sets the tail's scale; without one the plan is what it always was."""
         from ..CW.CW_utils import adv_utils as _adv_utils
         from ..CW.CW_utils import dist_utils as _dist_utils
         victim = _graphed.unwrap(self.model)
@@ -185,9 +200,23 @@ class CW:
             return None
         E = self.EOT_VIEWS if self.whether_3Dtransform else 0
         renorm = bool(self.whether_renormalization)
-        return dict(victim=victim, kind=kind, dist_kind=dist_kind, E=E, renorm=renorm,
+        G = int(self.global_batch) if self.global_batch else B
+        plan = dict(victim=victim, kind=kind, dist_kind=dist_kind, E=E, renorm=renorm,
                     resample=bool(E and self.whether_resample), prepare=bool(E or renorm), one_d=bool(self.whether_1d),
-                    untarget=not self.whether_target, box=float(self.box_constraint), scale=1.0 / ((E if E else 1) * B))
+                    untarget=not self.whether_target, box=float(self.box_constraint), scale=1.0 / ((E if E else 1) * G))
+        if self.global_batch:
+            plan["batch_mean"] = G
+        if ragged:
+            plan["ragged"] = True
+        return plan
+
+    def _loop_key(self, plan, B, K):
+        """The key of the loop of this shape, these constants, this kernel flavour and these weights. A ragged plan carries
+        its flag, never the lengths: they are device data of the launches."""
+        device_draws = bool(self.device_rng and plan["E"])
+        return _graphed.loop_key(plan["victim"], self.device, B, K, float(self.attack_lr), device_draws,
+                                 int(self.seed) if device_draws else None, bool(self.graph),
+                                 tuple(sorted((n, v) for n, v in plan.items() if n != "victim")))
 
     def _device_loop_state(self, plan, B, K):
         """The loop of this shape, these constants, this kernel flavour and these weights: its buffers (static: the graphs
@@ -196,8 +225,7 @@ class CW:
         device_draws = bool(self.device_rng and plan["E"])
         if device_draws and self.seed is None:
             self.seed = int(torch.initial_seed()) & 0x7FFFFFFFFFFFFFFF
-        key = _graphed.loop_key(victim, dev, B, K, float(lr), device_draws, int(self.seed) if device_draws else None,
-                                bool(self.graph), tuple(sorted((n, v) for n, v in plan.items() if n != "victim")))
+        key = self._loop_key(plan, B, K)
         loop = self._loop_cache.get(key)
         if loop is not None:
             return loop
@@ -211,8 +239,10 @@ class CW:
         # the per-iteration tables: T = two blocks of rows on the device, two pinned blocks on the host (none of those when
         # the device draws)
         rot = torch.zeros((T, E, 3, 3), **f32) if E else None
-        idx = torch.zeros((T, E, K), **i32) if plan["resample"] else None
-        inv = torch.zeros((T, E, K, 2), **i32) if plan["resample"] else None
+        ragged = bool(plan.get("ragged"))
+        # (ragged: a table per cloud, a cloud of another length draws other columns; attack() has refused host draws)
+        idx = torch.zeros((T, E, B, K) if ragged else (T, E, K), **i32) if plan["resample"] else None
+        inv = torch.zeros((T, E, B, K, 2) if ragged else (T, E, K, 2), **i32) if plan["resample"] else None
         host_draws = bool(E) and not device_draws
         rot_pin = torch.zeros((2, LB, E, 3, 3), dtype=torch.float32).pin_memory() if host_draws else None
         idx_pin = torch.zeros((2, LB, E, K), dtype=torch.int32).pin_memory() if host_draws and plan["resample"] else None
@@ -225,6 +255,12 @@ class CW:
         w, bestdist, o_bestdist = (torch.zeros((B,), **f32) for _ in range(3))
         bestscore, o_bestscore = (torch.zeros((B,), **i64) for _ in range(2))
         kind, kappa = plan["kind"]
+        # ragged: the lengths the launches read as data, and beside them the same lengths once per slot for the victim's
+        # stacked pass; every call refills all three in place
+        lens, lens_host = _ragged.loop_lengths(B, K, dev) if ragged else (None, None)
+        lens_s = torch.full((S * B,), K, **i32) if ragged else None
+        vkw = _ragged.victim_kwargs(victim, lens_s)
+        batch_mean = plan.get("batch_mean", B)
 
         def body():
             # one chain on one stream: the stacked input, the victim's passes on it (the classifier tail advances the step
@@ -232,20 +268,22 @@ class CW:
             with torch.no_grad():
                 x_in = adv
                 if plan["prepare"]:
-                    ops.eot_prepare(adv, ori, rot, idx, plan["renorm"], step, out=X, stats=stats, arg=arg)
+                    ops.eot_prepare(adv, ori, rot, idx, plan["renorm"], step, out=X, stats=stats, arg=arg, lengths=lens)
                     x_in = X
-                _, _, gx = victim.fused_attack_grad(x_in, goal_s, kind, kappa, pred_out=pred, step=step, scale=plan["scale"])
+                _, _, gx = victim.fused_attack_grad(x_in, goal_s, kind, kappa, pred_out=pred, step=step, scale=plan["scale"],
+                                                    **vkw)
                 if chamfer:
                     ops.nn_search_into(adv, ori, nn_d, nn_idx)
                 ops.eot_update(adv, ori, gx, m, v, step, lr, pred, goal, plan["untarget"], bestdist, bestscore,
                                o_bestdist, o_bestscore, o_bestattack, rot=rot, inv=inv, renorm=plan["renorm"], stats=stats,
-                               arg=arg, input_val=input_val, dist_kind=plan["dist_kind"], w=w, nn_idx=nn_idx, batch_mean=B,
-                               one_d=plan["one_d"], box=plan["box"])
+                               arg=arg, input_val=input_val, dist_kind=plan["dist_kind"], w=w, nn_idx=nn_idx,
+                               batch_mean=batch_mean, one_d=plan["one_d"], box=plan["box"], lengths=lens)
 
         bufs = dict(plan=plan, device_draws=device_draws, adv=adv, ori=ori, m=m, v=v, o_bestattack=o_bestattack,
                     input_val=input_val, X=X, stats=stats, arg=arg, rot=rot, idx=idx, inv=inv, rot_pin=rot_pin, idx_pin=idx_pin,
                     inv_pin=inv_pin, nn_d=nn_d, nn_idx=nn_idx, step=step, pred=pred, goal_s=goal_s, goal=goal, w=w,
                     bestdist=bestdist, o_bestdist=o_bestdist, bestscore=bestscore, o_bestscore=o_bestscore,
+                    lens=lens, lens_host=lens_host, lens_s=lens_s,
                     uploaded=[torch.cuda.Event(), torch.cuda.Event()])
         return self._loop_cache.put(key, _graphed.DeviceLoop(key, dev, owners=(victim,), counts=(1, self.LOOP_BLOCK),
                                                              warmup=2, body=body, bufs=bufs))
@@ -283,7 +321,9 @@ class CW:
         while left > 0:
             cnt, half = min(LB, left), n % 2
             if c["device_draws"]:
-                ops.eot_draw(self.seed, n0, (half * LB, cnt), c["rot"], c["idx"], c["inv"])
+                # (the rotations do not depend on a length: without resampling a ragged loop takes the dense launch)
+                ops.eot_draw(self.seed, n0, (half * LB, cnt), c["rot"], c["idx"], c["inv"],
+                             lengths=c["lens"] if c["idx"] is not None else None)
                 n0 += cnt
             elif E:
                 rows = slice(half * LB, half * LB + cnt)
@@ -298,11 +338,14 @@ class CW:
                 c["uploaded"][n % 2].synchronize()      # the pinned block about to be rewritten has been read
                 self._draw_block(c, n % 2, min(LB, left), K)
 
-    def _attack_device_loop(self, plan, adv_data, ori_data, goal, B, K):
+    def _attack_device_loop(self, plan, adv_data, ori_data, goal, B, K, lens=None):
         dev = self.device
         loop = self._device_loop_state(plan, B, K)
         c = loop.bufs
         S = 1 + plan["E"]
+        if lens is not None:
+            _ragged.set_loop_lengths(c, lens)
+            c["lens_s"].copy_(c["lens"].repeat(S))
         lower_bound = np.zeros((B,))
         upper_bound = np.ones((B,)) * self.max_weight
         current_weight = np.ones((B,)) * self.init_weight
@@ -344,15 +387,53 @@ class CW:
             print('Successfully attack {}/{}   pred: {}'.format(success_num, B, c["pred"][:B].tolist()))
         return (o_bestdist.cpu().numpy(), o_bestattack.double().cpu().numpy().transpose((0, 2, 1)), success_num)
 
-    def attack(self, data, target=torch.Tensor([0]), origin_label=torch.Tensor([105])):
+    def _ragged_lengths(self, data, lengths):
+        """lengths as int64 numpy [B] after every check of the ragged pass, or ValueError naming what does not fit, before
+        any launch: there is no silent fall-back, since a pass that does not know the lengths would centre, resample and
+        average over the padding."""
+        who = "CW.attack(lengths=...)"
+        if not self.device_loop:
+            raise ValueError(f"{who}: device_loop=False has no ragged pass (the autograd path does not know lengths)")
+        victim = _graphed.unwrap(self.model)
+        if not getattr(victim, "pad_invariant", False) or not hasattr(victim, "fused_attack_grad"):
+            raise ValueError(f"{who}: the victim {type(victim).__name__} does not declare pad_invariant or lacks the fused "
+                             "entry points (fused_attack_grad)")
+        if self.whether_3Dtransform and self.whether_resample and not self.device_rng:
+            raise ValueError(f"{who}: whether_resample needs device_rng=True (per-cloud tables drawn on the host would consume "
+                             "`random` in an order the reference does not define)")
+        if data.dim() != 3 or data.shape[2] != 3:
+            raise ValueError(f"{who}: data must be [B, Kmax, 3], got {tuple(data.shape)}")
+        B, K = data.shape[:2]
+        if K > ops.EOT_MAX_POINTS:
+            raise ValueError(f"{who}: Kmax={K} exceeds EOT_MAX_POINTS={ops.EOT_MAX_POINTS}")
+        lens = _ragged.check_lengths(who, lengths, B, K, low=1)
+        if self._device_loop_plan(B, K, ragged=True) is None:
+            raise ValueError(f"{who}: no device-loop plan (it needs a GPU victim, an AdvLossAdapter around this package's "
+                             "adversarial functors and PerSampleDist around ChamferDist('adv2ori') or L2Dist)")
+        return lens
+
+    def attack(self, data, target=torch.Tensor([0]), origin_label=torch.Tensor([105]), lengths=None):
         """data [B,K,3] (or [B,3,K]); target [B] (targeted) / origin_label [B] (untargeted).
-        Returns (o_bestdist [B] float64, o_bestattack [B,K,3] float64, success_num) like the reference (:321)."""
+        Returns (o_bestdist [B] float64, o_bestattack [B,K,3] float64, success_num) like the reference (:321).
+
+        lengths (default None: every cloud has K points, nothing changes): a sequence, array or tensor of B ints,
+        1 <= lengths[b] <= Kmax = data.shape[1], the sizes of a batch [B,Kmax,3] of clouds of different sizes; rows of data at
+        and beyond a cloud's length are ignored (dataset.cloud_io.stack_ragged builds such a batch, unstack_ragged takes the
+        result apart). It needs device_loop=True with a plan, a pad_invariant victim and, for whether_resample,
+        device_rng=True; anything else raises ValueError before any launch. With `sample_seeds` and `global_batch` = B every
+        cloud is attacked exactly as in a run of that cloud alone (same seed, draw_base and global_batch). In the returned
+        o_bestattack [B,Kmax,3], rows at and beyond a cloud's length hold that cloud's row 0."""
         dev = self.device
+        lens = None if lengths is None else self._ragged_lengths(data, lengths)
         if data.shape[2] == 3:
             data = data.transpose(1, 2).contiguous()
         B, _, K = data.shape
         data = data.float().to(dev).detach()
         ori_data = data.clone().detach()
+        lens_dev = None
+        if lens is not None:
+            lens_dev = torch.from_numpy(lens.astype(np.int32)).to(dev)
+            ops.pad_ragged(ori_data, lens_dev)
         target = target.long().to(dev).detach().view(-1)
         origin_label = origin_label.detach().to(dev).long().view(-1)
         if target.numel() == 1 and B > 1:
@@ -375,15 +456,26 @@ class CW:
             print('clean pred: {}  goal: {}'.format(pred.tolist(), goal.tolist()))
 
         # ONE start point for the whole search: later binary steps continue from the previous step's iterate (:88-93)
-        adv_data = ori_data.clone().detach() + torch.randn((B, 3, K)).to(dev) * 1e-7
-        plan = self._device_loop_plan(B, K) if self.device_loop else None
+        if self.sample_seeds is None:
+            # (ragged: the batch-shaped draw stays, its padding columns are overwritten below; a cloud's noise then depends
+            # on the batch it is in, so this mode is not comparable cloud by cloud with runs alone)
+            noise = torch.randn((B, 3, K))
+        else:
+            assert len(self.sample_seeds) == B, "sample_seeds needs one seed per sample"
+            gens = [torch.Generator().manual_seed(int(sd)) for sd in self.sample_seeds]
+            noise = _ragged.per_cloud_draw(B, 3, K, [K] * B if lens is None else lens,
+                                           lambda b, n: torch.randn((3, n), generator=gens[b]))
+        adv_data = ori_data.clone().detach() + noise.to(dev) * 1e-7
+        if lens is not None:
+            ops.pad_ragged(adv_data, lens_dev)
+        plan = self._device_loop_plan(B, K, ragged=lens is not None) if self.device_loop else None
         self.last_path = "device_loop" if plan is not None else "autograd"
         if plan is not None:
             self.last_draws = ("device" if self.device_rng else "host") if plan["E"] else None
         else:
             self.last_draws = "host" if self.whether_3Dtransform else None
         if plan is not None:
-            return self._attack_device_loop(plan, adv_data, ori_data, goal, B, K)
+            return self._attack_device_loop(plan, adv_data, ori_data, goal, B, K, lens)
         input_val = adv_data.detach().clone()
         for binary_step in range(self.binary_step):
             adv_data.requires_grad_()

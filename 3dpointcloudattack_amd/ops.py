@@ -1449,18 +1449,22 @@ def _eot_sizes(who, adv, rot):
     return B, K, T, E
 
 
-def eot_prepare(adv, ori, rot=None, idx=None, renorm=False, step=0, out=None, stats=None, arg=None):
+def eot_prepare(adv, ori, rot=None, idx=None, renorm=False, step=0, out=None, stats=None, arg=None, lengths=None):
     """The stacked victim input of one additional-experiments CW iteration (pc3d_eot_prepare_f32): X [(1+E) B,3,K],
     slot-major, slot 0 the iterate and slot e >= 1 its e-th rotated view rot[step mod T, e-1] ori + (adv - ori), each
     renormalised with `renorm`, the views resampled through idx [T,E,K] (int32) when given. rot None: no views (E = 0).
-    `step` (int32 device word or int) selects the table row. Returns (X, stats [(1+E) B,4], arg [(1+E) B])."""
+    `step` (int32 device word or int) selects the table row. Returns (X, stats [(1+E) B,4], arg [(1+E) B]).
+    lengths (int32 [B] on the device; None: the dense launch): clouds of different sizes (pc3d_eot_prepare_ragged_f32) — K is
+    the capacity, cloud b counts lengths[b] points, idx is [T,E,B,K] (ops.eot_draw(lengths=...)), and the columns of X at and
+    beyond a length are copies of their slot's column 0."""
     who = "eot_prepare"
     B, K, T, E = _eot_sizes(who, adv, rot)
     dev = adv.device
+    lens = None if lengths is None else _lengths_arg(who, lengths, B, dev)
     _eot_dense(who, ori, "ori", adv.shape, torch.float32, dev)
     if idx is not None and rot is None:
         raise ValueError("eot_prepare: resampling needs views (rot)")
-    _eot_dense(who, idx, "idx", (T, E, K), torch.int32, dev)
+    _eot_dense(who, idx, "idx", (T, E, K) if lens is None else (T, E, B, K), torch.int32, dev)
     S = 1 + E
     X = out if out is not None else torch.empty((S * B, 3, K), dtype=torch.float32, device=dev)
     stats = stats if stats is not None else torch.empty((S * B, 4), dtype=torch.float32, device=dev)
@@ -1469,25 +1473,33 @@ def eot_prepare(adv, ori, rot=None, idx=None, renorm=False, step=0, out=None, st
     _eot_dense(who, stats, "stats", (S * B, 4), torch.float32, dev)
     _eot_dense(who, arg, "arg", (S * B,), torch.int32, dev)
     step_dev, step_host = _eot_step(who, step, dev)
+    tail = (E, T, _ptr(rot), _ptr(idx), 1 if renorm else 0, step_dev, step_host, X.data_ptr(), stats.data_ptr(), arg.data_ptr())
     with torch.cuda.device(dev):
-        _lib.call("pc3d_eot_prepare_f32", adv.data_ptr(), ori.data_ptr(), B, K, E, T, _ptr(rot), _ptr(idx),
-                  1 if renorm else 0, step_dev, step_host, X.data_ptr(), stats.data_ptr(), arg.data_ptr(), _stream())
+        if lens is None:
+            _lib.call("pc3d_eot_prepare_f32", adv.data_ptr(), ori.data_ptr(), B, K, *tail, _stream())
+        else:
+            _lib.call("pc3d_eot_prepare_ragged_f32", adv.data_ptr(), ori.data_ptr(), B, K, lens, *tail, _stream())
     return X, stats, arg
 
 
 def eot_update(adv, ori, gx, m, v, step, lr, pred, goal, untarget, bestdist, bestscore, o_bestdist, o_bestscore, o_bestattack,
                rot=None, inv=None, renorm=False, stats=None, arg=None, input_val=None, dist_val=None, dist_kind="chamfer",
-               w=None, nn_idx=None, batch_mean=None, one_d=True, box=0.4, betas=(0.9, 0.999), eps=1e-8, g_out=None):
+               w=None, nn_idx=None, batch_mean=None, one_d=True, box=0.4, betas=(0.9, 0.999), eps=1e-8, g_out=None,
+               lengths=None):
     """The rest of the iteration as one launch (pc3d_eot_update_f32): the record block on the iterate as it stands, the
     gradient of the adversarial term from the stacked pass's input gradient gx [(1+E) B,3,K] (views 1 .. E through the
     inverse resampling table inv [T,E,K,2] and, with `renorm`, through the renormalisation on eot_prepare's stats / arg),
     the gradient of the distance term (dist_kind in EOT_DIST_KINDS; w [B] float32; nn_idx [B,K] int32 for Chamfer;
     batch_mean: the batch size of the loss mean, default B), Adam and, with one_d, the z-only box. adv / m / v and the
     best-so-far buffers are updated IN PLACE; `step` (int32 device word or int >= 1) is Adam's step number, the tables are
-    read at row (step - 1) mod T. g_out [B,3,K] (optional) receives the total gradient Adam consumes."""
+    read at row (step - 1) mod T. g_out [B,3,K] (optional) receives the total gradient Adam consumes.
+    lengths (int32 [B] on the device; None: the dense launch): clouds of different sizes (pc3d_eot_update_ragged_f32) — every
+    sum, mean and divisor is the cloud's own length, inv is [T,E,B,K,2], the rows of m / v behind a length stay, and adv,
+    input_val and (where copied) o_bestattack leave as padded clouds (row 0 behind the length)."""
     who = "eot_update"
     B, K, T, E = _eot_sizes(who, adv, rot)
     dev = adv.device
+    lens = None if lengths is None else _lengths_arg(who, lengths, B, dev)
     f32, i32, i64 = torch.float32, torch.int32, torch.int64
     for nm, t in (("ori", ori), ("m", m), ("v", v), ("o_bestattack", o_bestattack), ("input_val", input_val),
                   ("g_out", g_out)):
@@ -1496,7 +1508,7 @@ def eot_update(adv, ori, gx, m, v, step, lr, pred, goal, untarget, bestdist, bes
     _eot_dense(who, gx, "gx", (S * B, 3, K), f32, dev)
     if inv is not None and rot is None:
         raise ValueError("eot_update: resampling needs views (rot)")
-    _eot_dense(who, inv, "inv", (T, E, K, 2), i32, dev)
+    _eot_dense(who, inv, "inv", (T, E, K, 2) if lens is None else (T, E, B, K, 2), i32, dev)
     if renorm and (stats is None or arg is None):
         raise ValueError("eot_update: renorm needs eot_prepare's stats and arg")
     _eot_dense(who, stats, "stats", (S * B, 4), f32, dev)
@@ -1512,22 +1524,29 @@ def eot_update(adv, ori, gx, m, v, step, lr, pred, goal, untarget, bestdist, bes
         raise ValueError("eot_update: the Chamfer term needs nn_idx")
     _eot_dense(who, nn_idx, "nn_idx", (B, K), i32, dev)
     step_dev, step_host = _eot_step(who, step, dev)
+    head = (adv.data_ptr(), ori.data_ptr(), gx.data_ptr(), m.data_ptr(), v.data_ptr(), B, K)
+    tail = (E, T, _ptr(rot), _ptr(inv), 1 if renorm else 0, _ptr(stats), _ptr(arg), pred.data_ptr(), goal.data_ptr(),
+            1 if untarget else 0, bestdist.data_ptr(), bestscore.data_ptr(), o_bestdist.data_ptr(),
+            o_bestscore.data_ptr(), o_bestattack.data_ptr(), _ptr(input_val), _ptr(dist_val), _ptr(g_out), dk, _ptr(w),
+            _ptr(nn_idx),
+            int(batch_mean if batch_mean is not None else B), float(lr), float(betas[0]), float(betas[1]), float(eps),
+            1 if one_d else 0, float(box), step_dev, step_host)
     with torch.cuda.device(dev):
-        _lib.call("pc3d_eot_update_f32", adv.data_ptr(), ori.data_ptr(), gx.data_ptr(), m.data_ptr(), v.data_ptr(), B, K, E, T,
-                  _ptr(rot), _ptr(inv), 1 if renorm else 0, _ptr(stats), _ptr(arg), pred.data_ptr(), goal.data_ptr(),
-                  1 if untarget else 0, bestdist.data_ptr(), bestscore.data_ptr(), o_bestdist.data_ptr(),
-                  o_bestscore.data_ptr(), o_bestattack.data_ptr(), _ptr(input_val), _ptr(dist_val), _ptr(g_out), dk, _ptr(w),
-                  _ptr(nn_idx),
-                  int(batch_mean if batch_mean is not None else B), float(lr), float(betas[0]), float(betas[1]), float(eps),
-                  1 if one_d else 0, float(box), step_dev, step_host, _stream())
+        if lens is None:
+            _lib.call("pc3d_eot_update_f32", *head, *tail, _stream())
+        else:
+            _lib.call("pc3d_eot_update_ragged_f32", *head, lens, *tail, _stream())
     return adv
 
 
-def eot_draw(seed, n0, rows, rot, idx=None, inv=None):
+def eot_draw(seed, n0, rows, rot, idx=None, inv=None, lengths=None):
     """Draws rows of the loop's tables on the device (pc3d_eot_draw_f32; the stream is stated in include/pc3d.h): for
     `rows` (a slice with step 1, or (row0, cnt)) of rot [T,E,3,3] — and of idx [T,E,K] / inv [T,E,K,2] (int32, given
     together) — the draws of the indices n0, n0 + 1, ... under `seed`; the other rows are left alone. Not the host
-    generators' streams: nothing is consumed from torch's or Python's."""
+    generators' streams: nothing is consumed from torch's or Python's.
+    lengths (int32 [B] on the device; None: the dense launch): a table per cloud (pc3d_eot_draw_ragged_f32) — idx [T,E,B,K]
+    and inv [T,E,B,K,2], cloud b's the dense draw of the same (seed, n, view) at K = lengths[b], entry for entry; behind
+    the length idx repeats the cloud's idx[..., 0] and inv is -1. The rotations stay shared by the batch."""
     who = "eot_draw"
     if not isinstance(rot, torch.Tensor):
         raise TypeError(f"{who}: rot: expected a torch.Tensor, got {type(rot)}")
@@ -1541,13 +1560,24 @@ def eot_draw(seed, n0, rows, rot, idx=None, inv=None):
     _eot_dense(who, rot, "rot", (T, E, 3, 3), torch.float32, dev)
     if (idx is None) != (inv is None):
         raise ValueError(f"{who}: idx and inv are given together or not at all")
-    K = 1
-    if idx is not None:
+    K, B = 1, 0
+    if lengths is not None:
+        if not isinstance(lengths, torch.Tensor) or lengths.dim() != 1:
+            raise ValueError(f"{who}: lengths must be a contiguous int32 [B] tensor on the points' device")
+        B = lengths.shape[0]
+        lens = _lengths_arg(who, lengths, B, dev)
+    if idx is not None and lengths is None:
         if not isinstance(idx, torch.Tensor) or idx.dim() != 3 or not 1 <= idx.shape[2] <= EOT_MAX_POINTS:
             raise ValueError(f"{who}: idx must be [T,E,K] with 1 <= K <= {EOT_MAX_POINTS}")
         K = idx.shape[2]
         _eot_dense(who, idx, "idx", (T, E, K), torch.int32, dev)
         _eot_dense(who, inv, "inv", (T, E, K, 2), torch.int32, dev)
+    elif idx is not None:
+        if not isinstance(idx, torch.Tensor) or idx.dim() != 4 or not 1 <= idx.shape[3] <= EOT_MAX_POINTS:
+            raise ValueError(f"{who}: idx must be [T,E,B,K] with 1 <= K <= {EOT_MAX_POINTS}")
+        K = idx.shape[3]
+        _eot_dense(who, idx, "idx", (T, E, B, K), torch.int32, dev)
+        _eot_dense(who, inv, "inv", (T, E, B, K, 2), torch.int32, dev)
     if isinstance(rows, slice):
         if rows.step not in (None, 1):
             raise ValueError(f"{who}: rows must be consecutive, got {rows}")
@@ -1561,7 +1591,11 @@ def eot_draw(seed, n0, rows, rot, idx=None, inv=None):
     if not -(1 << 63) <= seed < (1 << 63) or not 0 <= n0 or n0 + cnt >= (1 << 63):
         raise ValueError(f"{who}: seed must fit int64 and 0 <= n0 (seed={seed}, n0={n0})")
     with torch.cuda.device(dev):
-        _lib.call("pc3d_eot_draw_f32", seed, n0, row0, cnt, T, E, K, rot.data_ptr(), _ptr(idx), _ptr(inv), _stream())
+        if lengths is None:
+            _lib.call("pc3d_eot_draw_f32", seed, n0, row0, cnt, T, E, K, rot.data_ptr(), _ptr(idx), _ptr(inv), _stream())
+        else:
+            _lib.call("pc3d_eot_draw_ragged_f32", seed, n0, row0, cnt, T, E, B, K, lens, rot.data_ptr(), _ptr(idx), _ptr(inv),
+                      _stream())
     return rot, idx, inv
 
 

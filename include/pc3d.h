@@ -1220,6 +1220,38 @@ int pc3d_eot_update_f32(float* adv, const float* ori, const float* gx, float* m,
 int pc3d_eot_draw_f32(int64_t seed, int64_t n0, int row0, int cnt, int T, int E, int K, float* rot, int32_t* idx,
                       int32_t* inv, void* stream);
 
+/* The three launches for clouds of different sizes in one batch: the dense kernel bodies instantiated a second time, with
+ * lengths [B] int32 (device data, must not be NULL; each value is clamped to [1, K]) behind the sizes. K is the capacity: the
+ * row stride of every tensor, the bound of the cap and of the LDS checks. Cloud b counts L = lengths[b] points; every walk,
+ * divisor (the centroid, both means, the Chamfer term) and index bound (nn_idx, arg, idx, inv) is L, in the dense launch's
+ * thread-to-point mapping and summation order, so the rows < L of every output carry the bits of the dense entry run on
+ * that cloud alone at K = L, and with every length = K the dense launch's bits. No row >= L of adv, ori, gx, m, v is read.
+ *   pc3d_eot_prepare_ragged_f32: idx is [T,E,B,K], a table per cloud, column j < L of slot e >= 1 is column
+ *     idx[t,e-1,b,j] mod L; the columns j >= L of EVERY slot of X are written as copies of that slot's output column 0, so a
+ *     victim that does not know the lengths sees a valid padded cloud.
+ *   pc3d_eot_update_ragged_f32: inv is [T,E,B,K,2]; rows >= L of m, v (and g_out) are left alone; rows >= L of adv take the
+ *     NEW row 0, rows >= L of input_val and (where the overall best is copied) of o_bestattack the row 0 they copy: all
+ *     three leave the launch as padded clouds.
+ *   pc3d_eot_draw_ragged_f32: rot stays [T,E,3,3], shared by the batch; idx [T,E,B,K] and inv [T,E,B,K,2]; one workgroup per
+ *     (row, view, cloud). Cloud b's table is pc3d_eot_draw_f32's of (seed, n, e) at K = L, entry for entry: the keys of the
+ *     columns 1 .. 2L - 1 — the cloud index is not part of a key, so two clouds of one length share their draws, as the
+ *     whole batch does in the dense loop — and since the keys are distinct and the pads sort last, the table is a pure
+ *     function of (seed, n, e, L) whatever sort size or thread count the launch takes from the capacity K. The entries
+ *     j >= L are CHOSEN as idx = the cloud's idx[.., 0] (a valid column, should a reader ignore the length) and inv = -1
+ *     (no column draws a row that does not exist); no kernel reads them. */
+int pc3d_eot_prepare_ragged_f32(const float* adv, const float* ori, int B, int K, const int32_t* lengths, int E, int T,
+                                const float* rot, const int32_t* idx, int renorm, const int32_t* step_dev, int step_host,
+                                float* X, float* stats, int32_t* arg, void* stream);
+int pc3d_eot_update_ragged_f32(float* adv, const float* ori, const float* gx, float* m, float* v, int B, int K,
+                               const int32_t* lengths, int E, int T, const float* rot, const int32_t* inv, int renorm,
+                               const float* stats, const int32_t* arg, const int64_t* pred, const int64_t* goal, int untarget,
+                               float* bestdist, int64_t* bestscore, float* o_bestdist, int64_t* o_bestscore,
+                               float* o_bestattack, float* input_val, float* dist_val, float* g_out, int dist_kind,
+                               const float* w, const int32_t* nn_idx, int batch_mean, double lr, double beta1, double beta2,
+                               double eps, int one_d, float box, const int32_t* step_dev, int step_host, void* stream);
+int pc3d_eot_draw_ragged_f32(int64_t seed, int64_t n0, int row0, int cnt, int T, int E, int B, int K, const int32_t* lengths,
+                             float* rot, int32_t* idx, int32_t* inv, void* stream);
+
 /* GeoA3's iteration after the victim's passes and the searches (attack/GeoA3/GeoA3_attack.py:139-181, :321-351, lp_clip
  * :92-102) as ONE launch, one workgroup per cloud; every point tensor is a contiguous [B,3,N]. In this order:
  *   record   pc3d_geoa3_record_f32's decisions on pred[b] (the loss launch's prediction), target[b], constrain[b] as it
